@@ -4,14 +4,17 @@ losses -> backward -> gradient all-reduce -> Adam) on synthetic data, BASELINE.j
 resnet50, encoder_size=7 (L=49), encoder_dim=512, vocab=6400, T=22, batch 128 images per GPU, R=5 captions
 per image (640 caption sequences per GPU-step).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: either under python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ..., or plainly as above --
      the parent then starts the N ranks itself, before anything touches the GPU, and relays rank 0's JSON line)
 
-Prints ONE JSON line on rank 0.  `roofline` is measured with HIP events inside the library (sat_profile_*): two
-untimed instrumented steps rank the kernel families (`families` / `top`), then the dominant family alone stays
-instrumented inside the timed region; `cpu_baseline` times the CPU oracle (a port of the reference's arithmetic,
-oracle/sat_oracle.py) on a bounded sample on rank 0 at N=1.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times K steps and prints the headline; nothing else runs.
+`--dump-outputs DIR` writes what the last timed step produced as DIR/<name>.npy (dump_outputs).
+`--full` adds everything else, as extra keys of the same line: `roofline` is measured with HIP events inside the library
+(sat_profile_*): two untimed instrumented steps rank the kernel families (`families` / `top`), then the dominant family
+alone stays instrumented inside the timed region; `exchange` (N>1) is the exposed cost of the gradient all-reduce;
+`fp32_parity_mode` and `sub_lines` time other precisions and configurations; `cpu_baseline` times the CPU oracle (a port
+of the reference's arithmetic, oracle/sat_oracle.py) on a bounded sample on rank 0 at N=1.
 """
 import argparse
 import json
@@ -266,6 +269,36 @@ def log(msg):
         print("[bench %7.1fs] %s" % (time.time() - _T0, msg), file=sys.stderr, flush=True)
 
 
+#: elements kept of an array larger than this (a seeded sample, the same indices in every run): 16 MB in float32
+DUMP_SAMPLE = 1 << 22
+
+
+def dump_outputs(path, model, out):
+    """--dump-outputs: what the last timed step hands its caller, as float32 DIR/<name>.npy: the ``loss`` and ``accuracy`` training_step
+    returned, and the state the step leaves behind -- every parameter after the optimizer step (``parameters``), its gradient (``gradients``,
+    zeros where none) and the floating-point buffers (``buffers``: BatchNorm statistics), each concatenated in model order.  An array of more
+    than DUMP_SAMPLE elements keeps DUMP_SAMPLE of them at indices drawn from a fixed seed, so the files stay under 64 MB in all and two
+    builds of the same model can be compared file for file."""
+    import numpy as np
+    import torch
+
+    def flat(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts]) if ts else torch.zeros(0)
+
+    params = list(model.parameters())
+    arrays = {"loss": out["loss"].detach().reshape(1).float(),
+              "accuracy": torch.as_tensor(out["accuracy"]).detach().reshape(1).float(),
+              "parameters": flat(params),
+              "gradients": flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]),
+              "buffers": flat([b for b in model.buffers() if b.is_floating_point()])}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, a.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a[idx.to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy().astype(np.float32))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks as children of this process
     through torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) and pass rank 0's JSON line through.
@@ -301,8 +334,13 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="lengths ~ U{8..T-1} instead of all T-1")
     ap.add_argument("--decoder-tf", default="always", choices=["always", "none"],
                     help="teacher forcing: always (epsilon = 1, the headline) or none (train.py:63 default: argmax feedback after step 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32 parity-mode sub-line and the second CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (profiled untimed steps + event pairs inside the timed region), "
+                         "all-reduce exposure (N>1), fp32 parity mode, the other configurations and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss, accuracy, parameters, gradients and BatchNorm statistics of the last step as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fp32 parity-mode sub-line, the other configurations and the second CPU baseline")
     ap.add_argument("--batch", type=int, default=None, help="override images per GPU")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: the config's global batch (BASELINE.json: C2 128, C3 256, C4 512 images) is split over the ranks "
@@ -311,6 +349,8 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"],
                     help="bf16: bf16 MFMA + bf16 activations (BASELINE configs[1]); fp32: exact fp32 MFMA parity mode")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         return spawn_ranks(args)
@@ -348,25 +388,32 @@ def main():
         B = args.batch
     if args.decoder_tf == "none":
         hp["decoder_tf"] = None
-    torch.manual_seed(42)
-    model = M.SAT(**hp).to(dev).train()
-    model.set_precision(args.precision)
-    broadcast_parameters(model)
-    model.__dict__["_sat_global_step"] = 2          # past encoder_finetune_after: the encoder trains (and is in the optimizer)
-    opt = model.configure_optimizers()
-    sync = GradSync(model, bucket_dtype=torch.bfloat16 if args.bucket_dtype == "bf16" else torch.float32)
+
+    def make():
+        torch.manual_seed(42)
+        model = M.SAT(**hp).to(dev).train()
+        model.set_precision(args.precision)
+        broadcast_parameters(model)
+        model.__dict__["_sat_global_step"] = 2          # past encoder_finetune_after: the encoder trains (and is in the optimizer)
+        opt = model.configure_optimizers()
+        sync = GradSync(model, bucket_dtype=torch.bfloat16 if args.bucket_dtype == "bf16" else torch.float32)
+        return model, opt, sync
+
+    settle = make()                 # the same seed: an identical instance that only brings the clocks up (below)
+    model, opt, sync = make()
     img, caps, lengths = synthetic_batch(B, R, T, hp["vocab_size"], 1234 + rank, args.ragged)
     img, caps = img.to(dev), caps.to(dev)
 
     steps_run = [0]
 
-    def step():
+    def step(inst=None):
+        m, o, s = inst or (model, opt, sync)
         steps_run[0] += 1
-        opt.zero_grad(set_to_none=True)
-        out = model.training_step((img, caps, lengths), 0)
+        o.zero_grad(set_to_none=True)
+        out = m.training_step((img, caps, lengths), 0)
         out["loss"].backward()
-        sync.finish()
-        opt.step()
+        s.finish()
+        o.step()
         return out
 
     def agree(flag):
@@ -378,47 +425,56 @@ def main():
         return flag
 
     log("model built (%s, %d images/GPU); warm-up" % (args.config, B))
-    # W untimed steps, and in any case MIN_WARM_S seconds of them: a GPU coming out of idle (fresh box / fresh process) needs
-    # ~1 s of load before its clocks settle -- with 3 warm-up steps the first 10 timed steps ran 20 % slow (37-42 vs 32 ms)
+    # a GPU coming out of idle (fresh box / fresh process) needs ~1 s of load before its clocks settle -- with 3 warm-up steps the first 10
+    # timed steps ran 20 % slow (37-42 vs 32 ms): MIN_WARM_S seconds of steps on the `settle` instance, then exactly W untimed steps on the
+    # measured one, so that the state the timed steps start from (and what --dump-outputs writes) does not depend on how fast the steps ran
     t_warm = time.perf_counter(); warm_done = 0
-    while agree(warm_done < args.warmup or time.perf_counter() - t_warm < MIN_WARM_S):
-        out = step()
+    while agree(time.perf_counter() - t_warm < MIN_WARM_S):
+        step(settle)
         torch.cuda.synchronize(); warm_done += 1
         if warm_done <= 3 or warm_done % 10 == 0:
             log("warm-up step %d done" % warm_done)
-    # ---- which kernel family dominates: HIP events on the launch stream around every instrumented launch, two untimed steps
+    settle[2].remove()
+    del settle
+    for _ in range(args.warmup):
+        step()
+        torch.cuda.synchronize(); warm_done += 1
+    log("warm-up done: %d steps" % warm_done)
+    # ---- --full: which kernel family dominates: HIP events on the launch stream around every instrumented launch, two untimed steps
     prof_steps = 2
-    _lib.profile_start()
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    entries = sorted(_lib.profile_stop(), key=lambda e: -e["total_ms"])
-    # the same two steps with the encoder's weight gradients back on the main stream: in the product (and in the timed region) they run on a
-    # second HIP stream beside the data-gradient chain, and two kernels sharing the chip stretch each other's durations - these `alone` figures
-    # are each kernel's duration with the chip to itself (kernel quality), the others what actually ran
-    from sat_amd import encoder as _enc
-    side = _enc._WGRAD_STREAM
-    _enc._WGRAD_STREAM = False
-    step(); torch.cuda.synchronize()
-    _lib.profile_start()
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    alone = _lib.profile_stop()
-    _enc._WGRAD_STREAM = side
-    step(); torch.cuda.synchronize()
-    # the contraction core is ONE kernel family launched under ~20 template names (tile shape x operand form): rank it as one entry
-    gemm = [e for e in entries if e["name"].startswith("gemm_")]
-    fams = [e for e in entries if not e["name"].startswith("gemm_")]
-    if gemm:
-        fams.append(dict(name="gemm_*", launches=sum(e["launches"] for e in gemm), total_ms=sum(e["total_ms"] for e in gemm),
-                         flops=sum(e["flops"] for e in gemm), bytes=sum(e["bytes"] for e in gemm)))
-    fams.sort(key=lambda e: -e["total_ms"])
-    dom_name = fams[0]["name"] if fams else None
+    entries, alone, fams, dom_name = [], [], [], None
+    if args.full:
+        _lib.profile_start()
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        entries = sorted(_lib.profile_stop(), key=lambda e: -e["total_ms"])
+        # the same two steps with the encoder's weight gradients back on the main stream: in the product (and in the timed region) they run on a
+        # second HIP stream beside the data-gradient chain, and two kernels sharing the chip stretch each other's durations - these `alone` figures
+        # are each kernel's duration with the chip to itself (kernel quality), the others what actually ran
+        from sat_amd import encoder as _enc
+        side = _enc._WGRAD_STREAM
+        _enc._WGRAD_STREAM = False
+        step(); torch.cuda.synchronize()
+        _lib.profile_start()
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        alone = _lib.profile_stop()
+        _enc._WGRAD_STREAM = side
+        step(); torch.cuda.synchronize()
+        # the contraction core is ONE kernel family launched under ~20 template names (tile shape x operand form): rank it as one entry
+        gemm = [e for e in entries if e["name"].startswith("gemm_")]
+        fams = [e for e in entries if not e["name"].startswith("gemm_")]
+        if gemm:
+            fams.append(dict(name="gemm_*", launches=sum(e["launches"] for e in gemm), total_ms=sum(e["total_ms"] for e in gemm),
+                             flops=sum(e["flops"] for e in gemm), bytes=sum(e["bytes"] for e in gemm)))
+        fams.sort(key=lambda e: -e["total_ms"])
+        dom_name = fams[0]["name"] if fams else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    # ---- the timed region; the dominant family alone stays instrumented inside it (an event pair per launch of that family)
+    # ---- the timed region; with --full the dominant family alone stays instrumented inside it (an event pair per launch of that family)
     if os.environ.get("SAT_BENCH_NO_INREGION") == "1":       # dev: A/B the cost of the in-region event pairs
         dom_name = None
     # an event pair costs the command processor ~2 us; the contraction core has ~280 launches per step, so it is instrumented on
@@ -447,10 +503,13 @@ def main():
         dt = float(tt.item())
     loss_val = float(out["loss"].item())
     log("timed region: %.1f ms/step" % (dt / args.steps * 1e3))
-    # ---- N > 1: what the exchange costs beyond the backward pass it overlaps (three untimed steps): the time the stream spends between the end of
-    # backward() and the end of GradSync.finish() (collectives still running + the divide), and which buckets started inside the encoder backward
+    if args.dump_outputs and rank == 0:          # before any further step changes the parameters
+        dump_outputs(args.dump_outputs, model, out)
+        log("outputs of the last timed step written to %s" % args.dump_outputs)
+    # ---- --full, N > 1: what the exchange costs beyond the backward pass it overlaps (three untimed steps): the time the stream spends between the end
+    # of backward() and the end of GradSync.finish() (collectives still running + the divide), and which buckets started inside the encoder backward
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         ex = []
         for _ in range(3):
             opt.zero_grad(set_to_none=True)
@@ -546,11 +605,12 @@ def main():
                                                                                hp["vocab_size"], T, B, R, "ragged" if args.ragged else "full", args.decoder_tf),
                            "global_batch_images": world * B, "captions_per_step": world * B * R, "parallelism": "dp%d" % world,
                            "images_per_s": round(world * B / (dt / args.steps), 1), "final_loss": round(loss_val, 4),
-                           "grad_bucket_dtype": args.bucket_dtype},
-                "roofline": roof}
+                           "grad_bucket_dtype": args.bucket_dtype}}
+        if args.full:
+            line["roofline"] = roof
 
-    # ---- fp32 parity mode (the mode that meets north_star's 1e-4): a short sub-line of the same workload, after the headline
-    if world == 1 and not args.no_extras and args.precision == "bf16":
+    # ---- --full: fp32 parity mode (the mode that meets north_star's 1e-4): a short sub-line of the same workload, after the headline
+    if world == 1 and args.full and not args.no_extras and args.precision == "bf16":
         model.set_precision("fp32")
         for _ in range(3):
             step()
@@ -570,8 +630,8 @@ def main():
         torch.cuda.synchronize()
     if line is not None and exchange is not None:
         line["exchange"] = exchange
-    # ---- every other BASELINE configuration as a short sub-line: 5 + 5 steps each, one GPU
-    if world == 1 and not args.no_extras and args.config == "c2" and args.precision == "bf16" and not args.batch:
+    # ---- --full: every other BASELINE configuration as a short sub-line: 5 + 5 steps each, one GPU
+    if world == 1 and args.full and not args.no_extras and args.config == "c2" and args.precision == "bf16" and not args.batch:
         subs = {}
         try:
             from sat_amd.graph import GraphedTrainStep
@@ -608,7 +668,7 @@ def main():
         line["sub_lines"] = subs
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("CPU baseline (oracle) ...")
             line["cpu_baseline"] = cpu_baseline(args.config)
             if not args.no_extras and args.config != "c1":      # BASELINE.json configs[0], the reference's own CPU-runnable case

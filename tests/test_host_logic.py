@@ -91,6 +91,32 @@ def test_bench_starts_its_own_ranks_without_touching_the_gpu(monkeypatch, capsys
     assert capsys.readouterr().out.strip() == '{"metric": "m", "value": 1}'
 
 
+def test_bench_dump_outputs_is_float32_seeded_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's loss / accuracy / parameters / gradients / buffers as float32 .npy; arrays past
+    DUMP_SAMPLE elements are sampled at the same indices every run (parameters and their gradients at the same positions)."""
+    import bench
+    torch.manual_seed(3)
+    net = torch.nn.Sequential(torch.nn.Linear(2100, 2100), torch.nn.BatchNorm1d(2100))
+    loss = net(torch.randn(4, 2100)).square().mean()
+    loss.backward()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), net, {"loss": loss, "accuracy": torch.tensor(0.25)})
+    total = 0
+    for name in ("loss", "accuracy", "parameters", "gradients", "buffers"):
+        a, b = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    params = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+    grads = torch.cat([p.grad.reshape(-1) for p in net.parameters()])
+    assert params.numel() > bench.DUMP_SAMPLE and np.load(str(tmp_path / "a" / "parameters.npy")).shape == (bench.DUMP_SAMPLE,)
+    ps, gs = np.load(str(tmp_path / "a" / "parameters.npy")), np.load(str(tmp_path / "a" / "gradients.npy"))
+    idx = torch.randint(0, params.numel(), (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(ps, params[idx].numpy()) and np.array_equal(gs, grads[idx].numpy())
+    assert np.load(str(tmp_path / "a" / "loss.npy"))[0] == np.float32(loss.item())
+    assert np.load(str(tmp_path / "a" / "buffers.npy")).shape == (2 * 2100,)      # running mean + var; num_batches_tracked is an integer
+
+
 def _torchvision_style_checkpoint(tmp_path, arch, name):
     """a checkpoint with torchvision's key names (conv1.*, bn1.*, layerN.*, fc.*) and non-trivial BatchNorm state"""
     torch.manual_seed(5)

@@ -6,7 +6,7 @@ set -o pipefail
 cfg=${1:-c2}; shift
 root=$(pwd); out=$root/gpurun_out/prof_$cfg${TAG:+_$TAG}; rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-B="$root/bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-extras $*"
+B="$root/bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-extras $*"
 cd /tmp
 python3 $B > "$out/bench_plain.json" 2> "$out/bench_plain.err" || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 $B > "$out/bench_trace.json" 2> "$out/trace.log" || exit 2
