@@ -520,6 +520,26 @@ size_t sat_image_batch_workspace_bytes(const sat_image_desc* desc_host, int32_t 
 int sat_image_batch_transform(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev,
                               int32_t n, int32_t out_h, int32_t out_w, const float* noise, float noise_std, float* out_nchw,
                               uint8_t* out_u8, void* workspace, size_t workspace_bytes, void* stream);
+/* T.ColorJitter(brightness, contrast, saturation, hue) of train.py:223-224 on the resampled (and mirrored) bytes, before
+ * ToTensor and noise: the four PIL adjustments of torchvision's functional_pil (ImageEnhance.Brightness / Contrast / Color,
+ * adjust_hue's HSV round trip), bit exact.  One per picture:
+ *   order       a permutation of 0..3 (0 brightness, 1 contrast, 2 saturation, 3 hue), applied first to last
+ *   brightness, contrast, saturation   blend factors, finite and >= 0
+ *   hue_shift   trunc(hue_factor * 255), in [-128, 127]: added to the HSV hue byte modulo 256
+ * jitter_host / jitter_dev: the same n records in host memory (validated) and device memory; NULL / NULL is
+ * sat_image_batch_transform.  The workspace (sat_image_batch_jitter_workspace_bytes) also holds the bytes in front of the
+ * contrast step and each picture's luma sum. */
+typedef struct sat_image_jitter {
+    int32_t order[4];
+    float brightness, contrast, saturation;
+    int32_t hue_shift;
+} sat_image_jitter;
+size_t sat_image_batch_jitter_workspace_bytes(const sat_image_desc* desc_host, const sat_image_jitter* jitter_host, int32_t n, int32_t out_h,
+                                              int32_t out_w);
+int sat_image_batch_transform_jitter(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev,
+                                     const sat_image_jitter* jitter_host, const sat_image_jitter* jitter_dev, int32_t n, int32_t out_h,
+                                     int32_t out_w, const float* noise, float noise_std, float* out_nchw, uint8_t* out_u8, void* workspace,
+                                     size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,13 @@
 // first, each pass rounded and clipped to bytes.  The kernels below compute exactly those bytes (22-bit coefficients from
 // double-precision weights, the same rounding), then byte/255 in fp32 and + noise * std.
 // Byte work, HBM/L2 bound: one read of the source box, a 4-byte-per-pixel intermediate, one fp32 write.
+// ColorJitter (train.py:223-224, on the mirrored bytes before ToTensor): the vertical-pass kernel applies the adjustments in front of
+// contrast and leaves the bytes plus each picture's luma sum in the workspace; a second kernel applies contrast (a blend with the
+// picture's mean luma, which needs the whole picture) and the adjustments after it, then ToTensor and noise.
 #include "../../include/sat_hip.h"
 #include "common.h"
+
+#include <cmath>
 
 // Every floating-point operation in this file must round on its own, as the host code it reproduces does: the Makefile
 // compiles it with -ffp-contract=off (hipcc's default lets the backend fuse a product with a following sum whatever the
@@ -90,16 +95,9 @@ __global__ __launch_bounds__(256) void resample_rows_kernel(const uint8_t* __res
     tmp[((long)img * hmax + row) * out_w + x] = make_uchar4((unsigned char)clip8(s0), (unsigned char)clip8(s1), (unsigned char)clip8(s2), 0);
 }
 
-// vertical pass + flip + ToTensor + noise; one thread per output pixel, the three colour planes written coalesced along x
-__global__ __launch_bounds__(256) void resample_cols_finish_kernel(const sat_image_desc* __restrict__ desc, int out_h, int out_w, int omax, int KT, int hmax,
-                                                                   const int* __restrict__ bounds, const int* __restrict__ coeffs,
-                                                                   const uchar4* __restrict__ tmp, const float* __restrict__ noise, float noise_std,
-                                                                   float* __restrict__ out, uint8_t* __restrict__ out_u8) {
-    const int img = blockIdx.z;
-    const sat_image_desc d = desc[img];
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= out_w || y >= out_h) return;
+// vertical pass of output pixel (x, y) of picture img: its RGB bytes
+__device__ inline void resample_col(int img, int x, int y, int omax, int KT, int hmax, int out_w, const int* __restrict__ bounds,
+                                    const int* __restrict__ coeffs, const uchar4* __restrict__ tmp, int v[3]) {
     const int* b = bounds + (((long)img * 2 + 1) * omax + y) * 2;
     const int* k = coeffs + (((long)img * 2 + 1) * omax + y) * KT;
     const int ymin = b[0], n = b[1];
@@ -110,8 +108,12 @@ __global__ __launch_bounds__(256) void resample_cols_finish_kernel(const sat_ima
         const uchar4 p = src[(long)t * out_w];
         s0 += p.x * kv; s1 += p.y * kv; s2 += p.z * kv;
     }
-    const int v[3] = {clip8(s0), clip8(s1), clip8(s2)};
-    const int xo = d.flip ? out_w - 1 - x : x;
+    v[0] = clip8(s0); v[1] = clip8(s1); v[2] = clip8(s2);
+}
+
+// ToTensor + noise of the bytes of output pixel (xo, y) (after the flip): three fp32 planes and / or the HWC bytes
+__device__ inline void finish_pixel(const int v[3], int img, int y, int xo, int out_h, int out_w, const float* __restrict__ noise, float noise_std,
+                                    float* __restrict__ out, uint8_t* __restrict__ out_u8) {
     const long plane = (long)out_h * out_w;
     const long o = (long)img * 3 * plane + (long)y * out_w + xo;
 #pragma unroll
@@ -125,9 +127,153 @@ __global__ __launch_bounds__(256) void resample_cols_finish_kernel(const sat_ima
     }
 }
 
-struct ImagePlan { int KT, hmax, omax; size_t bounds_off, coeffs_off, tmp_off, total; };
+// vertical pass + flip + ToTensor + noise; one thread per output pixel, the three colour planes written coalesced along x
+__global__ __launch_bounds__(256) void resample_cols_finish_kernel(const sat_image_desc* __restrict__ desc, int out_h, int out_w, int omax, int KT, int hmax,
+                                                                   const int* __restrict__ bounds, const int* __restrict__ coeffs,
+                                                                   const uchar4* __restrict__ tmp, const float* __restrict__ noise, float noise_std,
+                                                                   float* __restrict__ out, uint8_t* __restrict__ out_u8) {
+    const int img = blockIdx.z;
+    const sat_image_desc d = desc[img];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= out_w || y >= out_h) return;
+    int v[3];
+    resample_col(img, x, y, omax, KT, hmax, out_w, bounds, coeffs, tmp, v);
+    finish_pixel(v, img, y, d.flip ? out_w - 1 - x : x, out_h, out_w, noise, noise_std, out, out_u8);
+}
 
-static int image_plan(const sat_image_desc* d, int n, int64_t pixels_bytes, int out_h, int out_w, ImagePlan* p) {
+// ---------------------------------------------------------------------------------------------------------------------------------
+// ColorJitter (train.py:223-224, torchvision's functional_pil): every step is Pillow's C arithmetic on bytes, reproduced operation for
+// operation (float where Pillow computes in float, double where a double literal promotes, each operation rounded on its own).
+enum : int { CJ_BRIGHTNESS = 0, CJ_CONTRAST = 1, CJ_SATURATION = 2, CJ_HUE = 3 };
+
+// Image.convert("L"): ITU-R 601-2 luma in 16-bit fixed point
+__device__ inline int luma8(const int v[3]) { return (v[0] * 19595 + v[1] * 38470 + v[2] * 7471 + 0x8000) >> 16; }
+
+// Image.blend(degenerate, image, f) per byte: d + f * (x - d) in float, truncated and clipped to a byte
+__device__ inline int blend8(int d, int x, float f) {
+    const float t = (float)d + f * ((float)x - (float)d);
+    return t <= 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t);
+}
+
+// Image.convert("HSV") (Pillow's rgb2hsv)
+__device__ inline void rgb_to_hsv8(const int v[3], int& H, int& S, int& V) {
+    const int r = v[0], g = v[1], b = v[2];
+    const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
+    V = mx;
+    if (mx == mn) { H = 0; S = 0; return; }
+    const float cr = (float)(mx - mn);
+    const float s = (float)(mx - mn) / (float)mx;
+    const float rc = (float)(mx - r) / cr, gc = (float)(mx - g) / cr, bc = (float)(mx - b) / cr;
+    float h;
+    if (r == mx) h = bc - gc;
+    else if (g == mx) h = (float)(2.0 + (double)rc - (double)bc);
+    else h = (float)(4.0 + (double)gc - (double)rc);
+    // Pillow: fmod(h / 6.0 + 1.0, 1.0).  h lies in [-1, 5], so the argument lies in [5/6, 11/6) and fmod is a subtraction of 1,
+    // exact there (Sterbenz)
+    const double a = (double)h / 6.0 + 1.0;
+    h = (float)(a >= 1.0 ? a - 1.0 : a);
+    const int hi = (int)((double)h * 255.0), si = (int)((double)s * 255.0);
+    H = hi < 0 ? 0 : (hi > 255 ? 255 : hi);
+    S = si < 0 ? 0 : (si > 255 ? 255 : si);
+}
+
+__device__ inline int round8(double x) {
+    const int r = (int)round(x);                        // half away from zero, as C's round()
+    return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+
+// Image.convert("RGB") of HSV bytes (Pillow's hsv2rgb)
+__device__ inline void hsv_to_rgb8(int H, int S, int V, int v[3]) {
+    if (S == 0) { v[0] = v[1] = v[2] = V; return; }
+    const double hx = (double)(float)H * 6.0 / 255.0;
+    const int i = (int)floor(hx);
+    const float f = (float)(hx - (double)(float)i);
+    const float fs = (float)((double)(float)S / 255.0);
+    const double vv = (double)(float)V;
+    const int p = round8(vv * (1.0 - (double)fs));
+    const int q = round8(vv * (1.0 - (double)(fs * f)));
+    const int t = round8(vv * (1.0 - (double)fs * (1.0 - (double)f)));
+    switch (i % 6) {
+        case 0: v[0] = V; v[1] = t; v[2] = p; break;
+        case 1: v[0] = q; v[1] = V; v[2] = p; break;
+        case 2: v[0] = p; v[1] = V; v[2] = t; break;
+        case 3: v[0] = p; v[1] = q; v[2] = V; break;
+        case 4: v[0] = t; v[1] = p; v[2] = V; break;
+        default: v[0] = V; v[1] = p; v[2] = q; break;
+    }
+}
+
+// one adjustment other than contrast, in place
+__device__ inline void jitter_op(int op, const sat_image_jitter& j, int v[3]) {
+    if (op == CJ_BRIGHTNESS) {                          // ImageEnhance.Brightness: degenerate = black
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = blend8(0, v[c], j.brightness);
+    } else if (op == CJ_SATURATION) {                   // ImageEnhance.Color: degenerate = the picture's own luma
+        const int l = luma8(v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = blend8(l, v[c], j.saturation);
+    } else {                                            // F_pil.adjust_hue: H + shift as a wrapping byte
+        int H, S, V;
+        rgb_to_hsv8(v, H, S, V);
+        hsv_to_rgb8((H + j.hue_shift) & 255, S, V, v);
+    }
+}
+
+// vertical pass + flip + the adjustments in front of contrast.  The bytes go to `pre` (output layout, mirrored), and each picture's
+// luma sum - what ImageEnhance.Contrast averages - to sums[img]: one 64-bit integer atomic per block, so the sum is exact and does
+// not depend on the order of arrival.
+__global__ __launch_bounds__(256) void resample_cols_jitter_kernel(const sat_image_desc* __restrict__ desc, const sat_image_jitter* __restrict__ jit,
+                                                                   int out_h, int out_w, int omax, int KT, int hmax, const int* __restrict__ bounds,
+                                                                   const int* __restrict__ coeffs, const uchar4* __restrict__ tmp,
+                                                                   uchar4* __restrict__ pre, unsigned long long* __restrict__ sums) {
+    __shared__ int part[4];
+    const int img = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int l = 0;
+    if (x < out_w && y < out_h) {
+        const sat_image_desc d = desc[img];
+        const sat_image_jitter j = jit[img];
+        int v[3];
+        resample_col(img, x, y, omax, KT, hmax, out_w, bounds, coeffs, tmp, v);
+        for (int k = 0; k < 4 && j.order[k] != CJ_CONTRAST; ++k) jitter_op(j.order[k], j, v);
+        pre[((long)img * out_h + y) * out_w + (d.flip ? out_w - 1 - x : x)] = make_uchar4((unsigned char)v[0], (unsigned char)v[1], (unsigned char)v[2], 0);
+        l = luma8(v);
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) l += __shfl_xor(l, m, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = l;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(sums + img, (unsigned long long)(part[0] + part[1] + part[2] + part[3]));
+}
+
+// contrast against the picture's mean luma, the adjustments after it, ToTensor + noise; one thread per output pixel
+__global__ __launch_bounds__(256) void color_jitter_finish_kernel(const sat_image_jitter* __restrict__ jit, int out_h, int out_w,
+                                                                  const uchar4* __restrict__ pre, const unsigned long long* __restrict__ sums,
+                                                                  const float* __restrict__ noise, float noise_std, float* __restrict__ out,
+                                                                  uint8_t* __restrict__ out_u8) {
+    const int img = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= out_w || y >= out_h) return;
+    const sat_image_jitter j = jit[img];
+    // ImageEnhance.Contrast: degenerate = int(ImageStat mean of L + 0.5), the mean an exact integer sum over the pixel count
+    const int mean = (int)((double)sums[img] / (double)((long)out_h * out_w) + 0.5);
+    const uchar4 p = pre[((long)img * out_h + y) * out_w + x];
+    int v[3] = {p.x, p.y, p.z};
+    int k = 0;
+    while (k < 3 && j.order[k] != CJ_CONTRAST) ++k;     // the order is a permutation (validated on the host)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = blend8(mean, v[c], j.contrast);
+    for (++k; k < 4; ++k) jitter_op(j.order[k], j, v);
+    finish_pixel(v, img, y, x, out_h, out_w, noise, noise_std, out, out_u8);
+}
+
+struct ImagePlan { int KT, hmax, omax; size_t bounds_off, coeffs_off, tmp_off, pre_off, sums_off, total; };
+
+// jit (host, or NULL: no ColorJitter) adds the jitter checks and the workspace of the two jitter kernels
+static int image_plan(const sat_image_desc* d, const sat_image_jitter* jit, int n, int64_t pixels_bytes, int out_h, int out_w, ImagePlan* p) {
     SAT_REQUIRE(n > 0 && out_h > 0 && out_w > 0, "image_batch: n=%d out=%dx%d", n, out_h, out_w);
     int KT = 3, hmax = 1;
     for (int i = 0; i < n; ++i) {
@@ -142,6 +288,18 @@ static int image_plan(const sat_image_desc* d, int n, int64_t pixels_bytes, int 
         SAT_REQUIRE(k <= RS_MAX_TAPS, "image_batch: picture %d shrinks by more than 64x", i);
         if (k > KT) KT = k;
         if (e.crop_h > hmax) hmax = e.crop_h;
+        if (jit) {
+            const sat_image_jitter& j = jit[i];
+            int seen = 0;
+            for (int k = 0; k < 4; ++k) seen |= (j.order[k] >= 0 && j.order[k] < 4) ? 1 << j.order[k] : 16;
+            SAT_REQUIRE(seen == 15, "image_batch: picture %d jitter order (%d,%d,%d,%d) is not a permutation of 0..3", i, j.order[0], j.order[1],
+                        j.order[2], j.order[3]);
+            SAT_REQUIRE(std::isfinite(j.brightness) && std::isfinite(j.contrast) && std::isfinite(j.saturation) && j.brightness >= 0.0f &&
+                        j.contrast >= 0.0f && j.saturation >= 0.0f,
+                        "image_batch: picture %d jitter factors (%g, %g, %g) must be finite and >= 0", i, (double)j.brightness, (double)j.contrast,
+                        (double)j.saturation);
+            SAT_REQUIRE(j.hue_shift >= -128 && j.hue_shift <= 127, "image_batch: picture %d hue shift %d outside [-128, 127]", i, j.hue_shift);
+        }
     }
     p->KT = KT; p->hmax = hmax; p->omax = out_h > out_w ? out_h : out_w;
     size_t off = 0;
@@ -149,6 +307,8 @@ static int image_plan(const sat_image_desc* d, int n, int64_t pixels_bytes, int 
     p->bounds_off = take((size_t)n * 2 * p->omax * 2 * sizeof(int));
     p->coeffs_off = take((size_t)n * 2 * p->omax * KT * sizeof(int));
     p->tmp_off = take((size_t)n * hmax * out_w * sizeof(uchar4));
+    p->pre_off = jit ? take((size_t)n * out_h * out_w * sizeof(uchar4)) : 0;
+    p->sums_off = jit ? take((size_t)n * sizeof(unsigned long long)) : 0;
     p->total = off;
     return SAT_OK;
 }
@@ -161,16 +321,33 @@ extern "C" {
 size_t sat_image_batch_workspace_bytes(const sat_image_desc* desc_host, int32_t n, int32_t out_h, int32_t out_w) {
     if (!desc_host) { fail(SAT_EINVAL, "image_batch: null descriptors"); return 0; }
     ImagePlan p;
-    if (image_plan(desc_host, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
+    if (image_plan(desc_host, nullptr, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
+    return p.total;
+}
+
+size_t sat_image_batch_jitter_workspace_bytes(const sat_image_desc* desc_host, const sat_image_jitter* jitter_host, int32_t n, int32_t out_h,
+                                              int32_t out_w) {
+    if (!desc_host) { fail(SAT_EINVAL, "image_batch: null descriptors"); return 0; }
+    ImagePlan p;
+    if (image_plan(desc_host, jitter_host, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
     return p.total;
 }
 
 int sat_image_batch_transform(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev, int32_t n,
                               int32_t out_h, int32_t out_w, const float* noise, float noise_std, float* out_nchw, uint8_t* out_u8,
                               void* workspace, size_t workspace_bytes, void* stream) {
+    return sat_image_batch_transform_jitter(pixels, pixels_bytes, desc_host, desc_dev, nullptr, nullptr, n, out_h, out_w, noise, noise_std, out_nchw,
+                                            out_u8, workspace, workspace_bytes, stream);
+}
+
+int sat_image_batch_transform_jitter(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev,
+                                     const sat_image_jitter* jitter_host, const sat_image_jitter* jitter_dev, int32_t n, int32_t out_h,
+                                     int32_t out_w, const float* noise, float noise_std, float* out_nchw, uint8_t* out_u8, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
     if (!pixels || !desc_host || !desc_dev || !workspace || (!out_nchw && !out_u8)) return fail(SAT_EINVAL, "image_batch: null pointer");
+    if (!jitter_host != !jitter_dev) return fail(SAT_EINVAL, "image_batch: jitter records given in %s memory only", jitter_host ? "host" : "device");
     ImagePlan p;
-    SAT_TRY(image_plan(desc_host, n, pixels_bytes, out_h, out_w, &p));
+    SAT_TRY(image_plan(desc_host, jitter_host, n, pixels_bytes, out_h, out_w, &p));
     SAT_REQUIRE(workspace_bytes >= p.total, "image_batch: workspace %zu < %zu bytes", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -182,6 +359,17 @@ int sat_image_batch_transform(const uint8_t* pixels, int64_t pixels_bytes, const
     hipLaunchKernelGGL(resample_rows_kernel, dim3((out_w + 63) / 64, (p.hmax + 3) / 4, n), dim3(256), 0, st, pixels, desc_dev, out_w, p.omax, p.KT, p.hmax,
                        bounds, coeffs, tmp);
     SAT_TRY(launch_ok("resample_rows"));
+    if (jitter_host) {
+        uchar4* pre = (uchar4*)(ws + p.pre_off);
+        unsigned long long* sums = (unsigned long long*)(ws + p.sums_off);
+        SAT_TRY(dev_fill_bytes(st, sums, 0, (size_t)n * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(resample_cols_jitter_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, desc_dev, jitter_dev, out_h, out_w,
+                           p.omax, p.KT, p.hmax, bounds, coeffs, tmp, pre, sums);
+        SAT_TRY(launch_ok("resample_cols_jitter"));
+        hipLaunchKernelGGL(color_jitter_finish_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, jitter_dev, out_h, out_w, pre, sums,
+                           noise, noise_std, out_nchw, out_u8);
+        return launch_ok("color_jitter_finish");
+    }
     hipLaunchKernelGGL(resample_cols_finish_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, desc_dev, out_h, out_w, p.omax, p.KT, p.hmax,
                        bounds, coeffs, tmp, noise, noise_std, out_nchw, out_u8);
     return launch_ok("resample_cols_finish");

@@ -6,13 +6,14 @@ Host-side mirror of the reference's data path:
   preprocess.ipynb cell 17); ``__getitem__`` returns the *decoded bytes* (H, W, 3) uint8 instead of a transformed tensor.
 * ``BucketSampler``        util.py:48-87 - same grouping and shuffle; additionally rank/world_size aware.
 * ``BatchTransform``       train.py:208-233 - RandomResizedCrop | Resize+CenterCrop, RandomHorizontalFlip, ToTensor,
-  AddGaussianNoise (util.py:121-130) for a whole batch in three kernel launches (``sat_image_batch_transform``): the
-  pictures are resampled with Pillow's BILINEAR arithmetic bit for bit, the random draws are made on the host in the
-  reference's order (crop parameters, then the flip coin, per picture).
+  ColorJitter (train.py:223-224), AddGaussianNoise (util.py:121-130) for a whole batch in three kernel launches, four with
+  ColorJitter (``sat_image_batch_transform[_jitter]``): the pictures are resampled and jittered with Pillow's arithmetic
+  bit for bit, the random draws are made on the host in the reference's order (crop parameters, then the flip coin, then
+  ColorJitter's permutation and factors, per picture).
 * ``DeviceLoader``         train.py:244-259 DataLoader(pin_memory=True): decode threads -> one pinned staging buffer per
   batch -> one H2D copy on a side stream -> transform; batches arrive as ``(img, caps, lengths)`` on the device.
 
-ColorJitter / RandomPerspective / RandomAffine / RandomRotation (train.py:223-231, off by default) are not built.
+RandomPerspective / RandomAffine / RandomRotation (train.py:225-231, off by default) are not built.
 There is no CPU path: the transform needs libsat_hip.so and a GPU.
 """
 from __future__ import annotations
@@ -161,6 +162,19 @@ def random_resized_crop_params(h, w, scale, ratio=(3.0 / 4.0, 4.0 / 3.0)):
     return (h - ch) // 2, (w - cw) // 2, ch, cw
 
 
+def color_jitter_params(x, hue=0.03):
+    """T.ColorJitter(brightness=x, contrast=x, saturation=x, hue=hue).get_params, drawing from the global torch CPU
+    generator, as the fields of a picture's jitter record: the order of the adjustments (0 brightness, 1 contrast,
+    2 saturation, 3 hue), the three blend factors and the hue byte shift F_pil.adjust_hue adds (hue * 255 truncated)."""
+    fn_idx = torch.randperm(4)
+    lo = max(0.0, 1.0 - x)
+    b = float(torch.empty(1).uniform_(lo, 1.0 + x))
+    c = float(torch.empty(1).uniform_(lo, 1.0 + x))
+    s = float(torch.empty(1).uniform_(lo, 1.0 + x))
+    h = float(torch.empty(1).uniform_(-hue, hue))
+    return dict(jitter_order=tuple(fn_idx.tolist()), brightness=b, contrast=c, saturation=s, hue_shift=int(h * 255))
+
+
 def box_desc(h, w, box, size, flip=False):
     """descriptor fields of: crop ``box`` = (top, left, height, width) -> resize to size x size (-> flip)"""
     t, l, ch, cw = box
@@ -174,14 +188,25 @@ def center_desc(h, w, size):
                 out_top=int(round((rh - size) / 2.0)), out_left=int(round((rw - size) / 2.0)), flip=0)
 
 
+#: descriptor-dict keys of the ColorJitter record of a picture (sat_image_jitter); the other keys are sat_image_desc fields
+JITTER_KEYS = ("jitter_order", "brightness", "contrast", "saturation", "hue_shift")
+
+
 class StagedBatch:
-    """The decoded pictures of one batch in one pinned host buffer: [descriptors | pixels]."""
+    """The decoded pictures of one batch in one pinned host buffer: [descriptors | jitter records | pixels].  The jitter
+    records are there when the descriptor dicts carry ``JITTER_KEYS`` (all of them or none)."""
 
     def __init__(self, images, descs):
         n = len(images)
         self.n = n
         self.desc = (L.ImageDesc * n)()
-        head = (C.sizeof(L.ImageDesc) * n + 255) // 256 * 256
+        has = {sum(k in d for k in JITTER_KEYS) for d in descs}
+        if len(has) > 1 or has - {0, len(JITTER_KEYS)}:
+            raise ValueError("ColorJitter fields (%s) must be given for every picture of a batch or for none" % ", ".join(JITTER_KEYS))
+        self.jitter = (L.ImageJitter * n)() if has == {len(JITTER_KEYS)} else None
+        self.jitter_off = (C.sizeof(L.ImageDesc) * n + 15) // 16 * 16
+        head = self.jitter_off + (C.sizeof(L.ImageJitter) * n if self.jitter is not None else 0)
+        head = (head + 255) // 256 * 256
         total = head + sum(int(im.shape[0]) * int(im.shape[1]) * 3 for im in images)
         self.host = torch.empty(total, dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else torch.empty(total, dtype=torch.uint8)
         buf = self.host.numpy()
@@ -194,23 +219,38 @@ class StagedBatch:
             e = self.desc[i]
             e.offset = off
             for k, v in d.items():
-                setattr(e, k, int(v))
+                if k not in JITTER_KEYS:
+                    setattr(e, k, int(v))
+            if self.jitter is not None:
+                j = self.jitter[i]
+                j.order[:] = [int(o) for o in d["jitter_order"]]
+                j.brightness, j.contrast, j.saturation = float(d["brightness"]), float(d["contrast"]), float(d["saturation"])
+                j.hue_shift = int(d["hue_shift"])
             off += nb
         buf[:C.sizeof(L.ImageDesc) * n] = np.frombuffer(self.desc, dtype=np.uint8)
+        if self.jitter is not None:
+            buf[self.jitter_off:self.jitter_off + C.sizeof(L.ImageJitter) * n] = np.frombuffer(self.jitter, dtype=np.uint8)
         self.head, self.pixels_bytes = head, off
 
 
 class BatchTransform:
     """train.py:208-233 for a batch.  ``train=False``: Resize + CenterCrop + ToTensor (valid_transforms).
     ``train=True``: aug_scale == 1 -> Resize + CenterCrop, else RandomResizedCrop(scale=(aug_scale, 1)); a flip with
-    probability aug_hflip when 0 < aug_hflip < 1; ToTensor; + N(0,1) * aug_noise_std.
+    probability aug_hflip when 0 < aug_hflip < 1; T.ColorJitter(x, x, x, hue=0.03) when aug_color_jitter = x is not 0 and
+    at most 1 (a larger x is ignored, as the reference does; a negative one raises, as torchvision does); ToTensor;
+    + N(0,1) * aug_noise_std.
     ``randn(shape, device)`` supplies the noise draws (default: ``torch.randn`` on the device)."""
 
-    def __init__(self, input_size, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, randn=None):
+    def __init__(self, input_size, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, randn=None, aug_color_jitter=0.0):
         if train and not (0 <= aug_scale <= 1.0):
             raise ValueError("Invalid value for aug_scale. Choose in the range {0,1}.")       # train.py:219-220
+        x = float(aug_color_jitter)
+        self.jitter = train and x != 0 and x <= 1.0                                           # train.py:223
+        if self.jitter and x < 0:
+            raise ValueError("If brightness is a single number, it must be non negative.")   # T.ColorJitter._check_input
         self.size, self.train = int(input_size), train
         self.aug_scale, self.aug_hflip, self.noise_std, self.randn = aug_scale, aug_hflip, aug_noise_std, randn
+        self.aug_color_jitter = x
         self._ws = None
 
     def draw(self, shapes):
@@ -223,6 +263,8 @@ class BatchTransform:
                 d = box_desc(h, w, random_resized_crop_params(h, w, (self.aug_scale, 1.0)), self.size)
             if self.train and 0 < self.aug_hflip < 1.0:
                 d["flip"] = int(torch.rand(1).item() < self.aug_hflip)            # T.RandomHorizontalFlip.forward
+            if self.jitter:
+                d.update(color_jitter_params(self.aug_color_jitter))
             out.append(d)
         return out
 
@@ -240,7 +282,11 @@ class BatchTransform:
         S, n = self.size, staged.n
         with torch.cuda.stream(stream):
             dev = staged.host.to(device, non_blocking=True)
-            need = lib.sat_image_batch_workspace_bytes(C.cast(staged.desc, C.c_void_p), n, S, S)
+            jit = staged.jitter
+            if jit is None:
+                need = lib.sat_image_batch_workspace_bytes(C.cast(staged.desc, C.c_void_p), n, S, S)
+            else:
+                need = lib.sat_image_batch_jitter_workspace_bytes(C.cast(staged.desc, C.c_void_p), C.cast(jit, C.c_void_p), n, S, S)
             if need == 0:
                 L.check(1, "sat_image_batch_workspace_bytes")
             if self._ws is None or self._ws.numel() < need or self._ws.device != dev.device:
@@ -252,10 +298,15 @@ class BatchTransform:
             if noise is not None:
                 L.require_gpu(noise)
                 assert noise.shape == out.shape and noise.dtype == torch.float32 and noise.is_contiguous()
-            L.check(lib.sat_image_batch_transform(dev.data_ptr() + staged.head, staged.pixels_bytes, C.cast(staged.desc, C.c_void_p), dev.data_ptr(), n, S, S,
-                                                  L.ptr(noise) if noise is not None else None, float(self.noise_std if noise is not None else 0.0),
-                                                  L.ptr(out), L.ptr(raw) if raw is not None else None, L.ptr(self._ws), self._ws.numel(),
-                                                  C.c_void_p(stream.cuda_stream)), "sat_image_batch_transform")
+            tail = (n, S, S, L.ptr(noise) if noise is not None else None, float(self.noise_std if noise is not None else 0.0), L.ptr(out),
+                    L.ptr(raw) if raw is not None else None, L.ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream))
+            if jit is None:
+                L.check(lib.sat_image_batch_transform(dev.data_ptr() + staged.head, staged.pixels_bytes, C.cast(staged.desc, C.c_void_p), dev.data_ptr(),
+                                                      *tail), "sat_image_batch_transform")
+            else:
+                L.check(lib.sat_image_batch_transform_jitter(dev.data_ptr() + staged.head, staged.pixels_bytes, C.cast(staged.desc, C.c_void_p),
+                                                             dev.data_ptr(), C.cast(jit, C.c_void_p), dev.data_ptr() + staged.jitter_off, *tail),
+                        "sat_image_batch_transform_jitter")
             dev.record_stream(stream)
         return (out, raw) if want_bytes else out
 

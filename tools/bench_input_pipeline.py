@@ -1,8 +1,11 @@
 """Input pipeline: one C2-sized batch of decoded pictures (128 x 480x640 RGB bytes) -> (128, 3, 224, 224)
 fp32 through sat_image_batch_transform, against Pillow doing the same crop + BILINEAR resize (+ numpy ToTensor) on the host.
-    python tools/bench_input_pipeline.py [--batch 128] [--size 224]
+With --color-jitter X the same batch also goes through T.ColorJitter(X, X, X, 0.03) (sat_image_batch_transform_jitter), and
+both rates are reported from the same run.
+    python tools/bench_input_pipeline.py [--batch 128] [--size 224] [--color-jitter 0.4]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -14,7 +17,47 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import sat_amd  # noqa: E402,F401
+from sat_amd import _lib as L  # noqa: E402
 from sat_amd import data as D  # noqa: E402
+
+
+def time_ms(fn, iters):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def measure(tf, staged, noise, iters):
+    """(with the H2D copy, kernels only) in ms per batch"""
+    dev = torch.device("cuda")
+    B, S = staged.n, tf.size
+    with_copy_ms = time_ms(lambda: tf.run(staged, dev, noise=noise), iters)       # H2D copy of 118 MB + the kernels
+    lib = L.lib()
+    resident = staged.host.to(dev)                                               # kernels only: pixels already resident
+    desc, jit = C.cast(staged.desc, C.c_void_p), staged.jitter
+    if jit is None:
+        need = lib.sat_image_batch_workspace_bytes(desc, B, S, S)
+    else:
+        need = lib.sat_image_batch_jitter_workspace_bytes(desc, C.cast(jit, C.c_void_p), B, S, S)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, 3, S, S, device=dev)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def kernels():
+        if jit is None:
+            L.check(lib.sat_image_batch_transform(resident.data_ptr() + staged.head, staged.pixels_bytes, desc, resident.data_ptr(),
+                                                  B, S, S, L.ptr(noise), 0.01, L.ptr(out), None, L.ptr(ws), need, st), "transform")
+        else:
+            L.check(lib.sat_image_batch_transform_jitter(resident.data_ptr() + staged.head, staged.pixels_bytes, desc, resident.data_ptr(),
+                                                         C.cast(jit, C.c_void_p), resident.data_ptr() + staged.jitter_off, B, S, S, L.ptr(noise),
+                                                         0.01, L.ptr(out), None, L.ptr(ws), need, st), "transform_jitter")
+    return with_copy_ms, time_ms(kernels, iters)
 
 
 def main():
@@ -22,6 +65,7 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--color-jitter", type=float, default=0.0, help="also time T.ColorJitter(X, X, X, 0.03) on the same batch")
     a = ap.parse_args()
     H, W, S, B = 480, 640, a.size, a.batch
     rng = np.random.default_rng(0)
@@ -35,37 +79,27 @@ def main():
     staged = tf.stage(imgs, descs)
     stage_s = time.perf_counter() - t0
     noise = torch.randn(B, 3, S, S, device=dev)
-    for _ in range(5):
-        out = tf.run(staged, dev, noise=noise)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.iters):
-        out = tf.run(staged, dev, noise=noise)           # H2D copy of 118 MB + 3 kernels
-    e1.record(); torch.cuda.synchronize()
-    with_copy_ms = e0.elapsed_time(e1) / a.iters
-    # kernels only: pixels already resident
-    import ctypes as C
-    from sat_amd import _lib as L
-    lib = L.lib()
-    resident = staged.host.to(dev)
-    need = lib.sat_image_batch_workspace_bytes(C.cast(staged.desc, C.c_void_p), B, S, S)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def kernels():
-        L.check(lib.sat_image_batch_transform(resident.data_ptr() + staged.head, staged.pixels_bytes, C.cast(staged.desc, C.c_void_p), resident.data_ptr(),
-                                              B, S, S, L.ptr(noise), 0.01, L.ptr(out), None, L.ptr(ws), need, st), "transform")
-    for _ in range(5):
-        kernels()
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(a.iters):
-        kernels()
-    e1.record(); torch.cuda.synchronize()
-    kern_ms = e0.elapsed_time(e1) / a.iters
+    with_copy_ms, kern_ms = measure(tf, staged, noise, a.iters)
     src_bytes = sum(d["crop_h"] * d["crop_w"] * 3 for d in descs)
     alg_bytes = src_bytes + 2 * 4 * sum(d["crop_h"] for d in descs) * S + 2 * B * 3 * S * S * 4     # box read, RGBX intermediate w+r, noise read + fp32 write
+    res = {"metric": "input_pipeline_images_per_s", "batch": B, "source": "%dx%d u8" % (H, W), "out": S,
+           "kernels_ms": round(kern_ms, 4), "kernels_images_per_s": round(B / kern_ms * 1e3, 1),
+           "algorithmic_GBps": round(alg_bytes / kern_ms / 1e6, 1),
+           "with_h2d_ms": round(with_copy_ms, 3), "with_h2d_images_per_s": round(B / with_copy_ms * 1e3, 1),
+           "h2d_bytes": int(staged.host.numel()), "host_stage_ms": round(stage_s * 1e3, 2)}
+    if a.color_jitter:
+        x = a.color_jitter
+        tfj = D.BatchTransform(S, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, aug_color_jitter=x)
+        if not tfj.jitter:
+            raise SystemExit("--color-jitter %g: the reference applies no jitter for this value (0 < x <= 1)" % x)
+        torch.manual_seed(1)
+        jdescs = [dict(d, **D.color_jitter_params(x)) for d in descs]                # same crops, jitter draws added
+        jw_ms, jk_ms = measure(tfj, tfj.stage(imgs, jdescs), noise, a.iters)
+        # the same two timings of the plain batch again, after the jitter runs (drift between the two halves of the run)
+        w2_ms, k2_ms = measure(tf, staged, noise, a.iters)
+        res.update({"color_jitter": x, "jitter_kernels_ms": round(jk_ms, 4), "jitter_kernels_images_per_s": round(B / jk_ms * 1e3, 1),
+                    "jitter_with_h2d_ms": round(jw_ms, 3), "jitter_with_h2d_images_per_s": round(B / jw_ms * 1e3, 1),
+                    "plain_again_kernels_ms": round(k2_ms, 4), "plain_again_with_h2d_ms": round(w2_ms, 3)})
     # host: Pillow on one thread, a sample of the same batch
     from PIL import Image
     n_cpu = min(B, 32)
@@ -77,12 +111,8 @@ def main():
         x = torch.from_numpy(np.asarray(p).copy()).permute(2, 0, 1).float().div(255)
         x = x + torch.randn(x.size()) * 0.01
     cpu_s = (time.perf_counter() - t0) / n_cpu
-    print(json.dumps({"metric": "input_pipeline_images_per_s", "batch": B, "source": "%dx%d u8" % (H, W), "out": S,
-                      "kernels_ms": round(kern_ms, 4), "kernels_images_per_s": round(B / kern_ms * 1e3, 1),
-                      "algorithmic_GBps": round(alg_bytes / kern_ms / 1e6, 1),
-                      "with_h2d_ms": round(with_copy_ms, 3), "with_h2d_images_per_s": round(B / with_copy_ms * 1e3, 1),
-                      "h2d_bytes": int(staged.host.numel()), "host_stage_ms": round(stage_s * 1e3, 2),
-                      "pillow_1thread_images_per_s": round(1.0 / cpu_s, 1), "pillow_sample": n_cpu}))
+    res.update({"pillow_1thread_images_per_s": round(1.0 / cpu_s, 1), "pillow_sample": n_cpu})
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
