@@ -540,6 +540,27 @@ int sat_image_batch_transform_jitter(const uint8_t* pixels, int64_t pixels_bytes
                                      const sat_image_jitter* jitter_host, const sat_image_jitter* jitter_dev, int32_t n, int32_t out_h,
                                      int32_t out_w, const float* noise, float noise_std, float* out_nchw, uint8_t* out_u8, void* workspace,
                                      size_t workspace_bytes, void* stream);
+/* The "optical" augmentation of train.py:225-231 (T.RandomChoice of RandomPerspective, RandomAffine, RandomRotation) on the
+ * S x S bytes after ColorJitter, before ToTensor and noise: Pillow's Image.transform of the picture onto itself with fill 0,
+ * bit exact.  One record per picture, Pillow's inverse map (output pixel -> input point):
+ *   kind 0   affine map, NEAREST (RandomAffine, RandomRotation): coeffs[0..5], sampled in Pillow's 16.16 fixed point;
+ *            |x*c0 + y*c1 + c2| and |x*c3 + y*c4 + c5| must be below 32768 at the four corners (0,0) (W,0) (0,H) (W,H),
+ *            where Pillow takes that path
+ *   kind 1   perspective map, BILINEAR (RandomPerspective): coeffs[0..7], sampled in double
+ * Every coefficient must be finite.  warp_host / warp_dev: the same n records in host memory (validated) and device memory;
+ * NULL / NULL is sat_image_batch_transform_jitter.  jitter_host / jitter_dev NULL / NULL: no ColorJitter.  The workspace
+ * (sat_image_batch_warp_workspace_bytes) also holds the bytes in front of the warp. */
+typedef struct sat_image_warp {
+    int32_t kind;
+    int32_t reserved;
+    double coeffs[8];
+} sat_image_warp;
+size_t sat_image_batch_warp_workspace_bytes(const sat_image_desc* desc_host, const sat_image_jitter* jitter_host, const sat_image_warp* warp_host,
+                                            int32_t n, int32_t out_h, int32_t out_w);
+int sat_image_batch_transform_warp(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev,
+                                   const sat_image_jitter* jitter_host, const sat_image_jitter* jitter_dev, const sat_image_warp* warp_host,
+                                   const sat_image_warp* warp_dev, int32_t n, int32_t out_h, int32_t out_w, const float* noise, float noise_std,
+                                   float* out_nchw, uint8_t* out_u8, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,10 @@ class ImageJitter(C.Structure):
     _fields_ = [("order", C.c_int32 * 4), ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("hue_shift", C.c_int32)]
 
 
+class ImageWarp(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("coeffs", C.c_double * 8)]
+
+
 class DecoderBatch(C.Structure):
     _fields_ = [("ann", C.c_void_p), ("caps", C.c_void_p), ("lengths", C.c_void_p), ("prow", C.c_void_p), ("src_row", C.c_void_p),
                 ("step_offsets_host", C.c_void_p), ("teacher_host", C.c_void_p)]
@@ -236,7 +240,10 @@ SYMBOLS.update({"sat_image_batch_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32
                 "sat_image_batch_transform": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _f, _vp, _vp, _vp, C.c_size_t, _vp]),
                 "sat_image_batch_jitter_workspace_bytes": (C.c_size_t, [_vp, _vp, _i32, _i32, _i32]),
                 "sat_image_batch_transform_jitter": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f, _vp, _vp, _vp, C.c_size_t,
-                                                               _vp])})
+                                                               _vp]),
+                "sat_image_batch_warp_workspace_bytes": (C.c_size_t, [_vp, _vp, _vp, _i32, _i32, _i32]),
+                "sat_image_batch_transform_warp": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f, _vp, _vp, _vp,
+                                                             C.c_size_t, _vp])})
 SYMBOLS.update({"sat_profile_start": (C.c_int, []),
                 "sat_profile_start_only": (C.c_int, [C.c_char_p]),
                 "sat_profile_pause": (C.c_int, [_i32]),

@@ -9,6 +9,9 @@
 // ColorJitter (train.py:223-224, on the mirrored bytes before ToTensor): the vertical-pass kernel applies the adjustments in front of
 // contrast and leaves the bytes plus each picture's luma sum in the workspace; a second kernel applies contrast (a blend with the
 // picture's mean luma, which needs the whole picture) and the adjustments after it, then ToTensor and noise.
+// Optical augmentation (train.py:225-231, after ColorJitter): the last byte stage writes its bytes to the workspace instead of
+// finishing, and one more kernel warps them (Pillow's fixed-point affine NEAREST or double perspective BILINEAR sampling, fill 0),
+// then ToTensor and noise.
 #include "../../include/sat_hip.h"
 #include "common.h"
 
@@ -270,10 +273,79 @@ __global__ __launch_bounds__(256) void color_jitter_finish_kernel(const sat_imag
     finish_pixel(v, img, y, x, out_h, out_w, noise, noise_std, out, out_u8);
 }
 
-struct ImagePlan { int KT, hmax, omax; size_t bounds_off, coeffs_off, tmp_off, pre_off, sums_off, total; };
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The "optical" augmentation (train.py:225-231: RandomPerspective | RandomAffine | RandomRotation on the S x S picture after
+// ColorJitter): Pillow's Image.transform of the picture onto itself with fill 0.  The record holds Pillow's inverse map.
 
-// jit (host, or NULL: no ColorJitter) adds the jitter checks and the workspace of the two jitter kernels
-static int image_plan(const sat_image_desc* d, const sat_image_jitter* jit, int n, int64_t pixels_bytes, int out_h, int out_w, ImagePlan* p) {
+// RandomAffine / RandomRotation: Pillow's affine_fixed (NEAREST).  16.16 fixed point; the closed form below is Pillow's running
+// sums (xx += a0 along a row, a2 += a1 per row) evaluated modulo 2^32, as its int32 sums are.
+__device__ inline int fix16(double v) { return (int)floor(v * 65536.0 + 0.5); }
+
+__device__ inline void warp_affine_nearest(const double c[8], int x, int y, int W, int H, const uint8_t* __restrict__ pic, int v[3]) {
+    const unsigned a0 = (unsigned)fix16(c[0]), a1 = (unsigned)fix16(c[1]), a3 = (unsigned)fix16(c[3]), a4 = (unsigned)fix16(c[4]);
+    const unsigned a2 = (unsigned)fix16(c[2] + c[0] * 0.5 + c[1] * 0.5);
+    const unsigned a5 = (unsigned)fix16(c[5] + c[3] * 0.5 + c[4] * 0.5);
+    const int xin = (int)(a2 + (unsigned)y * a1 + (unsigned)x * a0) >> 16;
+    const int yin = (int)(a5 + (unsigned)y * a4 + (unsigned)x * a3) >> 16;
+    if (xin >= 0 && xin < W && yin >= 0 && yin < H) {
+        const uint8_t* p = pic + ((long)yin * W + xin) * 3;
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+    }
+}
+
+// RandomPerspective: Pillow's generic transform with perspective_transform and bilinear_filter32RGB, all in double.  A point
+// outside the picture (or a NaN from a zero denominator) is fill; the column and row indices are clamped, so no read leaves it.
+__device__ inline void warp_perspective_bilinear(const double c[8], int x, int y, int W, int H, const uint8_t* __restrict__ pic, int v[3]) {
+    const double xi = (double)x + 0.5, yi = (double)y + 0.5;
+    const double den = c[6] * xi + c[7] * yi + 1.0;
+    double xo = (c[0] * xi + c[1] * yi + c[2]) / den;
+    double yo = (c[3] * xi + c[4] * yi + c[5]) / den;
+    if (!(xo >= 0.0 && xo < (double)W && yo >= 0.0 && yo < (double)H)) return;
+    xo -= 0.5;
+    yo -= 0.5;
+    const double fx = floor(xo), fy = floor(yo);
+    const double dx = xo - fx, dy = yo - fy;
+    const int ix = (int)fx, iy = (int)fy;                                    // in [-1, W - 1] and [-1, H - 1]
+    const int x0 = min(max(ix, 0), W - 1), x1 = min(max(ix + 1, 0), W - 1);
+    const int y0 = min(max(iy, 0), H - 1), y1 = iy + 1;
+    const bool row2 = y1 >= 0 && y1 < H;
+    const uint8_t* r0 = pic + (long)y0 * W * 3;
+    const uint8_t* r1 = pic + (long)(row2 ? y1 : y0) * W * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int p0 = r0[x0 * 3 + k], p1 = r0[x1 * 3 + k];
+        const double v1 = (double)p0 + (double)(p1 - p0) * dx;              // BILINEAR(v, a, b, d): a + (b - a) * d
+        double v2 = v1;
+        if (row2) {
+            const int q0 = r1[x0 * 3 + k], q1 = r1[x1 * 3 + k];
+            v2 = (double)q0 + (double)(q1 - q0) * dx;
+        }
+        v[k] = (int)(v1 + (v2 - v1) * dy);                                   // (UINT8) v: truncated, in [0, 255]
+    }
+}
+
+// warp of the byte stage's output `src` (n, H, W, 3) + ToTensor + noise; one thread per output pixel
+__global__ __launch_bounds__(256) void warp_finish_kernel(const sat_image_warp* __restrict__ warp, int out_h, int out_w, const uint8_t* __restrict__ src,
+                                                          const float* __restrict__ noise, float noise_std, float* __restrict__ out,
+                                                          uint8_t* __restrict__ out_u8) {
+    const int img = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= out_w || y >= out_h) return;
+    const sat_image_warp w = warp[img];
+    const uint8_t* pic = src + (long)img * out_h * out_w * 3;
+    int v[3] = {0, 0, 0};                                                    // fillcolor (0, 0, 0)
+    if (w.kind == 0) warp_affine_nearest(w.coeffs, x, y, out_w, out_h, pic, v);
+    else warp_perspective_bilinear(w.coeffs, x, y, out_w, out_h, pic, v);
+    finish_pixel(v, img, y, x, out_h, out_w, noise, noise_std, out, out_u8);
+}
+
+struct ImagePlan { int KT, hmax, omax; size_t bounds_off, coeffs_off, tmp_off, pre_off, sums_off, warp_off, total; };
+
+// jit (host, or NULL: no ColorJitter) adds the jitter checks and the workspace of the two jitter kernels; warp (host, or NULL: no
+// optical augmentation) adds the warp checks and the bytes in front of the warp
+static int image_plan(const sat_image_desc* d, const sat_image_jitter* jit, const sat_image_warp* warp, int n, int64_t pixels_bytes, int out_h,
+                      int out_w, ImagePlan* p) {
     SAT_REQUIRE(n > 0 && out_h > 0 && out_w > 0, "image_batch: n=%d out=%dx%d", n, out_h, out_w);
     int KT = 3, hmax = 1;
     for (int i = 0; i < n; ++i) {
@@ -300,6 +372,23 @@ static int image_plan(const sat_image_desc* d, const sat_image_jitter* jit, int 
                         (double)j.saturation);
             SAT_REQUIRE(j.hue_shift >= -128 && j.hue_shift <= 127, "image_batch: picture %d hue shift %d outside [-128, 127]", i, j.hue_shift);
         }
+        if (warp) {
+            const sat_image_warp& w = warp[i];
+            SAT_REQUIRE(w.kind == 0 || w.kind == 1, "image_batch: picture %d warp kind %d is neither 0 (affine) nor 1 (perspective)", i, w.kind);
+            const double* c = w.coeffs;
+            for (int k = 0; k < (w.kind == 0 ? 6 : 8); ++k)
+                SAT_REQUIRE(std::isfinite(c[k]), "image_batch: picture %d warp coefficient %d is not finite (%g)", i, k, c[k]);
+            if (w.kind == 0) {
+                // Pillow's check_fixed at the four corners: where it fails Pillow samples in double, which is not restated here
+                const int cx[4] = {0, out_w, 0, out_w}, cy[4] = {0, 0, out_h, out_h};
+                for (int k = 0; k < 4; ++k) {
+                    const double xs = cx[k] * c[0] + cy[k] * c[1] + c[2], ys = cx[k] * c[3] + cy[k] * c[4] + c[5];
+                    SAT_REQUIRE(std::fabs(xs) < 32768.0 && std::fabs(ys) < 32768.0,
+                                "image_batch: picture %d affine warp maps corner (%d,%d) to (%g,%g), outside the fixed-point range |v| < 32768", i,
+                                cx[k], cy[k], xs, ys);
+                }
+            }
+        }
     }
     p->KT = KT; p->hmax = hmax; p->omax = out_h > out_w ? out_h : out_w;
     size_t off = 0;
@@ -309,6 +398,7 @@ static int image_plan(const sat_image_desc* d, const sat_image_jitter* jit, int 
     p->tmp_off = take((size_t)n * hmax * out_w * sizeof(uchar4));
     p->pre_off = jit ? take((size_t)n * out_h * out_w * sizeof(uchar4)) : 0;
     p->sums_off = jit ? take((size_t)n * sizeof(unsigned long long)) : 0;
+    p->warp_off = warp ? take((size_t)n * out_h * out_w * 3) : 0;
     p->total = off;
     return SAT_OK;
 }
@@ -321,7 +411,7 @@ extern "C" {
 size_t sat_image_batch_workspace_bytes(const sat_image_desc* desc_host, int32_t n, int32_t out_h, int32_t out_w) {
     if (!desc_host) { fail(SAT_EINVAL, "image_batch: null descriptors"); return 0; }
     ImagePlan p;
-    if (image_plan(desc_host, nullptr, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
+    if (image_plan(desc_host, nullptr, nullptr, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
     return p.total;
 }
 
@@ -329,7 +419,15 @@ size_t sat_image_batch_jitter_workspace_bytes(const sat_image_desc* desc_host, c
                                               int32_t out_w) {
     if (!desc_host) { fail(SAT_EINVAL, "image_batch: null descriptors"); return 0; }
     ImagePlan p;
-    if (image_plan(desc_host, jitter_host, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
+    if (image_plan(desc_host, jitter_host, nullptr, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
+    return p.total;
+}
+
+size_t sat_image_batch_warp_workspace_bytes(const sat_image_desc* desc_host, const sat_image_jitter* jitter_host, const sat_image_warp* warp_host,
+                                            int32_t n, int32_t out_h, int32_t out_w) {
+    if (!desc_host) { fail(SAT_EINVAL, "image_batch: null descriptors"); return 0; }
+    ImagePlan p;
+    if (image_plan(desc_host, jitter_host, warp_host, n, -1, out_h, out_w, &p) != SAT_OK) return 0;
     return p.total;
 }
 
@@ -344,16 +442,30 @@ int sat_image_batch_transform_jitter(const uint8_t* pixels, int64_t pixels_bytes
                                      const sat_image_jitter* jitter_host, const sat_image_jitter* jitter_dev, int32_t n, int32_t out_h,
                                      int32_t out_w, const float* noise, float noise_std, float* out_nchw, uint8_t* out_u8, void* workspace,
                                      size_t workspace_bytes, void* stream) {
+    return sat_image_batch_transform_warp(pixels, pixels_bytes, desc_host, desc_dev, jitter_host, jitter_dev, nullptr, nullptr, n, out_h, out_w, noise,
+                                          noise_std, out_nchw, out_u8, workspace, workspace_bytes, stream);
+}
+
+int sat_image_batch_transform_warp(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev,
+                                   const sat_image_jitter* jitter_host, const sat_image_jitter* jitter_dev, const sat_image_warp* warp_host,
+                                   const sat_image_warp* warp_dev, int32_t n, int32_t out_h, int32_t out_w, const float* noise, float noise_std,
+                                   float* out_nchw, uint8_t* out_u8, void* workspace, size_t workspace_bytes, void* stream) {
     if (!pixels || !desc_host || !desc_dev || !workspace || (!out_nchw && !out_u8)) return fail(SAT_EINVAL, "image_batch: null pointer");
     if (!jitter_host != !jitter_dev) return fail(SAT_EINVAL, "image_batch: jitter records given in %s memory only", jitter_host ? "host" : "device");
+    if (!warp_host != !warp_dev) return fail(SAT_EINVAL, "image_batch: warp records given in %s memory only", warp_host ? "host" : "device");
     ImagePlan p;
-    SAT_TRY(image_plan(desc_host, jitter_host, n, pixels_bytes, out_h, out_w, &p));
+    SAT_TRY(image_plan(desc_host, jitter_host, warp_host, n, pixels_bytes, out_h, out_w, &p));
     SAT_REQUIRE(workspace_bytes >= p.total, "image_batch: workspace %zu < %zu bytes", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     int* bounds = (int*)(ws + p.bounds_off);
     int* coeffs = (int*)(ws + p.coeffs_off);
     uchar4* tmp = (uchar4*)(ws + p.tmp_off);
+    // with a warp the last byte stage writes its bytes (no ToTensor, no noise) to the workspace, and the warp kernel finishes
+    uint8_t* warp_src = warp_host ? (uint8_t*)(ws + p.warp_off) : nullptr;
+    const float* stage_noise = warp_host ? nullptr : noise;
+    float* stage_out = warp_host ? nullptr : out_nchw;
+    uint8_t* stage_u8 = warp_host ? warp_src : out_u8;
     hipLaunchKernelGGL(resample_coeffs_kernel, dim3((p.omax + 63) / 64, 2, n), dim3(64), 0, st, desc_dev, out_h, out_w, p.omax, p.KT, bounds, coeffs);
     SAT_TRY(launch_ok("resample_coeffs"));
     hipLaunchKernelGGL(resample_rows_kernel, dim3((out_w + 63) / 64, (p.hmax + 3) / 4, n), dim3(256), 0, st, pixels, desc_dev, out_w, p.omax, p.KT, p.hmax,
@@ -367,12 +479,17 @@ int sat_image_batch_transform_jitter(const uint8_t* pixels, int64_t pixels_bytes
                            p.omax, p.KT, p.hmax, bounds, coeffs, tmp, pre, sums);
         SAT_TRY(launch_ok("resample_cols_jitter"));
         hipLaunchKernelGGL(color_jitter_finish_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, jitter_dev, out_h, out_w, pre, sums,
-                           noise, noise_std, out_nchw, out_u8);
-        return launch_ok("color_jitter_finish");
+                           stage_noise, noise_std, stage_out, stage_u8);
+        SAT_TRY(launch_ok("color_jitter_finish"));
+    } else {
+        hipLaunchKernelGGL(resample_cols_finish_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, desc_dev, out_h, out_w, p.omax, p.KT,
+                           p.hmax, bounds, coeffs, tmp, stage_noise, noise_std, stage_out, stage_u8);
+        SAT_TRY(launch_ok("resample_cols_finish"));
     }
-    hipLaunchKernelGGL(resample_cols_finish_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, desc_dev, out_h, out_w, p.omax, p.KT, p.hmax,
-                       bounds, coeffs, tmp, noise, noise_std, out_nchw, out_u8);
-    return launch_ok("resample_cols_finish");
+    if (!warp_host) return SAT_OK;
+    hipLaunchKernelGGL(warp_finish_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4, n), dim3(256), 0, st, warp_dev, out_h, out_w, warp_src, noise, noise_std,
+                       out_nchw, out_u8);
+    return launch_ok("warp_finish");
 }
 
 }

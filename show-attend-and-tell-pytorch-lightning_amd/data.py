@@ -6,14 +6,15 @@ Host-side mirror of the reference's data path:
   preprocess.ipynb cell 17); ``__getitem__`` returns the *decoded bytes* (H, W, 3) uint8 instead of a transformed tensor.
 * ``BucketSampler``        util.py:48-87 - same grouping and shuffle; additionally rank/world_size aware.
 * ``BatchTransform``       train.py:208-233 - RandomResizedCrop | Resize+CenterCrop, RandomHorizontalFlip, ToTensor,
-  ColorJitter (train.py:223-224), AddGaussianNoise (util.py:121-130) for a whole batch in three kernel launches, four with
-  ColorJitter (``sat_image_batch_transform[_jitter]``): the pictures are resampled and jittered with Pillow's arithmetic
-  bit for bit, the random draws are made on the host in the reference's order (crop parameters, then the flip coin, then
-  ColorJitter's permutation and factors, per picture).
+  ColorJitter (train.py:223-224), the "optical" RandomChoice of RandomPerspective / RandomAffine / RandomRotation
+  (train.py:225-231), AddGaussianNoise (util.py:121-130) for a whole batch in three kernel launches, four with ColorJitter,
+  one more with the optical augmentation (``sat_image_batch_transform[_jitter|_warp]``): the pictures are resampled,
+  jittered and warped with Pillow's arithmetic bit for bit, the random draws are made on the host in the reference's order
+  (crop parameters, then the flip coin, then ColorJitter's permutation and factors, then the optical choice and its
+  parameters, per picture).
 * ``DeviceLoader``         train.py:244-259 DataLoader(pin_memory=True): decode threads -> one pinned staging buffer per
   batch -> one H2D copy on a side stream -> transform; batches arrive as ``(img, caps, lengths)`` on the device.
 
-RandomPerspective / RandomAffine / RandomRotation (train.py:225-231, off by default) are not built.
 There is no CPU path: the transform needs libsat_hip.so and a GPU.
 """
 from __future__ import annotations
@@ -23,6 +24,7 @@ import json
 import math
 import os
 import queue
+import random
 import threading
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
@@ -175,6 +177,84 @@ def color_jitter_params(x, hue=0.03):
     return dict(jitter_order=tuple(fn_idx.tolist()), brightness=b, contrast=c, saturation=s, hue_shift=int(h * 255))
 
 
+def perspective_params(width, height, distortion_scale):
+    """T.RandomPerspective.get_params (torchvision 0.10), drawing from the global torch CPU generator: the picture's corners
+    (start points) and the drawn end points, topleft, topright, botright, botleft."""
+    hw, hh = width // 2, height // 2
+
+    def randint(lo, hi):
+        return int(torch.randint(lo, hi, size=(1,)).item())
+
+    topleft = [randint(0, int(distortion_scale * hw) + 1), randint(0, int(distortion_scale * hh) + 1)]
+    topright = [randint(width - int(distortion_scale * hw) - 1, width), randint(0, int(distortion_scale * hh) + 1)]
+    botright = [randint(width - int(distortion_scale * hw) - 1, width), randint(height - int(distortion_scale * hh) - 1, height)]
+    botleft = [randint(0, int(distortion_scale * hw) + 1), randint(height - int(distortion_scale * hh) - 1, height)]
+    start = [[0, 0], [width - 1, 0], [width - 1, height - 1], [0, height - 1]]
+    return start, [topleft, topright, botright, botleft]
+
+
+def perspective_coeffs(startpoints, endpoints):
+    """torchvision 0.10 F._get_perspective_coeffs: the 8 coefficients of the map from the end points (output) onto the
+    start points (input), Pillow's PERSPECTIVE data; a float32 least-squares solve on the CPU."""
+    a = torch.zeros(2 * len(startpoints), 8, dtype=torch.float)
+    for i, (p1, p2) in enumerate(zip(endpoints, startpoints)):
+        a[2 * i, :] = torch.tensor([p1[0], p1[1], 1, 0, 0, 0, -p2[0] * p1[0], -p2[0] * p1[1]])
+        a[2 * i + 1, :] = torch.tensor([0, 0, 0, p1[0], p1[1], 1, -p2[1] * p1[0], -p2[1] * p1[1]])
+    b = torch.tensor(startpoints, dtype=torch.float).view(8)
+    return torch.linalg.lstsq(a, b, driver="gels").solution.tolist()
+
+
+def inverse_affine_matrix(center, angle, translate, scale, shear):
+    """torchvision 0.10 F._get_inverse_affine_matrix: Pillow's AFFINE data (output -> input) of rotation, shear, scale and
+    translation about ``center``."""
+    rot = math.radians(angle)
+    sx, sy = math.radians(shear[0]), math.radians(shear[1])
+    cx, cy = center
+    tx, ty = translate
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [x / scale for x in (d, -b, 0.0, -c, a, 0.0)]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def rotate_matrix(angle, width, height):
+    """Pillow's Image.rotate(angle) AFFINE data about the picture's centre (no expand, no translate)."""
+    cx, cy = width / 2.0, height / 2.0
+    a = -math.radians(angle % 360.0)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def optical_params(s, size):
+    """train.py:225-231 on a size x size PIL picture, as the fields of its warp record (sat_image_warp): T.RandomChoice picks
+    with Python's ``random.choice``, then the chosen transform draws from the global torch CPU generator.
+      RandomPerspective(0.5 * s, p=1): torch.rand(1) for the coin, 8 randint draws; perspective map, BILINEAR (kind 1)
+      RandomAffine(45 * s, shear=45 * s): angle, then shear_x, uniform in [-45 s, 45 s]; affine map, NEAREST (kind 0)
+      RandomRotation(45 * s): angle uniform in [-45 s, 45 s]; Image.rotate's own matrix, NEAREST (kind 0)"""
+    k = random.choice((0, 1, 2))
+    deg = [-45.0 * s, 45.0 * s]
+    if k == 0:
+        torch.rand(1)                                                    # RandomPerspective.forward: torch.rand(1) < p
+        start, end = perspective_params(size, size, 0.5 * s)
+        return dict(warp_kind=1, warp_coeffs=tuple(perspective_coeffs(start, end)))
+    angle = float(torch.empty(1).uniform_(deg[0], deg[1]).item())
+    if k == 1:
+        shear_x = float(torch.empty(1).uniform_(deg[0], deg[1]).item())
+        m = inverse_affine_matrix([size * 0.5, size * 0.5], angle, [0, 0], 1.0, [shear_x, 0.0])
+    else:
+        m = rotate_matrix(angle, size, size)
+    return dict(warp_kind=0, warp_coeffs=tuple(m) + (0.0, 0.0))
+
+
 def box_desc(h, w, box, size, flip=False):
     """descriptor fields of: crop ``box`` = (top, left, height, width) -> resize to size x size (-> flip)"""
     t, l, ch, cw = box
@@ -190,11 +270,15 @@ def center_desc(h, w, size):
 
 #: descriptor-dict keys of the ColorJitter record of a picture (sat_image_jitter); the other keys are sat_image_desc fields
 JITTER_KEYS = ("jitter_order", "brightness", "contrast", "saturation", "hue_shift")
+#: descriptor-dict keys of the warp record of a picture (sat_image_warp): the kind (0 affine NEAREST, 1 perspective BILINEAR)
+#: and the 8 coefficients of Pillow's inverse map (an affine map uses the first 6)
+WARP_KEYS = ("warp_kind", "warp_coeffs")
 
 
 class StagedBatch:
-    """The decoded pictures of one batch in one pinned host buffer: [descriptors | jitter records | pixels].  The jitter
-    records are there when the descriptor dicts carry ``JITTER_KEYS`` (all of them or none)."""
+    """The decoded pictures of one batch in one pinned host buffer: [descriptors | jitter records | warp records | pixels].
+    The jitter records are there when the descriptor dicts carry ``JITTER_KEYS``, the warp records when they carry
+    ``WARP_KEYS`` (in each case all of them or none)."""
 
     def __init__(self, images, descs):
         n = len(images)
@@ -204,8 +288,13 @@ class StagedBatch:
         if len(has) > 1 or has - {0, len(JITTER_KEYS)}:
             raise ValueError("ColorJitter fields (%s) must be given for every picture of a batch or for none" % ", ".join(JITTER_KEYS))
         self.jitter = (L.ImageJitter * n)() if has == {len(JITTER_KEYS)} else None
+        has = {sum(k in d for k in WARP_KEYS) for d in descs}
+        if len(has) > 1 or has - {0, len(WARP_KEYS)}:
+            raise ValueError("warp fields (%s) must be given for every picture of a batch or for none" % ", ".join(WARP_KEYS))
+        self.warp = (L.ImageWarp * n)() if has == {len(WARP_KEYS)} else None
         self.jitter_off = (C.sizeof(L.ImageDesc) * n + 15) // 16 * 16
-        head = self.jitter_off + (C.sizeof(L.ImageJitter) * n if self.jitter is not None else 0)
+        self.warp_off = (self.jitter_off + (C.sizeof(L.ImageJitter) * n if self.jitter is not None else 0) + 7) // 8 * 8
+        head = self.warp_off + (C.sizeof(L.ImageWarp) * n if self.warp is not None else 0)
         head = (head + 255) // 256 * 256
         total = head + sum(int(im.shape[0]) * int(im.shape[1]) * 3 for im in images)
         self.host = torch.empty(total, dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else torch.empty(total, dtype=torch.uint8)
@@ -219,17 +308,26 @@ class StagedBatch:
             e = self.desc[i]
             e.offset = off
             for k, v in d.items():
-                if k not in JITTER_KEYS:
+                if k not in JITTER_KEYS and k not in WARP_KEYS:
                     setattr(e, k, int(v))
             if self.jitter is not None:
                 j = self.jitter[i]
                 j.order[:] = [int(o) for o in d["jitter_order"]]
                 j.brightness, j.contrast, j.saturation = float(d["brightness"]), float(d["contrast"]), float(d["saturation"])
                 j.hue_shift = int(d["hue_shift"])
+            if self.warp is not None:
+                wr = self.warp[i]
+                coeffs = [float(c) for c in d["warp_coeffs"]]
+                if len(coeffs) not in (6, 8):
+                    raise ValueError("picture %d: %d warp coefficients, expected 6 (affine) or 8 (perspective)" % (i, len(coeffs)))
+                wr.kind = int(d["warp_kind"])
+                wr.coeffs[:] = coeffs + [0.0] * (8 - len(coeffs))
             off += nb
         buf[:C.sizeof(L.ImageDesc) * n] = np.frombuffer(self.desc, dtype=np.uint8)
         if self.jitter is not None:
             buf[self.jitter_off:self.jitter_off + C.sizeof(L.ImageJitter) * n] = np.frombuffer(self.jitter, dtype=np.uint8)
+        if self.warp is not None:
+            buf[self.warp_off:self.warp_off + C.sizeof(L.ImageWarp) * n] = np.frombuffer(self.warp, dtype=np.uint8)
         self.head, self.pixels_bytes = head, off
 
 
@@ -237,24 +335,32 @@ class BatchTransform:
     """train.py:208-233 for a batch.  ``train=False``: Resize + CenterCrop + ToTensor (valid_transforms).
     ``train=True``: aug_scale == 1 -> Resize + CenterCrop, else RandomResizedCrop(scale=(aug_scale, 1)); a flip with
     probability aug_hflip when 0 < aug_hflip < 1; T.ColorJitter(x, x, x, hue=0.03) when aug_color_jitter = x is not 0 and
-    at most 1 (a larger x is ignored, as the reference does; a negative one raises, as torchvision does); ToTensor;
+    at most 1 (a larger x is ignored, as the reference does; a negative one raises, as torchvision does);
+    T.RandomChoice([RandomPerspective(0.5 s, p=1), RandomAffine(45 s, shear=45 s), RandomRotation(45 s)]) when
+    aug_optical_strength = s is not 0 and at most 1 (the same rules; a negative s raises, as RandomAffine does); ToTensor;
     + N(0,1) * aug_noise_std.
     ``randn(shape, device)`` supplies the noise draws (default: ``torch.randn`` on the device)."""
 
-    def __init__(self, input_size, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, randn=None, aug_color_jitter=0.0):
+    def __init__(self, input_size, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, randn=None, aug_color_jitter=0.0,
+                 aug_optical_strength=0.0):
         if train and not (0 <= aug_scale <= 1.0):
             raise ValueError("Invalid value for aug_scale. Choose in the range {0,1}.")       # train.py:219-220
         x = float(aug_color_jitter)
         self.jitter = train and x != 0 and x <= 1.0                                           # train.py:223
         if self.jitter and x < 0:
             raise ValueError("If brightness is a single number, it must be non negative.")   # T.ColorJitter._check_input
+        o = float(aug_optical_strength)
+        self.optical = train and o != 0 and o <= 1.0                                          # train.py:225
+        if self.optical and o < 0:
+            raise ValueError("If degrees is a single number, it must be positive.")          # T.RandomAffine's _setup_angle
         self.size, self.train = int(input_size), train
         self.aug_scale, self.aug_hflip, self.noise_std, self.randn = aug_scale, aug_hflip, aug_noise_std, randn
-        self.aug_color_jitter = x
+        self.aug_color_jitter, self.aug_optical_strength = x, o
         self._ws = None
 
     def draw(self, shapes):
-        """one descriptor per picture; consumes the torch CPU generator in the reference's per-sample order"""
+        """one descriptor per picture; consumes the torch CPU generator (and, for the optical choice, Python's ``random``)
+        in the reference's per-sample order"""
         out = []
         for h, w in shapes:
             if not self.train or self.aug_scale == 1.0:
@@ -265,6 +371,8 @@ class BatchTransform:
                 d["flip"] = int(torch.rand(1).item() < self.aug_hflip)            # T.RandomHorizontalFlip.forward
             if self.jitter:
                 d.update(color_jitter_params(self.aug_color_jitter))
+            if self.optical:
+                d.update(optical_params(self.aug_optical_strength, self.size))
             out.append(d)
         return out
 
@@ -282,8 +390,11 @@ class BatchTransform:
         S, n = self.size, staged.n
         with torch.cuda.stream(stream):
             dev = staged.host.to(device, non_blocking=True)
-            jit = staged.jitter
-            if jit is None:
+            jit, warp = staged.jitter, staged.warp
+            if warp is not None:
+                need = lib.sat_image_batch_warp_workspace_bytes(C.cast(staged.desc, C.c_void_p), C.cast(jit, C.c_void_p) if jit is not None else None,
+                                                                C.cast(warp, C.c_void_p), n, S, S)
+            elif jit is None:
                 need = lib.sat_image_batch_workspace_bytes(C.cast(staged.desc, C.c_void_p), n, S, S)
             else:
                 need = lib.sat_image_batch_jitter_workspace_bytes(C.cast(staged.desc, C.c_void_p), C.cast(jit, C.c_void_p), n, S, S)
@@ -300,7 +411,12 @@ class BatchTransform:
                 assert noise.shape == out.shape and noise.dtype == torch.float32 and noise.is_contiguous()
             tail = (n, S, S, L.ptr(noise) if noise is not None else None, float(self.noise_std if noise is not None else 0.0), L.ptr(out),
                     L.ptr(raw) if raw is not None else None, L.ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream))
-            if jit is None:
+            if warp is not None:
+                jit_ptrs = (C.cast(jit, C.c_void_p), dev.data_ptr() + staged.jitter_off) if jit is not None else (None, None)
+                L.check(lib.sat_image_batch_transform_warp(dev.data_ptr() + staged.head, staged.pixels_bytes, C.cast(staged.desc, C.c_void_p),
+                                                           dev.data_ptr(), *jit_ptrs, C.cast(warp, C.c_void_p), dev.data_ptr() + staged.warp_off, *tail),
+                        "sat_image_batch_transform_warp")
+            elif jit is None:
                 L.check(lib.sat_image_batch_transform(dev.data_ptr() + staged.head, staged.pixels_bytes, C.cast(staged.desc, C.c_void_p), dev.data_ptr(),
                                                       *tail), "sat_image_batch_transform")
             else:

@@ -1,13 +1,16 @@
 """Input pipeline: one C2-sized batch of decoded pictures (128 x 480x640 RGB bytes) -> (128, 3, 224, 224)
 fp32 through sat_image_batch_transform, against Pillow doing the same crop + BILINEAR resize (+ numpy ToTensor) on the host.
 With --color-jitter X the same batch also goes through T.ColorJitter(X, X, X, 0.03) (sat_image_batch_transform_jitter), and
-both rates are reported from the same run.
-    python tools/bench_input_pipeline.py [--batch 128] [--size 224] [--color-jitter 0.4]
+both rates are reported from the same run.  With --optical S the same batch (with the ColorJitter draws too when
+--color-jitter is given) also goes through the reference's RandomChoice of RandomPerspective / RandomAffine / RandomRotation
+at strength S (sat_image_batch_transform_warp).
+    python tools/bench_input_pipeline.py [--batch 128] [--size 224] [--color-jitter 0.4] [--optical 0.5]
 """
 import argparse
 import ctypes as C
 import json
 import os
+import random
 import sys
 import time
 
@@ -40,8 +43,10 @@ def measure(tf, staged, noise, iters):
     with_copy_ms = time_ms(lambda: tf.run(staged, dev, noise=noise), iters)       # H2D copy of 118 MB + the kernels
     lib = L.lib()
     resident = staged.host.to(dev)                                               # kernels only: pixels already resident
-    desc, jit = C.cast(staged.desc, C.c_void_p), staged.jitter
-    if jit is None:
+    desc, jit, warp = C.cast(staged.desc, C.c_void_p), staged.jitter, staged.warp
+    if warp is not None:
+        need = lib.sat_image_batch_warp_workspace_bytes(desc, C.cast(jit, C.c_void_p) if jit is not None else None, C.cast(warp, C.c_void_p), B, S, S)
+    elif jit is None:
         need = lib.sat_image_batch_workspace_bytes(desc, B, S, S)
     else:
         need = lib.sat_image_batch_jitter_workspace_bytes(desc, C.cast(jit, C.c_void_p), B, S, S)
@@ -50,7 +55,12 @@ def measure(tf, staged, noise, iters):
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def kernels():
-        if jit is None:
+        if warp is not None:
+            jit_ptrs = (C.cast(jit, C.c_void_p), resident.data_ptr() + staged.jitter_off) if jit is not None else (None, None)
+            L.check(lib.sat_image_batch_transform_warp(resident.data_ptr() + staged.head, staged.pixels_bytes, desc, resident.data_ptr(), *jit_ptrs,
+                                                       C.cast(warp, C.c_void_p), resident.data_ptr() + staged.warp_off, B, S, S, L.ptr(noise),
+                                                       0.01, L.ptr(out), None, L.ptr(ws), need, st), "transform_warp")
+        elif jit is None:
             L.check(lib.sat_image_batch_transform(resident.data_ptr() + staged.head, staged.pixels_bytes, desc, resident.data_ptr(),
                                                   B, S, S, L.ptr(noise), 0.01, L.ptr(out), None, L.ptr(ws), need, st), "transform")
         else:
@@ -66,6 +76,7 @@ def main():
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--color-jitter", type=float, default=0.0, help="also time T.ColorJitter(X, X, X, 0.03) on the same batch")
+    ap.add_argument("--optical", type=float, default=0.0, help="also time the optical augmentation of strength S on the same batch")
     a = ap.parse_args()
     H, W, S, B = 480, 640, a.size, a.batch
     rng = np.random.default_rng(0)
@@ -87,6 +98,7 @@ def main():
            "algorithmic_GBps": round(alg_bytes / kern_ms / 1e6, 1),
            "with_h2d_ms": round(with_copy_ms, 3), "with_h2d_images_per_s": round(B / with_copy_ms * 1e3, 1),
            "h2d_bytes": int(staged.host.numel()), "host_stage_ms": round(stage_s * 1e3, 2)}
+    jdescs = None
     if a.color_jitter:
         x = a.color_jitter
         tfj = D.BatchTransform(S, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, aug_color_jitter=x)
@@ -100,6 +112,20 @@ def main():
         res.update({"color_jitter": x, "jitter_kernels_ms": round(jk_ms, 4), "jitter_kernels_images_per_s": round(B / jk_ms * 1e3, 1),
                     "jitter_with_h2d_ms": round(jw_ms, 3), "jitter_with_h2d_images_per_s": round(B / jw_ms * 1e3, 1),
                     "plain_again_kernels_ms": round(k2_ms, 4), "plain_again_with_h2d_ms": round(w2_ms, 3)})
+    if a.optical:
+        o = a.optical
+        tfo = D.BatchTransform(S, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, aug_color_jitter=a.color_jitter, aug_optical_strength=o)
+        if not tfo.optical:
+            raise SystemExit("--optical %g: the reference applies no optical augmentation for this value (0 < s <= 1)" % o)
+        random.seed(2)
+        torch.manual_seed(2)
+        odescs = [dict(d, **D.optical_params(o, S)) for d in (jdescs or descs)]          # same crops (and jitter), warp draws added
+        ow_ms, ok_ms = measure(tfo, tfo.stage(imgs, odescs), noise, a.iters)
+        w3_ms, k3_ms = measure(tf, staged, noise, a.iters)
+        res.update({"optical": o, "optical_with_jitter": bool(jdescs), "optical_kinds": [sum(d["warp_kind"] == k for d in odescs) for k in (0, 1)],
+                    "optical_kernels_ms": round(ok_ms, 4), "optical_kernels_images_per_s": round(B / ok_ms * 1e3, 1),
+                    "optical_with_h2d_ms": round(ow_ms, 3), "optical_with_h2d_images_per_s": round(B / ow_ms * 1e3, 1),
+                    "plain_after_optical_kernels_ms": round(k3_ms, 4), "plain_after_optical_with_h2d_ms": round(w3_ms, 3)})
     # host: Pillow on one thread, a sample of the same batch
     from PIL import Image
     n_cpu = min(B, 32)
