@@ -562,6 +562,42 @@ int sat_image_batch_transform_warp(const uint8_t* pixels, int64_t pixels_bytes, 
                                    const sat_image_warp* warp_dev, int32_t n, int32_t out_h, int32_t out_w, const float* noise, float noise_std,
                                    float* out_nchw, uint8_t* out_u8, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- baseline JPEG decoding on device ---------------------------------------------------------------------------------
+ * The step in front of the transform: util.py:136-137's Image.open(f).convert("RGB") for Huffman-coded sequential 8-bit
+ * files (SOF0 / SOF1) with one scan of 1 (grayscale) or 3 YCbCr components, luma sampled h1v1, h2v1 or h2v2 and chroma
+ * 1x1, with or without restart markers; bit exact with libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling).  The
+ * host parses the headers (sat_amd/jpeg.py) and sends every other file to Pillow.  Three launches: entropy decoding (one
+ * thread per picture and restart segment), dequantisation + ISLOW IDCT (per block), upsampling + YCbCr->RGB (per pixel).
+ * The (height, width, 3) bytes of each picture are written at its out_offset in `pixels`.
+ *   data_offset, data_bytes   the entropy-coded data of the scan in `compressed`, RST markers included, 0xFF00 stuffed
+ *   segments_offset           byte offset in `compressed` of n_segments (start, end) uint32 pairs, 4-byte aligned: the
+ *                             restart segments relative to data_offset, the markers themselves excluded
+ *   restart_interval          MCUs per segment (DRI), 0: one segment
+ *   block_offset, segment_base  coefficient blocks and segments of the pictures in front of this one (prefix sums; checked)
+ *   quant, dc_table, ac_table per component (Y, Cb, Cr; a grayscale picture uses [0]): indices into the table arrays
+ *   h_samp, v_samp            luma sampling factors (1,1) (2,1) (2,2); a grayscale picture uses (1,1)
+ * status (n int32, device): 0, or an OR of 1 bad Huffman code, 2 ran out of data, 4 coefficient index past 63, 8 bad
+ * segment bounds, 16 a marker inside a segment.  The rest of the batch is unaffected by a bad stream.                     */
+typedef struct sat_jpeg_desc {
+    int64_t data_offset, data_bytes, segments_offset, out_offset, block_offset;
+    int32_t height, width, components, h_samp, v_samp, restart_interval, n_segments, segment_base;
+    int32_t quant[3], dc_table[3], ac_table[3];
+    int32_t reserved;
+} sat_jpeg_desc;
+typedef struct sat_jpeg_qtable {
+    uint16_t q[64];                                    /* natural (row-major) order                                     */
+} sat_jpeg_qtable;
+typedef struct sat_jpeg_htable {
+    uint16_t lookup[512];                              /* next 9 bits -> (length << 8) | symbol; 0: the code is longer   */
+    int32_t maxcode[18];                               /* [l]: largest code of length l, -1 none; [17] = 0xFFFFF          */
+    int32_t valoffset[18];                             /* symbol index = code + valoffset[l]                             */
+    uint8_t huffval[256];
+} sat_jpeg_htable;
+size_t sat_jpeg_decode_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n);
+int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
+                          int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
+                          uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,21 @@ class ImageWarp(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("coeffs", C.c_double * 8)]
 
 
+class JpegDesc(C.Structure):
+    """sat_jpeg_desc (include/sat_hip.h): one picture of sat_jpeg_decode_batch"""
+    _fields_ = [(k, C.c_int64) for k in ("data_offset", "data_bytes", "segments_offset", "out_offset", "block_offset")] + \
+               [(k, C.c_int32) for k in ("height", "width", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "segment_base")] + \
+               [(k, C.c_int32 * 3) for k in ("quant", "dc_table", "ac_table")] + [("reserved", C.c_int32)]
+
+
+class JpegQTable(C.Structure):
+    _fields_ = [("q", C.c_uint16 * 64)]
+
+
+class JpegHTable(C.Structure):
+    _fields_ = [("lookup", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoffset", C.c_int32 * 18), ("huffval", C.c_uint8 * 256)]
+
+
 class DecoderBatch(C.Structure):
     _fields_ = [("ann", C.c_void_p), ("caps", C.c_void_p), ("lengths", C.c_void_p), ("prow", C.c_void_p), ("src_row", C.c_void_p),
                 ("step_offsets_host", C.c_void_p), ("teacher_host", C.c_void_p)]
@@ -244,6 +259,8 @@ SYMBOLS.update({"sat_image_batch_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32
                 "sat_image_batch_warp_workspace_bytes": (C.c_size_t, [_vp, _vp, _vp, _i32, _i32, _i32]),
                 "sat_image_batch_transform_warp": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f, _vp, _vp, _vp,
                                                              C.c_size_t, _vp])})
+SYMBOLS.update({"sat_jpeg_decode_workspace_bytes": (C.c_size_t, [_vp, _i32]),
+                "sat_jpeg_decode_batch": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp])})
 SYMBOLS.update({"sat_profile_start": (C.c_int, []),
                 "sat_profile_start_only": (C.c_int, [C.c_char_p]),
                 "sat_profile_pause": (C.c_int, [_i32]),

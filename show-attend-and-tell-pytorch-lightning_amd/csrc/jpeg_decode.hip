@@ -1,0 +1,444 @@
+// Baseline JPEG decoding on device: util.py:136-137's Image.open(f).convert("RGB") for the files sat_amd/jpeg.py classifies
+// as GPU-decodable, bit exact with Pillow's libjpeg-turbo at its defaults (JDCT_ISLOW, fancy upsampling, no block smoothing).
+//   1. entropy decoding: one thread (lane 0 of a wave) per picture and restart segment.  Huffman codes through a 9-bit lookup
+//      table plus libjpeg's maxcode / valoffset search for longer codes; the picture's tables sit in LDS.  The coefficient
+//      blocks were cleared first, so only the non-zero coefficients are stored (int16, natural order).
+//   2. dequantisation + jidctint.c's jpeg_idct_islow, one thread per 8x8 block, operation for operation, output through
+//      libjpeg's range_limit table (a wrap, not a clamp, for overshooting coefficients).
+//   3. jdsample.c's fancy upsampling (h2v1, h2v2; plain replication when the chroma is at most 2 samples wide) and jdcolor.c's
+//      fixed-point YCbCr->RGB, one thread per output pixel.
+// Integer arithmetic only.  Every read is bounded by the segment and the table arrays, every write by the picture's blocks
+// and its (height, width, 3) output; a bad stream sets the picture's status word and leaves the other pictures alone.
+#include "../../include/sat_hip.h"
+#include "common.h"
+
+namespace sat {
+namespace {
+
+constexpr int JPEG_LOOKAHEAD = 9;
+constexpr int JPEG_BAD_CODE = 1, JPEG_OUT_OF_DATA = 2, JPEG_BAD_INDEX = 4, JPEG_BAD_SEGMENT = 8, JPEG_MARKER = 16;
+
+__constant__ uint8_t k_natural_order[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// geometry of component c of a picture: its blocks per row / column in the coefficient array and the samples that are real
+struct CompGeom {
+    int bw, bh;          // blocks (every block of every MCU: the array libjpeg's coefficient controller holds)
+    int dw, dh;          // downsampled_width / downsampled_height
+    int hs, vs;          // this component's sampling factors
+};
+
+__host__ __device__ inline CompGeom comp_geom(const sat_jpeg_desc& d, int c) {
+    CompGeom g;
+    if (d.components == 1) {
+        g.bw = (d.width + 7) / 8; g.bh = (d.height + 7) / 8;
+        g.dw = d.width; g.dh = d.height; g.hs = g.vs = 1;
+        return g;
+    }
+    const int mx = (d.width + 8 * d.h_samp - 1) / (8 * d.h_samp), my = (d.height + 8 * d.v_samp - 1) / (8 * d.v_samp);
+    g.hs = c == 0 ? d.h_samp : 1;
+    g.vs = c == 0 ? d.v_samp : 1;
+    g.bw = mx * g.hs; g.bh = my * g.vs;
+    g.dw = (d.width * g.hs + d.h_samp - 1) / d.h_samp;          // jdinput.c: ceil(image_width * h / max_h)
+    g.dh = (d.height * g.vs + d.v_samp - 1) / d.v_samp;
+    return g;
+}
+
+__host__ __device__ inline long picture_blocks(const sat_jpeg_desc& d) {
+    long total = 0;
+    for (int c = 0; c < d.components; ++c) { CompGeom g = comp_geom(d, c); total += (long)g.bw * g.bh; }
+    return total;
+}
+
+__host__ __device__ inline long picture_mcus(const sat_jpeg_desc& d) {
+    if (d.components == 1) return (long)((d.width + 7) / 8) * ((d.height + 7) / 8);
+    return (long)((d.width + 8 * d.h_samp - 1) / (8 * d.h_samp)) * ((d.height + 8 * d.v_samp - 1) / (8 * d.v_samp));
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 1. entropy
+// Bit reader over one restart segment: bytes [pos, end) of the picture's data, 0xFF00 -> 0xFF.  Past the end (or at a
+// marker) it shifts in zero bytes, as libjpeg does, and counts them: consuming any of those bits is "ran out of data".
+struct BitReader {
+    const uint8_t* base;     // the compressed buffer
+    long abs0;               // absolute offset of the picture's data
+    long pos, end;           // relative to abs0
+    long limit;              // compressed_bytes: bound for the aligned word loads
+    uint64_t buf;            // bits, left-aligned
+    int cnt;                 // valid bits in buf
+    int fill;                // zero bytes shifted in past the end
+    int flags;
+    long word_idx;
+    uint32_t word;
+
+    __device__ inline int byte_at(long rel) {
+        const long a = abs0 + rel;
+        const long w = a >> 2;
+        if (w != word_idx) {
+            if ((w << 2) + 4 <= limit) word = *reinterpret_cast<const uint32_t*>(base + (w << 2));
+            else {
+                word = 0;
+                for (int k = 0; k < 4 && (w << 2) + k < limit; ++k) word |= (uint32_t)base[(w << 2) + k] << (8 * k);
+            }
+            word_idx = w;
+        }
+        return (word >> (8 * (a & 3))) & 0xFF;
+    }
+
+    __device__ inline void refill() {
+        while (cnt <= 56) {
+            int v = 0;
+            if (pos < end) {
+                v = byte_at(pos++);
+                if (v == 0xFF) {
+                    const int nx = pos < end ? byte_at(pos) : 0;
+                    if (nx == 0) ++pos;
+                    else { flags |= JPEG_MARKER; pos = end; v = 0; ++fill; }
+                }
+            } else {
+                ++fill;
+            }
+            buf |= (uint64_t)v << (56 - cnt);
+            cnt += 8;
+            if (fill > 64) fill = 64;       // enough to flag it; keeps the counter bounded
+        }
+    }
+
+    __device__ inline uint32_t peek(int n) { return (uint32_t)(buf >> (64 - n)); }
+    __device__ inline void skip(int n) { buf <<= n; cnt -= n; }
+    __device__ inline bool overrun() const { return fill * 8 > cnt; }
+};
+
+__device__ inline int huff_decode(BitReader& br, const sat_jpeg_htable& t) {
+    br.refill();
+    const int e = t.lookup[br.peek(JPEG_LOOKAHEAD)];
+    if (e) { br.skip(e >> 8); return e & 0xFF; }
+    const uint32_t w = br.peek(16);
+    for (int l = JPEG_LOOKAHEAD + 1; l <= 16; ++l) {
+        const int code = (int)(w >> (16 - l));
+        if (code <= t.maxcode[l]) {
+            const int idx = code + t.valoffset[l];
+            if (idx < 0 || idx > 255) break;
+            br.skip(l);
+            return t.huffval[idx];
+        }
+    }
+    br.flags |= JPEG_BAD_CODE;
+    return -1;
+}
+
+__device__ inline int receive_extend(BitReader& br, int s) {
+    if (s == 0) return 0;
+    br.refill();
+    const int r = (int)br.peek(s);
+    br.skip(s);
+    return r < (1 << (s - 1)) ? r + (int)((~0u << s) + 1u) : r;       // HUFF_EXTEND
+}
+
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                          int n, const sat_jpeg_htable* __restrict__ huff, int16_t* __restrict__ coefs,
+                                                          int* __restrict__ status) {
+    __shared__ sat_jpeg_htable tabs[6];
+    const int seg_global = blockIdx.x;
+    int lo = 0, hi = n - 1;                                   // picture: last one whose segment_base <= seg_global
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[mid].segment_base <= seg_global) lo = mid; else hi = mid - 1;
+    }
+    const int p = lo;
+    const sat_jpeg_desc& d = desc[p];                        // a reference: a local copy's arrays would live in scratch memory
+    const int seg = seg_global - d.segment_base;
+    if (seg < 0 || seg >= d.n_segments) return;
+    const int nt = 2 * d.components;
+    for (int t = 0; t < nt; ++t) {
+        const int idx = (t & 1) ? d.ac_table[t >> 1] : d.dc_table[t >> 1];
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(huff + idx);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&tabs[t]);
+        for (int k = threadIdx.x; k < (int)(sizeof(sat_jpeg_htable) / 4); k += 64) dst[k] = src[k];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+
+    const uint32_t* segtab = reinterpret_cast<const uint32_t*>(comp + d.segments_offset);
+    const long s0 = segtab[2 * seg], s1 = segtab[2 * seg + 1];
+    if (s0 > s1 || s1 > d.data_bytes) { atomicOr(status + p, JPEG_BAD_SEGMENT); return; }
+    BitReader br;
+    br.base = comp; br.abs0 = d.data_offset; br.pos = s0; br.end = s1; br.limit = comp_bytes;
+    br.buf = 0; br.cnt = 0; br.fill = 0; br.flags = 0; br.word_idx = -1; br.word = 0;
+
+    const long total = picture_mcus(d);
+    const long m0 = d.restart_interval ? (long)seg * d.restart_interval : 0;
+    const long m1 = d.restart_interval ? min(total, m0 + d.restart_interval) : total;
+    // per-component values as scalars (a run-time index into small arrays would put them in scratch memory)
+    const CompGeom g0 = comp_geom(d, 0);
+    const int hs = g0.hs, vs = g0.vs, bw0 = g0.bw;
+    const int mx = d.components == 1 ? bw0 : bw0 / hs;
+    const int bwc = mx;                                        // chroma: one block per MCU
+    const long base0 = d.block_offset, base1 = base0 + (long)g0.bw * g0.bh, base2 = base1 + (d.components == 3 ? (long)mx * (g0.bh / vs) : 0);
+    const int ny = hs * vs, slots = ny + (d.components == 3 ? 2 : 0);
+    int dc0 = 0, dc1 = 0, dc2 = 0;
+    for (long m = m0; m < m1 && !(br.flags & ~JPEG_MARKER); ++m) {
+        const int mcu_x = (int)(m % mx), mcu_y = (int)(m / mx);
+        for (int slot = 0; slot < slots && !(br.flags & ~JPEG_MARKER); ++slot) {
+            const int c = slot < ny ? 0 : slot - ny + 1;
+            long bi;
+            if (c == 0) bi = base0 + (long)(mcu_y * vs + slot / hs) * bw0 + mcu_x * hs + slot % hs;
+            else bi = (c == 1 ? base1 : base2) + (long)mcu_y * bwc + mcu_x;
+            int16_t* blk = coefs + bi * 64;
+            const sat_jpeg_htable& dct = tabs[2 * c];
+            const sat_jpeg_htable& act = tabs[2 * c + 1];
+            int s = huff_decode(br, dct);
+            if (s > 15) br.flags |= JPEG_BAD_CODE;
+            if (s >= 0 && s <= 15) {
+                const int diff = receive_extend(br, s);
+                const int dcv = (c == 0 ? dc0 : (c == 1 ? dc1 : dc2)) + diff;
+                if (c == 0) dc0 = dcv; else if (c == 1) dc1 = dcv; else dc2 = dcv;
+                if (dcv) blk[0] = (int16_t)dcv;
+                for (int k = 1; k < 64; ++k) {
+                    const int rs = huff_decode(br, act);
+                    if (rs < 0) break;
+                    const int r = rs >> 4;
+                    s = rs & 15;
+                    if (s) {
+                        k += r;
+                        if (k > 63) { br.flags |= JPEG_BAD_INDEX; break; }
+                        blk[k_natural_order[k]] = (int16_t)receive_extend(br, s);
+                    } else {
+                        if (r != 15) break;
+                        k += 15;
+                    }
+                }
+            }
+            if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
+        }
+    }
+    if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
+    if (br.flags) atomicOr(status + p, br.flags);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 2. IDCT
+// jidctint.c, CONST_BITS 13, PASS1_BITS 2; JLONG arithmetic (64-bit) and an int workspace, as libjpeg on LP64.
+constexpr int CB = 13, P1 = 2;
+constexpr long F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299, F1_847 = 15137,
+               F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
+
+__device__ inline long descale(long x, int n) { return (x + (1L << (n - 1))) >> n; }
+
+// one 1-D pass: in[0..7] -> out[0..7] descaled by `sh`
+template <typename T>
+__device__ inline void idct_1d(const T* in, long* out, int sh) {
+    long z2 = in[2], z3 = in[6];
+    long z1 = (z2 + z3) * F0_541;
+    long tmp2 = z1 + z3 * (-F1_847);
+    long tmp3 = z1 + z2 * F0_765;
+    z2 = in[0]; z3 = in[4];
+    long tmp0 = (z2 + z3) << CB;
+    long tmp1 = (z2 - z3) << CB;
+    const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = in[7]; tmp1 = in[5]; tmp2 = in[3]; tmp3 = in[1];
+    z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
+    long z4 = tmp1 + tmp3;
+    const long z5 = (z3 + z4) * F1_175;
+    tmp0 *= F0_298; tmp1 *= F2_053; tmp2 *= F3_072; tmp3 *= F1_501;
+    z1 *= -F0_899; z2 *= -F2_562; z3 *= -F1_961; z4 *= -F0_390;
+    z3 += z5; z4 += z5;
+    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+    out[0] = descale(tmp10 + tmp3, sh); out[7] = descale(tmp10 - tmp3, sh);
+    out[1] = descale(tmp11 + tmp2, sh); out[6] = descale(tmp11 - tmp2, sh);
+    out[2] = descale(tmp12 + tmp1, sh); out[5] = descale(tmp12 - tmp1, sh);
+    out[3] = descale(tmp13 + tmp0, sh); out[4] = descale(tmp13 - tmp0, sh);
+}
+
+// IDCT_range_limit(cinfo)[x & RANGE_MASK] (jdmaster.c prepare_range_limit_table): x in [-128, 127] -> x + 128; the rest of
+// [128, 511] -> 255, of [512, 895] -> 0; [896, 1023] (x < -128 read modulo 1024) -> x - 896
+__device__ inline uint8_t range_limit(long x) {
+    const int y = (int)x & 1023;
+    if (y < 128) return (uint8_t)(y + 128);
+    if (y < 512) return 255;
+    if (y < 896) return 0;
+    return (uint8_t)(y - 896);
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const sat_jpeg_desc* __restrict__ desc, const sat_jpeg_qtable* __restrict__ quant,
+                                                        const int16_t* __restrict__ coefs, uint8_t* __restrict__ planes) {
+    const sat_jpeg_desc& d = desc[blockIdx.y];
+    const CompGeom g0 = comp_geom(d, 0), g1 = comp_geom(d, d.components - 1);          // g1: both chroma components
+    const long nb0 = (long)g0.bw * g0.bh, nb1 = d.components == 3 ? (long)g1.bw * g1.bh : 0;
+    const long total = nb0 + 2 * nb1;
+    for (long b = (long)blockIdx.x * blockDim.x + threadIdx.x; b < total; b += (long)gridDim.x * blockDim.x) {
+        const int c = b < nb0 ? 0 : (b < nb0 + nb1 ? 1 : 2);
+        const long lb = c == 0 ? b : (c == 1 ? b - nb0 : b - nb0 - nb1);
+        const int bw = c == 0 ? g0.bw : g1.bw;
+        const uint16_t* q = quant[d.quant[c]].q;
+        const long gb = d.block_offset + b;
+        int16_t in[64];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) reinterpret_cast<uint4*>(in)[k] = reinterpret_cast<const uint4*>(coefs + gb * 64)[k];
+        int ws[64];
+#pragma unroll
+        for (int col = 0; col < 8; ++col) {                  // pass 1: columns, into the int workspace
+            long x[8], y[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = (long)in[8 * k + col] * (long)q[8 * k + col];
+            idct_1d(x, y, CB - P1);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) ws[8 * k + col] = (int)y[k];
+        }
+        const long row0 = (lb / bw) * 8, col0 = (lb % bw) * 8;
+        uint8_t* out = planes + gb * 64 - lb * 64 + row0 * (bw * 8) + col0;      // the component's plane starts at its first block * 64
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {                        // pass 2: rows
+            long y[8];
+            idct_1d(ws + 8 * r, y, CB + P1 + 3);
+            uint64_t v = 0;
+            for (int k = 0; k < 8; ++k) v |= (uint64_t)range_limit((long)(int)y[k]) << (8 * k);
+            *reinterpret_cast<uint64_t*>(out + (long)r * bw * 8) = v;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 3. colour
+__device__ inline int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// the component's sample at output pixel (x, y) after jdsample.c's upsampling
+__device__ inline int upsampled(const uint8_t* P, const CompGeom& g, int hmax, int vmax, int x, int y) {
+    const int pw = g.bw * 8;
+    if (g.hs == hmax && g.vs == vmax) return P[(long)y * pw + x];                     // fullsize
+    const int i = x >> 1;
+    if (g.dw <= 2) return P[(long)(vmax == 2 ? y >> 1 : y) * pw + i];                   // h2v1_upsample / h2v2_upsample
+    if (vmax == 1) {                                                                  // h2v1_fancy_upsample
+        const uint8_t* row = P + (long)y * pw;
+        const int s = 3 * row[i];
+        return (x & 1) ? (s + row[min(i + 1, g.dw - 1)] + 2) >> 2 : (s + row[max(i - 1, 0)] + 1) >> 2;
+    }
+    const int j = y >> 1;                                                             // h2v2_fancy_upsample
+    const int jf = (y & 1) ? min(j + 1, g.dh - 1) : max(j - 1, 0);
+    const uint8_t* near = P + (long)j * pw;
+    const uint8_t* far = P + (long)jf * pw;
+    const int cs = 3 * near[i] + far[i];
+    if (x & 1) {
+        const int k = min(i + 1, g.dw - 1);
+        return (3 * cs + 3 * near[k] + far[k] + 7) >> 4;
+    }
+    const int k = max(i - 1, 0);
+    return (3 * cs + 3 * near[k] + far[k] + 8) >> 4;
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const sat_jpeg_desc* __restrict__ desc, const uint8_t* __restrict__ planes,
+                                                         uint8_t* __restrict__ pixels) {
+    const sat_jpeg_desc d = desc[blockIdx.y];
+    CompGeom g[3];
+    const uint8_t* P[3];
+    long base = d.block_offset * 64;
+    for (int c = 0; c < d.components; ++c) { g[c] = comp_geom(d, c); P[c] = planes + base; base += (long)g[c].bw * g[c].bh * 64; }
+    const int hmax = d.components == 3 ? d.h_samp : 1, vmax = d.components == 3 ? d.v_samp : 1;
+    const long npx = (long)d.height * d.width;
+    uint8_t* out = pixels + d.out_offset;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < npx; t += (long)gridDim.x * blockDim.x) {
+        const int y = (int)(t / d.width), x = (int)(t % d.width);
+        const int Y = P[0][(long)y * (g[0].bw * 8) + x];
+        int r = Y, gg = Y, b = Y;
+        if (d.components == 3) {
+            const int cb = upsampled(P[1], g[1], hmax, vmax, x, y) - 128, cr = upsampled(P[2], g[2], hmax, vmax, x, y) - 128;
+            // jdcolor.c build_ycc_rgb_table, SCALEBITS 16: FIX(1.40200) = 91881, FIX(1.77200) = 116130, FIX(0.71414) = 46802,
+            // FIX(0.34414) = 22554, ONE_HALF = 32768
+            r = clamp255(Y + ((91881 * cr + 32768) >> 16));
+            gg = clamp255(Y + ((-46802 * cr + (-22554 * cb + 32768)) >> 16));
+            b = clamp255(Y + ((116130 * cb + 32768) >> 16));
+        }
+        out[3 * t] = (uint8_t)r; out[3 * t + 1] = (uint8_t)gg; out[3 * t + 2] = (uint8_t)b;
+    }
+}
+
+int validate(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* dh, const sat_jpeg_desc* dd, int32_t n, const void* quant,
+             int32_t n_quant, const void* huff, int32_t n_huff, const uint8_t* pixels, int64_t pixels_bytes, const int32_t* status,
+             long* blocks_out, long* segs_out, long* max_px, long* max_blocks) {
+    SAT_REQUIRE(dh && dd && n > 0 && n <= 65535, "sat_jpeg_decode_batch: null descriptors or n = %d (1 ... 65535)", n);
+    SAT_REQUIRE(compressed && compressed_bytes > 0 && quant && n_quant > 0 && huff && n_huff > 0 && pixels && pixels_bytes > 0 && status,
+                "sat_jpeg_decode_batch: null buffer or empty table array");
+    long blocks = 0, segs = 0;
+    *max_px = *max_blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const sat_jpeg_desc& d = dh[i];
+        SAT_REQUIRE(d.height >= 1 && d.height <= 65535 && d.width >= 1 && d.width <= 65535, "jpeg %d: size %dx%d", i, d.height, d.width);
+        SAT_REQUIRE(d.components == 1 || d.components == 3, "jpeg %d: %d components (1 or 3)", i, d.components);
+        if (d.components == 3)
+            SAT_REQUIRE((d.h_samp == 1 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 2),
+                        "jpeg %d: luma sampling %dx%d (1x1, 2x1 or 2x2)", i, d.h_samp, d.v_samp);
+        else
+            SAT_REQUIRE(d.h_samp == 1 && d.v_samp == 1, "jpeg %d: a grayscale picture takes sampling 1x1", i);
+        SAT_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpeg %d: restart interval %d", i, d.restart_interval);
+        const long mcus = picture_mcus(d);
+        const long want = d.restart_interval ? (mcus + d.restart_interval - 1) / d.restart_interval : 1;
+        SAT_REQUIRE(d.n_segments == want, "jpeg %d: %d segments, the restart interval makes %ld", i, d.n_segments, want);
+        SAT_REQUIRE(d.segment_base == segs, "jpeg %d: segment_base %d, expected %ld", i, d.segment_base, segs);
+        SAT_REQUIRE(d.block_offset == blocks, "jpeg %d: block_offset %ld, expected %ld", i, (long)d.block_offset, blocks);
+        SAT_REQUIRE(d.data_offset >= 0 && d.data_bytes >= 0 && d.data_offset + d.data_bytes <= compressed_bytes, "jpeg %d: data outside the buffer", i);
+        SAT_REQUIRE(d.segments_offset >= 0 && d.segments_offset % 4 == 0 && d.segments_offset + 8L * d.n_segments <= compressed_bytes,
+                    "jpeg %d: segment table outside the buffer or not 4-byte aligned", i);
+        SAT_REQUIRE(d.out_offset >= 0 && d.out_offset + 3L * d.height * d.width <= pixels_bytes, "jpeg %d: output outside the pixel buffer", i);
+        for (int c = 0; c < 3; ++c)
+            SAT_REQUIRE(d.quant[c] >= 0 && d.quant[c] < n_quant && d.dc_table[c] >= 0 && d.dc_table[c] < n_huff && d.ac_table[c] >= 0 &&
+                            d.ac_table[c] < n_huff, "jpeg %d: table index out of range", i);
+        const long nb = picture_blocks(d);
+        blocks += nb;
+        segs += d.n_segments;
+        SAT_REQUIRE(segs < (1L << 31), "sat_jpeg_decode_batch: too many segments");
+        if (nb > *max_blocks) *max_blocks = nb;
+        if ((long)d.height * d.width > *max_px) *max_px = (long)d.height * d.width;
+    }
+    *blocks_out = blocks;
+    *segs_out = segs;
+    return SAT_OK;
+}
+
+}  // namespace
+}  // namespace sat
+
+using namespace sat;
+
+extern "C" {
+
+size_t sat_jpeg_decode_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n) {
+    if (!desc_host || n <= 0) { fail(SAT_EINVAL, "sat_jpeg_decode_workspace_bytes: null descriptors or n = %d", n); return 0; }
+    long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const sat_jpeg_desc& d = desc_host[i];
+        if (d.height < 1 || d.width < 1 || !(d.components == 1 || d.components == 3) || d.h_samp < 1 || d.h_samp > 2 || d.v_samp < 1 ||
+            d.v_samp > 2) {
+            fail(SAT_EINVAL, "sat_jpeg_decode_workspace_bytes: jpeg %d has a bad geometry", i);
+            return 0;
+        }
+        blocks += picture_blocks(d);
+    }
+    return (size_t)blocks * (64 * sizeof(int16_t) + 64);      // coefficients, then the sample planes
+}
+
+int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
+                          int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
+                          uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    long blocks = 0, segs = 0, max_px = 0, max_blocks = 0;
+    SAT_TRY(validate(compressed, compressed_bytes, desc_host, desc_dev, n, quant_dev, n_quant, huff_dev, n_huff, pixels, pixels_bytes, status,
+                     &blocks, &segs, &max_px, &max_blocks));
+    const size_t need = (size_t)blocks * (64 * sizeof(int16_t) + 64);
+    SAT_REQUIRE(workspace && workspace_bytes >= need, "sat_jpeg_decode_batch: workspace %zu bytes, need %zu", workspace_bytes, need);
+    SAT_REQUIRE(((uintptr_t)compressed & 3) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)desc_dev & 7) == 0 && ((uintptr_t)status & 3) == 0 &&
+                    ((uintptr_t)huff_dev & 3) == 0 && ((uintptr_t)quant_dev & 1) == 0,
+                "sat_jpeg_decode_batch: compressed (4), workspace (16), records (8), status and tables must be aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int16_t* coefs = reinterpret_cast<int16_t*>(workspace);
+    uint8_t* planes = reinterpret_cast<uint8_t*>(workspace) + (size_t)blocks * 64 * sizeof(int16_t);
+    SAT_TRY(dev_fill_bytes(st, status, 0, sizeof(int32_t) * (size_t)n));
+    SAT_TRY(dev_fill_bytes(st, coefs, 0, (size_t)blocks * 64 * sizeof(int16_t)));
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)segs), dim3(64), 0, st, compressed, (long)compressed_bytes, desc_dev, n, huff_dev, coefs,
+                       reinterpret_cast<int*>(status));
+    SAT_TRY(launch_ok("jpeg_entropy_kernel"));
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)min(cdiv(max_blocks, 256), 1024), (unsigned)n), dim3(256), 0, st, desc_dev, quant_dev, coefs,
+                       planes);
+    SAT_TRY(launch_ok("jpeg_idct_kernel"));
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)min(cdiv(max_px, 256), 1024), (unsigned)n), dim3(256), 0, st, desc_dev, planes, pixels);
+    SAT_TRY(launch_ok("jpeg_color_kernel"));
+    return SAT_OK;
+}
+
+}  // extern "C"

@@ -14,6 +14,9 @@ Host-side mirror of the reference's data path:
   parameters, per picture).
 * ``DeviceLoader``         train.py:244-259 DataLoader(pin_memory=True): decode threads -> one pinned staging buffer per
   batch -> one H2D copy on a side stream -> transform; batches arrive as ``(img, caps, lengths)`` on the device.
+* JPEG decoding on the GPU (``sat_amd.jpeg``): with ``CocoCaptionDataset(decode=jpeg.read_jpeg)`` the worker threads only read
+  the files, the staging buffer carries the compressed bytes, and ``sat_jpeg_decode_batch`` decodes them in front of the
+  transform, bit exact with ``decode_rgb``.  Files the GPU decoder does not take are decoded by Pillow on the worker threads.
 
 There is no CPU path: the transform needs libsat_hip.so and a GPU.
 """
@@ -33,6 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import jpeg as J
 
 
 def json_loader(path):
@@ -276,11 +280,17 @@ WARP_KEYS = ("warp_kind", "warp_coeffs")
 
 
 class StagedBatch:
-    """The decoded pictures of one batch in one pinned host buffer: [descriptors | jitter records | warp records | pixels].
+    """The pictures of one batch in one pinned host buffer: [descriptors | jitter records | warp records | pixels].
     The jitter records are there when the descriptor dicts carry ``JITTER_KEYS``, the warp records when they carry
-    ``WARP_KEYS`` (in each case all of them or none)."""
+    ``WARP_KEYS`` (in each case all of them or none).
+    A picture is an (H, W, 3) uint8 array or the bytes of a JPEG file (``jpeg.JpegBytes``, or plain bytes, parsed here; a
+    file the GPU decoder does not take is decoded by Pillow here).  With JPEG pictures the buffer is
+    [descriptors | jitter | warp | JPEG region (jpeg.JpegBatch) | pixels of the array pictures]; the device buffer has room
+    behind those pixels for the GPU-decoded ones, which ``run`` writes there before the transform reads them (``device_bytes``
+    in all; ``head`` is where the pixels start, in both buffers).  ``jpeg_index[j]``: the picture of the j-th JPEG record."""
 
     def __init__(self, images, descs):
+        images = [J.as_picture(im) for im in images]
         n = len(images)
         self.n = n
         self.desc = (L.ImageDesc * n)()
@@ -296,17 +306,31 @@ class StagedBatch:
         self.warp_off = (self.jitter_off + (C.sizeof(L.ImageJitter) * n if self.jitter is not None else 0) + 7) // 8 * 8
         head = self.warp_off + (C.sizeof(L.ImageWarp) * n if self.warp is not None else 0)
         head = (head + 255) // 256 * 256
-        total = head + sum(int(im.shape[0]) * int(im.shape[1]) * 3 for im in images)
+        self.jpeg_index = [i for i, im in enumerate(images) if isinstance(im, J.JpegBytes)]
+        arrays_bytes = sum(int(im.shape[0]) * int(im.shape[1]) * 3 for im in images if not isinstance(im, J.JpegBytes))
+        self.jpeg, self.jpeg_off = None, head
+        if self.jpeg_index:
+            self.jpeg = J.JpegBatch([images[i] for i in self.jpeg_index], out_base=arrays_bytes)
+            head = (head + self.jpeg.nbytes + 255) // 256 * 256
+        total = head + arrays_bytes
+        self.device_bytes = total + (self.jpeg.out_bytes if self.jpeg is not None else 0)
         self.host = torch.empty(total, dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else torch.empty(total, dtype=torch.uint8)
         buf = self.host.numpy()
+        if self.jpeg is not None:
+            self.jpeg.write(buf[self.jpeg_off:self.jpeg_off + self.jpeg.nbytes])
+        jpeg_out = dict(zip(self.jpeg_index, self.jpeg.out_offsets)) if self.jpeg is not None else {}
         off = 0
         for i, (im, d) in enumerate(zip(images, descs)):
-            if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
-                raise ValueError("picture %d: expected (H, W, 3) uint8, got %s %s" % (i, im.shape, im.dtype))
-            nb = im.shape[0] * im.shape[1] * 3
-            buf[head + off: head + off + nb] = im.reshape(-1)
             e = self.desc[i]
-            e.offset = off
+            if i in jpeg_out:
+                e.offset = jpeg_out[i]
+            else:
+                if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+                    raise ValueError("picture %d: expected (H, W, 3) uint8, got %s %s" % (i, im.shape, im.dtype))
+                nb = im.shape[0] * im.shape[1] * 3
+                buf[head + off: head + off + nb] = im.reshape(-1)
+                e.offset = off
+                off += nb
             for k, v in d.items():
                 if k not in JITTER_KEYS and k not in WARP_KEYS:
                     setattr(e, k, int(v))
@@ -322,13 +346,13 @@ class StagedBatch:
                     raise ValueError("picture %d: %d warp coefficients, expected 6 (affine) or 8 (perspective)" % (i, len(coeffs)))
                 wr.kind = int(d["warp_kind"])
                 wr.coeffs[:] = coeffs + [0.0] * (8 - len(coeffs))
-            off += nb
         buf[:C.sizeof(L.ImageDesc) * n] = np.frombuffer(self.desc, dtype=np.uint8)
         if self.jitter is not None:
             buf[self.jitter_off:self.jitter_off + C.sizeof(L.ImageJitter) * n] = np.frombuffer(self.jitter, dtype=np.uint8)
         if self.warp is not None:
             buf[self.warp_off:self.warp_off + C.sizeof(L.ImageWarp) * n] = np.frombuffer(self.warp, dtype=np.uint8)
-        self.head, self.pixels_bytes = head, off
+        self.head, self.pixels_bytes = head, self.device_bytes - head
+        self.status = None          # run(): (number of JPEG records,) int32 device status words of the GPU decoder
 
 
 class BatchTransform:
@@ -356,7 +380,7 @@ class BatchTransform:
         self.size, self.train = int(input_size), train
         self.aug_scale, self.aug_hflip, self.noise_std, self.randn = aug_scale, aug_hflip, aug_noise_std, randn
         self.aug_color_jitter, self.aug_optical_strength = x, o
-        self._ws = None
+        self._ws = self._jws = None
 
     def draw(self, shapes):
         """one descriptor per picture; consumes the torch CPU generator (and, for the optical choice, Python's ``random``)
@@ -377,6 +401,9 @@ class BatchTransform:
         return out
 
     def stage(self, images, descs=None):
+        """``images``: (H, W, 3) uint8 arrays and / or JPEG bytes; a JPEG picture's shape comes from its header, so the draws
+        are the same whichever form a picture arrives in"""
+        images = [J.as_picture(im) for im in images]
         return StagedBatch(images, descs if descs is not None else self.draw([im.shape[:2] for im in images]))
 
     def run(self, staged, device, stream=None, noise=None, want_bytes=False):
@@ -389,7 +416,17 @@ class BatchTransform:
         stream = stream if stream is not None else torch.cuda.current_stream(device)
         S, n = self.size, staged.n
         with torch.cuda.stream(stream):
-            dev = staged.host.to(device, non_blocking=True)
+            if staged.jpeg is None:
+                dev = staged.host.to(device, non_blocking=True)
+            else:                                   # room behind the copied bytes for the pictures the GPU decodes
+                dev = torch.empty(staged.device_bytes, dtype=torch.uint8, device=device)
+                dev[:staged.host.numel()].copy_(staged.host, non_blocking=True)
+                jb = staged.jpeg
+                need = jb.workspace_bytes()
+                if self._jws is None or self._jws.numel() < need or self._jws.device != dev.device:
+                    self._jws = torch.empty(need, dtype=torch.uint8, device=device)
+                staged.status = torch.empty(jb.n, dtype=torch.int32, device=device)
+                jb.launch(dev.data_ptr() + staged.jpeg_off, dev.data_ptr() + staged.head, staged.pixels_bytes, staged.status, self._jws, stream)
             jit, warp = staged.jitter, staged.warp
             if warp is not None:
                 need = lib.sat_image_batch_warp_workspace_bytes(C.cast(staged.desc, C.c_void_p), C.cast(jit, C.c_void_p) if jit is not None else None,
@@ -433,7 +470,10 @@ class BatchTransform:
 class DeviceLoader:
     """train.py:244-259: ``DataLoader(dataset, sampler=BucketSampler | shuffle, batch_size, num_workers, pin_memory=True)``
     with the transform moved behind the H2D copy.  Decoding runs in ``workers`` threads (PIL releases the GIL), staging and
-    the copy + kernels of batch i+1 overlap the consumer's work on batch i (side stream, ``prefetch`` batches in flight)."""
+    the copy + kernels of batch i+1 overlap the consumer's work on batch i (side stream, ``prefetch`` batches in flight).
+    With a dataset whose ``decode`` is ``jpeg.read_jpeg`` the GPU decodes the pictures; the producer thread reads their status
+    words after its side stream is done, and a bad stream raises ``jpeg.JpegDecodeError`` (naming the dataset index) on the
+    consumer side, in place of the batch that held it."""
 
     def __init__(self, dataset, batch_size, transform, sampler=None, shuffle=False, workers=4, prefetch=2, device="cuda", drop_last=False):
         self.ds, self.batch_size, self.tf, self.sampler, self.shuffle = dataset, batch_size, transform, sampler, shuffle
@@ -475,8 +515,18 @@ class DeviceLoader:
                         with torch.cuda.stream(side):
                             caps_d = caps.pin_memory().to(self.device, non_blocking=True)
                             lens_d = lens.pin_memory().to(self.device, non_blocking=True)
+                            if staged.status is not None:
+                                status = torch.empty(staged.status.numel(), dtype=torch.int32).pin_memory()
+                                status.copy_(staged.status, non_blocking=True)
                             done = torch.cuda.Event()
                             done.record(side)
+                        if staged.status is not None:
+                            done.synchronize()          # this thread waits for its own side stream; the consumer's stream does not
+                            bad = [(idxs[staged.jpeg_index[j]], int(c)) for j, c in enumerate(status.tolist()) if c]
+                            if bad:
+                                q.put(J.JpegDecodeError("corrupt JPEG data: " + "; ".join("dataset index %d: %s" % (i, J.status_text(c))
+                                                                                         for i, c in bad)))
+                                return
                         q.put((img, caps_d, lens_d, done, staged))
                 q.put(None)
             except BaseException as e:          # surfaces in the consumer

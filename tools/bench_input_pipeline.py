@@ -4,7 +4,11 @@ With --color-jitter X the same batch also goes through T.ColorJitter(X, X, X, 0.
 both rates are reported from the same run.  With --optical S the same batch (with the ColorJitter draws too when
 --color-jitter is given) also goes through the reference's RandomChoice of RandomPerspective / RandomAffine / RandomRotation
 at strength S (sat_image_batch_transform_warp).
+With --jpeg the batch arrives as JPEG files instead (Pillow-encoded 480x640, quality 90, 4:2:0, restart-free and again with
+a restart marker per MCU row; or the first --batch files of --jpeg-dir): GPU decoding alone (sat_jpeg_decode_batch, bytes
+resident), decoding + the transform with and without the H2D copy, and Pillow's decode_rgb on one host thread.
     python tools/bench_input_pipeline.py [--batch 128] [--size 224] [--color-jitter 0.4] [--optical 0.5]
+    python tools/bench_input_pipeline.py --jpeg [--jpeg-dir DIR]
 """
 import argparse
 import ctypes as C
@@ -70,6 +74,87 @@ def measure(tf, staged, noise, iters):
     return with_copy_ms, time_ms(kernels, iters)
 
 
+def jpeg_rates(tf, files, iters, label):
+    """decode alone / decode + transform with and without the H2D copy, images/s; Pillow per host thread"""
+    from sat_amd import jpeg as J
+    dev = torch.device("cuda")
+    B = len(files)
+    torch.manual_seed(0)
+    staged = tf.stage(files)
+    assert staged.jpeg is not None, "no GPU-decodable file"
+    S = tf.size
+    noise = torch.randn(B, 3, S, S, device=dev)
+    with_copy_ms = time_ms(lambda: tf.run(staged, dev, noise=noise), iters)
+    lib, jb = L.lib(), staged.jpeg
+    resident = torch.empty(staged.device_bytes, dtype=torch.uint8, device=dev)
+    resident[:staged.host.numel()].copy_(staged.host)
+    status = torch.empty(jb.n, dtype=torch.int32, device=dev)
+    jws = torch.empty(jb.workspace_bytes(), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream()
+    base = resident.data_ptr()
+
+    def decode():
+        jb.launch(base + staged.jpeg_off, base + staged.head, staged.pixels_bytes, status, jws, stream)
+    desc = C.cast(staged.desc, C.c_void_p)
+    need = lib.sat_image_batch_workspace_bytes(desc, B, S, S)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, 3, S, S, device=dev)
+
+    def decode_transform():
+        decode()
+        L.check(lib.sat_image_batch_transform(base + staged.head, staged.pixels_bytes, desc, base, B, S, S, L.ptr(noise), 0.01, L.ptr(out), None,
+                                              L.ptr(ws), need, C.c_void_p(stream.cuda_stream)), "transform")
+    dec_ms = time_ms(decode, iters)
+    assert not status.any().item(), "decode status %s" % status.tolist()
+    dt_ms = time_ms(decode_transform, iters)
+    n_cpu = min(B, 32)
+    t0 = time.perf_counter()
+    for f in files[:n_cpu]:
+        J.pillow_decode(f)
+    cpu_s = (time.perf_counter() - t0) / n_cpu
+    mb = sum(len(f) for f in files) / 1e6
+    return {label + "decode_ms": round(dec_ms, 3), label + "decode_images_per_s": round(B / dec_ms * 1e3, 1),
+            label + "decode_transform_ms": round(dt_ms, 3), label + "decode_transform_images_per_s": round(B / dt_ms * 1e3, 1),
+            label + "decode_transform_with_h2d_ms": round(with_copy_ms, 3), label + "decode_transform_with_h2d_images_per_s": round(B / with_copy_ms * 1e3, 1),
+            label + "compressed_MB": round(mb, 2), label + "h2d_bytes": int(staged.host.numel()), label + "segments": int(sum(jb.desc[j].n_segments for j in range(B))),
+            label + "pillow_decode_1thread_images_per_s": round(1.0 / cpu_s, 1)}
+
+
+def main_jpeg(a):
+    import io
+    from PIL import Image
+    B, S = a.batch, a.size
+    tf = D.BatchTransform(S, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01)
+    res = {"metric": "input_pipeline_jpeg_images_per_s", "batch": B, "out": S}
+    if a.jpeg_dir:
+        names = sorted(n for n in os.listdir(a.jpeg_dir) if n.lower().endswith((".jpg", ".jpeg")))[:B]
+        files = []
+        for n in names:
+            with open(os.path.join(a.jpeg_dir, n), "rb") as f:
+                files.append(f.read())
+        from sat_amd import jpeg as J
+        gpu = [f for f in files if isinstance(J.as_picture(f), J.JpegBytes)]
+        res.update({"jpeg_dir_files": len(files), "jpeg_dir_gpu_decodable": len(gpu)})
+        res.update(jpeg_rates(tf, gpu, a.iters, "dir_"))
+    else:
+        H, W = 480, 640
+        rng = np.random.default_rng(0)
+        y, x = np.mgrid[0:H, 0:W]
+        base = []
+        for k in range(8):
+            ramp = np.stack([x * 255.0 / W, y * 255.0 / H, 128 + 100 * np.sin((x + (k + 1) * y) / (9.0 + k))], -1)
+            base.append(np.clip(np.rint(ramp + rng.normal(0, 10, (H, W, 3))), 0, 255).astype(np.uint8))
+
+        def enc(im, **kw):
+            buf = io.BytesIO()
+            Image.fromarray(im).save(buf, "JPEG", quality=90, subsampling=2, **kw)
+            return buf.getvalue()
+        res["source"] = "%dx%d q90 4:2:0" % (H, W)
+        res.update(jpeg_rates(tf, [enc(base[i % 8]) for i in range(B)], a.iters, ""))
+        res.update(jpeg_rates(tf, [enc(base[i % 8], restart_marker_rows=1) for i in range(B)], a.iters, "rst_rows1_"))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
@@ -77,7 +162,11 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--color-jitter", type=float, default=0.0, help="also time T.ColorJitter(X, X, X, 0.03) on the same batch")
     ap.add_argument("--optical", type=float, default=0.0, help="also time the optical augmentation of strength S on the same batch")
+    ap.add_argument("--jpeg", action="store_true", help="time GPU JPEG decoding (+ the transform) of a batch of JPEG files instead")
+    ap.add_argument("--jpeg-dir", default=None, help="with --jpeg: the first --batch *.jpg files of this directory instead of synthetic ones")
     a = ap.parse_args()
+    if a.jpeg or a.jpeg_dir:
+        return main_jpeg(a)
     H, W, S, B = 480, 640, a.size, a.batch
     rng = np.random.default_rng(0)
     base = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for _ in range(8)]
