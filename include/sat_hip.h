@@ -598,6 +598,39 @@ int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, c
                           int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
                           uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* mobilenet_v3_small trunk (model.py:38-39 keeps torchvision's `features`; torchvision 0.10 _mobilenet_v3_conf("mobilenet_v3_small"), Howard et
+ * al. 2019 table 2).  dtype: 0 = fp32, 1 = bf16 activations; NHWC; statistics, SE vectors, parameters and their gradients fp32.
+ *   depthwise 5x5, pad 2, stride 1 | 2 (InvertedResidual's depthwise ConvBNActivation, kernel_size 5): as sat_dwconv3x3_*, C a multiple of 4
+ *     in both storage types; w = the (C, 1, 5, 5) parameter in memory ([C][25]); wgrad: per-chunk partials added in a fixed order
+ *     (scratch: sat_dwconv5x5_wgrad_scratch_bytes). */
+int sat_dwconv5x5_fwd_t(int32_t dtype, const void* x, const float* w, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, void* stream);
+int sat_dwconv5x5_dgrad_t(int32_t dtype, const void* dy, const float* w, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, void* stream);
+size_t sat_dwconv5x5_wgrad_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride);
+int sat_dwconv5x5_wgrad_t(int32_t dtype, const void* dy, const void* x, float* dw, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride,
+                          float* scratch, void* stream);
+/* BatchNorm2d + nn.Hardswish (ConvBNActivation with activation_layer = nn.Hardswish; BatchNorm2d(eps = 0.001, momentum = 0.01)):
+ * y = v * min(max(v + 3, 0), 6) / 6 with v the BatchNorm output.  Training statistics (and running statistics) as sat_bn_train_fwd_t, or from
+ * the producing bf16 convolution's tile statistics (tile_stats != NULL, as sat_bn_train_fwd_tiles_bf16).  The backward recomputes v from x,
+ * mean, invstd, gamma and beta and takes torch's hardswish_backward: v <= -3 -> 0, v < 3 -> g (v / 3 + 0.5), else g.
+ * scratch: sat_bn_scratch_bytes(rows, C).  C a multiple of 4 (fp32) / 8 (bf16). */
+int sat_bn_hswish_train_fwd_t(int32_t dtype, const void* x, int64_t rows, int32_t C, const float* tile_stats /* or NULL */, int32_t tile_rows,
+                              const float* gamma, const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                              float* save_mean, float* save_invstd, void* y, float* scratch, void* stream);
+int sat_bn_hswish_eval_fwd_t(int32_t dtype, const void* x, int64_t rows, int32_t C, const float* running_mean, const float* running_var, float eps,
+                             const float* gamma, const float* beta, void* y, void* stream);
+int sat_bn_hswish_train_bwd_t(int32_t dtype, const void* dy, const void* x, int64_t rows, int32_t C, const float* save_mean, const float* save_invstd,
+                              const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* scratch, void* stream);
+/* SqueezeExcitation (torchvision 0.10 mobilenetv3.py: fc1 / fc2 = 1x1 Conv2d with bias, squeeze width S): over x (N, HW, C),
+ * pool = mean_hw x, h = relu(w1 pool + b1) (w1: (S, C)), z2 = w2 h + b2 (w2: (C, S)), s = hardsigmoid(z2), y = x * s.  pool / z2 / s: [N][C],
+ * h: [N][S] fp32, written by the forward and read by the backward.  Backward: ds = sum_hw dy x, dz2 = ds / 6 where -3 < z2 < 3, the parameter
+ * gradients summed over the images in order, dx = dy s + dpool / HW.  Every sum in a fixed order, no atomics.  C <= 1024, S <= 256;
+ * scratch: sat_se_bwd_scratch_bytes(N, C, S). */
+int sat_se_fwd_t(int32_t dtype, const void* x, int32_t N, int32_t HW, int32_t C, int32_t S, const float* w1, const float* b1, const float* w2, const float* b2,
+                 float* pool, float* h, float* z2, float* s, void* y, void* stream);
+size_t sat_se_bwd_scratch_bytes(int32_t N, int32_t C, int32_t S);
+int sat_se_bwd_t(int32_t dtype, const void* dy, const void* x, int32_t N, int32_t HW, int32_t C, int32_t S, const float* w1, const float* w2, const float* pool,
+                 const float* h, const float* z2, const float* s, void* dx, float* dw1, float* db1, float* dw2, float* db2, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

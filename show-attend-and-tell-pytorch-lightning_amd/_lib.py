@@ -265,6 +265,18 @@ SYMBOLS.update({"sat_profile_start": (C.c_int, []),
                 "sat_profile_start_only": (C.c_int, [C.c_char_p]),
                 "sat_profile_pause": (C.c_int, [_i32]),
                 "sat_profile_stop": (C.c_int, [C.POINTER(ProfileEntry), _i32, C.POINTER(C.c_int32)])})
+SYMBOLS.update({          # mobilenet_v3_small: depthwise 5x5, BatchNorm + hard-swish, squeeze-and-excitation
+    "sat_dwconv5x5_fwd_t": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sat_dwconv5x5_dgrad_t": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sat_dwconv5x5_wgrad_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
+    "sat_dwconv5x5_wgrad_t": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sat_bn_hswish_train_fwd_t": (C.c_int, [_i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sat_bn_hswish_eval_fwd_t": (C.c_int, [_i32, _vp, _i64, _i32, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "sat_bn_hswish_train_bwd_t": (C.c_int, [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sat_se_fwd_t": (C.c_int, [_i32, _vp, _i32, _i32, _i32, _i32] + [_vp] * 10),
+    "sat_se_bwd_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "sat_se_bwd_t": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32] + [_vp] * 13),
+})
 
 
 def profile_start(only=None):

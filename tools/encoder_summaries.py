@@ -11,7 +11,7 @@ from sat_amd import encoder as E
 from sat_amd.encoder_shuffle import SHUFFLENETS
 
 batch = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 32
-archs = [a for a in sys.argv[1:] if not a.isdigit()] or (list(E.RESNETS) + list(SHUFFLENETS) + ["mobilenet_v2"])
+archs = [a for a in sys.argv[1:] if not a.isdigit()] or (list(E.RESNETS) + list(SHUFFLENETS) + ["mobilenet_v2", "mobilenet_v3_small"])
 warmup, n_trials = 5, 100
 data = torch.rand(batch, 3, 224, 224, device="cuda")
 print("ENCODER SUMMARIES (sat_amd on %s)" % torch.cuda.get_device_name(0))
