@@ -165,6 +165,26 @@ int sat_doubly_stochastic_fwd(const float* alphas, int32_t N, int32_t T1, int32_
 int sat_doubly_stochastic_bwd(const float* asum, const float* gscale, int32_t N, int32_t T1, int32_t L, float gamma,
                               float* dalphas, void* stream);
 
+/* ------------------------------------------------------------------ temperature-scaling calibration (temperature_scaling.py:51-59)
+ * For packed logits (P, V) and targets (P):  loss(T) = F.cross_entropy(logits / T, targets)  and its derivative
+ * dloss/dT = mean_i [ x_iy - sum_j softmax(x_i / T)_j x_ij ] / T^2.  The row maximum does not depend on T > 0, so it is taken once;
+ * each evaluation is then ONE streaming read of the logits and writes nothing of size P*V.  Reductions run in a fixed order in
+ * double (no atomics): the same input gives the same bits.  A target outside [0, V) or a non-finite logit gives NaN, never an
+ * out-of-bounds read.  workspace: sat_temperature_workspace_bytes(P, V) bytes, 16-byte aligned; 0 + message for non-positive sizes. */
+#define SAT_TEMPERATURE_MAX 8
+size_t sat_temperature_workspace_bytes(int32_t P, int32_t V);
+/* loss_out[t], grad_out[t] at temperatures[t] (device array, every one > 0), t < n_temperatures <= SAT_TEMPERATURE_MAX, all from the
+ * same read of the logits; n temperatures in one call equal n single calls bit for bit. */
+int sat_temperature_nll(const float* logits, const int32_t* targets, int32_t P, int32_t V, const float* temperatures,
+                        int32_t n_temperatures, float* loss_out, float* grad_out, void* workspace, void* stream);
+/* `iters` steps of torch.optim.SGD(lr, momentum, nesterov) on the scalar T from `init`, in fp32 as the reference's tensor: first step
+ * buf = g, then buf = momentum * buf + g; step = g + momentum * buf (nesterov) or buf; T -= lr * step.  T never visits the host:
+ * t_trace (iters + 1 floats, t_trace[0] = init) and loss_trace (iters floats, the loss at t_trace[k]) are device arrays.  If T
+ * becomes non-positive or non-finite at step k, t_trace[k + 1] holds that value, T is left alone from then on (t_trace repeats
+ * it) and the later loss_trace entries are NaN. */
+int sat_temperature_fit(const float* logits, const int32_t* targets, int32_t P, int32_t V, float init, float lr, float momentum,
+                        int32_t nesterov, int32_t iters, float* t_trace, float* loss_trace, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ inference: SAT.forward / caption (model.py:214-472)
  * The reference decodes one image at a time with the beam as the batch (model.py:260-266).  `begin` computes att_enc
  * and the initial state of `beams` rows (InitLSTM over the expanded annotations, F3 reshape: model.py:265-269);

@@ -277,6 +277,11 @@ SYMBOLS.update({          # mobilenet_v3_small: depthwise 5x5, BatchNorm + hard-
     "sat_se_bwd_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "sat_se_bwd_t": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32] + [_vp] * 13),
 })
+SYMBOLS.update({          # temperature-scaling calibration (calibration.py)
+    "sat_temperature_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "sat_temperature_nll": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "sat_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _f, _f, _f, _i32, _i32, _vp, _vp, _vp, _vp]),
+})
 
 
 def profile_start(only=None):

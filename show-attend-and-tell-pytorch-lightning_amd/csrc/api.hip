@@ -5,6 +5,7 @@
 #include "decoder.h"
 #include "gemm.h"
 #include "gemm_bf16_common.h"
+#include "temperature.h"
 
 namespace sat {
 static thread_local char g_err[512] = {0};
@@ -119,6 +120,30 @@ int sat_doubly_stochastic_fwd(const float* alphas, int32_t N, int32_t T1, int32_
 int sat_doubly_stochastic_bwd(const float* asum, const float* gscale, int32_t N, int32_t T1, int32_t L, float gamma, float* dalphas, void* stream) {
     if (!asum || !dalphas) return fail(SAT_EINVAL, "doubly_stochastic_bwd: null pointer");
     return ds_bwd(asum, gscale, N, T1, L, gamma, dalphas, (hipStream_t)stream);
+}
+
+size_t sat_temperature_workspace_bytes(int32_t P, int32_t V) {
+    if (P <= 0 || V <= 0) { fail(SAT_EINVAL, "temperature_workspace_bytes: non-positive size (P=%d V=%d)", P, V); return 0; }
+    return temperature_workspace_bytes(P, V);
+}
+int sat_temperature_nll(const float* logits, const int32_t* targets, int32_t P, int32_t V, const float* temperatures, int32_t n_temperatures,
+                        float* loss_out, float* grad_out, void* workspace, void* stream) {
+    if (!logits || !targets || !temperatures || !loss_out || !grad_out || !workspace) return fail(SAT_EINVAL, "temperature_nll: null pointer");
+    if (P <= 0 || V <= 0) return fail(SAT_EINVAL, "temperature_nll: empty input (P=%d V=%d)", P, V);
+    if (n_temperatures < 1 || n_temperatures > SAT_TEMPERATURE_MAX)
+        return fail(SAT_EINVAL, "temperature_nll: %d temperatures (1..%d in one pass)", n_temperatures, SAT_TEMPERATURE_MAX);
+    if ((uintptr_t)workspace % 16) return fail(SAT_EINVAL, "temperature_nll: workspace must be 16-byte aligned");
+    return temperature_nll(logits, targets, P, V, temperatures, n_temperatures, loss_out, grad_out, (char*)workspace, (hipStream_t)stream);
+}
+int sat_temperature_fit(const float* logits, const int32_t* targets, int32_t P, int32_t V, float init, float lr, float momentum, int32_t nesterov,
+                        int32_t iters, float* t_trace, float* loss_trace, void* workspace, void* stream) {
+    if (!logits || !targets || !t_trace || !loss_trace || !workspace) return fail(SAT_EINVAL, "temperature_fit: null pointer");
+    if (P <= 0 || V <= 0 || iters <= 0) return fail(SAT_EINVAL, "temperature_fit: non-positive size (P=%d V=%d iters=%d)", P, V, iters);
+    if (!(init > 0.f) || !(init < INFINITY)) return fail(SAT_EINVAL, "temperature_fit: initial temperature %g is not a positive finite number", init);
+    if (!(lr > 0.f)) return fail(SAT_EINVAL, "temperature_fit: learning rate %g is not positive", lr);
+    if (!(momentum >= 0.f)) return fail(SAT_EINVAL, "temperature_fit: momentum %g is negative", momentum);
+    if ((uintptr_t)workspace % 16) return fail(SAT_EINVAL, "temperature_fit: workspace must be 16-byte aligned");
+    return temperature_fit(logits, targets, P, V, init, lr, momentum, nesterov ? 1 : 0, iters, t_trace, loss_trace, (char*)workspace, (hipStream_t)stream);
 }
 
 size_t sat_decoder_infer_workspace_bytes(const sat_decoder_dims* d, int32_t max_beams) {

@@ -499,6 +499,13 @@ class SAT(SATDecoder, _Base):
         tp = PackedSequence(res["targets_packed"], plan.batch_sizes, plan.sorted_indices_dev, plan.unsorted_indices_dev)
         return lp, tp, res["alphas"]
 
+    def calibrate_temperature(self, batches, max_batches=42, **fit_kwargs):
+        """The reference's temperature_scaling.py in one call: teacher-forced logits of the frozen model over ``batches``, then the
+        temperature fit (calibration.py).  Returns a ``TemperatureFit``; its ``temperature`` is what ``caption`` / ``val_batch`` take.
+        Changes no parameter, buffer or hyper-parameter."""
+        from . import calibration
+        return calibration.calibrate_temperature(self, batches, max_batches, **fit_kwargs)
+
     def teacher_forcing_epsilon(self, current_epoch=0):
         """model.py:565-582 (host scalars)."""
         hp = self.hp
