@@ -240,6 +240,45 @@ int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float tempera
                     int32_t n_masked, const float* parent_scores /* (beams) or NULL */, float* scores, void* stream);
 int sat_topk(const float* x, float* work /* n floats scratch */, int64_t n, int32_t k, float* values, int32_t* indices, void* stream);
 
+/* ------------------------------------------------------------------ scoring decoded captions (SAT.val_batch: model.py:449-472, 646-682)
+ * The three calls below take the buffers sat_beam_search_batched / _sampled leave on the device to per-image metric statistics
+ * without a host round trip (kernel launches only: capturable).  Tokens are int32 everywhere: pass int32 device copies of the
+ * dataset's int64 captions and lengths.  Limits (SAT_EINVAL with a message beyond them, never a truncated count):
+ * max_gen_length + 1 = cap_width <= SAT_CAPTION_MAX_LEN, T <= SAT_CAPTION_MAX_LEN, R <= SAT_CAPTION_MAX_REFS, m <= SAT_CAPTION_MAX_EMBED.
+ * Indices read from device memory (steps, rows, lengths) are clamped to their ranges before they address anything. */
+#define SAT_CAPTION_MAX_LEN 128
+#define SAT_CAPTION_MAX_REFS 16
+#define SAT_CAPTION_MAX_EMBED 2048
+#define SAT_RESCORE_NONE 0
+#define SAT_RESCORE_LN 1   /* s / step                 */
+#define SAT_RESCORE_WR 2   /* s + reward * step        */
+#define SAT_RESCORE_BAR 3  /* s + reward * (-fin_mean) */
+/* Winning hypothesis of every image (model.py:341-348, 467-471): the fin_count[b] finished hypotheses are rescored in fp32 without
+ * FMA contraction (the reward is the fp32 the caller passes), the FIRST maximum in append order wins (list.index(max(...))), and its
+ * parent rows are walked from fin_step down to step 1.
+ *   cap_tokens (B, max_gen_length + 1)  tokens fed at steps 1..step, then pad_id
+ *   cap_len, cap_step (B)               step = number of tokens;  cap_score (B) the rescored value;  cap_raw (B) the raw score
+ *   cap_alpha (B, max_gen_length, L)    optional (needs alpha_hist): the attention maps of steps 0..step-1, zero beyond */
+int sat_beam_select(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
+                    const float* fin_score, const float* fin_mean, const float* alpha_hist /* or NULL */, int32_t B, int32_t beamk,
+                    int32_t max_gen_length, int32_t L, int32_t rescore_method, float rescore_reward, int32_t pad_id, int32_t* cap_tokens,
+                    int32_t* cap_len, float* cap_score, float* cap_raw, int32_t* cap_step, float* cap_alpha /* or NULL */, void* stream);
+/* The integers nltk's corpus BLEU / GLEU sum per segment (sat_amd/metrics.py is the specification).  Hypothesis b = the first
+ * cap_len[b] tokens of cap_tokens (B, cap_width); reference (b, r) = refs[b][r][1:ref_lengths[b][r]] of refs (B, R, T) (without START
+ * and END, as score_captions slices them).  stats (B, 12) int32:
+ *   [0..3]  clipped n-gram matches, n = 1..4          [4..7]  max(1, hyp_len - n + 1), per segment as modified_precision
+ *   [8]     hyp_len                                    [9]     closest reference length (a tie goes to the shorter reference)
+ *   [10,11] GLEU tp and max(tp + fp, tp + fn) over all 1..4-grams of the reference with the best ratio (integer cross-multiplication;
+ *           a later reference replaces an earlier one only if strictly better; references with a zero total are skipped; 0, 0 if all are) */
+int sat_caption_stats(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
+                      int32_t B, int32_t R, int32_t T, int32_t* stats, void* stream);
+/* best_cosine[b] = max over r of F.cosine_similarity(mean embedding of reference (b, r), mean embedding of hypothesis b) (model.py:660-673;
+ * torch 2's definition: sum_d (x_d / max(|x|, eps)) (y_d / max(|y|, eps)), eps = 1e-8).  A kernel of its own, not fused into
+ * sat_caption_stats.  Rows of embedding (V, m) are gathered in fp32; an empty hypothesis or reference gives NaN like torch's empty mean,
+ * and so does a token outside [0, V) (it is not read). */
+int sat_caption_cosine(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
+                       int32_t B, int32_t R, int32_t T, const float* embedding, int32_t V, int32_t m, float* best_cosine, void* stream);
+
 /* out[c] = sum_r x[r*ld + c] in a fixed order (bias gradients).  scratch: ceil(rows/256)*cols floats */
 int sat_colsum(const float* x, int64_t ld, int64_t rows, int32_t cols, float* out, float* scratch, void* stream);
 

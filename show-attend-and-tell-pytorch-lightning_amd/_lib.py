@@ -283,6 +283,13 @@ SYMBOLS.update({          # temperature-scaling calibration (calibration.py)
     "sat_temperature_fit": (C.c_int, [_vp, _vp, _i32, _i32, _f, _f, _f, _i32, _i32, _vp, _vp, _vp, _vp]),
 })
 
+SYMBOLS.update({          # scoring decoded captions on the device (evaluation.py)
+    "sat_beam_select": (C.c_int, [_vp] * 8 + [_i32, _i32, _i32, _i32, _i32, _f, _i32] + [_vp] * 7),
+    "sat_caption_stats": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "sat_caption_cosine": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+})
+CAPTION_MAX_LEN, CAPTION_MAX_REFS, CAPTION_MAX_EMBED = 128, 16, 2048          # SAT_CAPTION_MAX_* of include/sat_hip.h
+RESCORE = {None: 0, "NONE": 0, "LN": 1, "WR": 2, "BAR": 3}                      # SAT_RESCORE_*
 
 def profile_start(only=None):
     """record every instrumented scope, or only the family ``only``"""

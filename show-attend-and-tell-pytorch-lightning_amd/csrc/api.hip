@@ -6,6 +6,7 @@
 #include "gemm.h"
 #include "gemm_bf16_common.h"
 #include "temperature.h"
+#include "caption_score.h"
 
 namespace sat {
 static thread_local char g_err[512] = {0};
@@ -188,6 +189,42 @@ int sat_beam_search_sampled(const sat_decoder_dims* d, const sat_decoder_params*
     for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_sampled: temperature %g", temperatures_host[i]);
     return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling);
+}
+int sat_beam_select(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
+                    const float* fin_score, const float* fin_mean, const float* alpha_hist, int32_t B, int32_t beamk, int32_t max_gen_length, int32_t L,
+                    int32_t rescore_method, float rescore_reward, int32_t pad_id, int32_t* cap_tokens, int32_t* cap_len, float* cap_score, float* cap_raw,
+                    int32_t* cap_step, float* cap_alpha, void* stream) {
+    if (!tok_in || !prev_row || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !cap_tokens || !cap_len || !cap_score || !cap_raw || !cap_step)
+        return fail(SAT_EINVAL, "beam_select: null pointer");
+    if (cap_alpha && !alpha_hist) return fail(SAT_EINVAL, "beam_select: cap_alpha asked for without alpha_hist (null pointer)");
+    if (B < 1 || beamk < 1 || max_gen_length < 1 || (cap_alpha && L < 1))
+        return fail(SAT_EINVAL, "beam_select: non-positive size (B=%d beamk=%d max_gen_length=%d L=%d)", B, beamk, max_gen_length, L);
+    if (max_gen_length + 1 > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "beam_select: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length, SAT_CAPTION_MAX_LEN);
+    if (rescore_method < SAT_RESCORE_NONE || rescore_method > SAT_RESCORE_BAR) return fail(SAT_EINVAL, "beam_select: rescore_method %d (0..3)", rescore_method);
+    return beam_select(tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, fin_mean, alpha_hist, B, beamk, max_gen_length, L, rescore_method,
+                       rescore_reward, pad_id, cap_tokens, cap_len, cap_score, cap_raw, cap_step, cap_alpha, (hipStream_t)stream);
+}
+static int check_caption_sizes(const char* what, int32_t cap_width, int32_t B, int32_t R, int32_t T) {
+    if (B < 1 || R < 1 || T < 1 || cap_width < 1) return fail(SAT_EINVAL, "%s: non-positive size (B=%d R=%d T=%d cap_width=%d)", what, B, R, T, cap_width);
+    if (R > SAT_CAPTION_MAX_REFS || T > SAT_CAPTION_MAX_LEN || cap_width > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "%s: over the limits (R=%d <= %d, T=%d <= %d, cap_width=%d <= %d)", what, R, SAT_CAPTION_MAX_REFS, T, SAT_CAPTION_MAX_LEN,
+                    cap_width, SAT_CAPTION_MAX_LEN);
+    return SAT_OK;
+}
+int sat_caption_stats(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths, int32_t B,
+                      int32_t R, int32_t T, int32_t* stats, void* stream) {
+    if (!cap_tokens || !cap_len || !refs || !ref_lengths || !stats) return fail(SAT_EINVAL, "caption_stats: null pointer");
+    SAT_TRY(check_caption_sizes("caption_stats", cap_width, B, R, T));
+    return caption_stats(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, stats, (hipStream_t)stream);
+}
+int sat_caption_cosine(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths, int32_t B,
+                       int32_t R, int32_t T, const float* embedding, int32_t V, int32_t m, float* best_cosine, void* stream) {
+    if (!cap_tokens || !cap_len || !refs || !ref_lengths || !embedding || !best_cosine) return fail(SAT_EINVAL, "caption_cosine: null pointer");
+    SAT_TRY(check_caption_sizes("caption_cosine", cap_width, B, R, T));
+    if (V < 1 || m < 1) return fail(SAT_EINVAL, "caption_cosine: non-positive size (V=%d m=%d)", V, m);
+    if (m > SAT_CAPTION_MAX_EMBED) return fail(SAT_EINVAL, "caption_cosine: embedding width %d is over the limit %d", m, SAT_CAPTION_MAX_EMBED);
+    return caption_cosine(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, embedding, V, m, best_cosine, (hipStream_t)stream);
 }
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids, int32_t n_masked,
                     const float* parent_scores, float* scores, void* stream) {

@@ -1,0 +1,15 @@
+// Internal C++ entry points of the on-device caption scoring (caption_score.hip; wrapped by the C ABI in api.hip).
+#pragma once
+#include "common.h"
+
+namespace sat {
+constexpr int kCaptionMaxLen = 128;      // SAT_CAPTION_MAX_LEN
+constexpr int kCaptionMaxRefs = 16;      // SAT_CAPTION_MAX_REFS
+constexpr int kCaptionMaxEmbed = 2048;   // SAT_CAPTION_MAX_EMBED
+int beam_select(const int* tok_in, const int* prev_row, const int* fin_count, const int* fin_step, const int* fin_row, const float* fin_score,
+                const float* fin_mean, const float* alpha_hist, int B, int K, int S, int L, int method, float reward, int pad_id, int* cap_tokens,
+                int* cap_len, float* cap_score, float* cap_raw, int* cap_step, float* cap_alpha, hipStream_t st);
+int caption_stats(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, int* stats, hipStream_t st);
+int caption_cosine(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, const float* embedding,
+                   int V, int m, float* best, hipStream_t st);
+}  // namespace sat

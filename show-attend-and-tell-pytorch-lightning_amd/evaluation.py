@@ -1,0 +1,174 @@
+"""The reference's ``evaluate.ipynb`` without the host tail: a validation batch stays on the device from image to metric statistics.
+
+``SAT.val_batch`` reads the search's back-trace (attention history included) to the host, rebuilds Python lists, counts n-grams four
+times over and loops over B x R tiny torch ops for the cosine.  Here the winning hypothesis of every image is picked and traced back
+by ``sat_beam_select``, ``sat_caption_stats`` produces the integers that corpus BLEU / GLEU sum per segment, ``sat_caption_cosine`` the
+best mean-embedding cosine (csrc/caption_score.hip); what reaches the host is one vector of 14 numbers per batch -- or per split:
+
+* ``caption_tokens``    encoder + batched search + selection: device tensors, no copy to the host, no synchronisation, capturable;
+* ``val_batch_stats``   the device counterpart of ``SAT.val_batch``: a ``CaptionStats`` (sums over the images of the batch);
+* ``evaluate``          a loader's batches: the notebook's mean of per-batch metrics AND the corpus-level score of the whole split
+                        (dev/todo.txt: "add the val_epoch_end, sum the nom/dem"), read from the device once at the end;
+* ``random_search``     the notebook's random search over decode parameters, same draws in the same order.
+"""
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import metrics
+
+#: the reference's BLEU weights (model.py:651-654), bleu3 as written there
+BLEU_WEIGHTS = {"bleu1": (1, 0, 0, 0), "bleu2": (0.5, 0.5, 0, 0), "bleu3": (0.33, 0.33, 0.33, 0), "bleu4": (0.25, 0.25, 0.25, 0.25)}
+METRIC_KEYS = ("bleu1", "bleu2", "bleu3", "bleu4", "cosine_similarity", "gleu", "perplexity")
+#: evaluate.ipynb's result table and parameter ranges
+HEADERS = ["beamk", "temperature", "sample_method", "decoder_noise", "rescore_method", "rescore_reward"] + list(METRIC_KEYS)
+NOTEBOOK_SPACE = dict(beamks=[5, 20], temperatures=(0.7, 1.2), sample_methods=["beam", "multinomial"], decoder_noises=[0.0],
+                      rescore_methods=["LN", "BAR"], rescore_rewards=(0.6, 1.3), max_gen_length=32)
+
+
+def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, with_alpha=False):
+    """``sat_beam_select`` on the buffers ``SATDecoder._beam_search_device`` returns: the best hypothesis of every image as
+    ``dict(tokens (B, S + 1) int32 padded with pad_id, lengths (B) int32, scores (B) rescored, raw (B), steps (B), alphas (B, S, L) or None)``."""
+    if rescore_method not in L.RESCORE:
+        raise ValueError("rescore_method=%r (None, 'LN', 'WR', 'BAR')" % (rescore_method,))
+    tok_in, alpha_hist = buffers["tok_in"], buffers["alpha_hist"]
+    L.require_gpu(tok_in)
+    S, (B, K), Lc = tok_in.shape[0] - 2, tok_in.shape[1:], alpha_hist.shape[-1]
+    dev = tok_in.device
+    i32 = dict(dtype=torch.int32, device=dev); f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(tokens=torch.empty(B, S + 1, **i32), lengths=torch.empty(B, **i32), scores=torch.empty(B, **f32), raw=torch.empty(B, **f32),
+               steps=torch.empty(B, **i32), alphas=torch.empty(B, S, Lc, **f32) if with_alpha else None)
+    L.check(L.lib().sat_beam_select(L.ptr(tok_in), L.ptr(buffers["prev_row"]), L.ptr(buffers["fin_count"]), L.ptr(buffers["fin_step"]),
+                                    L.ptr(buffers["fin_row"]), L.ptr(buffers["fin_score"]), L.ptr(buffers["fin_mean"]),
+                                    L.ptr(alpha_hist) if with_alpha else None, B, K, S, Lc, L.RESCORE[rescore_method], float(rescore_reward), int(pad_id),
+                                    L.ptr(out["tokens"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.ptr(out["raw"]), L.ptr(out["steps"]),
+                                    L.ptr(out["alphas"]), L.stream_ptr()), "sat_beam_select")
+    return out
+
+
+@torch.no_grad()
+def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
+                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
+    """``SAT.caption(..., return_all=False)`` with the result left on the device: ``(tokens (B, max_gen_length + 1) int32 padded with
+    <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises."""
+    if int(max_gen_length) < 1:
+        raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
+    model.eval()
+    ann_bld, _ = model.encode(img)
+    o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
+                                  graph)
+    sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward)
+    ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
+    return sel["tokens"], sel["lengths"], sel["scores"], ppl
+
+
+def caption_statistics(tokens, lengths, refs, ref_lengths, embedding):
+    """``(stats (B, 12) int32, best_cosine (B) float32)`` of hypotheses ``tokens (B, W)`` / ``lengths (B)`` against references
+    ``refs (B, R, T)`` / ``ref_lengths (B, R)`` (all int32, on the device; layouts: include/sat_hip.h, sat_caption_stats)."""
+    L.require_gpu(tokens, lengths, refs, ref_lengths, embedding)
+    for t in (tokens, lengths, refs, ref_lengths):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert embedding.dtype == torch.float32 and embedding.is_contiguous()
+    B, W = tokens.shape
+    _, R, T = refs.shape
+    V, m = embedding.shape
+    stats = torch.empty(B, 12, dtype=torch.int32, device=tokens.device)
+    best = torch.empty(B, dtype=torch.float32, device=tokens.device)
+    lib = L.lib()
+    L.check(lib.sat_caption_stats(L.ptr(tokens), L.ptr(lengths), W, L.ptr(refs), L.ptr(ref_lengths), B, R, T, L.ptr(stats), L.stream_ptr()),
+            "sat_caption_stats")
+    L.check(lib.sat_caption_cosine(L.ptr(tokens), L.ptr(lengths), W, L.ptr(refs), L.ptr(ref_lengths), B, R, T, L.ptr(embedding), V, m, L.ptr(best),
+                                   L.stream_ptr()), "sat_caption_cosine")
+    return stats, best
+
+
+def metrics_from_sums(counts, cosine_sum, perplexity_sum, images):
+    """the seven keys of ``score_captions`` from host numbers: 12 summed integers, two float sums, the image count"""
+    counts = [int(c) for c in counts]
+    out = {k: metrics.bleu_from_stats(counts[0:4], counts[4:8], counts[8], counts[9], w) for k, w in BLEU_WEIGHTS.items()}
+    out["cosine_similarity"] = float(cosine_sum) / images
+    out["gleu"] = metrics.gleu_from_stats(counts[10], counts[11])
+    out["perplexity"] = float(perplexity_sum) / images
+    return out
+
+
+class CaptionStats:
+    """Sums over images: ``counts`` (12,) int64 (the columns of sat_caption_stats), ``cosine_sum`` / ``perplexity_sum`` (float64
+    scalars) on the device, ``images`` a host int.  ``a + b`` adds; ``metrics()`` reads the device once."""
+
+    def __init__(self, counts, cosine_sum, perplexity_sum, images):
+        self.counts, self.cosine_sum, self.perplexity_sum, self.images = counts, cosine_sum, perplexity_sum, int(images)
+
+    def __add__(self, other):
+        return CaptionStats(self.counts + other.counts, self.cosine_sum + other.cosine_sum, self.perplexity_sum + other.perplexity_sum,
+                            self.images + other.images)
+
+    def vector(self):
+        """(14,) float64 on the device: the counts (exact below 2^53), then the two sums"""
+        return torch.cat([self.counts.to(torch.float64), self.cosine_sum.reshape(1), self.perplexity_sum.reshape(1)])
+
+    def metrics(self):
+        v = self.vector().cpu().tolist()
+        return metrics_from_sums(v[:12], v[12], v[13], self.images)
+
+
+@torch.no_grad()
+def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
+                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
+    """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back."""
+    img, encoded_captions, lengths = batch
+    dev = model.embedding.weight.device
+    tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
+                                          rescore_method, rescore_reward, seed, graph)
+    refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
+    ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+    stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())
+    return CaptionStats(stats.sum(0, dtype=torch.int64), best.sum(dtype=torch.float64), ppl.sum(dtype=torch.float64), tokens.shape[0])
+
+
+def evaluate(model, loader, max_batches=None, seed=None, **decode):
+    """``val_batch_stats`` over the batches of ``loader`` (at most ``max_batches``).  Returns ``{"batch_mean": the notebook's protocol,
+    the plain mean of the per-batch metric dicts, "corpus": BLEU / GLEU taken once from the statistics summed over every image (cosine and
+    perplexity: means over images), "batches", "images"}``.  The per-batch statistics stay on the device and are read once at the end.
+    ``seed``: batch i of a sampled search draws with ``seed + i``."""
+    vecs, images = [], []
+    for i, batch in enumerate(loader):
+        if max_batches is not None and i >= max_batches:
+            break
+        st = model.val_batch_stats(batch, seed=None if seed is None else int(seed) + i, **decode)
+        vecs.append(st.vector()); images.append(st.images)
+    if not vecs:
+        raise ValueError("evaluate: the loader gave no batch")
+    rows = torch.stack(vecs).cpu().tolist()                                  # the one host read
+    per_batch = [metrics_from_sums(r[:12], r[12], r[13], n) for r, n in zip(rows, images)]
+    total = [sum(int(r[c]) for r in rows) for c in range(12)]
+    corpus = metrics_from_sums(total, sum(r[12] for r in rows), sum(r[13] for r in rows), sum(images))
+    return {"batch_mean": {k: sum(d[k] for d in per_batch) / len(per_batch) for k in METRIC_KEYS}, "corpus": corpus, "batches": len(per_batch),
+            "images": sum(images)}
+
+
+def draw_decode_params(rs, space=NOTEBOOK_SPACE):
+    """one trial's parameters from ``rs`` (np.random.RandomState) in the notebook's order: choice, uniform, choice, choice, choice, uniform"""
+    beamk = rs.choice(space["beamks"])
+    temperature = rs.uniform(space["temperatures"][0], space["temperatures"][1])
+    sample_method = rs.choice(space["sample_methods"])
+    decoder_noise = rs.choice(space["decoder_noises"])
+    rescore_method = rs.choice(space["rescore_methods"])
+    rescore_reward = rs.uniform(space["rescore_rewards"][0], space["rescore_rewards"][1])
+    return {"beamk": int(beamk), "temperature": float(temperature), "sample_method": str(sample_method), "decoder_noise": float(decoder_noise),
+            "rescore_method": str(rescore_method), "rescore_reward": float(rescore_reward)}
+
+
+def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4):
+    """evaluate.ipynb's random search: ``trials`` draws from one ``np.random.RandomState(seed)``, each scored over the first
+    ``max_batches`` batches.  Rows carry the notebook's 13 columns (the metrics are its batch means) plus ``<metric>_corpus``."""
+    rs = np.random.RandomState(seed)
+    rows = []
+    for trial in range(int(trials)):
+        row = draw_decode_params(rs, space)
+        res = evaluate(model, loader, max_batches=max_batches, seed=None if seed is None else (int(seed) * 1000003 + trial) % (2 ** 62),
+                       max_gen_length=space["max_gen_length"], **row)
+        row.update(res["batch_mean"])
+        row.update({k + "_corpus": v for k, v in res["corpus"].items()})
+        rows.append(row)
+    return rows

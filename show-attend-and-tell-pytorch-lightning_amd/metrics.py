@@ -91,3 +91,22 @@ def corpus_gleu(list_of_references, hypotheses, min_len=1, max_len=4):
         if best is not None:
             n_match += best[0]; n_all += best[1]
     return 0.0 if n_all == 0 else n_match / n_all
+
+
+def bleu_from_stats(clipped, total, hyp_len, ref_len, weights=(0.25, 0.25, 0.25, 0.25)):
+    """The tail of ``corpus_bleu`` on statistics already summed over the corpus: ``clipped[i]`` / ``total[i]`` the clipped matches and the
+    per-segment ``max(1, .)`` hypothesis n-gram totals of order i + 1, ``hyp_len`` / ``ref_len`` the summed hypothesis and closest reference
+    lengths (integers)."""
+    bp = brevity_penalty(int(ref_len), int(hyp_len))
+    if int(clipped[0]) == 0:
+        return 0
+    terms = []
+    for i, w in enumerate(weights):
+        p = Fraction(int(clipped[i]), int(total[i])) if int(clipped[i]) != 0 else None          # method0, as in corpus_bleu
+        terms.append(w * math.log(p if p is not None else sys.float_info.min))
+    return bp * math.exp(math.fsum(terms))
+
+
+def gleu_from_stats(tp, total):
+    """The tail of ``corpus_gleu``: matches and totals of each segment's best reference, summed over the corpus."""
+    return 0.0 if int(total) == 0 else int(tp) / int(total)

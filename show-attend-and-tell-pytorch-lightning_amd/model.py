@@ -237,22 +237,11 @@ class SATDecoder(nn.Module):
                 cap_scores.append(fin_scores[best]); cap_ppl.append(fin_ppl[best])
         return captions, cap_scores, cap_alphas, cap_ppl
 
-    @torch.no_grad()
-    def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
-                            return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False):
-        """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
-        (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
-        completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
-        the back-trace once and rebuilds the reference's four lists (model.py:449-472).
-        ``sample_method`` "multinomial" / "topk" (model.py:360-379) and ``decoder_noise`` (model.py:322-324) run in the same call:
-        the hypotheses are drawn on the device as the top k of log p + Gumbel noise (an ordered sample without replacement, like
-        ``torch.multinomial``) from a counter-based generator seeded by ``seed`` (default: one draw from torch's CPU generator);
-        ``gumbel`` / ``normals`` replace the generator by tables (layouts: include/sat_hip.h, sat_beam_sampling).
-        ``graph=True`` ("beam" sampling without noise): the call's ~25 launches per decode step are captured once per (batch
-        shape, beam, length, temperatures, weights) into a hipGraph over static buffers and replayed - the same kernels with the
-        same arguments, one submission."""
+    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph):
+        """The device half of ``beam_decode_batched``: enqueue the whole search for annotations (B, L, D) (eagerly, or as the replay of
+        its cached hipGraph) and return the buffers it leaves on the device (tok_in, prev_row, alpha_hist, fin_*: include/sat_hip.h,
+        sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted)."""
         import ctypes as C
-        import numpy as np
         assert sample_method in ("beam", "multinomial", "topk")
         lib = L.lib()
         L.require_gpu(ann_bld)
@@ -260,7 +249,6 @@ class SATDecoder(nn.Module):
         dev = ann_bld.device
         ann_bld = ann_bld.contiguous()
         B, Lc, D = ann_bld.shape
-        Hh, Ww = hw
         V, m = self.embedding.weight.shape
         n = self.lstm.weight_hh_l0.shape[1]
         A = self.attention.decoder_att.weight.shape[0]
@@ -318,6 +306,27 @@ class SATDecoder(nn.Module):
         else:
             o = buffers()
             enqueue(ann_bld, o)
+        return o
+
+    @torch.no_grad()
+    def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
+                            return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False):
+        """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
+        (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
+        completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
+        the back-trace once and rebuilds the reference's four lists (model.py:449-472).
+        ``sample_method`` "multinomial" / "topk" (model.py:360-379) and ``decoder_noise`` (model.py:322-324) run in the same call:
+        the hypotheses are drawn on the device as the top k of log p + Gumbel noise (an ordered sample without replacement, like
+        ``torch.multinomial``) from a counter-based generator seeded by ``seed`` (default: one draw from torch's CPU generator);
+        ``gumbel`` / ``normals`` replace the generator by tables (layouts: include/sat_hip.h, sat_beam_sampling).
+        ``graph=True`` ("beam" sampling without noise): the call's ~25 launches per decode step are captured once per (batch
+        shape, beam, length, temperatures, weights) into a hipGraph over static buffers and replayed - the same kernels with the
+        same arguments, one submission."""
+        import numpy as np
+        o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph)
+        B = ann_bld.shape[0]
+        Hh, Ww = hw
+        K, S = int(beamk), int(max_gen_length)
         tok_in, prev_row, alpha_hist = o["tok_in"], o["prev_row"], o["alpha_hist"]
         fin_count, fin_step, fin_row, fin_score, fin_mean = o["fin_count"], o["fin_step"], o["fin_row"], o["fin_score"], o["fin_mean"]
         tok_in, prev_row = tok_in.cpu().numpy(), prev_row.cpu().numpy()
@@ -646,6 +655,20 @@ class SAT(SATDecoder, _Base):
         captions, scores, alphas, perplexities = self.caption(img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                                                               rescore_method, rescore_reward, return_all=False)
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
+
+    def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
+                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
+        """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
+        from . import evaluation
+        return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
+                                         rescore_reward, seed, graph)
+
+    def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
+                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
+        """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict"""
+        from . import evaluation
+        return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
+                                          rescore_reward, seed, graph)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

@@ -1,0 +1,75 @@
+"""The reference's evaluate.ipynb as a command (dev/todo.txt: "new eval script"): checkpoint + dataset json in, a table of decode
+parameters and metrics out.  Without --trials: one pass over the split at the given decode parameters, printing the notebook's mean
+of per-batch metrics and the corpus-level score of the whole split.  With --trials N: the notebook's random search (N draws from its
+parameter ranges, each scored over the first --max-batches batches), written as csv with its 13 columns plus ``<metric>_corpus``.
+All work is in sat_amd/evaluation.py: a batch is decoded and scored on the device, one host read per pass.
+    python tools/evaluate.py CHECKPOINT [--json DATASET.json] [--root IMAGE_DIR] [--split test] [--batch N] [--max-batches M]
+                             [--trials N --seed S --out results.csv]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import sat_amd  # noqa: E402,F401
+from sat_amd import data as D  # noqa: E402
+from sat_amd import evaluation as E  # noqa: E402
+from sat_amd.model import SAT  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("checkpoint")
+    ap.add_argument("--json", default=None, help="dataset json; default: the one recorded in the checkpoint's hyper-parameters")
+    ap.add_argument("--root", default=None, help="directory the json's relative image paths start from")
+    ap.add_argument("--split", default="test")
+    ap.add_argument("--batch", type=int, default=None, help="default: the checkpoint's training batch size, as the notebook")
+    ap.add_argument("--max-batches", type=int, default=None, help="default: the whole split (4 with --trials, as the notebook)")
+    ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--trials", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--out", default=None, help="csv (with --trials) or json (without) to write")
+    ap.add_argument("--beamk", type=int, default=5)
+    ap.add_argument("--max-gen-length", type=int, default=32)
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk"])
+    ap.add_argument("--sample-topk", type=int, default=3)
+    ap.add_argument("--decoder-noise", type=float, default=0.0)
+    ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
+    ap.add_argument("--rescore-reward", type=float, default=0.5)
+    a = ap.parse_args()
+
+    ckpt = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    model = SAT(**dict(ckpt["hyper_parameters"]))
+    model.load_state_dict(ckpt["state_dict"])
+    model = model.cuda()
+    ds = D.CocoCaptionDataset(a.json or model.hparams.json, a.split, root=a.root)
+    loader = D.DeviceLoader(ds, a.batch or model.hparams.batch, D.BatchTransform(model.hparams.input_size, train=False), workers=a.workers)
+    if a.trials > 0:
+        rows = E.random_search(model, loader, a.trials, seed=a.seed, max_batches=a.max_batches or 4)
+        cols = list(rows[0])
+        for r in sorted(rows, key=lambda r: -r["bleu4"]):
+            print("  ".join("%s=%s" % (k, ("%.4f" % r[k]) if isinstance(r[k], float) else r[k]) for k in E.HEADERS))
+        if a.out:
+            with open(a.out, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=cols)
+                w.writeheader(); w.writerows(rows)
+        return
+    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
+                     sample_method=a.sample_method, sample_topk=a.sample_topk, decoder_noise=a.decoder_noise,
+                     rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward)
+    print("%d images in %d batches" % (res["images"], res["batches"]))
+    for k in E.METRIC_KEYS:
+        print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f)
+
+
+if __name__ == "__main__":
+    main()
