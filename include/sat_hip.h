@@ -657,6 +657,43 @@ int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, c
                           int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
                           uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- attention overlays on device (visualize.ipynb's make_visual) ------------------------------------------------------
+ * The single-image front end of util.py:141-164: load_square = crop_center(min side) then Image.resize((S, S)) with no filter
+ * named, which is Pillow's BICUBIC; prepare_image = the same once more, then T.ToTensor().  Bit exact with Pillow 12.2.
+ * Input: n HWC uint8 pictures in `pixels`, one sat_image_desc each of which ONLY offset, height and width are read (the
+ * bytes may be what sat_jpeg_decode_batch wrote).  The box is util.py's integer rule
+ *   s = min(W, H);  left = (W - s) // 2;  top = (H - s) // 2     (right - left = lower - top = s for every parity)
+ * and the resample is Resample.c as sat_image_batch_transform restates it for BILINEAR, except
+ *   support = 2.0 * filterscale,  taps = ceil(support) * 2 + 1   (5 when enlarging, clipped at the borders)
+ *   weight(x) = ((a + 2)|x| - (a + 3)) x^2 + 1  for |x| < 1,  (((|x| - 5)|x| + 8)|x| - 4) a  for |x| < 2,  else 0;  a = -0.5
+ *   coefficient = (int)(w 2^22 + 0.5) for w >= 0 and (int)(w 2^22 - 0.5) for w < 0, w normalised by the sum of the taps
+ * every double operation rounded on its own in Pillow's order; horizontal pass first into 8-bit, clip8 after each pass.
+ * A box side above SAT_BICUBIC_MAX_SHRINK * S is SAT_EINVAL (129 taps at most, as the BILINEAR path's table).
+ * out_u8 (n, S, S, 3) and / or out_nchw (n, 3, S, S) = byte / 255 in fp32, one correctly rounded division (T.ToTensor()).
+ * prepare_image(load_square(path, V), s) is two calls: the second reads the first's out_u8 through descriptors with
+ * offset = i * V * V * 3 and height = width = V.  desc_host / desc_dev: the same records in host and device memory. */
+#define SAT_BICUBIC_MAX_SHRINK 32
+size_t sat_image_square_bicubic_workspace_bytes(const sat_image_desc* desc_host, int32_t n, int32_t S);
+int sat_image_square_bicubic(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev, int32_t n,
+                             int32_t S, uint8_t* out_u8 /* or NULL */, float* out_nchw /* or NULL */, void* workspace, size_t workspace_bytes,
+                             void* stream);
+/* The panels of make_visual for B captioned pictures: square (B, V, V, 3) uint8, cap_alpha (B, Tmax, h * w) and cap_len (B) as
+ * sat_beam_select leaves them (cap_len is clamped to [0, Tmax]) -> panels (B, Tmax + 2, V, V, 3) uint8.  With n = cap_len[b]:
+ *   panel 0        the picture
+ *   panel 1 + t    t < n: att = cap_alpha[b, t];  x = (att - min) / (max - min) in fp32;  x ** power (the host's powf: evaluated
+ *                  in double, rounded once);  m = (uint8)(x * 255), truncated;  m enlarged from (h, w) to (V, V) by the BICUBIC
+ *                  resample above (an L-mode resize: what the notebook's RGB resize of a grey mask gives in every channel);
+ *                  byte = (uint8)(p + opacity * (m - p)) in fp32 without contraction, truncated = Image.blend(picture, mask, opacity)
+ *   panel n + 1    "Total Attention": att = the fp32 sum of cap_alpha[b, 0..n-1] in step order, normalised the same way, no
+ *                  power, enlarged, written to the three channels with no picture under it
+ *   panels beyond  zero
+ * max == min (a 1 x 1 map, the total of a blank caption; 0 / 0 in the notebook) gives a zero mask.
+ * h * w <= SAT_ATTENTION_MAX_MAP, h <= V and w <= V (the mask is only ever enlarged), 0 <= opacity <= 1, power finite and > 0.
+ * One launch; the masks live in LDS only. */
+#define SAT_ATTENTION_MAX_MAP 256
+int sat_attention_panels(const uint8_t* square, const float* cap_alpha, const int32_t* cap_len, int32_t B, int32_t Tmax, int32_t V, int32_t h,
+                         int32_t w, float power, float opacity, uint8_t* panels, void* stream);
+
 /* mobilenet_v3_small trunk (model.py:38-39 keeps torchvision's `features`; torchvision 0.10 _mobilenet_v3_conf("mobilenet_v3_small"), Howard et
  * al. 2019 table 2).  dtype: 0 = fp32, 1 = bf16 activations; NHWC; statistics, SE vectors, parameters and their gradients fp32.
  *   depthwise 5x5, pad 2, stride 1 | 2 (InvertedResidual's depthwise ConvBNActivation, kernel_size 5): as sat_dwconv3x3_*, C a multiple of 4

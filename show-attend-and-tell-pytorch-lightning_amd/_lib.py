@@ -288,6 +288,12 @@ SYMBOLS.update({          # scoring decoded captions on the device (evaluation.p
     "sat_caption_stats": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "sat_caption_cosine": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
 })
+SYMBOLS.update({          # attention overlays (visualize.py)
+    "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
+    "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_attention_panels": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _f, _vp, _vp]),
+})
+BICUBIC_MAX_SHRINK, ATTENTION_MAX_MAP = 32, 256                                 # SAT_BICUBIC_MAX_SHRINK, SAT_ATTENTION_MAX_MAP
 CAPTION_MAX_LEN, CAPTION_MAX_REFS, CAPTION_MAX_EMBED = 128, 16, 2048          # SAT_CAPTION_MAX_* of include/sat_hip.h
 RESCORE = {None: 0, "NONE": 0, "LN": 1, "WR": 2, "BAR": 3}                      # SAT_RESCORE_*
 

@@ -670,6 +670,21 @@ class SAT(SATDecoder, _Base):
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                           rescore_reward, seed, graph)
 
+    def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
+                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, **render):
+        """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
+        attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py)"""
+        from . import visualize
+        return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
+                                   rescore_reward, visual_size, input_size, **render)
+
+    def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
+                      rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None):
+        """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities)"""
+        from . import visualize
+        return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
+                                       rescore_reward, visual_size, input_size, seed)
+
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""
         return self.val_batch(batch, beamk=self.hp.val_beamk, max_gen_length=self.hp.val_max_len, temperature=1.0, rescore_method="LN")
