@@ -663,12 +663,11 @@ int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, c
  * Input: n HWC uint8 pictures in `pixels`, one sat_image_desc each of which ONLY offset, height and width are read (the
  * bytes may be what sat_jpeg_decode_batch wrote).  The box is util.py's integer rule
  *   s = min(W, H);  left = (W - s) // 2;  top = (H - s) // 2     (right - left = lower - top = s for every parity)
- * and the resample is Resample.c as sat_image_batch_transform restates it for BILINEAR, except
- *   support = 2.0 * filterscale,  taps = ceil(support) * 2 + 1   (5 when enlarging, clipped at the borders)
+ * and the resample is the code of sat_image_batch_transform (the same kernels, csrc/pillow_resample.h) with three differences:
+ *   support = 2.0 * filterscale, so taps = ceil(support) * 2 + 1   (5 when enlarging, clipped at the borders)
  *   weight(x) = ((a + 2)|x| - (a + 3)) x^2 + 1  for |x| < 1,  (((|x| - 5)|x| + 8)|x| - 4) a  for |x| < 2,  else 0;  a = -0.5
- *   coefficient = (int)(w 2^22 + 0.5) for w >= 0 and (int)(w 2^22 - 0.5) for w < 0, w normalised by the sum of the taps
- * every double operation rounded on its own in Pillow's order; horizontal pass first into 8-bit, clip8 after each pass.
- * A box side above SAT_BICUBIC_MAX_SHRINK * S is SAT_EINVAL (129 taps at most, as the BILINEAR path's table).
+ *   a negative coefficient is (int)(w 2^22 - 0.5): rounded away from zero, as the positive ones are
+ * A box side above SAT_BICUBIC_MAX_SHRINK * S is SAT_EINVAL (129 taps at most, the table both filters share).
  * out_u8 (n, S, S, 3) and / or out_nchw (n, 3, S, S) = byte / 255 in fp32, one correctly rounded division (T.ToTensor()).
  * prepare_image(load_square(path, V), s) is two calls: the second reads the first's out_u8 through descriptors with
  * offset = i * V * V * 3 and height = width = V.  desc_host / desc_dev: the same records in host and device memory. */

@@ -7,7 +7,8 @@ What the reference does per sample (train.py:208-233, util.py:16-45,121-130):
 torchvision's resize is ``PIL.Image.resize(size, BILINEAR)``, i.e. Pillow's
 antialiased two-pass resampler (third party: Pillow ``src/libImaging/Resample.c``;
 12.2.0 is the version in this image).  ``resample_u8`` restates that published algorithm
-in numpy integer arithmetic; ``tests/golden/g11_input_pipeline.npz`` pins it bit for bit
+in integer arithmetic, for BILINEAR and for the BICUBIC of the attention overlays
+(tests/attention_panels_ref.py); ``tests/golden/g11_input_pipeline.npz`` pins it bit for bit
 against Pillow itself, and pins ``BucketSampler`` / ``AddGaussianNoise`` /
 ``crop_max_square`` against the reference's own ``util.py`` run in the build container.
 
@@ -26,39 +27,50 @@ import torch
 PRECISION_BITS = 32 - 8 - 2      # Resample.c: 8-bit pixels, 2 bits of head room
 
 
-def _triangle(x):
+def _bilinear_filter(x):
     """Resample.c bilinear_filter."""
-    x = np.abs(x)
-    return np.where(x < 1.0, 1.0 - x, 0.0)
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
 
 
-def resample_coeffs(in_size, out_size):
-    """Resample.c precompute_coeffs + normalize_coeffs_8bpc for the box [0, in_size).
-    Returns (bounds (out,2) int32 = first tap / tap count, coeffs (out,ksize) int32)."""
+def _bicubic_filter(x):
+    """Resample.c bicubic_filter (a = -0.5), in its order of evaluation."""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+FILTERS = {"bilinear": (1.0, _bilinear_filter), "bicubic": (2.0, _bicubic_filter)}      # name -> (support, weight function)
+
+
+def resample_coeffs(in_size, out_size, filter="bilinear"):
+    """Resample.c precompute_coeffs + normalize_coeffs_8bpc for the box [0, in_size), in Python floats
+    (= C doubles, one rounding per operation).  Returns (bounds (out,2) int32 = first tap / tap count,
+    coeffs (out,ksize) int32)."""
+    support, weight = FILTERS[filter]
     scale = float(in_size) / float(out_size)
     filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
+    support = support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     kk = np.zeros((out_size, ksize), np.int32)
     ss = 1.0 / filterscale
     for xx in range(out_size):
         center = 0.0 + (xx + 0.5) * scale
-        xmin = int(center - support + 0.5)
-        if xmin < 0:
-            xmin = 0
-        xmax = int(center + support + 0.5)
-        if xmax > in_size:
-            xmax = in_size
-        xmax -= xmin
-        x = np.arange(xmax, dtype=np.float64)
-        w = _triangle(((x + xmin) - center + 0.5) * ss)
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [weight((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:                       # sequential sum, as the C loop
-            ww += float(v)
+            ww += v
         if ww != 0.0:
-            w = w / ww
-        kk[xx, :xmax] = (0.5 + w * float(1 << PRECISION_BITS)).astype(np.int64)
+            w = [v / ww for v in w]
+        # a negative lobe (BICUBIC only) rounds away from zero too
+        kk[xx, :xmax] = [int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS)) for v in w]
         bounds[xx] = (xmin, xmax)
     return bounds, kk
 
@@ -75,14 +87,14 @@ def _pass(img, bounds, kk, axis):
     return np.moveaxis(out, 0, axis)
 
 
-def resample_u8(img, out_h, out_w):
-    """``Image.fromarray(img).resize((out_w, out_h), BILINEAR)`` for an (H, W, C) uint8 array:
-    horizontal pass to 8 bits, then vertical pass (Resample.c ImagingResample)."""
+def resample_u8(img, out_h, out_w, filter="bilinear"):
+    """``Image.fromarray(img).resize((out_w, out_h), BILINEAR | BICUBIC)`` for an (H, W) or (H, W, C) uint8
+    array: horizontal pass to 8 bits, then vertical pass (Resample.c ImagingResample)."""
     h, w = img.shape[:2]
     if w != out_w:
-        img = _pass(img, *resample_coeffs(w, out_w), axis=1)
+        img = _pass(img, *resample_coeffs(w, out_w, filter), axis=1)
     if h != out_h:
-        img = _pass(img, *resample_coeffs(h, out_h), axis=0)
+        img = _pass(img, *resample_coeffs(h, out_h, filter), axis=0)
     return img
 
 

@@ -4,70 +4,18 @@
 //                              batch of HWC uint8 pictures, bit exact, with T.ToTensor()'s fp32 planes on request
 //   sat_attention_panels       per caption step: the (h, w) attention map normalised to [0, 1], raised to a power, cut to bytes,
 //                              enlarged to (V, V) by the same BICUBIC resample and blended over the picture; plus "Total Attention"
-// Pillow's Resample.c is restated as image_pipeline.hip restates it for BILINEAR (separable, support scaled by the shrink factor,
-// 22-bit integer coefficients from double weights, horizontal pass first, each pass rounded and clipped to bytes); what differs is the
-// support (2.0 * filterscale), the weight function (bicubic_filter, a = -0.5) and the rounding of the negative coefficients it brings.
-// Nothing is shared with image_pipeline.hip, so the BILINEAR path cannot move.
-#include "../../include/sat_hip.h"
-#include "common.h"
-
-#include <cmath>
+// The resample is pillow_resample.h, shared with image_pipeline.hip's BILINEAR path: the same coefficient, rows and column-finish
+// kernels, here with the BICUBIC filter (support 2.0 * filterscale, the cubic weights with a = -0.5, negative coefficients rounded away
+// from zero) and the centred square as geometry.  The panels kernel builds its 5-tap tables with the same resample_entry.
+#include "pillow_resample.h"
 
 // every floating-point operation rounds on its own, as the host code it reproduces does (Makefile: -ffp-contract=off)
 #pragma clang fp contract(off)
 
 namespace sat {
 
-constexpr int BC_BITS = 32 - 8 - 2;          // Pillow's PRECISION_BITS for 8-bit pixels
-constexpr int BC_MAX_SHRINK = SAT_BICUBIC_MAX_SHRINK;
-constexpr int BC_MAX_TAPS = 4 * BC_MAX_SHRINK + 1;      // ceil(2 * 32) * 2 + 1 = 129
+constexpr int BC_MAX_SHRINK = SAT_BICUBIC_MAX_SHRINK;   // ceil(2 * 32) * 2 + 1 = 129 = RS_MAX_TAPS
 constexpr int BC_UP_TAPS = 5;                // enlarging: ceil(2.0) * 2 + 1
-
-// Pillow's ksize: ceil(support) * 2 + 1 with support = 2 * max(1, in / out)
-__host__ __device__ inline int bicubic_taps(int in_size, int out_size) {
-    double fs = (double)in_size / (double)out_size;
-    if (fs < 1.0) fs = 1.0;
-    return (int)ceil(2.0 * fs) * 2 + 1;
-}
-
-// Resample.c bicubic_filter with a = -0.5, in its order of evaluation
-__device__ inline double bicubic_filter(double x) {
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return __dadd_rn(__dmul_rn(__dmul_rn(__dsub_rn(__dmul_rn(1.5, x), 2.5), x), x), 1.0);
-    if (x < 2.0) return __dmul_rn(__dsub_rn(__dmul_rn(__dadd_rn(__dmul_rn(__dsub_rn(x, 5.0), x), 8.0), x), 4.0), -0.5);
-    return 0.0;
-}
-
-// precompute_coeffs + normalize_coeffs_8bpc for output index xx of in_size samples resampled to out_size: the first tap, the tap count
-// (at most KT: the caller sizes KT by bicubic_taps) and the integer weights k[0..KT), zero past the count
-__device__ inline void bicubic_entry(int in_size, int out_size, int xx, int KT, int* __restrict__ first, int* __restrict__ count, int* __restrict__ k) {
-    const double scale = __ddiv_rn((double)in_size, (double)out_size);
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = __dmul_rn(2.0, filterscale);
-    const double ss = __ddiv_rn(1.0, filterscale);
-    const double center = __dadd_rn(0.0, __dmul_rn(__dadd_rn((double)xx, 0.5), scale));
-    int xmin = (int)__dadd_rn(__dsub_rn(center, support), 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)__dadd_rn(__dadd_rn(center, support), 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    if (xmax > KT) xmax = KT;                          // cannot happen (KT from the same rule); keeps the table in bounds
-    if (xmax < 0) xmax = 0;
-    double ww = 0.0;
-    for (int x = 0; x < xmax; ++x)
-        ww = __dadd_rn(ww, bicubic_filter(__dmul_rn(__dadd_rn(__dsub_rn((double)(x + xmin), center), 0.5), ss)));
-    for (int x = 0; x < xmax; ++x) {
-        double wv = bicubic_filter(__dmul_rn(__dadd_rn(__dsub_rn((double)(x + xmin), center), 0.5), ss));
-        if (ww != 0.0) wv = __ddiv_rn(wv, ww);
-        const double scaled = __dmul_rn(wv, (double)(1 << BC_BITS));
-        k[x] = wv < 0.0 ? (int)__dadd_rn(-0.5, scaled) : (int)__dadd_rn(0.5, scaled);      // negative lobes round away from zero too
-    }
-    for (int x = xmax; x < KT; ++x) k[x] = 0;
-    *first = xmin;
-    *count = xmax;
-}
-
-__device__ inline int bc_clip8(int v) { v >>= BC_BITS; return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // util.py:152-157 crop_center(img, s, s) with s = min(width, height): ((W - s) // 2, (H - s) // 2, (W + s) // 2, (H + s) // 2); the
 // box is s wide and high whatever the parities, because W - s and W + s are both even or both odd
@@ -78,93 +26,38 @@ __host__ __device__ inline void square_box(int height, int width, int* top, int*
     *top = (height - s) / 2;
 }
 
-// the box is square and so is the output: one coefficient table per picture serves both passes
-__global__ __launch_bounds__(64) void square_coeffs_kernel(const sat_image_desc* __restrict__ desc, int S, int KT, int* __restrict__ bounds,
-                                                           int* __restrict__ coeffs) {
-    const int img = blockIdx.z;
-    const int o = blockIdx.x * 64 + threadIdx.x;
-    if (o >= S) return;
-    int top, left, side;
-    square_box(desc[img].height, desc[img].width, &top, &left, &side);
-    int* b = bounds + ((long)img * S + o) * 2;
-    bicubic_entry(side, S, o, KT, b, b + 1, coeffs + ((long)img * S + o) * KT);
-}
-
-// horizontal pass over every row of the box: tmp[img][row][x] = RGBX bytes
-__global__ __launch_bounds__(256) void square_rows_kernel(const uint8_t* __restrict__ pixels, const sat_image_desc* __restrict__ desc, int S, int KT, int hmax,
-                                                          const int* __restrict__ bounds, const int* __restrict__ coeffs, uchar4* __restrict__ tmp) {
-    const int img = blockIdx.z;
-    const sat_image_desc d = desc[img];
-    int top, left, side;
-    square_box(d.height, d.width, &top, &left, &side);
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= S || row >= side) return;
-    const int* b = bounds + ((long)img * S + x) * 2;
-    const int* k = coeffs + ((long)img * S + x) * KT;
-    const int xmin = b[0], n = b[1];
-    const uint8_t* src = pixels + d.offset + ((long)(top + row) * d.width + left + xmin) * 3;
-    int s0 = 1 << (BC_BITS - 1), s1 = s0, s2 = s0;
-    for (int t = 0; t < n; ++t) {
-        const int kv = k[t];
-        s0 += src[t * 3 + 0] * kv; s1 += src[t * 3 + 1] * kv; s2 += src[t * 3 + 2] * kv;
+// sat_image_square_bicubic reads ONLY height and width (and offset) of a descriptor: the box is the centred square, resampled to the
+// output size, no window, no mirror.  The box is square and so is the output: one coefficient table per picture serves both passes.
+struct SquareGeometry {
+    static constexpr int TABLES = 1;
+    static __device__ ResampleGeometry of(const sat_image_desc& d, int out_h, int out_w) {
+        int top, left, side;
+        square_box(d.height, d.width, &top, &left, &side);
+        return {top, left, side, side, out_h, out_w, 0, 0, 0};
     }
-    tmp[((long)img * hmax + row) * S + x] = make_uchar4((unsigned char)bc_clip8(s0), (unsigned char)bc_clip8(s1), (unsigned char)bc_clip8(s2), 0);
-}
+};
 
-// vertical pass; the HWC bytes and / or T.ToTensor()'s planes (byte / 255, one correctly rounded fp32 division)
-__global__ __launch_bounds__(256) void square_cols_kernel(int S, int KT, int hmax, const int* __restrict__ bounds, const int* __restrict__ coeffs,
-                                                          const uchar4* __restrict__ tmp, uint8_t* __restrict__ out_u8, float* __restrict__ out) {
-    const int img = blockIdx.z;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= S || y >= S) return;
-    const int* b = bounds + ((long)img * S + y) * 2;
-    const int* k = coeffs + ((long)img * S + y) * KT;
-    const int ymin = b[0], n = b[1];
-    const uchar4* src = tmp + ((long)img * hmax + ymin) * S + x;
-    int s0 = 1 << (BC_BITS - 1), s1 = s0, s2 = s0;
-    for (int t = 0; t < n; ++t) {
-        const int kv = k[t];
-        const uchar4 p = src[(long)t * S];
-        s0 += p.x * kv; s1 += p.y * kv; s2 += p.z * kv;
-    }
-    const int v[3] = {bc_clip8(s0), bc_clip8(s1), bc_clip8(s2)};
-    const long plane = (long)S * S;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (out_u8) out_u8[(((long)img * S + y) * S + x) * 3 + c] = (uint8_t)v[c];
-        if (out) out[((long)img * 3 + c) * plane + (long)y * S + x] = __fdiv_rn((float)v[c], 255.0f);
-    }
-}
-
-struct SquarePlan { int KT, hmax; size_t bounds_off, coeffs_off, tmp_off, total; };
-
-static int square_plan(const sat_image_desc* d, int n, int64_t pixels_bytes, int S, SquarePlan* p) {
+static int square_plan(const sat_image_desc* d, int n, int64_t pixels_bytes, int S, ResamplePlan* p) {
     SAT_REQUIRE(n > 0 && n <= 65535, "square_bicubic: n=%d outside [1, 65535]", n);
     SAT_REQUIRE(S > 0 && S <= 16384, "square_bicubic: output size %d outside [1, 16384]", S);
     int KT = BC_UP_TAPS, hmax = 1;
     for (int i = 0; i < n; ++i) {
         const sat_image_desc& e = d[i];
-        SAT_REQUIRE(e.height > 0 && e.width > 0 && e.offset >= 0 && (pixels_bytes < 0 || e.offset + (int64_t)e.height * e.width * 3 <= pixels_bytes),
-                    "square_bicubic: picture %d (%dx%d at byte %lld) lies outside the pixel buffer", i, e.height, e.width, (long long)e.offset);
+        SAT_TRY(picture_in_buffer("square_bicubic", i, e, pixels_bytes));
         int top, left, side;
         square_box(e.height, e.width, &top, &left, &side);
         SAT_REQUIRE((int64_t)side <= (int64_t)BC_MAX_SHRINK * S, "square_bicubic: picture %d (side %d -> %d) shrinks by more than %dx", i, side, S,
                     BC_MAX_SHRINK);
-        const int k = bicubic_taps(side, S);
-        SAT_REQUIRE(k <= BC_MAX_TAPS, "square_bicubic: picture %d needs %d taps (at most %d)", i, k, BC_MAX_TAPS);
+        const int k = resample_taps<Bicubic>(side, S);
+        SAT_REQUIRE(k <= RS_MAX_TAPS, "square_bicubic: picture %d needs %d taps (at most %d)", i, k, RS_MAX_TAPS);
         if (k > KT) KT = k;
         if (side > hmax) hmax = side;
     }
     SAT_REQUIRE((hmax + 3) / 4 <= 65535, "square_bicubic: a side of %d pixels is too large", hmax);
-    p->KT = KT; p->hmax = hmax;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    p->bounds_off = take((size_t)n * S * 2 * sizeof(int));
-    p->coeffs_off = take((size_t)n * S * KT * sizeof(int));
-    p->tmp_off = take((size_t)n * hmax * S * sizeof(uchar4));
-    p->total = off;
+    p->KT = KT; p->hmax = hmax; p->omax = S;
+    Workspace ws;
+    carve_resample<SquareGeometry>(ws, p, n, S);
+    p->total = ws.total;
     return SAT_OK;
 }
 
@@ -226,7 +119,7 @@ __global__ __launch_bounds__(256) void attention_panels_kernel(const uint8_t* __
     if (tid < AP_TW + AP_TH) {                         // the tables of this tile's columns (w -> V) and rows (h -> V)
         const bool col = tid < AP_TW;
         const int o = col ? (blockIdx.x % tiles_x) * AP_TW + tid : (blockIdx.x / tiles_x) * AP_TH + (tid - AP_TW);
-        if (o < V) bicubic_entry(col ? w : h, V, o, BC_UP_TAPS, &tab_first[tid], &tab_count[tid], tab_k[tid]);
+        if (o < V) resample_entry<Bicubic>(col ? w : h, V, o, BC_UP_TAPS, &tab_first[tid], &tab_count[tid], tab_k[tid]);
     }
     __syncthreads();
     mn = fminf(fminf(red_min[0], red_min[1]), fminf(red_min[2], red_min[3]));
@@ -250,14 +143,14 @@ __global__ __launch_bounds__(256) void attention_panels_kernel(const uint8_t* __
         const int y = y0 + 4 * i;
         if (y >= V) continue;
         const int ry = AP_TW + (tid >> 6) + 4 * i, ymin = tab_first[ry], ny = tab_count[ry];
-        int v = 1 << (BC_BITS - 1);
+        int v = 1 << (RS_BITS - 1);
         for (int t = 0; t < ny; ++t) {                 // the horizontal pass of row ymin + t at column x, then its vertical weight
             const uint8_t* row = mask + (ymin + t) * w + xmin;
-            int s = 1 << (BC_BITS - 1);
+            int s = 1 << (RS_BITS - 1);
             for (int u = 0; u < nx; ++u) s += row[u] * tab_k[cx][u];
-            v += bc_clip8(s) * tab_k[ry][t];
+            v += clip8(s) * tab_k[ry][t];
         }
-        const int m = bc_clip8(v);
+        const int m = clip8(v);
         const long o = ((long)y * V + x) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) dst[o + c] = (uint8_t)(total ? m : blend_over(pic[o + c], m, opacity));
@@ -271,7 +164,7 @@ extern "C" {
 
 size_t sat_image_square_bicubic_workspace_bytes(const sat_image_desc* desc_host, int32_t n, int32_t S) {
     if (!desc_host) { fail(SAT_EINVAL, "square_bicubic: null descriptors"); return 0; }
-    SquarePlan p;
+    ResamplePlan p;
     if (square_plan(desc_host, n, -1, S, &p) != SAT_OK) return 0;
     return p.total;
 }
@@ -279,20 +172,16 @@ size_t sat_image_square_bicubic_workspace_bytes(const sat_image_desc* desc_host,
 int sat_image_square_bicubic(const uint8_t* pixels, int64_t pixels_bytes, const sat_image_desc* desc_host, const sat_image_desc* desc_dev, int32_t n,
                              int32_t S, uint8_t* out_u8, float* out_nchw, void* workspace, size_t workspace_bytes, void* stream) {
     if (!pixels || !desc_host || !desc_dev || !workspace || (!out_u8 && !out_nchw)) return fail(SAT_EINVAL, "square_bicubic: null pointer");
-    SquarePlan p;
+    ResamplePlan p;
     SAT_TRY(square_plan(desc_host, n, pixels_bytes, S, &p));
     SAT_REQUIRE(workspace_bytes >= p.total, "square_bicubic: workspace %zu < %zu bytes", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    int* bounds = (int*)(ws + p.bounds_off);
-    int* coeffs = (int*)(ws + p.coeffs_off);
-    uchar4* tmp = (uchar4*)(ws + p.tmp_off);
-    hipLaunchKernelGGL(square_coeffs_kernel, dim3((S + 63) / 64, 1, n), dim3(64), 0, st, desc_dev, S, p.KT, bounds, coeffs);
-    SAT_TRY(launch_ok("square_coeffs"));
-    hipLaunchKernelGGL(square_rows_kernel, dim3((S + 63) / 64, (p.hmax + 3) / 4, n), dim3(256), 0, st, pixels, desc_dev, S, p.KT, p.hmax, bounds, coeffs, tmp);
-    SAT_TRY(launch_ok("square_rows"));
-    hipLaunchKernelGGL(square_cols_kernel, dim3((S + 63) / 64, (S + 3) / 4, n), dim3(256), 0, st, S, p.KT, p.hmax, bounds, coeffs, tmp, out_u8, out_nchw);
-    return launch_ok("square_cols");
+    SAT_TRY((launch_resample_rows<Bicubic, SquareGeometry>(st, pixels, desc_dev, n, S, S, p, ws)));
+    hipLaunchKernelGGL(resample_cols_finish_kernel<SquareGeometry>, dim3((S + 63) / 64, (S + 3) / 4, n), dim3(256), 0, st, desc_dev, S, S, p.omax, p.KT, p.hmax,
+                       (const int*)(ws + p.bounds_off), (const int*)(ws + p.coeffs_off), (const uchar4*)(ws + p.tmp_off), (const float*)nullptr, 0.0f,
+                       out_nchw, out_u8);
+    return launch_ok("resample_cols_finish");
 }
 
 int sat_attention_panels(const uint8_t* square, const float* cap_alpha, const int32_t* cap_len, int32_t B, int32_t Tmax, int32_t V, int32_t h, int32_t w,

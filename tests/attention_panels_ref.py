@@ -3,8 +3,8 @@ what sat_image_square_bicubic and sat_attention_panels (csrc/attention_panels.hi
 
 * ``square`` / ``to_tensor``    crop_center's box arithmetic + ``Image.resize((size, size))`` (no filter: BICUBIC), ``T.ToTensor()``
 * ``panels``                    numpy fp32 for the mask, ``Image.resize`` to enlarge it, ``Image.blend`` to lay it over the picture
-* ``resample_int``              Pillow's BICUBIC resample in plain Python integers (coefficients in Python floats = doubles, one
-                                rounding per operation): pins the kernel's arithmetic against Pillow without a GPU
+* ``resample_int``              Pillow's BICUBIC resample in integers: oracle/image_oracle.py's restatement of Resample.c with its
+                                "bicubic" filter; pins the kernel's arithmetic against Pillow without a GPU
 * ``alpha_case`` / ``margin``   the attention maps the GPU test uses, generated from a seed, and the distance of every mask value
                                 from a truncation boundary (tests/test_visualize.py asserts it for those very arrays)
 """
@@ -14,14 +14,15 @@ import math
 import numpy as np
 from PIL import Image
 
-PRECISION_BITS = 32 - 8 - 2
+from oracle import image_oracle as IO
 
-#: (input (H, W), output size) pairs of the square tests
+#: (input (H, W), output size) pairs of the square tests; the last one has a side of exactly 32 x the output: 129 taps, the largest
+#: shrink sat_image_square_bicubic accepts
 SQUARE_CASES = [((7, 7), 32), ((14, 14), 256), ((5, 7), 32), ((1, 1), 8), ((1, 5), 16), ((37, 37), 16), ((61, 45), 32), ((480, 640), 256),
-                ((256, 256), 224), ((32, 32), 32)]
+                ((256, 256), 224), ((32, 32), 32), ((128, 130), 4)]
 #: (input (H, W), output (H, W)) pairs of the integer restatement: the list above, 5 x 7 as the mask path resizes it (no crop)
 RESAMPLE_CASES = [((7, 7), (32, 32)), ((14, 14), (256, 256)), ((5, 7), (32, 32)), ((1, 1), (8, 8)), ((1, 5), (16, 16)), ((37, 37), (16, 16)),
-                  ((45, 45), (32, 32)), ((480, 480), (256, 256)), ((256, 256), (224, 224)), ((32, 32), (32, 32))]
+                  ((45, 45), (32, 32)), ((480, 480), (256, 256)), ((256, 256), (224, 224)), ((32, 32), (32, 32)), ((128, 128), (4, 4))]
 
 
 def picture(h, w, seed, channels=3):
@@ -55,62 +56,9 @@ def to_tensor(sq):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the integers
-def bicubic_filter(x):
-    a = -0.5
-    if x < 0.0:
-        x = -x
-    if x < 1.0:
-        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
-    if x < 2.0:
-        return (((x - 5) * x + 8) * x - 4) * a
-    return 0.0
-
-
-def bicubic_coeffs(in_size, out_size):
-    """per output index: (first tap, [integer weights]) as Resample.c's precompute_coeffs + normalize_coeffs_8bpc give them"""
-    scale = in_size / out_size
-    filterscale = max(scale, 1.0)
-    support = 2.0 * filterscale
-    ss = 1.0 / filterscale
-    out = []
-    for xx in range(out_size):
-        center = 0.0 + (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [bicubic_filter((x + xmin - center + 0.5) * ss) for x in range(xmax)]
-        ww = 0.0
-        for v in w:
-            ww += v
-        if ww != 0.0:
-            w = [v / ww for v in w]
-        out.append((xmin, [int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS)) for v in w]))
-    return out
-
-
-def _clip8(v):
-    return min(max(v >> PRECISION_BITS, 0), 255)
-
-
-def _pass(a, table):
-    """resample the last axis of the integer array ``a`` (..., n) by ``table``"""
-    a = a.astype(np.int64)
-    out = np.empty(a.shape[:-1] + (len(table),), np.int64)
-    for o, (first, k) in enumerate(table):
-        acc = np.full(a.shape[:-1], 1 << (PRECISION_BITS - 1), np.int64)
-        for t, kv in enumerate(k):
-            acc += a[..., first + t] * kv
-        out[..., o] = np.clip(acc >> PRECISION_BITS, 0, 255)
-    return out
-
-
 def resample_int(a, out_h, out_w):
-    """``Image.resize((out_w, out_h), BICUBIC)`` of an (H, W) or (H, W, C) uint8 array: horizontal pass into bytes, then vertical"""
-    a = np.asarray(a)
-    x = a[..., None] if a.ndim == 2 else a
-    x = _pass(x.transpose(0, 2, 1), bicubic_coeffs(x.shape[1], out_w)).transpose(0, 2, 1)          # (H, out_w, C)
-    x = _pass(x.transpose(1, 2, 0), bicubic_coeffs(x.shape[0], out_h)).transpose(2, 0, 1)          # (out_h, out_w, C)
-    x = x.astype(np.uint8)
-    return x[..., 0] if a.ndim == 2 else x
+    """``Image.resize((out_w, out_h), BICUBIC)`` of an (H, W) or (H, W, C) uint8 array"""
+    return IO.resample_u8(np.asarray(a), out_h, out_w, "bicubic")
 
 
 def blend_rule(p, m):

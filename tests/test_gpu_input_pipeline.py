@@ -56,6 +56,26 @@ def test_rectangular_output_through_the_c_abi(D, g11):
         assert np.array_equal(raw[0].cpu().numpy(), g11["resize_out%d" % i]), "case %d" % i
 
 
+def test_rectangles_with_unequal_axes_equal_the_restatement(D):
+    """whole pictures, no flip, no noise: the two axes need very different tap counts (130 -> 4 next to an identity, 256 -> 4 =
+    129 taps, the table's limit, next to an enlargement), so a table stride or an axis taken from the other one shows"""
+    import ctypes as C
+    from sat_amd import _lib as L
+    lib = L.lib()
+    rng = np.random.default_rng(31)
+    for (h, w), (oh, ow) in (((130, 9), (4, 9)), ((9, 130), (9, 4)), ((5, 7), (3, 11)), ((1, 1), (8, 3)), ((256, 3), (4, 6))):
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        st = D.StagedBatch([img], [whole(h, w, oh, ow)])
+        dev = st.host.cuda()
+        need = lib.sat_image_batch_workspace_bytes(C.cast(st.desc, C.c_void_p), 1, oh, ow)
+        assert need > 0
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        raw = torch.empty(1, oh, ow, 3, dtype=torch.uint8, device="cuda")
+        L.check(lib.sat_image_batch_transform(dev.data_ptr() + st.head, st.pixels_bytes, C.cast(st.desc, C.c_void_p), dev.data_ptr(), 1, oh, ow, None, 0.0,
+                                              None, L.ptr(raw), L.ptr(ws), need, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "transform")
+        assert np.array_equal(raw[0].cpu().numpy(), IO.resample_u8(img, oh, ow)), ((h, w), (oh, ow))
+
+
 def test_crop_boxes_equal_pillow_fixture(D, g11):
     img = g11["crop_in"]
     boxes = g11["crop_boxes"].tolist()

@@ -36,7 +36,7 @@ def test_load_square_and_prepare_image_equal_pillow():
     ten = Z.prepare_image_batch(got)                              # ToTensor alone
     assert ten.shape == (len(items), 3, 32, 32) and ten.dtype == torch.float32
     assert np.array_equal(ten.cpu().numpy(), np.stack([R.to_tensor(s) for s in want]))
-    # every (shape, size) pair of the list at its own size
+    # every (shape, size) pair of the list at its own size; 128 x 130 -> 4 is the largest shrink the entry point accepts (129 taps)
     for size in sorted({s for _, s in R.SQUARE_CASES}):
         arrays = [R.picture(h, w, 60 + i) for i, ((h, w), s) in enumerate(R.SQUARE_CASES) if s == size]
         got = Z.load_square_batch(arrays, size).cpu().numpy()

@@ -50,6 +50,22 @@ def test_oracle_live_against_installed_pillow():
         assert np.array_equal(IO.resample_u8(img, oh, ow), np.asarray(Image.fromarray(img).resize((ow, oh), Image.BILINEAR)))
 
 
+def test_one_restatement_serves_both_filters_on_rectangles():
+    """the shared coefficient function and integer pass against the installed Pillow for BILINEAR and BICUBIC: axes with very
+    different tap counts, an identity axis, 64x shrinks, enlargements from 1 x 1"""
+    Image = pytest.importorskip("PIL.Image")
+    rng = np.random.default_rng(5)
+    cases = [((5, 7), (3, 11)), ((130, 9), (4, 9)), ((9, 130), (9, 4)), ((1, 1), (8, 3)), ((1, 5), (16, 2)), ((37, 23), (16, 31)),
+             ((2, 2), (64, 64)), ((256, 3), (4, 6))]
+    for name, pil in (("bilinear", Image.BILINEAR), ("bicubic", Image.BICUBIC)):
+        for (h, w), (oh, ow) in cases:
+            if name == "bicubic" and (h, w) == (256, 3):
+                continue                                 # a 64x BICUBIC shrink needs 257 taps: above what the kernels' table holds
+            img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+            want = np.asarray(Image.fromarray(img).resize((ow, oh), pil))
+            assert np.array_equal(IO.resample_u8(img, oh, ow, name), want), (name, (h, w), (oh, ow))
+
+
 # ------------------------------------------------------------------------------------------------ host logic of the product
 def test_bucket_sampler_matches_reference_order(g11):
     import sat_amd  # noqa: F401
