@@ -625,8 +625,15 @@ int sat_image_batch_transform_warp(const uint8_t* pixels, int64_t pixels_bytes, 
  * The step in front of the transform: util.py:136-137's Image.open(f).convert("RGB") for Huffman-coded sequential 8-bit
  * files (SOF0 / SOF1) with one scan of 1 (grayscale) or 3 YCbCr components, luma sampled h1v1, h2v1 or h2v2 and chroma
  * 1x1, with or without restart markers; bit exact with libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling).  The
- * host parses the headers (sat_amd/jpeg.py) and sends every other file to Pillow.  Three launches: entropy decoding (one
- * thread per picture and restart segment), dequantisation + ISLOW IDCT (per block), upsampling + YCbCr->RGB (per pixel).
+ * host parses the headers (sat_amd/jpeg.py) and sends every other file to Pillow.  Three stages: entropy decoding,
+ * dequantisation + ISLOW IDCT (per block), upsampling + YCbCr->RGB (per pixel).  Entropy decoding gives every restart
+ * segment one thread; a restart-free picture (n_segments == 1) of at least parallel_min_bytes of data is instead cut into
+ * subsequences of subseq_bytes raw bytes, each decoded by a thread of its own: a speculative pass from (slot 0, DC next),
+ * a self-synchronisation loop in which every thread decodes again from its predecessor's exit state until no state
+ * changes (one workgroup per picture, no host round trip), a prefix sum of the completed blocks, a write pass and a
+ * prefix sum of the DC differences.  A picture on which that comes up short (a marker in the data, an unverified chain, a
+ * wrong block count, a bad code met while writing) is cleared and decoded by the one-thread path in the same call, so
+ * status words and pixels never depend on the path.  No host synchronisation, allocation or read-back inside the call.
  * The (height, width, 3) bytes of each picture are written at its out_offset in `pixels`.
  *   data_offset, data_bytes   the entropy-coded data of the scan in `compressed`, RST markers included, 0xFF00 stuffed
  *   segments_offset           byte offset in `compressed` of n_segments (start, end) uint32 pairs, 4-byte aligned: the
@@ -656,6 +663,28 @@ size_t sat_jpeg_decode_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n
 int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
                           int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
                           uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two calls with options (NULL: the defaults, which is what the two calls above pass).
+ *   subseq_bytes        0: SAT_JPEG_SUBSEQ_BYTES_DEFAULT; else a multiple of 4 from 16 to 2^20.  The grid is measured from
+ *                       data_offset, stuffed bytes count; the workspace holds 24 bytes of state per subsequence.
+ *   parallel_min_bytes  -1: SAT_JPEG_PARALLEL_MIN_BYTES_DEFAULT; 0: every restart-free picture; INT64_MAX: none.  (A
+ *                       picture of more than 2^27 data bytes stays on the one-thread path.)
+ *   info                NULL, or n x 4 int32 on the device, per picture: the path taken (0 one thread per segment,
+ *                       1 subsequences, 2 subsequences abandoned for the one-thread path), its subsequences, the
+ *                       synchronisation rounds run, 0.
+ * SAT_EINVAL, before anything is enqueued: a bad subseq_bytes or parallel_min_bytes, null descriptors, a small workspace. */
+#define SAT_JPEG_SUBSEQ_BYTES_DEFAULT 128
+#define SAT_JPEG_PARALLEL_MIN_BYTES_DEFAULT 2048
+typedef struct sat_jpeg_decode_opts {
+    int32_t subseq_bytes;
+    int32_t reserved;
+    int64_t parallel_min_bytes;
+    int32_t* info;
+} sat_jpeg_decode_opts;
+size_t sat_jpeg_decode_workspace_bytes_ex(const sat_jpeg_desc* desc_host, int32_t n, const sat_jpeg_decode_opts* opts);
+int sat_jpeg_decode_batch_ex(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
+                             int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
+                             uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream,
+                             const sat_jpeg_decode_opts* opts);
 
 /* ---- attention overlays on device (visualize.ipynb's make_visual) ------------------------------------------------------
  * The single-image front end of util.py:141-164: load_square = crop_center(min side) then Image.resize((S, S)) with no filter

@@ -98,6 +98,11 @@ class JpegDesc(C.Structure):
                [(k, C.c_int32 * 3) for k in ("quant", "dc_table", "ac_table")] + [("reserved", C.c_int32)]
 
 
+class JpegDecodeOpts(C.Structure):
+    """sat_jpeg_decode_opts: subseq_bytes 0 and parallel_min_bytes -1 are the library's defaults; info: device (n, 4) int32 or None"""
+    _fields_ = [("subseq_bytes", C.c_int32), ("reserved", C.c_int32), ("parallel_min_bytes", C.c_int64), ("info", C.c_void_p)]
+
+
 class JpegQTable(C.Structure):
     _fields_ = [("q", C.c_uint16 * 64)]
 
@@ -260,7 +265,9 @@ SYMBOLS.update({"sat_image_batch_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32
                 "sat_image_batch_transform_warp": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _f, _vp, _vp, _vp,
                                                              C.c_size_t, _vp])})
 SYMBOLS.update({"sat_jpeg_decode_workspace_bytes": (C.c_size_t, [_vp, _i32]),
-                "sat_jpeg_decode_batch": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp])})
+                "sat_jpeg_decode_batch": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+                "sat_jpeg_decode_workspace_bytes_ex": (C.c_size_t, [_vp, _i32, _vp]),
+                "sat_jpeg_decode_batch_ex": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp, _vp])})
 SYMBOLS.update({"sat_profile_start": (C.c_int, []),
                 "sat_profile_start_only": (C.c_int, [C.c_char_p]),
                 "sat_profile_pause": (C.c_int, [_i32]),

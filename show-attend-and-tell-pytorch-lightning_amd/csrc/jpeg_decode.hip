@@ -3,6 +3,8 @@
 //   1. entropy decoding: one thread (lane 0 of a wave) per picture and restart segment.  Huffman codes through a 9-bit lookup
 //      table plus libjpeg's maxcode / valoffset search for longer codes; the picture's tables sit in LDS.  The coefficient
 //      blocks were cleared first, so only the non-zero coefficients are stored (int16, natural order).
+//      A restart-free picture above a size threshold is instead cut into subsequences with a lane each that synchronise on the
+//      device (section 1b below); what comes out is the same.
 //   2. dequantisation + jidctint.c's jpeg_idct_islow, one thread per 8x8 block, operation for operation, output through
 //      libjpeg's range_limit table (a wrap, not a clamp, for overshooting coefficients).
 //   3. jdsample.c's fancy upsampling (h2v1, h2v2; plain replication when the chroma is at most 2 samples wide) and jdcolor.c's
@@ -135,30 +137,21 @@ __device__ inline int receive_extend(BitReader& br, int s) {
     return r < (1 << (s - 1)) ? r + (int)((~0u << s) + 1u) : r;       // HUFF_EXTEND
 }
 
-__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
-                                                          int n, const sat_jpeg_htable* __restrict__ huff, int16_t* __restrict__ coefs,
-                                                          int* __restrict__ status) {
-    __shared__ sat_jpeg_htable tabs[6];
-    const int seg_global = blockIdx.x;
-    int lo = 0, hi = n - 1;                                   // picture: last one whose segment_base <= seg_global
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[mid].segment_base <= seg_global) lo = mid; else hi = mid - 1;
-    }
-    const int p = lo;
-    const sat_jpeg_desc& d = desc[p];                        // a reference: a local copy's arrays would live in scratch memory
-    const int seg = seg_global - d.segment_base;
-    if (seg < 0 || seg >= d.n_segments) return;
+// the picture's DC / AC tables (component c: tabs[2 c], tabs[2 c + 1]) into LDS, by every thread of the block
+__device__ __forceinline__ void load_tables(sat_jpeg_htable* tabs, const sat_jpeg_desc& d, const sat_jpeg_htable* __restrict__ huff) {
     const int nt = 2 * d.components;
     for (int t = 0; t < nt; ++t) {
         const int idx = (t & 1) ? d.ac_table[t >> 1] : d.dc_table[t >> 1];
         const uint32_t* src = reinterpret_cast<const uint32_t*>(huff + idx);
         uint32_t* dst = reinterpret_cast<uint32_t*>(&tabs[t]);
-        for (int k = threadIdx.x; k < (int)(sizeof(sat_jpeg_htable) / 4); k += 64) dst[k] = src[k];
+        for (int k = threadIdx.x; k < (int)(sizeof(sat_jpeg_htable) / 4); k += blockDim.x) dst[k] = src[k];
     }
     __syncthreads();
-    if (threadIdx.x != 0) return;
+}
 
+// the serial lane: restart segment `seg` of picture p, one thread (inlined into its kernels, so that `tabs` stays an LDS address)
+__device__ __forceinline__ void entropy_serial_lane(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc& d, int p, int seg,
+                                           const sat_jpeg_htable* tabs, int16_t* __restrict__ coefs, int* __restrict__ status) {
     const uint32_t* segtab = reinterpret_cast<const uint32_t*>(comp + d.segments_offset);
     const long s0 = segtab[2 * seg], s1 = segtab[2 * seg + 1];
     if (s0 > s1 || s1 > d.data_bytes) { atomicOr(status + p, JPEG_BAD_SEGMENT); return; }
@@ -214,6 +207,438 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     }
     if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
     if (br.flags) atomicOr(status + p, br.flags);
+}
+
+// Per-picture control words of the parallel path (PAR_CTRL int32 each, in the workspace; written by jpeg_par_setup_kernel)
+constexpr int PAR_CTRL = 8;
+constexpr int PC_PATH = 0, PC_BASE = 1, PC_NSUB = 2, PC_ITERS = 3, PC_FAIL = 4, PC_WFAIL = 5;      // FAIL: before the write pass; WFAIL: in it
+
+// One lane per picture and restart segment.  `ctrl` (may be null): the pictures the parallel path below has taken are skipped.
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                          int n, const sat_jpeg_htable* __restrict__ huff, int16_t* __restrict__ coefs,
+                                                          int* __restrict__ status, const int* __restrict__ ctrl) {
+    __shared__ sat_jpeg_htable tabs[6];
+    const int seg_global = blockIdx.x;
+    int lo = 0, hi = n - 1;                                   // picture: last one whose segment_base <= seg_global
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[mid].segment_base <= seg_global) lo = mid; else hi = mid - 1;
+    }
+    const int p = lo;
+    const sat_jpeg_desc& d = desc[p];                        // a reference: a local copy's arrays would live in scratch memory
+    const int seg = seg_global - d.segment_base;
+    if (seg < 0 || seg >= d.n_segments) return;
+    if (ctrl && ctrl[p * PAR_CTRL + PC_PATH]) return;
+    load_tables(tabs, d, huff);
+    if (threadIdx.x != 0) return;
+    entropy_serial_lane(comp, comp_bytes, d, p, seg, tabs, coefs, status);
+}
+
+// -------------------------------------------------------------------------------------------------- 1b. entropy, many lanes
+// A restart-free picture (one segment) of at least parallel_min_bytes is cut into subsequences of subseq_bytes raw bytes,
+// measured from data_offset, stuffed bytes counted.  A decoder state is (bit position in the raw bytes, slot within the MCU,
+// zigzag index k; k == 0: a DC symbol comes next).  jpeg_par_spec_kernel: lane i decodes subsequence i from (its first bit,
+// slot 0, k 0) until a symbol would start at or past the subsequence's end; lane 0's state is the true one.
+// jpeg_par_sync_kernel (one workgroup per picture): lane i + 1 decodes again from lane i's exit state until no exit state
+// changes, then the exclusive prefix sum of the completed blocks gives every lane its first block.  jpeg_par_write_kernel:
+// every lane decodes once more from its verified entry state and stores the non-zero AC coefficients and the DC differences
+// with jpeg_entropy_kernel's block addressing.  jpeg_par_dc_kernel: the prefix sum of the DC differences per component in
+// decode order.  A picture on which any of this comes up short (a marker in the data, an unverified chain, a block count that
+// is not the picture's, a flag in the write pass) is cleared and decoded by the serial lane in jpeg_par_finish_kernel, so its
+// status word and pixels are the serial path's.
+// A bit position is canonical: the byte after a 0xFF is never pointed at (the reader skips it when it loads the 0xFF, and a
+// lane that starts on it steps over it), so equal decoder states compare equal.
+constexpr int PAR_THREADS = 256;            // spec / write / dc kernels
+constexpr int PAR_SYNC_THREADS = 1024;      // one workgroup per picture
+constexpr long PAR_MAX_BYTES = 1L << 27;    // bit positions stay below 2^30
+constexpr uint64_t ST_ERR = 1ull << 63;
+
+__host__ __device__ inline uint64_t st_pack(uint32_t bitpos, int slot, int k) { return (uint64_t)bitpos | ((uint64_t)slot << 32) | ((uint64_t)k << 40); }
+__host__ __device__ inline uint32_t st_pos(uint64_t s) { return (uint32_t)s; }
+__host__ __device__ inline int st_slot(uint64_t s) { return (int)((s >> 32) & 0xFF); }
+__host__ __device__ inline int st_k(uint64_t s) { return (int)((s >> 40) & 0xFF); }
+
+__host__ __device__ inline bool par_takes(const sat_jpeg_desc& d, long min_bytes) {
+    return d.n_segments == 1 && d.data_bytes > 0 && d.data_bytes >= min_bytes && d.data_bytes <= PAR_MAX_BYTES;
+}
+
+// Bit reader of a lane over the whole data [0, end) of the picture.  `pos` is the next raw byte; past the end it goes on counting
+// while zero bytes are shifted in.  `stuff` remembers, for the last bytes loaded (bit 0: the latest), whether a stuffed byte
+// followed, so that the raw position of the next unread bit can be told from pos and cnt.
+struct LaneReader {
+    const uint8_t* base;
+    long abs0, limit;
+    int pos, end;
+    uint64_t buf;
+    int cnt;
+    uint32_t stuff;
+    int flags;
+    long word_idx;
+    uint32_t word;
+
+    __device__ inline int byte_at(int rel) {
+        const long a = abs0 + rel;
+        const long w = a >> 2;
+        if (w != word_idx) {
+            if ((w << 2) + 4 <= limit) word = *reinterpret_cast<const uint32_t*>(base + (w << 2));
+            else {
+                word = 0;
+                for (int k = 0; k < 4 && (w << 2) + k < limit; ++k) word |= (uint32_t)base[(w << 2) + k] << (8 * k);
+            }
+            word_idx = w;
+        }
+        return (word >> (8 * (a & 3))) & 0xFF;
+    }
+
+    __device__ inline void refill() {
+        while (cnt <= 56) {
+            int v = 0, st = 0;
+            if (pos < end) {
+                v = byte_at(pos);
+                if (v == 0xFF) {
+                    const int nx = pos + 1 < end ? byte_at(pos + 1) : 0;
+                    if (nx == 0) { ++pos; st = 1; }
+                    else { flags |= JPEG_MARKER; end = pos; v = 0; }        // the data ends here; the picture goes to the serial lane
+                }
+            }
+            ++pos;
+            buf |= (uint64_t)v << (56 - cnt);
+            cnt += 8;
+            stuff = (stuff << 1) | st;
+        }
+    }
+
+    __device__ inline void start(uint32_t bitpos) {
+        pos = (int)(bitpos >> 3);
+        const int bit = (int)(bitpos & 7);
+        buf = 0; cnt = 0; stuff = 0; flags = 0; word_idx = -1; word = 0;
+        if (bit == 0 && pos > 0 && pos < end && byte_at(pos) == 0 && byte_at(pos - 1) == 0xFF) ++pos;      // on a stuffed byte
+        refill();
+        skip(bit);
+    }
+
+    // raw bit position of the next unread bit
+    __device__ inline uint32_t bitpos() const {
+        const int nb = (cnt + 7) >> 3;
+        const int first = pos - nb - __popc(stuff & ((1u << nb) - 1u));
+        return ((uint32_t)first << 3) + (uint32_t)((8 - (cnt & 7)) & 7);
+    }
+    __device__ inline uint32_t peek(int n) { return (uint32_t)(buf >> (64 - n)); }
+    __device__ inline void skip(int n) { buf <<= n; cnt -= n; }
+};
+
+// block addressing of jpeg_entropy_kernel, for the write and DC passes
+struct BlockMap {
+    int hs, vs, bw0, mx, ny, slots;
+    long base0, base1, base2, total;
+
+    __device__ inline void init(const sat_jpeg_desc& d) {
+        const CompGeom g0 = comp_geom(d, 0);
+        hs = g0.hs; vs = g0.vs; bw0 = g0.bw;
+        mx = d.components == 1 ? bw0 : bw0 / hs;
+        base0 = d.block_offset; base1 = base0 + (long)g0.bw * g0.bh; base2 = base1 + (d.components == 3 ? (long)mx * (g0.bh / vs) : 0);
+        ny = hs * vs; slots = ny + (d.components == 3 ? 2 : 0);
+        total = picture_mcus(d) * slots;
+    }
+    __device__ inline long block(long m, int slot) const {
+        const int mcu_x = (int)(m % mx), mcu_y = (int)(m / mx);
+        if (slot < ny) return base0 + (long)(mcu_y * vs + slot / hs) * bw0 + mcu_x * hs + slot % hs;
+        return (slot == ny ? base1 : base2) + (long)mcu_y * mx + mcu_x;
+    }
+};
+
+// One lane: decode from `entry` until a symbol would start at or past byte `end_byte` (or, when writing, until the picture's
+// blocks are done).  One symbol per iteration, DC or AC by k, so the lanes of a wave reconverge every symbol; a symbol takes at
+// least one bit, so the loop makes at most 8 * (end_byte - first byte) iterations whatever the bytes are.
+// Returns the exit state (ST_ERR set on a bad code, an index past 63 or a block that ran out of data) and the blocks completed.
+template <bool WRITE>
+__device__ __forceinline__ uint64_t lane_decode(LaneReader& br, const sat_jpeg_htable* tabs, int ny, int slots, uint64_t entry, int end_byte, int* nblk_out,
+                                       const BlockMap* bm, long blk_abs, int16_t* __restrict__ coefs) {
+    *nblk_out = 0;
+    if ((int)(st_pos(entry) >> 3) >= end_byte) return entry;            // handed a position past this subsequence: pass it on
+    int slot = st_slot(entry), k = st_k(entry), nblk = 0;
+    br.start(st_pos(entry));
+    const uint32_t data_bits = (uint32_t)br.end << 3;
+    int16_t* blk = nullptr;
+    if (WRITE && blk_abs < bm->total) blk = coefs + bm->block(blk_abs / slots, (int)(blk_abs % slots)) * 64;
+    bool err = false;
+    for (;;) {
+        if ((int)(br.bitpos() >> 3) >= end_byte) break;
+        if (WRITE && blk_abs >= bm->total) break;
+        br.refill();                                                      // >= 57 bits: a code (16) and its value bits (15)
+        const int c = slot < ny ? 0 : slot - ny + 1;
+        const sat_jpeg_htable& t = tabs[2 * c + (k ? 1 : 0)];
+        int sym = -1;
+        const int e = t.lookup[br.peek(JPEG_LOOKAHEAD)];
+        if (e >> 8) { br.skip(e >> 8); sym = e & 0xFF; }
+        else if (!e) {
+            const uint32_t w = br.peek(16);
+            for (int l = JPEG_LOOKAHEAD + 1; l <= 16; ++l) {
+                const int code = (int)(w >> (16 - l));
+                if (code <= t.maxcode[l]) {
+                    const int idx = code + t.valoffset[l];
+                    if (idx >= 0 && idx <= 255) { br.skip(l); sym = t.huffval[idx]; }
+                    break;
+                }
+            }
+        }
+        if (sym < 0) { br.flags |= JPEG_BAD_CODE; err = true; break; }
+        int s = sym & 15, v = 0;
+        if (k == 0) {
+            if (sym > 15) { br.flags |= JPEG_BAD_CODE; err = true; break; }
+        } else {
+            const int r = sym >> 4;
+            if (s) {
+                k += r;
+                if (k > 63) { br.flags |= JPEG_BAD_INDEX; err = true; break; }
+            } else {
+                k = (r == 15 && k + 15 < 63) ? k + 15 : 63;               // ZRL: 16 zeros; EOB (or a ZRL past the end): the block is done
+            }
+        }
+        if (s) {
+            const int r = (int)br.peek(s);
+            br.skip(s);
+            v = r < (1 << (s - 1)) ? r + (int)((~0u << s) + 1u) : r;      // HUFF_EXTEND
+            if (WRITE) blk[k_natural_order[k]] = (int16_t)v;              // k == 0: the DC difference
+        }
+        if (++k > 63) {
+            if (br.bitpos() > data_bits) { br.flags |= JPEG_OUT_OF_DATA; err = true; break; }
+            ++nblk; k = 0;
+            if (++slot == slots) slot = 0;
+            if (WRITE) {
+                ++blk_abs;
+                if (blk_abs < bm->total) blk = coefs + bm->block(blk_abs / slots, (int)(blk_abs % slots)) * 64;
+            }
+        }
+    }
+    *nblk_out = nblk;
+    return st_pack(br.bitpos(), slot, k) | (err ? ST_ERR : 0);
+}
+
+// ctrl[p]: does picture p take the parallel path, its first subsequence in the state arrays and its subsequences.  One block.
+__global__ __launch_bounds__(PAR_THREADS) void jpeg_par_setup_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                                      int n, int subseq, long min_bytes, long cap, int* __restrict__ ctrl) {
+    __shared__ long part[PAR_THREADS];
+    const int per = (n + PAR_THREADS - 1) / PAR_THREADS;
+    const int p0 = min(n, (int)threadIdx.x * per), p1 = min(n, p0 + per);
+    auto subs = [&](int p) -> long {
+        const sat_jpeg_desc& d = desc[p];
+        if (!par_takes(d, min_bytes)) return 0;
+        if (d.data_offset < 0 || d.data_offset + d.data_bytes > comp_bytes || d.segments_offset < 0 || d.segments_offset + 8 > comp_bytes) return 0;
+        const uint32_t* segtab = reinterpret_cast<const uint32_t*>(comp + d.segments_offset);
+        if (segtab[0] != 0 || (long)segtab[1] != d.data_bytes) return 0;          // the serial lane's segment is not the whole data
+        return (d.data_bytes + subseq - 1) / subseq;
+    };
+    long sum = 0;
+    for (int p = p0; p < p1; ++p) sum += subs(p);
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long run = 0;
+        for (int t = 0; t < PAR_THREADS; ++t) { const long v = part[t]; part[t] = run; run += v; }
+    }
+    __syncthreads();
+    long base = part[threadIdx.x];
+    for (int p = p0; p < p1; ++p) {
+        long ns = subs(p);
+        if (base + ns > cap) ns = 0;                                             // never past the state arrays
+        int* c = ctrl + (long)p * PAR_CTRL;
+        c[PC_PATH] = ns > 0; c[PC_BASE] = (int)base; c[PC_NSUB] = (int)ns; c[PC_ITERS] = 0; c[PC_FAIL] = 0; c[5] = c[6] = c[7] = 0;
+        base += ns;
+    }
+}
+
+__device__ inline void lane_reader_init(LaneReader& br, const uint8_t* comp, long comp_bytes, const sat_jpeg_desc& d) {
+    br.base = comp; br.abs0 = d.data_offset; br.limit = comp_bytes; br.end = (int)d.data_bytes;
+}
+
+// is there a marker (0xFF followed by anything but 0x00) that starts in bytes [b0, b1) of the data?
+__device__ inline bool has_marker(LaneReader& br, int b0, int b1, int data_bytes) {
+    br.word_idx = -1; br.word = 0;
+    bool found = false;
+    for (int b = b0; b < b1;) {
+        const long a = br.abs0 + b;
+        br.byte_at(b);                                                            // loads the word that holds byte b
+        const uint32_t x = ~br.word;
+        const int in_word = 4 - (int)(a & 3);
+        if (((x - 0x01010101u) & ~x & 0x80808080u) == 0) { b += in_word; continue; }       // no 0xFF in this word
+        const int stop = min(b1, b + in_word);
+        for (; b < stop; ++b)
+            if (br.byte_at(b) == 0xFF && b + 1 < data_bytes && br.byte_at(b + 1) != 0) found = true;
+    }
+    return found;
+}
+
+__global__ __launch_bounds__(PAR_THREADS) void jpeg_par_spec_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                                     const sat_jpeg_htable* __restrict__ huff, int subseq, int* __restrict__ ctrl,
+                                                                     uint64_t* __restrict__ st_exit, uint64_t* __restrict__ st_entry, int* __restrict__ nblk) {
+    __shared__ sat_jpeg_htable tabs[6];
+    const int p = blockIdx.y;
+    int* c = ctrl + (long)p * PAR_CTRL;
+    const int nsub = c[PC_NSUB], base = c[PC_BASE];
+    if (!c[PC_PATH] || (long)blockIdx.x * PAR_THREADS >= nsub) return;
+    const sat_jpeg_desc& d = desc[p];
+    load_tables(tabs, d, huff);
+    const int ny = d.components == 1 ? 1 : d.h_samp * d.v_samp, slots = ny + (d.components == 3 ? 2 : 0);
+    LaneReader br;
+    lane_reader_init(br, comp, comp_bytes, d);
+    const int data_bytes = br.end;
+    for (long i = (long)blockIdx.x * PAR_THREADS + threadIdx.x; i < nsub; i += (long)gridDim.x * PAR_THREADS) {
+        const int b0 = (int)(i * subseq), b1 = min(data_bytes, b0 + subseq);
+        if (has_marker(br, b0, b1, data_bytes)) atomicOr(c + PC_FAIL, 1);
+        const uint64_t entry = st_pack((uint32_t)b0 << 3, 0, 0);
+        int nb;
+        br.end = data_bytes;
+        const uint64_t ex = lane_decode<false>(br, tabs, ny, slots, entry, b1, &nb, nullptr, 0, nullptr);
+        st_entry[base + i] = entry; st_exit[base + i] = ex; nblk[base + i] = nb;
+    }
+}
+
+__global__ __launch_bounds__(PAR_SYNC_THREADS) void jpeg_par_sync_kernel(const uint8_t* __restrict__ comp, long comp_bytes,
+                                                                          const sat_jpeg_desc* __restrict__ desc, const sat_jpeg_htable* __restrict__ huff,
+                                                                          int subseq, int* __restrict__ ctrl, uint64_t* st_exit, uint64_t* st_entry, int* nblk,
+                                                                          int* __restrict__ blk_base) {
+    __shared__ sat_jpeg_htable tabs[6];
+    __shared__ int part[PAR_SYNC_THREADS];
+    const int p = blockIdx.x;
+    int* c = ctrl + (long)p * PAR_CTRL;
+    const int nsub = c[PC_NSUB], base = c[PC_BASE];
+    if (!c[PC_PATH] || c[PC_FAIL]) return;                                      // the whole block: no barrier is left waiting
+    const sat_jpeg_desc& d = desc[p];
+    load_tables(tabs, d, huff);
+    const int ny = d.components == 1 ? 1 : d.h_samp * d.v_samp, slots = ny + (d.components == 3 ? 2 : 0);
+    LaneReader br;
+    lane_reader_init(br, comp, comp_bytes, d);
+    const int data_bytes = br.end;
+    uint64_t* ex = st_exit + base;
+    uint64_t* en = st_entry + base;
+    // Every round, lane i decodes again if lane i - 1's exit state is not the entry state it last used.  The exit words are read
+    // while other lanes of the round may store them (8-byte atomic accesses); a round in which no lane stored anything has read
+    // stable words, so at its end ex[i - 1] == en[i] and ex[i] = decode(en[i]) for every lane behind a good predecessor.  After
+    // round r lanes 0 ... r hold their true states, hence at most nsub rounds.
+    int iters = 0;
+    bool converged = false;
+    while (iters < nsub) {
+        ++iters;
+        int changed = 0;
+        for (int i = 1 + threadIdx.x; i < nsub; i += PAR_SYNC_THREADS) {
+            const uint64_t e = __atomic_load_n(ex + i - 1, __ATOMIC_RELAXED);
+            if ((e & ST_ERR) || e == en[i]) continue;
+            int nb;
+            br.end = data_bytes;
+            const uint64_t out = lane_decode<false>(br, tabs, ny, slots, e, min(data_bytes, (i + 1) * subseq), &nb, nullptr, 0, nullptr);
+            en[i] = e; nblk[base + i] = nb;
+            __atomic_store_n(ex + i, out, __ATOMIC_RELAXED);
+            changed = 1;
+        }
+        if (!__syncthreads_or(changed)) { converged = true; break; }
+    }
+    // exclusive prefix sum of the completed blocks: a contiguous run of subsequences per thread
+    const int per = (nsub + PAR_SYNC_THREADS - 1) / PAR_SYNC_THREADS;
+    const int i0 = min(nsub, (int)threadIdx.x * per), i1 = min(nsub, i0 + per);
+    int sum = 0;
+    for (int i = i0; i < i1; ++i) sum += nblk[base + i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < PAR_SYNC_THREADS; off <<= 1) {
+        const int v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - sum;
+    for (int i = i0; i < i1; ++i) { blk_base[base + i] = run; run += nblk[base + i]; }
+    if (threadIdx.x == PAR_SYNC_THREADS - 1) {
+        const long total = picture_mcus(d) * slots;
+        c[PC_ITERS] = iters;
+        if (!converged || (long)part[threadIdx.x] != total) atomicOr(c + PC_FAIL, 2);
+    }
+}
+
+__global__ __launch_bounds__(PAR_THREADS) void jpeg_par_write_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                                      const sat_jpeg_htable* __restrict__ huff, int subseq, int* __restrict__ ctrl,
+                                                                      const uint64_t* __restrict__ st_exit, const uint64_t* __restrict__ st_entry,
+                                                                      const int* __restrict__ blk_base, int16_t* __restrict__ coefs) {
+    __shared__ sat_jpeg_htable tabs[6];
+    const int p = blockIdx.y;
+    int* c = ctrl + (long)p * PAR_CTRL;
+    const int nsub = c[PC_NSUB], base = c[PC_BASE];
+    if (!c[PC_PATH] || c[PC_FAIL] || (long)blockIdx.x * PAR_THREADS >= nsub) return;
+    const sat_jpeg_desc& d = desc[p];
+    load_tables(tabs, d, huff);
+    BlockMap bm;
+    bm.init(d);
+    LaneReader br;
+    lane_reader_init(br, comp, comp_bytes, d);
+    const int data_bytes = br.end;
+    for (long i = (long)blockIdx.x * PAR_THREADS + threadIdx.x; i < nsub; i += (long)gridDim.x * PAR_THREADS) {
+        const uint64_t entry = st_entry[base + i];
+        const long first = blk_base[base + i];
+        // the chain is verified only where a lane's entry is its predecessor's exit (an error exit never is) and the slot fits the block
+        bool bad = (i > 0 && st_exit[base + i - 1] != entry) || (first < bm.total && (int)(first % bm.slots) != st_slot(entry));
+        if (!bad) {
+            int nb;
+            br.end = data_bytes; br.flags = 0;
+            lane_decode<true>(br, tabs, bm.ny, bm.slots, entry, (int)min((long)data_bytes, (i + 1) * subseq), &nb, &bm, first, coefs);
+            bad = br.flags != 0;
+        }
+        if (bad) atomicOr(c + PC_WFAIL, 1);
+    }
+}
+
+// blk[0] of every block holds its DC difference: replace it by the running sum per component, in decode order
+__global__ __launch_bounds__(PAR_THREADS) void jpeg_par_dc_kernel(const sat_jpeg_desc* __restrict__ desc, const int* __restrict__ ctrl, int16_t* __restrict__ coefs) {
+    __shared__ int part[PAR_THREADS];
+    const int p = blockIdx.y, comp_i = blockIdx.x;
+    const int* c = ctrl + (long)p * PAR_CTRL;
+    const sat_jpeg_desc& d = desc[p];
+    if (!c[PC_PATH] || c[PC_FAIL] || c[PC_WFAIL] || comp_i >= d.components) return;
+    BlockMap bm;
+    bm.init(d);
+    const long mcus = bm.total / bm.slots;
+    const int per_mcu = comp_i == 0 ? bm.ny : 1, slot0 = comp_i == 0 ? 0 : bm.ny + comp_i - 1;
+    const long nb = mcus * per_mcu;
+    const long per = (nb + PAR_THREADS - 1) / PAR_THREADS;
+    const long j0 = min(nb, (long)threadIdx.x * per), j1 = min(nb, j0 + per);
+    unsigned sum = 0;                                                             // int arithmetic modulo 2^32, as the serial lane's
+    for (long j = j0; j < j1; ++j) sum += (unsigned)(int)coefs[bm.block(j / per_mcu, slot0 + (int)(j % per_mcu)) * 64];
+    part[threadIdx.x] = (int)sum;
+    __syncthreads();
+    for (int off = 1; off < PAR_THREADS; off <<= 1) {
+        const int v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] = (int)((unsigned)part[threadIdx.x] + (unsigned)v);
+        __syncthreads();
+    }
+    unsigned run = (unsigned)part[threadIdx.x] - sum;
+    for (long j = j0; j < j1; ++j) {
+        int16_t* blk = coefs + bm.block(j / per_mcu, slot0 + (int)(j % per_mcu)) * 64;
+        const int diff = blk[0];
+        run += (unsigned)diff;
+        if ((int)run != diff) blk[0] = (int16_t)(int)run;
+    }
+}
+
+// One block per picture.  A picture the parallel path gave up on: clear its blocks and decode it on the serial lane.  Every
+// picture: its info words (path 0 serial, 1 parallel, 2 parallel abandoned for the serial lane; subsequences; iterations; 0).
+__global__ __launch_bounds__(64) void jpeg_par_finish_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                              const sat_jpeg_htable* __restrict__ huff, const int* __restrict__ ctrl,
+                                                              int16_t* __restrict__ coefs, int* __restrict__ status, int* __restrict__ info) {
+    __shared__ sat_jpeg_htable tabs[6];
+    const int p = blockIdx.x;
+    const int* c = ctrl + (long)p * PAR_CTRL;
+    const bool redo = c[PC_PATH] && (c[PC_FAIL] || c[PC_WFAIL]);
+    if (info && threadIdx.x == 0) {
+        info[4 * p] = c[PC_PATH] ? (redo ? 2 : 1) : 0; info[4 * p + 1] = c[PC_NSUB]; info[4 * p + 2] = c[PC_ITERS]; info[4 * p + 3] = 0;
+    }
+    if (!redo) return;
+    const sat_jpeg_desc& d = desc[p];
+    uint4* blocks = reinterpret_cast<uint4*>(coefs + d.block_offset * 64);
+    const long n16 = picture_blocks(d) * 8;
+    for (long k = threadIdx.x; k < n16; k += 64) blocks[k] = make_uint4(0, 0, 0, 0);
+    load_tables(tabs, d, huff);                                                   // ends in a barrier: the blocks are clear
+    if (threadIdx.x != 0) return;
+    entropy_serial_lane(comp, comp_bytes, d, p, 0, tabs, coefs, status);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- 2. IDCT
@@ -392,6 +817,38 @@ int validate(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg
     return SAT_OK;
 }
 
+// the options of a call: the defaults filled in, checked
+struct ParOpts { int subseq; long min_bytes; int32_t* info; };
+
+int par_opts(const sat_jpeg_decode_opts* o, const char* who, ParOpts* out) {
+    out->subseq = SAT_JPEG_SUBSEQ_BYTES_DEFAULT; out->min_bytes = SAT_JPEG_PARALLEL_MIN_BYTES_DEFAULT; out->info = nullptr;
+    if (!o) return SAT_OK;
+    SAT_REQUIRE(o->subseq_bytes == 0 || (o->subseq_bytes >= 16 && o->subseq_bytes % 4 == 0 && o->subseq_bytes <= (1 << 20)),
+                "%s: subseq_bytes = %d (0 for the default, else a multiple of 4 from 16 to 2^20)", who, o->subseq_bytes);
+    SAT_REQUIRE(o->parallel_min_bytes >= -1, "%s: parallel_min_bytes = %lld (-1 for the default, else >= 0)", who, (long long)o->parallel_min_bytes);
+    if (o->subseq_bytes) out->subseq = o->subseq_bytes;
+    if (o->parallel_min_bytes >= 0) out->min_bytes = o->parallel_min_bytes;
+    out->info = o->info;
+    return SAT_OK;
+}
+
+// subsequences of the pictures the parallel path may take (all of them, and the most of one picture)
+void par_count(const sat_jpeg_desc* dh, int n, const ParOpts& o, long* subs, long* max_subs) {
+    *subs = *max_subs = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!par_takes(dh[i], o.min_bytes)) continue;
+        const long ns = (dh[i].data_bytes + o.subseq - 1) / o.subseq;
+        *subs += ns;
+        if (ns > *max_subs) *max_subs = ns;
+    }
+}
+
+// workspace: coefficients | sample planes | control words | exit states | entry states | blocks completed | first block
+size_t par_state_offset(long blocks) { return ((size_t)blocks * (64 * sizeof(int16_t) + 64) + 15) / 16 * 16; }
+size_t workspace_need(long blocks, int n, long subs) {
+    return par_state_offset(blocks) + (size_t)n * PAR_CTRL * sizeof(int) + (size_t)subs * (2 * sizeof(uint64_t) + 2 * sizeof(int));
+}
+
 }  // namespace
 }  // namespace sat
 
@@ -399,8 +856,10 @@ using namespace sat;
 
 extern "C" {
 
-size_t sat_jpeg_decode_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n) {
+size_t sat_jpeg_decode_workspace_bytes_ex(const sat_jpeg_desc* desc_host, int32_t n, const sat_jpeg_decode_opts* opts) {
     if (!desc_host || n <= 0) { fail(SAT_EINVAL, "sat_jpeg_decode_workspace_bytes: null descriptors or n = %d", n); return 0; }
+    ParOpts o;
+    if (par_opts(opts, "sat_jpeg_decode_workspace_bytes", &o) != SAT_OK) return 0;
     long blocks = 0;
     for (int i = 0; i < n; ++i) {
         const sat_jpeg_desc& d = desc_host[i];
@@ -411,34 +870,82 @@ size_t sat_jpeg_decode_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n
         }
         blocks += picture_blocks(d);
     }
-    return (size_t)blocks * (64 * sizeof(int16_t) + 64);      // coefficients, then the sample planes
+    long subs = 0, max_subs = 0;
+    par_count(desc_host, n, o, &subs, &max_subs);
+    return workspace_need(blocks, n, subs);
 }
 
-int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
-                          int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
-                          uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+size_t sat_jpeg_decode_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n) { return sat_jpeg_decode_workspace_bytes_ex(desc_host, n, nullptr); }
+
+int sat_jpeg_decode_batch_ex(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
+                             int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
+                             uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream,
+                             const sat_jpeg_decode_opts* opts) {
+    ParOpts o;
+    SAT_TRY(par_opts(opts, "sat_jpeg_decode_batch", &o));
     long blocks = 0, segs = 0, max_px = 0, max_blocks = 0;
     SAT_TRY(validate(compressed, compressed_bytes, desc_host, desc_dev, n, quant_dev, n_quant, huff_dev, n_huff, pixels, pixels_bytes, status,
                      &blocks, &segs, &max_px, &max_blocks));
-    const size_t need = (size_t)blocks * (64 * sizeof(int16_t) + 64);
+    long subs = 0, max_subs = 0;
+    par_count(desc_host, n, o, &subs, &max_subs);
+    SAT_REQUIRE(subs < (1L << 31), "sat_jpeg_decode_batch: %ld subsequences (raise subseq_bytes)", subs);
+    const size_t need = workspace_need(blocks, n, subs);
     SAT_REQUIRE(workspace && workspace_bytes >= need, "sat_jpeg_decode_batch: workspace %zu bytes, need %zu", workspace_bytes, need);
     SAT_REQUIRE(((uintptr_t)compressed & 3) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)desc_dev & 7) == 0 && ((uintptr_t)status & 3) == 0 &&
-                    ((uintptr_t)huff_dev & 3) == 0 && ((uintptr_t)quant_dev & 1) == 0,
-                "sat_jpeg_decode_batch: compressed (4), workspace (16), records (8), status and tables must be aligned");
+                    ((uintptr_t)huff_dev & 3) == 0 && ((uintptr_t)quant_dev & 1) == 0 && ((uintptr_t)o.info & 3) == 0,
+                "sat_jpeg_decode_batch: compressed (4), workspace (16), records (8), status, info and tables must be aligned");
     hipStream_t st = (hipStream_t)stream;
     int16_t* coefs = reinterpret_cast<int16_t*>(workspace);
     uint8_t* planes = reinterpret_cast<uint8_t*>(workspace) + (size_t)blocks * 64 * sizeof(int16_t);
+    int* ctrl = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(workspace) + par_state_offset(blocks));
+    uint64_t* st_exit = reinterpret_cast<uint64_t*>(ctrl + (size_t)n * PAR_CTRL);          // n * 32 bytes behind a 16-byte boundary: 8-byte aligned
+    uint64_t* st_entry = st_exit + subs;
+    int* nblk = reinterpret_cast<int*>(st_entry + subs);
+    int* blk_base = nblk + subs;
+    int* stat = reinterpret_cast<int*>(status);
+    const long cbytes = (long)compressed_bytes;
     SAT_TRY(dev_fill_bytes(st, status, 0, sizeof(int32_t) * (size_t)n));
     SAT_TRY(dev_fill_bytes(st, coefs, 0, (size_t)blocks * 64 * sizeof(int16_t)));
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)segs), dim3(64), 0, st, compressed, (long)compressed_bytes, desc_dev, n, huff_dev, coefs,
-                       reinterpret_cast<int*>(status));
-    SAT_TRY(launch_ok("jpeg_entropy_kernel"));
+    if (subs == 0) {                                            // today's path: every picture on the serial lanes
+        if (o.info) SAT_TRY(dev_fill_bytes(st, o.info, 0, 4 * sizeof(int32_t) * (size_t)n));
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)segs), dim3(64), 0, st, compressed, cbytes, desc_dev, n, huff_dev, coefs, stat,
+                           (const int*)nullptr);
+        SAT_TRY(launch_ok("jpeg_entropy_kernel"));
+    } else {
+        const dim3 lanes((unsigned)min(cdiv(max_subs, PAR_THREADS), 4096), (unsigned)n);
+        hipLaunchKernelGGL(jpeg_par_setup_kernel, dim3(1), dim3(PAR_THREADS), 0, st, compressed, cbytes, desc_dev, n, o.subseq, o.min_bytes, subs, ctrl);
+        SAT_TRY(launch_ok("jpeg_par_setup_kernel"));
+        hipLaunchKernelGGL(jpeg_par_spec_kernel, lanes, dim3(PAR_THREADS), 0, st, compressed, cbytes, desc_dev, huff_dev, o.subseq, ctrl, st_exit, st_entry,
+                           nblk);
+        SAT_TRY(launch_ok("jpeg_par_spec_kernel"));
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)segs), dim3(64), 0, st, compressed, cbytes, desc_dev, n, huff_dev, coefs, stat,
+                           (const int*)ctrl);
+        SAT_TRY(launch_ok("jpeg_entropy_kernel"));
+        hipLaunchKernelGGL(jpeg_par_sync_kernel, dim3((unsigned)n), dim3(PAR_SYNC_THREADS), 0, st, compressed, cbytes, desc_dev, huff_dev, o.subseq, ctrl,
+                           st_exit, st_entry, nblk, blk_base);
+        SAT_TRY(launch_ok("jpeg_par_sync_kernel"));
+        hipLaunchKernelGGL(jpeg_par_write_kernel, lanes, dim3(PAR_THREADS), 0, st, compressed, cbytes, desc_dev, huff_dev, o.subseq, ctrl,
+                           (const uint64_t*)st_exit, (const uint64_t*)st_entry, (const int*)blk_base, coefs);
+        SAT_TRY(launch_ok("jpeg_par_write_kernel"));
+        hipLaunchKernelGGL(jpeg_par_dc_kernel, dim3(3, (unsigned)n), dim3(PAR_THREADS), 0, st, desc_dev, (const int*)ctrl, coefs);
+        SAT_TRY(launch_ok("jpeg_par_dc_kernel"));
+        hipLaunchKernelGGL(jpeg_par_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, compressed, cbytes, desc_dev, huff_dev, (const int*)ctrl, coefs, stat,
+                           reinterpret_cast<int*>(o.info));
+        SAT_TRY(launch_ok("jpeg_par_finish_kernel"));
+    }
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)min(cdiv(max_blocks, 256), 1024), (unsigned)n), dim3(256), 0, st, desc_dev, quant_dev, coefs,
                        planes);
     SAT_TRY(launch_ok("jpeg_idct_kernel"));
     hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)min(cdiv(max_px, 256), 1024), (unsigned)n), dim3(256), 0, st, desc_dev, planes, pixels);
     SAT_TRY(launch_ok("jpeg_color_kernel"));
     return SAT_OK;
+}
+
+int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host, const sat_jpeg_desc* desc_dev,
+                          int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
+                          uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return sat_jpeg_decode_batch_ex(compressed, compressed_bytes, desc_host, desc_dev, n, quant_dev, n_quant, huff_dev, n_huff, pixels, pixels_bytes,
+                                    status, workspace, workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"

@@ -363,10 +363,12 @@ class BatchTransform:
     T.RandomChoice([RandomPerspective(0.5 s, p=1), RandomAffine(45 s, shear=45 s), RandomRotation(45 s)]) when
     aug_optical_strength = s is not 0 and at most 1 (the same rules; a negative s raises, as RandomAffine does); ToTensor;
     + N(0,1) * aug_noise_std.
-    ``randn(shape, device)`` supplies the noise draws (default: ``torch.randn`` on the device)."""
+    ``randn(shape, device)`` supplies the noise draws (default: ``torch.randn`` on the device).
+    ``jpeg_subseq_bytes`` / ``jpeg_parallel_min_bytes``: the options of the GPU JPEG decoder for pictures that arrive as JPEG
+    bytes (``jpeg.decode_jpeg_batch``; None: the library's defaults)."""
 
     def __init__(self, input_size, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, randn=None, aug_color_jitter=0.0,
-                 aug_optical_strength=0.0):
+                 aug_optical_strength=0.0, jpeg_subseq_bytes=None, jpeg_parallel_min_bytes=None):
         if train and not (0 <= aug_scale <= 1.0):
             raise ValueError("Invalid value for aug_scale. Choose in the range {0,1}.")       # train.py:219-220
         x = float(aug_color_jitter)
@@ -380,6 +382,7 @@ class BatchTransform:
         self.size, self.train = int(input_size), train
         self.aug_scale, self.aug_hflip, self.noise_std, self.randn = aug_scale, aug_hflip, aug_noise_std, randn
         self.aug_color_jitter, self.aug_optical_strength = x, o
+        self.jpeg_subseq_bytes, self.jpeg_parallel_min_bytes = jpeg_subseq_bytes, jpeg_parallel_min_bytes     # None: the library's defaults
         self._ws = self._jws = None
 
     def draw(self, shapes):
@@ -422,11 +425,12 @@ class BatchTransform:
                 dev = torch.empty(staged.device_bytes, dtype=torch.uint8, device=device)
                 dev[:staged.host.numel()].copy_(staged.host, non_blocking=True)
                 jb = staged.jpeg
-                need = jb.workspace_bytes()
+                need = jb.workspace_bytes(self.jpeg_subseq_bytes, self.jpeg_parallel_min_bytes)
                 if self._jws is None or self._jws.numel() < need or self._jws.device != dev.device:
                     self._jws = torch.empty(need, dtype=torch.uint8, device=device)
                 staged.status = torch.empty(jb.n, dtype=torch.int32, device=device)
-                jb.launch(dev.data_ptr() + staged.jpeg_off, dev.data_ptr() + staged.head, staged.pixels_bytes, staged.status, self._jws, stream)
+                jb.launch(dev.data_ptr() + staged.jpeg_off, dev.data_ptr() + staged.head, staged.pixels_bytes, staged.status, self._jws, stream,
+                          self.jpeg_subseq_bytes, self.jpeg_parallel_min_bytes)
             jit, warp = staged.jitter, staged.warp
             if warp is not None:
                 need = lib.sat_image_batch_warp_workspace_bytes(C.cast(staged.desc, C.c_void_p), C.cast(jit, C.c_void_p) if jit is not None else None,

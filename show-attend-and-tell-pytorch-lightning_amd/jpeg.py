@@ -7,7 +7,9 @@ the kernels read.
 
 GPU-decodable: Huffman-coded sequential 8-bit files (SOF0, SOF1) with one scan holding every component, either
 1 component (grayscale) or 3 components that libjpeg reads as YCbCr, luma sampled h1v1, h2v1 or h2v2 and chroma 1x1, with
-or without restart markers.  Everything else (progressive, arithmetic-coded, 12-bit, lossless, CMYK / YCCK, Adobe RGB,
+or without restart markers.  A file with restart markers is entropy-decoded by one thread per restart segment; a restart-free
+file (most cameras, COCO) of at least ``parallel_min_bytes`` of data by one thread per ``subseq_bytes`` of it, the threads
+synchronising on the device (include/sat_hip.h, ``sat_jpeg_decode_batch_ex``); the bytes that come out are the same.  Everything else (progressive, arithmetic-coded, 12-bit, lossless, CMYK / YCCK, Adobe RGB,
 several scans, other sampling factors, non-JPEG bytes) is decoded by Pillow, as ``data.decode_rgb`` does.
 """
 from __future__ import annotations
@@ -434,24 +436,49 @@ class JpegBatch:
         for o, blob in self._parts:
             buf[c + o:c + o + len(blob)] = np.frombuffer(blob, dtype=np.uint8)
 
-    def workspace_bytes(self):
-        need = L.lib().sat_jpeg_decode_workspace_bytes(C.cast(self.desc, C.c_void_p), self.n)
+    def workspace_bytes(self, subseq_bytes=None, parallel_min_bytes=None):
+        opts = decode_opts(subseq_bytes, parallel_min_bytes)
+        need = L.lib().sat_jpeg_decode_workspace_bytes_ex(C.cast(self.desc, C.c_void_p), self.n, C.byref(opts))
         if need == 0:
-            L.check(1, "sat_jpeg_decode_workspace_bytes")
+            L.check(1, "sat_jpeg_decode_workspace_bytes_ex")
         return need
 
-    def launch(self, region_ptr, pixels_ptr, pixels_bytes, status, workspace, stream):
-        """sat_jpeg_decode_batch with the region at device address ``region_ptr``; ``status``: (n,) int32 device tensor"""
-        L.check(L.lib().sat_jpeg_decode_batch(region_ptr + self.comp_off, self.comp_bytes, C.cast(self.desc, C.c_void_p), region_ptr, self.n,
-                                              region_ptr + self.quant_off, len(self.quant), region_ptr + self.huff_off, len(self.huff),
-                                              pixels_ptr, pixels_bytes, L.ptr(status), L.ptr(workspace), workspace.numel(),
-                                              C.c_void_p(stream.cuda_stream)), "sat_jpeg_decode_batch")
+    def launch(self, region_ptr, pixels_ptr, pixels_bytes, status, workspace, stream, subseq_bytes=None, parallel_min_bytes=None, info=None):
+        """sat_jpeg_decode_batch_ex with the region at device address ``region_ptr``; ``status``: (n,) int32 device tensor;
+        ``info``: None or an (n, 4) int32 device tensor (path, subsequences, synchronisation rounds, 0 per picture)"""
+        opts = decode_opts(subseq_bytes, parallel_min_bytes)
+        if info is not None:
+            L.require_gpu(info)
+            assert info.dtype == status.dtype and info.numel() == 4 * self.n and info.is_contiguous()
+            opts.info = info.data_ptr()
+        L.check(L.lib().sat_jpeg_decode_batch_ex(region_ptr + self.comp_off, self.comp_bytes, C.cast(self.desc, C.c_void_p), region_ptr, self.n,
+                                                 region_ptr + self.quant_off, len(self.quant), region_ptr + self.huff_off, len(self.huff),
+                                                 pixels_ptr, pixels_bytes, L.ptr(status), L.ptr(workspace), workspace.numel(),
+                                                 C.c_void_p(stream.cuda_stream), C.byref(opts)), "sat_jpeg_decode_batch_ex")
 
 
-def decode_jpeg_batch(items, device="cuda", check=True):
+#: ``parallel_min_bytes`` that keeps every picture on the one-thread-per-segment path
+NEVER_PARALLEL = (1 << 63) - 1
+#: the library's defaults (SAT_JPEG_SUBSEQ_BYTES_DEFAULT, SAT_JPEG_PARALLEL_MIN_BYTES_DEFAULT of include/sat_hip.h)
+SUBSEQ_BYTES_DEFAULT = 128
+PARALLEL_MIN_BYTES_DEFAULT = 2048
+
+
+def decode_opts(subseq_bytes=None, parallel_min_bytes=None):
+    """sat_jpeg_decode_opts; None: the library's default"""
+    return L.JpegDecodeOpts(subseq_bytes=0 if subseq_bytes is None else int(subseq_bytes),
+                            parallel_min_bytes=-1 if parallel_min_bytes is None else int(parallel_min_bytes), info=None)
+
+
+def decode_jpeg_batch(items, device="cuda", check=True, subseq_bytes=None, parallel_min_bytes=None, return_info=False):
     """The decoded (H, W, 3) uint8 tensors on ``device`` of a list of JPEG byte strings (or ``JpegBytes``): the GPU decodes the
     files it takes, Pillow the others.  A bad stream raises ``JpegDecodeError``; with ``check=False`` the call returns
-    ``(tensors, status)`` instead, status an (n,) int32 CPU tensor, 0 for a good picture (and for every Pillow-decoded one)."""
+    ``(tensors, status)`` instead, status an (n,) int32 CPU tensor, 0 for a good picture (and for every Pillow-decoded one).
+    ``subseq_bytes`` / ``parallel_min_bytes``: the options of ``sat_jpeg_decode_batch_ex`` (None: the library's defaults;
+    ``parallel_min_bytes=0`` sends every restart-free picture to the many-thread path, ``NEVER_PARALLEL`` none).  With
+    ``return_info`` an (n, 4) int32 CPU tensor comes back as the last value: per picture the path taken (0 one thread per restart
+    segment, 1 one thread per subsequence, 2 the latter abandoned for the former), its subsequences, the synchronisation rounds
+    run and 0; the row of a Pillow-decoded picture is all -1."""
     import torch
     device = torch.device(device)
     if device.type != "cuda":
@@ -460,6 +487,7 @@ def decode_jpeg_batch(items, device="cuda", check=True):
     gpu = [i for i, p in enumerate(pics) if isinstance(p, JpegBytes)]
     out = [None] * len(pics)
     status = torch.zeros(len(pics), dtype=torch.int32)
+    info = torch.full((len(pics), 4), -1, dtype=torch.int32)
     for i, p in enumerate(pics):
         if not isinstance(p, JpegBytes):
             out[i] = torch.from_numpy(np.array(p, dtype=np.uint8, copy=True)).to(device)
@@ -471,9 +499,12 @@ def decode_jpeg_batch(items, device="cuda", check=True):
         region = host.to(device, non_blocking=True)
         pixels = torch.empty(max(jb.out_bytes, 1), dtype=torch.uint8, device=device)
         st = torch.empty(jb.n, dtype=torch.int32, device=device)
-        ws = torch.empty(jb.workspace_bytes(), dtype=torch.uint8, device=device)
-        jb.launch(region.data_ptr(), pixels.data_ptr(), pixels.numel(), st, ws, stream)
+        ws = torch.empty(jb.workspace_bytes(subseq_bytes, parallel_min_bytes), dtype=torch.uint8, device=device)
+        inf = torch.empty(jb.n, 4, dtype=torch.int32, device=device) if return_info else None
+        jb.launch(region.data_ptr(), pixels.data_ptr(), pixels.numel(), st, ws, stream, subseq_bytes, parallel_min_bytes, inf)
         st = st.cpu()
+        if return_info:
+            info[gpu] = inf.cpu()
         for j, i in enumerate(gpu):
             h, w = jb.shapes[j]
             out[i] = pixels[jb.out_offsets[j]:jb.out_offsets[j] + h * w * 3].view(h, w, 3)
@@ -482,5 +513,5 @@ def decode_jpeg_batch(items, device="cuda", check=True):
         bad = [i for i in range(len(pics)) if status[i]]
         if bad:
             raise JpegDecodeError("corrupt JPEG data: " + "; ".join("picture %d: %s" % (i, status_text(int(status[i]))) for i in bad))
-        return out
-    return out, status
+        return (out, info) if return_info else out
+    return (out, status, info) if return_info else (out, status)

@@ -7,8 +7,10 @@ at strength S (sat_image_batch_transform_warp).
 With --jpeg the batch arrives as JPEG files instead (Pillow-encoded 480x640, quality 90, 4:2:0, restart-free and again with
 a restart marker per MCU row; or the first --batch files of --jpeg-dir): GPU decoding alone (sat_jpeg_decode_batch, bytes
 resident), decoding + the transform with and without the H2D copy, and Pillow's decode_rgb on one host thread.
+--subseq-bytes / --parallel-min-bytes set the options of sat_jpeg_decode_batch_ex (default: the library's); the paths the
+pictures took and the mean number of synchronisation rounds are reported.
     python tools/bench_input_pipeline.py [--batch 128] [--size 224] [--color-jitter 0.4] [--optical 0.5]
-    python tools/bench_input_pipeline.py --jpeg [--jpeg-dir DIR]
+    python tools/bench_input_pipeline.py --jpeg [--jpeg-dir DIR] [--subseq-bytes 128] [--parallel-min-bytes 2048]
 """
 import argparse
 import ctypes as C
@@ -89,12 +91,14 @@ def jpeg_rates(tf, files, iters, label):
     resident = torch.empty(staged.device_bytes, dtype=torch.uint8, device=dev)
     resident[:staged.host.numel()].copy_(staged.host)
     status = torch.empty(jb.n, dtype=torch.int32, device=dev)
-    jws = torch.empty(jb.workspace_bytes(), dtype=torch.uint8, device=dev)
+    info = torch.empty(jb.n, 4, dtype=torch.int32, device=dev)
+    sb, pm = tf.jpeg_subseq_bytes, tf.jpeg_parallel_min_bytes
+    jws = torch.empty(jb.workspace_bytes(sb, pm), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream()
     base = resident.data_ptr()
 
     def decode():
-        jb.launch(base + staged.jpeg_off, base + staged.head, staged.pixels_bytes, status, jws, stream)
+        jb.launch(base + staged.jpeg_off, base + staged.head, staged.pixels_bytes, status, jws, stream, sb, pm, info)
     desc = C.cast(staged.desc, C.c_void_p)
     need = lib.sat_image_batch_workspace_bytes(desc, B, S, S)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -113,19 +117,26 @@ def jpeg_rates(tf, files, iters, label):
         J.pillow_decode(f)
     cpu_s = (time.perf_counter() - t0) / n_cpu
     mb = sum(len(f) for f in files) / 1e6
+    inf = info.cpu()
+    par = inf[:, 0] == 1
+    paths = {label + "paths_serial_parallel_abandoned": [int((inf[:, 0] == k).sum()) for k in (0, 1, 2)],
+             label + "mean_subsequences": round(float(inf[par, 1].float().mean()), 1) if par.any() else 0.0,
+             label + "mean_sync_iterations": round(float(inf[par, 2].float().mean()), 2) if par.any() else 0.0}
     return {label + "decode_ms": round(dec_ms, 3), label + "decode_images_per_s": round(B / dec_ms * 1e3, 1),
             label + "decode_transform_ms": round(dt_ms, 3), label + "decode_transform_images_per_s": round(B / dt_ms * 1e3, 1),
             label + "decode_transform_with_h2d_ms": round(with_copy_ms, 3), label + "decode_transform_with_h2d_images_per_s": round(B / with_copy_ms * 1e3, 1),
             label + "compressed_MB": round(mb, 2), label + "h2d_bytes": int(staged.host.numel()), label + "segments": int(sum(jb.desc[j].n_segments for j in range(B))),
-            label + "pillow_decode_1thread_images_per_s": round(1.0 / cpu_s, 1)}
+            label + "pillow_decode_1thread_images_per_s": round(1.0 / cpu_s, 1), **paths}
 
 
 def main_jpeg(a):
     import io
     from PIL import Image
     B, S = a.batch, a.size
-    tf = D.BatchTransform(S, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01)
-    res = {"metric": "input_pipeline_jpeg_images_per_s", "batch": B, "out": S}
+    tf = D.BatchTransform(S, train=True, aug_scale=0.9, aug_hflip=0.5, aug_noise_std=0.01, jpeg_subseq_bytes=a.subseq_bytes,
+                          jpeg_parallel_min_bytes=a.parallel_min_bytes)
+    res = {"metric": "input_pipeline_jpeg_images_per_s", "batch": B, "out": S, "subseq_bytes": a.subseq_bytes or "default",
+           "parallel_min_bytes": "default" if a.parallel_min_bytes is None else a.parallel_min_bytes}
     if a.jpeg_dir:
         names = sorted(n for n in os.listdir(a.jpeg_dir) if n.lower().endswith((".jpg", ".jpeg")))[:B]
         files = []
@@ -164,6 +175,9 @@ def main():
     ap.add_argument("--optical", type=float, default=0.0, help="also time the optical augmentation of strength S on the same batch")
     ap.add_argument("--jpeg", action="store_true", help="time GPU JPEG decoding (+ the transform) of a batch of JPEG files instead")
     ap.add_argument("--jpeg-dir", default=None, help="with --jpeg: the first --batch *.jpg files of this directory instead of synthetic ones")
+    ap.add_argument("--subseq-bytes", type=int, default=None, help="with --jpeg: bytes per subsequence of a restart-free picture (default: the library's)")
+    ap.add_argument("--parallel-min-bytes", type=int, default=None,
+                    help="with --jpeg: least data bytes of a restart-free picture decoded by subsequences (default: the library's; 0 all; 2^63-1 none)")
     a = ap.parse_args()
     if a.jpeg or a.jpeg_dir:
         return main_jpeg(a)
