@@ -625,7 +625,8 @@ int sat_image_batch_transform_warp(const uint8_t* pixels, int64_t pixels_bytes, 
  * The step in front of the transform: util.py:136-137's Image.open(f).convert("RGB") for Huffman-coded sequential 8-bit
  * files (SOF0 / SOF1) with one scan of 1 (grayscale) or 3 YCbCr components, luma sampled h1v1, h2v1 or h2v2 and chroma
  * 1x1, with or without restart markers; bit exact with libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling).  The
- * host parses the headers (sat_amd/jpeg.py) and sends every other file to Pillow.  Three stages: entropy decoding,
+ * host parses the headers (sat_amd/jpeg.py) and sends every other file to Pillow (progressive files: the section after
+ * this one, on request).  Three stages: entropy decoding,
  * dequantisation + ISLOW IDCT (per block), upsampling + YCbCr->RGB (per pixel).  Entropy decoding gives every restart
  * segment one thread; a restart-free picture (n_segments == 1) of at least parallel_min_bytes of data is instead cut into
  * subsequences of subseq_bytes raw bytes, each decoded by a thread of its own: a speculative pass from (slot 0, DC next),
@@ -685,6 +686,49 @@ int sat_jpeg_decode_batch_ex(const uint8_t* compressed, int64_t compressed_bytes
                              int32_t n, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev, int32_t n_huff,
                              uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream,
                              const sat_jpeg_decode_opts* opts);
+
+/* ---- progressive JPEG decoding on device -------------------------------------------------------------------------------
+ * The same step for Huffman-coded 8-bit progressive files (SOF2) whose scan script the host admits (sat_amd/jpeg.py,
+ * parse(progressive=True): libjpeg's jpeg_simple_progression, the ten scans Pillow writes for YCbCr and the six for
+ * grayscale, complete down to Al = 0, with or without restart markers; every other progressive file goes to Pillow).
+ * Opt-in: nothing calls this unless the caller asks for progressive files on the GPU.
+ * sat_jpeg_desc is reused for the geometry, the quantisation tables, out_offset and block_offset (prefix sums over the n
+ * pictures of THIS call); its scan fields (data_*, segments_offset, restart_interval, n_segments, segment_base, dc_table,
+ * ac_table) are ignored and reserved stays 0.  One sat_jpeg_scan per scan of every picture, ordered by level:
+ *   picture                   index into desc
+ *   level                     dependency level: 1 + the highest level of an earlier scan of the picture that touches one of
+ *                             the same (component, coefficient) cells, 0 if none.  Non-decreasing along the array; the
+ *                             scans of one level touch disjoint cells of a picture (the caller's promise).
+ *   n_components, component   1 (a non-interleaved scan: the ceil(w_c / 8) x ceil(h_c / 8) blocks of that component in raster
+ *                             order, which is what its restart interval counts) or all 3 in order 0, 1, 2 (DC scans only: the
+ *                             padded MCU grid)
+ *   ss, se, ah, al            band and successive-approximation bits: ss = se = 0 a DC scan, else 1 <= ss <= se <= 63;
+ *                             ah = 0 a first scan, else a refinement with al = ah - 1
+ *   dc_table, ac_table        indices into the Huffman tables as latched at the scan's SOS (dc_table per component of a DC
+ *                             first scan, ac_table of an AC scan; the others are not read)
+ *   restart_interval          MCUs of this scan per segment, 0: one segment
+ *   data_offset, data_bytes, segments_offset, n_segments   as in sat_jpeg_desc, for this scan
+ *   segment_base              segments of the scans in front of this one in the array (prefix sum; checked)
+ * Stages: the coefficient blocks are cleared; one entropy launch per level with one lane per (scan, restart segment) running
+ * jdphuff.c's DC-first / DC-refine / AC-first / AC-refine arithmetic, every read bounded by the lane's segment, every
+ * coefficient index by se, every block by the scan's blocks; then the baseline path's IDCT and colour kernels.  status as
+ * above (index past 63 reads: past se).  info: NULL or n x 4 int32 on the device, per picture (3, scans, levels, 0).
+ * workspace: 192 bytes per coefficient block.  SAT_EINVAL, before anything is enqueued: null pointers, a small workspace,
+ * scan records that do not fit their picture.  No host synchronisation, allocation or read-back inside the call.         */
+typedef struct sat_jpeg_scan {
+    int64_t data_offset, data_bytes, segments_offset;
+    int32_t picture, level, n_components, component[3];
+    int32_t ss, se, ah, al;
+    int32_t dc_table[3], ac_table;
+    int32_t restart_interval, n_segments, segment_base;
+    int32_t reserved;
+} sat_jpeg_scan;
+size_t sat_jpeg_progressive_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n, const sat_jpeg_scan* scans_host, int32_t n_scans);
+int sat_jpeg_decode_progressive_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host,
+                                      const sat_jpeg_desc* desc_dev, int32_t n, const sat_jpeg_scan* scans_host, const sat_jpeg_scan* scans_dev,
+                                      int32_t n_scans, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev,
+                                      int32_t n_huff, uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, void* stream, int32_t* info);
 
 /* ---- attention overlays on device (visualize.ipynb's make_visual) ------------------------------------------------------
  * The single-image front end of util.py:141-164: load_square = crop_center(min side) then Image.resize((S, S)) with no filter

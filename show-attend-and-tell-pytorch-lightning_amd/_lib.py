@@ -103,6 +103,14 @@ class JpegDecodeOpts(C.Structure):
     _fields_ = [("subseq_bytes", C.c_int32), ("reserved", C.c_int32), ("parallel_min_bytes", C.c_int64), ("info", C.c_void_p)]
 
 
+class JpegScan(C.Structure):
+    """sat_jpeg_scan: one scan of a progressive picture of sat_jpeg_decode_progressive_batch"""
+    _fields_ = [(k, C.c_int64) for k in ("data_offset", "data_bytes", "segments_offset")] + \
+               [("picture", C.c_int32), ("level", C.c_int32), ("n_components", C.c_int32), ("component", C.c_int32 * 3)] + \
+               [(k, C.c_int32) for k in ("ss", "se", "ah", "al")] + [("dc_table", C.c_int32 * 3), ("ac_table", C.c_int32)] + \
+               [(k, C.c_int32) for k in ("restart_interval", "n_segments", "segment_base", "reserved")]
+
+
 class JpegQTable(C.Structure):
     _fields_ = [("q", C.c_uint16 * 64)]
 
@@ -267,7 +275,10 @@ SYMBOLS.update({"sat_image_batch_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32
 SYMBOLS.update({"sat_jpeg_decode_workspace_bytes": (C.c_size_t, [_vp, _i32]),
                 "sat_jpeg_decode_batch": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp]),
                 "sat_jpeg_decode_workspace_bytes_ex": (C.c_size_t, [_vp, _i32, _vp]),
-                "sat_jpeg_decode_batch_ex": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp, _vp])})
+                "sat_jpeg_decode_batch_ex": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_size_t, _vp, _vp]),
+                "sat_jpeg_progressive_workspace_bytes": (C.c_size_t, [_vp, _i32, _vp, _i32]),
+                "sat_jpeg_decode_progressive_batch": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp,
+                                                                C.c_size_t, _vp, _vp])})
 SYMBOLS.update({"sat_profile_start": (C.c_int, []),
                 "sat_profile_start_only": (C.c_int, [C.c_char_p]),
                 "sat_profile_pause": (C.c_int, [_i32]),

@@ -641,6 +641,255 @@ __global__ __launch_bounds__(64) void jpeg_par_finish_kernel(const uint8_t* __re
     entropy_serial_lane(comp, comp_bytes, d, p, 0, tabs, coefs, status);
 }
 
+// -------------------------------------------------------------------------------------------------- 1c. entropy, progressive
+// sat_jpeg_decode_progressive_batch: the scans of a progressive picture fill the same coefficient array, a band and a bit position
+// at a time.  One launch per dependency level, one workgroup (one wave) per scan and restart segment.  Lane 0 is the serial bit
+// reader and runs jdphuff.c's arithmetic; the other lanes move coefficients: they stage the block an AC-refinement lane corrects
+// in LDS (it reads every coefficient of its band, and a dependent global load apiece would be the whole run time) and apply the
+// 64 bits of a DC-refinement step to 64 blocks.  The scans of one level touch disjoint (component, coefficient) cells of a
+// picture, and the segments of one scan disjoint blocks, so no two lanes of a launch write the same int16.
+// A unit is one block of the scan in coding order: an interleaved scan walks the padded MCU grid as the baseline scan does; a scan
+// of one component covers the ceil(dw / 8) x ceil(dh / 8) blocks that hold its samples in raster order, and that is what its
+// restart interval counts.
+struct ScanMap {
+    bool inter;
+    BlockMap bm;
+    int c, sw, bwc;
+    long basec, units;
+
+    __device__ inline void init(const sat_jpeg_desc& d, const sat_jpeg_scan& sc) {
+        inter = sc.n_components > 1;
+        bm.init(d);
+        c = sc.component[0];
+        const CompGeom g = comp_geom(d, c);
+        sw = (g.dw + 7) / 8; bwc = g.bw;
+        basec = c == 0 ? bm.base0 : (c == 1 ? bm.base1 : bm.base2);
+        units = inter ? bm.total : (long)sw * ((g.dh + 7) / 8);
+    }
+    __device__ inline int per_mcu() const { return inter ? bm.slots : 1; }
+    __device__ inline long block(long u) const {
+        if (inter) return bm.block(u / bm.slots, (int)(u % bm.slots));
+        return basec + (u / sw) * bwc + u % sw;
+    }
+    __device__ inline int comp(long u) const {
+        if (!inter) return c;
+        const int slot = (int)(u % bm.slots);
+        return slot < bm.ny ? 0 : slot - bm.ny + 1;
+    }
+};
+
+__host__ __device__ inline long scan_units(const sat_jpeg_desc& d, const sat_jpeg_scan& sc) {
+    if (sc.n_components > 1) return picture_mcus(d);
+    const CompGeom g = comp_geom(d, sc.component[0]);
+    return (long)((g.dw + 7) / 8) * ((g.dh + 7) / 8);
+}
+
+__device__ inline int get_bits(BitReader& br, int n) {
+    br.refill();
+    const int v = (int)br.peek(n);
+    br.skip(n);
+    return v;
+}
+
+// decode_mcu_AC_first, one block
+__device__ inline void prog_ac_first(BitReader& br, const sat_jpeg_htable& t, int ss, int se, int al, int& eobrun, int16_t* __restrict__ blk) {
+    if (eobrun > 0) { --eobrun; return; }
+    for (int k = ss; k <= se; ++k) {
+        const int rs = huff_decode(br, t);
+        if (rs < 0) return;
+        const int r = rs >> 4, s = rs & 15;
+        if (s) {
+            k += r;
+            if (k > se) { br.flags |= JPEG_BAD_INDEX; return; }
+            blk[k_natural_order[k]] = (int16_t)((unsigned)receive_extend(br, s) << al);
+        } else if (r == 15) {
+            k += 15;
+        } else {
+            eobrun = 1 << r;
+            if (r) eobrun += get_bits(br, r);
+            --eobrun;                                             // this block is the first of the run
+            return;
+        }
+    }
+}
+
+// a correction bit for a coefficient that is already non-zero: add p1 / m1 only if that bit is not set yet
+__device__ inline void prog_correct(BitReader& br, int16_t* c, int p1, int m1) {
+    if (get_bits(br, 1)) {
+        const int v = *c;
+        if ((v & p1) == 0) *c = (int16_t)(v >= 0 ? v + p1 : v + m1);
+    }
+}
+
+// decode_mcu_AC_refine, one block (in LDS)
+__device__ inline void prog_ac_refine(BitReader& br, const sat_jpeg_htable& t, int ss, int se, int al, int& eobrun, int16_t* blk) {
+    const int p1 = 1 << al, m1 = -p1;
+    int k = ss;
+    if (eobrun == 0) {
+        for (; k <= se; ++k) {
+            const int rs = huff_decode(br, t);
+            if (rs < 0) return;
+            int r = rs >> 4, s = rs & 15;
+            if (s) {
+                s = get_bits(br, 1) ? p1 : m1;                    // the size is 1 in a good stream; libjpeg reads one bit whatever it is
+            } else if (r != 15) {
+                eobrun = 1 << r;
+                if (r) eobrun += get_bits(br, r);
+                break;                                            // the rest of this block is worked off below
+            }
+            // pass r zero-valued positions (16 for a ZRL), correcting the non-zero ones on the way
+            do {
+                int16_t* c = blk + k_natural_order[k];
+                if (*c != 0) prog_correct(br, c, p1, m1);
+                else if (--r < 0) break;
+                ++k;
+            } while (k <= se);
+            if (s) {
+                if (k > se) { br.flags |= JPEG_BAD_INDEX; return; }
+                blk[k_natural_order[k]] = (int16_t)s;
+            }
+            if (br.flags & ~JPEG_MARKER) return;
+        }
+    }
+    if (eobrun > 0) {
+        for (; k <= se; ++k) {
+            int16_t* c = blk + k_natural_order[k];
+            if (*c != 0) prog_correct(br, c, p1, m1);
+        }
+        --eobrun;
+    }
+}
+
+__global__ __launch_bounds__(64) void jpeg_prog_entropy_kernel(const uint8_t* __restrict__ comp, long comp_bytes, const sat_jpeg_desc* __restrict__ desc,
+                                                               const sat_jpeg_scan* __restrict__ scans, int scan_lo, int scan_hi, int seg_lo,
+                                                               const sat_jpeg_htable* __restrict__ huff, int16_t* __restrict__ coefs,
+                                                               int* __restrict__ status) {
+    __shared__ sat_jpeg_htable tabs[3];
+    __shared__ int16_t sblk[64];
+    __shared__ uint32_t smask[2];
+    const int seg_global = seg_lo + blockIdx.x;
+    int lo = scan_lo, hi = scan_hi - 1;                          // scan of this level: last one whose segment_base <= seg_global
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (scans[mid].segment_base <= seg_global) lo = mid; else hi = mid - 1;
+    }
+    const sat_jpeg_scan& sc = scans[lo];
+    const int seg = seg_global - sc.segment_base;
+    if (seg < 0 || seg >= sc.n_segments) return;
+    const int p = sc.picture;
+    const sat_jpeg_desc& d = desc[p];
+    const int ss = sc.ss, se = sc.se, ah = sc.ah, al = sc.al;
+    const bool dc_scan = ss == 0;
+    const int nt = dc_scan ? (ah == 0 ? sc.n_components : 0) : 1;          // a DC refinement reads raw bits only
+    for (int t = 0; t < nt; ++t) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(huff + (dc_scan ? sc.dc_table[t] : sc.ac_table));
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&tabs[t]);
+        for (int k = threadIdx.x; k < (int)(sizeof(sat_jpeg_htable) / 4); k += blockDim.x) dst[k] = src[k];
+    }
+    __syncthreads();
+    const int tid = threadIdx.x;
+    ScanMap map;
+    map.init(d, sc);
+    const long ri = (long)sc.restart_interval * map.per_mcu();
+    const long u0 = ri ? (long)seg * ri : 0;
+    const long u1 = ri ? min(map.units, u0 + ri) : map.units;
+
+    BitReader br;
+    br.base = comp; br.abs0 = sc.data_offset; br.pos = 0; br.end = 0; br.limit = comp_bytes;
+    br.buf = 0; br.cnt = 0; br.fill = 0; br.flags = 0; br.word_idx = -1; br.word = 0;
+    {
+        const uint32_t* segtab = reinterpret_cast<const uint32_t*>(comp + sc.segments_offset);
+        const long s0 = segtab[2 * seg], s1 = segtab[2 * seg + 1];
+        if (s0 > s1 || s1 > sc.data_bytes) {                      // the whole wave leaves: no barrier is left waiting
+            if (tid == 0) atomicOr(status + p, JPEG_BAD_SEGMENT);
+            return;
+        }
+        br.pos = s0; br.end = s1;
+    }
+
+    if (dc_scan && ah == 0) {                                     // DC first: lane 0 alone
+        if (tid != 0) return;
+        int dc0 = 0, dc1 = 0, dc2 = 0;                            // the predictors start at 0 in every restart segment
+        for (long u = u0; u < u1 && !(br.flags & ~JPEG_MARKER); ++u) {
+            const int c = map.comp(u);
+            const int slot = map.inter ? c : 0;
+            const int s = huff_decode(br, tabs[slot]);
+            if (s > 15) br.flags |= JPEG_BAD_CODE;
+            if (s >= 0 && s <= 15) {
+                const int dcv = (c == 0 ? dc0 : (c == 1 ? dc1 : dc2)) + receive_extend(br, s);
+                if (c == 0) dc0 = dcv; else if (c == 1) dc1 = dcv; else dc2 = dcv;
+                const int16_t v = (int16_t)((unsigned)dcv << al);
+                if (v) coefs[map.block(u) * 64] = v;
+            }
+            if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
+        }
+        if (br.flags) atomicOr(status + p, br.flags);
+    } else if (dc_scan) {                                         // DC refine: bit i of the segment belongs to unit u0 + i
+        const int16_t p1 = (int16_t)(1 << al);
+        for (long u = u0; u < u1; u += 64) {
+            int bad = 0;
+            if (tid == 0) {
+                const int nb = (int)min(64L, u1 - u);
+                uint32_t m0 = 0, m1 = 0;
+                for (int i = 0; i < nb; ++i) {
+                    const uint32_t bit = (uint32_t)get_bits(br, 1);
+                    if (i < 32) m0 |= bit << i; else m1 |= bit << (i - 32);
+                }
+                if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
+                smask[0] = m0; smask[1] = m1;
+                bad = br.flags & ~JPEG_MARKER;
+            }
+            __syncthreads();
+            if (u + tid < u1 && ((smask[tid >> 5] >> (tid & 31)) & 1u)) {
+                int16_t* b = coefs + map.block(u + tid) * 64;
+                b[0] = (int16_t)(b[0] | p1);
+            }
+            if (__syncthreads_or(bad)) break;                     // also: smask is free again
+        }
+        if (tid == 0 && br.flags) atomicOr(status + p, br.flags);
+    } else if (ah == 0) {                                         // AC first: lane 0 alone, only the non-zero coefficients are stored
+        if (tid != 0) return;
+        int eobrun = 0;                                           // and so does EOBRUN
+        for (long u = u0; u < u1 && !(br.flags & ~JPEG_MARKER); ++u) {
+            if (eobrun > 0) { --eobrun; continue; }
+            prog_ac_first(br, tabs[0], ss, se, al, eobrun, coefs + map.block(u) * 64);
+            if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
+        }
+        if (br.flags) atomicOr(status + p, br.flags);
+    } else {                                                      // AC refine: the block goes through LDS
+        int eobrun = 0;
+        int16_t next = u0 < u1 ? coefs[map.block(u0) * 64 + tid] : (int16_t)0;
+        for (long u = u0; u < u1; ++u) {
+            int16_t* blk = coefs + map.block(u) * 64;
+            const int16_t v = next;
+            sblk[tid] = v;
+            if (u + 1 < u1) next = coefs[map.block(u + 1) * 64 + tid];        // in flight while lane 0 decodes this block
+            __syncthreads();
+            int bad = 0;
+            if (tid == 0) {
+                prog_ac_refine(br, tabs[0], ss, se, al, eobrun, sblk);
+                if (br.overrun()) br.flags |= JPEG_OUT_OF_DATA;
+                bad = br.flags & ~JPEG_MARKER;
+            }
+            const int stop = __syncthreads_or(bad);
+            const int16_t w = sblk[tid];
+            if (w != v) blk[tid] = w;
+            if (stop) break;
+        }
+        if (tid == 0 && br.flags) atomicOr(status + p, br.flags);
+    }
+}
+
+// info rows of the progressive pictures: (3, scans, levels, 0)
+__global__ __launch_bounds__(256) void jpeg_prog_info_kernel(const sat_jpeg_scan* __restrict__ scans, int n_scans, int n, int* __restrict__ info) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    int cnt = 0, top = -1;
+    for (int i = 0; i < n_scans; ++i)
+        if (scans[i].picture == p) { ++cnt; top = max(top, scans[i].level); }
+    info[4 * p] = 3; info[4 * p + 1] = cnt; info[4 * p + 2] = top + 1; info[4 * p + 3] = 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- 2. IDCT
 // jidctint.c, CONST_BITS 13, PASS1_BITS 2; JLONG arithmetic (64-bit) and an int workspace, as libjpeg on LP64.
 constexpr int CB = 13, P1 = 2;
@@ -849,6 +1098,76 @@ size_t workspace_need(long blocks, int n, long subs) {
     return par_state_offset(blocks) + (size_t)n * PAR_CTRL * sizeof(int) + (size_t)subs * (2 * sizeof(uint64_t) + 2 * sizeof(int));
 }
 
+// the geometry checks both entry points make of a picture
+int check_geometry(const sat_jpeg_desc& d, int i) {
+    SAT_REQUIRE(d.height >= 1 && d.height <= 65535 && d.width >= 1 && d.width <= 65535, "jpeg %d: size %dx%d", i, d.height, d.width);
+    SAT_REQUIRE(d.components == 1 || d.components == 3, "jpeg %d: %d components (1 or 3)", i, d.components);
+    if (d.components == 3)
+        SAT_REQUIRE((d.h_samp == 1 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 1) || (d.h_samp == 2 && d.v_samp == 2),
+                    "jpeg %d: luma sampling %dx%d (1x1, 2x1 or 2x2)", i, d.h_samp, d.v_samp);
+    else
+        SAT_REQUIRE(d.h_samp == 1 && d.v_samp == 1, "jpeg %d: a grayscale picture takes sampling 1x1", i);
+    return SAT_OK;
+}
+
+int prog_validate(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* dh, const sat_jpeg_desc* dd, int32_t n,
+                  const sat_jpeg_scan* sh, const sat_jpeg_scan* sd, int32_t n_scans, const void* quant, int32_t n_quant, const void* huff,
+                  int32_t n_huff, const uint8_t* pixels, int64_t pixels_bytes, const int32_t* status, long* blocks_out, long* max_px, long* max_blocks) {
+    const char* who = "sat_jpeg_decode_progressive_batch";
+    SAT_REQUIRE(dh && dd && n > 0 && n <= 65535, "%s: null descriptors or n = %d (1 ... 65535)", who, n);
+    SAT_REQUIRE(sh && sd && n_scans > 0, "%s: null scan records or n_scans = %d", who, n_scans);
+    SAT_REQUIRE(compressed && compressed_bytes > 0 && quant && n_quant > 0 && huff && n_huff > 0 && pixels && pixels_bytes > 0 && status,
+                "%s: null buffer or empty table array", who);
+    long blocks = 0;
+    *max_px = *max_blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const sat_jpeg_desc& d = dh[i];
+        SAT_TRY(check_geometry(d, i));
+        SAT_REQUIRE(d.block_offset == blocks, "jpeg %d: block_offset %ld, expected %ld", i, (long)d.block_offset, blocks);
+        SAT_REQUIRE(d.out_offset >= 0 && d.out_offset + 3L * d.height * d.width <= pixels_bytes, "jpeg %d: output outside the pixel buffer", i);
+        for (int c = 0; c < 3; ++c) SAT_REQUIRE(d.quant[c] >= 0 && d.quant[c] < n_quant, "jpeg %d: table index out of range", i);
+        const long nb = picture_blocks(d);
+        blocks += nb;
+        if (nb > *max_blocks) *max_blocks = nb;
+        if ((long)d.height * d.width > *max_px) *max_px = (long)d.height * d.width;
+    }
+    long segs = 0;
+    int level = 0;
+    for (int i = 0; i < n_scans; ++i) {
+        const sat_jpeg_scan& sc = sh[i];
+        SAT_REQUIRE(sc.picture >= 0 && sc.picture < n, "scan %d: picture %d of %d", i, sc.picture, n);
+        const sat_jpeg_desc& d = dh[sc.picture];
+        SAT_REQUIRE(sc.level >= level, "scan %d: level %d behind level %d (the records are ordered by level)", i, sc.level, level);
+        level = sc.level;
+        SAT_REQUIRE((sc.n_components == 1 && sc.component[0] >= 0 && sc.component[0] < d.components) ||
+                        (sc.n_components == 3 && d.components == 3 && sc.component[0] == 0 && sc.component[1] == 1 && sc.component[2] == 2),
+                    "scan %d: components (one, or all three in order)", i);
+        if (sc.ss == 0)
+            SAT_REQUIRE(sc.se == 0, "scan %d: band %d..%d mixes DC and AC", i, sc.ss, sc.se);
+        else
+            SAT_REQUIRE(sc.n_components == 1 && sc.ss >= 1 && sc.ss <= sc.se && sc.se <= 63, "scan %d: AC band %d..%d of %d components", i, sc.ss, sc.se,
+                        sc.n_components);
+        SAT_REQUIRE(sc.ah >= 0 && sc.ah <= 13 && sc.al >= 0 && sc.al <= 13 && (sc.ah == 0 || sc.al == sc.ah - 1),
+                    "scan %d: successive approximation Ah %d Al %d", i, sc.ah, sc.al);
+        if (sc.ss == 0 && sc.ah == 0)
+            for (int c = 0; c < sc.n_components; ++c)
+                SAT_REQUIRE(sc.dc_table[c] >= 0 && sc.dc_table[c] < n_huff, "scan %d: table index out of range", i);
+        if (sc.ss) SAT_REQUIRE(sc.ac_table >= 0 && sc.ac_table < n_huff, "scan %d: table index out of range", i);
+        SAT_REQUIRE(sc.restart_interval >= 0 && sc.restart_interval <= 65535, "scan %d: restart interval %d", i, sc.restart_interval);
+        const long units = scan_units(d, sc);
+        const long want = sc.restart_interval ? (units + sc.restart_interval - 1) / sc.restart_interval : 1;
+        SAT_REQUIRE(sc.n_segments == want, "scan %d: %d segments, the restart interval makes %ld", i, sc.n_segments, want);
+        SAT_REQUIRE(sc.segment_base == segs, "scan %d: segment_base %d, expected %ld", i, sc.segment_base, segs);
+        SAT_REQUIRE(sc.data_offset >= 0 && sc.data_bytes >= 0 && sc.data_offset + sc.data_bytes <= compressed_bytes, "scan %d: data outside the buffer", i);
+        SAT_REQUIRE(sc.segments_offset >= 0 && sc.segments_offset % 4 == 0 && sc.segments_offset + 8L * sc.n_segments <= compressed_bytes,
+                    "scan %d: segment table outside the buffer or not 4-byte aligned", i);
+        segs += sc.n_segments;
+        SAT_REQUIRE(segs < (1L << 31), "%s: too many segments", who);
+    }
+    *blocks_out = blocks;
+    return SAT_OK;
+}
+
 }  // namespace
 }  // namespace sat
 
@@ -946,6 +1265,59 @@ int sat_jpeg_decode_batch(const uint8_t* compressed, int64_t compressed_bytes, c
                           uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     return sat_jpeg_decode_batch_ex(compressed, compressed_bytes, desc_host, desc_dev, n, quant_dev, n_quant, huff_dev, n_huff, pixels, pixels_bytes,
                                     status, workspace, workspace_bytes, stream, nullptr);
+}
+
+size_t sat_jpeg_progressive_workspace_bytes(const sat_jpeg_desc* desc_host, int32_t n, const sat_jpeg_scan* scans_host, int32_t n_scans) {
+    if (!desc_host || n <= 0 || !scans_host || n_scans <= 0) {
+        fail(SAT_EINVAL, "sat_jpeg_progressive_workspace_bytes: null records, n = %d or n_scans = %d", n, n_scans);
+        return 0;
+    }
+    long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (check_geometry(desc_host[i], i) != SAT_OK) return 0;
+        blocks += picture_blocks(desc_host[i]);
+    }
+    return par_state_offset(blocks);                           // coefficients | sample planes
+}
+
+int sat_jpeg_decode_progressive_batch(const uint8_t* compressed, int64_t compressed_bytes, const sat_jpeg_desc* desc_host,
+                                      const sat_jpeg_desc* desc_dev, int32_t n, const sat_jpeg_scan* scans_host, const sat_jpeg_scan* scans_dev,
+                                      int32_t n_scans, const sat_jpeg_qtable* quant_dev, int32_t n_quant, const sat_jpeg_htable* huff_dev,
+                                      int32_t n_huff, uint8_t* pixels, int64_t pixels_bytes, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, void* stream, int32_t* info) {
+    long blocks = 0, max_px = 0, max_blocks = 0;
+    SAT_TRY(prog_validate(compressed, compressed_bytes, desc_host, desc_dev, n, scans_host, scans_dev, n_scans, quant_dev, n_quant, huff_dev, n_huff,
+                          pixels, pixels_bytes, status, &blocks, &max_px, &max_blocks));
+    const size_t need = par_state_offset(blocks);
+    SAT_REQUIRE(workspace && workspace_bytes >= need, "sat_jpeg_decode_progressive_batch: workspace %zu bytes, need %zu", workspace_bytes, need);
+    SAT_REQUIRE(((uintptr_t)compressed & 3) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)desc_dev & 7) == 0 && ((uintptr_t)scans_dev & 7) == 0 &&
+                    ((uintptr_t)status & 3) == 0 && ((uintptr_t)huff_dev & 3) == 0 && ((uintptr_t)quant_dev & 1) == 0 && ((uintptr_t)info & 3) == 0,
+                "sat_jpeg_decode_progressive_batch: compressed (4), workspace (16), records (8), status, info and tables must be aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int16_t* coefs = reinterpret_cast<int16_t*>(workspace);
+    uint8_t* planes = reinterpret_cast<uint8_t*>(workspace) + (size_t)blocks * 64 * sizeof(int16_t);
+    SAT_TRY(dev_fill_bytes(st, status, 0, sizeof(int32_t) * (size_t)n));
+    SAT_TRY(dev_fill_bytes(st, coefs, 0, (size_t)blocks * 64 * sizeof(int16_t)));
+    if (info) {
+        hipLaunchKernelGGL(jpeg_prog_info_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, scans_dev, n_scans, n, reinterpret_cast<int*>(info));
+        SAT_TRY(launch_ok("jpeg_prog_info_kernel"));
+    }
+    // one launch per level: the records are ordered by level, so a level is a run of records and of segments
+    for (int lo = 0; lo < n_scans;) {
+        int hi = lo;
+        long segs = 0;
+        while (hi < n_scans && scans_host[hi].level == scans_host[lo].level) segs += scans_host[hi++].n_segments;
+        hipLaunchKernelGGL(jpeg_prog_entropy_kernel, dim3((unsigned)segs), dim3(64), 0, st, compressed, (long)compressed_bytes, desc_dev, scans_dev, lo, hi,
+                           scans_host[lo].segment_base, huff_dev, coefs, reinterpret_cast<int*>(status));
+        SAT_TRY(launch_ok("jpeg_prog_entropy_kernel"));
+        lo = hi;
+    }
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)min(cdiv(max_blocks, 256), 1024), (unsigned)n), dim3(256), 0, st, desc_dev, quant_dev, coefs,
+                       planes);
+    SAT_TRY(launch_ok("jpeg_idct_kernel"));
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)min(cdiv(max_px, 256), 1024), (unsigned)n), dim3(256), 0, st, desc_dev, planes, pixels);
+    SAT_TRY(launch_ok("jpeg_color_kernel"));
+    return SAT_OK;
 }
 
 }  // extern "C"

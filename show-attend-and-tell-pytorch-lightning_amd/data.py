@@ -311,6 +311,7 @@ class StagedBatch:
         self.jpeg, self.jpeg_off = None, head
         if self.jpeg_index:
             self.jpeg = J.JpegBatch([images[i] for i in self.jpeg_index], out_base=arrays_bytes)
+            self.jpeg_index = [self.jpeg_index[k] for k in self.jpeg.order]        # record order: baseline files, then progressive ones
             head = (head + self.jpeg.nbytes + 255) // 256 * 256
         total = head + arrays_bytes
         self.device_bytes = total + (self.jpeg.out_bytes if self.jpeg is not None else 0)

@@ -673,17 +673,19 @@ class SAT(SATDecoder, _Base):
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, **render):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
-        attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py)"""
+        attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
+        ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
         from . import visualize
         return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                    rescore_reward, visual_size, input_size, **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                      rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None):
-        """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities)"""
+                      rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False):
+        """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
+        ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
         from . import visualize
         return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed)
+                                       rescore_reward, visual_size, input_size, seed, progressive)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

@@ -55,15 +55,15 @@ def _square_bicubic(pixels_ptr, pixels_bytes, desc, desc_dev_ptr, n, size, devic
     return raw, out
 
 
-def _as_item(item):
+def _as_item(item, progressive=False):
     if isinstance(item, (str, os.PathLike)):
-        return J.read_jpeg(item)
+        return J.read_jpeg_progressive(item) if progressive else J.read_jpeg(item)
     if torch.is_tensor(item):
         item = item.cpu().numpy()
-    return J.as_picture(item)
+    return J.as_picture(item, progressive=progressive)
 
 
-def _load_squares(items, size, device):
+def _load_squares(items, size, device, progressive=False):
     """``load_square_batch`` plus the JPEG decoder's status words ((number of GPU-decoded files,) int32 on the device, or None) and the
     positions of those files in ``items``: the caller reads them when it reads everything else"""
     from .data import StagedBatch
@@ -71,7 +71,7 @@ def _load_squares(items, size, device):
     size = int(size or 0)
     if size <= 0:
         raise L.SatHipError("load_square_batch: size=%r (the squares of one batch share one size > 0)" % (size,))
-    pics = [_as_item(x) for x in items]
+    pics = [_as_item(x, progressive) for x in items]
     if not pics:
         raise ValueError("load_square_batch: no picture")
     staged = StagedBatch(pics, [dict(height=int(p.shape[0]), width=int(p.shape[1])) for p in pics])
@@ -97,11 +97,12 @@ def _raise_bad_jpeg(status, index):
         raise J.JpegDecodeError("corrupt JPEG data: " + "; ".join("picture %d: %s" % (i, J.status_text(int(s))) for i, s in bad))
 
 
-def load_square_batch(items, size, device="cuda"):
+def load_square_batch(items, size, device="cuda", progressive=False):
     """util.py:141-143 ``load_square(path, size)`` for a batch: ``items`` are file paths, JPEG bytes (``jpeg.JpegBytes`` or plain bytes: the
     GPU decodes what it can, Pillow the rest) or decoded (H, W, 3) uint8 arrays of any shapes.  Returns (B, size, size, 3) uint8 on
-    ``device``, the bytes ``crop_max_square`` leaves in the PIL image.  A corrupt GPU-decoded file raises ``jpeg.JpegDecodeError``."""
-    raw, status, index = _load_squares(items, size, device)
+    ``device``, the bytes ``crop_max_square`` leaves in the PIL image.  A corrupt GPU-decoded file raises ``jpeg.JpegDecodeError``.
+    ``progressive``: the GPU also decodes the progressive files ``jpeg.parse(progressive=True)`` admits."""
+    raw, status, index = _load_squares(items, size, device, progressive)
     _raise_bad_jpeg(status, index)
     return raw
 
@@ -151,14 +152,14 @@ def _names(items):
 
 @torch.no_grad()
 def _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method, rescore_reward, visual_size,
-            input_size, seed, with_alpha):
+            input_size, seed, with_alpha, progressive=False):
     """load_square -> prepare_image -> encoder -> batched search -> the winning hypothesis of every picture, all enqueued back to back"""
     from . import evaluation as E
     if int(max_gen_length) < 1:
         raise ValueError("visualize: max_gen_length >= 1 (the batched search)")
     dev = model.embedding.weight.device
     model.eval()
-    squares, status, index = _load_squares(items, visual_size, dev)
+    squares, status, index = _load_squares(items, visual_size, dev, progressive)
     img = prepare_image_batch(squares, input_size if input_size is not None else model.hp.get("input_size"))
     ann_bld, hw = model.encode(img)
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
@@ -186,23 +187,23 @@ def _read(model, sel, status, index):
 
 
 def visualize(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None, rescore_method=None,
-              rescore_reward=1.0, visual_size=256, input_size=None, power=5.0, opacity=0.75, seed=None):
+              rescore_reward=1.0, visual_size=256, input_size=None, power=5.0, opacity=0.75, seed=None, progressive=False):
     """``make_visual`` without the figure, for a batch: returns a ``Visual``.  ``input_size`` None: the model's ``input_size``.  The winning
     caption is the one ``SAT.caption(..., return_all=True)`` lists first (the highest rescored value; among hypotheses with the very same
     value this picks the first to finish).  Everything stays on the device until one read of tokens and scores."""
     squares, hw, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                              rescore_reward, visual_size, input_size, seed, True)
+                                              rescore_reward, visual_size, input_size, seed, True, progressive)
     panels = attention_panels(squares, sel["alphas"], sel["lengths"], hw, power, opacity)
     captions, words, scores, ppl, lengths = _read(model, sel, status, index)
     return Visual(captions, words, scores, ppl, lengths, panels, _names(items))
 
 
 def caption_image(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None):
+                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False):
     """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch, without panels:
     ``(captions, words, scores, perplexities)``, one entry per picture."""
     _, _, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, False)
+                                       rescore_reward, visual_size, input_size, seed, False, progressive)
     captions, words, scores, ppl, _ = _read(model, sel, status, index)
     return captions, words, scores, ppl
 

@@ -76,8 +76,9 @@ def measure(tf, staged, noise, iters):
     return with_copy_ms, time_ms(kernels, iters)
 
 
-def jpeg_rates(tf, files, iters, label):
-    """decode alone / decode + transform with and without the H2D copy, images/s; Pillow per host thread"""
+def jpeg_rates(tf, files, iters, label, pool_threads=0):
+    """decode alone / decode + transform with and without the H2D copy, images/s; Pillow per host thread, and with ``pool_threads``
+    also Pillow on that many threads at once (what a loader's workers make of files the GPU does not take)"""
     from sat_amd import jpeg as J
     dev = torch.device("cuda")
     B = len(files)
@@ -116,6 +117,18 @@ def jpeg_rates(tf, files, iters, label):
     for f in files[:n_cpu]:
         J.pillow_decode(f)
     cpu_s = (time.perf_counter() - t0) / n_cpu
+    pool = {}
+    if pool_threads:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(pool_threads) as ex:
+            list(ex.map(J.pillow_decode, files))                       # warm-up
+            rates = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                list(ex.map(J.pillow_decode, files))
+                rates.append(B / (time.perf_counter() - t0))
+        pool = {label + "pillow_decode_%dthreads_images_per_s" % pool_threads: dict(median=round(sorted(rates)[2], 1), min=round(min(rates), 1),
+                                                                                    max=round(max(rates), 1))}
     mb = sum(len(f) for f in files) / 1e6
     inf = info.cpu()
     par = inf[:, 0] == 1
@@ -126,7 +139,7 @@ def jpeg_rates(tf, files, iters, label):
             label + "decode_transform_ms": round(dt_ms, 3), label + "decode_transform_images_per_s": round(B / dt_ms * 1e3, 1),
             label + "decode_transform_with_h2d_ms": round(with_copy_ms, 3), label + "decode_transform_with_h2d_images_per_s": round(B / with_copy_ms * 1e3, 1),
             label + "compressed_MB": round(mb, 2), label + "h2d_bytes": int(staged.host.numel()), label + "segments": int(sum(jb.desc[j].n_segments for j in range(B))),
-            label + "pillow_decode_1thread_images_per_s": round(1.0 / cpu_s, 1), **paths}
+            label + "pillow_decode_1thread_images_per_s": round(1.0 / cpu_s, 1), **pool, **paths}
 
 
 def main_jpeg(a):
@@ -161,6 +174,15 @@ def main_jpeg(a):
             Image.fromarray(im).save(buf, "JPEG", quality=90, subsampling=2, **kw)
             return buf.getvalue()
         res["source"] = "%dx%d q90 4:2:0" % (H, W)
+        if a.progressive:                                     # the same pictures as progressive files, decoded on the GPU on request
+            from sat_amd import jpeg as J
+            res["source"] += " progressive"
+            for label, kw in (("progressive_", {}), ("progressive_rst_rows1_", dict(restart_marker_rows=1))):
+                files = [J.as_picture(enc(base[i % 8], progressive=True, **kw), progressive=True) for i in range(B)]
+                assert all(isinstance(f, J.JpegBytes) and f.header.progressive for f in files)
+                res.update(jpeg_rates(tf, files, a.iters, label, pool_threads=16))
+            print(json.dumps(res))
+            return
         res.update(jpeg_rates(tf, [enc(base[i % 8]) for i in range(B)], a.iters, ""))
         res.update(jpeg_rates(tf, [enc(base[i % 8], restart_marker_rows=1) for i in range(B)], a.iters, "rst_rows1_"))
     print(json.dumps(res))
@@ -178,8 +200,11 @@ def main():
     ap.add_argument("--subseq-bytes", type=int, default=None, help="with --jpeg: bytes per subsequence of a restart-free picture (default: the library's)")
     ap.add_argument("--parallel-min-bytes", type=int, default=None,
                     help="with --jpeg: least data bytes of a restart-free picture decoded by subsequences (default: the library's; 0 all; 2^63-1 none)")
+    ap.add_argument("--progressive", action="store_true",
+                    help="with --jpeg: encode the synthetic pictures progressively and decode them on the GPU (as_picture(progressive=True)); also "
+                         "times Pillow on 16 threads, which is what decodes such files without the option")
     a = ap.parse_args()
-    if a.jpeg or a.jpeg_dir:
+    if a.jpeg or a.jpeg_dir or a.progressive:
         return main_jpeg(a)
     H, W, S, B = 480, 640, a.size, a.batch
     rng = np.random.default_rng(0)

@@ -26,12 +26,12 @@ import sat_amd  # noqa: E402,F401
 from sat_amd import model as M  # noqa: E402
 
 
-def synthetic_jpeg(seed, h=480, w=640):
+def synthetic_jpeg(seed, h=480, w=640, **kw):
     rs = np.random.RandomState(seed)
     yy, xx = np.mgrid[0:h, 0:w]
     a = np.stack([xx * 255.0 / (w - 1), yy * 255.0 / (h - 1), ((xx + yy) % 128) * 2.0], -1) + rs.randint(-24, 25, (h, w, 3))
     buf = io.BytesIO()
-    Image.fromarray(np.clip(a, 0, 255).astype(np.uint8)).save(buf, format="JPEG", quality=90)
+    Image.fromarray(np.clip(a, 0, 255).astype(np.uint8)).save(buf, format="JPEG", quality=90, **kw)
     return buf.getvalue()
 
 
@@ -69,6 +69,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--progressive", action="store_true", help="progressive files, decoded on the GPU (visualize(progressive=True))")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_visualize.py measures on the GPU; there is no CPU path")
@@ -76,7 +77,7 @@ def main():
     torch.manual_seed(42)
     model = M.SAT(**hp).cuda().eval()
     model.set_precision(a.precision)
-    files = [synthetic_jpeg(i) for i in range(a.images)]
+    files = [synthetic_jpeg(i, progressive=a.progressive) for i in range(a.images)]
     kw = dict(beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN", rescore_reward=1.0)
     size = int(hp["input_size"])
 
@@ -84,7 +85,7 @@ def main():
         return [host_visual(model, f, kw, a.visual_size, size) for f in files[:a.host_images]]
 
     def path_b():
-        return model.visualize(files, visual_size=a.visual_size, input_size=size, **kw)
+        return model.visualize(files, visual_size=a.visual_size, input_size=size, progressive=a.progressive, **kw)
 
     ra, rb = path_a(), path_b()                          # warm-up; and the two paths' captions side by side
     same = sum(ra[i][0] == rb.captions[i] for i in range(len(ra)))
@@ -94,7 +95,7 @@ def main():
         rate["b"].append(len(files) / clock_s(path_b)[0])
     med = {k: statistics.median(v) for k, v in rate.items()}
     res = dict(images=a.images, host_images=a.host_images, beamk=a.beamk, max_gen_length=a.max_gen_length, visual_size=a.visual_size, input_size=size,
-               precision=a.precision, repeats=a.repeats, mean_caption_length=sum(rb.lengths) / len(rb.lengths),
+               precision=a.precision, repeats=a.repeats, progressive=a.progressive, mean_caption_length=sum(rb.lengths) / len(rb.lengths),
                host_loop_images_per_s=dict(median=med["a"], min=min(rate["a"]), max=max(rate["a"])),
                visualize_images_per_s=dict(median=med["b"], min=min(rate["b"]), max=max(rate["b"])), ratio=med["b"] / med["a"],
                captions_equal="%d of %d" % (same, len(ra)))
