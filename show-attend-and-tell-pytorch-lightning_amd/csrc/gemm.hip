@@ -354,6 +354,11 @@ int launch_gemm(const GemmArgs& g, hipStream_t st) {
     SAT_REQUIRE(g.M >= 0 && g.N >= 0 && g.K >= 0, "gemm: negative dims");
     if (g.M == 0 || g.N == 0) return SAT_OK;
     SAT_REQUIRE(g.A && g.B && g.C, "gemm: null operand");
+    // everything an epilogue or the split-K path dereferences is checked here, in front of the hand-off: the bf16 kernels take what passes
+    SAT_REQUIRE(g.epi >= EPI_NONE && g.epi <= EPI_BIAS_RELU, "gemm: epi %d outside 0..%d", g.epi, (int)EPI_BIAS_RELU);
+    if ((g.epi == EPI_BIAS || g.epi == EPI_BIAS_RELU) && !g.bias) return fail(SAT_EINVAL, "gemm: epilogue %d needs bias", g.epi);
+    if ((g.epi == EPI_ADD_TANH || g.epi == EPI_MUL_DTANH) && !g.e0) return fail(SAT_EINVAL, "gemm: epilogue %d needs e0", g.epi);
+    SAT_REQUIRE(g.slab_elems >= 0 && (g.slab || g.slab_elems == 0), "gemm: split-K slab of %ld elements at address %p", g.slab_elems, (void*)g.slab);
     if (g.bf16_mfma && gemm_bf16_eligible(g)) return launch_gemm_bf16(g, st);
     SAT_REQUIRE(!g.a_bf16 && !g.b_bf16 && !g.c_bf16, "gemm: bf16 operands need the bf16 MFMA kernel (16-byte gatherable shapes)");
     SAT_REQUIRE(!g.add_src, "gemm: add_src is a bf16-storage feature");
@@ -362,8 +367,6 @@ int launch_gemm(const GemmArgs& g, hipStream_t st) {
     k.C = (float*)g.C; k.ldc = g.ldc; k.c_rows = g.c_rows; k.M = g.M; k.N = g.N; k.K = g.K;
     k.accumulate = g.accumulate; k.epi = g.epi; k.bias = g.bias; k.e0 = g.e0; k.lde0 = g.lde0;
     k.c0 = g.c0; k.c1 = g.c1; k.g = g.g; k.slab = g.slab;
-    if ((g.epi == EPI_BIAS || g.epi == EPI_BIAS_RELU) && !g.bias) return fail(SAT_EINVAL, "gemm: bias epilogue without bias");
-    if ((g.epi == EPI_ADD_TANH || g.epi == EPI_MUL_DTANH) && !g.e0) return fail(SAT_EINVAL, "gemm: epilogue operand missing");
     const bool conv_a = (g.amode == A_CONV_FWD || g.amode == A_CONV_DGRAD);
     const bool conv_b = (g.bmode == B_CONV_WGRAD || g.bmode == B_CONV_DGRAD_W);
     if (conv_a || conv_b) {

@@ -388,8 +388,12 @@ static int launch_gemm_bf16_tile(const GemmArgs& g, int tile_mode, hipStream_t s
     int ktiles = cdiv(g.K, KB); if (ktiles < 1) ktiles = 1;
     int per = cdiv(ktiles, ns);
     k.kchunk = per * KB; k.nsplit = cdiv(ktiles, per);
+    // The staged bf16 write-out applies the epilogue function while it packs the tile and adds the old values in its write loop, i.e.
+    // f(acc) + C_old; the contract (gemm.h) is f(C_old + acc).  No launch of the step combines the two on a bf16 result (the accumulating
+    // data-gradient launches carry no epilogue, the biased forward launches do not accumulate), so such a request takes put() instead of
+    // paying for a second epilogue site in the write loop of every bf16 kernel.
     k.wide_store = (g.c_bf16 && !g.c_rows && k.nsplit == 1 && g.N % 8 == 0 && g.ldc % 8 == 0 && al16(g.C) &&
-                    (g.epi == EPI_NONE || g.epi == EPI_BIAS || g.epi == EPI_BIAS_RELU)) ? 1 : 0;
+                    (g.epi == EPI_NONE || ((g.epi == EPI_BIAS || g.epi == EPI_BIAS_RELU) && !g.accumulate))) ? 1 : 0;
     if (!g.c_bf16 && !g.c_rows && g.N % 4 == 0 && g.ldc % 4 == 0 && al16(g.C)) k.wide_store = 1;      // fp32 result (with split-K: of the reduce kernel)
     k.wide_slab = (k.nsplit > 1 && g.N % 4 == 0 && al16(g.slab)) ? 1 : 0;
     k.tile_stats = nullptr;
