@@ -279,6 +279,42 @@ int sat_caption_stats(const int32_t* cap_tokens, const int32_t* cap_len, int32_t
 int sat_caption_cosine(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
                        int32_t B, int32_t R, int32_t T, const float* embedding, int32_t V, int32_t m, float* best_cosine, void* stream);
 
+/* ------------------------------------------------------------------ CIDEr-D and ROUGE-L against a corpus of references
+ * (sat_amd/metrics.py is the specification: document_frequency, cider_d, rouge_l).  Reference (b, r) and hypothesis b are sliced as in
+ * sat_caption_stats; an "n-gram" is n = 1..4 consecutive tokens; the same limits and SAT_EINVAL messages apply, and a capacity that is
+ * not a power of two (or is above 2^36) is refused.  Tokens are clamped into [0, 65534] before they are packed: a vocabulary needs
+ * vocab_size <= 65535, and out-of-range input gives a wrong score, never a stray access.
+ *
+ * The document-frequency table is an open-addressing hash table (linear probing) in device memory that the caller allocates:
+ * sat_ngram_table_bytes(capacity) bytes = capacity 64-bit keys followed by capacity 32-bit counts.  A key packs an n-gram exactly:
+ * (token + 1) in 16 bits per position, the first token in the lowest bits, unused positions 0; the order n is implicit, different
+ * n-grams never share a key, key 0 is an empty slot.  count = df = the number of images added whose references contain the n-gram at
+ * least once, in any of the image's R references (duplicated references count once).  The content as a key -> count mapping does not
+ * depend on the order in which images arrive; slot positions may differ from run to run.
+ *   sat_ngram_table_clear   empties the table (a launch; call it before the first add)
+ *   sat_ngram_table_add     adds B images, one launch (may be called again and again; launches on one stream are ordered).  A full table
+ *                           sets *error_flag (device int32, zeroed by the caller) to non-zero and drops the n-gram; the probe loop is
+ *                           bounded by the capacity and the launch always completes.  The caller keeps the number of images added.
+ *   sat_caption_consensus   scores (B, 2) float64 = [CIDEr-D, ROUGE-L] per image against a table holding n_images images, in a LATER
+ *                           launch than the adds.  All arithmetic in fp64, every sum in a fixed order: the same table content gives
+ *                           bit-identical scores.
+ * CIDEr-D (sigma = 6 in the COCO scorer): with logN = log(n_images), every distinct n-gram g of a sentence s with term frequency tf
+ * weighs w_s[g] = tf * (logN - log(max(1, df[g]))); norm_s[n] = sqrt(sum w^2); len_s = max(len - 1, 0) (the number of bigram
+ * positions: the scorer's quirk).  For hypothesis h and reference r, val[n] = sum over g in h of min(w_h[g], w_r[g]) * w_r[g], divided
+ * by norm_h[n] * norm_r[n] if both are non-zero, times exp(-(len_h - len_r)^2 / (2 sigma^2)); the image scores
+ * 10 * mean over n of (sum over r of val[n]) / R.  n_images = 1 gives 0; an n-gram of every image weighs 0; an n-gram of no reference
+ * has df 0 and weighs tf * logN.
+ * ROUGE-L (beta = 1.2): p = max over r of LCS(r, h) / len(h), q = max over r of LCS(r, h) / len(r) (an empty reference gives 0);
+ * (1 + beta^2) p q / (q + beta^2 p) if both are non-zero, else 0; an empty hypothesis scores 0. */
+#define SAT_NGRAM_TABLE_MAX_CAPACITY (1LL << 36)
+size_t sat_ngram_table_bytes(int64_t capacity);   /* 0 (and a message) for a refused capacity */
+int sat_ngram_table_clear(void* table, int64_t capacity, void* stream);
+int sat_ngram_table_add(const int32_t* refs, const int32_t* ref_lengths, int32_t B, int32_t R, int32_t T, void* table, int64_t capacity,
+                        int32_t* error_flag, void* stream);
+int sat_caption_consensus(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
+                          int32_t B, int32_t R, int32_t T, const void* table, int64_t capacity, int64_t n_images, double sigma,
+                          double* scores /* (B, 2) */, void* stream);
+
 /* out[c] = sum_r x[r*ld + c] in a fixed order (bias gradients).  scratch: ceil(rows/256)*cols floats */
 int sat_colsum(const float* x, int64_t ld, int64_t rows, int32_t cols, float* out, float* scratch, void* stream);
 

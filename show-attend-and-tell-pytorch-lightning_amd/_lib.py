@@ -306,6 +306,12 @@ SYMBOLS.update({          # scoring decoded captions on the device (evaluation.p
     "sat_caption_stats": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "sat_caption_cosine": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
 })
+SYMBOLS.update({          # CIDEr-D / ROUGE-L against a reference corpus (evaluation.ReferenceCorpus, consensus_scores)
+    "sat_ngram_table_bytes": (C.c_size_t, [_i64]),
+    "sat_ngram_table_clear": (C.c_int, [_vp, _i64, _vp]),
+    "sat_ngram_table_add": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "sat_caption_consensus": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.c_double, _vp, _vp]),
+})
 SYMBOLS.update({          # attention overlays (visualize.py)
     "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
     "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),

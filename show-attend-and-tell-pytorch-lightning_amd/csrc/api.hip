@@ -226,6 +226,41 @@ int sat_caption_cosine(const int32_t* cap_tokens, const int32_t* cap_len, int32_
     if (m > SAT_CAPTION_MAX_EMBED) return fail(SAT_EINVAL, "caption_cosine: embedding width %d is over the limit %d", m, SAT_CAPTION_MAX_EMBED);
     return caption_cosine(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, embedding, V, m, best_cosine, (hipStream_t)stream);
 }
+size_t sat_ngram_table_bytes(int64_t capacity) {
+    if (capacity < 1 || (capacity & (capacity - 1)) || capacity > SAT_NGRAM_TABLE_MAX_CAPACITY) {
+        fail(SAT_EINVAL, "ngram_table_bytes: capacity %lld is not a power of two in [1, 2^%d]", (long long)capacity, 36);
+        return 0;
+    }
+    return ngram_table_bytes((long)capacity);
+}
+static int check_table(const char* what, const void* table, int64_t capacity) {
+    if (!table) return fail(SAT_EINVAL, "%s: null pointer", what);
+    if (capacity < 1 || (capacity & (capacity - 1)) || capacity > SAT_NGRAM_TABLE_MAX_CAPACITY)
+        return fail(SAT_EINVAL, "%s: capacity %lld is not a power of two in [1, 2^%d]", what, (long long)capacity, 36);
+    return SAT_OK;
+}
+int sat_ngram_table_clear(void* table, int64_t capacity, void* stream) {
+    SAT_TRY(check_table("ngram_table_clear", table, capacity));
+    return ngram_table_clear(table, (long)capacity, (hipStream_t)stream);
+}
+int sat_ngram_table_add(const int32_t* refs, const int32_t* ref_lengths, int32_t B, int32_t R, int32_t T, void* table, int64_t capacity,
+                        int32_t* error_flag, void* stream) {
+    if (!refs || !ref_lengths || !error_flag) return fail(SAT_EINVAL, "ngram_table_add: null pointer");
+    SAT_TRY(check_table("ngram_table_add", table, capacity));
+    SAT_TRY(check_caption_sizes("ngram_table_add", 1, B, R, T));
+    return ngram_table_add(refs, ref_lengths, B, R, T, table, (long)capacity, error_flag, (hipStream_t)stream);
+}
+int sat_caption_consensus(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
+                          int32_t B, int32_t R, int32_t T, const void* table, int64_t capacity, int64_t n_images, double sigma, double* scores,
+                          void* stream) {
+    if (!cap_tokens || !cap_len || !refs || !ref_lengths || !scores) return fail(SAT_EINVAL, "caption_consensus: null pointer");
+    SAT_TRY(check_table("caption_consensus", table, capacity));
+    SAT_TRY(check_caption_sizes("caption_consensus", cap_width, B, R, T));
+    if (n_images < 1) return fail(SAT_EINVAL, "caption_consensus: n_images %lld (the table holds no image)", (long long)n_images);
+    if (!(sigma > 0.0)) return fail(SAT_EINVAL, "caption_consensus: sigma %g is not positive", sigma);
+    return caption_consensus(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, table, (long)capacity, (long)n_images, sigma, scores,
+                             (hipStream_t)stream);
+}
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids, int32_t n_masked,
                     const float* parent_scores, float* scores, void* stream) {
     if (!logits || !scores || (n_masked > 0 && !masked_ids)) return fail(SAT_EINVAL, "beam_scores: null pointer");

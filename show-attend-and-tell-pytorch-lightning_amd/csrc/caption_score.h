@@ -12,4 +12,10 @@ int beam_select(const int* tok_in, const int* prev_row, const int* fin_count, co
 int caption_stats(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, int* stats, hipStream_t st);
 int caption_cosine(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, const float* embedding,
                    int V, int m, float* best, hipStream_t st);
+// caption_consensus.hip: the n-gram document-frequency table and CIDEr-D / ROUGE-L against it
+size_t ngram_table_bytes(long capacity);
+int ngram_table_clear(void* table, long capacity, hipStream_t st);
+int ngram_table_add(const int* refs, const int* ref_len, int B, int R, int T, void* table, long capacity, int* error_flag, hipStream_t st);
+int caption_consensus(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, const void* table,
+                      long capacity, long n_images, double sigma, double* scores, hipStream_t st);
 }  // namespace sat

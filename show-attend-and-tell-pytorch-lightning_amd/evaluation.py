@@ -10,6 +10,11 @@ best mean-embedding cosine (csrc/caption_score.hip); what reaches the host is on
 * ``evaluate``          a loader's batches: the notebook's mean of per-batch metrics AND the corpus-level score of the whole split
                         (dev/todo.txt: "add the val_epoch_end, sum the nom/dem"), read from the device once at the end;
 * ``random_search``     the notebook's random search over decode parameters, same draws in the same order.
+
+Opt-in, ``corpus=ReferenceCorpus``: CIDEr-D and ROUGE-L (csrc/caption_consensus.hip; ``metrics.cider_d`` / ``metrics.rouge_l`` are the
+specification).  The document frequency of every 1..4-gram of a split's references is built once into a hash table on the device
+(``ReferenceCorpus``) and stays there; ``consensus_scores`` scores a batch against it in the same enqueue as the statistics above, and
+``val_batch_stats`` / ``evaluate`` / ``random_search`` carry the two sums along.  Without ``corpus`` nothing changes.
 """
 import numpy as np
 import torch
@@ -82,6 +87,120 @@ def caption_statistics(tokens, lengths, refs, ref_lengths, embedding):
     return stats, best
 
 
+CONSENSUS_KEYS = ("cider", "rouge_l")
+MAX_VOCAB = 65535          # an n-gram key holds (token + 1) in 16 bits per position (include/sat_hip.h)
+
+
+def _pow2_at_least(x):
+    return 1 << max(0, int(x) - 1).bit_length()
+
+
+class ReferenceCorpus:
+    """The n-gram document-frequency table of a split's references on the device (include/sat_hip.h, sat_ngram_table_add).
+
+    ``capacity``: slots of the hash table, a power of two, honoured as given; by default the smallest power of two >= 2 x the n-gram
+    positions announced by ``expected_positions`` (the constructor's, or ``from_dataset``'s count; 2^16 positions when none is
+    announced).  The table is allocated at the first ``add`` (or ``clear``); every ``add`` is one launch.  ``images`` is a host int;
+    ``check()`` is the one host read."""
+
+    DEFAULT_POSITIONS = 1 << 16
+
+    def __init__(self, vocab_size, capacity=None, device="cuda", expected_positions=None):
+        if int(vocab_size) < 1 or int(vocab_size) > MAX_VOCAB:
+            raise ValueError("ReferenceCorpus: vocab_size=%d (1..%d: an n-gram key holds token + 1 in 16 bits per position)" % (vocab_size, MAX_VOCAB))
+        if capacity is not None and (int(capacity) < 1 or int(capacity) & (int(capacity) - 1)):
+            raise ValueError("ReferenceCorpus: capacity=%d is not a power of two" % capacity)
+        self.vocab_size, self.device, self.images = int(vocab_size), torch.device(device), 0
+        self.capacity = int(capacity) if capacity is not None else _pow2_at_least(2 * int(expected_positions or self.DEFAULT_POSITIONS))
+        self._table = self._flag = None
+
+    def _allocate(self):
+        if self.device.type != "cuda":
+            raise L.SatHipError("sat_amd computes on the GPU only: ReferenceCorpus on %s (no CPU fallback)" % self.device)
+        nbytes = L.lib().sat_ngram_table_bytes(self.capacity)
+        if nbytes == 0:
+            L.check(1, "sat_ngram_table_bytes")
+        self._table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._flag = torch.empty(1, dtype=torch.int32, device=self.device)
+
+    def clear(self):
+        """empties the table and the error flag (launches only; the first call allocates): the corpus holds no image again"""
+        if self._table is None:
+            self._allocate()
+        L.check(L.lib().sat_ngram_table_clear(L.ptr(self._table), self.capacity, L.stream_ptr()), "sat_ngram_table_clear")
+        self._flag.zero_()
+        self.images = 0
+        return self
+
+    def add(self, refs, ref_lengths):
+        """the references ``refs (B, R, T)`` / ``ref_lengths (B, R)`` (any integer dtype, device or host) of B more images: one launch"""
+        if self._table is None:
+            self.clear()
+        refs = torch.as_tensor(refs).to(device=self.device, dtype=torch.int32).contiguous()
+        ref_lengths = torch.as_tensor(ref_lengths).to(device=self.device, dtype=torch.int32).contiguous()
+        B, R, T = refs.shape
+        assert tuple(ref_lengths.shape) == (B, R), "ref_lengths is (B, R)"
+        L.check(L.lib().sat_ngram_table_add(L.ptr(refs), L.ptr(ref_lengths), B, R, T, L.ptr(self._table), self.capacity, L.ptr(self._flag),
+                                            L.stream_ptr()), "sat_ngram_table_add")
+        self.images += B
+        return self
+
+    @staticmethod
+    def positions(lengths):
+        """the number of (n, position) pairs, n = 1..4, of references ``c[1:l]`` with the given stored lengths ``l``"""
+        l = torch.as_tensor(lengths).to(torch.int64).reshape(-1).clamp(min=1) - 1
+        return int(sum((l - n).clamp(min=0).sum() for n in range(4)))
+
+    @classmethod
+    def from_dataset(cls, ds, vocab_size=None, capacity=None, device="cuda", chunk=1024):
+        """the corpus of ``ds.encoded_captions (N, R, T)`` / ``ds.lengths (N, R)``, fed in chunks of ``chunk`` images; no image is touched"""
+        caps, lens = torch.as_tensor(ds.encoded_captions), torch.as_tensor(ds.lengths)
+        if vocab_size is None:
+            vocab_size = len(ds.vocab_stoi) if hasattr(ds, "vocab_stoi") else int(caps.max()) + 1
+        rc = cls(vocab_size, capacity, device, expected_positions=cls.positions(lens))
+        for i in range(0, caps.shape[0], int(chunk)):
+            rc.add(caps[i:i + chunk], lens[i:i + chunk])
+        return rc
+
+    def check(self):
+        """reads the error flag (the one host read): raises if an ``add`` found the table full and dropped n-grams"""
+        if self._flag is not None and int(self._flag.item()) != 0:
+            raise L.SatHipError("ReferenceCorpus: the table overflowed (capacity %d): document frequencies are incomplete; "
+                                "rebuild with a larger capacity" % self.capacity)
+        return self
+
+    def to_dict(self):
+        """``{n-gram tuple: document frequency}`` on the host (tests, debugging)"""
+        if self._table is None:
+            return {}
+        host = self._table.cpu().numpy()
+        keys = host[:8 * self.capacity].view(np.uint64)
+        counts = host[8 * self.capacity:].view(np.uint32)
+        out = {}
+        for k, c in zip(keys[keys != 0].tolist(), counts[keys != 0].tolist()):
+            gram = []
+            while k:
+                gram.append((k & 0xFFFF) - 1); k >>= 16
+            out[tuple(gram)] = c
+        return out
+
+
+def consensus_scores(tokens, lengths, refs, ref_lengths, corpus, sigma=6.0):
+    """``(B, 2)`` float64 on the device, ``[CIDEr-D, ROUGE-L]`` per image, of hypotheses ``tokens (B, W)`` / ``lengths (B)`` against
+    ``refs (B, R, T)`` / ``ref_lengths (B, R)`` (int32, on the device) with the document frequencies of ``corpus``."""
+    L.require_gpu(tokens, lengths, refs, ref_lengths)
+    for t in (tokens, lengths, refs, ref_lengths):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    if corpus.images < 1 or corpus._table is None:
+        raise ValueError("consensus_scores: the corpus holds no image (ReferenceCorpus.add)")
+    B, W = tokens.shape
+    _, R, T = refs.shape
+    scores = torch.empty(B, 2, dtype=torch.float64, device=tokens.device)
+    L.check(L.lib().sat_caption_consensus(L.ptr(tokens), L.ptr(lengths), W, L.ptr(refs), L.ptr(ref_lengths), B, R, T, L.ptr(corpus._table),
+                                          corpus.capacity, corpus.images, float(sigma), L.ptr(scores), L.stream_ptr()), "sat_caption_consensus")
+    return scores
+
+
 def metrics_from_sums(counts, cosine_sum, perplexity_sum, images):
     """the seven keys of ``score_captions`` from host numbers: 12 summed integers, two float sums, the image count"""
     counts = [int(c) for c in counts]
@@ -92,30 +211,45 @@ def metrics_from_sums(counts, cosine_sum, perplexity_sum, images):
     return out
 
 
+def metrics_from_vector(v, images):
+    """``metrics_from_sums`` of a host ``CaptionStats.vector()``: 14 numbers, or 16 with the CIDEr-D and ROUGE-L sums (means over images)"""
+    out = metrics_from_sums(v[:12], v[12], v[13], images)
+    if len(v) > 14:
+        out["cider"], out["rouge_l"] = float(v[14]) / images, float(v[15]) / images
+    return out
+
+
 class CaptionStats:
     """Sums over images: ``counts`` (12,) int64 (the columns of sat_caption_stats), ``cosine_sum`` / ``perplexity_sum`` (float64
-    scalars) on the device, ``images`` a host int.  ``a + b`` adds; ``metrics()`` reads the device once."""
+    scalars) on the device, ``images`` a host int; scored against a ``ReferenceCorpus`` also ``consensus_sum`` (2,) float64, the sums of
+    CIDEr-D and ROUGE-L.  ``a + b`` adds; ``metrics()`` reads the device once."""
 
-    def __init__(self, counts, cosine_sum, perplexity_sum, images):
+    def __init__(self, counts, cosine_sum, perplexity_sum, images, consensus_sum=None):
         self.counts, self.cosine_sum, self.perplexity_sum, self.images = counts, cosine_sum, perplexity_sum, int(images)
+        self.consensus_sum = consensus_sum
 
     def __add__(self, other):
+        if (self.consensus_sum is None) != (other.consensus_sum is None):
+            raise ValueError("CaptionStats: one side was scored against a ReferenceCorpus and the other was not")
         return CaptionStats(self.counts + other.counts, self.cosine_sum + other.cosine_sum, self.perplexity_sum + other.perplexity_sum,
-                            self.images + other.images)
+                            self.images + other.images, None if self.consensus_sum is None else self.consensus_sum + other.consensus_sum)
 
     def vector(self):
-        """(14,) float64 on the device: the counts (exact below 2^53), then the two sums"""
-        return torch.cat([self.counts.to(torch.float64), self.cosine_sum.reshape(1), self.perplexity_sum.reshape(1)])
+        """(14,) float64 on the device: the counts (exact below 2^53), then the two sums; (16,) with the CIDEr-D and ROUGE-L sums"""
+        parts = [self.counts.to(torch.float64), self.cosine_sum.reshape(1), self.perplexity_sum.reshape(1)]
+        if self.consensus_sum is not None:
+            parts.append(self.consensus_sum.reshape(2))
+        return torch.cat(parts)
 
     def metrics(self):
-        v = self.vector().cpu().tolist()
-        return metrics_from_sums(v[:12], v[12], v[13], self.images)
+        return metrics_from_vector(self.vector().cpu().tolist(), self.images)
 
 
 @torch.no_grad()
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
-    """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back."""
+                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None):
+    """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
+    with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue."""
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
     tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
@@ -123,14 +257,18 @@ def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, s
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())
-    return CaptionStats(stats.sum(0, dtype=torch.int64), best.sum(dtype=torch.float64), ppl.sum(dtype=torch.float64), tokens.shape[0])
+    consensus = None if corpus is None else consensus_scores(tokens, lens, refs, ref_lengths, corpus).sum(0)
+    return CaptionStats(stats.sum(0, dtype=torch.int64), best.sum(dtype=torch.float64), ppl.sum(dtype=torch.float64), tokens.shape[0], consensus)
 
 
-def evaluate(model, loader, max_batches=None, seed=None, **decode):
+def evaluate(model, loader, max_batches=None, seed=None, corpus=None, **decode):
     """``val_batch_stats`` over the batches of ``loader`` (at most ``max_batches``).  Returns ``{"batch_mean": the notebook's protocol,
     the plain mean of the per-batch metric dicts, "corpus": BLEU / GLEU taken once from the statistics summed over every image (cosine and
     perplexity: means over images), "batches", "images"}``.  The per-batch statistics stay on the device and are read once at the end.
-    ``seed``: batch i of a sampled search draws with ``seed + i``."""
+    ``seed``: batch i of a sampled search draws with ``seed + i``.  ``corpus`` (a ``ReferenceCorpus``): both dicts gain "cider" and
+    "rouge_l" (means over images); still one host read."""
+    if corpus is not None:
+        decode["corpus"] = corpus
     vecs, images = [], []
     for i, batch in enumerate(loader):
         if max_batches is not None and i >= max_batches:
@@ -140,11 +278,11 @@ def evaluate(model, loader, max_batches=None, seed=None, **decode):
     if not vecs:
         raise ValueError("evaluate: the loader gave no batch")
     rows = torch.stack(vecs).cpu().tolist()                                  # the one host read
-    per_batch = [metrics_from_sums(r[:12], r[12], r[13], n) for r, n in zip(rows, images)]
-    total = [sum(int(r[c]) for r in rows) for c in range(12)]
-    corpus = metrics_from_sums(total, sum(r[12] for r in rows), sum(r[13] for r in rows), sum(images))
-    return {"batch_mean": {k: sum(d[k] for d in per_batch) / len(per_batch) for k in METRIC_KEYS}, "corpus": corpus, "batches": len(per_batch),
-            "images": sum(images)}
+    per_batch = [metrics_from_vector(r, n) for r, n in zip(rows, images)]
+    total = [sum(int(r[c]) for r in rows) for c in range(12)] + [sum(r[c] for r in rows) for c in range(12, len(rows[0]))]
+    keys = METRIC_KEYS + (CONSENSUS_KEYS if len(rows[0]) > 14 else ())
+    return {"batch_mean": {k: sum(d[k] for d in per_batch) / len(per_batch) for k in keys}, "corpus": metrics_from_vector(total, sum(images)),
+            "batches": len(per_batch), "images": sum(images)}
 
 
 def draw_decode_params(rs, space=NOTEBOOK_SPACE):
@@ -159,16 +297,20 @@ def draw_decode_params(rs, space=NOTEBOOK_SPACE):
             "rescore_method": str(rescore_method), "rescore_reward": float(rescore_reward)}
 
 
-def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4):
+def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4, corpus=None):
     """evaluate.ipynb's random search: ``trials`` draws from one ``np.random.RandomState(seed)``, each scored over the first
-    ``max_batches`` batches.  Rows carry the notebook's 13 columns (the metrics are its batch means) plus ``<metric>_corpus``."""
+    ``max_batches`` batches.  Rows carry the notebook's 13 columns (the metrics are its batch means) plus ``<metric>_corpus``; with
+    ``corpus`` (a ``ReferenceCorpus``, built once and reused by every trial) also cider, rouge_l, cider_corpus, rouge_l_corpus."""
     rs = np.random.RandomState(seed)
     rows = []
     for trial in range(int(trials)):
         row = draw_decode_params(rs, space)
         res = evaluate(model, loader, max_batches=max_batches, seed=None if seed is None else (int(seed) * 1000003 + trial) % (2 ** 62),
-                       max_gen_length=space["max_gen_length"], **row)
-        row.update(res["batch_mean"])
-        row.update({k + "_corpus": v for k, v in res["corpus"].items()})
+                       max_gen_length=space["max_gen_length"], **row, **({} if corpus is None else {"corpus": corpus}))
+        row.update({k: res["batch_mean"][k] for k in METRIC_KEYS})
+        row.update({k + "_corpus": res["corpus"][k] for k in METRIC_KEYS})
+        if corpus is not None:
+            row.update({k: res["batch_mean"][k] for k in CONSENSUS_KEYS})
+            row.update({k + "_corpus": res["corpus"][k] for k in CONSENSUS_KEYS})
         rows.append(row)
     return rows

@@ -110,3 +110,89 @@ def bleu_from_stats(clipped, total, hyp_len, ref_len, weights=(0.25, 0.25, 0.25,
 def gleu_from_stats(tp, total):
     """The tail of ``corpus_gleu``: matches and totals of each segment's best reference, summed over the corpus."""
     return 0.0 if int(total) == 0 else int(tp) / int(total)
+
+
+# ----------------------------------------------------------------------------- consensus metrics: CIDEr-D and ROUGE-L
+# The two COCO caption metrics that need nothing but tokens, restated from the published algorithms (Vedantam et al. 2015, the
+# "CIDEr-D" of the COCO evaluation server with sigma = 6; Lin 2004, ROUGE-L as the COCO scorer takes it, beta = 1.2) over token-id
+# lists.  They are the specification of sat_ngram_table_add / sat_caption_consensus (csrc/caption_consensus.hip): plain dictionaries,
+# fp64.  A reference here is the token list without START and END, as everywhere in this file.
+
+def document_frequency(list_of_references):
+    """``{n-gram tuple: number of images whose references contain it}`` over all 1..4-grams.  An image counts once, however often and
+    in however many of its references the n-gram occurs."""
+    df = Counter()
+    for references in list_of_references:
+        seen = set()
+        for ref in references:
+            for n in range(1, 5):
+                seen.update(_ngrams(ref, n))
+        df.update(seen)
+    return dict(df)
+
+
+def _cider_vector(seq, df, log_n):
+    """per order n = 1..4: ``{n-gram: tf * (log N - log max(1, df))}`` in first-occurrence order, its norm, and the scorer's length
+    (the number of bigram positions)"""
+    vec, norm = [], []
+    for n in range(1, 5):
+        tf = Counter(_ngrams(seq, n))
+        w = {g: float(c) * (log_n - math.log(max(1.0, float(df.get(g, 0))))) for g, c in tf.items()}
+        vec.append(w)
+        norm.append(math.sqrt(sum(x * x for x in w.values())))
+    return vec, norm, max(len(seq) - 1, 0)
+
+
+def cider_d(list_of_references, hypotheses, df=None, n_images=None, sigma=6.0):
+    """CIDEr-D of every image as the COCO scorer computes it (a list; the corpus score is its mean).  ``df`` / ``n_images``: the
+    document frequencies and the image count of the corpus the weights come from; by default those of ``list_of_references`` itself."""
+    assert len(list_of_references) == len(hypotheses), "one reference set per hypothesis"
+    if df is None:
+        df = document_frequency(list_of_references)
+        if n_images is None:
+            n_images = len(list_of_references)
+    if n_images is None or int(n_images) < 1:
+        raise ValueError("cider_d: n_images >= 1 goes with an explicit df")
+    log_n = math.log(float(int(n_images)))
+    scores = []
+    for references, hypothesis in zip(list_of_references, hypotheses):
+        vec_h, norm_h, len_h = _cider_vector(hypothesis, df, log_n)
+        total = [0.0] * 4
+        for ref in references:
+            vec_r, norm_r, len_r = _cider_vector(ref, df, log_n)
+            delta = float(len_h - len_r)
+            for n in range(4):
+                val = 0.0
+                for g, wh in vec_h[n].items():
+                    wr = vec_r[n].get(g, 0.0)
+                    val += min(wh, wr) * wr
+                if norm_h[n] != 0 and norm_r[n] != 0:
+                    val /= norm_h[n] * norm_r[n]
+                total[n] += val * math.exp(-(delta * delta) / (2.0 * sigma * sigma))
+        scores.append(10.0 * ((((total[0] + total[1]) + total[2]) + total[3]) / 4.0 / len(references)) if references else 0.0)
+    return scores
+
+
+def lcs_length(a, b):
+    """length of the longest common subsequence"""
+    row = [0] * (len(b) + 1)
+    for x in a:
+        diag = 0
+        for j, y in enumerate(b):
+            diag, row[j + 1] = row[j + 1], (diag + 1 if x == y else max(row[j + 1], row[j]))
+    return row[len(b)]
+
+
+def rouge_l(references, hypothesis, beta=1.2):
+    """ROUGE-L of one image in the COCO scorer's form: the best LCS precision and the best LCS recall over the references (each its
+    own maximum), F with beta = 1.2.  An empty hypothesis scores 0; an empty reference contributes 0."""
+    if len(hypothesis) == 0:
+        return 0.0
+    prec = rec = 0.0
+    for ref in references:
+        lcs = lcs_length(ref, hypothesis)
+        prec = max(prec, lcs / float(len(hypothesis)))
+        rec = max(rec, lcs / float(len(ref)) if len(ref) else 0.0)
+    if prec != 0 and rec != 0:
+        return ((1 + beta ** 2) * prec * rec) / float(rec + beta ** 2 * prec)
+    return 0.0

@@ -664,11 +664,12 @@ class SAT(SATDecoder, _Base):
                                          rescore_reward, seed, graph)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
-        """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict"""
+                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None):
+        """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
+        (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                          rescore_reward, seed, graph)
+                                          rescore_reward, seed, graph, corpus)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, **render):

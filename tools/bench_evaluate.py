@@ -5,7 +5,11 @@ process and in alternating rounds, through
   (b) ``SAT.val_batch_stats``  selection, statistics and cosine on the device; one host read per trial (``evaluation.evaluate``).
 hipEvent timing of whole trials after a warm-up trial of each; median (min - max) of --repeats, reported per batch.  Path (a) is also
 split, by host clocks around synchronised sections of one more trial, into encoder, search, read-back + back-trace and score_captions.
+--cider measures instead what CIDEr-D and ROUGE-L cost at beam 5: the per-batch time of ``val_batch_stats`` without and with
+``corpus=`` (alternating rounds, hipEvents), the host clock of ``metrics.cider_d`` + ``metrics.rouge_l`` on the same tokens (already
+on the host as lists: the read-back is not counted), and the one-off build of the document-frequency table for --split-images images.
     python tools/bench_evaluate.py [--beams 5 20] [--batches 4] [--images 128] [--repeats 5] [--precision bf16] [--json]
+    python tools/bench_evaluate.py --cider [--split-images 5000] [--batches 4] [--images 128] [--repeats 5] [--json]
 """
 import argparse
 import json
@@ -21,6 +25,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import sat_amd  # noqa: E402,F401
 from sat_amd import evaluation as E  # noqa: E402
+from sat_amd import metrics  # noqa: E402
 from sat_amd import model as M  # noqa: E402
 
 
@@ -38,6 +43,71 @@ def clock_ms(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+def bench_cider(a, model, batches, hp, T, R):
+    """--cider: val_batch_stats without / with corpus, the host scorer on the same tokens, the table build"""
+    kw = dict(beamk=5, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
+    n_chunks = max(1, a.split_images // a.images)
+    split = [bench.synthetic_batch(a.images, R, T, hp["vocab_size"], 500 + i, ragged=True, px=8)[1:] for i in range(n_chunks)]
+    split = [(c.cuda(), l.cuda()) for c, l in split]
+    positions = sum(E.ReferenceCorpus.positions(l) for _, l in split)
+
+    def build():
+        rc = E.ReferenceCorpus(hp["vocab_size"], expected_positions=positions)
+        for c, l in split:
+            rc.add(c, l)
+        return rc
+
+    build().check()                                      # warm-up: code objects, allocator
+    build_ms = [event_ms(build)[0] for _ in range(a.repeats)]
+    rc = build().check()
+
+    def plain():
+        return E.evaluate(model, batches, **kw)
+
+    def with_corpus():
+        return E.evaluate(model, batches, corpus=rc, **kw)
+
+    def host():
+        out = []
+        for img, caps, lengths in batches:
+            tok, ln, _, _ = model.caption_tokens(img, **kw)
+            hyps = [t[:n] for t, n in zip(tok.tolist(), ln.tolist())]
+            refs = [[c[1:n] for c, n in zip(cs, ns)] for cs, ns in zip(caps.tolist(), lengths.tolist())]
+            t0 = time.perf_counter()
+            df = host.df
+            c = metrics.cider_d(refs, hyps, df=df, n_images=rc.images)
+            r = [metrics.rouge_l(rf, h) for rf, h in zip(refs, hyps)]
+            out.append(((time.perf_counter() - t0) * 1e3, sum(c) / len(c), sum(r) / len(r)))
+        return out
+
+    host.df = rc.to_dict()
+    plain(); got = with_corpus(); want = host()
+    torch.cuda.synchronize()
+    ms = {"plain": [], "corpus": []}
+    for _ in range(a.repeats):                           # alternating rounds
+        ms["plain"].append(event_ms(plain)[0] / a.batches)
+        ms["corpus"].append(event_ms(with_corpus)[0] / a.batches)
+    host_ms = [statistics.median(t for t, _, _ in host()) for _ in range(a.repeats)]
+    res = dict(beamk=5, images=a.images, references=R, batches=a.batches, repeats=a.repeats, precision=a.precision, split_images=rc.images,
+               table_capacity=rc.capacity, distinct_ngrams=len(host.df),
+               val_batch_stats_ms_per_batch=dict(median=statistics.median(ms["plain"]), min=min(ms["plain"]), max=max(ms["plain"])),
+               val_batch_stats_corpus_ms_per_batch=dict(median=statistics.median(ms["corpus"]), min=min(ms["corpus"]), max=max(ms["corpus"])),
+               host_cider_rouge_ms_per_batch=dict(median=statistics.median(host_ms), min=min(host_ms), max=max(host_ms)),
+               table_build_ms=dict(median=statistics.median(build_ms), min=min(build_ms), max=max(build_ms)),
+               cider_device=got["batch_mean"]["cider"], cider_host=sum(c for _, c, _ in want) / len(want),
+               rouge_l_device=got["batch_mean"]["rouge_l"], rouge_l_host=sum(r for _, _, r in want) / len(want))
+    if a.json:
+        print(json.dumps(res))
+        return
+    print("beam 5, %d batches of %d images x %d references, %s; corpus of %d images, %d distinct n-grams in %d slots" %
+          (a.batches, a.images, R, a.precision, rc.images, len(host.df), rc.capacity))
+    for name, key in (("val_batch_stats", "val_batch_stats_ms_per_batch"), ("val_batch_stats(corpus=)", "val_batch_stats_corpus_ms_per_batch"),
+                      ("host cider_d + rouge_l (tokens already on the host)", "host_cider_rouge_ms_per_batch"), ("table build, once per split", "table_build_ms")):
+        print("  %-52s %8.3f ms (min %.3f, max %.3f)" % (name, res[key]["median"], res[key]["min"], res[key]["max"]))
+    print("  CIDEr-D device %.12f host %.12f; ROUGE-L device %.12f host %.12f" %
+          (res["cider_device"], res["cider_host"], res["rouge_l_device"], res["rouge_l_host"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beams", type=int, nargs="+", default=[5, 20])
@@ -47,6 +117,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--cider", action="store_true", help="measure CIDEr-D / ROUGE-L: val_batch_stats with and without corpus=, the host scorer, the build")
+    ap.add_argument("--split-images", type=int, default=5000, help="--cider: images in the corpus the table is built from")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_evaluate.py measures on the GPU; there is no CPU path")
@@ -58,6 +130,8 @@ def main():
     for i in range(a.batches):
         img, caps, lengths = bench.synthetic_batch(a.images, R, T, hp["vocab_size"], 100 + i, ragged=True, px=hp["input_size"])
         batches.append((img.cuda(), caps.cuda(), lengths.cuda()))
+    if a.cider:
+        return bench_cider(a, model, batches, hp, T, R)
     for beamk in a.beams:
         kw = dict(beamk=beamk, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
 

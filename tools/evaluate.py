@@ -2,9 +2,11 @@
 parameters and metrics out.  Without --trials: one pass over the split at the given decode parameters, printing the notebook's mean
 of per-batch metrics and the corpus-level score of the whole split.  With --trials N: the notebook's random search (N draws from its
 parameter ranges, each scored over the first --max-batches batches), written as csv with its 13 columns plus ``<metric>_corpus``.
+--cider: CIDEr-D and ROUGE-L as well; the n-gram document frequencies of the evaluated split are built once on the device
+(``evaluation.ReferenceCorpus``) and every batch and trial is scored against them (columns cider, rouge_l, cider_corpus, rouge_l_corpus).
 All work is in sat_amd/evaluation.py: a batch is decoded and scored on the device, one host read per pass.
     python tools/evaluate.py CHECKPOINT [--json DATASET.json] [--root IMAGE_DIR] [--split test] [--batch N] [--max-batches M]
-                             [--trials N --seed S --out results.csv]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
+                             [--trials N --seed S --out results.csv]  [--cider]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
 """
 import argparse
 import csv
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--trials", type=int, default=0)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--out", default=None, help="csv (with --trials) or json (without) to write")
+    ap.add_argument("--cider", action="store_true", help="also CIDEr-D and ROUGE-L against the document frequencies of the evaluated split")
     ap.add_argument("--beamk", type=int, default=5)
     ap.add_argument("--max-gen-length", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -50,21 +53,23 @@ def main():
     model = model.cuda()
     ds = D.CocoCaptionDataset(a.json or model.hparams.json, a.split, root=a.root)
     loader = D.DeviceLoader(ds, a.batch or model.hparams.batch, D.BatchTransform(model.hparams.input_size, train=False), workers=a.workers)
+    corpus = E.ReferenceCorpus.from_dataset(ds).check() if a.cider else None
+    shown = E.HEADERS + (list(E.CONSENSUS_KEYS) if a.cider else [])
     if a.trials > 0:
-        rows = E.random_search(model, loader, a.trials, seed=a.seed, max_batches=a.max_batches or 4)
+        rows = E.random_search(model, loader, a.trials, seed=a.seed, max_batches=a.max_batches or 4, corpus=corpus)
         cols = list(rows[0])
         for r in sorted(rows, key=lambda r: -r["bleu4"]):
-            print("  ".join("%s=%s" % (k, ("%.4f" % r[k]) if isinstance(r[k], float) else r[k]) for k in E.HEADERS))
+            print("  ".join("%s=%s" % (k, ("%.4f" % r[k]) if isinstance(r[k], float) else r[k]) for k in shown))
         if a.out:
             with open(a.out, "w", newline="") as f:
                 w = csv.DictWriter(f, fieldnames=cols)
                 w.writeheader(); w.writerows(rows)
         return
-    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
+    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
                      sample_method=a.sample_method, sample_topk=a.sample_topk, decoder_noise=a.decoder_noise,
                      rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward)
     print("%d images in %d batches" % (res["images"], res["batches"]))
-    for k in E.METRIC_KEYS:
+    for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()):
         print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))
     if a.out:
         with open(a.out, "w") as f:
