@@ -236,6 +236,37 @@ int sat_beam_search_sampled(const sat_decoder_dims* d, const sat_decoder_params*
                             const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
                             int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row,
                             float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes, void* stream);
+/* The same search under constraints on the selection step ("Constrained search"); step s is 0-based, image b has a forced
+ * prefix of P_b = prefix_len[b] words:
+ *   banned  : score[:, id] = -inf for every banned id at every step of every image, on top of the START / PAD (/ END / UNK) masks.
+ *   prefix  : s < P_b   every one of the beamk rows keeps its parent and takes prefix[b][s]; its score is the word's own
+ *                       log-probability added to the running sum (masks and banned ids apply; the sampling method is not consulted)
+ *             s == P_b  the first free step: the top beamk of row 0 only (model.py:343), row j keeps parent j; the first-step mask
+ *                       {START, PAD, END, UNK} when P_b == 0, the mask of the later steps {START, PAD} when P_b > 0
+ *             s > P_b   the free search
+ *   topg    : at s > P_b the candidates of an image are the topg best words of every live row (value descending, ties to the lower
+ *             id); the kept hypotheses are the top k of these k * topg candidates (value descending, ties to the lower flat index
+ *             row * V + word).  Deterministic; combines with SAT_SAMPLE_BEAM only.  topg >= beamk is the plain search.
+ * Finished hypotheses, tok_in, prev_row, alpha_hist and fin_* keep the layout above; sequences and scores include the prefix.
+ * The ids are DEVICE arrays and are not read on the host: prefix ids must lie in [0, V) and be none of START / PAD / END / UNK / banned
+ * (out-of-range ids are clamped, prefix_len to 0..max_prefix).  constraints = NULL, or topg == 0 && max_prefix == 0 && n_banned == 0,
+ * enqueues exactly what sat_beam_search_sampled enqueues.  Workspace: sat_beam_search_constrained_workspace_bytes (topg adds the
+ * (B * beamk, topg) candidate list to the plain search's workspace; with topg == 0 both queries agree). */
+typedef struct sat_beam_constraints {
+    int32_t topg;              /* 0 = off, else 1..V                                             */
+    int32_t max_prefix;        /* row stride of prefix; 0 = no prefix; <= max_gen_length         */
+    const int32_t* prefix;     /* device (B, max_prefix) or NULL                                 */
+    const int32_t* prefix_len; /* device (B) or NULL                                             */
+    const int32_t* banned;     /* device (n_banned) or NULL                                      */
+    int32_t n_banned;
+    int32_t reserved;
+} sat_beam_constraints;
+size_t sat_beam_search_constrained_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t topg);
+int sat_beam_search_constrained(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                                const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                                const sat_beam_constraints* constraints, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
+                                int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
+                                void* stream);
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids /* device */,
                     int32_t n_masked, const float* parent_scores /* (beams) or NULL */, float* scores, void* stream);
 int sat_topk(const float* x, float* work /* n floats scratch */, int64_t n, int32_t k, float* values, int32_t* indices, void* stream);

@@ -78,6 +78,12 @@ class BeamSampling(C.Structure):
                 ("reserved", C.c_int32), ("normals", C.c_void_p)]
 
 
+class BeamConstraints(C.Structure):
+    """sat_beam_constraints (include/sat_hip.h)"""
+    _fields_ = [("topg", C.c_int32), ("max_prefix", C.c_int32), ("prefix", C.c_void_p), ("prefix_len", C.c_void_p), ("banned", C.c_void_p),
+                ("n_banned", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [("offset", C.c_int64)] + [(k, C.c_int32) for k in ("height", "width", "crop_top", "crop_left", "crop_h", "crop_w", "resized_h",
                                                                   "resized_w", "out_top", "out_left", "flip", "reserved")]
@@ -240,6 +246,10 @@ SYMBOLS.update({
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "sat_beam_search_sampled": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _i32, _i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_int32),
                                           C.POINTER(BeamSampling), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_beam_search_constrained_workspace_bytes": (C.c_size_t, [C.POINTER(DecoderDims), _i32, _i32]),
+    "sat_beam_search_constrained": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _i32, _i32, C.POINTER(C.c_float), _i32,
+                                              C.POINTER(C.c_int32), C.POINTER(BeamSampling), C.POINTER(BeamConstraints), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, C.c_size_t, _vp]),
     "sat_beam_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp]),
     "sat_topk": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
 })

@@ -1,0 +1,97 @@
+"""Constraints on the beam search's selection step ("Constrained search"): the host half.
+
+``resolve`` turns the public keywords ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` into one checked ``SearchConstraints``
+(or ``None`` when nothing constrains the search) and raises every ``ValueError`` of the specification; it touches no GPU.
+The batched search (``SATDecoder._beam_search_device``) hands the result to ``sat_beam_search_constrained`` as device
+arrays, the per-image loop (``SATDecoder.beam_decode``) applies the same rules with torch ops."""
+import torch
+
+from . import _lib as L
+
+SPECIALS = ("<START>", "<PAD>", "<END>", "<UNK>")
+
+
+class SearchConstraints:
+    """topg: 0 = off; prefix: one list of token ids per image; banned: sorted list of token ids"""
+
+    def __init__(self, topg, prefix, banned):
+        self.topg, self.prefix, self.banned = int(topg), prefix, banned
+        self.max_prefix = max([len(p) for p in prefix] or [0])
+
+    def device_struct(self, dev):
+        """(sat_beam_constraints, the tensors it points into)"""
+        B, keep = len(self.prefix), []
+        con = L.BeamConstraints(topg=self.topg, max_prefix=self.max_prefix, n_banned=len(self.banned))
+        if self.max_prefix:
+            rows = [p + [0] * (self.max_prefix - len(p)) for p in self.prefix]
+            pre = torch.tensor(rows, dtype=torch.int32).reshape(B, self.max_prefix).to(dev)
+            plen = torch.tensor([len(p) for p in self.prefix], dtype=torch.int32).to(dev)
+            con.prefix, con.prefix_len = pre.data_ptr(), plen.data_ptr()
+            keep += [pre, plen]
+        if self.banned:
+            ban = torch.tensor(self.banned, dtype=torch.int32).to(dev)
+            con.banned = ban.data_ptr()
+            keep.append(ban)
+        return con, keep
+
+
+def _one_prefix(p, stoi):
+    if isinstance(p, str):
+        ids = []
+        for word in p.split():
+            if word not in stoi:
+                raise ValueError("prefix word %r is not in the vocabulary" % word)
+            ids.append(int(stoi[word]))
+        return ids
+    if torch.is_tensor(p):
+        p = p.reshape(-1).tolist()
+    return [int(t) for t in p]
+
+
+def resolve(stoi, V, B, beamk, max_gen_length, sample_method="beam", topg=None, prefix=None, banned=None, no_unk=False):
+    """The checked constraints of one search over ``B`` images, or ``None`` when the search is unconstrained."""
+    if topg is None and prefix is None and banned is None and not no_unk:
+        return None
+    ids = {s: int(stoi[s]) for s in SPECIALS}
+    V, K, S = int(V), int(beamk), int(max_gen_length)
+    g = 0
+    if topg is not None:
+        g = int(topg)
+        if not 1 <= g <= V:
+            raise ValueError("topg=%d outside 1..V=%d" % (g, V))
+        if sample_method != "beam":
+            raise ValueError("topg combines with sample_method='beam' only, not %r" % (sample_method,))
+    ban = set(int(t) for t in (banned.reshape(-1).tolist() if torch.is_tensor(banned) else (banned or [])))
+    if no_unk:
+        ban.add(ids["<UNK>"])
+    for t in sorted(ban):
+        if not 0 <= t < V:
+            raise ValueError("banned id %d outside [0, V=%d)" % (t, V))
+    if ids["<END>"] in ban:
+        raise ValueError("<END> cannot be banned: no hypothesis could finish")
+    left = V - len(ban | set(ids.values()))
+    if left < max(K, g or 1):
+        raise ValueError("%d unmasked ids left, the search needs max(beamk, topg) = %d" % (left, max(K, g or 1)))
+    if prefix is None:
+        pre = [[] for _ in range(B)]
+    elif isinstance(prefix, str) or torch.is_tensor(prefix) and prefix.dim() == 1 or (
+            isinstance(prefix, (list, tuple)) and all(isinstance(t, int) for t in prefix)):
+        pre = [_one_prefix(prefix, stoi)] * B                       # one prefix for every image
+    else:
+        pre = [_one_prefix(p, stoi) for p in prefix]
+        if len(pre) != B:
+            raise ValueError("%d prefixes for %d images" % (len(pre), B))
+    names = {v: k for k, v in ids.items()}
+    for b, p in enumerate(pre):
+        if len(p) > S:
+            raise ValueError("prefix of image %d has %d words, max_gen_length is %d" % (b, len(p), S))
+        for t in p:
+            if not 0 <= t < V:
+                raise ValueError("prefix id %d outside [0, V=%d)" % (t, V))
+            if t in names:
+                raise ValueError("%s (id %d) in a prefix" % (names[t], t))
+            if t in ban:
+                raise ValueError("banned id %d in a prefix" % t)
+    con = SearchConstraints(g, [list(p) for p in pre], sorted(ban))
+    return con if (con.topg or con.max_prefix or con.banned) else None
+

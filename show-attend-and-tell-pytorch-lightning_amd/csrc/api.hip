@@ -190,6 +190,22 @@ int sat_beam_search_sampled(const sat_decoder_dims* d, const sat_decoder_params*
     return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling);
 }
+size_t sat_beam_search_constrained_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t topg) {
+    if (check_dims(d) != SAT_OK || beamk < 1) return 0;
+    if (topg < 0 || topg > d->V) { fail(SAT_EINVAL, "beam_search_constrained_workspace_bytes: topg %d outside 0..V=%d", topg, d->V); return 0; }
+    return decoder_beam_workspace_bytes(*d, beamk, topg);
+}
+int sat_beam_search_constrained(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                                const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                                const sat_beam_constraints* constraints, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
+                                int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes, void* stream) {
+    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_constrained"));
+    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
+        return fail(SAT_EINVAL, "beam_search_constrained: null pointer");
+    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_constrained: temperature %g", temperatures_host[i]);
+    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
+                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints);
+}
 int sat_beam_select(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
                     const float* fin_score, const float* fin_mean, const float* alpha_hist, int32_t B, int32_t beamk, int32_t max_gen_length, int32_t L,
                     int32_t rescore_method, float rescore_reward, int32_t pad_id, int32_t* cap_tokens, int32_t* cap_len, float* cap_score, float* cap_raw,

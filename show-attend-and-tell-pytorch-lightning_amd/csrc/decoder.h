@@ -19,10 +19,11 @@ int decoder_infer_begin(const sat_decoder_dims& d, const sat_decoder_params& p, 
                         char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_infer_step(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, const int* tokens, int K, int Kmax,
                        float* h, float* c, float* logits, float* alpha, const float* h_noise, char* ws, size_t ws_bytes, hipStream_t st);
-size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K);
+size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg = 0);
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row,
-                         float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling);
+                         float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
+                         const sat_beam_constraints* constraints = nullptr);
 int attention_step_bwd(const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step, const float* alphas,
                        const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc, int dhc_ld, float* dU,
                        float* dwf_part, float* da, int B, int R, int L, int D, int A, hipStream_t st);

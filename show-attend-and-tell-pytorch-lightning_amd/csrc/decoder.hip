@@ -740,8 +740,9 @@ int decoder_infer_step(const sat_decoder_dims& d, const sat_decoder_params& p, c
 struct BeamWs {
     size_t total; float *U, *Wcat, *bcat, *mean, *f, *init_img, *hc, *Z, *XZ, *Y, *u, *gu, *bup, *h, *c, *h2, *c2, *logits, *scores, *work, *keys, *noise, *vals, *top, *sc;
     int *live, *klive, *inds, *gmap, *mask_first, *mask_rest;
+    float* cand_val; int* cand_idx;        // top-g clipping only: (B*K, topg) candidates, after everything the plain search uses
 };
-static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base) {
+static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg = 0) {
     BeamWs w; size_t off = 0;
     const long HCW = d.A + d.D + 4L * d.n, N = (long)d.B * K;
     auto take = [&](size_t elems) { size_t o = off; off += (elems * 4 + 255) & ~(size_t)255; return base ? base + o : (char*)nullptr; };
@@ -755,16 +756,33 @@ static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base) {
     w.logits = (float*)take((size_t)N * d.V); w.scores = (float*)take((size_t)N * d.V); w.work = (float*)take((size_t)N * d.V); w.keys = (float*)take((size_t)N * d.V); w.noise = (float*)take((size_t)d.layers * N * d.n);
     w.vals = (float*)take(N); w.top = (float*)take(N); w.sc = (float*)take((size_t)N * d.L);
     w.live = (int*)take(N); w.klive = (int*)take(d.B); w.inds = (int*)take(N); w.gmap = (int*)take(N); w.mask_first = (int*)take(4); w.mask_rest = (int*)take(4);
+    w.cand_val = nullptr; w.cand_idx = nullptr;
+    if (topg > 0) { w.cand_val = (float*)take((size_t)N * topg); w.cand_idx = (int*)take((size_t)N * topg); }
     w.total = off;
     return w;
 }
-size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K) { return beam_layout(d, K, nullptr).total; }
+size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg) { return beam_layout(d, K, nullptr, topg).total; }
 
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
-                         int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp) {
-    BeamWs w = beam_layout(d, K, ws);
+                         int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
+                         const sat_beam_constraints* con) {
+    // no constraint at all: exactly the launches of the plain / sampled search
+    if (con && con->topg == 0 && con->max_prefix == 0 && con->n_banned == 0) con = nullptr;
     const int method = smp ? smp->method : 0;
+    if (con) {
+        SAT_REQUIRE(K <= 1024, "beam_constrained: beamk %d above 1024 (one thread per row in the forced steps)", K);
+        SAT_REQUIRE(con->topg >= 0 && con->topg <= d.V, "beam_constrained: topg %d outside 1..V=%d (0 = off)", con->topg, d.V);
+        SAT_REQUIRE(con->topg == 0 || method == 0, "beam_constrained: topg %d combines with \"beam\" sampling only (method %d)", con->topg, method);
+        SAT_REQUIRE(con->max_prefix >= 0 && con->max_prefix <= max_gen_length, "beam_constrained: max_prefix %d outside 0..max_gen_length=%d", con->max_prefix,
+                    max_gen_length);
+        SAT_REQUIRE(con->n_banned >= 0 && con->n_banned <= d.V, "beam_constrained: n_banned %d outside 0..V=%d", con->n_banned, d.V);
+        SAT_REQUIRE((con->max_prefix == 0 || (con->prefix && con->prefix_len)) && (con->n_banned == 0 || con->banned),
+                    "beam_constrained: null pointer (prefix / prefix_len with max_prefix %d, banned with n_banned %d)", con->max_prefix, con->n_banned);
+    }
+    const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
+    const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
+    BeamWs w = beam_layout(d, K, ws, topg);
     SAT_REQUIRE(method >= 0 && method <= 2 && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)), "beam_batched: sampling method %d, sample_topk %d",
                 method, smp ? smp->sample_topk : 0);
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
@@ -853,24 +871,49 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         SAT_TRY(gemm(st, A_ROW, B_ROW, w.u, m, p.out_w, m, w.logits, V, N, V, m, 0, p.out_b ? EPI_BIAS : EPI_NONE, p.out_b));
         // ---- model.py:330-359: log-softmax, special-token masks, parent scores, top-k per image
         const float T = temps_host[step % n_temps];
-        hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, w.logits, V, 1.0f / T, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2,
-                           step == 0 ? (const float*)nullptr : w.top, w.scores);
-        SAT_TRY(launch_ok("beam_scores"));
-        if (method == 0 || step == 0) {                // the first step always takes the top beamk words (model.py:343)
-            hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
-            SAT_TRY(launch_ok("beam_topk"));
-        } else {                                       // model.py:360-379: draw the continuing hypotheses (Gumbel-top-k == multinomial without replacement)
-            const int gstride = method == 1 ? V : smp->sample_topk;
-            hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
-                               (unsigned long long)smp->seed, (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr,
-                               gstride, w.keys);
-            SAT_TRY(launch_ok("beam_sample_keys"));
-            hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.keys, w.work, w.klive, K, V, 0, w.vals, w.inds);
-            SAT_TRY(launch_ok("beam_topk (keys)"));
-            hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
-            SAT_TRY(launch_ok("beam_take_scores"));
+        if (con) {                                     // per image: forced word (step < P_b), row 0 (step == P_b), the free search after it
+            hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, w.logits, K, V, 1.0f / T, w.mask_first, w.mask_rest, step, prefix_len,
+                               max_prefix, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, w.scores);
+            SAT_TRY(launch_ok("beam_scores (constrained)"));
+            const bool drawn = method != 0 && step > 0;
+            if (topg > 0 && step > 0) {
+                hipLaunchKernelGGL(beam_row_topg_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, topg, step, prefix_len, max_prefix, w.cand_val, w.cand_idx);
+                SAT_TRY(launch_ok("beam_row_topg"));
+            }
+            if (drawn) {
+                const int gstride = method == 1 ? V : smp->sample_topk;
+                hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
+                                   (unsigned long long)smp->seed, (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr,
+                                   gstride, w.keys);
+                SAT_TRY(launch_ok("beam_sample_keys"));
+            }
+            hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, drawn ? w.keys : (const float*)nullptr, w.cand_val, w.cand_idx, topg, w.work,
+                               w.klive, K, V, step, max_prefix > 0 ? con->prefix : (const int*)nullptr, prefix_len, max_prefix, w.vals, w.inds);
+            SAT_TRY(launch_ok("beam_select"));
+            if (drawn) {
+                hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
+                SAT_TRY(launch_ok("beam_take_scores"));
+            }
+        } else {
+            hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, w.logits, V, 1.0f / T, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2,
+                               step == 0 ? (const float*)nullptr : w.top, w.scores);
+            SAT_TRY(launch_ok("beam_scores"));
+            if (method == 0 || step == 0) {                // the first step always takes the top beamk words (model.py:343)
+                hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_topk"));
+            } else {                                       // model.py:360-379: draw the continuing hypotheses (Gumbel-top-k == multinomial without replacement)
+                const int gstride = method == 1 ? V : smp->sample_topk;
+                hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
+                                   (unsigned long long)smp->seed, (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr,
+                                   gstride, w.keys);
+                SAT_TRY(launch_ok("beam_sample_keys"));
+                hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.keys, w.work, w.klive, K, V, 0, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_topk (keys)"));
+                hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
+                SAT_TRY(launch_ok("beam_take_scores"));
+            }
         }
-        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, B, K, V, step, max_gen_length, END,
+        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, B, K, V, step, max_gen_length, END, prefix_len, max_prefix,
                            tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, fin_count, fin_step, fin_row, fin_score, fin_mean);
         SAT_TRY(launch_ok("beam_update"));
         if (step < max_gen_length) {

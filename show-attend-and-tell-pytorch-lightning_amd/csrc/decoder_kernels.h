@@ -1196,11 +1196,8 @@ __global__ void scatter_rows_kernel(const float* __restrict__ src, const int* __
 
 // ------------------------------------------------------------------ inference (beam search, model.py:329-343, 351-359)
 // scores[r, v] = log_softmax(logits[r, :] / T)[v] (+ parent[r]); masked token ids become -inf.  One block per beam row.
-__global__ __launch_bounds__(256) void beam_scores_kernel(const float* __restrict__ logits, int V, float inv_temp,
-                                                          const int* __restrict__ masked, int n_masked,
-                                                          const float* __restrict__ parent, float* __restrict__ scores) {
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const float* x = logits + (long)r * V;
+// The row's arithmetic (shared by the constrained kernel below, so that a word has the same float in both searches).
+__device__ __forceinline__ void beam_scores_row(const float* __restrict__ x, int V, float inv_temp, float add, float* __restrict__ o, int tid) {
     __shared__ float s_m[4], s_s[4];
     float mx = -INFINITY, sum = 0.f;
     for (int v = tid; v < V; v += 256) {
@@ -1217,10 +1214,16 @@ __global__ __launch_bounds__(256) void beam_scores_kernel(const float* __restric
     __syncthreads();
     float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3])), S = 0.f;
     for (int k = 0; k < 4; ++k) S += (s_m[k] == M) ? s_s[k] : s_s[k] * __expf(s_m[k] - M);
-    const float lse = M + __logf(S), add = parent ? parent[r] : 0.f;
-    float* o = scores + (long)r * V;
+    const float lse = M + __logf(S);
     for (int v = tid; v < V; v += 256) o[v] = x[v] * inv_temp - lse + add;
     __syncthreads();
+}
+__global__ __launch_bounds__(256) void beam_scores_kernel(const float* __restrict__ logits, int V, float inv_temp,
+                                                          const int* __restrict__ masked, int n_masked,
+                                                          const float* __restrict__ parent, float* __restrict__ scores) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    float* o = scores + (long)r * V;
+    beam_scores_row(logits + (long)r * V, V, inv_temp, parent ? parent[r] : 0.f, o, tid);
     for (int k = tid; k < n_masked; k += 256) { int id = masked[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
 }
 
@@ -1276,14 +1279,9 @@ __global__ void beam_live_kernel(const int* __restrict__ klive, int* __restrict_
 }
 // torch.topk of the flattened live scores of every image (model.py:343 at step 0: row 0 only; model.py:359 afterwards),
 // descending, ties to the lowest index.  One block per image; `work` (B, K*V) is scratch.
-__global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ scores, float* __restrict__ work, const int* __restrict__ klive,
-                                                         int K, int V, int first_step, float* __restrict__ values, int* __restrict__ indices) {
+__device__ __forceinline__ void beam_block_topk(const float* __restrict__ x, float* __restrict__ wk, long n, int k, float* __restrict__ values,
+                                                int* __restrict__ indices, int tid) {
     __shared__ float s_v[16]; __shared__ long s_i[16];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int k = klive[b];
-    if (k <= 0) return;
-    const long n = first_step ? V : (long)k * V;
-    const float* x = scores + (long)b * K * V; float* wk = work + (long)b * K * V;
     for (long i = tid; i < n; i += 1024) wk[i] = x[i];
     __syncthreads();
     for (int it = 0; it < k; ++it) {
@@ -1297,11 +1295,19 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
         __syncthreads();
         if (tid == 0) {
             for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-            values[b * K + it] = bv; indices[b * K + it] = (int)bi;
+            values[it] = bv; indices[it] = (int)bi;
             if (bi < n) wk[bi] = -INFINITY;
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ scores, float* __restrict__ work, const int* __restrict__ klive,
+                                                         int K, int V, int first_step, float* __restrict__ values, int* __restrict__ indices) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int k = klive[b];
+    if (k <= 0) return;
+    const long n = first_step ? V : (long)k * V;
+    beam_block_topk(scores + (long)b * K * V, work + (long)b * K * V, n, k, values + b * K, indices + b * K, tid);
 }
 // ---- sampled continuation of the beams (model.py:360-379) for all images at once.
 // torch.multinomial(p, k) without replacement draws an ordered sample from the Plackett-Luce distribution of p; so does
@@ -1386,6 +1392,113 @@ __global__ void beam_take_scores_kernel(const float* __restrict__ scores, const 
     const int b = i / K, j = i - b * K;
     if (j < klive[b]) { const int ind = inds[i]; if (ind >= 0 && ind < K * V) values[i] = scores[(long)b * K * V + ind]; }
 }
+// ---- constrained search: forced prefix, banned ids, top-g clipping ("Constrained search").
+// Image b has a forced prefix of P_b words.  Step s < P_b: every row keeps its parent and takes prefix[b][s].  s == P_b: the
+// first free step, the top k of row 0 (model.py:343).  s > P_b: the free search.  P_b = 0 is the unconstrained search.
+__device__ __forceinline__ int beam_prefix_len(const int* __restrict__ prefix_len, int b, int max_prefix) {
+    if (!prefix_len) return 0;
+    const int p = prefix_len[b];
+    return p < 0 ? 0 : (p > max_prefix ? max_prefix : p);
+}
+// beam_scores_kernel with the mask chosen per image (the first-step mask only where step 0 is the image's first free step)
+// and the banned ids on top.
+__global__ __launch_bounds__(256) void beam_scores_constrained_kernel(const float* __restrict__ logits, int K, int V, float inv_temp,
+                                                                      const int* __restrict__ mask_first, const int* __restrict__ mask_rest, int step,
+                                                                      const int* __restrict__ prefix_len, int max_prefix,
+                                                                      const int* __restrict__ banned, int n_banned,
+                                                                      const float* __restrict__ parent, float* __restrict__ scores) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    float* o = scores + (long)r * V;
+    beam_scores_row(logits + (long)r * V, V, inv_temp, parent ? parent[r] : 0.f, o, tid);
+    const bool first = step == 0 && beam_prefix_len(prefix_len, r / K, max_prefix) == 0;
+    const int* masked = first ? mask_first : mask_rest; const int n_masked = first ? 4 : 2;
+    for (int k = tid; k < n_masked; k += 256) { int id = masked[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
+    for (int k = tid; k < n_banned; k += 256) { int id = banned[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
+}
+// top-g clipping, stage 1: the g best entries of every live row in its free steps (value descending, ties to the lower id), as
+// (value, flat index j * V + v) in cand_*[(b * K + j) * g + t].  One block per row; no scratch, every pass looks for the best
+// entry strictly after the previous pick.
+__global__ __launch_bounds__(256) void beam_row_topg_kernel(const float* __restrict__ scores, const int* __restrict__ klive, int K, int V, int g, int step,
+                                                            const int* __restrict__ prefix_len, int max_prefix, float* __restrict__ cand_val,
+                                                            int* __restrict__ cand_idx) {
+    const int i = blockIdx.x, b = i / K, j = i - b * K, tid = threadIdx.x;
+    if (j >= klive[b] || step <= beam_prefix_len(prefix_len, b, max_prefix)) return;
+    const float* s = scores + (long)i * V;
+    __shared__ float s_v[4]; __shared__ int s_i[4]; __shared__ float s_b; __shared__ int s_bi;
+    float lastv = INFINITY; int lasti = -1;
+    for (int t = 0; t < g; ++t) {
+        float bv = -INFINITY; int bi = 0x7fffffff;
+        for (int v = tid; v < V; v += 256) {
+            const float x = s[v];
+            const bool after = x < lastv || (x == lastv && v > lasti);
+            if (after && (x > bv || (x == bv && v < bi))) { bv = x; bi = v; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
+            s_b = bv; s_bi = bi;
+            cand_val[(long)i * g + t] = bv; cand_idx[(long)i * g + t] = bi < V ? j * V + bi : 0x7fffffff;   // g <= V: the row never runs out
+        }
+        __syncthreads();
+        lastv = s_b; lasti = s_bi;
+    }
+}
+// The selection of one step with the per-image branch; one block per image, writes what beam_topk_kernel writes (values and
+// flat indices parent * V + word of the k kept hypotheses).  keys: the sampled search's keys (free steps draw from them) or
+// NULL; g > 0: stage 2 of top-g clipping, the top k of the image's k * g candidates (value descending, ties to the lower flat
+// index).  A pure function of the scores: no atomics, no dependence on arrival order.
+__global__ __launch_bounds__(1024) void beam_select_kernel(const float* __restrict__ scores, const float* __restrict__ keys, const float* __restrict__ cand_val,
+                                                           const int* __restrict__ cand_idx, int g, float* __restrict__ work, const int* __restrict__ klive,
+                                                           int K, int V, int step, const int* __restrict__ prefix, const int* __restrict__ prefix_len,
+                                                           int max_prefix, float* __restrict__ values, int* __restrict__ indices) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int k = klive[b];
+    if (k <= 0) return;
+    const int P = beam_prefix_len(prefix_len, b, max_prefix);
+    if (step < P) {                                        // forced: row j -> (j, prefix[b][step]) with the word's own score
+        if (tid < k) {
+            int w = prefix[(long)b * max_prefix + step];
+            w = w < 0 ? 0 : (w >= V ? V - 1 : w);
+            values[b * K + tid] = scores[((long)b * K + tid) * V + w]; indices[b * K + tid] = tid * V + w;
+        }
+        return;
+    }
+    if (step == P || g <= 0) {
+        const float* src = (step > P && keys) ? keys : scores;
+        beam_block_topk(src + (long)b * K * V, work + (long)b * K * V, step == P ? (long)V : (long)k * V, k, values + b * K, indices + b * K, tid);
+        return;
+    }
+    __shared__ float s_v[16]; __shared__ int s_i[16]; __shared__ float s_b; __shared__ int s_bi;
+    const float* cv = cand_val + (long)b * K * g; const int* ci = cand_idx + (long)b * K * g;
+    const int n = k * g;
+    float lastv = INFINITY; int lasti = -1;
+    for (int it = 0; it < k; ++it) {
+        float bv = -INFINITY; int bi = 0x7fffffff;
+        for (int i = tid; i < n; i += 1024) {
+            const float x = cv[i]; const int id = ci[i];
+            const bool after = x < lastv || (x == lastv && id > lasti);
+            if (after && (x > bv || (x == bv && id < bi))) { bv = x; bi = id; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
+            s_b = bv; s_bi = bi;
+            values[b * K + it] = bv; indices[b * K + it] = bi < K * V ? bi : 0;
+        }
+        __syncthreads();
+        lastv = s_b; lasti = s_bi;
+    }
+}
 // decoder noise (model.py:322-324): out = N(0, 1) * scale for every layer and live row (0 for dead rows); normals from the table
 // or the hash (Box-Muller).  The noise joins h after attention and the gate were taken from the clean state, so it reaches the
 // step through the recurrent products only: the caller adds out * W_hh^T to the gate pre-activations.
@@ -1410,7 +1523,8 @@ __global__ void beam_state_noise_kernel(float* __restrict__ out, const int* __re
 // and the state gather), parent score; the finished list keeps (step, parent row, raw score, mean of the beam's scores at
 // that moment -- what the BAR rescoring needs).
 __global__ void beam_update_kernel(const float* __restrict__ values, const int* __restrict__ indices, int* __restrict__ klive, int B, int K, int V,
-                                   int step, int last_step, int end_id, int* __restrict__ tok_next, int* __restrict__ prev_next,
+                                   int step, int last_step, int end_id, const int* __restrict__ prefix_len, int max_prefix,
+                                   int* __restrict__ tok_next, int* __restrict__ prev_next,
                                    float* __restrict__ top_scores, int* __restrict__ gmap, int* __restrict__ fin_count, int* __restrict__ fin_step,
                                    int* __restrict__ fin_row, float* __restrict__ fin_score, float* __restrict__ fin_mean) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1418,6 +1532,7 @@ __global__ void beam_update_kernel(const float* __restrict__ values, const int* 
     const int k = klive[b];
     int nk = 0;
     if (k > 0) {
+        const bool own = step <= beam_prefix_len(prefix_len, b, max_prefix);     // up to its first free step a row is its own parent
         float mean_all = 0.f;
         for (int j = 0; j < k; ++j) mean_all += values[b * K + j];
         mean_all /= (float)k;
@@ -1425,7 +1540,7 @@ __global__ void beam_update_kernel(const float* __restrict__ values, const int* 
         // completed hypotheses first, in index order (torch.nonzero(complete))
         for (int j = 0; j < k; ++j) {
             const int ind = indices[b * K + j];
-            const int parent = step == 0 ? j : ind / V, tok = step == 0 ? ind : ind - (ind / V) * V;
+            const int parent = own ? j : ind / V, tok = ind - (ind / V) * V;
             if (tok == end_id) {
                 fin_step[b * K + fc] = step; fin_row[b * K + fc] = parent; fin_score[b * K + fc] = values[b * K + j]; fin_mean[b * K + fc] = mean_all; ++fc;
             }
@@ -1434,7 +1549,7 @@ __global__ void beam_update_kernel(const float* __restrict__ values, const int* 
         float rest = 0.f;
         for (int j = 0; j < k; ++j) {
             const int ind = indices[b * K + j];
-            const int parent = step == 0 ? j : ind / V, tok = step == 0 ? ind : ind - (ind / V) * V;
+            const int parent = own ? j : ind / V, tok = ind - (ind / V) * V;
             if (tok != end_id) {
                 tok_next[b * K + nk] = tok; prev_next[b * K + nk] = parent; top_scores[b * K + nk] = values[b * K + j]; gmap[b * K + nk] = parent;
                 rest += values[b * K + j]; ++nk;

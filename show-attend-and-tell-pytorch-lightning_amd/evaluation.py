@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import constraints
 from . import metrics
 
 #: the reference's BLEU weights (model.py:651-654), bleu3 as written there
@@ -53,15 +54,18 @@ def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, 
 
 @torch.no_grad()
 def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
+                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False):
     """``SAT.caption(..., return_all=False)`` with the result left on the device: ``(tokens (B, max_gen_length + 1) int32 padded with
-    <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises."""
+    <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises.
+    ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
+    con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
+    constraints.resolve(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length, str(sample_method), **con)   # refuse before any launch
     model.eval()
     ann_bld, _ = model.encode(img)
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
-                                  graph)
+                                  graph, **con)
     sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward)
     ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
     return sel["tokens"], sel["lengths"], sel["scores"], ppl
@@ -247,13 +251,14 @@ class CaptionStats:
 
 @torch.no_grad()
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None):
+                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False):
     """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
-    with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue."""
+    with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue.  ``topg`` / ``prefix`` / ``banned`` /
+    ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
     tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                                          rescore_method, rescore_reward, seed, graph)
+                                          rescore_method, rescore_reward, seed, graph, topg, prefix, banned, no_unk)
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())
@@ -266,7 +271,8 @@ def evaluate(model, loader, max_batches=None, seed=None, corpus=None, **decode):
     the plain mean of the per-batch metric dicts, "corpus": BLEU / GLEU taken once from the statistics summed over every image (cosine and
     perplexity: means over images), "batches", "images"}``.  The per-batch statistics stay on the device and are read once at the end.
     ``seed``: batch i of a sampled search draws with ``seed + i``.  ``corpus`` (a ``ReferenceCorpus``): both dicts gain "cider" and
-    "rouge_l" (means over images); still one host read."""
+    "rouge_l" (means over images); still one host read.  ``decode`` takes every keyword of ``val_batch_stats``, the search constraints
+    ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` among them."""
     if corpus is not None:
         decode["corpus"] = corpus
     vecs, images = [], []
@@ -286,21 +292,29 @@ def evaluate(model, loader, max_batches=None, seed=None, corpus=None, **decode):
 
 
 def draw_decode_params(rs, space=NOTEBOOK_SPACE):
-    """one trial's parameters from ``rs`` (np.random.RandomState) in the notebook's order: choice, uniform, choice, choice, choice, uniform"""
+    """one trial's parameters from ``rs`` (np.random.RandomState) in the notebook's order: choice, uniform, choice, choice, choice, uniform.
+    An optional ``space["topgs"]`` (a list of top-g clipping widths, ``None`` = off) adds one more choice AFTER the notebook's draws and a
+    ``topg`` entry; top-g clipping belongs to "beam" sampling, so a trial that drew another method carries ``topg=None``."""
     beamk = rs.choice(space["beamks"])
     temperature = rs.uniform(space["temperatures"][0], space["temperatures"][1])
     sample_method = rs.choice(space["sample_methods"])
     decoder_noise = rs.choice(space["decoder_noises"])
     rescore_method = rs.choice(space["rescore_methods"])
     rescore_reward = rs.uniform(space["rescore_rewards"][0], space["rescore_rewards"][1])
-    return {"beamk": int(beamk), "temperature": float(temperature), "sample_method": str(sample_method), "decoder_noise": float(decoder_noise),
-            "rescore_method": str(rescore_method), "rescore_reward": float(rescore_reward)}
+    row = {"beamk": int(beamk), "temperature": float(temperature), "sample_method": str(sample_method), "decoder_noise": float(decoder_noise),
+           "rescore_method": str(rescore_method), "rescore_reward": float(rescore_reward)}
+    if "topgs" in space:
+        topgs = list(space["topgs"])
+        topg = topgs[int(rs.randint(len(topgs)))]
+        row["topg"] = int(topg) if topg is not None and row["sample_method"] == "beam" else None
+    return row
 
 
 def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4, corpus=None):
     """evaluate.ipynb's random search: ``trials`` draws from one ``np.random.RandomState(seed)``, each scored over the first
     ``max_batches`` batches.  Rows carry the notebook's 13 columns (the metrics are its batch means) plus ``<metric>_corpus``; with
-    ``corpus`` (a ``ReferenceCorpus``, built once and reused by every trial) also cider, rouge_l, cider_corpus, rouge_l_corpus."""
+    ``corpus`` (a ``ReferenceCorpus``, built once and reused by every trial) also cider, rouge_l, cider_corpus, rouge_l_corpus; with
+    ``space["topgs"]`` also a ``topg`` column (``draw_decode_params``)."""
     rs = np.random.RandomState(seed)
     rows = []
     for trial in range(int(trials)):

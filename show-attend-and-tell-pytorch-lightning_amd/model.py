@@ -17,6 +17,7 @@ from torch.nn.utils.rnn import PackedSequence
 from torch.optim.lr_scheduler import MultiStepLR, ReduceLROnPlateau, ExponentialLR, CosineAnnealingWarmRestarts, OneCycleLR
 
 from . import _lib as L
+from . import constraints
 from . import decoder as Dk
 from .modules import DeepOutput, Embedding, Gate, InitLSTM, LSTM, SoftAttention  # noqa: F401  (the reference's module names, model.py:66-131)
 from .encoder import get_encoder  # noqa: F401  (module-level name, as in the reference)
@@ -109,16 +110,21 @@ class SATDecoder(nn.Module):
 
     @torch.no_grad()
     def beam_decode(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
-                    decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, multinomial=None, randn=None):
+                    decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, multinomial=None, randn=None,
+                    topg=None, prefix=None, banned=None, no_unk=False):
         """SAT.forward's per-image beam search (model.py:260-472) on annotations (B, L, D).  The decode step,
         log-softmax / masking and top-k run in the library; the beam bookkeeping (which hypotheses to keep, finished
         lists, rescoring) stays on the host like in the reference.  ``sample_method`` "multinomial" / "topk"
         (model.py:360-379) draw the continuing hypotheses with ``multinomial(probs, k)`` and ``decoder_noise``
         (model.py:322-324) perturbs the recurrent state with ``randn(shape)``: both default to the torch samplers on the
-        annotations' device and can be replaced (tests feed both sides the same draws)."""
+        annotations' device and can be replaced (tests feed both sides the same draws).
+        ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: the constrained search ("Constrained search"), the same rules as
+        ``beam_decode_batched`` with torch ops on the scores this loop already holds."""
         import ctypes as C
         assert sample_method in ("beam", "multinomial", "topk")
         multinomial = multinomial or torch.multinomial
+        con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
+                                  topg, prefix, banned, no_unk)
         lib = L.lib()
         L.require_gpu(ann_bld)
         hp = self.hp
@@ -144,8 +150,11 @@ class SATDecoder(nn.Module):
         work = torch.empty(beamk * V, **f32)
         captions, cap_scores, cap_alphas, cap_ppl = [], [], [], []
         st = L.stream_ptr
+        ban_t = torch.tensor(con.banned, dtype=torch.int64, device=dev) if con is not None and con.banned else None
+        g = con.topg if con is not None else 0
         for idx in range(B):
             k = beamk
+            forced = con.prefix[idx] if con is not None else []       # this image's forced words; the first free step is len(forced)
             ann = ann_bld[idx].contiguous()
             h = torch.empty(NL, k, n, **f32); c = torch.empty(NL, k, n, **f32)
             L.check(lib.sat_decoder_infer_begin(C.byref(dims), C.byref(w), L.ptr(ann), k, beamk, L.ptr(h), L.ptr(c), L.ptr(ws), ws_bytes, st()),
@@ -176,16 +185,30 @@ class SATDecoder(nn.Module):
                                                    L.ptr(alpha), L.ptr(noise), L.ptr(ws), ws_bytes, st()), "sat_decoder_infer_step")
                 scores = torch.empty(k, V, **f32)
                 vals = torch.empty(k, **f32); inds = torch.empty(k, dtype=torch.int32, device=dev)
-                if step == 0:
+                if step == 0 and not forced:
                     L.check(lib.sat_beam_scores(L.ptr(logits), k, V, T, L.ptr(mask_first), 4, None, L.ptr(scores), st()), "sat_beam_scores")
-                    L.check(lib.sat_topk(L.ptr(scores), L.ptr(work), V, k, L.ptr(vals), L.ptr(inds), st()), "sat_topk")       # row 0 only (model.py:343)
-                    top_scores = vals
+                else:
+                    L.check(lib.sat_beam_scores(L.ptr(logits), k, V, T, L.ptr(mask_rest), 2, L.ptr(top_scores.contiguous()) if step else None, L.ptr(scores),
+                                                st()), "sat_beam_scores")
+                if ban_t is not None:
+                    scores[:, ban_t] = float("-inf")
+                if step <= len(forced):                 # every row is its own parent up to the image's first free step
+                    if step < len(forced):              # forced word: its own score joins the running sum
+                        top_scores = scores[:, forced[step]].contiguous()
+                        inds = torch.full((k,), forced[step], dtype=torch.int32, device=dev)
+                    else:
+                        L.check(lib.sat_topk(L.ptr(scores), L.ptr(work), V, k, L.ptr(vals), L.ptr(inds), st()), "sat_topk")   # row 0 only (model.py:343)
+                        top_scores = vals
                     top_preds = torch.cat([top_preds, inds.to(torch.int64).unsqueeze(0)], 0)
                     alphas = torch.cat([alphas, alpha.unsqueeze(0)], 0)
                 else:
-                    L.check(lib.sat_beam_scores(L.ptr(logits), k, V, T, L.ptr(mask_rest), 2, L.ptr(top_scores.contiguous()), L.ptr(scores), st()),
-                            "sat_beam_scores")
-                    if sample_method == "beam":
+                    if g:                               # top-g clipping: the g best words of every row, then the top k of the k * g candidates
+                        cv, ci = torch.sort(scores, dim=1, descending=True, stable=True)
+                        cv, ci = cv[:, :g].reshape(-1), (ci[:, :g] + (torch.arange(k, device=dev) * V).unsqueeze(1)).reshape(-1)
+                        by_index = torch.argsort(ci)    # ties go to the lower flat index
+                        top = torch.sort(cv[by_index], descending=True, stable=True).indices[:k]
+                        pred, top_scores = ci[by_index][top], cv[by_index][top]
+                    elif sample_method == "beam":
                         L.check(lib.sat_topk(L.ptr(scores), L.ptr(work), k * V, k, L.ptr(vals), L.ptr(inds), st()), "sat_topk")
                         top_scores = vals
                         pred = inds.to(torch.int64)
@@ -237,12 +260,16 @@ class SATDecoder(nn.Module):
                 cap_scores.append(fin_scores[best]); cap_ppl.append(fin_ppl[best])
         return captions, cap_scores, cap_alphas, cap_ppl
 
-    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph):
+    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
+                            topg=None, prefix=None, banned=None, no_unk=False):
         """The device half of ``beam_decode_batched``: enqueue the whole search for annotations (B, L, D) (eagerly, or as the replay of
         its cached hipGraph) and return the buffers it leaves on the device (tok_in, prev_row, alpha_hist, fin_*: include/sat_hip.h,
-        sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted)."""
+        sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted).
+        With a constraint (``topg`` / ``prefix`` / ``banned`` / ``no_unk``) the call is sat_beam_search_constrained and runs eagerly."""
         import ctypes as C
         assert sample_method in ("beam", "multinomial", "topk")
+        con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
+                                  topg, prefix, banned, no_unk)
         lib = L.lib()
         L.require_gpu(ann_bld)
         hp = self.hp
@@ -261,6 +288,10 @@ class SATDecoder(nn.Module):
         w, _keep = self._params_struct()
         ws_bytes = lib.sat_beam_search_workspace_bytes(C.byref(dims), K)
         i32 = dict(dtype=torch.int32, device=dev); f32 = dict(dtype=torch.float32, device=dev)
+        cst = None
+        if con is not None:
+            cst, _keep_con = con.device_struct(dev)
+            ws_bytes = lib.sat_beam_search_constrained_workspace_bytes(C.byref(dims), K, con.topg)
         smp = None
         if sample_method != "beam" or decoder_noise:
             if seed is None:
@@ -280,12 +311,18 @@ class SATDecoder(nn.Module):
                         fin_mean=torch.empty(B, K, **f32))
 
         def enqueue(ann, o):
+            if cst is not None:
+                L.check(lib.sat_beam_search_constrained(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
+                                                        C.byref(cst), L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]),
+                                                        L.ptr(o["fin_step"]), L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]),
+                                                        ws_bytes, L.stream_ptr()), "sat_beam_search_constrained")
+                return
             L.check(lib.sat_beam_search_sampled(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
                                                 L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]),
                                                 L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]), ws_bytes, L.stream_ptr()),
                     "sat_beam_search_sampled")
 
-        if graph and smp is None:
+        if graph and smp is None and cst is None:
             cache = self.__dict__.setdefault("_beam_graphs", {})
             key = (B, Lc, D, K, S, tuple(float(t) for t in temps), int(dims.precision), str(dev), tuple(t.data_ptr() for t in _keep.values() if torch.is_tensor(t)))
             ent = cache.get(key)
@@ -310,7 +347,8 @@ class SATDecoder(nn.Module):
 
     @torch.no_grad()
     def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
-                            return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False):
+                            return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False,
+                            topg=None, prefix=None, banned=None, no_unk=False):
         """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
         (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
         completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
@@ -321,9 +359,14 @@ class SATDecoder(nn.Module):
         ``gumbel`` / ``normals`` replace the generator by tables (layouts: include/sat_hip.h, sat_beam_sampling).
         ``graph=True`` ("beam" sampling without noise): the call's ~25 launches per decode step are captured once per (batch
         shape, beam, length, temperatures, weights) into a hipGraph over static buffers and replayed - the same kernels with the
-        same arguments, one submission."""
+        same arguments, one submission.
+        Constraints on the selection step ("Constrained search"), all inside the same call: ``topg`` keeps only the g best
+        words of every hypothesis as candidates ("beam" sampling only), ``prefix`` (token ids, or a string looked up in ``vocab_stoi``;
+        one for all images or one per image) forces the first words of every caption, ``banned`` ids / ``no_unk`` never appear.
+        ``graph=True`` combined with any constraint runs eagerly, as sampling does."""
         import numpy as np
-        o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph)
+        o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
+                                     topg, prefix, banned, no_unk)
         B = ann_bld.shape[0]
         Hh, Ww = hw
         K, S = int(beamk), int(max_gen_length)
@@ -480,24 +523,26 @@ class SAT(SATDecoder, _Base):
 
     @torch.no_grad()
     def caption(self, img_tensor, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
-                decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False):
-        """model.py:214-235: eval mode, then forward."""
+                decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False):
+        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: ``beam_decode_batched``."""
         self.eval()
         return self.forward(img_tensor, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                            rescore_method, rescore_reward, return_all)
+                            rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk)
 
     def forward(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                rescore_method=None, rescore_reward=0.5, return_all=False):
+                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False):
         """Inference only (model.py:237-472): encode the batch once, then beam-search every image."""
         assert sample_method in ["beam", "multinomial", "topk"]
+        con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
+        constraints.resolve(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
         with torch.no_grad():
             ann_bld, hw = self.encode(img)
             if max_gen_length >= 1:        # every image at once; sampled continuations and decoder noise draw from the device generator
                 return self.beam_decode_batched(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, rescore_method, rescore_reward, return_all,
                                                 sample_method=sample_method, sample_topk=sample_topk, decoder_noise=decoder_noise,
-                                                graph=bool(self.__dict__.get("beam_graph", False)))       # model.beam_graph = True: hipGraph replay
+                                                graph=bool(self.__dict__.get("beam_graph", False)), **con)  # model.beam_graph = True: hipGraph replay
             return self.beam_decode(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, sample_method, sample_topk,
-                                    decoder_noise, rescore_method, rescore_reward, return_all)
+                                    decoder_noise, rescore_method, rescore_reward, return_all, **con)
 
     def train_batch(self, batch, epsilon=0, draw=None, teacher=None):
         img, encoded_captions, lengths = batch
@@ -649,44 +694,46 @@ class SAT(SATDecoder, _Base):
         return out
 
     def val_batch(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                  rescore_method=None, rescore_reward=0.5):
+                  rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False):
         """model.py:684-691"""
         img, encoded_captions, lengths = batch
         captions, scores, alphas, perplexities = self.caption(img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                                                              rescore_method, rescore_reward, return_all=False)
+                                                              rescore_method, rescore_reward, return_all=False, topg=topg, prefix=prefix, banned=banned,
+                                                              no_unk=no_unk)
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
 
     def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False):
+                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False):
         """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
         from . import evaluation
         return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                         rescore_reward, seed, graph)
+                                         rescore_reward, seed, graph, topg, prefix, banned, no_unk)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None):
+                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
         (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                          rescore_reward, seed, graph, corpus)
+                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, **render):
+                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False, **render):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
         attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
         ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
         from . import visualize
         return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                   rescore_reward, visual_size, input_size, **render)
+                                   rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                      rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False):
+                      rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
+                      topg=None, prefix=None, banned=None, no_unk=False):
         """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
         ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
         from . import visualize
         return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, progressive)
+                                       rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

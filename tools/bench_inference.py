@@ -1,20 +1,31 @@
 """Dev tool / BASELINE configs[4] (C5): caption() throughput, greedy (beam 1) vs beam 5, resnet50 encoder, 64 images, on one GPU.
-Decode-only timing (annotations precomputed) and end-to-end timing (encoder included)."""
-import os, sys, time
+Decode-only timing (annotations precomputed) and end-to-end timing (encoder included).
+``--topg G`` / ``--prefix-len P`` / ``--no-unk`` time the constrained batched search instead ("Constrained search"): the
+prefix of an image is the first P words of its unconstrained caption; the result is checked against the per-image loop."""
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 import sat_amd  # noqa
 from sat_amd import model as M
 
+ap = argparse.ArgumentParser()
+ap.add_argument("precision", nargs="?", default="bf16", choices=["bf16", "fp32"])
+ap.add_argument("--topg", type=int, default=None)
+ap.add_argument("--prefix-len", type=int, default=0)
+ap.add_argument("--no-unk", action="store_true")
+ap.add_argument("--beams", type=int, nargs="+", default=[1, 5])
+a = ap.parse_args()
+constrained = a.topg is not None or a.prefix_len > 0 or a.no_unk
+
 hp, T, B, R = bench.hparams("c2")
 torch.manual_seed(42)
-model = M.SAT(**hp).cuda().eval(); model.set_precision(sys.argv[1] if len(sys.argv) > 1 else "bf16")
+model = M.SAT(**hp).cuda().eval(); model.set_precision(a.precision)
 img = torch.rand(64, 3, hp["input_size"], hp["input_size"], device="cuda")
 with torch.no_grad():
     ann, hw = model.encode(img)
     ann = ann.contiguous()
-    for beamk in (1, 5):
+    for beamk in a.beams:
         for _ in range(2):
             model.beam_decode(ann[:8], hw, beamk=beamk, max_gen_length=20)
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -23,6 +34,22 @@ with torch.no_grad():
         steps = sum(len(c) + 1 for c in caps)
         print("beam %d: decode-only %.1f images/s (%.1f ms/image, mean caption length %.1f, %.0f us per decode step of the kept hypothesis)"
               % (beamk, 64 / dt, dt / 64 * 1e3, steps / 64, dt / steps * 1e6))
+        if constrained:
+            special = {int(hp["vocab_stoi"][s]) for s in ("<START>", "<PAD>", "<END>", "<UNK>")}
+            prefix = [c[:min([a.prefix_len] + [i for i, t in enumerate(c) if t in special])] for c in caps]
+            kw = dict(beamk=beamk, max_gen_length=20, topg=a.topg, prefix=prefix if a.prefix_len > 0 else None, no_unk=a.no_unk)
+            capsl = model.beam_decode(ann, hw, **kw)[0]
+            for _ in range(2):
+                model.beam_decode_batched(ann, hw, **kw)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(5):
+                capsc, _, _, _ = model.beam_decode_batched(ann, hw, **kw)
+            torch.cuda.synchronize(); dtc = (time.perf_counter() - t0) / 5
+            assert capsc == capsl
+            print("beam %d: constrained batched search (topg=%s, prefix-len=%d, no-unk=%s), decode-only %.0f images/s (%.2f ms per 64 images incl. host "
+                  "back-trace), %d of 64 captions differ from the unconstrained search"
+                  % (beamk, a.topg, a.prefix_len, a.no_unk, 64 / dtc, dtc * 1e3, sum(x != y for x, y in zip(capsc, caps))))
+            continue
         for _ in range(2):
             model.beam_decode_batched(ann, hw, beamk=beamk, max_gen_length=20)
         torch.cuda.synchronize(); t0 = time.perf_counter()

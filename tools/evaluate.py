@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--decoder-noise", type=float, default=0.0)
     ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
     ap.add_argument("--rescore-reward", type=float, default=0.5)
+    ap.add_argument("--topg", type=int, default=None, help="top-g clipping: only the G best words of every hypothesis are candidates (beam sampling)")
+    ap.add_argument("--no-unk", action="store_true", help="never emit <UNK>")
     a = ap.parse_args()
 
     ckpt = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
@@ -67,7 +69,8 @@ def main():
         return
     res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
                      sample_method=a.sample_method, sample_topk=a.sample_topk, decoder_noise=a.decoder_noise,
-                     rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward)
+                     rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward, topg=a.topg,
+                     no_unk=a.no_unk)
     print("%d images in %d batches" % (res["images"], res["batches"]))
     for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()):
         print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))

@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
     ap.add_argument("--rescore-reward", type=float, default=1.0)
     ap.add_argument("--progressive", action="store_true", help="decode progressive JPEG files on the GPU as well (default: Pillow decodes them)")
+    ap.add_argument("--topg", type=int, default=None, help="top-g clipping: only the G best words of every hypothesis are candidates (beam sampling)")
+    ap.add_argument("--prefix", default=None, help='words every caption starts with, e.g. "a photo of" (each must be in the vocabulary)')
+    ap.add_argument("--no-unk", action="store_true", help="never emit <UNK>")
     a = ap.parse_args()
     if (a.idx is None) == (a.count is None):
         ap.error("give either --idx or --count")
@@ -60,7 +63,8 @@ def main():
         paths = [ds.img_paths[i] if a.root is None or os.path.isabs(ds.img_paths[i]) else os.path.join(a.root, ds.img_paths[i]) for i in chunk]
         vis = model.visualize(paths, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature, sample_method=a.sample_method,
                               sample_topk=a.sample_topk, decoder_noise=a.decoder_noise, rescore_method=None if a.rescore_method == "NONE" else a.rescore_method,
-                              rescore_reward=a.rescore_reward, visual_size=a.visual_size, input_size=a.input_size, seed=a.seed, progressive=a.progressive)
+                              rescore_reward=a.rescore_reward, visual_size=a.visual_size, input_size=a.input_size, seed=a.seed, progressive=a.progressive,
+                              topg=a.topg, prefix=a.prefix, no_unk=a.no_unk)
         for j, i in enumerate(chunk):
             refs = [" ".join(ds.itos(t) for t in c[1:n]) for c, n in zip(ds.encoded_captions[i], ds.lengths[i])]
             name = os.path.join(a.out, "%s_result.jpg" % vis.names[j])
