@@ -536,6 +536,11 @@ int sat_dwconv3x3_dgrad_t(int32_t dtype, const void* dy, const float* w, void* d
 size_t sat_dwconv3x3_wgrad_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride);
 int sat_dwconv3x3_wgrad_t(int32_t dtype, const void* dy, const void* x, float* dw, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride,
                           float* scratch, void* stream);
+/* The launch plan the three entry points above take for a shape, without touching a device (callable on a machine without a GPU).
+ * op: 0 forward, 1 data gradient, 2 filter gradient.  out = {form (0 generic kernel, 1 rolling window over the rows of a column),
+ * rows per thread R, channel vectors per block cvb, partial [9][C] slices in the scratch}; cvb and the slices are 0 for op 0 and 1, R is 1
+ * for the generic filter-gradient form.  Validates like the entry points (C % 4 | 8 by dtype, stride 1 | 2, positive sizes).            */
+int sat_dwconv3x3_plan(int32_t op, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t out[4]);
 int sat_shuffle_join_t(int32_t dtype, const void* a, const void* b, void* full, void* x1, void* x2, int64_t rows, int32_t Ch, int32_t Chp, void* stream);
 int sat_shuffle_split_t(int32_t dtype, const void* dfull, const void* dx1, const void* dx2, void* da, void* db, int64_t rows, int32_t Ch, int32_t Chp, void* stream);
 /* bf16 -> fp32 copy (n % 8 == 0): the annotations of a bf16 trunk without the 1x1 projection (encoder_dim == trunk width, model.py:56-57) */

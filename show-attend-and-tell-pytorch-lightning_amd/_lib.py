@@ -217,6 +217,7 @@ SYMBOLS.update({
     "sat_dwconv3x3_dgrad_t": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sat_dwconv3x3_wgrad_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32]),
     "sat_dwconv3x3_wgrad_t": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sat_dwconv3x3_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     "sat_shuffle_join_t": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "sat_shuffle_split_t": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "sat_cast_bf16_to_f32": (C.c_int, [_vp, _vp, _i64, _vp]),

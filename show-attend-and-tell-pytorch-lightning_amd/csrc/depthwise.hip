@@ -371,33 +371,72 @@ __global__ void cast_bf16_f32_kernel(const bf* __restrict__ src, float* __restri
 
 using namespace sat;
 
-// launch shape of dw3x3_wgrad_s1_kernel: rows per thread R (<= 1: use the generic kernel), channel vectors per block, number of blocks along x
-static int dw_wgrad_s1_blocks(int N, int H, int W, int C, int V, int& R, int& cvb) {
+// The launch plan of the depthwise 3x3 entry points: the one place where the kernel form, the rows per thread, the block shape of the filter
+// gradient and its number of partial slices are decided.  The launchers, the scratch size and sat_dwconv3x3_plan all read it from here.
+struct DwPlan {
+    int form;          // 0: generic kernel, 1: rolling window over R rows of one column (stride 1 only)
+    int R;             // rows per thread
+    int cvb;           // filter gradient: channel vectors per block
+    int parts;         // filter gradient: partial [9][C] slices = blocks along x
+    int chunk;         // filter gradient, generic form: output pixels per block
+    long total;        // forward / data gradient: threads
+};
+static DwPlan dw_plan(int op, int V, int N, int H, int W, int C, int stride) {
+    DwPlan p{};
     const int cv = C / V;
-    cvb = cv < 32 ? cv : 32;          // the largest divisor of cv up to 32 (no idle lanes; >= 8 columns in flight per block)
-    while (cv % cvb) --cvb;
-    R = dw_rows((long)N * H * W * cv * 4);          // the reduction wants long columns: 8 rows from 64 k vectors on
-    if (R <= 1) return 0;
-    const int nb = cdiv((long)N * cdiv(H, R) * W, (long)(256 / cvb));
-    return nb < 1024 ? nb : 1024;          // more columns than that: the blocks take several (fewer partials for the finish to add)
+    const int P = (H + 2 - 3) / stride + 1, Q = (W + 2 - 3) / stride + 1;
+    if (op == 0 || op == 1) {          // forward walks the output map (P x Q), the data gradient the input map (H x W)
+        const int rows = op == 0 ? P : H, cols = op == 0 ? Q : W;
+        p.R = dw_rows((long)N * rows * cols * cv);
+        p.form = stride == 1 && p.R > 1;          // (one row per thread: nothing to roll, the plain kernel is 2 us faster on the small maps)
+        p.total = (long)N * cdiv(rows, p.R) * cols * cv;
+        return p;
+    }
+    p.cvb = cv < 32 ? cv : 32;          // the largest divisor of cv up to 32 (no idle lanes; >= 8 columns in flight per block)
+    while (cv % p.cvb) --p.cvb;
+    p.R = dw_rows((long)N * H * W * cv * 4);          // the reduction wants long columns: 8 rows from 64 k vectors on
+    if (stride == 1 && p.R > 1) {          // stride 1, long enough columns: the rolling-window form, one partial per block
+        const int nb = cdiv((long)N * cdiv(H, p.R) * W, (long)(256 / p.cvb));
+        p.form = 1;
+        p.parts = nb < 1024 ? nb : 1024;          // more columns than that: the blocks take several (fewer partials for the finish to add)
+        return p;
+    }
+    p.R = 1;
+    p.chunk = dw_chunk((long)N * P * Q);
+    p.parts = cdiv((long)N * P * Q, (long)p.chunk);
+    return p;
 }
 
 extern "C" {
 
-static int dw_check(const void* a, const void* b, const void* c, int N, int H, int W, int C, int stride, int dtype, const char* what) {
-    if (!a || !b || !c) return fail(SAT_EINVAL, "%s: null pointer", what);
+static int dw_check_shape(int N, int H, int W, int C, int stride, int dtype, const char* what) {
     const int V = dtype ? 8 : 4;
     SAT_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % V == 0 && (stride == 1 || stride == 2), "%s: bad shape (N=%d H=%d W=%d C=%d stride=%d; C %% %d == 0)", what, N, H, W, C,
                 stride, V);
+    return SAT_OK;
+}
+static int dw_check(const void* a, const void* b, const void* c, int N, int H, int W, int C, int stride, int dtype, const char* what) {
+    if (!a || !b || !c) return fail(SAT_EINVAL, "%s: null pointer", what);
+    return dw_check_shape(N, H, W, C, stride, dtype, what);
+}
+
+int sat_dwconv3x3_plan(int32_t op, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t out[4]) {
+    if (!out) return fail(SAT_EINVAL, "dwconv3x3_plan: null pointer");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    SAT_REQUIRE(op >= 0 && op <= 2 && (dtype == 0 || dtype == 1), "dwconv3x3_plan: op=%d (0 forward, 1 data gradient, 2 filter gradient) dtype=%d (0 fp32, 1 bf16)", op, dtype);
+    SAT_TRY(dw_check_shape(N, H, W, C, stride, dtype, "dwconv3x3_plan"));
+    const DwPlan p = dw_plan(op, dtype ? 8 : 4, N, H, W, C, stride);
+    out[0] = p.form; out[1] = p.R; out[2] = p.cvb; out[3] = p.parts;
     return SAT_OK;
 }
 
 int sat_dwconv3x3_fwd_t(int32_t dtype, const void* x, const float* w, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, void* stream) {
     SAT_TRY(dw_check(x, w, y, N, H, W, C, stride, dtype, "dwconv3x3_fwd"));
     const int P = (H + 2 - 3) / stride + 1, Q = (W + 2 - 3) / stride + 1;
-    const int cv = C / (dtype ? 8 : 4), R = dw_rows((long)N * P * Q * cv);
-    const long total = (long)N * cdiv(P, R) * Q * cv;
-    if (stride == 1 && R > 1) {          // (one row per thread: nothing to roll, the plain kernel is 2 us faster on the small maps)
+    const DwPlan p = dw_plan(0, dtype ? 8 : 4, N, H, W, C, stride);
+    const int R = p.R;
+    const long total = p.total;
+    if (p.form) {
         if (dtype) hipLaunchKernelGGL((dw3x3_s1_kernel<bf, false>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const bf*)x, w, (bf*)y, N, H, W, C, R);
         else hipLaunchKernelGGL((dw3x3_s1_kernel<float, false>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x, w, (float*)y, N, H, W, C, R);
         return launch_ok("dwconv3x3_fwd (stride 1)");
@@ -410,9 +449,10 @@ int sat_dwconv3x3_fwd_t(int32_t dtype, const void* x, const float* w, void* y, i
 int sat_dwconv3x3_dgrad_t(int32_t dtype, const void* dy, const float* w, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride, void* stream) {
     SAT_TRY(dw_check(dy, w, dx, N, H, W, C, stride, dtype, "dwconv3x3_dgrad"));
     const int P = (H + 2 - 3) / stride + 1, Q = (W + 2 - 3) / stride + 1;
-    const int cv = C / (dtype ? 8 : 4), R = dw_rows((long)N * H * W * cv);
-    const long total = (long)N * cdiv(H, R) * W * cv;
-    if (stride == 1 && R > 1) {
+    const DwPlan p = dw_plan(1, dtype ? 8 : 4, N, H, W, C, stride);
+    const int R = p.R;
+    const long total = p.total;
+    if (p.form) {
         if (dtype) hipLaunchKernelGGL((dw3x3_s1_kernel<bf, true>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const bf*)dy, w, (bf*)dx, N, H, W, C, R);
         else hipLaunchKernelGGL((dw3x3_s1_kernel<float, true>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, w, (float*)dx, N, H, W, C, R);
         return launch_ok("dwconv3x3_dgrad (stride 1)");
@@ -424,13 +464,11 @@ int sat_dwconv3x3_dgrad_t(int32_t dtype, const void* dy, const float* w, void* d
 
 size_t sat_dwconv3x3_wgrad_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t stride) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (stride != 1 && stride != 2)) return 0;
-    const int P = (H + 2 - 3) / stride + 1, Q = (W + 2 - 3) / stride + 1;
-    size_t parts = (size_t)cdiv((long)N * P * Q, (long)dw_chunk((long)N * P * Q));
-    if (stride == 1)          // the rolling form writes one partial per block; whichever storage type the call will have
-        for (int V = 4; V <= 8; V += 4) {
-            int R, cvb;
-            const size_t nb = C % V ? 0 : (size_t)dw_wgrad_s1_blocks(N, H, W, C, V, R, cvb);
-            if (nb > parts) parts = nb;
+    size_t parts = 0;          // the call's storage type is not known here: the larger plan of the types that accept this C (none: 0 bytes)
+    for (int V = 4; V <= 8; V += 4)
+        if (C % V == 0) {
+            const size_t n = (size_t)dw_plan(2, V, N, H, W, C, stride).parts;
+            if (n > parts) parts = n;
         }
     return parts * 9 * C * sizeof(float);
 }
@@ -441,26 +479,21 @@ int sat_dwconv3x3_wgrad_t(int32_t dtype, const void* dy, const void* x, float* d
     if (!scratch) return fail(SAT_EINVAL, "dwconv3x3_wgrad: null scratch");
     const int V = dtype ? 8 : 4, cv = C / V;
     const int P = (H + 2 - 3) / stride + 1, Q = (W + 2 - 3) / stride + 1;
-    const int chunk = dw_chunk((long)N * P * Q);
-    const int nparts = cdiv((long)N * P * Q, (long)chunk);
-    int R, cvb;
-    int nblk = dw_wgrad_s1_blocks(N, H, W, C, V, R, cvb);          // (also sets cvb for the generic form)
-    if (stride != 1) nblk = 0;
+    const DwPlan p = dw_plan(2, V, N, H, W, C, stride);
+    const int cvb = p.cvb;
     const int pix_par = 256 / cvb;
     const size_t lds = (size_t)pix_par * cvb * V * sizeof(float);
-    if (nblk > 0) {          // stride 1, long enough columns: the rolling-window form
-        const dim3 g1(nblk, cdiv(cv, cvb));
-        if (dtype) hipLaunchKernelGGL(dw3x3_wgrad_s1_kernel<bf>, g1, dim3(256), lds, (hipStream_t)stream, (const bf*)dy, (const bf*)x, scratch, N, H, W, C, R, cvb);
-        else hipLaunchKernelGGL(dw3x3_wgrad_s1_kernel<float>, g1, dim3(256), lds, (hipStream_t)stream, (const float*)dy, (const float*)x, scratch, N, H, W, C, R, cvb);
+    const dim3 grid(p.parts, cdiv(cv, cvb));
+    if (p.form) {
+        if (dtype) hipLaunchKernelGGL(dw3x3_wgrad_s1_kernel<bf>, grid, dim3(256), lds, (hipStream_t)stream, (const bf*)dy, (const bf*)x, scratch, N, H, W, C, p.R, cvb);
+        else hipLaunchKernelGGL(dw3x3_wgrad_s1_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, (const float*)dy, (const float*)x, scratch, N, H, W, C, p.R, cvb);
         SAT_TRY(launch_ok("dwconv3x3_wgrad (stride 1, partials)"));
-        hipLaunchKernelGGL(dw3x3_wgrad_finish_kernel, dim3(9 * C), dim3(64), 0, (hipStream_t)stream, scratch, nblk, C, dw);
-        return launch_ok("dwconv3x3_wgrad (finish)");
+    } else {
+        if (dtype) hipLaunchKernelGGL(dw3x3_wgrad_part_kernel<bf>, grid, dim3(256), lds, (hipStream_t)stream, (const bf*)dy, (const bf*)x, scratch, N, H, W, C, P, Q, stride, p.chunk, cvb);
+        else hipLaunchKernelGGL(dw3x3_wgrad_part_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, (const float*)dy, (const float*)x, scratch, N, H, W, C, P, Q, stride, p.chunk, cvb);
+        SAT_TRY(launch_ok("dwconv3x3_wgrad (partials)"));
     }
-    const dim3 grid(nparts, cdiv(cv, cvb));
-    if (dtype) hipLaunchKernelGGL(dw3x3_wgrad_part_kernel<bf>, grid, dim3(256), lds, (hipStream_t)stream, (const bf*)dy, (const bf*)x, scratch, N, H, W, C, P, Q, stride, chunk, cvb);
-    else hipLaunchKernelGGL(dw3x3_wgrad_part_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, (const float*)dy, (const float*)x, scratch, N, H, W, C, P, Q, stride, chunk, cvb);
-    SAT_TRY(launch_ok("dwconv3x3_wgrad (partials)"));
-    hipLaunchKernelGGL(dw3x3_wgrad_finish_kernel, dim3(9 * C), dim3(64), 0, (hipStream_t)stream, scratch, nparts, C, dw);
+    hipLaunchKernelGGL(dw3x3_wgrad_finish_kernel, dim3(9 * C), dim3(64), 0, (hipStream_t)stream, scratch, p.parts, C, dw);
     return launch_ok("dwconv3x3_wgrad (finish)");
 }
 
