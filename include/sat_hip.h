@@ -353,7 +353,8 @@ int sat_colsum(const float* x, int64_t ld, int64_t rows, int32_t cols, float* ou
  * (drop-in for attention / init_lstm called on their own, e.g. from caption(), model.py:269,299) */
 /* att_enc = ann * W_e^T (model.py:100), hoisted */
 int sat_attention_precompute(const float* ann, const float* att_enc_w, float* U, int32_t B, int32_t L, int32_t D, int32_t A, void* stream);
-/* one SoftAttention.forward + beta gate for N = B*R rows: hc (N, hc_ld) holds [q | beta | ...] */
+/* one SoftAttention.forward + beta gate for N = B*R rows: hc (N, hc_ld) holds [q | beta | ...]; alphas (N, T1, L), written at `step`.
+ * B, R, L, D, A, T1 >= 1, 0 <= step < T1, hc_ld >= A + D, else SAT_EINVAL.  Any D, A and alignment (they only select the kernel). */
 int sat_attention_step_fwd(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f,
                            const int32_t* lengths, int32_t step, float* alphas, int32_t T1, float* Z, float* XZ,
                            int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, void* stream);
@@ -367,6 +368,31 @@ int sat_attention_step_fwd(const float* ann, const float* U, const float* hc, in
 int sat_attention_step_bwd(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths, int32_t step,
                            const float* alphas, const float* dalphas, int32_t T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
                            int32_t dhc_ld, float* dU, float* dwf_part, float* da_scratch, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, void* stream);
+/* The two step entry points with the operands only the train loop used to reach; every extra pointer may be NULL, which gives the plain call.
+ *   scores_scratch (B*R, L) floats: lets the forward run as the split pair (scores + context kernels) where the shape allows it;
+ *   ann_bf16 (B, L, D): a bf16 copy of ann that the context / dalpha kernels stream instead of ann (products and sums stay fp32);
+ *   xz_bf16 (B*R, D) / dhc_bf16 (B*R, dhc_ld): bf16 copies of XZ and of dhc[:, 0:A+D], written next to the fp32 outputs.
+ * The bf16 operands exist in the split kernels only: a shape or view that the plan sends to the single launch refuses them (SAT_EINVAL). */
+int sat_attention_step_fwd_ex(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f,
+                              const int32_t* lengths, int32_t step, float* alphas, int32_t T1, float* Z, float* XZ,
+                              int32_t B, int32_t R, int32_t L, int32_t D, int32_t A,
+                              float* scores_scratch, const void* ann_bf16, void* xz_bf16, void* stream);
+int sat_attention_step_bwd_ex(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths, int32_t step,
+                              const float* alphas, const float* dalphas, int32_t T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
+                              int32_t dhc_ld, float* dU, float* dwf_part, float* da_scratch, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A,
+                              const void* ann_bf16, void* dhc_bf16, void* stream);
+/* The launch plan of one attention call (host arithmetic only, no device is touched; the launchers read the same function).
+ * op: 0 sat_attention_step_fwd, 1 sat_attention_step_bwd, 2 sat_attention_context_bwd (A, hc_ld and flags are ignored).
+ * flags: 1 a score / dalpha scratch is passed, 2 ann (and its bf16 copy) is 16-byte (8-byte) aligned, 4 hc, Z and XZ are 16-byte aligned
+ * (forward only), 8 a bf16 operand is passed.
+ * out: [0] form (0 split pair, 1 single launch), [1] caption rows per pass RN, [2] passes, [3] floats per annotation load VW,
+ * [4] features per block of the forward (dchunk), [5] NQ and [6] Lq of the context backward, [7] dynamic LDS bytes of the scores /
+ * dalpha / single kernel, [8] of the context / tanh kernel.  A shape no call accepts returns SAT_EINVAL and zeros. */
+#define SAT_ATT_PLAN_SCRATCH 1
+#define SAT_ATT_PLAN_ANN_ALIGNED 2
+#define SAT_ATT_PLAN_ROWS_ALIGNED 4
+#define SAT_ATT_PLAN_BF16 8
+int sat_attention_step_plan(int32_t op, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, int32_t hc_ld, int32_t T1, int32_t flags, int32_t out[9]);
 /* dann[b, l, :] (+)= sum over the image's R captions and their live steps t < lengths of alphas[b*R + r, t, l] * DZ[t, b*R + r, :]
  * (alphas (B*R, T1, L); DZ time-major (T1, B*R, D)) */
 int sat_attention_context_bwd(const float* alphas, const float* DZ, const int32_t* lengths, float* dann, int32_t accumulate, int32_t B, int32_t R, int32_t T1,

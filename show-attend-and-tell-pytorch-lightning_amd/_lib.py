@@ -265,6 +265,10 @@ SYMBOLS.update({
     "sat_attention_step_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                          _i32, _i32, _i32, _i32, _i32, _vp]),
     "sat_attention_context_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sat_attention_step_fwd_ex": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "sat_attention_step_bwd_ex": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                            _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "sat_attention_step_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     "sat_lstm_cell_fwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "sat_lstm_cell_bwd": (C.c_int, [_vp, _i32] + [_vp] * 17 + [_i32, _i32, _vp]),
     "sat_deep_output_fwd": (C.c_int, [_vp] * 7 + [_f, _u64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

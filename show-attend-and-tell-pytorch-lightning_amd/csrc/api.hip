@@ -298,22 +298,45 @@ int sat_attention_precompute(const float* ann, const float* att_enc_w, float* U,
     GemmArgs g; g.A = ann; g.lda = D; g.B = att_enc_w; g.ldb = D; g.C = U; g.ldc = A; g.M = B * L; g.N = A; g.K = D;
     return launch_gemm(g, (hipStream_t)stream);
 }
+int sat_attention_step_fwd_ex(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths,
+                              int32_t step, float* alphas, int32_t T1, float* Z, float* XZ, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A,
+                              float* scores_scratch, const void* ann_bf16, void* xz_bf16, void* stream) {
+    if (!ann || !U || !hc || !att_f || !lengths || !alphas || !Z || !XZ) return fail(SAT_EINVAL, "attention_step_fwd: null pointer");
+    if (B < 1 || R < 1 || L < 1 || D < 1 || A < 1 || T1 < 1 || step < 0 || step >= T1) return fail(SAT_EINVAL, "attention_step_fwd: bad shape");
+    if (hc_ld < A + D) return fail(SAT_EINVAL, "attention_step_fwd: hc_ld %d < A+D", hc_ld);
+    return launch_attention_fwd((hipStream_t)stream, ann, U, hc, hc_ld, att_f, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, scores_scratch, xz_bf16, ann_bf16);
+}
 int sat_attention_step_fwd(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths,
                            int32_t step, float* alphas, int32_t T1, float* Z, float* XZ, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, void* stream) {
-    if (!ann || !U || !hc || !att_f || !lengths || !alphas || !Z || !XZ) return fail(SAT_EINVAL, "attention_step_fwd: null pointer");
-    if (hc_ld < A + D) return fail(SAT_EINVAL, "attention_step_fwd: hc_ld %d < A+D", hc_ld);
-    return launch_attention_fwd((hipStream_t)stream, ann, U, hc, hc_ld, att_f, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A);
+    return sat_attention_step_fwd_ex(ann, U, hc, hc_ld, att_f, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, nullptr, nullptr, nullptr, stream);
 }
 
-int sat_attention_step_bwd(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths, int32_t step,
-                           const float* alphas, const float* dalphas, int32_t T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
-                           int32_t dhc_ld, float* dU, float* dwf_part, float* da_scratch, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, void* stream) {
+int sat_attention_step_bwd_ex(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths, int32_t step,
+                              const float* alphas, const float* dalphas, int32_t T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
+                              int32_t dhc_ld, float* dU, float* dwf_part, float* da_scratch, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A,
+                              const void* ann_bf16, void* dhc_bf16, void* stream) {
     if (!ann || !U || !hc || !att_f || !lengths || !alphas || !Z || !dZ || !dXZ || !DZ || !dhc || !dU || !dwf_part || !da_scratch)
         return fail(SAT_EINVAL, "attention_step_bwd: null pointer");
     if (hc_ld < A + D || dhc_ld < A + D) return fail(SAT_EINVAL, "attention_step_bwd: hc_ld %d / dhc_ld %d < A+D", hc_ld, dhc_ld);
     if (B < 1 || R < 1 || L < 1 || D < 1 || A < 1 || T1 < 1 || step < 0 || step >= T1) return fail(SAT_EINVAL, "attention_step_bwd: bad shape");
-    return attention_step_bwd(ann, U, hc, hc_ld, att_f, lengths, step, alphas, dalphas, T1, Z, dZ, dXZ, DZ, dhc, dhc_ld, dU, dwf_part, da_scratch, B, R, L, D, A,
-                              (hipStream_t)stream);
+    return launch_attention_bwd((hipStream_t)stream, ann, U, hc, hc_ld, att_f, lengths, step, alphas, dalphas, T1, Z, dZ, dXZ, DZ, dhc, dhc_ld, dU, dwf_part,
+                                da_scratch, B, R, L, D, A, dhc_bf16, ann_bf16);
+}
+int sat_attention_step_bwd(const float* ann, const float* U, const float* hc, int32_t hc_ld, const float* att_f, const int32_t* lengths, int32_t step,
+                           const float* alphas, const float* dalphas, int32_t T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
+                           int32_t dhc_ld, float* dU, float* dwf_part, float* da_scratch, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, void* stream) {
+    return sat_attention_step_bwd_ex(ann, U, hc, hc_ld, att_f, lengths, step, alphas, dalphas, T1, Z, dZ, dXZ, DZ, dhc, dhc_ld, dU, dwf_part, da_scratch,
+                                     B, R, L, D, A, nullptr, nullptr, stream);
+}
+int sat_attention_step_plan(int32_t op, int32_t B, int32_t R, int32_t L, int32_t D, int32_t A, int32_t hc_ld, int32_t T1, int32_t flags, int32_t out[9]) {
+    if (!out) return fail(SAT_EINVAL, "attention_step_plan: null pointer");
+    for (int i = 0; i < 9; ++i) out[i] = 0;
+    if (B < 1) return fail(SAT_EINVAL, "attention_step_plan: B=%d", B);
+    if (flags < 0 || flags > 15) return fail(SAT_EINVAL, "attention_step_plan: flags=%d outside 0..15", flags);
+    AttPlan p;
+    SAT_TRY(attention_plan(op, R, L, D, A, hc_ld, T1, (unsigned)flags, p, "attention_step_plan"));
+    out[0] = p.form; out[1] = p.rn; out[2] = p.passes; out[3] = p.vw; out[4] = p.dchunk; out[5] = p.nq; out[6] = p.lq; out[7] = (int32_t)p.lds0; out[8] = (int32_t)p.lds1;
+    return SAT_OK;
 }
 int sat_attention_context_bwd(const float* alphas, const float* DZ, const int32_t* lengths, float* dann, int32_t accumulate, int32_t B, int32_t R, int32_t T1,
                               int32_t L, int32_t D, void* stream) {

@@ -11,6 +11,17 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                 char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,
                 const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st);
+// launch plan of one attention step (decoder.hip: attention_plan decides it, the launchers and sat_attention_step_plan read it)
+enum { ATT_OP_FWD = 0, ATT_OP_BWD = 1, ATT_OP_CONTEXT_BWD = 2 };
+enum { ATT_FORM_SPLIT = 0, ATT_FORM_SINGLE = 1 };
+enum : unsigned { ATT_HAS_SCRATCH = 1, ATT_ANN_ALIGNED = 2, ATT_ROWS_ALIGNED = 4, ATT_HAS_BF16 = 8 };
+struct AttPlan {
+    int form = 0, rn = 0, passes = 0;          // split pair or single launch; caption rows per pass; passes over the R rows of an image
+    int vw = 0, dchunk = 0;                    // floats per annotation load; forward: features per block
+    int nq = 0, lq = 0;                        // context backward: float4 per location slab, float4 per padded alphas row
+    size_t lds0 = 0, lds1 = 0;                 // dynamic LDS bytes: scores | dalpha | the single kernel, and context | tanh
+};
+int attention_plan(int op, int R, int L, int D, int A, int hc_ld, int T1, unsigned flags, AttPlan& plan, const char* who);
 int launch_attention_fwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf,
                          const int* lengths, int step, float* alphas, int T1, float* Z, float* XZ, int B, int R, int L, int D, int A, float* sc = nullptr, void* xzb = nullptr,
                          const void* annb = nullptr);
@@ -24,9 +35,9 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                          int n_temps, const int* special_host, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row,
                          float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
                          const sat_beam_constraints* constraints = nullptr);
-int attention_step_bwd(const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step, const float* alphas,
-                       const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc, int dhc_ld, float* dU,
-                       float* dwf_part, float* da, int B, int R, int L, int D, int A, hipStream_t st);
+int launch_attention_bwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
+                         const float* alphas, const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
+                         int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, void* dhcb = nullptr, const void* annb = nullptr);
 int attention_context_bwd(const float* alphas, const float* DZ, const int* lengths, float* dann, int accumulate, int B, int R, int T1, int L, int D, hipStream_t st);
 int lstm_cell_fwd(const float* x, int in, const float* h_prev, const float* c_prev, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                   float* gates, float* h_new, float* c_new, float* bias_scratch, int N, int n, hipStream_t st);

@@ -66,7 +66,7 @@ Ws layout(const sat_decoder_dims& d, char* base) {
     }
     w.Hb = w.XZb = w.Wcat_b = w.Wz_b = w.DHCb = nullptr;
     // bf16 mode: a bf16 copy of the annotations for the two kernels that stream them every time step (attention context / dalpha)
-    w.annb = (d.precision && d.D % 4 == 0) ? (__bf16*)take((size_t)d.B * d.L * d.D, 2) : nullptr;
+    w.annb = (d.precision && d.D % 4 == 0 && d.A % 4 == 0) ? (__bf16*)take((size_t)d.B * d.L * d.D, 2) : nullptr;
     if (d.precision && d.layers == 1 && d.n % 64 == 0 && d.D % 64 == 0 && d.A % 4 == 0 && d.m % 4 == 0) {
         w.Hb = (__bf16*)take((size_t)(T1 + 1) * N * d.n, 2); w.XZb = (__bf16*)take((size_t)N * d.D, 2);
         w.Wcat_b = (__bf16*)take((size_t)HCW * d.n, 2); w.Wz_b = (__bf16*)take((size_t)4 * d.n * d.D, 2);
@@ -169,6 +169,66 @@ static int live_steps(const sat_decoder_dims& d, const sat_decoder_batch& b) {
 static size_t att_fwd_lds(int L, int A, int vw) { return (size_t)(ATT_RMAX * L + ATT_RMAX * A + A + ATT_RMAX * ATT_THREADS * vw) * 4; }
 static size_t att_bwd_lds(int L, int A, int D) { return (size_t)(2 * ATT_RMAX * L + ATT_RMAX * A + A + ATT_RMAX * D + ATTB_WAVES * ATT_RMAX * A + ATTB_WAVES * A) * 4; }
 
+// The one place where the launch form of the attention step is decided.  launch_attention_fwd, launch_attention_bwd, attention_context_bwd
+// and the query sat_attention_step_plan all read it from here.
+//   forward  split : scores + context kernels.  Needs the score scratch, D, A and hc_ld multiples of 4 (float4 reads of the gate and of the
+//                    annotations, float4 stores of Z / XZ) and ann, hc, Z, XZ on 16-byte boundaries.
+//            single: attention_fwd_kernel<VW, RN>; VW = 4 (256-wide chunks of D) when D % 4 == 0 and ann is 16-byte aligned, else VW = 1 (64-wide).
+//   backward split : dalpha + tanh kernels.  The dalpha kernel walks D in 16-byte vectors of ann and of its dz rows in LDS: D % 4 == 0 and
+//                    ann on a 16-byte boundary (its bf16 copy on an 8-byte one).  The tanh kernel is scalar in A, L and every pointer.
+//            single: attention_bwd_kernel<RN>, scalar throughout: any D, A, alignment.
+//   context bwd    : dann_from_context_kernel<NQ>, scalar in D; NQ float4 of a (zero-padded) alphas row per slab.
+// The bf16 copies (annotation stream in, gated context / dhc out) exist in the split kernels only.
+int attention_plan(int op, int R, int L, int D, int A, int hc_ld, int T1, unsigned flags, AttPlan& p, const char* who) {
+    p = AttPlan();
+    SAT_REQUIRE(op >= ATT_OP_FWD && op <= ATT_OP_CONTEXT_BWD, "%s: op=%d (0 forward, 1 backward, 2 context backward)", who, op);
+    SAT_REQUIRE(R >= 1 && L >= 1 && D >= 1 && T1 >= 1 && (op == ATT_OP_CONTEXT_BWD || (A >= 1 && hc_ld >= A + D)),
+                "%s: bad shape (R=%d L=%d D=%d A=%d hc_ld=%d T1=%d)", who, R, L, D, A, hc_ld, T1);
+    const bool scratch = flags & ATT_HAS_SCRATCH, ann_al = flags & ATT_ANN_ALIGNED, rows_al = flags & ATT_ROWS_ALIGNED;
+    p.rn = R < ATT_RMAX ? R : ATT_RMAX;            // rows per pass, compile-time in the kernels
+    p.passes = cdiv(R, p.rn);
+    const int RN = p.rn;
+    if (op == ATT_OP_FWD) {
+        if (scratch && D % 4 == 0 && A % 4 == 0 && hc_ld % 4 == 0 && ann_al && rows_al) {
+            p.form = ATT_FORM_SPLIT; p.vw = 4; p.dchunk = ATTC_DCH;
+            p.lds0 = (size_t)(RN * A + A) * 4;                                                   // scores: [RN][A] q, [A] w
+            p.lds1 = (size_t)((RN * L + 3) & ~3) * 4 + (size_t)16 * RN * 16 * 16;                // context: [RN][L] alpha, [16][RN][16] float4
+        } else {
+            p.form = ATT_FORM_SINGLE;
+            const bool vec = D % 4 == 0 && ann_al;
+            p.vw = vec ? 4 : 1;
+            p.dchunk = vec ? 256 : 64;
+            if (p.dchunk > D) p.dchunk = D;
+            p.lds0 = att_fwd_lds(L, A, p.vw);
+        }
+    } else if (op == ATT_OP_BWD) {
+        if (scratch && D % 4 == 0 && ann_al) {
+            p.form = ATT_FORM_SPLIT; p.vw = 4;
+            p.lds0 = (size_t)RN * D * 4;                                                         // dalpha: [RN][D] dz
+            p.lds1 = (size_t)(RN * L + RN * ATTB_KCH + 32 * (RN + 1) * ATTB_KCH) * 4;            // tanh: [RN][L] ds, [RN][32] q, [32][RN + 1][32]
+        } else {
+            p.form = ATT_FORM_SINGLE; p.vw = 1;
+            p.lds0 = att_bwd_lds(L, A, D);
+        }
+    } else {
+        // location slab = NQ float4 per LDS row: 13 covers L <= 52 (7x7 maps) in one pass, 16 the 8x8 / 14x14 maps
+        const int lq4 = (L + 3) / 4;
+        p.form = ATT_FORM_SINGLE; p.rn = R; p.passes = 1; p.vw = 1;
+        p.nq = (lq4 <= 13) ? 13 : 16;
+        p.lq = (lq4 + p.nq - 1) / p.nq * p.nq;
+        p.lds0 = (size_t)R * T1 * p.lq * 16;
+    }
+    if ((flags & ATT_HAS_BF16) && p.form != ATT_FORM_SPLIT) { p = AttPlan(); SAT_REQUIRE(false, "%s: the bf16 copies need the split kernels (aligned shapes)", who); }
+    if (p.lds0 > 160 * 1024 || p.lds1 > 160 * 1024) {
+        const size_t need = p.lds0 > p.lds1 ? p.lds0 : p.lds1;
+        p = AttPlan();
+        SAT_REQUIRE(false, "%s: R=%d L=%d D=%d A=%d T1=%d need %zu B of LDS (> 160 KiB)", who, R, L, D, A, T1, need);
+    }
+    return SAT_OK;
+}
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 static bool ann_bf16_enabled() { static const bool off = getenv("SAT_ANN_BF16") && !atoi(getenv("SAT_ANN_BF16")); return !off; }      // dev switch
 static bool attention_split_enabled() {
     static const int no_split = getenv("SAT_ATT_FUSED") ? atoi(getenv("SAT_ATT_FUSED")) : 0;
@@ -176,9 +236,8 @@ static bool attention_split_enabled() {
 }
 template <int RN, typename TA>
 static int attention_fwd_split(hipStream_t st, const TA* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
-                               float* alphas, int T1, float* Z, float* XZ, int B, int R, int L, int D, int A, float* sc, __bf16* xzb) {
-    const size_t lds_s = (size_t)(RN * A + A) * 4, lds_c = (size_t)((RN * L + 3) & ~3) * 4 + (size_t)16 * RN * 16 * 16;
-    SAT_REQUIRE(lds_s <= 160 * 1024 && lds_c <= 160 * 1024, "attention_fwd: L=%d A=%d do not fit the LDS", L, A);
+                               float* alphas, int T1, float* Z, float* XZ, int B, int R, int L, int D, int A, float* sc, __bf16* xzb, const AttPlan& pl) {
+    const size_t lds_s = pl.lds0, lds_c = pl.lds1;
     SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_scores_kernel<RN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
     SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_context_kernel<RN, TA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
     // algorithmic bytes (per image-step): scores read att_enc U (L x A fp32) and the R query rows, write R x L raw scores; context streams the
@@ -200,37 +259,36 @@ int launch_attention_fwd(hipStream_t st, const float* ann, const float* U, const
     __bf16* xzb = reinterpret_cast<__bf16*>(xzb_v);
     const __bf16* annb = reinterpret_cast<const __bf16*>(annb_v);          // bf16 copy of ann for the context stream (split kernels only), or NULL
     static const int no_split = getenv("SAT_ATT_FUSED") ? atoi(getenv("SAT_ATT_FUSED")) : 0;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (sc && !no_split && D % 4 == 0 && A % 4 == 0 && hc_ld % 4 == 0 && al16(ann) && al16(hc) && al16(Z) && al16(XZ)) {
+    const unsigned flags = (sc && !no_split ? ATT_HAS_SCRATCH : 0u) | (al16(ann) && (!annb || al8(annb)) ? ATT_ANN_ALIGNED : 0u) |
+                           (al16(hc) && al16(Z) && al16(XZ) ? ATT_ROWS_ALIGNED : 0u) | (xzb || annb ? ATT_HAS_BF16 : 0u);
+    AttPlan pl;
+    SAT_TRY(attention_plan(ATT_OP_FWD, R, L, D, A, hc_ld, T1, flags, pl, "attention_fwd"));
+    if (pl.form == ATT_FORM_SPLIT) {
         // scores and context as two chip-wide launches (scratch: raw scores (B*R, L))
-        switch (R < ATT_RMAX ? R : ATT_RMAX) {
-            case 1: return annb ? attention_fwd_split<1, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<1, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            case 2: return annb ? attention_fwd_split<2, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<2, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            case 3: return annb ? attention_fwd_split<3, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<3, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            case 4: return annb ? attention_fwd_split<4, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<4, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            case 5: return annb ? attention_fwd_split<5, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<5, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            case 6: return annb ? attention_fwd_split<6, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<6, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            case 7: return annb ? attention_fwd_split<7, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                : attention_fwd_split<7, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
-            default: return annb ? attention_fwd_split<8, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb)
-                                 : attention_fwd_split<8, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb);
+        switch (pl.rn) {
+            case 1: return annb ? attention_fwd_split<1, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<1, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            case 2: return annb ? attention_fwd_split<2, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<2, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            case 3: return annb ? attention_fwd_split<3, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<3, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            case 4: return annb ? attention_fwd_split<4, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<4, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            case 5: return annb ? attention_fwd_split<5, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<5, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            case 6: return annb ? attention_fwd_split<6, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<6, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            case 7: return annb ? attention_fwd_split<7, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                : attention_fwd_split<7, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
+            default: return annb ? attention_fwd_split<8, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl)
+                                 : attention_fwd_split<8, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, B, R, L, D, A, sc, xzb, pl);
         }
     }
-    SAT_REQUIRE(!xzb && !annb, "attention_fwd: the bf16 copies need the split kernels (aligned shapes)");
-    const bool vec = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(ann) & 15) == 0);
-    const int vw = vec ? 4 : 1;
-    int dchunk = vec ? 256 : 64;
-    if (dchunk > D) dchunk = D;
-    size_t lds = att_fwd_lds(L, A, vw);
-    SAT_REQUIRE(lds <= 160 * 1024, "attention_fwd: L=%d A=%d need %zu B of LDS (> 160 KiB)", L, A, lds);
+    const bool vec = pl.vw == 4;
+    const int dchunk = pl.dchunk;
+    const size_t lds = pl.lds0;
     dim3 grid(B, cdiv(D, dchunk));
-    const int RN = R < ATT_RMAX ? R : ATT_RMAX;            // rows per pass, compile-time in the kernel
+    const int RN = pl.rn;
 #define SAT_ATTF(VWV, RNV)                                                                                                                  \
     case RNV:                                                                                                                               \
         SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fwd_kernel<VWV, RNV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
@@ -248,9 +306,8 @@ int launch_attention_fwd(hipStream_t st, const float* ann, const float* U, const
 template <int RN, typename TA>
 static int attention_bwd_split_t(hipStream_t st, const TA* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
                                  const float* alphas, const float* dalphas, int T1, const float* Zs, const float* dZ_out, const float* dXZ, float* DZ, float* dhc,
-                                 int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, __bf16* dhcb) {
-    const size_t lds_a = (size_t)RN * D * 4, lds_t = (size_t)(RN * L + RN * ATTB_KCH + 32 * (RN + 1) * ATTB_KCH) * 4;
-    SAT_REQUIRE(lds_a <= 160 * 1024 && lds_t <= 160 * 1024, "attention_bwd: L=%d D=%d do not fit the LDS", L, D);
+                                 int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, __bf16* dhcb, const AttPlan& pl) {
+    const size_t lds_a = pl.lds0, lds_t = pl.lds1;
     SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_dalpha_kernel<RN, TA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
     SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_tanh_kernel<RN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
     // algorithmic bytes: dalpha streams the annotations once per image, reads the R gradient rows of z / gated z / the gate (3 x D) and z, writes dz and
@@ -267,13 +324,35 @@ static int attention_bwd_split_t(hipStream_t st, const TA* ann, const float* U, 
                        dwf_part, R, L, A, dhcb);
     return launch_ok("attention_bwd_tanh");
 }
-static int attention_bwd_split(int RN, hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
-                               const float* alphas, const float* dalphas, int T1, const float* Zs, const float* dZ_out, const float* dXZ, float* DZ, float* dhc,
-                               int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, __bf16* dhcb, const __bf16* annb = nullptr) {
-#define SAT_ATTB(RNV) case RNV: return annb ? attention_bwd_split_t<RNV, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Zs, dZ_out, dXZ, DZ, dhc, dhc_ld, dU, dwf_part, da, B, R, L, D, A, dhcb) \
-                                            : attention_bwd_split_t<RNV, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Zs, dZ_out, dXZ, DZ, dhc, dhc_ld, dU, dwf_part, da, B, R, L, D, A, dhcb);
-    switch (RN) { SAT_ATTB(1) SAT_ATTB(2) SAT_ATTB(3) SAT_ATTB(4) SAT_ATTB(5) SAT_ATTB(6) SAT_ATTB(7) default: SAT_ATTB(8) }
+// One attention backward step in the form attention_plan decides; `da` ((B*R, L) floats, or NULL) is the split pair's scratch.
+int launch_attention_bwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
+                         const float* alphas, const float* dalphas, int T1, const float* Zs, const float* dZ_out, const float* dXZ, float* DZ, float* dhc,
+                         int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, void* dhcb_v, const void* annb_v) {
+    __bf16* dhcb = reinterpret_cast<__bf16*>(dhcb_v);
+    const __bf16* annb = reinterpret_cast<const __bf16*>(annb_v);
+    const unsigned flags = (da ? ATT_HAS_SCRATCH : 0u) | (al16(ann) && (!annb || al8(annb)) ? ATT_ANN_ALIGNED : 0u) | (dhcb || annb ? ATT_HAS_BF16 : 0u);
+    AttPlan pl;
+    SAT_TRY(attention_plan(ATT_OP_BWD, R, L, D, A, hc_ld, T1, flags, pl, "attention_bwd"));
+    SAT_REQUIRE(dhc_ld >= A + D, "attention_bwd: dhc_ld %d < A+D", dhc_ld);
+    if (pl.form == ATT_FORM_SPLIT) {
+#define SAT_ATTB(RNV) case RNV: return annb ? attention_bwd_split_t<RNV, __bf16>(st, annb, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Zs, dZ_out, dXZ, DZ, dhc, dhc_ld, dU, dwf_part, da, B, R, L, D, A, dhcb, pl) \
+                                            : attention_bwd_split_t<RNV, float>(st, ann, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Zs, dZ_out, dXZ, DZ, dhc, dhc_ld, dU, dwf_part, da, B, R, L, D, A, dhcb, pl);
+        switch (pl.rn) { SAT_ATTB(1) SAT_ATTB(2) SAT_ATTB(3) SAT_ATTB(4) SAT_ATTB(5) SAT_ATTB(6) SAT_ATTB(7) default: SAT_ATTB(8) }
 #undef SAT_ATTB
+    }
+    // one block per image, scalar in D and A: the shapes and views the vector loads of the dalpha kernel cannot take (and the dev switch)
+    typedef void (*attb_fn)(const float*, const float*, const float*, int, const float*, const int*, int, const float*, const float*, int, const float*,
+                            const float*, const float*, float*, float*, int, float*, float*, int, int, int, int);
+    attb_fn attb = nullptr;
+    switch (pl.rn) {
+        case 1: attb = attention_bwd_kernel<1>; break; case 2: attb = attention_bwd_kernel<2>; break; case 3: attb = attention_bwd_kernel<3>; break;
+        case 4: attb = attention_bwd_kernel<4>; break; case 5: attb = attention_bwd_kernel<5>; break; case 6: attb = attention_bwd_kernel<6>; break;
+        case 7: attb = attention_bwd_kernel<7>; break; default: attb = attention_bwd_kernel<8>; break;
+    }
+    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds0));
+    hipLaunchKernelGGL(attb, dim3(B), dim3(ATTB_THREADS), pl.lds0, st, ann, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Zs, dZ_out, dXZ, DZ, dhc, dhc_ld,
+                       dU, dwf_part, R, L, D, A);
+    return launch_ok("attention_bwd");
 }
 
 // ------------------------------------------------------------------ output stage for packed rows [p0, p1)
@@ -361,7 +440,7 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
 
     // bf16 mode, one layer: the per-step GEMMs read bf16 copies (state written by the cell kernel, gated context by the attention
     // kernel, weights cast here once) through the direct-to-LDS kernel instead of rounding fp32 operands in registers every step
-    const __bf16* annb = (w.annb && attention_split_enabled() && ann_bf16_enabled()) ? w.annb : nullptr;
+    const __bf16* annb = (w.annb && attention_split_enabled() && ann_bf16_enabled() && al16(b.ann)) ? w.annb : nullptr;
     if (annb) SAT_TRY(cast_bf16(st, b.ann, w.annb, (long)d.B * d.L * D));
     if (use_b) {
         hipLaunchKernelGGL(cast_block_bf16_kernel, dim3(cdiv((long)4 * n * (D / 4), 256)), dim3(256), 0, st, p.w_ih + m, (long)(m + D), w.Wz_b, 4 * n, D);
@@ -498,20 +577,9 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         SAT_TRY(dev_fill_bytes(st, w.dY, 0, (size_t)T1 * N * m * 4));     // shallow output does not see the embedding
 
     // ---- back through time
-    const size_t lds_b = att_bwd_lds(d.L, A, D);
-    SAT_REQUIRE(lds_b <= 160 * 1024, "attention_bwd: L=%d A=%d D=%d need %zu B of LDS (> 160 KiB)", d.L, A, D, lds_b);
     static const int att_fused = getenv("SAT_ATT_FUSED") ? atoi(getenv("SAT_ATT_FUSED")) : 0;
     const bool use_b = w.Hb != nullptr && !att_fused;           // bf16 operand copies (the forward cast the weights into Wcat_b / Wz_b)
-    const __bf16* annb = (w.annb && !att_fused && ann_bf16_enabled()) ? w.annb : nullptr;      // the forward left the bf16 annotations there
-    typedef void (*attb_fn)(const float*, const float*, const float*, int, const float*, const int*, int, const float*, const float*, int, const float*,
-                            const float*, const float*, float*, float*, int, float*, float*, int, int, int, int);
-    attb_fn attb = nullptr;
-    switch (d.R < ATT_RMAX ? d.R : ATT_RMAX) {           // rows per pass are compile-time in the kernel
-        case 1: attb = attention_bwd_kernel<1>; break; case 2: attb = attention_bwd_kernel<2>; break; case 3: attb = attention_bwd_kernel<3>; break;
-        case 4: attb = attention_bwd_kernel<4>; break; case 5: attb = attention_bwd_kernel<5>; break; case 6: attb = attention_bwd_kernel<6>; break;
-        case 7: attb = attention_bwd_kernel<7>; break; default: attb = attention_bwd_kernel<8>; break;
-    }
-    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
+    const __bf16* annb = (w.annb && !att_fused && ann_bf16_enabled() && al16(b.ann)) ? w.annb : nullptr;      // the forward left the bf16 annotations there
     for (int t = ts - 1; t >= 0; --t) {
         const float* hc = w.HC + (long)t * N * HCW;
         float* dhc = w.DHC + (long)t * N * HCW;
@@ -530,15 +598,10 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         // d(beta*z) = dG * W_ih[:, m:]
         if (use_b) SAT_TRY(gemm_bb_nn(st, w.DHCb + A + D, HCW, w.Wz_b, D, w.dXZ, D, N, D, 4 * n, 0, slab, se));
         else SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dhc + A + D, HCW, p.w_ih + m, m + D, w.dXZ, D, N, D, 4 * n, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
-        if (!att_fused) {
-            SAT_TRY(attention_bwd_split(d.R < ATT_RMAX ? d.R : ATT_RMAX, st, b.ann, w.U, hc, HCW, p.att_f, b.lengths, t, alphas, dalphas, T1, w.Z + (long)t * N * D,
-                                        w.dZout + (long)t * N * D, w.dXZ, w.DZ + (long)t * N * D, dhc, HCW, w.dU, w.dwf_part, w.DA, d.B, d.R, d.L, D, A,
-                                        use_b ? w.DHCb : nullptr, annb));
-        } else
-        hipLaunchKernelGGL(attb, dim3(d.B), dim3(ATTB_THREADS), lds_b, st, b.ann, w.U, hc, HCW, p.att_f, b.lengths, t, alphas,
-                           dalphas, T1, w.Z + (long)t * N * D, w.dZout + (long)t * N * D, w.dXZ, w.DZ + (long)t * N * D, dhc, HCW, w.dU, w.dwf_part,
-                           d.R, d.L, D, A);
-        SAT_TRY(launch_ok("attention_bwd"));
+        // the dev switch withholds the scratch: the single-launch form
+        SAT_TRY(launch_attention_bwd(st, b.ann, w.U, hc, HCW, p.att_f, b.lengths, t, alphas, dalphas, T1, w.Z + (long)t * N * D, w.dZout + (long)t * N * D, w.dXZ,
+                                     w.DZ + (long)t * N * D, dhc, HCW, w.dU, w.dwf_part, att_fused ? nullptr : w.DA, d.B, d.R, d.L, D, A,
+                                     use_b ? w.DHCb : nullptr, annb));
         // dh_{t-1} += [dq | dbeta_pre | dG] * Wcat
         if (use_b) {
             SAT_TRY(gemm_bb_nn(st, w.DHCb, HCW, w.Wcat_b, n, w.dHc, n, N, n, HCW, 1, slab, se));
@@ -590,22 +653,7 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     SAT_TRY(colsum(st, w, w.dwf_part, A, d.B, A, g.att_f));
     SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.dU, A, b.ann, D, g.att_enc, D, A, D, d.B * d.L, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
     SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dU, A, p.att_enc, D, dann, D, d.B * d.L, D, A));
-    {
-        // location slab = NQ float4 per LDS row: 13 covers L <= 52 (7x7 maps) in one pass, 16 the 8x8 / 14x14 maps
-        const int lq4 = (d.L + 3) / 4;
-        const int NQ = (lq4 <= 13) ? 13 : 16;
-        const int Lq = (lq4 + NQ - 1) / NQ * NQ;
-        const size_t lds_dann = (size_t)d.R * T1 * Lq * 16;
-        SAT_REQUIRE(lds_dann <= 160 * 1024, "dann_from_context: R*(T-1)*L = %d floats of alphas do not fit the LDS", d.R * T1 * d.L);
-        if (NQ == 13) {
-            SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dann_from_context_kernel<13>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dann));
-            hipLaunchKernelGGL(dann_from_context_kernel<13>, dim3(d.B, cdiv(D, 256)), dim3(256), lds_dann, st, alphas, w.DZ, b.lengths, dann, 1, d.R, N, T1, d.L, D);
-        } else {
-            SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dann_from_context_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dann));
-            hipLaunchKernelGGL(dann_from_context_kernel<16>, dim3(d.B, cdiv(D, 256)), dim3(256), lds_dann, st, alphas, w.DZ, b.lengths, dann, 1, d.R, N, T1, d.L, D);
-        }
-    }
-    SAT_TRY(launch_ok("dann_from_context"));
+    SAT_TRY(attention_context_bwd(alphas, w.DZ, b.lengths, dann, 1, d.B, d.R, T1, d.L, D, st));
     // InitLSTM backward (the raw reshape is a reinterpretation: gradients of the repeated rows add up per image)
     if (d.dropout > 0.f) {                 // per-caption-row path (see decoder_fwd)
         const int n2 = 2 * n * NL;
@@ -948,21 +996,11 @@ static int fill_f(hipStream_t st, float* p, long n, float v) {
     return launch_ok("fill");
 }
 
-int attention_step_bwd(const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step, const float* alphas,
-                       const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc, int dhc_ld, float* dU,
-                       float* dwf_part, float* da, int B, int R, int L, int D, int A, hipStream_t st) {
-    t_bf16_mfma = 0;
-    return attention_bwd_split(R < ATT_RMAX ? R : ATT_RMAX, st, ann, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Z, dZ, dXZ, DZ, dhc, dhc_ld, dU, dwf_part,
-                               da, B, R, L, D, A, nullptr);
-}
-
 int attention_context_bwd(const float* alphas, const float* DZ, const int* lengths, float* dann, int accumulate, int B, int R, int T1, int L, int D, hipStream_t st) {
-    const int lq4 = (L + 3) / 4;
-    const int NQ = (lq4 <= 13) ? 13 : 16;
-    const int Lq = (lq4 + NQ - 1) / NQ * NQ;
-    const size_t lds = (size_t)R * T1 * Lq * 16;
-    SAT_REQUIRE(lds <= 160 * 1024, "attention_context_bwd: R*T1*L = %d floats of alphas do not fit the LDS", R * T1 * L);
-    if (NQ == 13) {
+    AttPlan pl;
+    SAT_TRY(attention_plan(ATT_OP_CONTEXT_BWD, R, L, D, 0, 0, T1, 0u, pl, "attention_context_bwd"));
+    const size_t lds = pl.lds0;
+    if (pl.nq == 13) {
         SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dann_from_context_kernel<13>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(dann_from_context_kernel<13>, dim3(B, cdiv(D, 256)), dim3(256), lds, st, alphas, DZ, lengths, dann, accumulate, R, B * R, T1, L, D);
     } else {

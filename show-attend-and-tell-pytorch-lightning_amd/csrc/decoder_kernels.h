@@ -602,7 +602,8 @@ __global__ __launch_bounds__(ATTB_THREADS) void attention_bwd_kernel(
             for (int e = tid; e < rn * A; e += ATTB_THREADS) { int r = e / A, k = e - r * A; dhc[(long)(i0 + r) * dhc_ld + k] = 0.f; }
             continue;
         }
-        for (int e = tid; e < RN * A; e += ATTB_THREADS) { int r = e / A, k = e - r * A; s_q[r * A + k] = (r < rn) ? hc[(long)(i0 + r) * hc_ld + k] : 0.f; }
+        // dead rows run on q = 0: their ds is 0, but 0 * (1 - tanh^2) is only 0 for a finite tanh, and nothing promises that a finished row of hc is finite
+        for (int e = tid; e < RN * A; e += ATTB_THREADS) { int r = e / A, k = e - r * A; s_q[r * A + k] = ((lmask >> r) & 1u) ? hc[(long)(i0 + r) * hc_ld + k] : 0.f; }
         for (int e = tid; e < RN * L; e += ATTB_THREADS) { int r = e / L, l = e - r * L; s_al[r * L + l] = ((lmask >> r) & 1u) ? alphas[((long)(i0 + r) * T1 + step) * L + l] : 0.f; }
         __syncthreads();
         // ---- dalpha[r][l] = dz[r] . ann[b,l,:]  (wave per location)
@@ -763,7 +764,7 @@ __global__ __launch_bounds__(1024) void attention_bwd_tanh_kernel(const float* _
         }
         for (int e = tid; e < RN * ATTB_KCH; e += 1024) {
             const int r = e / ATTB_KCH, k2 = blockIdx.y * ATTB_KCH + (e - r * ATTB_KCH);
-            s_q[e] = (r < rn && k2 < A) ? hc[(long)(i0 + r) * hc_ld + k2] : 0.f;
+            s_q[e] = (((lmask >> r) & 1u) && k2 < A) ? hc[(long)(i0 + r) * hc_ld + k2] : 0.f;          // dead rows: q = 0 (finite), ds = 0
         }
         __syncthreads();
         float dq[RN], dw = 0.f;

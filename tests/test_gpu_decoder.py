@@ -256,6 +256,32 @@ def test_stacked_lstm_layers_against_oracle(M, layers, dropout):
         close(p.grad, sdo[k].grad, 2e-4, k)
 
 
+@pytest.mark.parametrize("attention_dim", [7, 8])
+def test_encoder_dim_not_a_multiple_of_4_against_oracle(M, attention_dim):
+    """encoder_dim = 10: no 16-byte annotation vectors, so the forward runs the scalar single launch and the backward must leave the split
+    pair (its dalpha kernel walks D in float4) for attention_bwd_kernel; attention_dim 7 and 8, ragged lengths, a 2 x 3 map."""
+    from oracle import prng, sat_oracle as O
+    hp = O.default_hparams(vocab_size=97, encoder_dim=10, embed_dim=20, attention_dim=attention_dim, decoder_dim=16)
+    sd = {k: torch.from_numpy(v) for k, v in prng.decoder_state(hp, 330 + attention_dim).items()}
+    B, R, T, Hh, Ww = 4, 3, 9, 2, 3
+    ann = torch.from_numpy(prng.uniform((B, 10, Hh, Ww), 331, 0.0, 2.0))
+    caps, lengths = prng.captions(B, R, T, 97, 332, min_len=2)
+    caps, lengths = torch.from_numpy(caps), torch.from_numpy(lengths)
+    assert len(set(lengths.reshape(-1).tolist())) > 2
+    dec = M.SATDecoder(hp).cuda(); dec.load_decoder_state(sd)
+    dec.train()
+    ann_bld = ann.permute(0, 2, 3, 1).reshape(B, Hh * Ww, 10).contiguous().cuda().requires_grad_()
+    res = dec.train_decode(ann_bld, caps.cuda(), lengths, 1.0)
+    sdo = {k: v.clone().requires_grad_() for k, v in sd.items()}
+    ann_o = ann.clone().requires_grad_()
+    loss_o, out_o = O.training_loss(sdo, hp, ann_o, caps, lengths, 1.0)
+    close(res["logits_packed"], out_o["logits_packed"], what="logits"); close(res["alphas"], out_o["alphas"], what="alphas")
+    (res["ce"] + res["ds"]).backward(); loss_o.backward()
+    close(ann_bld.grad.reshape(B, Hh, Ww, 10).permute(0, 3, 1, 2), ann_o.grad, 2e-4, "d_ann")
+    for k, p in dec.named_parameters():
+        close(p.grad, sdo[k].grad, 2e-4, k)
+
+
 def test_embedding_gradient_with_very_frequent_tokens(M):
     """tiny vocabulary: every word occurs > 1024 times among the fed tokens (the embedding gradient's long-segment path), plus the
     sorted short-segment path for the rest; against the oracle."""
