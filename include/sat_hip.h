@@ -218,18 +218,34 @@ int sat_beam_search_batched(const sat_decoder_dims* d, const sat_decoder_params*
  * from the caller's tables (tests):
  *   gumbel  : method 1: (max_gen_length + 1, B * beamk, V)            Gumbel(0, 1) variate of candidate word v of a row
  *             method 2: (max_gen_length + 1, B * beamk, sample_topk)  ... of the row's t-th best candidate (torch.topk order)
+ *             method 3: (max_gen_length + 1, B * beamk, V)            as method 1
  *   normals : (max_gen_length + 1, layers, B * beamk, n) standard normals of the state noise
- * rows are the compacted beam rows of that step (image b owns rows b * beamk ...).  sampling = NULL is sat_beam_search_batched. */
+ * rows are the compacted beam rows of that step (image b owns rows b * beamk ...).  sampling = NULL is sat_beam_search_batched.
+ *
+ * SAT_SAMPLE_NUCLEUS (top-p; Holtzman et al. 2019) differs from SAT_SAMPLE_TOPK only in which words of a hypothesis are candidates.
+ * For a live row at a free step >= 1 with scores s[v] (running sum + this step's log-probability; masked and banned words at -inf):
+ *   F = the finite entries, w[v] = exp(s[v] - max_F s), W = sum_F w; F ordered by score descending, ties to the lower word id;
+ *   the nucleus N is the shortest leading run of that order with sum w >= sample_topp * W.  sample_topp >= 1, or a target that
+ *   rounding keeps the running sum from reaching, gives N = F; a non-empty F always gives a non-empty N.  The parent's score is a
+ *   constant of the row, so N is the top-p set of the step's own conditional distribution.
+ *   key[v] = s[v] / step + G[v] for v in N, else -inf: method 2's rule, candidate_probs = softmax(candidate_scores / step)
+ *   (model.py:365-379), on another candidate set.  The per-image top-k over the keys and the score gather then run as for the
+ *   other methods, and the first free step stays the deterministic top beamk of row 0 (model.py:338-347).
+ * With beamk = 1 this draws proportionally to p^(1/step) inside the nucleus, as SAT_SAMPLE_TOPK does inside its candidates, NOT
+ * proportionally to p: the reference's convention, kept on purpose so that the two methods differ in the candidate set only.
+ * Without a table the variate of word v is the hash at (seed, step, row * V + v), method 1's indexing.  sample_topp must be finite
+ * and in (0, 1] (SAT_EINVAL before any launch); top-g clipping does not combine with it; prefix, banned ids and the masks do. */
 #define SAT_SAMPLE_BEAM 0
 #define SAT_SAMPLE_MULTINOMIAL 1
 #define SAT_SAMPLE_TOPK 2
+#define SAT_SAMPLE_NUCLEUS 3
 typedef struct sat_beam_sampling {
     int32_t method;            /* SAT_SAMPLE_*                                                  */
     int32_t sample_topk;       /* candidates per hypothesis, method 2                            */
     uint64_t seed;
     const float* gumbel;       /* device pointer or NULL                                         */
     float decoder_noise;       /* 0 = off; step s adds N(0,1) * decoder_noise / (s + 1) to h     */
-    int32_t reserved;
+    float sample_topp;         /* method 3: the nucleus' share of the mass, (0, 1]; all-zero bits = unset (methods 0-2 ignore it) */
     const float* normals;      /* device pointer or NULL                                         */
 } sat_beam_sampling;
 int sat_beam_search_sampled(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
@@ -270,6 +286,11 @@ int sat_beam_search_constrained(const sat_decoder_dims* d, const sat_decoder_par
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids /* device */,
                     int32_t n_masked, const float* parent_scores /* (beams) or NULL */, float* scores, void* stream);
 int sat_topk(const float* x, float* work /* n floats scratch */, int64_t n, int32_t k, float* values, int32_t* indices, void* stream);
+/* The key kernel of SAT_SAMPLE_NUCLEUS on its own, every row live: keys (rows, V) as above with `step` the divisor (> 0) and
+ * `stream` the hash stream (the search passes the step); gumbel (rows, V) or NULL; nucleus_size (rows) or NULL receives |N| per row
+ * (0 for a row without a finite entry, whose keys are all -inf).  Same input, same output, bit for bit. */
+int sat_nucleus_keys(const float* scores, int32_t rows, int32_t V, float topp, float step, uint64_t seed, uint64_t stream,
+                     const float* gumbel /* (rows, V) or NULL */, float* keys, int32_t* nucleus_size /* (rows) or NULL */, void* stream_handle);
 
 /* ------------------------------------------------------------------ scoring decoded captions (SAT.val_batch: model.py:449-472, 646-682)
  * The three calls below take the buffers sat_beam_search_batched / _sampled leave on the device to per-image metric statistics

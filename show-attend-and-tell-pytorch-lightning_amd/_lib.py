@@ -74,8 +74,13 @@ class OptHyper(C.Structure):
 
 
 class BeamSampling(C.Structure):
+    """sat_beam_sampling (include/sat_hip.h); sample_topp took the place of a reserved word: same size, same offsets"""
     _fields_ = [("method", C.c_int32), ("sample_topk", C.c_int32), ("seed", C.c_uint64), ("gumbel", C.c_void_p), ("decoder_noise", C.c_float),
-                ("reserved", C.c_int32), ("normals", C.c_void_p)]
+                ("sample_topp", C.c_float), ("normals", C.c_void_p)]
+
+
+#: SAT.forward's sample_method -> SAT_SAMPLE_*
+SAMPLE_METHODS = {"beam": 0, "multinomial": 1, "topk": 2, "nucleus": 3}
 
 
 class BeamConstraints(C.Structure):
@@ -253,6 +258,7 @@ SYMBOLS.update({
                                               _vp, C.c_size_t, _vp]),
     "sat_beam_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp]),
     "sat_topk": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "sat_nucleus_keys": (C.c_int, [_vp, _i32, _i32, _f, _f, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
 })
 SYMBOLS.update({"sat_optimizer_chunk_elems": (C.c_int32, []),
                 "sat_grad_clip_coef": (C.c_int, [_vp, _vp, _i32, _f, _vp, _vp, _vp]),

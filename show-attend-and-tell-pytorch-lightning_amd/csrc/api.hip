@@ -286,6 +286,14 @@ int sat_topk(const float* x, float* work, int64_t n, int32_t k, float* values, i
     if (!x || !work || !values || !indices) return fail(SAT_EINVAL, "topk: null pointer");
     return topk(x, work, n, k, values, indices, (hipStream_t)stream);
 }
+int sat_nucleus_keys(const float* scores, int32_t rows, int32_t V, float topp, float step, uint64_t seed, uint64_t stream, const float* gumbel, float* keys,
+                     int32_t* nucleus_size, void* stream_handle) {
+    if (rows <= 0 || V <= 0) return fail(SAT_EINVAL, "nucleus_keys: non-positive size (rows=%d V=%d)", rows, V);
+    if (!(topp > 0.f && topp <= 1.f)) return fail(SAT_EINVAL, "nucleus_keys: topp %g outside (0, 1]", (double)topp);
+    if (!(step > 0.f && step < INFINITY)) return fail(SAT_EINVAL, "nucleus_keys: step %g is not a positive finite number", (double)step);
+    if (!scores || !keys) return fail(SAT_EINVAL, "nucleus_keys: null pointer");
+    return nucleus_keys(scores, rows, V, topp, step, seed, stream, gumbel, keys, nucleus_size, (hipStream_t)stream_handle);
+}
 
 int sat_colsum(const float* x, int64_t ld, int64_t rows, int32_t cols, float* out, float* scratch, void* stream) {
     if (!x || !out || !scratch) return fail(SAT_EINVAL, "colsum: null pointer");

@@ -58,6 +58,8 @@ int embedding_bwd(const float* dY, const int* tokens, float* dtable, int rows, i
 int sigmoid_bwd(const float* dy, const float* y, float* dpre, long n, hipStream_t st);
 int beam_scores(const float* logits, int K, int V, float temperature, const int* masked, int n_masked, const float* parent, float* scores, hipStream_t st);
 int topk(const float* x, float* work, long n, int k, float* values, int* indices, hipStream_t st);
+int nucleus_keys(const float* scores, int rows, int V, float topp, float step, unsigned long long seed, unsigned long long stream, const float* gumbel,
+                 float* keys, int* nucleus_size, hipStream_t st);
 int colsum_public(const float* x, long ld, long rows, int cols, float* out, float* scratch, hipStream_t st);
 int ce_fwd(const float* logits, const int* targets, int P, int V, float smoothing, float* lse_rows, float* loss_rows, int* correct_rows, float* out, hipStream_t st);
 int ce_bwd(const float* logits, const int* targets, const float* lse_rows, int P, int V, float smoothing, const float* gscale, float* dlogits, hipStream_t st);

@@ -811,6 +811,13 @@ static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg
 }
 size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg) { return beam_layout(d, K, nullptr, topg).total; }
 
+// the keys of one free step of the "nucleus" search: method 1's table layout and hash indexing, (step, row, word)
+static int launch_nucleus_keys(hipStream_t st, const float* scores, const int* klive, int N, int K, int V, const sat_beam_sampling& smp, int step, float* keys) {
+    hipLaunchKernelGGL(beam_nucleus_keys_kernel, dim3(N), dim3(256), 0, st, scores, klive, K, V, smp.sample_topp, (float)step, (unsigned long long)smp.seed,
+                       (unsigned long long)step, smp.gumbel ? smp.gumbel + (long)step * N * V : (const float*)nullptr, keys, (int*)nullptr);
+    return launch_ok("beam_nucleus_keys");
+}
+
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
                          int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
@@ -831,8 +838,10 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
     const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
     BeamWs w = beam_layout(d, K, ws, topg);
-    SAT_REQUIRE(method >= 0 && method <= 2 && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)), "beam_batched: sampling method %d, sample_topk %d",
-                method, smp ? smp->sample_topk : 0);
+    SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_NUCLEUS && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
+                "beam_batched: sampling method %d, sample_topk %d", method, smp ? smp->sample_topk : 0);
+    SAT_REQUIRE(method != SAT_SAMPLE_NUCLEUS || (smp->sample_topp > 0.f && smp->sample_topp <= 1.f),
+                "beam_batched: sample_topp %g outside (0, 1] (nucleus sampling)", smp ? (double)smp->sample_topp : 0.0);
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
     t_bf16_mfma = d.precision ? 1 : 0;
     const int B = d.B, N = B * K, n = d.n, A = d.A, D = d.D, m = d.m, V = d.V, NL = d.layers, HCW = A + D + 4 * n;
@@ -928,7 +937,9 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                 hipLaunchKernelGGL(beam_row_topg_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, topg, step, prefix_len, max_prefix, w.cand_val, w.cand_idx);
                 SAT_TRY(launch_ok("beam_row_topg"));
             }
-            if (drawn) {
+            if (drawn && method == SAT_SAMPLE_NUCLEUS) {
+                SAT_TRY(launch_nucleus_keys(st, w.scores, w.klive, N, K, V, *smp, step, w.keys));
+            } else if (drawn) {
                 const int gstride = method == 1 ? V : smp->sample_topk;
                 hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
                                    (unsigned long long)smp->seed, (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr,
@@ -950,11 +961,15 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                 hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
                 SAT_TRY(launch_ok("beam_topk"));
             } else {                                       // model.py:360-379: draw the continuing hypotheses (Gumbel-top-k == multinomial without replacement)
-                const int gstride = method == 1 ? V : smp->sample_topk;
-                hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
-                                   (unsigned long long)smp->seed, (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr,
-                                   gstride, w.keys);
-                SAT_TRY(launch_ok("beam_sample_keys"));
+                if (method == SAT_SAMPLE_NUCLEUS) {
+                    SAT_TRY(launch_nucleus_keys(st, w.scores, w.klive, N, K, V, *smp, step, w.keys));
+                } else {
+                    const int gstride = method == 1 ? V : smp->sample_topk;
+                    hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
+                                       (unsigned long long)smp->seed, (unsigned long long)step,
+                                       smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr, gstride, w.keys);
+                    SAT_TRY(launch_ok("beam_sample_keys"));
+                }
                 hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.keys, w.work, w.klive, K, V, 0, w.vals, w.inds);
                 SAT_TRY(launch_ok("beam_topk (keys)"));
                 hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
@@ -980,6 +995,12 @@ int beam_scores(const float* logits, int K, int V, float temperature, const int*
     SAT_REQUIRE(K > 0 && V > 0 && temperature > 0.f, "beam_scores: bad arguments");
     hipLaunchKernelGGL(beam_scores_kernel, dim3(K), dim3(256), 0, st, logits, V, 1.0f / temperature, masked, n_masked, parent, scores);
     return launch_ok("beam_scores");
+}
+int nucleus_keys(const float* scores, int rows, int V, float topp, float step, unsigned long long seed, unsigned long long stream, const float* gumbel,
+                 float* keys, int* nucleus_size, hipStream_t st) {
+    hipLaunchKernelGGL(beam_nucleus_keys_kernel, dim3(rows), dim3(256), 0, st, scores, (const int*)nullptr, 1, V, topp, step, seed, stream, gumbel, keys,
+                       nucleus_size);
+    return launch_ok("beam_nucleus_keys");
 }
 int topk(const float* x, float* work, long n, int k, float* values, int* indices, hipStream_t st) {
     SAT_REQUIRE(n > 0 && k > 0 && k <= n, "topk: bad arguments (n=%ld k=%d)", n, k);

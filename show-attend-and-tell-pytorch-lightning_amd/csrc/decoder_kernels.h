@@ -1385,6 +1385,140 @@ __global__ __launch_bounds__(256) void beam_sample_keys_kernel(const float* __re
         }
     }
 }
+// ---- method 3 ("nucleus", DESIGN.md 5 "Sampled decoding"): "topk"'s rule s / step + G on another candidate set, the fewest words of
+// the row (score descending, ties to the lower id) whose weights w = exp(s - max) sum to topp * W.  The cut is searched on the
+// score itself: the order-preserving unsigned image of the float is bisected bit by bit, every pass one block reduction of
+// sum{ w : s >= t }.  Sums of non-negative floats taken in one fixed order are monotone in the set summed, so the bisection is
+// well defined in fp32, and a pass that includes every finite entry reproduces W bit for bit.
+__device__ __forceinline__ unsigned ordered_bits(float x) {
+    const unsigned u = x == 0.f ? 0u : __float_as_uint(x);  // -0 and +0 are one score
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_float(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+// fixed-order block reductions for 256 threads: xor butterfly inside each wave (every lane ends with the same value), then
+// (wave0 + wave1) + (wave2 + wave3).  `slot` holds 4 words; callers alternate between two slots, so one barrier a call is enough.
+__device__ __forceinline__ float block_sum_f(float x, float* slot, int tid) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    if ((tid & 63) == 0) slot[tid >> 6] = x;
+    __syncthreads();
+    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+}
+__device__ __forceinline__ int block_sum_i(int x, int* slot, int tid) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    if ((tid & 63) == 0) slot[tid >> 6] = x;
+    __syncthreads();
+    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+}
+#define NUCLEUS_REGS 32                                     // entries a thread keeps in registers: rows up to 256 * 32 = 8192 words
+// keys[i, v] = s[v] / step + G[v] for the words of row i's nucleus, else -inf; nucleus_size[i] (optional) = the member count.
+// klive NULL: every row is live (sat_nucleus_keys).  gumbel: optional (rows, V) table of this step, else the hash at (i * V + v).
+__global__ __launch_bounds__(256) void beam_nucleus_keys_kernel(const float* __restrict__ scores, const int* __restrict__ klive, int K, int V, float topp,
+                                                                float step, unsigned long long seed, unsigned long long stream,
+                                                                const float* __restrict__ gumbel, float* __restrict__ keys, int* __restrict__ nucleus_size) {
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (klive) { const int b = i / K; if (i - b * K >= klive[b]) return; }
+    const float* s = scores + (long)i * V; float* key = keys + (long)i * V;
+    __shared__ float s_f[2][4]; __shared__ int s_n[2][4]; __shared__ int s_c[2][4]; __shared__ int s_scan[4];
+    const bool cached = V <= 256 * NUCLEUS_REGS;
+    const int nk = (V + 255) >> 8;                           // strided passes a thread makes over the row
+    // the largest finite score.  Non-finite entries (masked and banned words at -inf) are no candidates.
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) { const float x = s[v]; if (x < INFINITY) mx = fmaxf(mx, x); }
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if ((tid & 63) == 0) s_f[1][tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(s_f[1][0], s_f[1][1]), fmaxf(s_f[1][2], s_f[1][3]));
+    if (!(mx > -INFINITY)) {                                 // no finite entry: an empty nucleus
+        for (int v = tid; v < V; v += 256) key[v] = -INFINITY;
+        if (nucleus_size && tid == 0) nucleus_size[i] = 0;
+        return;
+    }
+    // w and the ordered image in registers where the row fits; image 0 marks "not a candidate" (no finite float maps to 0)
+    float rw[NUCLEUS_REGS]; unsigned ru[NUCLEUS_REGS];
+    auto weight = [&](float x) { return __expf(x - mx); };
+    auto finite = [](float x) { return x > -INFINITY && x < INFINITY; };
+    if (cached) {
+#pragma unroll
+        for (int k = 0; k < NUCLEUS_REGS; ++k) {
+            const int v = tid + (k << 8);
+            rw[k] = 0.f; ru[k] = 0u;
+            if (v < V) { const float x = s[v]; if (finite(x)) { rw[k] = weight(x); ru[k] = ordered_bits(x); } }
+        }
+    }
+    // mass_ge(t) = sum{ w[v] : image[v] >= t } over the candidates, t >= 1
+    int pass = 0;
+    auto mass_ge = [&](unsigned t) {
+        float acc = 0.f;
+        if (cached) {
+#pragma unroll
+            for (int k = 0; k < NUCLEUS_REGS; ++k) { if (k < nk && ru[k] >= t) acc += rw[k]; }
+        } else {
+            for (int v = tid; v < V; v += 256) { const float x = s[v]; if (finite(x) && ordered_bits(x) >= t) acc += weight(x); }
+        }
+        return block_sum_f(acc, s_f[(pass++) & 1], tid);
+    };
+    const float W = mass_ge(1u);
+    const float target = topp * W;
+    unsigned t = 1u;                                         // every candidate: topp >= 1, or a target the sums never reach
+    if (topp < 1.f) {
+        t = 0u;
+        for (int bit = 31; bit >= 0; --bit) {                // the largest t with mass_ge(t) >= target: the image of a score of the row
+            const unsigned cand = t | (1u << bit);
+            if (mass_ge(cand) >= target) t = cand;
+        }
+        if (t == 0u) t = 1u;
+    }
+    // the entries above the threshold are in; of the cnt entries AT it (equal scores, equal weights c) the m lowest ids are
+    float above = 0.f; int n_above = 0, cnt = 0;
+    if (cached) {
+#pragma unroll
+        for (int k = 0; k < NUCLEUS_REGS; ++k) {
+            if (k < nk) { if (ru[k] > t) { above += rw[k]; ++n_above; } else if (ru[k] == t) ++cnt; }
+        }
+    } else {
+        for (int v = tid; v < V; v += 256) {
+            const float x = s[v];
+            if (finite(x)) { const unsigned u = ordered_bits(x); if (u > t) { above += weight(x); ++n_above; } else if (u == t) ++cnt; }
+        }
+    }
+    const int p = (pass++) & 1;
+    above = block_sum_f(above, s_f[p], tid);
+    n_above = block_sum_i(n_above, s_n[p], tid);
+    cnt = block_sum_i(cnt, s_c[p], tid);
+    int m = cnt;                                             // t == 1 lies below every candidate: all of them are "above", cnt = 0
+    if (t > 1u) {
+        const float c = weight(ordered_float(t));
+        const float need = ceilf((target - above) / c);
+        m = need >= (float)cnt ? cnt : (need >= 1.f ? (int)need : 1);
+    }
+    if (nucleus_size && tid == 0) nucleus_size[i] = n_above + m;
+    const bool split = m < cnt;                              // the cut falls inside the run of equal scores
+    const float tv = ordered_float(t);
+    auto draw = [&](int v) {
+        return gumbel ? gumbel[(long)i * V + v] : gumbel_of(hash_uniform(seed, stream, (unsigned long long)i * V + v));
+    };
+    // strided pass: everything but a split run, whose entries the blocked pass below writes
+    for (int v = tid; v < V; v += 256) {
+        const float x = s[v];
+        const unsigned u = finite(x) ? ordered_bits(x) : 0u;
+        if (split && u == t) continue;
+        key[v] = (u >= t) ? x / step + draw(v) : -INFINITY;
+    }
+    if (!split) return;
+    // ranks of the tied entries by id: thread tid owns the ids [tid * chunk, tid * chunk + chunk), a block prefix count orders them
+    const int chunk = (V + 255) >> 8, lo = tid * chunk, hi = min(V, lo + chunk);
+    int mine = 0;
+    for (int v = lo; v < hi; ++v) mine += (s[v] == tv) ? 1 : 0;
+    int incl = mine;
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += y; }
+    if ((tid & 63) == 63) s_scan[tid >> 6] = incl;
+    __syncthreads();
+    int rank = incl - mine;
+    for (int w = 0; w < (tid >> 6); ++w) rank += s_scan[w];
+    for (int v = lo; v < hi; ++v) {
+        if (s[v] == tv) { key[v] = rank < m ? tv / step + draw(v) : -INFINITY; ++rank; }
+    }
+}
 // after the top-k over the keys: the kept hypotheses carry their SCORES (model.py:382 top_scores = seq_scores.reshape(-1)[pred_idx])
 __global__ void beam_take_scores_kernel(const float* __restrict__ scores, const int* __restrict__ inds, const int* __restrict__ klive, int B, int K, int V,
                                         float* __restrict__ values) {

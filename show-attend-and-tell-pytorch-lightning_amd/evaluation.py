@@ -54,10 +54,11 @@ def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, 
 
 @torch.no_grad()
 def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False):
+                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
     """``SAT.caption(..., return_all=False)`` with the result left on the device: ``(tokens (B, max_gen_length + 1) int32 padded with
     <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises.
-    ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
+    ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``); ``sample_topp`` belongs to
+    ``sample_method="nucleus"``."""
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
     con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
@@ -65,7 +66,7 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     model.eval()
     ann_bld, _ = model.encode(img)
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
-                                  graph, **con)
+                                  graph, sample_topp=sample_topp, **con)
     sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward)
     ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
     return sel["tokens"], sel["lengths"], sel["scores"], ppl
@@ -251,14 +252,15 @@ class CaptionStats:
 
 @torch.no_grad()
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False):
+                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
+                    sample_topp=0.9):
     """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
     with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue.  ``topg`` / ``prefix`` / ``banned`` /
     ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
     tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                                          rescore_method, rescore_reward, seed, graph, topg, prefix, banned, no_unk)
+                                          rescore_method, rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp)
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())

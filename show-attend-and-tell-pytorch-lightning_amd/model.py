@@ -55,6 +55,55 @@ class LabelSmoothing(nn.Module):
         return loss
 
 
+SAMPLE_METHODS = tuple(L.SAMPLE_METHODS)
+
+
+def check_sample_topp(sample_method, sample_topp):
+    """``sample_topp`` of "nucleus" sampling is a finite share in (0, 1] (include/sat_hip.h refuses the same values)"""
+    if sample_method == "nucleus" and not (0.0 < float(sample_topp) <= 1.0):
+        raise ValueError("sample_topp %r outside (0, 1] (sample_method='nucleus')" % (sample_topp,))
+
+
+def nucleus_candidates(scores, topp, with_margin=False):
+    """The candidates of "nucleus" sampling ("Sampled decoding") for scores (k, V), in torch ops: per row the finite
+    entries ordered by (-score, id) (a stable sort), their weights exp(s - max) summed cumulatively in float64, cut at the shortest
+    leading run that reaches ``topp`` of the total (``topp >= 1`` or a run that never reaches it: every finite entry).  Returns the
+    flat indices row * V + word, rows in order and each row's words in sorted order; with ``with_margin`` also, per row, how far
+    the cumulative share at the cut and just before it (a run of equal scores around the cut counting as one position) lies from
+    ``topp``: the distance by which rounding would have to move a sum to change the set (inf where nothing is cut)."""
+    k, V = scores.shape
+    sv, si = torch.sort(scores, dim=1, descending=True, stable=True)
+    fin = torch.isfinite(sv)
+    svd = sv.double()
+    w = torch.where(fin, torch.exp(svd - svd[:, :1]), torch.zeros((), dtype=torch.float64, device=scores.device))
+    cum = w.cumsum(1)
+    total = w.sum(1, keepdim=True)
+    n_fin = fin.sum(1)
+    reach = (cum >= float(topp) * total) & fin
+    count = torch.where(reach.any(1), reach.to(torch.int64).argmax(1) + 1, n_fin)
+    if float(topp) >= 1.0:
+        count = n_fin
+    member = torch.arange(V, device=scores.device).unsqueeze(0) < count.unsqueeze(1)
+    cand = (si + (torch.arange(k, device=scores.device) * V).unsqueeze(1))[member]
+    if not with_margin:
+        return cand
+    margins = []
+    svc, share, cnt = sv.cpu(), (cum / total).cpu(), count.tolist()
+    for r in range(k):
+        if float(topp) >= 1.0 or cnt[r] == 0:
+            margins.append(float("inf")); continue
+        a = b = cnt[r] - 1                                  # the cut position, widened to the run of scores equal to it
+        while a > 0 and svc[r, a - 1] == svc[r, a]:
+            a -= 1
+        while b + 1 < V and svc[r, b + 1] == svc[r, b]:
+            b += 1
+        m = abs(float(share[r, b]) - float(topp))
+        if a > 0:
+            m = min(m, abs(float(share[r, a - 1]) - float(topp)))
+        margins.append(m)
+    return cand, margins
+
+
 class SATDecoder(nn.Module):
     """Everything of ``SAT`` except the encoder (model.py:146-199): the decoder parameters under
     the reference's names and the fused train-time decode."""
@@ -111,7 +160,7 @@ class SATDecoder(nn.Module):
     @torch.no_grad()
     def beam_decode(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
                     decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, multinomial=None, randn=None,
-                    topg=None, prefix=None, banned=None, no_unk=False):
+                    topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, nucleus_log=None):
         """SAT.forward's per-image beam search (model.py:260-472) on annotations (B, L, D).  The decode step,
         log-softmax / masking and top-k run in the library; the beam bookkeeping (which hypotheses to keep, finished
         lists, rescoring) stays on the host like in the reference.  ``sample_method`` "multinomial" / "topk"
@@ -119,9 +168,13 @@ class SATDecoder(nn.Module):
         (model.py:322-324) perturbs the recurrent state with ``randn(shape)``: both default to the torch samplers on the
         annotations' device and can be replaced (tests feed both sides the same draws).
         ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: the constrained search ("Constrained search"), the same rules as
-        ``beam_decode_batched`` with torch ops on the scores this loop already holds."""
+        ``beam_decode_batched`` with torch ops on the scores this loop already holds.
+        ``sample_method="nucleus"`` with ``sample_topp``: "topk"'s draw over the top-p set of every row (``nucleus_candidates``).
+        ``nucleus_log``: a list that receives, per free step, ``dict(image, step, cand, margins)`` before the draw (tests gather their
+        Gumbel variates by ``cand`` and read how close every cut came to ``sample_topp``)."""
         import ctypes as C
-        assert sample_method in ("beam", "multinomial", "topk")
+        assert sample_method in SAMPLE_METHODS
+        check_sample_topp(sample_method, sample_topp)
         multinomial = multinomial or torch.multinomial
         con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
                                   topg, prefix, banned, no_unk)
@@ -215,6 +268,14 @@ class SATDecoder(nn.Module):
                     else:
                         if sample_method == "multinomial":                                 # model.py:360-364
                             pred = multinomial(torch.softmax(20 * scores / step, dim=1).reshape(-1), k)
+                        elif sample_method == "nucleus":                                   # "topk"'s draw on the top-p set of every row
+                            if nucleus_log is not None:
+                                cand, margins = nucleus_candidates(scores, sample_topp, with_margin=True)
+                                nucleus_log.append(dict(image=idx, step=step, cand=cand, margins=margins))
+                            else:
+                                cand = nucleus_candidates(scores, sample_topp)
+                            choice = multinomial(torch.softmax(scores.reshape(-1)[cand] / step, dim=0), k)
+                            pred = cand[choice.to(cand.device)]
                         else:                                                              # model.py:365-379
                             _, cand = torch.topk(scores, sample_topk, dim=1)
                             cand = (cand + (torch.arange(k, device=dev) * V).unsqueeze(1)).reshape(-1)
@@ -261,13 +322,16 @@ class SATDecoder(nn.Module):
         return captions, cap_scores, cap_alphas, cap_ppl
 
     def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                            topg=None, prefix=None, banned=None, no_unk=False):
+                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
         """The device half of ``beam_decode_batched``: enqueue the whole search for annotations (B, L, D) (eagerly, or as the replay of
         its cached hipGraph) and return the buffers it leaves on the device (tok_in, prev_row, alpha_hist, fin_*: include/sat_hip.h,
         sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted).
-        With a constraint (``topg`` / ``prefix`` / ``banned`` / ``no_unk``) the call is sat_beam_search_constrained and runs eagerly."""
+        With a constraint (``topg`` / ``prefix`` / ``banned`` / ``no_unk``) the call is sat_beam_search_constrained and runs eagerly.
+        ``graph=True`` replays the "beam" search without noise, and the "nucleus" search drawn by the device generator from a
+        given ``seed`` (the seed and ``sample_topp`` are arguments of the captured launches, so both are part of the cache key)."""
         import ctypes as C
-        assert sample_method in ("beam", "multinomial", "topk")
+        assert sample_method in SAMPLE_METHODS
+        check_sample_topp(sample_method, sample_topp)
         con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
                                   topg, prefix, banned, no_unk)
         lib = L.lib()
@@ -293,6 +357,7 @@ class SATDecoder(nn.Module):
             cst, _keep_con = con.device_struct(dev)
             ws_bytes = lib.sat_beam_search_constrained_workspace_bytes(C.byref(dims), K, con.topg)
         smp = None
+        seeded = seed is not None
         if sample_method != "beam" or decoder_noise:
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)))
@@ -300,8 +365,9 @@ class SATDecoder(nn.Module):
                 if t is not None:
                     L.require_gpu(t)
                     assert t.dtype == torch.float32 and t.is_contiguous()
-            smp = L.BeamSampling(method={"beam": 0, "multinomial": 1, "topk": 2}[sample_method], sample_topk=int(sample_topk), seed=int(seed),
+            smp = L.BeamSampling(method=L.SAMPLE_METHODS[sample_method], sample_topk=int(sample_topk), seed=int(seed),
                                  gumbel=(gumbel.data_ptr() if gumbel is not None else None), decoder_noise=float(decoder_noise or 0.0),
+                                 sample_topp=(float(sample_topp) if sample_method == "nucleus" else 0.0),
                                  normals=(normals.data_ptr() if normals is not None else None))
 
         def buffers():
@@ -322,9 +388,12 @@ class SATDecoder(nn.Module):
                                                 L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]), ws_bytes, L.stream_ptr()),
                     "sat_beam_search_sampled")
 
-        if graph and smp is None and cst is None:
+        replayable = smp is None or (sample_method == "nucleus" and seeded and gumbel is None and normals is None)
+        if graph and replayable and cst is None:
             cache = self.__dict__.setdefault("_beam_graphs", {})
             key = (B, Lc, D, K, S, tuple(float(t) for t in temps), int(dims.precision), str(dev), tuple(t.data_ptr() for t in _keep.values() if torch.is_tensor(t)))
+            if smp is not None:
+                key += ("nucleus", float(smp.sample_topp), int(smp.seed), float(smp.decoder_noise))
             ent = cache.get(key)
             if ent is None:
                 o = buffers()
@@ -348,7 +417,7 @@ class SATDecoder(nn.Module):
     @torch.no_grad()
     def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
                             return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False,
-                            topg=None, prefix=None, banned=None, no_unk=False):
+                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
         """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
         (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
         completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
@@ -363,10 +432,13 @@ class SATDecoder(nn.Module):
         Constraints on the selection step ("Constrained search"), all inside the same call: ``topg`` keeps only the g best
         words of every hypothesis as candidates ("beam" sampling only), ``prefix`` (token ids, or a string looked up in ``vocab_stoi``;
         one for all images or one per image) forces the first words of every caption, ``banned`` ids / ``no_unk`` never appear.
-        ``graph=True`` combined with any constraint runs eagerly, as sampling does."""
+        ``graph=True`` combined with any constraint runs eagerly, as sampling does.
+        ``sample_method="nucleus"`` with ``sample_topp`` in (0, 1] (top-p sampling; DESIGN.md 5, "Sampled decoding"): "topk"'s draw with
+        the candidates of a hypothesis being the fewest words that carry ``sample_topp`` of its probability mass.  Prefix, banned ids
+        and ``no_unk`` combine with it, ``topg`` does not; ``graph=True`` replays it when ``seed`` is given and no table is."""
         import numpy as np
         o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                                     topg, prefix, banned, no_unk)
+                                     topg, prefix, banned, no_unk, sample_topp)
         B = ann_bld.shape[0]
         Hh, Ww = hw
         K, S = int(beamk), int(max_gen_length)
@@ -523,16 +595,18 @@ class SAT(SATDecoder, _Base):
 
     @torch.no_grad()
     def caption(self, img_tensor, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
-                decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False):
-        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: ``beam_decode_batched``."""
+                decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False,
+                sample_topp=0.9):
+        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` / ``sample_topp``: ``beam_decode_batched``."""
         self.eval()
         return self.forward(img_tensor, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                            rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk)
+                            rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk, sample_topp)
 
     def forward(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False):
+                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
         """Inference only (model.py:237-472): encode the batch once, then beam-search every image."""
-        assert sample_method in ["beam", "multinomial", "topk"]
+        assert sample_method in SAMPLE_METHODS
+        check_sample_topp(sample_method, sample_topp)
         con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
         constraints.resolve(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
         with torch.no_grad():
@@ -540,9 +614,9 @@ class SAT(SATDecoder, _Base):
             if max_gen_length >= 1:        # every image at once; sampled continuations and decoder noise draw from the device generator
                 return self.beam_decode_batched(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, rescore_method, rescore_reward, return_all,
                                                 sample_method=sample_method, sample_topk=sample_topk, decoder_noise=decoder_noise,
-                                                graph=bool(self.__dict__.get("beam_graph", False)), **con)  # model.beam_graph = True: hipGraph replay
+                                                graph=bool(self.__dict__.get("beam_graph", False)), sample_topp=sample_topp, **con)  # model.beam_graph = True: hipGraph replay
             return self.beam_decode(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, sample_method, sample_topk,
-                                    decoder_noise, rescore_method, rescore_reward, return_all, **con)
+                                    decoder_noise, rescore_method, rescore_reward, return_all, sample_topp=sample_topp, **con)
 
     def train_batch(self, batch, epsilon=0, draw=None, teacher=None):
         img, encoded_captions, lengths = batch
@@ -694,46 +768,49 @@ class SAT(SATDecoder, _Base):
         return out
 
     def val_batch(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                  rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False):
+                  rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
         """model.py:684-691"""
         img, encoded_captions, lengths = batch
         captions, scores, alphas, perplexities = self.caption(img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                                                               rescore_method, rescore_reward, return_all=False, topg=topg, prefix=prefix, banned=banned,
-                                                              no_unk=no_unk)
+                                                              no_unk=no_unk, sample_topp=sample_topp)
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
 
     def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False):
+                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
         """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
         from . import evaluation
         return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                         rescore_reward, seed, graph, topg, prefix, banned, no_unk)
+                                         rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False):
+                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
+                        sample_topp=0.9):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
         (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk)
+                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False, **render):
+                  rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False,
+                  sample_topp=0.9, **render):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
         attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
         ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
         from . import visualize
         return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                   rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, **render)
+                                   rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, sample_topp=sample_topp,
+                                   **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                       rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
-                      topg=None, prefix=None, banned=None, no_unk=False):
+                      topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
         """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
         ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
         from . import visualize
         return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk)
+                                       rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk, sample_topp)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

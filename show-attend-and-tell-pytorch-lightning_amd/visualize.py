@@ -152,7 +152,7 @@ def _names(items):
 
 @torch.no_grad()
 def _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method, rescore_reward, visual_size,
-            input_size, seed, with_alpha, progressive=False, topg=None, prefix=None, banned=None, no_unk=False):
+            input_size, seed, with_alpha, progressive=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
     """load_square -> prepare_image -> encoder -> batched search -> the winning hypothesis of every picture, all enqueued back to back"""
     from . import constraints, evaluation as E
     if int(max_gen_length) < 1:
@@ -165,7 +165,7 @@ def _search(model, items, beamk, max_gen_length, temperature, sample_method, sam
     img = prepare_image_batch(squares, input_size if input_size is not None else model.hp.get("input_size"))
     ann_bld, hw = model.encode(img)
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
-                                  False, **con)
+                                  False, sample_topp=sample_topp, **con)
     sel = E.select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward, with_alpha=with_alpha)
     return squares, hw, sel, status, index
 
@@ -190,13 +190,13 @@ def _read(model, sel, status, index):
 
 def visualize(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None, rescore_method=None,
               rescore_reward=1.0, visual_size=256, input_size=None, power=5.0, opacity=0.75, seed=None, progressive=False,
-              topg=None, prefix=None, banned=None, no_unk=False):
+              topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
     """``make_visual`` without the figure, for a batch: returns a ``Visual``.  ``input_size`` None: the model's ``input_size``.  The winning
     caption is the one ``SAT.caption(..., return_all=True)`` lists first (the highest rescored value; among hypotheses with the very same
     value this picks the first to finish).  Everything stays on the device until one read of tokens and scores.
     ``topg`` / ``prefix`` (e.g. ``"a photo of"``) / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
     squares, hw, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                              rescore_reward, visual_size, input_size, seed, True, progressive, topg, prefix, banned, no_unk)
+                                              rescore_reward, visual_size, input_size, seed, True, progressive, topg, prefix, banned, no_unk, sample_topp)
     panels = attention_panels(squares, sel["alphas"], sel["lengths"], hw, power, opacity)
     captions, words, scores, ppl, lengths = _read(model, sel, status, index)
     return Visual(captions, words, scores, ppl, lengths, panels, _names(items))
@@ -204,11 +204,11 @@ def visualize(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_
 
 def caption_image(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
-                  topg=None, prefix=None, banned=None, no_unk=False):
+                  topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
     """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch, without panels:
     ``(captions, words, scores, perplexities)``, one entry per picture.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: as ``visualize``."""
     _, _, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, False, progressive, topg, prefix, banned, no_unk)
+                                       rescore_reward, visual_size, input_size, seed, False, progressive, topg, prefix, banned, no_unk, sample_topp)
     captions, words, scores, ppl, _ = _read(model, sel, status, index)
     return captions, words, scores, ppl
 

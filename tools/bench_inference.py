@@ -1,8 +1,10 @@
 """Dev tool / BASELINE configs[4] (C5): caption() throughput, greedy (beam 1) vs beam 5, resnet50 encoder, 64 images, on one GPU.
 Decode-only timing (annotations precomputed) and end-to-end timing (encoder included).
 ``--topg G`` / ``--prefix-len P`` / ``--no-unk`` time the constrained batched search instead ("Constrained search"): the
-prefix of an image is the first P words of its unconstrained caption; the result is checked against the per-image loop."""
-import argparse, os, sys, time
+prefix of an image is the first P words of its unconstrained caption; the result is checked against the per-image loop.
+``--sample-method multinomial|topk|nucleus`` (``--sample-topk``, ``--sample-topp``) times the sampled batched search drawn by the device
+generator from a fixed seed: the median of ``--repeats`` timed calls after two warm-up calls."""
+import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
@@ -15,6 +17,10 @@ ap.add_argument("--topg", type=int, default=None)
 ap.add_argument("--prefix-len", type=int, default=0)
 ap.add_argument("--no-unk", action="store_true")
 ap.add_argument("--beams", type=int, nargs="+", default=[1, 5])
+ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk", "nucleus"])
+ap.add_argument("--sample-topk", type=int, default=3)
+ap.add_argument("--sample-topp", type=float, default=0.9)
+ap.add_argument("--repeats", type=int, default=9)
 a = ap.parse_args()
 constrained = a.topg is not None or a.prefix_len > 0 or a.no_unk
 
@@ -49,6 +55,21 @@ with torch.no_grad():
             print("beam %d: constrained batched search (topg=%s, prefix-len=%d, no-unk=%s), decode-only %.0f images/s (%.2f ms per 64 images incl. host "
                   "back-trace), %d of 64 captions differ from the unconstrained search"
                   % (beamk, a.topg, a.prefix_len, a.no_unk, 64 / dtc, dtc * 1e3, sum(x != y for x, y in zip(capsc, caps))))
+            continue
+        if a.sample_method != "beam":
+            kw = dict(beamk=beamk, max_gen_length=20, sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, seed=7)
+            for _ in range(2):
+                model.beam_decode_batched(ann, hw, **kw)
+            times = []
+            for _ in range(a.repeats):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                capss = model.beam_decode_batched(ann, hw, **kw)[0]
+                torch.cuda.synchronize(); times.append(time.perf_counter() - t0)
+            dts = statistics.median(times)
+            print("beam %d: sampled batched search (%s, sample_topk=%d, sample_topp=%g), decode-only %.0f images/s (median %.2f ms, min %.2f, max %.2f per 64 images "
+                  "incl. host back-trace over %d calls), mean caption length %.1f"
+                  % (beamk, a.sample_method, a.sample_topk, a.sample_topp, 64 / dts, dts * 1e3, min(times) * 1e3, max(times) * 1e3, a.repeats,
+                     sum(len(c) + 1 for c in capss) / 64))
             continue
         for _ in range(2):
             model.beam_decode_batched(ann, hw, beamk=beamk, max_gen_length=20)

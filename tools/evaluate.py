@@ -40,8 +40,9 @@ def main():
     ap.add_argument("--beamk", type=int, default=5)
     ap.add_argument("--max-gen-length", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0)
-    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk"])
+    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk", "nucleus"])
     ap.add_argument("--sample-topk", type=int, default=3)
+    ap.add_argument("--sample-topp", type=float, default=0.9, help="nucleus sampling: the share of the probability mass the candidates of a hypothesis carry, (0, 1]")
     ap.add_argument("--decoder-noise", type=float, default=0.0)
     ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
     ap.add_argument("--rescore-reward", type=float, default=0.5)
@@ -68,7 +69,7 @@ def main():
                 w.writeheader(); w.writerows(rows)
         return
     res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
-                     sample_method=a.sample_method, sample_topk=a.sample_topk, decoder_noise=a.decoder_noise,
+                     sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise,
                      rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward, topg=a.topg,
                      no_unk=a.no_unk)
     print("%d images in %d batches" % (res["images"], res["batches"]))

@@ -38,8 +38,9 @@ def main():
     ap.add_argument("--beamk", type=int, default=3)
     ap.add_argument("--max-gen-length", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0)
-    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk"])
+    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk", "nucleus"])
     ap.add_argument("--sample-topk", type=int, default=3)
+    ap.add_argument("--sample-topp", type=float, default=0.9, help="nucleus sampling: the share of the probability mass the candidates of a hypothesis carry, (0, 1]")
     ap.add_argument("--decoder-noise", type=float, default=0.0)
     ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
     ap.add_argument("--rescore-reward", type=float, default=1.0)
@@ -62,7 +63,7 @@ def main():
         chunk = idx[start:start + a.batch]
         paths = [ds.img_paths[i] if a.root is None or os.path.isabs(ds.img_paths[i]) else os.path.join(a.root, ds.img_paths[i]) for i in chunk]
         vis = model.visualize(paths, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature, sample_method=a.sample_method,
-                              sample_topk=a.sample_topk, decoder_noise=a.decoder_noise, rescore_method=None if a.rescore_method == "NONE" else a.rescore_method,
+                              sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise, rescore_method=None if a.rescore_method == "NONE" else a.rescore_method,
                               rescore_reward=a.rescore_reward, visual_size=a.visual_size, input_size=a.input_size, seed=a.seed, progressive=a.progressive,
                               topg=a.topg, prefix=a.prefix, no_unk=a.no_unk)
         for j, i in enumerate(chunk):
