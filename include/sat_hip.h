@@ -367,6 +367,28 @@ int sat_caption_consensus(const int32_t* cap_tokens, const int32_t* cap_len, int
                           int32_t B, int32_t R, int32_t T, const void* table, int64_t capacity, int64_t n_images, double sigma,
                           double* scores /* (B, 2) */, void* stream);
 
+/* ------------------------------------------------------------------ chrF over the characters of the vocabulary's spelling
+ * (sat_amd/metrics.py is the specification: chrf_text, chrf_stats, chrf_sentence, chrf; nltk's sentence_chrf with whitespace ignored).
+ * Reference (b, r) and hypothesis b are sliced as in sat_caption_stats, with the same limits and SAT_EINVAL messages.  A sentence is
+ * the concatenation of its tokens' spellings without a separator: token v spells word_chars[word_offsets[v] .. word_offsets[v + 1])
+ * (int32 code points, whitespace already stripped; word_offsets (V + 1), ascending from 0); a token outside [0, V) contributes no
+ * character.  max_word_chars bounds every word's length; cap_width * max_word_chars and (T - 1) * max_word_chars must not exceed
+ * SAT_CHRF_MAX_CHARS, and beta must be positive and finite (SAT_EINVAL before any launch).  Offsets and lengths read from device memory
+ * are clamped before they address anything ([0, min(word_offsets[V], V * max_word_chars)], a word to max_word_chars); characters
+ * beyond SAT_CHRF_MAX_CHARS would be dropped, which only a misstated max_word_chars can reach.
+ *   per reference and order n = 1..SAT_CHRF_MAX_ORDER, with Lh / Lr the hypothesis's / reference's characters:
+ *     nh = max(Lh - n + 1, 0), nr = max(Lr - n + 1, 0), tp = sum over distinct character n-grams g of min(count_h(g), count_r(g));
+ *     F_n = 1e-16 if nh, nr or tp is 0, else with p = tp / nh, q = tp / nr: ((1 + beta^2) * (p * q)) / (beta^2 * p + q), in fp64;
+ *     the sentence scores (F_1 + ... + F_6) / 6, summed in ascending n;
+ *   scores (B) float64: the maximum over the image's R references (the first maximum);
+ *   stats (B, R, 8) int32, optional: tp_1..tp_6, Lh, Lr.
+ * One launch, integer arithmetic up to the F-scores: the same input gives bit-identical scores. */
+#define SAT_CHRF_MAX_ORDER 6
+#define SAT_CHRF_MAX_CHARS 2048      /* code points per sentence */
+int sat_caption_chrf(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
+                     int32_t B, int32_t R, int32_t T, const int32_t* word_offsets, const int32_t* word_chars, int32_t V,
+                     int32_t max_word_chars, double beta, double* scores /* (B) */, int32_t* stats /* (B, R, 8) or NULL */, void* stream);
+
 /* out[c] = sum_r x[r*ld + c] in a fixed order (bias gradients).  scratch: ceil(rows/256)*cols floats */
 int sat_colsum(const float* x, int64_t ld, int64_t rows, int32_t cols, float* out, float* scratch, void* stream);
 

@@ -333,6 +333,9 @@ SYMBOLS.update({          # CIDEr-D / ROUGE-L against a reference corpus (evalua
     "sat_ngram_table_add": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "sat_caption_consensus": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.c_double, _vp, _vp]),
 })
+SYMBOLS.update({          # chrF over the vocabulary's spelling (evaluation.VocabChars, chrf_scores)
+    "sat_caption_chrf": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp]),
+})
 SYMBOLS.update({          # attention overlays (visualize.py)
     "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
     "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),
@@ -340,6 +343,7 @@ SYMBOLS.update({          # attention overlays (visualize.py)
 })
 BICUBIC_MAX_SHRINK, ATTENTION_MAX_MAP = 32, 256                                 # SAT_BICUBIC_MAX_SHRINK, SAT_ATTENTION_MAX_MAP
 CAPTION_MAX_LEN, CAPTION_MAX_REFS, CAPTION_MAX_EMBED = 128, 16, 2048          # SAT_CAPTION_MAX_* of include/sat_hip.h
+CHRF_MAX_ORDER, CHRF_MAX_CHARS = 6, 2048                                       # SAT_CHRF_MAX_* of include/sat_hip.h
 RESCORE = {None: 0, "NONE": 0, "LN": 1, "WR": 2, "BAR": 3}                      # SAT_RESCORE_*
 
 def profile_start(only=None):

@@ -277,6 +277,19 @@ int sat_caption_consensus(const int32_t* cap_tokens, const int32_t* cap_len, int
     return caption_consensus(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, table, (long)capacity, (long)n_images, sigma, scores,
                              (hipStream_t)stream);
 }
+int sat_caption_chrf(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths, int32_t B,
+                     int32_t R, int32_t T, const int32_t* word_offsets, const int32_t* word_chars, int32_t V, int32_t max_word_chars, double beta,
+                     double* scores, int32_t* stats, void* stream) {
+    if (!cap_tokens || !cap_len || !refs || !ref_lengths || !word_offsets || !word_chars || !scores) return fail(SAT_EINVAL, "caption_chrf: null pointer");
+    SAT_TRY(check_caption_sizes("caption_chrf", cap_width, B, R, T));
+    if (V < 1 || max_word_chars < 0) return fail(SAT_EINVAL, "caption_chrf: V=%d (>= 1), max_word_chars=%d (>= 0)", V, max_word_chars);
+    if ((int64_t)cap_width * max_word_chars > SAT_CHRF_MAX_CHARS || (int64_t)(T - 1) * max_word_chars > SAT_CHRF_MAX_CHARS)
+        return fail(SAT_EINVAL, "caption_chrf: a sentence could exceed %d characters (cap_width=%d, T - 1=%d tokens of up to max_word_chars=%d)",
+                    SAT_CHRF_MAX_CHARS, cap_width, T - 1, max_word_chars);
+    if (!(beta > 0.0) || beta > 1.79769313486231570815e308) return fail(SAT_EINVAL, "caption_chrf: beta %g is not a positive finite number", beta);
+    return caption_chrf(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, word_offsets, word_chars, V, max_word_chars, beta, scores, stats,
+                        (hipStream_t)stream);
+}
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids, int32_t n_masked,
                     const float* parent_scores, float* scores, void* stream) {
     if (!logits || !scores || (n_masked > 0 && !masked_ids)) return fail(SAT_EINVAL, "beam_scores: null pointer");

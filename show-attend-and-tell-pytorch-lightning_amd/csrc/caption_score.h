@@ -6,6 +6,8 @@ namespace sat {
 constexpr int kCaptionMaxLen = 128;      // SAT_CAPTION_MAX_LEN
 constexpr int kCaptionMaxRefs = 16;      // SAT_CAPTION_MAX_REFS
 constexpr int kCaptionMaxEmbed = 2048;   // SAT_CAPTION_MAX_EMBED
+constexpr int kChrfMaxOrder = 6;         // SAT_CHRF_MAX_ORDER
+constexpr int kChrfMaxChars = 2048;      // SAT_CHRF_MAX_CHARS
 int beam_select(const int* tok_in, const int* prev_row, const int* fin_count, const int* fin_step, const int* fin_row, const float* fin_score,
                 const float* fin_mean, const float* alpha_hist, int B, int K, int S, int L, int method, float reward, int pad_id, int* cap_tokens,
                 int* cap_len, float* cap_score, float* cap_raw, int* cap_step, float* cap_alpha, hipStream_t st);
@@ -18,4 +20,7 @@ int ngram_table_clear(void* table, long capacity, hipStream_t st);
 int ngram_table_add(const int* refs, const int* ref_len, int B, int R, int T, void* table, long capacity, int* error_flag, hipStream_t st);
 int caption_consensus(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, const void* table,
                       long capacity, long n_images, double sigma, double* scores, hipStream_t st);
+// caption_chrf.hip: chrF over the characters of the vocabulary's spelling
+int caption_chrf(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, const int* word_offsets,
+                 const int* word_chars, int V, int max_word_chars, double beta, double* scores, int* stats, hipStream_t st);
 }  // namespace sat

@@ -15,6 +15,10 @@ Opt-in, ``corpus=ReferenceCorpus``: CIDEr-D and ROUGE-L (csrc/caption_consensus.
 specification).  The document frequency of every 1..4-gram of a split's references is built once into a hash table on the device
 (``ReferenceCorpus``) and stays there; ``consensus_scores`` scores a batch against it in the same enqueue as the statistics above, and
 ``val_batch_stats`` / ``evaluate`` / ``random_search`` carry the two sums along.  Without ``corpus`` nothing changes.
+
+Opt-in, ``chrf=VocabChars``: chrF (csrc/caption_chrf.hip; ``metrics.chrf`` is the specification), the one metric here that looks inside
+words.  The vocabulary's spelling is put on the device once (``VocabChars``); ``chrf_scores`` scores a batch over the characters of its
+tokens in one launch, and the same three carry the sum along.  Without ``chrf`` nothing changes.
 """
 import numpy as np
 import torch
@@ -206,6 +210,58 @@ def consensus_scores(tokens, lengths, refs, ref_lengths, corpus, sigma=6.0):
     return scores
 
 
+CHRF_KEYS = ("chrf",)
+
+
+class VocabChars:
+    """The vocabulary's spelling on the device (include/sat_hip.h, sat_caption_chrf): ``word_offsets (V + 1) int32`` and ``word_chars
+    (total) int32``, the code points of every id's word with whitespace stripped (``metrics.chrf_text``), and the host int
+    ``max_word_chars``.  An id absent from ``vocab_itos`` spells ``<UNK>``, as ``SAT.itos`` does.  Built once and reused by every batch
+    and trial: two copies to the device at construction, no launch and no device read afterwards."""
+
+    def __init__(self, vocab_itos, vocab_size, device="cuda"):
+        offsets, chars, self.max_word_chars = self.host_tables(vocab_itos, vocab_size)
+        self.vocab_size, self.device = int(vocab_size), torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SatHipError("sat_amd computes on the GPU only: VocabChars on %s (no CPU fallback)" % self.device)
+        self.word_offsets = torch.from_numpy(offsets).to(self.device)
+        self.word_chars = torch.from_numpy(chars if chars.size else np.zeros(1, np.int32)).to(self.device)     # never a null pointer
+
+    @staticmethod
+    def host_tables(vocab_itos, vocab_size):
+        """``(word_offsets (V + 1) int32, word_chars (total) int32, max_word_chars)`` as numpy arrays on the host"""
+        if int(vocab_size) < 1:
+            raise ValueError("VocabChars: vocab_size=%d" % vocab_size)
+        words = [metrics.chrf_text([str(vocab_itos.get(i, "<UNK>"))]) for i in range(int(vocab_size))]
+        offsets = np.zeros(len(words) + 1, np.int64)
+        np.cumsum([len(w) for w in words], out=offsets[1:])
+        if offsets[-1] > np.iinfo(np.int32).max:
+            raise ValueError("VocabChars: the vocabulary spells %d characters (int32 offsets)" % offsets[-1])
+        chars = np.array([c for w in words for c in w], np.int32)
+        return offsets.astype(np.int32), chars, max(len(w) for w in words)
+
+    @classmethod
+    def from_model(cls, model):
+        return cls(model.hp.vocab_itos, model.hp.vocab_size, model.embedding.weight.device)
+
+
+def chrf_scores(tokens, lengths, refs, ref_lengths, chars, beta=3.0, with_stats=False):
+    """``(B,)`` float64 on the device, chrF per image (the maximum over its references), of hypotheses ``tokens (B, W)`` / ``lengths
+    (B)`` against ``refs (B, R, T)`` / ``ref_lengths (B, R)`` (int32, on the device) over the spelling ``chars`` (a ``VocabChars``);
+    ``with_stats``: also ``(B, R, 8)`` int32, per reference ``tp_1..tp_6, Lh, Lr`` (``metrics.chrf_stats``).  One launch."""
+    L.require_gpu(tokens, lengths, refs, ref_lengths, chars.word_offsets, chars.word_chars)
+    for t in (tokens, lengths, refs, ref_lengths):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    B, W = tokens.shape
+    _, R, T = refs.shape
+    scores = torch.empty(B, dtype=torch.float64, device=tokens.device)
+    stats = torch.empty(B, R, 8, dtype=torch.int32, device=tokens.device) if with_stats else None
+    L.check(L.lib().sat_caption_chrf(L.ptr(tokens), L.ptr(lengths), W, L.ptr(refs), L.ptr(ref_lengths), B, R, T, L.ptr(chars.word_offsets),
+                                     L.ptr(chars.word_chars), chars.vocab_size, chars.max_word_chars, float(beta), L.ptr(scores), L.ptr(stats),
+                                     L.stream_ptr()), "sat_caption_chrf")
+    return (scores, stats) if with_stats else scores
+
+
 def metrics_from_sums(counts, cosine_sum, perplexity_sum, images):
     """the seven keys of ``score_captions`` from host numbers: 12 summed integers, two float sums, the image count"""
     counts = [int(c) for c in counts]
@@ -217,33 +273,50 @@ def metrics_from_sums(counts, cosine_sum, perplexity_sum, images):
 
 
 def metrics_from_vector(v, images):
-    """``metrics_from_sums`` of a host ``CaptionStats.vector()``: 14 numbers, or 16 with the CIDEr-D and ROUGE-L sums (means over images)"""
+    """``metrics_from_sums`` of a host ``CaptionStats.vector()``: 14 numbers; 16 with the CIDEr-D and ROUGE-L sums; 15 or 17 with the
+    chrF sum behind them (means over images)"""
+    if len(v) not in (14, 15, 16, 17):
+        raise ValueError("metrics_from_vector: %d numbers (14, 15, 16 or 17)" % len(v))
     out = metrics_from_sums(v[:12], v[12], v[13], images)
-    if len(v) > 14:
+    if len(v) >= 16:
         out["cider"], out["rouge_l"] = float(v[14]) / images, float(v[15]) / images
+    if len(v) in (15, 17):
+        out["chrf"] = float(v[-1]) / images
     return out
+
+
+def vector_keys(n):
+    """the metric keys a ``CaptionStats.vector()`` of ``n`` numbers carries"""
+    return METRIC_KEYS + (CONSENSUS_KEYS if n >= 16 else ()) + (CHRF_KEYS if n in (15, 17) else ())
 
 
 class CaptionStats:
     """Sums over images: ``counts`` (12,) int64 (the columns of sat_caption_stats), ``cosine_sum`` / ``perplexity_sum`` (float64
     scalars) on the device, ``images`` a host int; scored against a ``ReferenceCorpus`` also ``consensus_sum`` (2,) float64, the sums of
-    CIDEr-D and ROUGE-L.  ``a + b`` adds; ``metrics()`` reads the device once."""
+    CIDEr-D and ROUGE-L; scored over a ``VocabChars`` also ``chrf_sum``, a float64 scalar.  ``a + b`` adds; ``metrics()`` reads the
+    device once."""
 
-    def __init__(self, counts, cosine_sum, perplexity_sum, images, consensus_sum=None):
+    def __init__(self, counts, cosine_sum, perplexity_sum, images, consensus_sum=None, chrf_sum=None):
         self.counts, self.cosine_sum, self.perplexity_sum, self.images = counts, cosine_sum, perplexity_sum, int(images)
-        self.consensus_sum = consensus_sum
+        self.consensus_sum, self.chrf_sum = consensus_sum, chrf_sum
 
     def __add__(self, other):
         if (self.consensus_sum is None) != (other.consensus_sum is None):
             raise ValueError("CaptionStats: one side was scored against a ReferenceCorpus and the other was not")
+        if (self.chrf_sum is None) != (other.chrf_sum is None):
+            raise ValueError("CaptionStats: one side was scored with chrF (a VocabChars) and the other was not")
         return CaptionStats(self.counts + other.counts, self.cosine_sum + other.cosine_sum, self.perplexity_sum + other.perplexity_sum,
-                            self.images + other.images, None if self.consensus_sum is None else self.consensus_sum + other.consensus_sum)
+                            self.images + other.images, None if self.consensus_sum is None else self.consensus_sum + other.consensus_sum,
+                            None if self.chrf_sum is None else self.chrf_sum + other.chrf_sum)
 
     def vector(self):
-        """(14,) float64 on the device: the counts (exact below 2^53), then the two sums; (16,) with the CIDEr-D and ROUGE-L sums"""
+        """(14,) float64 on the device: the counts (exact below 2^53), then the two sums; (16,) with the CIDEr-D and ROUGE-L sums; the
+        chrF sum, if any, comes last: (15,) or (17,)"""
         parts = [self.counts.to(torch.float64), self.cosine_sum.reshape(1), self.perplexity_sum.reshape(1)]
         if self.consensus_sum is not None:
             parts.append(self.consensus_sum.reshape(2))
+        if self.chrf_sum is not None:
+            parts.append(self.chrf_sum.reshape(1))
         return torch.cat(parts)
 
     def metrics(self):
@@ -253,10 +326,10 @@ class CaptionStats:
 @torch.no_grad()
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                     rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
-                    sample_topp=0.9):
+                    sample_topp=0.9, chrf=None, chrf_beta=3.0):
     """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
-    with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue.  ``topg`` / ``prefix`` / ``banned`` /
-    ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
+    with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue, with ``chrf`` (a ``VocabChars``) chrF
+    with ``chrf_beta``.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
     tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
@@ -265,18 +338,23 @@ def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, s
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())
     consensus = None if corpus is None else consensus_scores(tokens, lens, refs, ref_lengths, corpus).sum(0)
-    return CaptionStats(stats.sum(0, dtype=torch.int64), best.sum(dtype=torch.float64), ppl.sum(dtype=torch.float64), tokens.shape[0], consensus)
+    chrf_sum = None if chrf is None else chrf_scores(tokens, lens, refs, ref_lengths, chrf, chrf_beta).sum()
+    return CaptionStats(stats.sum(0, dtype=torch.int64), best.sum(dtype=torch.float64), ppl.sum(dtype=torch.float64), tokens.shape[0], consensus,
+                        chrf_sum)
 
 
-def evaluate(model, loader, max_batches=None, seed=None, corpus=None, **decode):
+def evaluate(model, loader, max_batches=None, seed=None, corpus=None, chrf=None, **decode):
     """``val_batch_stats`` over the batches of ``loader`` (at most ``max_batches``).  Returns ``{"batch_mean": the notebook's protocol,
     the plain mean of the per-batch metric dicts, "corpus": BLEU / GLEU taken once from the statistics summed over every image (cosine and
     perplexity: means over images), "batches", "images"}``.  The per-batch statistics stay on the device and are read once at the end.
     ``seed``: batch i of a sampled search draws with ``seed + i``.  ``corpus`` (a ``ReferenceCorpus``): both dicts gain "cider" and
-    "rouge_l" (means over images); still one host read.  ``decode`` takes every keyword of ``val_batch_stats``, the search constraints
+    "rouge_l" (means over images), ``chrf`` (a ``VocabChars``; ``chrf_beta`` travels in ``decode``): both gain "chrf"; still one host
+    read.  ``decode`` takes every keyword of ``val_batch_stats``, the search constraints
     ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` among them."""
     if corpus is not None:
         decode["corpus"] = corpus
+    if chrf is not None:
+        decode["chrf"] = chrf
     vecs, images = [], []
     for i, batch in enumerate(loader):
         if max_batches is not None and i >= max_batches:
@@ -288,7 +366,7 @@ def evaluate(model, loader, max_batches=None, seed=None, corpus=None, **decode):
     rows = torch.stack(vecs).cpu().tolist()                                  # the one host read
     per_batch = [metrics_from_vector(r, n) for r, n in zip(rows, images)]
     total = [sum(int(r[c]) for r in rows) for c in range(12)] + [sum(r[c] for r in rows) for c in range(12, len(rows[0]))]
-    keys = METRIC_KEYS + (CONSENSUS_KEYS if len(rows[0]) > 14 else ())
+    keys = vector_keys(len(rows[0]))
     return {"batch_mean": {k: sum(d[k] for d in per_batch) / len(per_batch) for k in keys}, "corpus": metrics_from_vector(total, sum(images)),
             "batches": len(per_batch), "images": sum(images)}
 
@@ -312,21 +390,27 @@ def draw_decode_params(rs, space=NOTEBOOK_SPACE):
     return row
 
 
-def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4, corpus=None):
+def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4, corpus=None, chrf=None, chrf_beta=3.0):
     """evaluate.ipynb's random search: ``trials`` draws from one ``np.random.RandomState(seed)``, each scored over the first
     ``max_batches`` batches.  Rows carry the notebook's 13 columns (the metrics are its batch means) plus ``<metric>_corpus``; with
     ``corpus`` (a ``ReferenceCorpus``, built once and reused by every trial) also cider, rouge_l, cider_corpus, rouge_l_corpus; with
-    ``space["topgs"]`` also a ``topg`` column (``draw_decode_params``)."""
+    ``chrf`` (a ``VocabChars``, likewise) also chrf and chrf_corpus; with ``space["topgs"]`` also a ``topg`` column (``draw_decode_params``)."""
     rs = np.random.RandomState(seed)
     rows = []
+    extra = {} if corpus is None else {"corpus": corpus}
+    if chrf is not None:
+        extra.update(chrf=chrf, chrf_beta=chrf_beta)
     for trial in range(int(trials)):
         row = draw_decode_params(rs, space)
         res = evaluate(model, loader, max_batches=max_batches, seed=None if seed is None else (int(seed) * 1000003 + trial) % (2 ** 62),
-                       max_gen_length=space["max_gen_length"], **row, **({} if corpus is None else {"corpus": corpus}))
+                       max_gen_length=space["max_gen_length"], **row, **extra)
         row.update({k: res["batch_mean"][k] for k in METRIC_KEYS})
         row.update({k + "_corpus": res["corpus"][k] for k in METRIC_KEYS})
         if corpus is not None:
             row.update({k: res["batch_mean"][k] for k in CONSENSUS_KEYS})
             row.update({k + "_corpus": res["corpus"][k] for k in CONSENSUS_KEYS})
+        if chrf is not None:
+            row.update({k: res["batch_mean"][k] for k in CHRF_KEYS})
+            row.update({k + "_corpus": res["corpus"][k] for k in CHRF_KEYS})
         rows.append(row)
     return rows

@@ -196,3 +196,60 @@ def rouge_l(references, hypothesis, beta=1.2):
     if prec != 0 and rec != 0:
         return ((1 + beta ** 2) * prec * rec) / float(rec + beta ** 2 * prec)
     return 0.0
+
+
+# ----------------------------------------------------------------------------- chrF: character n-gram F-score
+# chrF (Popovic 2015) as nltk's ``chrf_score.py`` computes it (``sentence_chrf`` / ``corpus_chrf`` with ``min_len=1, max_len=6,
+# beta=3.0, ignore_whitespace=True``): restated over lists of word strings, nltk being absent here.  It is the specification of
+# sat_caption_chrf (csrc/caption_chrf.hip): plain counters, fp64.  The one metric of this file that looks inside words.
+CHRF_MAX_ORDER = 6
+CHRF_EPSILON = 1e-16          # the F-score of an order that is undefined (no n-gram on one side) or has no match
+
+
+def chrf_text(words):
+    """the Unicode code points (a list of ints) of the words concatenated, every whitespace code point dropped: tokens do not separate
+    n-grams ("a man" gives a, m, a, n and the bigram "am" exists)"""
+    return [ord(c) for w in words for c in str(w) if not c.isspace()]
+
+
+def chrf_stats(reference, hypothesis):
+    """``(tp, Lh, Lr)``: per order n = 1..6 the matches ``sum over distinct n-grams g of min(count_h(g), count_r(g))``, and the
+    character counts of hypothesis and reference"""
+    hyp, ref = chrf_text(hypothesis), chrf_text(reference)
+    tp = []
+    for n in range(1, CHRF_MAX_ORDER + 1):
+        ch, cr = Counter(_ngrams(hyp, n)), Counter(_ngrams(ref, n))
+        tp.append(sum(min(c, cr[g]) for g, c in ch.items()))
+    return tp, len(hyp), len(ref)
+
+
+def chrf_from_stats(tp, hyp_chars, ref_chars, beta=3.0):
+    """the sentence score from the integers of ``chrf_stats``: the mean over all six orders of F_n, summed in ascending n"""
+    beta2 = float(beta) * float(beta)
+    total = 0.0
+    for n in range(1, CHRF_MAX_ORDER + 1):
+        nh, nr, t = max(int(hyp_chars) - n + 1, 0), max(int(ref_chars) - n + 1, 0), int(tp[n - 1])
+        if nh == 0 or nr == 0 or t == 0:
+            f = CHRF_EPSILON
+        else:
+            p, q = t / nh, t / nr
+            f = ((1.0 + beta2) * (p * q)) / (beta2 * p + q)
+        total += f
+    return total / CHRF_MAX_ORDER
+
+
+def chrf_sentence(reference, hypothesis, beta=3.0):
+    """chrF of one hypothesis against one reference (lists of word strings)"""
+    return chrf_from_stats(*chrf_stats(reference, hypothesis), beta=beta)
+
+
+def chrf(references, hypothesis, beta=3.0):
+    """chrF of one image: the maximum over its references"""
+    return max(chrf_sentence(ref, hypothesis, beta) for ref in references)
+
+
+def corpus_chrf(list_of_references, hypotheses, beta=3.0):
+    """the mean of the image scores"""
+    assert len(list_of_references) == len(hypotheses), "one reference set per hypothesis"
+    scores = [chrf(references, hypothesis, beta) for references, hypothesis in zip(list_of_references, hypotheses)]
+    return sum(scores) / len(scores)

@@ -785,12 +785,12 @@ class SAT(SATDecoder, _Base):
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                         rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
-                        sample_topp=0.9):
+                        sample_topp=0.9, chrf=None, chrf_beta=3.0):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
-        (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L)"""
+        (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L; with ``chrf``, an ``evaluation.VocabChars``, also chrF)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp)
+                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp, chrf, chrf_beta)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False,

@@ -8,8 +8,12 @@ split, by host clocks around synchronised sections of one more trial, into encod
 --cider measures instead what CIDEr-D and ROUGE-L cost at beam 5: the per-batch time of ``val_batch_stats`` without and with
 ``corpus=`` (alternating rounds, hipEvents), the host clock of ``metrics.cider_d`` + ``metrics.rouge_l`` on the same tokens (already
 on the host as lists: the read-back is not counted), and the one-off build of the document-frequency table for --split-images images.
+--chrf measures the same for chrF: ``val_batch_stats`` without and with ``chrf=`` (alternating rounds, hipEvents), the host clock of
+``metrics.chrf`` on the same tokens (already on the host as lists), and the build of the ``VocabChars``.  The synthetic vocabulary is
+spelled with pseudo-words of 1..12 letters (5 on average, about an English caption's), drawn from a seed.
     python tools/bench_evaluate.py [--beams 5 20] [--batches 4] [--images 128] [--repeats 5] [--precision bf16] [--json]
     python tools/bench_evaluate.py --cider [--split-images 5000] [--batches 4] [--images 128] [--repeats 5] [--json]
+    python tools/bench_evaluate.py --chrf [--batches 4] [--images 128] [--repeats 5] [--json]
 """
 import argparse
 import json
@@ -108,6 +112,67 @@ def bench_cider(a, model, batches, hp, T, R):
           (res["cider_device"], res["cider_host"], res["rouge_l_device"], res["rouge_l_host"]))
 
 
+def synthetic_spelling(model, seed=7):
+    """gives every id of the synthetic vocabulary a pseudo-word: 1..12 lower-case letters, 5 on average, from ``seed``"""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    itos = dict(model.hp.vocab_itos)
+    for i in range(model.hp.vocab_size):
+        if i not in itos:
+            itos[i] = "".join(chr(97 + c) for c in rs.randint(0, 26, size=int(np.clip(rs.poisson(4.0) + 1, 1, 12))))
+    model.hp.vocab_itos = itos
+
+
+def bench_chrf(a, model, batches, hp, T, R):
+    """--chrf: val_batch_stats without / with chrf, the host scorer on the same tokens, the VocabChars build"""
+    kw = dict(beamk=5, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
+    synthetic_spelling(model)
+    E.VocabChars.from_model(model)                       # warm-up
+    build_ms = [clock_ms(lambda: E.VocabChars.from_model(model))[0] for _ in range(a.repeats)]
+    chars = E.VocabChars.from_model(model)
+
+    def plain():
+        return E.evaluate(model, batches, **kw)
+
+    def with_chrf():
+        return E.evaluate(model, batches, chrf=chars, **kw)
+
+    def host():
+        out = []
+        for img, caps, lengths in batches:
+            tok, ln, _, _ = model.caption_tokens(img, **kw)
+            hyps = [model.decode_seq(t[:n]) for t, n in zip(tok.tolist(), ln.tolist())]
+            refs = [[model.decode_seq(c[1:n]) for c, n in zip(cs, ns)] for cs, ns in zip(caps.tolist(), lengths.tolist())]
+            t0 = time.perf_counter()
+            c = metrics.corpus_chrf(refs, hyps)
+            out.append(((time.perf_counter() - t0) * 1e3, c, sum(len(metrics.chrf_text(h)) for h in hyps) / len(hyps)))
+        return out
+
+    plain(); got = with_chrf(); want = host()
+    torch.cuda.synchronize()
+    ms = {"plain": [], "chrf": []}
+    for _ in range(a.repeats):                           # alternating rounds
+        ms["plain"].append(event_ms(plain)[0] / a.batches)
+        ms["chrf"].append(event_ms(with_chrf)[0] / a.batches)
+    host_ms = [statistics.median(t for t, _, _ in host()) for _ in range(a.repeats)]
+    spread = lambda v: dict(median=statistics.median(v), min=min(v), max=max(v))
+    res = dict(beamk=5, images=a.images, references=R, batches=a.batches, repeats=a.repeats, precision=a.precision, vocab_size=chars.vocab_size,
+               vocab_characters=int(chars.word_chars.numel()), max_word_chars=chars.max_word_chars,
+               hypothesis_characters_mean=sum(n for _, _, n in want) / len(want),
+               val_batch_stats_ms_per_batch=spread(ms["plain"]), val_batch_stats_chrf_ms_per_batch=spread(ms["chrf"]),
+               host_chrf_ms_per_batch=spread(host_ms), vocab_chars_build_ms=spread(build_ms),
+               chrf_device=got["batch_mean"]["chrf"], chrf_host=sum(c for _, c, _ in want) / len(want))
+    if a.json:
+        print(json.dumps(res))
+        return
+    print("beam 5, %d batches of %d images x %d references, %s; %d words spelled with %d characters, hypotheses of %.1f characters on average" %
+          (a.batches, a.images, R, a.precision, chars.vocab_size, res["vocab_characters"], res["hypothesis_characters_mean"]))
+    for name, key in (("val_batch_stats", "val_batch_stats_ms_per_batch"), ("val_batch_stats(chrf=)", "val_batch_stats_chrf_ms_per_batch"),
+                      ("host metrics.chrf (words already on the host)", "host_chrf_ms_per_batch"), ("VocabChars build, once per model", "vocab_chars_build_ms")):
+        print("  %-52s %8.3f ms (min %.3f, max %.3f)" % (name, res[key]["median"], res[key]["min"], res[key]["max"]))
+    print("  chrF device %.12f host %.12f" % (res["chrf_device"], res["chrf_host"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beams", type=int, nargs="+", default=[5, 20])
@@ -118,6 +183,7 @@ def main():
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--cider", action="store_true", help="measure CIDEr-D / ROUGE-L: val_batch_stats with and without corpus=, the host scorer, the build")
+    ap.add_argument("--chrf", action="store_true", help="measure chrF: val_batch_stats with and without chrf=, the host scorer, the VocabChars build")
     ap.add_argument("--split-images", type=int, default=5000, help="--cider: images in the corpus the table is built from")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -132,6 +198,8 @@ def main():
         batches.append((img.cuda(), caps.cuda(), lengths.cuda()))
     if a.cider:
         return bench_cider(a, model, batches, hp, T, R)
+    if a.chrf:
+        return bench_chrf(a, model, batches, hp, T, R)
     for beamk in a.beams:
         kw = dict(beamk=beamk, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
 

@@ -4,9 +4,11 @@ of per-batch metrics and the corpus-level score of the whole split.  With --tria
 parameter ranges, each scored over the first --max-batches batches), written as csv with its 13 columns plus ``<metric>_corpus``.
 --cider: CIDEr-D and ROUGE-L as well; the n-gram document frequencies of the evaluated split are built once on the device
 (``evaluation.ReferenceCorpus``) and every batch and trial is scored against them (columns cider, rouge_l, cider_corpus, rouge_l_corpus).
+--chrf [--chrf-beta 3.0]: chrF as well (character n-grams, n = 1..6, across word boundaries); the vocabulary's spelling is put on the
+device once (``evaluation.VocabChars``) and every batch and trial is scored over it (columns chrf, chrf_corpus).  Combinable with --cider.
 All work is in sat_amd/evaluation.py: a batch is decoded and scored on the device, one host read per pass.
     python tools/evaluate.py CHECKPOINT [--json DATASET.json] [--root IMAGE_DIR] [--split test] [--batch N] [--max-batches M]
-                             [--trials N --seed S --out results.csv]  [--cider]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
+                             [--trials N --seed S --out results.csv]  [--cider]  [--chrf --chrf-beta 3.0]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
 """
 import argparse
 import csv
@@ -37,6 +39,8 @@ def main():
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--out", default=None, help="csv (with --trials) or json (without) to write")
     ap.add_argument("--cider", action="store_true", help="also CIDEr-D and ROUGE-L against the document frequencies of the evaluated split")
+    ap.add_argument("--chrf", action="store_true", help="also chrF over the characters of the vocabulary's spelling")
+    ap.add_argument("--chrf-beta", type=float, default=3.0, help="chrF: the weight of recall over precision")
     ap.add_argument("--beamk", type=int, default=5)
     ap.add_argument("--max-gen-length", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -57,9 +61,10 @@ def main():
     ds = D.CocoCaptionDataset(a.json or model.hparams.json, a.split, root=a.root)
     loader = D.DeviceLoader(ds, a.batch or model.hparams.batch, D.BatchTransform(model.hparams.input_size, train=False), workers=a.workers)
     corpus = E.ReferenceCorpus.from_dataset(ds).check() if a.cider else None
-    shown = E.HEADERS + (list(E.CONSENSUS_KEYS) if a.cider else [])
+    chars = E.VocabChars.from_model(model) if a.chrf else None
+    shown = E.HEADERS + (list(E.CONSENSUS_KEYS) if a.cider else []) + (list(E.CHRF_KEYS) if a.chrf else [])
     if a.trials > 0:
-        rows = E.random_search(model, loader, a.trials, seed=a.seed, max_batches=a.max_batches or 4, corpus=corpus)
+        rows = E.random_search(model, loader, a.trials, seed=a.seed, max_batches=a.max_batches or 4, corpus=corpus, chrf=chars, chrf_beta=a.chrf_beta)
         cols = list(rows[0])
         for r in sorted(rows, key=lambda r: -r["bleu4"]):
             print("  ".join("%s=%s" % (k, ("%.4f" % r[k]) if isinstance(r[k], float) else r[k]) for k in shown))
@@ -68,12 +73,12 @@ def main():
                 w = csv.DictWriter(f, fieldnames=cols)
                 w.writeheader(); w.writerows(rows)
         return
-    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
+    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, **(dict(chrf=chars, chrf_beta=a.chrf_beta) if a.chrf else {}), beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
                      sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise,
                      rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward, topg=a.topg,
                      no_unk=a.no_unk)
     print("%d images in %d batches" % (res["images"], res["batches"]))
-    for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()):
+    for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()) + (E.CHRF_KEYS if a.chrf else ()):
         print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))
     if a.out:
         with open(a.out, "w") as f:
