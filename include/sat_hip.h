@@ -165,6 +165,51 @@ int sat_doubly_stochastic_fwd(const float* alphas, int32_t N, int32_t T1, int32_
 int sat_doubly_stochastic_bwd(const float* asum, const float* gscale, int32_t N, int32_t T1, int32_t L, float gamma,
                               float* dalphas, void* stream);
 
+/* ------------------------------------------------------------------ policy-gradient loss (self-critical sequence training; Rennie et al. 2017)
+ * The REINFORCE surrogate over packed logits (P, V): every packed row p is one sampled action (targets[p]) with a weight of its own
+ * (row_weight[p], the advantage of the caption it belongs to; any sign, 0 allowed).  The distribution differentiated is the one
+ * SAT_SAMPLE_ANCESTRAL draws from: the softmax at the search's temperature over the words the search leaves unmasked.
+ * masked_ids is a DEVICE array of 4 ids {START, PAD, END, UNK}: the first n_first_rows rows (the rows of decode step 0: packed rows are
+ * time-major) mask all four, the other rows the first two.  An id outside [0, V) masks nothing.  With x = logits[p] * inv_temperature
+ * and U the unmasked ids of the row:
+ *   lse_rows[p]  = logsumexp over v in U of x[v]
+ *   logq_rows[p] = x[targets[p]] - lse_rows[p]                 (NaN when the target is outside [0, V) or masked in its row; never a stray read)
+ *   out[0]       = -scale * sum over the rows with row_weight != 0 of row_weight[p] * logq_rows[p]
+ * The row terms are summed in double in a fixed order without atomics: the same input gives the same bits.  The forward reads every
+ * row once (logq_rows is written for the rows of weight zero too); a row of weight zero adds exactly 0 to the loss whatever it holds.
+ * Backward: dlogits[p][v] = gscale[0] * scale * row_weight[p] * inv_temperature * (softmax_U(x)[v] - [v == targets[p]]) for v in U and
+ * exactly 0 for masked v; a row of weight zero is written as zeros and its logits are not read.  gscale: device pointer or NULL = 1.
+ * One 256-thread block per row; 16-byte loads and stores when V % 4 == 0 and logits (and dlogits) are 16-byte aligned, 4-byte ones
+ * otherwise.  SAT_EINVAL before any launch: a null pointer, P <= 0, V <= 0, n_first_rows outside [0, P], an inv_temperature that is
+ * not a positive finite number, a non-finite scale.  scratch: lse_rows, logq_rows P floats each. */
+int sat_policy_nll_fwd(const float* logits, const int32_t* targets, const float* row_weight, int32_t P, int32_t V, float inv_temperature,
+                       const int32_t* masked_ids, int32_t n_first_rows, float scale, float* lse_rows, float* logq_rows, float* out, void* stream);
+int sat_policy_nll_bwd(const float* logits, const int32_t* targets, const float* row_weight, const float* lse_rows, int32_t P, int32_t V,
+                       float inv_temperature, const int32_t* masked_ids, int32_t n_first_rows, float scale, const float* gscale, float* dlogits,
+                       void* stream);
+/* From the scores of sampled captions to the train batch of the policy loss, one launch, one block per image, no host read.
+ *   cap_tokens (N, S + 1), cap_len (N): sat_beam_select's output for N = B * K rows, image b owning rows b * K .. b * K + K - 1
+ *   scores (N, 2) float64: sat_caption_consensus's [CIDEr-D, ROUGE-L]; scores_greedy (B, 2): the same for the image's greedy caption
+ *   reward[n]    = w_cider * cider + w_rouge * rouge
+ *   baseline[n]  = SAT_SCST_BASELINE_GREEDY: the image's greedy reward; SAT_SCST_BASELINE_MEAN: the mean reward of the image's other
+ *                  K - 1 samples, summed in ascending order (needs K >= 2)                     (optional output: NULL skips it)
+ *   advantage[n] = reward[n] - baseline[n], in double up to the final float
+ *   caps (N, S + 2) int32 = START, w_1 .. w_len, END, PAD ...;  lengths[n] = len + 1, the decode steps (the dataset's convention)
+ *   step_weight (N, S + 1): advantage[n] for the steps 0 .. len - 1 and for the END step len when len < S, else 0.  A caption of S
+ *                words was cut by the search: the word drawn at its last step is dropped, that draw cannot change the reward, and
+ *                its step carries no gradient.
+ *   count[n]     = len + (len < S): the steps the mask keeps
+ * len = cap_len[n] clamped to [1, S] before it addresses anything.  special_ids_host {START, PAD, END, UNK} is a HOST array.
+ * SAT_EINVAL before the launch: a null pointer, B / K / S < 1, K > SAT_SCST_MAX_SAMPLES, S + 1 > SAT_CAPTION_MAX_LEN, an unknown
+ * mode, the greedy baseline without scores_greedy, the mean baseline with K < 2, a non-finite reward weight. */
+#define SAT_SCST_BASELINE_GREEDY 0
+#define SAT_SCST_BASELINE_MEAN 1
+#define SAT_SCST_MAX_SAMPLES 256
+int sat_scst_prepare(const int32_t* cap_tokens, const int32_t* cap_len, const double* scores, const double* scores_greedy /* or NULL */, int32_t B,
+                     int32_t K, int32_t S, double w_cider, double w_rouge, int32_t baseline_mode, const int32_t* special_ids_host, float* reward,
+                     float* baseline /* or NULL */, float* advantage, int32_t* caps, int32_t* lengths, float* step_weight, int32_t* count,
+                     void* stream);
+
 /* ------------------------------------------------------------------ temperature-scaling calibration (temperature_scaling.py:51-59)
  * For packed logits (P, V) and targets (P):  loss(T) = F.cross_entropy(logits / T, targets)  and its derivative
  * dloss/dT = mean_i [ x_iy - sum_j softmax(x_i / T)_j x_ij ] / T^2.  The row maximum does not depend on T > 0, so it is taken once;
@@ -219,6 +264,7 @@ int sat_beam_search_batched(const sat_decoder_dims* d, const sat_decoder_params*
  *   gumbel  : method 1: (max_gen_length + 1, B * beamk, V)            Gumbel(0, 1) variate of candidate word v of a row
  *             method 2: (max_gen_length + 1, B * beamk, sample_topk)  ... of the row's t-th best candidate (torch.topk order)
  *             method 3: (max_gen_length + 1, B * beamk, V)            as method 1
+ *             method 4: (max_gen_length + 1, B * beamk, V)            as method 1; slab 0 (step 0) is read as well
  *   normals : (max_gen_length + 1, layers, B * beamk, n) standard normals of the state noise
  * rows are the compacted beam rows of that step (image b owns rows b * beamk ...).  sampling = NULL is sat_beam_search_batched.
  *
@@ -234,11 +280,23 @@ int sat_beam_search_batched(const sat_decoder_dims* d, const sat_decoder_params*
  * With beamk = 1 this draws proportionally to p^(1/step) inside the nucleus, as SAT_SAMPLE_TOPK does inside its candidates, NOT
  * proportionally to p: the reference's convention, kept on purpose so that the two methods differ in the candidate set only.
  * Without a table the variate of word v is the hash at (seed, step, row * V + v), method 1's indexing.  sample_topp must be finite
- * and in (0, 1] (SAT_EINVAL before any launch); top-g clipping does not combine with it; prefix, banned ids and the masks do. */
+ * and in (0, 1] (SAT_EINVAL before any launch); top-g clipping does not combine with it; prefix, banned ids and the masks do.
+ *
+ * SAT_SAMPLE_ANCESTRAL draws every word, the first one included, from the model's own distribution: methods 1 to 3 sharpen it
+ * (softmax(20 s / step), p^(1/step)) and take the first step deterministically, which biases a policy gradient.  For a live row with
+ * masked scores s[v] (step 0 masks {START, PAD, END, UNK}, later steps {START, PAD}; masked words stay at -inf):
+ *   key[v] = s[v] + G[v]; the row takes the arg-max key, ties to the lower word id; the recorded score is s at the pick.
+ * That is one draw from softmax(logits / T) renormalised over the unmasked words (the Gumbel-max identity), T the search's own
+ * temperature of the step.  G comes from the table gumbel (max_gen_length + 1, B * beamk, V) or from the hash at
+ * (seed, step, row * V + v): method 1's layout and indexing, here for step 0 too.  Defined for beamk == 1 only (independent samples
+ * of one image are rows of a larger batch, so that no per-image top-k couples them); beamk != 1, any constraint, or a stream that
+ * is being captured gives SAT_EINVAL before any launch.  The cut rule holds as for every method: the word drawn at step
+ * max_gen_length is dropped, so a hypothesis of max_gen_length words does not depend on the last step's draw. */
 #define SAT_SAMPLE_BEAM 0
 #define SAT_SAMPLE_MULTINOMIAL 1
 #define SAT_SAMPLE_TOPK 2
 #define SAT_SAMPLE_NUCLEUS 3
+#define SAT_SAMPLE_ANCESTRAL 4
 typedef struct sat_beam_sampling {
     int32_t method;            /* SAT_SAMPLE_*                                                  */
     int32_t sample_topk;       /* candidates per hypothesis, method 2                            */

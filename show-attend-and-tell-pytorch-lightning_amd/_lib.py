@@ -80,7 +80,7 @@ class BeamSampling(C.Structure):
 
 
 #: SAT.forward's sample_method -> SAT_SAMPLE_*
-SAMPLE_METHODS = {"beam": 0, "multinomial": 1, "topk": 2, "nucleus": 3}
+SAMPLE_METHODS = {"beam": 0, "multinomial": 1, "topk": 2, "nucleus": 3, "ancestral": 4}
 
 
 class BeamConstraints(C.Structure):
@@ -336,6 +336,13 @@ SYMBOLS.update({          # CIDEr-D / ROUGE-L against a reference corpus (evalua
 SYMBOLS.update({          # chrF over the vocabulary's spelling (evaluation.VocabChars, chrf_scores)
     "sat_caption_chrf": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp]),
 })
+SYMBOLS.update({          # self-critical sequence training (scst.py): the row-weighted policy loss and the train batch of sampled captions
+    "sat_policy_nll_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _f, _vp, _i32, _f, _vp, _vp, _vp, _vp]),
+    "sat_policy_nll_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _f, _vp, _i32, _f, _vp, _vp, _vp]),
+    "sat_scst_prepare": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32, C.POINTER(C.c_int32)] + [_vp] * 8),
+})
+SCST_BASELINES = {"greedy": 0, "mean": 1}                                       # SAT_SCST_BASELINE_*
+SCST_MAX_SAMPLES = 256                                                          # SAT_SCST_MAX_SAMPLES
 SYMBOLS.update({          # attention overlays (visualize.py)
     "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
     "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -35,6 +35,20 @@ class SearchConstraints:
         return con, keep
 
 
+def check_ancestral(sample_method, beamk, graph=False, topg=None, prefix=None, banned=None, no_unk=False):
+    """``ValueError`` for a call that ``sample_method="ancestral"`` is not defined for (include/sat_hip.h, SAT_SAMPLE_ANCESTRAL): it draws one
+    hypothesis per row (``beamk == 1``; independent samples of an image are rows of a larger batch), takes no constraint and is not
+    replayed from a graph.  Touches no GPU."""
+    if sample_method != "ancestral":
+        return
+    if int(beamk) != 1:
+        raise ValueError("sample_method='ancestral' is defined for beamk=1 only (beamk=%d): repeat the images to draw several samples" % int(beamk))
+    if topg is not None or prefix is not None or no_unk or (banned is not None and len(banned) > 0):
+        raise ValueError("sample_method='ancestral' does not combine with topg / prefix / banned / no_unk")
+    if graph:
+        raise ValueError("sample_method='ancestral' is not replayed from a graph (graph=True)")
+
+
 def _one_prefix(p, stoi):
     if isinstance(p, str):
         ids = []

@@ -838,8 +838,15 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
     const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
     BeamWs w = beam_layout(d, K, ws, topg);
-    SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_NUCLEUS && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
+    SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_ANCESTRAL && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
                 "beam_batched: sampling method %d, sample_topk %d", method, smp ? smp->sample_topk : 0);
+    if (method == SAT_SAMPLE_ANCESTRAL) {
+        SAT_REQUIRE(K == 1, "beam_batched: ancestral sampling is defined for beamk == 1 (beamk %d): samples are rows of the batch", K);
+        SAT_REQUIRE(!con, "beam_batched: ancestral sampling does not combine with constraints (topg / prefix / banned ids)");
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+        SAT_REQUIRE(cap == hipStreamCaptureStatusNone, "beam_batched: ancestral sampling is not replayed from a graph (the stream is being captured)");
+    }
     SAT_REQUIRE(method != SAT_SAMPLE_NUCLEUS || (smp->sample_topp > 0.f && smp->sample_topp <= 1.f),
                 "beam_batched: sample_topp %g outside (0, 1] (nucleus sampling)", smp ? (double)smp->sample_topp : 0.0);
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
@@ -957,7 +964,15 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
             hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, w.logits, V, 1.0f / T, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2,
                                step == 0 ? (const float*)nullptr : w.top, w.scores);
             SAT_TRY(launch_ok("beam_scores"));
-            if (method == 0 || step == 0) {                // the first step always takes the top beamk words (model.py:343)
+            if (method == SAT_SAMPLE_ANCESTRAL) {          // beamk == 1: every step, the first included, is one draw from the row's own distribution
+                hipLaunchKernelGGL(beam_ancestral_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, (unsigned long long)smp->seed,
+                                   (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * V : (const float*)nullptr, w.keys);
+                SAT_TRY(launch_ok("beam_ancestral_keys"));
+                hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.keys, w.work, w.klive, K, V, 0, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_topk (keys)"));
+                hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
+                SAT_TRY(launch_ok("beam_take_scores"));
+            } else if (method == 0 || step == 0) {         // the first step always takes the top beamk words (model.py:343)
                 hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
                 SAT_TRY(launch_ok("beam_topk"));
             } else {                                       // model.py:360-379: draw the continuing hypotheses (Gumbel-top-k == multinomial without replacement)

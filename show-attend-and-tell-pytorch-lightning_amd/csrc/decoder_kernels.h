@@ -1385,6 +1385,19 @@ __global__ __launch_bounds__(256) void beam_sample_keys_kernel(const float* __re
         }
     }
 }
+// ---- method 4 ("ancestral", DESIGN.md 5 "Self-critical training"): keys[i, v] = s[v] + G[v] for live row i, every step: the arg-max
+// key is one draw from the row's own distribution over its unmasked words (-inf stays -inf).  Table layout and hash indexing of method 1.
+__global__ __launch_bounds__(256) void beam_ancestral_keys_kernel(const float* __restrict__ scores, const int* __restrict__ klive, int K, int V,
+                                                                  unsigned long long seed, unsigned long long stream, const float* __restrict__ gumbel,
+                                                                  float* __restrict__ keys) {
+    const int i = blockIdx.x, b = i / K, j = i - b * K;
+    if (j >= klive[b]) return;
+    const float* s = scores + (long)i * V; float* key = keys + (long)i * V;
+    for (int v = threadIdx.x; v < V; v += 256) {
+        const float g = gumbel ? gumbel[(long)i * V + v] : gumbel_of(hash_uniform(seed, stream, (unsigned long long)i * V + v));
+        key[v] = s[v] + g;
+    }
+}
 // ---- method 3 ("nucleus", DESIGN.md 5 "Sampled decoding"): "topk"'s rule s / step + G on another candidate set, the fewest words of
 // the row (score descending, ties to the lower id) whose weights w = exp(s - max) sum to topp * W.  The cut is searched on the
 // score itself: the order-preserving unsigned image of the float is bisected bit by bit, every pass one block reduction of

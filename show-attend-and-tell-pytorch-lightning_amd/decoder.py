@@ -249,6 +249,46 @@ class LabelSmoothingFn(torch.autograd.Function):
         return dlogits, None, None
 
 
+class PolicyNLLFn(torch.autograd.Function):
+    """The row-weighted policy loss of self-critical training on packed rows (include/sat_hip.h, sat_policy_nll_fwd):
+    ``-scale * sum_p row_weight[p] * log q(targets[p])`` with q the softmax of ``logits / temperature`` over the words the search leaves
+    unmasked.  ``masked_ids``: device int32 (4) {START, PAD, END, UNK}; the first ``n_first_rows`` packed rows mask all four, the others
+    the first two.  Differentiable in ``logits`` only; rows of weight zero get a zero gradient without being read."""
+
+    @staticmethod
+    def forward(ctx, logits, targets_i32, row_weight, inv_temperature, masked_ids, n_first_rows, scale):
+        lib = L.lib()
+        L.require_gpu(logits, targets_i32, row_weight, masked_ids)
+        logits = logits.contiguous()
+        P, V = logits.shape
+        if targets_i32.dtype != torch.int32 or masked_ids.dtype != torch.int32 or row_weight.dtype != torch.float32:
+            raise ValueError("PolicyNLLFn: targets and masked_ids are int32, row_weight is float32")
+        if targets_i32.numel() != P or row_weight.numel() != P or masked_ids.numel() != 4:
+            raise ValueError("PolicyNLLFn: %d targets / %d weights for %d packed rows, %d masked ids (4)"
+                             % (targets_i32.numel(), row_weight.numel(), P, masked_ids.numel()))
+        targets_i32, row_weight, masked_ids = targets_i32.contiguous(), row_weight.contiguous(), masked_ids.contiguous()
+        lse = torch.empty(P, dtype=torch.float32, device=logits.device)
+        logq = torch.empty(P, dtype=torch.float32, device=logits.device)
+        out = torch.empty(1, dtype=torch.float32, device=logits.device)
+        L.check(lib.sat_policy_nll_fwd(L.ptr(logits), L.ptr(targets_i32), L.ptr(row_weight), P, V, float(inv_temperature), L.ptr(masked_ids),
+                                       int(n_first_rows), float(scale), L.ptr(lse), L.ptr(logq), L.ptr(out), L.stream_ptr()), "sat_policy_nll_fwd")
+        ctx.save_for_backward(logits, targets_i32, row_weight, lse, masked_ids)
+        ctx.args = (float(inv_temperature), int(n_first_rows), float(scale))
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        lib = L.lib()
+        logits, targets, row_weight, lse, masked_ids = ctx.saved_tensors
+        inv_temperature, n_first_rows, scale = ctx.args
+        P, V = logits.shape
+        dlogits = torch.empty_like(logits)
+        g = gloss.reshape(1).to(torch.float32).contiguous()
+        L.check(lib.sat_policy_nll_bwd(L.ptr(logits), L.ptr(targets), L.ptr(row_weight), L.ptr(lse), P, V, inv_temperature, L.ptr(masked_ids),
+                                       n_first_rows, scale, L.ptr(g), L.ptr(dlogits), L.stream_ptr()), "sat_policy_nll_bwd")
+        return dlogits, None, None, None, None, None, None
+
+
 class DoublyStochasticFn(torch.autograd.Function):
     """model.py:594: gamma * ((1 - alphas.sum(dim=1)) ** 2).mean(), fixed-order reduction."""
 

@@ -62,10 +62,11 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     """``SAT.caption(..., return_all=False)`` with the result left on the device: ``(tokens (B, max_gen_length + 1) int32 padded with
     <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises.
     ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``); ``sample_topp`` belongs to
-    ``sample_method="nucleus"``."""
+    ``sample_method="nucleus"``; ``sample_method="ancestral"`` (``beamk=1``, no constraint, no graph) is pure sampling."""
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
     con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
+    constraints.check_ancestral(str(sample_method), beamk, graph, **con)
     constraints.resolve(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length, str(sample_method), **con)   # refuse before any launch
     model.eval()
     ann_bld, _ = model.encode(img)

@@ -64,6 +64,9 @@ def check_sample_topp(sample_method, sample_topp):
         raise ValueError("sample_topp %r outside (0, 1] (sample_method='nucleus')" % (sample_topp,))
 
 
+check_ancestral = constraints.check_ancestral
+
+
 def nucleus_candidates(scores, topp, with_margin=False):
     """The candidates of "nucleus" sampling ("Sampled decoding") for scores (k, V), in torch ops: per row the finite
     entries ordered by (-score, id) (a stable sort), their weights exp(s - max) summed cumulatively in float64, cut at the shortest
@@ -175,6 +178,8 @@ class SATDecoder(nn.Module):
         import ctypes as C
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
+        if sample_method == "ancestral":
+            raise ValueError("sample_method='ancestral' runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         multinomial = multinomial or torch.multinomial
         con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
                                   topg, prefix, banned, no_unk)
@@ -328,10 +333,13 @@ class SATDecoder(nn.Module):
         sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted).
         With a constraint (``topg`` / ``prefix`` / ``banned`` / ``no_unk``) the call is sat_beam_search_constrained and runs eagerly.
         ``graph=True`` replays the "beam" search without noise, and the "nucleus" search drawn by the device generator from a
-        given ``seed`` (the seed and ``sample_topp`` are arguments of the captured launches, so both are part of the cache key)."""
+        given ``seed`` (the seed and ``sample_topp`` are arguments of the captured launches, so both are part of the cache key).
+        ``sample_method="ancestral"`` (``beamk == 1``, no constraint, no graph: ``check_ancestral``) draws every word, the first included,
+        from the model's own distribution; ``gumbel`` is then (max_gen_length + 1, B, V)."""
         import ctypes as C
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
+        check_ancestral(sample_method, beamk, graph, topg, prefix, banned, no_unk)
         con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
                                   topg, prefix, banned, no_unk)
         lib = L.lib()
@@ -435,7 +443,9 @@ class SATDecoder(nn.Module):
         ``graph=True`` combined with any constraint runs eagerly, as sampling does.
         ``sample_method="nucleus"`` with ``sample_topp`` in (0, 1] (top-p sampling; DESIGN.md 5, "Sampled decoding"): "topk"'s draw with
         the candidates of a hypothesis being the fewest words that carry ``sample_topp`` of its probability mass.  Prefix, banned ids
-        and ``no_unk`` combine with it, ``topg`` does not; ``graph=True`` replays it when ``seed`` is given and no table is."""
+        and ``no_unk`` combine with it, ``topg`` does not; ``graph=True`` replays it when ``seed`` is given and no table is.
+        ``sample_method="ancestral"`` (``beamk=1`` only; DESIGN.md 5, "Self-critical training"): pure sampling, every word drawn from
+        softmax(logits / temperature) over the unmasked words, step 0 included; no constraint and no graph combine with it."""
         import numpy as np
         o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
                                      topg, prefix, banned, no_unk, sample_topp)
@@ -608,6 +618,9 @@ class SAT(SATDecoder, _Base):
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
         con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
+        check_ancestral(sample_method, beamk, bool(self.__dict__.get("beam_graph", False)), **con)
+        if sample_method == "ancestral" and max_gen_length < 1:
+            raise ValueError("sample_method='ancestral' runs in the batched search only (max_gen_length >= 1)")
         constraints.resolve(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
         with torch.no_grad():
             ann_bld, hw = self.encode(img)
@@ -717,6 +730,20 @@ class SAT(SATDecoder, _Base):
         loss = self._step_losses(batch, epsilon)
         self._step_end(gstep)
         return {"loss": loss, "accuracy": self.criterion.last_accuracy, "epsilon_tf": float(epsilon)}
+
+    def scst_step(self, batch, corpus, samples=5, baseline="mean", reward=(1.0, 0.0), max_gen_length=20, temperature=1.0, seed=None):
+        """Self-critical sequence training (Rennie et al. 2017; DESIGN.md 5, "Self-critical training"): the counterpart of
+        ``training_step`` for the second training stage, ``scst.step`` with this module's two host halves around it.  ``batch`` is
+        ``training_step``'s (img, references (B, R, T), lengths (B, R)); ``corpus`` a ``ReferenceCorpus`` holding the split's document
+        frequencies.  Returns ``{"loss", "reward", "baseline_reward", "advantage_abs", "sample_length"}`` (device scalars: the loss the
+        trainer back-propagates, and batch means) plus ``"samples"`` / ``"sample_lengths"`` / ``"rewards"`` / ``"advantages"``, the
+        device tensors they were taken from."""
+        from . import scst
+        scst.check_step_args(self, corpus, samples, baseline, reward, max_gen_length, temperature)        # refuse before any launch
+        _, gstep = self._step_begin()
+        out = scst.step(self, batch, corpus, samples, baseline, reward, max_gen_length, temperature, seed)
+        self._step_end(gstep)
+        return out
 
     # ------------------------------------------------------------------ validation (model.py:630-718)
     def _log_scalar(self, key, val, step):

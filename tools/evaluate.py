@@ -44,7 +44,7 @@ def main():
     ap.add_argument("--beamk", type=int, default=5)
     ap.add_argument("--max-gen-length", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0)
-    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk", "nucleus"])
+    ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial", "topk", "nucleus", "ancestral"])
     ap.add_argument("--sample-topk", type=int, default=3)
     ap.add_argument("--sample-topp", type=float, default=0.9, help="nucleus sampling: the share of the probability mass the candidates of a hypothesis carry, (0, 1]")
     ap.add_argument("--decoder-noise", type=float, default=0.0)
