@@ -341,8 +341,52 @@ int sat_beam_search_constrained(const sat_decoder_dims* d, const sat_decoder_par
                                 const sat_beam_constraints* constraints, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
                                 int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
                                 void* stream);
+/* The same search under rules that read what a hypothesis has already said ("History rules").  A live row of step s has
+ * the history w_1 .. w_s: the words fed at steps 1..s, without START, forced prefix words included.  With x the row's raw fp32 logits
+ * and T the step's temperature, in this order:
+ *   1. repetition_penalty theta (CTRL, Keskar et al. 2019): for every DISTINCT word v of the history, once however often it occurs,
+ *      x[v] = x[v] > 0 ? x[v] / theta : x[v] * theta; then log-softmax of x / T plus the parent score as in every search.  Every
+ *      step with a non-empty history, forced steps included (the forced word's penalised score joins the running sum).
+ *   2. the START / PAD (/ END / UNK) masks and the banned ids, unchanged.
+ *   3. min_length m: at a free step s < m, score[END] = -inf.  END taken at step s closes a caption of s words, so no finished caption
+ *      has fewer than m words; the cut at max_gen_length is unchanged.
+ *   4. no_repeat_ngram n: at a free step s >= n - 1, with u the last n - 1 words of the history (empty for n = 1), every p in 0 .. s - n
+ *      with hist[p : p + n - 1] == u sets score[hist[p + n - 1]] = -inf.  n = 1 blocks every word already used.
+ *   Rules 3 and 4 skip the forced steps (s < P_b): a prefix is obeyed even if it repeats, and its words count as history afterwards.
+ * Everything downstream (top-g candidates, multinomial / top-k / nucleus keys, the per-image top-k, the score gather, the update) reads
+ * these scores as it reads today's; SAT_SAMPLE_ANCESTRAL refuses the rules as it refuses every constraint.  A row loses at most one
+ * word per earlier position, so V - masked - banned - max_gen_length >= max(beamk, topg, 1) keeps enough words selectable (the caller's
+ * check; sat_amd/constraints.py makes it).  The history is a (B * beamk, max_gen_length + 1) int32 table in the workspace, double-buffered
+ * and advanced by one small launch per step; the search stays launches only but is not graph-replayed.
+ * history = NULL, or every rule off (no_repeat_ngram == 0 && min_length == 0 && repetition_penalty all-zero bits or 1.0f), enqueues
+ * exactly what sat_beam_search_constrained enqueues and needs only sat_beam_search_constrained_workspace_bytes; the query below adds
+ * the two history tables of a search with a rule on to that figure (and serves either).  SAT_EINVAL before any launch: a negative
+ * no_repeat_ngram or min_length, min_length > max_gen_length, repetition_penalty <= 0 or not finite, and with a rule on:
+ * max_gen_length + 1 > SAT_CAPTION_MAX_LEN, ancestral sampling, a stream that is being captured. */
+typedef struct sat_beam_history {
+    int32_t no_repeat_ngram;     /* 0 = off, else >= 1 */
+    int32_t min_length;          /* 0 = off, <= max_gen_length */
+    float   repetition_penalty;  /* all-zero bits or 1.0f = off; finite, > 0 */
+    int32_t reserved;
+} sat_beam_history;
+size_t sat_beam_search_history_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t topg, int32_t max_gen_length);
+int sat_beam_search_history(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                            const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                            const sat_beam_constraints* constraints, const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row,
+                            float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean,
+                            void* workspace, size_t workspace_bytes, void* stream);
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids /* device */,
                     int32_t n_masked, const float* parent_scores /* (beams) or NULL */, float* scores, void* stream);
+/* The score kernel of sat_beam_search_history on its own, every row at a free step: row r has said the first hist_len[r] words of
+ * hist (rows, hist_stride), hist_stride <= SAT_CAPTION_MAX_LEN (lengths are clamped to 0..hist_stride, ids outside [0, V) are skipped).
+ * Rules 1, 2 (masked_ids) and 4 as above with s = hist_len[r]; rule 3 masks end_id when step < rules->min_length.  logits is only read.
+ * With every rule off the output is sat_beam_scores' bit for bit.  No atomics: same input, same bits.  SAT_EINVAL before the launch:
+ * a null pointer, rows / V < 1, a temperature that is not positive, hist_stride outside 0..SAT_CAPTION_MAX_LEN, malformed rules (as
+ * above), a stream that is being captured. */
+int sat_beam_history_scores(const float* logits /* (rows, V) */, int32_t rows, int32_t V, float temperature, const int32_t* masked_ids,
+                            int32_t n_masked, const float* parent_scores /* (rows) or NULL */, const int32_t* hist /* (rows, hist_stride) */,
+                            const int32_t* hist_len /* (rows) */, int32_t hist_stride, const sat_beam_history* rules, int32_t step, int32_t end_id,
+                            float* scores, void* stream);
 int sat_topk(const float* x, float* work /* n floats scratch */, int64_t n, int32_t k, float* values, int32_t* indices, void* stream);
 /* The key kernel of SAT_SAMPLE_NUCLEUS on its own, every row live: keys (rows, V) as above with `step` the divisor (> 0) and
  * `stream` the hash stream (the search passes the step); gumbel (rows, V) or NULL; nucleus_size (rows) or NULL receives |N| per row

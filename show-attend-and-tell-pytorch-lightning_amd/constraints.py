@@ -3,7 +3,13 @@
 ``resolve`` turns the public keywords ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` into one checked ``SearchConstraints``
 (or ``None`` when nothing constrains the search) and raises every ``ValueError`` of the specification; it touches no GPU.
 The batched search (``SATDecoder._beam_search_device``) hands the result to ``sat_beam_search_constrained`` as device
-arrays, the per-image loop (``SATDecoder.beam_decode``) applies the same rules with torch ops."""
+arrays, the per-image loop (``SATDecoder.beam_decode``) applies the same rules with torch ops.
+
+``resolve_history`` does the same for the rules that read what a hypothesis has already said ("History rules"):
+``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` become one checked ``HistoryRules`` (or ``None``), handed to
+``sat_beam_search_history`` as a ``sat_beam_history``; ``resolve_all`` runs both."""
+import math
+
 import torch
 
 from . import _lib as L
@@ -35,7 +41,23 @@ class SearchConstraints:
         return con, keep
 
 
-def check_ancestral(sample_method, beamk, graph=False, topg=None, prefix=None, banned=None, no_unk=False):
+class HistoryRules:
+    """no_repeat_ngram: 0 = off; min_length: 0 = off; repetition_penalty: 1.0 = off"""
+
+    def __init__(self, no_repeat_ngram, min_length, repetition_penalty):
+        self.no_repeat_ngram, self.min_length, self.repetition_penalty = int(no_repeat_ngram), int(min_length), float(repetition_penalty)
+
+    def device_struct(self):
+        """sat_beam_history"""
+        return L.BeamHistory(no_repeat_ngram=self.no_repeat_ngram, min_length=self.min_length, repetition_penalty=self.repetition_penalty)
+
+
+#: sat_beam_search_history keeps a row's history in a table of SAT_CAPTION_MAX_LEN words (include/sat_hip.h)
+HISTORY_MAX_LEN = 128
+
+
+def check_ancestral(sample_method, beamk, graph=False, topg=None, prefix=None, banned=None, no_unk=False, no_repeat_ngram=None, min_length=None,
+                    repetition_penalty=None):
     """``ValueError`` for a call that ``sample_method="ancestral"`` is not defined for (include/sat_hip.h, SAT_SAMPLE_ANCESTRAL): it draws one
     hypothesis per row (``beamk == 1``; independent samples of an image are rows of a larger batch), takes no constraint and is not
     replayed from a graph.  Touches no GPU."""
@@ -45,6 +67,8 @@ def check_ancestral(sample_method, beamk, graph=False, topg=None, prefix=None, b
         raise ValueError("sample_method='ancestral' is defined for beamk=1 only (beamk=%d): repeat the images to draw several samples" % int(beamk))
     if topg is not None or prefix is not None or no_unk or (banned is not None and len(banned) > 0):
         raise ValueError("sample_method='ancestral' does not combine with topg / prefix / banned / no_unk")
+    if no_repeat_ngram is not None or min_length is not None or repetition_penalty is not None:
+        raise ValueError("sample_method='ancestral' does not combine with no_repeat_ngram / min_length / repetition_penalty")
     if graph:
         raise ValueError("sample_method='ancestral' is not replayed from a graph (graph=True)")
 
@@ -109,3 +133,40 @@ def resolve(stoi, V, B, beamk, max_gen_length, sample_method="beam", topg=None, 
     con = SearchConstraints(g, [list(p) for p in pre], sorted(ban))
     return con if (con.topg or con.max_prefix or con.banned) else None
 
+
+
+def resolve_history(V, beamk, max_gen_length, sample_method, topg, n_banned, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+    """The checked history rules of one search, or ``None`` when every rule is off (``None``, ``no_repeat_ngram=0``, ``min_length=0``,
+    ``repetition_penalty=1.0``).  ``n_banned``: the banned ids that are none of the four specials.  A row loses at most one word per
+    earlier position to the n-gram rule, so ``V - 4 - n_banned - max_gen_length`` selectable words must cover ``max(beamk, topg or 1)``.
+    Touches no GPU."""
+    n = 0 if no_repeat_ngram is None else int(no_repeat_ngram)
+    m = 0 if min_length is None else int(min_length)
+    theta = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    S = int(max_gen_length)
+    if n < 0:
+        raise ValueError("no_repeat_ngram=%d is negative (0 = off)" % n)
+    if not 0 <= m <= S:
+        raise ValueError("min_length=%d outside 0..max_gen_length=%d" % (m, S))
+    if not (math.isfinite(theta) and theta > 0.0):
+        raise ValueError("repetition_penalty=%r is not a positive finite number (1.0 = off)" % (repetition_penalty,))
+    if n == 0 and m == 0 and theta == 1.0:
+        return None
+    if sample_method == "ancestral":
+        raise ValueError("sample_method='ancestral' does not combine with no_repeat_ngram / min_length / repetition_penalty")
+    if S + 1 > HISTORY_MAX_LEN:
+        raise ValueError("the history rules need max_gen_length + 1 <= %d (max_gen_length=%d)" % (HISTORY_MAX_LEN, S))
+    need = max(int(beamk), int(topg or 0) or 1)
+    left = int(V) - len(SPECIALS) - int(n_banned) - S
+    if left < need:
+        raise ValueError("%d unmasked ids left after max_gen_length=%d blocked words, the search needs max(beamk, topg) = %d" % (left, S, need))
+    return HistoryRules(n, m, theta)
+
+
+def resolve_all(stoi, V, B, beamk, max_gen_length, sample_method="beam", topg=None, prefix=None, banned=None, no_unk=False, no_repeat_ngram=None,
+                min_length=None, repetition_penalty=None):
+    """``(resolve(...), resolve_history(...))``: every ``ValueError`` of both, before any launch"""
+    con = resolve(stoi, V, B, beamk, max_gen_length, sample_method, topg, prefix, banned, no_unk)
+    special = {int(stoi[s]) for s in SPECIALS}
+    n_banned = len([t for t in con.banned if t not in special]) if con is not None else 0
+    return con, resolve_history(V, beamk, max_gen_length, sample_method, topg, n_banned, no_repeat_ngram, min_length, repetition_penalty)

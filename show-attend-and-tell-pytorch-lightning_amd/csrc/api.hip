@@ -206,6 +206,40 @@ int sat_beam_search_constrained(const sat_decoder_dims* d, const sat_decoder_par
     return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints);
 }
+size_t sat_beam_search_history_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t topg, int32_t max_gen_length) {
+    if (check_dims(d) != SAT_OK || beamk < 1) return 0;
+    if (topg < 0 || topg > d->V) { fail(SAT_EINVAL, "beam_search_history_workspace_bytes: topg %d outside 0..V=%d", topg, d->V); return 0; }
+    if (max_gen_length < 0 || max_gen_length + 1 > SAT_CAPTION_MAX_LEN) {
+        fail(SAT_EINVAL, "beam_search_history_workspace_bytes: max_gen_length %d outside 0..%d", max_gen_length, SAT_CAPTION_MAX_LEN - 1);
+        return 0;
+    }
+    return decoder_beam_workspace_bytes(*d, beamk, topg, max_gen_length + 1);
+}
+int sat_beam_search_history(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                            const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                            const sat_beam_constraints* constraints, const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row, float* alpha_hist,
+                            int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_history"));
+    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
+        return fail(SAT_EINVAL, "beam_search_history: null pointer");
+    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_history: temperature %g", temperatures_host[i]);
+    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
+                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history);
+}
+int sat_beam_history_scores(const float* logits, int32_t rows, int32_t V, float temperature, const int32_t* masked_ids, int32_t n_masked,
+                            const float* parent_scores, const int32_t* hist, const int32_t* hist_len, int32_t hist_stride, const sat_beam_history* rules,
+                            int32_t step, int32_t end_id, float* scores, void* stream) {
+    if (rows < 1 || V < 1) return fail(SAT_EINVAL, "beam_history_scores: non-positive size (rows=%d V=%d)", rows, V);
+    if (!(temperature > 0.f)) return fail(SAT_EINVAL, "beam_history_scores: temperature %g", (double)temperature);
+    if (hist_stride < 0 || hist_stride > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "beam_history_scores: hist_stride %d outside 0..%d", hist_stride, SAT_CAPTION_MAX_LEN);
+    if (!logits || !scores || !rules || !hist_len || (hist_stride > 0 && !hist) || (n_masked > 0 && !masked_ids))
+        return fail(SAT_EINVAL, "beam_history_scores: null pointer");
+    SAT_TRY(beam_history_check(rules, -1, "beam_history_scores"));
+    return beam_history_scores(logits, rows, V, temperature, masked_ids, n_masked < 0 ? 0 : n_masked, parent_scores, hist, hist_len, hist_stride, *rules, step,
+                               end_id, scores, (hipStream_t)stream);
+}
 int sat_beam_select(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
                     const float* fin_score, const float* fin_mean, const float* alpha_hist, int32_t B, int32_t beamk, int32_t max_gen_length, int32_t L,
                     int32_t rescore_method, float rescore_reward, int32_t pad_id, int32_t* cap_tokens, int32_t* cap_len, float* cap_score, float* cap_raw,

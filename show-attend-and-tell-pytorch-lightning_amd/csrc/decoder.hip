@@ -789,8 +789,9 @@ struct BeamWs {
     size_t total; float *U, *Wcat, *bcat, *mean, *f, *init_img, *hc, *Z, *XZ, *Y, *u, *gu, *bup, *h, *c, *h2, *c2, *logits, *scores, *work, *keys, *noise, *vals, *top, *sc;
     int *live, *klive, *inds, *gmap, *mask_first, *mask_rest;
     float* cand_val; int* cand_idx;        // top-g clipping only: (B*K, topg) candidates, after everything the plain search uses
+    int *hist_a, *hist_b;                  // history rules only: (B*K, hist_stride) words every row has said, double-buffered, after the candidates
 };
-static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg = 0) {
+static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg = 0, int hist_stride = 0) {
     BeamWs w; size_t off = 0;
     const long HCW = d.A + d.D + 4L * d.n, N = (long)d.B * K;
     auto take = [&](size_t elems) { size_t o = off; off += (elems * 4 + 255) & ~(size_t)255; return base ? base + o : (char*)nullptr; };
@@ -806,10 +807,32 @@ static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg
     w.live = (int*)take(N); w.klive = (int*)take(d.B); w.inds = (int*)take(N); w.gmap = (int*)take(N); w.mask_first = (int*)take(4); w.mask_rest = (int*)take(4);
     w.cand_val = nullptr; w.cand_idx = nullptr;
     if (topg > 0) { w.cand_val = (float*)take((size_t)N * topg); w.cand_idx = (int*)take((size_t)N * topg); }
+    w.hist_a = nullptr; w.hist_b = nullptr;
+    if (hist_stride > 0) { w.hist_a = (int*)take((size_t)N * hist_stride); w.hist_b = (int*)take((size_t)N * hist_stride); }
     w.total = off;
     return w;
 }
-size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg) { return beam_layout(d, K, nullptr, topg).total; }
+size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg, int hist_stride) { return beam_layout(d, K, nullptr, topg, hist_stride).total; }
+
+// sat_beam_history: which rules are on, and are they well-formed (include/sat_hip.h)
+bool beam_history_on(const sat_beam_history* h) {
+    return h && (h->no_repeat_ngram != 0 || h->min_length != 0 || (h->repetition_penalty != 0.f && h->repetition_penalty != 1.0f));
+}
+int beam_history_check(const sat_beam_history* h, int max_gen_length, const char* what) {
+    if (!h) return SAT_OK;
+    SAT_REQUIRE(h->no_repeat_ngram >= 0, "%s: no_repeat_ngram %d is negative (0 = off)", what, h->no_repeat_ngram);
+    SAT_REQUIRE(h->min_length >= 0 && (max_gen_length < 0 || h->min_length <= max_gen_length), "%s: min_length %d outside 0..max_gen_length=%d", what,
+                h->min_length, max_gen_length);
+    const float t = h->repetition_penalty;
+    SAT_REQUIRE(t == 0.f ? !__builtin_signbit(t) : (t > 0.f && t < INFINITY), "%s: repetition_penalty %g is not a positive finite number (1 = off)", what, (double)t);
+    return SAT_OK;
+}
+static int not_capturing(hipStream_t st, const char* what) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    SAT_REQUIRE(cap == hipStreamCaptureStatusNone, "%s: not replayed from a graph (the stream is being captured)", what);
+    return SAT_OK;
+}
 
 // the keys of one free step of the "nucleus" search: method 1's table layout and hash indexing, (step, row, word)
 static int launch_nucleus_keys(hipStream_t st, const float* scores, const int* klive, int N, int K, int V, const sat_beam_sampling& smp, int step, float* keys) {
@@ -821,10 +844,22 @@ static int launch_nucleus_keys(hipStream_t st, const float* scores, const int* k
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
                          int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
-                         const sat_beam_constraints* con) {
+                         const sat_beam_constraints* con, const sat_beam_history* hist) {
     // no constraint at all: exactly the launches of the plain / sampled search
     if (con && con->topg == 0 && con->max_prefix == 0 && con->n_banned == 0) con = nullptr;
     const int method = smp ? smp->method : 0;
+    SAT_TRY(beam_history_check(hist, max_gen_length, "beam_history"));
+    const bool hist_on = beam_history_on(hist);
+    const sat_beam_constraints no_constraint = {};
+    if (hist_on) {                                         // the history rules run in the constrained search's per-image selection
+        SAT_REQUIRE(max_gen_length + 1 <= SAT_BEAM_HIST_MAX, "beam_history: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length,
+                    SAT_BEAM_HIST_MAX);
+        SAT_REQUIRE(method != SAT_SAMPLE_ANCESTRAL, "beam_history: ancestral sampling does not combine with the history rules");
+        SAT_TRY(not_capturing(st, "beam_history"));
+        if (!con) con = &no_constraint;
+    }
+    const int hist_stride = hist_on ? max_gen_length + 1 : 0;
+    const float theta = hist_on && hist->repetition_penalty != 0.f ? hist->repetition_penalty : 1.0f;
     if (con) {
         SAT_REQUIRE(K <= 1024, "beam_constrained: beamk %d above 1024 (one thread per row in the forced steps)", K);
         SAT_REQUIRE(con->topg >= 0 && con->topg <= d.V, "beam_constrained: topg %d outside 1..V=%d (0 = off)", con->topg, d.V);
@@ -837,7 +872,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     }
     const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
     const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
-    BeamWs w = beam_layout(d, K, ws, topg);
+    BeamWs w = beam_layout(d, K, ws, topg, hist_stride);
     SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_ANCESTRAL && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
                 "beam_batched: sampling method %d, sample_topk %d", method, smp ? smp->sample_topk : 0);
     if (method == SAT_SAMPLE_ANCESTRAL) {
@@ -890,9 +925,11 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     zero_w(w.c2, (long)NL * N * n);
     zero_w(w.top, N);
     zero_w(fin_count, B);
+    if (hist_on) { zero_w(w.hist_a, (long)N * hist_stride); zero_w(w.hist_b, (long)N * hist_stride); }
     SAT_TRY(launch_ok("beam: clears"));
 
     float *h = w.h, *c = w.c, *h2 = w.h2, *c2 = w.c2;
+    int *hcur = w.hist_a, *hnext = w.hist_b;
     for (int step = 0; step <= max_gen_length; ++step) {
         const int* tok = tok_in + (long)step * N;
         float* alpha = alpha_hist + (long)step * N * d.L;
@@ -936,9 +973,16 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         // ---- model.py:330-359: log-softmax, special-token masks, parent scores, top-k per image
         const float T = temps_host[step % n_temps];
         if (con) {                                     // per image: forced word (step < P_b), row 0 (step == P_b), the free search after it
-            hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, w.logits, K, V, 1.0f / T, w.mask_first, w.mask_rest, step, prefix_len,
-                               max_prefix, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, w.scores);
-            SAT_TRY(launch_ok("beam_scores (constrained)"));
+            if (hist_on) {
+                hipLaunchKernelGGL(beam_history_scores_kernel, dim3(N), dim3(256), 0, st, w.logits, K, V, 1.0f / T, w.mask_first, 4, w.mask_rest, 2, step, prefix_len,
+                                   max_prefix, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, hcur, (const int*)nullptr, hist_stride,
+                                   hist->no_repeat_ngram, hist->min_length, theta, END, w.scores);
+                SAT_TRY(launch_ok("beam_scores (history)"));
+            } else {
+                hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, w.logits, K, V, 1.0f / T, w.mask_first, w.mask_rest, step, prefix_len,
+                                   max_prefix, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, w.scores);
+                SAT_TRY(launch_ok("beam_scores (constrained)"));
+            }
             const bool drawn = method != 0 && step > 0;
             if (topg > 0 && step > 0) {
                 hipLaunchKernelGGL(beam_row_topg_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, topg, step, prefix_len, max_prefix, w.cand_val, w.cand_idx);
@@ -994,6 +1038,12 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, B, K, V, step, max_gen_length, END, prefix_len, max_prefix,
                            tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, fin_count, fin_step, fin_row, fin_score, fin_mean);
         SAT_TRY(launch_ok("beam_update"));
+        if (hist_on && step < max_gen_length) {
+            hipLaunchKernelGGL(beam_history_advance_kernel, dim3(cdiv((long)N * (step + 1), 256)), dim3(256), 0, st, hcur, hnext, tok_in + (long)(step + 1) * N,
+                               prev_row + (long)(step + 1) * N, w.klive, B, K, hist_stride, step);
+            SAT_TRY(launch_ok("beam_history_advance"));
+            int* t0 = hcur; hcur = hnext; hnext = t0;
+        }
         if (step < max_gen_length) {
             const long tot = (long)NL * N * n;
             hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, h, h2, w.gmap, w.klive, B, K, n, NL);
@@ -1010,6 +1060,15 @@ int beam_scores(const float* logits, int K, int V, float temperature, const int*
     SAT_REQUIRE(K > 0 && V > 0 && temperature > 0.f, "beam_scores: bad arguments");
     hipLaunchKernelGGL(beam_scores_kernel, dim3(K), dim3(256), 0, st, logits, V, 1.0f / temperature, masked, n_masked, parent, scores);
     return launch_ok("beam_scores");
+}
+int beam_history_scores(const float* logits, int rows, int V, float temperature, const int* masked, int n_masked, const float* parent, const int* hist,
+                        const int* hist_len, int hist_stride, const sat_beam_history& rules, int step, int end_id, float* scores, hipStream_t st) {
+    SAT_TRY(not_capturing(st, "beam_history_scores"));
+    const float theta = rules.repetition_penalty != 0.f ? rules.repetition_penalty : 1.0f;
+    hipLaunchKernelGGL(beam_history_scores_kernel, dim3(rows), dim3(256), 0, st, logits, 1, V, 1.0f / temperature, masked, n_masked, masked, n_masked, step,
+                       (const int*)nullptr, 0, (const int*)nullptr, 0, parent, hist, hist_len, hist_stride, rules.no_repeat_ngram, rules.min_length, theta, end_id,
+                       scores);
+    return launch_ok("beam_history_scores");
 }
 int nucleus_keys(const float* scores, int rows, int V, float topp, float step, unsigned long long seed, unsigned long long stream, const float* gumbel,
                  float* keys, int* nucleus_size, hipStream_t st) {

@@ -1198,7 +1198,9 @@ __global__ void scatter_rows_kernel(const float* __restrict__ src, const int* __
 // ------------------------------------------------------------------ inference (beam search, model.py:329-343, 351-359)
 // scores[r, v] = log_softmax(logits[r, :] / T)[v] (+ parent[r]); masked token ids become -inf.  One block per beam row.
 // The row's arithmetic (shared by the constrained kernel below, so that a word has the same float in both searches).
-__device__ __forceinline__ void beam_scores_row(const float* __restrict__ x, int V, float inv_temp, float add, float* __restrict__ o, int tid) {
+// x and o may be the same row (beam_history_scores_kernel normalises its penalised copy in place): every element is read in the
+// first pass, and the last pass reads and writes element v from the same thread.
+__device__ __forceinline__ void beam_scores_row(const float* x, int V, float inv_temp, float add, float* o, int tid) {
     __shared__ float s_m[4], s_s[4];
     float mx = -INFINITY, sum = 0.f;
     for (int v = tid; v < V; v += 256) {
@@ -1723,6 +1725,76 @@ __global__ void beam_gather_state_kernel(const float* __restrict__ src, float* _
     const long l = e / (N * n); const long rem = e - l * N * n; const long i = rem / n; const int col = (int)(rem - i * n);
     const int b = (int)(i / K), j = (int)(i - (long)b * K);
     if (j < klive[b]) dst[e] = src[(l * N + (long)b * K + gmap[i]) * n + col];
+}
+
+// ---- history rules: repetition penalty, minimum length, no-repeat n-gram ("History rules").
+// A live row of step s has said w_1 .. w_s (the words fed at steps 1..s, prefix words included); the search keeps them as a
+// materialised (B * K, stride) table, double-buffered, so that the score kernel reads one short row instead of walking prev_row.
+#define SAT_BEAM_HIST_MAX SAT_CAPTION_MAX_LEN
+// beam_scores_constrained_kernel for rows with a history.  In order: the penalty on the raw logits of the distinct history words
+// (x > 0 ? x / theta : x * theta, a copy in the row's own output so that logits stay untouched), beam_scores_row's arithmetic,
+// today's masks and banned ids, END below min_length, the words that would complete an n-gram the row already holds.  Rules 3
+// and 4 wait for the image's first free step.  hist_len == NULL: every row holds `step` words (the search).  No atomics; every
+// id and length read from memory is clamped or skipped before it addresses anything; the same input gives the same bits.
+__global__ __launch_bounds__(256) void beam_history_scores_kernel(const float* __restrict__ logits, int K, int V, float inv_temp,
+                                                                  const int* __restrict__ mask_first, int n_first, const int* __restrict__ mask_rest,
+                                                                  int n_rest, int step, const int* __restrict__ prefix_len, int max_prefix,
+                                                                  const int* __restrict__ banned, int n_banned, const float* __restrict__ parent,
+                                                                  const int* __restrict__ hist, const int* __restrict__ hist_len, int hist_stride,
+                                                                  int ngram, int min_length, float theta, int end_id, float* __restrict__ scores) {
+    __shared__ int s_hist[SAT_BEAM_HIST_MAX];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int cap = hist_stride < SAT_BEAM_HIST_MAX ? hist_stride : SAT_BEAM_HIST_MAX;
+    int len = hist_len ? hist_len[r] : step;
+    len = len < 0 ? 0 : (len > cap ? cap : len);
+    if (tid < len) s_hist[tid] = hist[(long)r * hist_stride + tid];
+    __syncthreads();
+    const float* x = logits + (long)r * V;
+    float* o = scores + (long)r * V;
+    const float add = parent ? parent[r] : 0.f;
+    if (theta != 1.0f && len > 0) {
+        for (int v = tid; v < V; v += 256) o[v] = x[v];
+        __syncthreads();
+        if (tid < len) {                                   // one thread per position; the first occurrence of a word applies the penalty, once
+            const int w = s_hist[tid];
+            bool first = w >= 0 && w < V;
+            for (int q = 0; q < tid && first; ++q) first = s_hist[q] != w;
+            if (first) { const float xv = x[w]; o[w] = xv > 0.f ? xv / theta : xv * theta; }
+        }
+        __syncthreads();
+        beam_scores_row(o, V, inv_temp, add, o, tid);
+    } else {
+        beam_scores_row(x, V, inv_temp, add, o, tid);
+    }
+    const int P = beam_prefix_len(prefix_len, r / K, max_prefix);
+    const bool first_step = step == 0 && P == 0;
+    const int* masked = first_step ? mask_first : mask_rest; const int n_masked = first_step ? n_first : n_rest;
+    for (int k = tid; k < n_masked; k += 256) { int id = masked[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
+    for (int k = tid; k < n_banned; k += 256) { int id = banned[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
+    if (step < P) return;                                  // a forced word is obeyed even if it repeats or ends too early
+    if (tid == 0 && step < min_length && end_id >= 0 && end_id < V) o[end_id] = -INFINITY;
+    // thread p: does hist[p : p + n - 1] equal the last n - 1 words?  Then hist[p + n - 1] would repeat that n-gram.
+    if (ngram >= 1 && len >= ngram - 1 && tid <= len - ngram) {
+        const int u = len - (ngram - 1);
+        bool eq = true;
+        for (int i = 0; i < ngram - 1 && eq; ++i) eq = s_hist[tid + i] == s_hist[u + i];
+        const int w = s_hist[tid + ngram - 1];
+        if (eq && w >= 0 && w < V) o[w] = -INFINITY;
+    }
+}
+// next[i, :step] = cur[parent(i), :step]; next[i, step] = the word row i was just given.  After beam_update_kernel of `step`, for
+// the rows that stay live; one thread per (row, position).
+__global__ void beam_history_advance_kernel(const int* __restrict__ cur, int* __restrict__ next, const int* __restrict__ tok_next,
+                                            const int* __restrict__ prev_next, const int* __restrict__ klive, int B, int K, int stride, int step) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (step < 0 || step >= stride || e >= (long)B * K * (step + 1)) return;
+    const int i = (int)(e / (step + 1)), p = (int)(e - (long)i * (step + 1));
+    const int b = i / K, j = i - b * K;
+    if (j >= klive[b]) return;
+    if (p == step) { next[(long)i * stride + p] = tok_next[i]; return; }
+    int parent = prev_next[i];
+    parent = parent < 0 ? 0 : (parent >= K ? K - 1 : parent);
+    next[(long)i * stride + p] = cur[((long)b * K + parent) * stride + p];
 }
 
 }  // namespace sat

@@ -163,7 +163,7 @@ class SATDecoder(nn.Module):
     @torch.no_grad()
     def beam_decode(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
                     decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, multinomial=None, randn=None,
-                    topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, nucleus_log=None):
+                    topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, nucleus_log=None, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """SAT.forward's per-image beam search (model.py:260-472) on annotations (B, L, D).  The decode step,
         log-softmax / masking and top-k run in the library; the beam bookkeeping (which hypotheses to keep, finished
         lists, rescoring) stays on the host like in the reference.  ``sample_method`` "multinomial" / "topk"
@@ -174,15 +174,17 @@ class SATDecoder(nn.Module):
         ``beam_decode_batched`` with torch ops on the scores this loop already holds.
         ``sample_method="nucleus"`` with ``sample_topp``: "topk"'s draw over the top-p set of every row (``nucleus_candidates``).
         ``nucleus_log``: a list that receives, per free step, ``dict(image, step, cand, margins)`` before the draw (tests gather their
-        Gumbel variates by ``cand`` and read how close every cut came to ``sample_topp``)."""
+        Gumbel variates by ``cand`` and read how close every cut came to ``sample_topp``).
+        ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``: the history rules ("History rules") with torch ops
+        on ``top_preds`` and the logits; the implementation ``beam_decode_batched``'s kernels are tested against."""
         import ctypes as C
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
         if sample_method == "ancestral":
             raise ValueError("sample_method='ancestral' runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         multinomial = multinomial or torch.multinomial
-        con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
-                                  topg, prefix, banned, no_unk)
+        con, hist = constraints.resolve_all(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
+                                            topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
         lib = L.lib()
         L.require_gpu(ann_bld)
         hp = self.hp
@@ -210,6 +212,8 @@ class SATDecoder(nn.Module):
         st = L.stream_ptr
         ban_t = torch.tensor(con.banned, dtype=torch.int64, device=dev) if con is not None and con.banned else None
         g = con.topg if con is not None else 0
+        ngram, min_len = (hist.no_repeat_ngram, hist.min_length) if hist is not None else (0, 0)
+        theta = torch.tensor(hist.repetition_penalty, dtype=torch.float32, device=dev) if hist is not None and hist.repetition_penalty != 1.0 else None
         for idx in range(B):
             k = beamk
             forced = con.prefix[idx] if con is not None else []       # this image's forced words; the first free step is len(forced)
@@ -241,6 +245,10 @@ class SATDecoder(nn.Module):
                     noise = (randn((NL, k, n)).to(device=dev, dtype=torch.float32) * (decoder_noise / (step + 1))).contiguous()
                 L.check(lib.sat_decoder_infer_step(C.byref(dims), C.byref(w), L.ptr(ann), L.ptr(tok), k, beamk, L.ptr(h), L.ptr(c), L.ptr(logits),
                                                    L.ptr(alpha), L.ptr(noise), L.ptr(ws), ws_bytes, st()), "sat_decoder_infer_step")
+                said = top_preds[1:step + 1].t()            # (k, step): what every row has said, prefix words included
+                if theta is not None and step > 0:          # every distinct word of the history, once: x > 0 ? x / theta : x * theta
+                    seen = torch.zeros(k, V, dtype=torch.bool, device=dev).scatter_(1, said, True)
+                    logits = torch.where(seen, torch.where(logits > 0, logits / theta, logits * theta), logits).contiguous()
                 scores = torch.empty(k, V, **f32)
                 vals = torch.empty(k, **f32); inds = torch.empty(k, dtype=torch.int32, device=dev)
                 if step == 0 and not forced:
@@ -250,6 +258,16 @@ class SATDecoder(nn.Module):
                                                 st()), "sat_beam_scores")
                 if ban_t is not None:
                     scores[:, ban_t] = float("-inf")
+                if step >= len(forced):                 # the free steps: END waits for min_length, no n-gram is said twice
+                    if step < min_len:
+                        scores[:, END] = float("-inf")
+                    if ngram == 1 and step > 0:
+                        scores.scatter_(1, said, float("-inf"))
+                    elif ngram > 1 and step >= ngram:
+                        grams = said.unfold(1, ngram, 1)    # (k, step - n + 1, n): every n-gram of the history
+                        hit = (grams[:, :, :ngram - 1] == said[:, step - ngram + 1:].unsqueeze(1)).all(-1)
+                        rows, pos = hit.nonzero(as_tuple=True)
+                        scores[rows, grams[rows, pos, ngram - 1]] = float("-inf")
                 if step <= len(forced):                 # every row is its own parent up to the image's first free step
                     if step < len(forced):              # forced word: its own score joins the running sum
                         top_scores = scores[:, forced[step]].contiguous()
@@ -327,7 +345,7 @@ class SATDecoder(nn.Module):
         return captions, cap_scores, cap_alphas, cap_ppl
 
     def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """The device half of ``beam_decode_batched``: enqueue the whole search for annotations (B, L, D) (eagerly, or as the replay of
         its cached hipGraph) and return the buffers it leaves on the device (tok_in, prev_row, alpha_hist, fin_*: include/sat_hip.h,
         sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted).
@@ -335,13 +353,14 @@ class SATDecoder(nn.Module):
         ``graph=True`` replays the "beam" search without noise, and the "nucleus" search drawn by the device generator from a
         given ``seed`` (the seed and ``sample_topp`` are arguments of the captured launches, so both are part of the cache key).
         ``sample_method="ancestral"`` (``beamk == 1``, no constraint, no graph: ``check_ancestral``) draws every word, the first included,
-        from the model's own distribution; ``gumbel`` is then (max_gen_length + 1, B, V)."""
+        from the model's own distribution; ``gumbel`` is then (max_gen_length + 1, B, V).
+        With a history rule on (``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``) the call is sat_beam_search_history, eager too."""
         import ctypes as C
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
-        check_ancestral(sample_method, beamk, graph, topg, prefix, banned, no_unk)
-        con = constraints.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
-                                  topg, prefix, banned, no_unk)
+        check_ancestral(sample_method, beamk, graph, topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
+        con, hist = constraints.resolve_all(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
+                                            topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
         lib = L.lib()
         L.require_gpu(ann_bld)
         hp = self.hp
@@ -364,6 +383,10 @@ class SATDecoder(nn.Module):
         if con is not None:
             cst, _keep_con = con.device_struct(dev)
             ws_bytes = lib.sat_beam_search_constrained_workspace_bytes(C.byref(dims), K, con.topg)
+        hst = None
+        if hist is not None:
+            hst = hist.device_struct()
+            ws_bytes = lib.sat_beam_search_history_workspace_bytes(C.byref(dims), K, con.topg if con is not None else 0, S)
         smp = None
         seeded = seed is not None
         if sample_method != "beam" or decoder_noise:
@@ -385,6 +408,13 @@ class SATDecoder(nn.Module):
                         fin_mean=torch.empty(B, K, **f32))
 
         def enqueue(ann, o):
+            if hst is not None:
+                L.check(lib.sat_beam_search_history(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
+                                                    C.byref(cst) if cst is not None else None, C.byref(hst), L.ptr(o["tok_in"]), L.ptr(o["prev_row"]),
+                                                    L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]), L.ptr(o["fin_row"]),
+                                                    L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]), ws_bytes, L.stream_ptr()),
+                        "sat_beam_search_history")
+                return
             if cst is not None:
                 L.check(lib.sat_beam_search_constrained(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
                                                         C.byref(cst), L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]),
@@ -397,7 +427,7 @@ class SATDecoder(nn.Module):
                     "sat_beam_search_sampled")
 
         replayable = smp is None or (sample_method == "nucleus" and seeded and gumbel is None and normals is None)
-        if graph and replayable and cst is None:
+        if graph and replayable and cst is None and hst is None:
             cache = self.__dict__.setdefault("_beam_graphs", {})
             key = (B, Lc, D, K, S, tuple(float(t) for t in temps), int(dims.precision), str(dev), tuple(t.data_ptr() for t in _keep.values() if torch.is_tensor(t)))
             if smp is not None:
@@ -425,7 +455,7 @@ class SATDecoder(nn.Module):
     @torch.no_grad()
     def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
                             return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False,
-                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
         (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
         completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
@@ -445,10 +475,14 @@ class SATDecoder(nn.Module):
         the candidates of a hypothesis being the fewest words that carry ``sample_topp`` of its probability mass.  Prefix, banned ids
         and ``no_unk`` combine with it, ``topg`` does not; ``graph=True`` replays it when ``seed`` is given and no table is.
         ``sample_method="ancestral"`` (``beamk=1`` only; DESIGN.md 5, "Self-critical training"): pure sampling, every word drawn from
-        softmax(logits / temperature) over the unmasked words, step 0 included; no constraint and no graph combine with it."""
+        softmax(logits / temperature) over the unmasked words, step 0 included; no constraint and no graph combine with it.
+        History rules ("History rules"), in the same call and with every method but "ancestral": ``repetition_penalty``
+        theta (CTRL) divides the positive and multiplies the negative raw logits of the words a hypothesis has already said,
+        ``min_length`` keeps <END> masked until a caption has that many words, ``no_repeat_ngram=n`` masks every word that would say an
+        n-gram of the hypothesis a second time.  Forced prefix words count as history but are obeyed.  Eager, like the constraints."""
         import numpy as np
         o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                                     topg, prefix, banned, no_unk, sample_topp)
+                                     topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length, repetition_penalty)
         B = ann_bld.shape[0]
         Hh, Ww = hw
         K, S = int(beamk), int(max_gen_length)
@@ -606,22 +640,25 @@ class SAT(SATDecoder, _Base):
     @torch.no_grad()
     def caption(self, img_tensor, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
                 decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False,
-                sample_topp=0.9):
-        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` / ``sample_topp``: ``beam_decode_batched``."""
+                sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` / ``sample_topp`` and the history
+        rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``: ``beam_decode_batched``."""
         self.eval()
         return self.forward(img_tensor, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                            rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk, sample_topp)
+                            rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
+                            repetition_penalty)
 
     def forward(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """Inference only (model.py:237-472): encode the batch once, then beam-search every image."""
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
-        con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
+        con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
+                   repetition_penalty=repetition_penalty)
         check_ancestral(sample_method, beamk, bool(self.__dict__.get("beam_graph", False)), **con)
         if sample_method == "ancestral" and max_gen_length < 1:
             raise ValueError("sample_method='ancestral' runs in the batched search only (max_gen_length >= 1)")
-        constraints.resolve(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
+        constraints.resolve_all(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
         with torch.no_grad():
             ann_bld, hw = self.encode(img)
             if max_gen_length >= 1:        # every image at once; sampled continuations and decoder noise draw from the device generator
@@ -795,49 +832,53 @@ class SAT(SATDecoder, _Base):
         return out
 
     def val_batch(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
-                  rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                  rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """model.py:684-691"""
         img, encoded_captions, lengths = batch
         captions, scores, alphas, perplexities = self.caption(img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                                                               rescore_method, rescore_reward, return_all=False, topg=topg, prefix=prefix, banned=banned,
-                                                              no_unk=no_unk, sample_topp=sample_topp)
+                                                              no_unk=no_unk, sample_topp=sample_topp, no_repeat_ngram=no_repeat_ngram,
+                                                              min_length=min_length, repetition_penalty=repetition_penalty)
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
 
     def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
         from . import evaluation
         return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                         rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp)
+                                         rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
+                                         repetition_penalty)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                         rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
-                        sample_topp=0.9, chrf=None, chrf_beta=3.0):
+                        sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
         (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L; with ``chrf``, an ``evaluation.VocabChars``, also chrF)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp, chrf, chrf_beta)
+                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp, chrf, chrf_beta,
+                                          no_repeat_ngram, min_length, repetition_penalty)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False,
-                  sample_topp=0.9, **render):
+                  sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None, **render):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
         attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
         ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
         from . import visualize
         return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                    rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, sample_topp=sample_topp,
-                                   **render)
+                                   no_repeat_ngram=no_repeat_ngram, min_length=min_length, repetition_penalty=repetition_penalty, **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                       rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
-                      topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                      topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
         """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
         ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
         from . import visualize
         return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk, sample_topp)
+                                       rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk, sample_topp,
+                                       no_repeat_ngram, min_length, repetition_penalty)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

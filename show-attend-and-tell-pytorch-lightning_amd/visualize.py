@@ -152,13 +152,14 @@ def _names(items):
 
 @torch.no_grad()
 def _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method, rescore_reward, visual_size,
-            input_size, seed, with_alpha, progressive=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+            input_size, seed, with_alpha, progressive=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
     """load_square -> prepare_image -> encoder -> batched search -> the winning hypothesis of every picture, all enqueued back to back"""
     from . import constraints, evaluation as E
     if int(max_gen_length) < 1:
         raise ValueError("visualize: max_gen_length >= 1 (the batched search)")
-    con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk)
-    constraints.resolve(model.hp.vocab_stoi, model.hp.vocab_size, len(items), beamk, max_gen_length, str(sample_method), **con)     # refuse before any launch
+    con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
+               repetition_penalty=repetition_penalty)
+    constraints.resolve_all(model.hp.vocab_stoi, model.hp.vocab_size, len(items), beamk, max_gen_length, str(sample_method), **con)     # refuse before any launch
     dev = model.embedding.weight.device
     model.eval()
     squares, status, index = _load_squares(items, visual_size, dev, progressive)
@@ -190,13 +191,15 @@ def _read(model, sel, status, index):
 
 def visualize(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None, rescore_method=None,
               rescore_reward=1.0, visual_size=256, input_size=None, power=5.0, opacity=0.75, seed=None, progressive=False,
-              topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+              topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
     """``make_visual`` without the figure, for a batch: returns a ``Visual``.  ``input_size`` None: the model's ``input_size``.  The winning
     caption is the one ``SAT.caption(..., return_all=True)`` lists first (the highest rescored value; among hypotheses with the very same
     value this picks the first to finish).  Everything stays on the device until one read of tokens and scores.
-    ``topg`` / ``prefix`` (e.g. ``"a photo of"``) / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``)."""
+    ``topg`` / ``prefix`` (e.g. ``"a photo of"``) / ``banned`` / ``no_unk`` constrain the search, ``no_repeat_ngram`` / ``min_length`` /
+    ``repetition_penalty`` are its history rules (``SATDecoder.beam_decode_batched``)."""
     squares, hw, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                              rescore_reward, visual_size, input_size, seed, True, progressive, topg, prefix, banned, no_unk, sample_topp)
+                                              rescore_reward, visual_size, input_size, seed, True, progressive, topg, prefix, banned, no_unk, sample_topp,
+                                              no_repeat_ngram, min_length, repetition_penalty)
     panels = attention_panels(squares, sel["alphas"], sel["lengths"], hw, power, opacity)
     captions, words, scores, ppl, lengths = _read(model, sel, status, index)
     return Visual(captions, words, scores, ppl, lengths, panels, _names(items))
@@ -204,11 +207,12 @@ def visualize(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_
 
 def caption_image(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
-                  topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9):
+                  topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
     """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch, without panels:
     ``(captions, words, scores, perplexities)``, one entry per picture.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: as ``visualize``."""
     _, _, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, False, progressive, topg, prefix, banned, no_unk, sample_topp)
+                                       rescore_reward, visual_size, input_size, seed, False, progressive, topg, prefix, banned, no_unk, sample_topp,
+                                       no_repeat_ngram, min_length, repetition_penalty)
     captions, words, scores, ppl, _ = _read(model, sel, status, index)
     return captions, words, scores, ppl
 

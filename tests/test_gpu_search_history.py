@@ -1,0 +1,342 @@
+"""GPU: the history rules of the batched caption search ("History rules"): repetition penalty, minimum length, no-repeat
+n-gram.  Shapes, helpers and models of tests/test_gpu_constrained_search.py: V = 83 (every kernel's tail), 9 images x 4 beams, L = 12,
+max_gen_length = 9, temperatures [1.0, 0.7], one and two LSTM layers.
+
+The bound of test 1.  No test pins sat_beam_scores against float64, so the bound is derived here from the arithmetic of
+beam_scores_row, score = x * (1 / T) - (M + log S) + parent in fp32 with S a sum of V fast exponentials: a thread adds ceil(V / 256)
+terms, the wave and block reductions add 6 + 4 more, every term carries a few ulp of the fast exponential and of x * (1 / T), the fast
+logarithm, 1 / T, the penalty (one multiply or divide) and the three additions one rounding each.  With u = 2^-24 that is at most
+(ceil(V / 256) + 32) u relative to the magnitudes that enter the result, max|x| / T + |logsumexp| + |parent| + 1 of the row, taken
+from the float64 restatement.  The same bound holds with and without the penalty."""
+import ctypes as C
+import math
+from collections import Counter
+
+import numpy as np
+import pytest
+import torch
+
+import history_ref as HR
+import test_gpu_constrained_search as TC
+
+pytestmark = pytest.mark.gpu
+
+V, S, HW, TEMPS, PLENS = TC.V, TC.S, TC.HW, TC.TEMPS, TC.PLENS
+#: seeds chosen on the CPU with tests/history_ref.py: every selection of the reference keeps >= 1e-3 between the last kept and the
+#: first dropped score and >= 2e-4 between the final scores of an image (test 4 asserts both again)
+REF_SEEDS = {1: 526, 2: 285}
+MORE_SEEDS = {1: 509, 2: 197}
+REF_CASES = {"n2": dict(no_repeat_ngram=2), "n3_m4_pen": dict(no_repeat_ngram=3, min_length=4, repetition_penalty=1.3), "n1": dict(no_repeat_ngram=1)}
+_cache = {}
+
+
+# ------------------------------------------------------------------------------------------------ 1. the kernel alone
+def _restate(x, T, masked, parent, hist, lens, rules, step, end):
+    """float64: (scores with -inf at the masked positions, the magnitude of every row that enters the bound)"""
+    n, m, theta = rules
+    x64 = x.astype(np.float64)
+    th = float(np.float32(theta))
+    for r in range(x.shape[0]):
+        if theta != 1.0:
+            for v in set(hist[r, :lens[r]].tolist()):
+                x64[r, v] = x64[r, v] / th if x[r, v] > 0 else x64[r, v] * th
+    z = x64 / float(np.float32(T))
+    mx = z.max(1, keepdims=True)
+    lse = mx + np.log(np.exp(z - mx).sum(1, keepdims=True))
+    add = parent.astype(np.float64)[:, None] if parent is not None else 0.0
+    s = z - lse + add
+    mag = np.abs(z).max(1) + np.abs(lse[:, 0]) + (np.abs(parent.astype(np.float64)) if parent is not None else 0.0) + 1.0
+    for r in range(x.shape[0]):
+        s[r, masked] = -np.inf
+        if step < m:
+            s[r, end] = -np.inf
+        for v in HR.blocked_words(hist[r, :lens[r]].tolist(), n):
+            s[r, v] = -np.inf
+    return s, mag
+
+
+def _history_scores(lib, L, x, T, masked, parent, hist, lens, rules, step, end):
+    out = torch.full_like(x, float("nan"))
+    st = L.BeamHistory(no_repeat_ngram=rules[0], min_length=rules[1], repetition_penalty=rules[2])
+    L.check(lib.sat_beam_history_scores(L.ptr(x), x.shape[0], x.shape[1], T, L.ptr(masked), masked.numel(), L.ptr(parent) if parent is not None else None,
+                                        L.ptr(hist), L.ptr(lens), hist.shape[1], C.byref(st), step, end, L.ptr(out), L.stream_ptr()), "sat_beam_history_scores")
+    return out
+
+
+@pytest.mark.parametrize("Vk", [83, 257, 1030])
+def test_history_scores_kernel_against_float64(Vk):
+    """1. rows = 7, hist_stride = 128, lengths 0, 1, n - 1, n, 128 and two more, histories over a small alphabet (heavy repeats);
+    n in {1, 2, 3, 5}, theta in {1.0, 1.3, 0.8}, step below and at min_length, with and without parent scores.  -inf positions exact,
+    finite values within the bound of the module docstring; every rule off is sat_beam_scores bit for bit; two runs, same bits."""
+    import sat_amd  # noqa: F401
+    from sat_amd import _lib as L
+    lib = L.lib()
+    rows, stride, m = 7, 128, 4
+    g = torch.Generator().manual_seed(100 + Vk)
+    x = (torch.randn(rows, Vk, generator=g) * 3.0).cuda().contiguous()
+    parent = (-torch.rand(rows, generator=g) * 20.0).cuda().contiguous()
+    end, masked = Vk - 1, torch.tensor([Vk - 2, 0], dtype=torch.int32, device="cuda")
+    alphabet = torch.tensor([1, 2, 3, 5, Vk - 4, Vk // 2])           # six words: every n-gram of a long history repeats
+    hist = alphabet[torch.randint(0, 6, (rows, stride), generator=g)].to(torch.int32)
+    hist[5, :40] = torch.tensor([7, 8, 9, 7, 8] * 8, dtype=torch.int32)  # a period-5 history: n = 5 has something to block
+    bound_u = (math.ceil(Vk / 256) + 32) * 2.0 ** -24
+    worst, n_inf = 0.0, 0
+    for n in (1, 2, 3, 5):
+        lens = torch.tensor([0, 1, max(n - 1, 0), n, 128, 40, 9], dtype=torch.int32)
+        hist_d, lens_d = hist.cuda().contiguous(), lens.cuda().contiguous()
+        for theta in (1.0, 1.3, 0.8):
+            for step in (m - 1, m):
+                for par in (None, parent):
+                    T = 0.7 if par is not None else 1.0
+                    rules = (n, m, theta)
+                    got = _history_scores(lib, L, x, T, masked, par, hist_d, lens_d, rules, step, end)
+                    again = _history_scores(lib, L, x, T, masked, par, hist_d, lens_d, rules, step, end)
+                    assert torch.equal(got.view(torch.int32), again.view(torch.int32))
+                    want, mag = _restate(x.cpu().numpy(), T, masked.cpu().tolist(), par.cpu().numpy() if par is not None else None, hist.numpy(),
+                                         lens.tolist(), rules, step, end)
+                    got = got.cpu().numpy().astype(np.float64)
+                    assert not np.isnan(got).any()
+                    assert np.array_equal(np.isneginf(got), np.isneginf(want)), (n, theta, step)
+                    fin = np.isfinite(want)
+                    with np.errstate(invalid="ignore"):
+                        ratio = float((np.abs(np.where(fin, got - want, 0.0)) / (bound_u * mag[:, None])).max())
+                    worst = max(worst, ratio); n_inf += int((~fin).sum())
+                    assert ratio <= 1.0, (n, theta, step, par is not None, ratio)
+    print("V=%d: worst error / bound %.3f, %d blocked entries checked" % (Vk, worst, n_inf))
+    # every rule off: sat_beam_scores bit for bit, whatever the history holds
+    for par, T in ((None, 1.0), (parent, 0.7)):
+        want = torch.full_like(x, float("nan"))
+        L.check(lib.sat_beam_scores(L.ptr(x), rows, Vk, T, L.ptr(masked), 2, L.ptr(par) if par is not None else None, L.ptr(want), L.stream_ptr()),
+                "sat_beam_scores")
+        for rules in ((0, 0, 0.0), (0, 0, 1.0)):
+            got = _history_scores(lib, L, x, T, masked, par, hist_d, lens_d, rules, 0, end)
+            assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+
+
+# ------------------------------------------------------------------------------------------------ 2. off is today's search
+def _raw_history(dec, hp, ann, K, smp, con, hist):
+    """sat_beam_search_history on zeroed buffers, as TC._raw calls its neighbours"""
+    from sat_amd import _lib as L, decoder as Dk
+    lib = L.lib()
+    B, Lc, D = ann.shape
+    dims = Dk.decoder_dims(B, K, 2, Lc, D, 16, 24, 40, V, 0, hp.deep_output, dec.pad_idx, 0, layers=int(hp.decoder_layers))
+    w, keep = dec._params_struct()
+    i32 = dict(dtype=torch.int32, device="cuda"); f32 = dict(dtype=torch.float32, device="cuda")
+    o = dict(tok_in=torch.zeros(S + 2, B, K, **i32), prev_row=torch.zeros(S + 2, B, K, **i32), alpha_hist=torch.zeros(S + 1, B, K, Lc, **f32),
+             fin_count=torch.zeros(B, **i32), fin_step=torch.zeros(B, K, **i32), fin_row=torch.zeros(B, K, **i32),
+             fin_score=torch.zeros(B, K, **f32), fin_mean=torch.zeros(B, K, **f32))
+    tarr = (C.c_float * len(TEMPS))(*TEMPS)
+    ids = (C.c_int32 * 4)(*[int(hp.vocab_stoi[s]) for s in ("<START>", "<PAD>", "<END>", "<UNK>")])
+    outs = [L.ptr(o[k]) for k in ("tok_in", "prev_row", "alpha_hist", "fin_count", "fin_step", "fin_row", "fin_score", "fin_mean")]
+    nbytes = lib.sat_beam_search_history_workspace_bytes(C.byref(dims), K, con.topg if con is not None else 0, S)
+    assert nbytes >= lib.sat_beam_search_constrained_workspace_bytes(C.byref(dims), K, con.topg if con is not None else 0) > 0
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    L.check(lib.sat_beam_search_history(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(TEMPS), ids, C.byref(smp) if smp is not None else None,
+                                        C.byref(con) if con is not None else None, C.byref(hist) if hist is not None else None, *outs, L.ptr(ws), nbytes,
+                                        L.stream_ptr()), "sat_beam_search_history")
+    torch.cuda.synchronize()
+    return o
+
+
+@pytest.mark.parametrize("layers", [1, 2])
+def test_rules_off_is_todays_search_bit_for_bit(layers):
+    """2. history = NULL, an all-zero struct and theta = 1.0f against sat_beam_search_constrained: every back-trace buffer equal, at
+    beams 1 and 4; once with a prefix plus topg = 2, once the sampled "topk" search on a Gumbel table"""
+    from sat_amd import _lib as L
+    dec, hp, ann = TC._setup(layers)
+    B = ann.shape[0]
+    pre = torch.tensor([p + [0] * (S - len(p)) for p in TC._prefixes(PLENS)], dtype=torch.int32, device="cuda")
+    plen = torch.tensor(PLENS, dtype=torch.int32, device="cuda")
+    g = torch.Generator().manual_seed(5)
+    gum = (-torch.log(-torch.log(torch.rand(S + 1, B * 4, 3, generator=g).clamp_(1e-9, 1 - 1e-7)))).cuda().contiguous()
+    runs = [(1, None, None), (4, None, None),
+            (4, None, L.BeamConstraints(topg=2, max_prefix=S, prefix=pre.data_ptr(), prefix_len=plen.data_ptr())),
+            (4, L.BeamSampling(method=2, sample_topk=3, seed=1, gumbel=gum.data_ptr()), None)]
+    for K, smp, con in runs:
+        want = TC._raw(dec, hp, ann, K, "constrained", smp, con)
+        assert int(want["fin_count"].min()) >= 1
+        for hist in (None, L.BeamHistory(), L.BeamHistory(repetition_penalty=1.0)):
+            got = _raw_history(dec, hp, ann, K, smp, con, hist)
+            for k in want:
+                assert torch.equal(got[k], want[k]), (K, smp is not None, con is not None, hist is not None, k)
+
+
+# ------------------------------------------------------------------------------------------------ the searches under test
+def _model(layers, seed):
+    return TC._setup(layers, seed=seed)
+
+
+def _batched(layers, seed, **kw):
+    """beam_decode_batched(beam 4, LN, return_all) on the seeded decoder, computed once per setting and left unchanged"""
+    key = (layers, seed, tuple(sorted((k, repr(v)) for k, v in kw.items())))
+    if key not in _cache:
+        dec, _, ann = _model(layers, seed)
+        _cache[key] = dec.beam_decode_batched(ann, HW, beamk=4, max_gen_length=S, temperature=TEMPS, rescore_method="LN", return_all=True, **kw)
+    return _cache[key]
+
+
+def _repeating_prefixes():
+    """PLENS words per image; three of the prefixes repeat themselves (they are obeyed, and count as history afterwards)"""
+    pre = TC._prefixes(PLENS)
+    pre[2] = [11, 11, 11]
+    pre[5] = [21, 22, 21, 22, 21, 22, 21, 22, 21]
+    pre[8] = [31, 32, 31, 32]
+    assert [len(p) for p in pre] == PLENS
+    return pre
+
+
+def _loop_cases(layers, seed):
+    """name -> keywords: the three cases of test 4 and n = 2 with topg = 2, with mixed-length prefixes, with no_unk and two banned ids"""
+    plain = _batched(layers, seed)
+    _, hp, _ = _model(layers, seed)
+    special = {int(hp.vocab_stoi[s]) for s in ("<START>", "<PAD>", "<END>", "<UNK>")}
+    common = [t for t, _ in Counter(t for caps in plain[0] for c in caps for t in c if t not in special).most_common(2)]
+    cases = dict(REF_CASES)
+    cases["n2_topg2"] = dict(no_repeat_ngram=2, topg=2)
+    cases["n2_prefix"] = dict(no_repeat_ngram=2, prefix=_repeating_prefixes())
+    cases["n2_banned"] = dict(no_repeat_ngram=2, no_unk=True, banned=common)
+    return cases
+
+
+CASE_NAMES = ["n2", "n3_m4_pen", "n1", "n2_topg2", "n2_prefix", "n2_banned"]
+MODELS = [(1, REF_SEEDS[1]), (1, MORE_SEEDS[1]), (2, REF_SEEDS[2]), (2, MORE_SEEDS[2])]
+
+
+def _check_properties(caps_all, kw, plens=None):
+    n, m = kw.get("no_repeat_ngram", 0), kw.get("min_length", 0)
+    for b, caps in enumerate(caps_all):
+        for c in caps:
+            assert len(c) >= m, (b, c)
+            if n:
+                assert not HR.repeats_ngram(c, n, free_from=plens[b] if plens else 0), (b, c)
+
+
+@pytest.mark.parametrize("layers", [1, 2])
+def test_rules_that_cannot_bite_change_nothing(layers):
+    """3. no_repeat_ngram = max_gen_length + 1, min_length = 1 (step 0 masks <END> already), repetition_penalty = 1.0: the plain result
+    bit for bit, through the new kernels"""
+    dec, _, ann = TC._setup(layers)
+    want = TC._plain(layers, 4, rescore_method="LN", return_all=True)
+    kw = dict(beamk=4, max_gen_length=S, temperature=TEMPS, rescore_method="LN", return_all=True)
+    for rules in (dict(no_repeat_ngram=S + 1, min_length=1, repetition_penalty=1.0), dict(no_repeat_ngram=S + 1), dict(min_length=1)):
+        TC._same(dec.beam_decode_batched(ann, HW, **kw, **rules), want)
+
+
+@pytest.mark.parametrize("case", list(REF_CASES))
+@pytest.mark.parametrize("layers", [1, 2])
+def test_against_the_cpu_reference_search(layers, case):
+    """4. captions and list order identical, values within 1e-4 (the GPU-vs-CPU bound); the reference's own margins prove that no pick
+    and no final order rests on a near-tie.  Measured on the CPU: seed 526 boundary 1.5e-3 .. 1.7e-3, final >= 2.6e-3; seed 285 boundary
+    1.7e-3 .. 2.9e-3, final 2.3e-4"""
+    seed = REF_SEEDS[layers]
+    dec, hp, ann = _model(layers, seed)
+    sd = {k: v.detach().cpu().clone() for k, v in dec.state_dict().items()}
+    ann_img = ann.cpu().reshape(9, 3, 4, 32).permute(0, 3, 1, 2).contiguous()
+    margins = {}
+    with torch.no_grad():
+        want = HR.beam_search(sd, hp, ann_img, beamk=4, max_gen_length=S, temperature=TEMPS, rescore_method="LN", return_all=True, margins=margins,
+                              **REF_CASES[case])
+    boundary = [g for g in margins["boundary"] if g is not None]
+    final = [g for gaps in margins["final"] for g in gaps]
+    print("reference margins: boundary %.3e over %d selections, final %.3e over %d neighbours" % (min(boundary), len(boundary), min(final), len(final)))
+    assert min(boundary) >= 1e-3 and min(final) >= 2e-4
+    got = _batched(layers, seed, **REF_CASES[case])
+    want = (want[0], want[1], [[a.reshape(-1, *HW) for a in al] for al in want[2]], want[3])
+    TC._close(want, got, 1e-4)
+
+
+@pytest.mark.parametrize("case", CASE_NAMES)
+@pytest.mark.parametrize("layers,seed", MODELS)
+def test_batched_equals_the_per_image_loop(layers, seed, case):
+    """5. the loop applies the rules with torch ops on top_preds and the logits: captions and list order identical, values within 1e-5"""
+    dec, _, ann = _model(layers, seed)
+    kw = _loop_cases(layers, seed)[case]
+    loop = dec.beam_decode(ann, HW, beamk=4, max_gen_length=S, temperature=TEMPS, rescore_method="LN", return_all=True, **kw)
+    TC._close(loop, _batched(layers, seed, **kw), 1e-5)
+
+
+@pytest.mark.parametrize("case", CASE_NAMES)
+@pytest.mark.parametrize("layers,seed", MODELS)
+def test_properties_with_bite(layers, seed, case):
+    """6. no returned caption repeats an n-gram (those wholly inside a forced prefix excepted), none is shorter than min_length, and
+    the result differs from the search without the rules, which does repeat itself"""
+    kw = _loop_cases(layers, seed)[case]
+    got = _batched(layers, seed, **kw)
+    plain = _batched(layers, seed)
+    n = kw["no_repeat_ngram"]
+    assert sum(HR.repeats_ngram(c, n) for caps in plain[0] for c in caps) >= 5 and sum(len(caps) for caps in plain[0]) == 36
+    _check_properties(got[0], kw, PLENS if "prefix" in kw else None)
+    assert all(len(caps) == 4 for caps in got[0])
+    unruled = _batched(layers, seed, **{k: v for k, v in kw.items() if k not in ("no_repeat_ngram", "min_length", "repetition_penalty")})
+    assert got[0] != unruled[0] and got[0] != plain[0]
+    if "prefix" in kw:
+        assert all(c[:len(kw["prefix"][b])] == kw["prefix"][b] for b, caps in enumerate(got[0]) for c in caps)
+        assert got[0][5] == [kw["prefix"][5]] * 4               # P_b = max_gen_length: the repeating prefix is obeyed to the cut
+    if "banned" in kw:
+        _, hp, _ = _model(layers, seed)
+        ban = set(kw["banned"]) | {int(hp.vocab_stoi["<UNK>"])}
+        assert not any(t in ban for caps in got[0] for c in caps for t in c)
+    if seed == 285:
+        assert min(len(c) for caps in plain[0] for c in caps) == 1
+        if case == "n3_m4_pen":
+            assert min(len(c) for caps in got[0] for c in caps) == 8
+
+
+@pytest.mark.parametrize("method", ["nucleus", "topk"])
+@pytest.mark.parametrize("layers", [1, 2])
+def test_sampling_methods_take_the_rules(layers, method):
+    """7. n = 2, m = 3 under "nucleus" (p = 0.9) and "topk", drawn by the device generator: the properties of test 6, and the same seed
+    draws the same captions"""
+    seed = REF_SEEDS[layers]
+    dec, _, ann = _model(layers, seed)
+    rules = dict(no_repeat_ngram=2, min_length=3)
+    kw = dict(beamk=4, max_gen_length=S, temperature=TEMPS, rescore_method="LN", return_all=True, sample_method=method, sample_topk=3, sample_topp=0.9, seed=7)
+    got = dec.beam_decode_batched(ann, HW, **kw, **rules)
+    again = dec.beam_decode_batched(ann, HW, **kw, **rules)
+    assert got[0] == again[0] and got[1] == again[1]
+    _check_properties(got[0], rules)
+    assert all(len(caps) == 4 for caps in got[0])
+    plain = _batched(layers, seed)
+    assert sum(HR.repeats_ngram(c, 2) for caps in plain[0] for c in caps) >= 5 and got[0] != plain[0]
+    unruled = dec.beam_decode_batched(ann, HW, **kw)            # the same draws without the rules, for the record
+    print("%s without the rules: %d of 36 hypotheses repeat a bigram, shortest %d words, %s the ruled result"
+          % (method, sum(HR.repeats_ngram(c, 2) for caps in unruled[0] for c in caps), min(len(c) for caps in unruled[0] for c in caps),
+             "equal to" if unruled[0] == got[0] else "differs from"))
+
+
+def test_evaluation_surface_takes_the_rules():
+    """8. val_batch_stats(...).metrics() against score_captions on caption(...), both with no_repeat_ngram = 2 and min_length = 3:
+    bleu / gleu exactly, cosine within max(2 e_torch, 1e-6) of the float64 value, perplexity 1e-6 relative (the rule of the
+    unconstrained pair, as in test_evaluation_surface_takes_the_constraints)"""
+    import sat_amd  # noqa: F401
+    from sat_amd import model as M
+    from oracle import prng, sat_oracle as O
+    over = dict(encoder_arch="resnet18", encoder_dim=32, input_size=64, encoder_size=3, vocab_size=60, embed_dim=24, attention_dim=16,
+                decoder_dim=40, deep_output=True, val_beamk=3, val_max_len=7)
+    torch.manual_seed(5)
+    model = M.SAT(**vars(O.default_hparams(**over))).cuda()
+    img = torch.from_numpy(prng.uniform((4, 3, 64, 64), 41, 0.0, 1.0)).cuda()
+    caps, lengths = prng.captions(4, 3, 9, 60, 42, min_len=3)
+    caps, lengths = torch.from_numpy(caps).cuda(), torch.from_numpy(lengths)
+    kw = dict(beamk=3, max_gen_length=7, temperature=1.0, rescore_method="LN", rescore_reward=0.7, no_repeat_ngram=2, min_length=3)
+    captions, _, _, ppl = model.caption(img, return_all=False, **kw)
+    assert all(len(c) >= 3 and not HR.repeats_ngram(c, 2) for c in captions)
+    want = model.score_captions(captions, caps, lengths, ppl)
+    assert want == model.val_batch((img, caps, lengths), **kw)
+    got = model.val_batch_stats((img, caps, lengths), **kw).metrics()
+    assert set(got) == set(want)
+    for k in ("bleu1", "bleu2", "bleu3", "bleu4", "gleu"):
+        assert got[k] == want[k], (k, got[k], want[k])
+    E64 = model.embedding.weight.detach().cpu().double()
+    c64 = []
+    for i, h in enumerate(captions):
+        cv = E64[torch.as_tensor(h, dtype=torch.long)].mean(0)
+        rvs = [E64[caps[i][j][1:int(l)].cpu()].mean(0) for j, l in enumerate(lengths[i])]
+        c64.append(max(float(((rv / rv.norm().clamp_min(1e-8)) * (cv / cv.norm().clamp_min(1e-8))).sum()) for rv in rvs))
+    c64 = sum(c64) / len(c64)
+    e_kernel, e_torch = abs(got["cosine_similarity"] - c64), abs(want["cosine_similarity"] - c64)
+    print("cosine: e_kernel %.3e  e_torch %.3e" % (e_kernel, e_torch))
+    assert e_kernel <= max(2 * e_torch, 1e-6)
+    assert abs(got["perplexity"] - want["perplexity"]) <= 1e-6 * abs(want["perplexity"])
+    words = model.caption_image([np.zeros((80, 80, 3), np.uint8)], beamk=3, max_gen_length=7, rescore_method="LN", no_repeat_ngram=2, min_length=3)
+    assert len(words[0][0]) >= 3 and not HR.repeats_ngram(words[0][0], 2)

@@ -3,7 +3,10 @@ Decode-only timing (annotations precomputed) and end-to-end timing (encoder incl
 ``--topg G`` / ``--prefix-len P`` / ``--no-unk`` time the constrained batched search instead ("Constrained search"): the
 prefix of an image is the first P words of its unconstrained caption; the result is checked against the per-image loop.
 ``--sample-method multinomial|topk|nucleus`` (``--sample-topk``, ``--sample-topp``) times the sampled batched search drawn by the device
-generator from a fixed seed: the median of ``--repeats`` timed calls after two warm-up calls."""
+generator from a fixed seed: the median of ``--repeats`` timed calls after two warm-up calls.
+``--no-repeat-ngram N`` / ``--min-length M`` / ``--repetition-penalty X`` time the batched search under the history rules (DESIGN.md 5,
+"History rules") next to the plain batched search, alternating the two over ``--repeats`` calls each; ``--skip-loop`` leaves the
+per-image loop (the slowest line, and the check of the result) out."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,8 +24,14 @@ ap.add_argument("--sample-method", default="beam", choices=["beam", "multinomial
 ap.add_argument("--sample-topk", type=int, default=3)
 ap.add_argument("--sample-topp", type=float, default=0.9)
 ap.add_argument("--repeats", type=int, default=9)
+ap.add_argument("--no-repeat-ngram", type=int, default=None, help="no n-gram of this size is said twice in a caption (0 / unset = off)")
+ap.add_argument("--min-length", type=int, default=None, help="<END> stays masked until a caption has this many words")
+ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's penalty on the logits of the words already said (1.0 = off)")
+ap.add_argument("--skip-loop", action="store_true")
 a = ap.parse_args()
 constrained = a.topg is not None or a.prefix_len > 0 or a.no_unk
+history = dict(no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty)
+history_on = any(v is not None for v in history.values())
 
 hp, T, B, R = bench.hparams("c2")
 torch.manual_seed(42)
@@ -32,6 +41,31 @@ with torch.no_grad():
     ann, hw = model.encode(img)
     ann = ann.contiguous()
     for beamk in a.beams:
+        if history_on:
+            plain_kw = dict(beamk=beamk, max_gen_length=20)
+            rule_kw = dict(plain_kw, sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, topg=a.topg, no_unk=a.no_unk, **history)
+            if a.sample_method != "beam":
+                rule_kw["seed"] = 7
+            for _ in range(2):
+                caps = model.beam_decode_batched(ann, hw, **plain_kw)[0]
+                capsh = model.beam_decode_batched(ann, hw, **rule_kw)[0]
+            if not a.skip_loop and a.sample_method == "beam":
+                capsl = model.beam_decode(ann, hw, **rule_kw)[0]
+                print("beam %d: %d of 64 captions under the rules equal the per-image loop's" % (beamk, sum(x == y for x, y in zip(capsh, capsl))))
+            tp, th = [], []
+            for _ in range(a.repeats):                  # alternate, so that both lines see the same machine
+                for kw, times in ((plain_kw, tp), (rule_kw, th)):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    model.beam_decode_batched(ann, hw, **kw)
+                    torch.cuda.synchronize(); times.append(time.perf_counter() - t0)
+            mp, mh = statistics.median(tp), statistics.median(th)
+            print("beam %d: batched search, rules off: median %.2f ms (min %.2f, max %.2f) per 64 images incl. host back-trace over %d calls"
+                  % (beamk, mp * 1e3, min(tp) * 1e3, max(tp) * 1e3, a.repeats))
+            print("beam %d: batched search, history rules (no_repeat_ngram=%s, min_length=%s, repetition_penalty=%s, %s): median %.2f ms (min %.2f, max %.2f), "
+                  "%.3fx the rules-off line, %d of 64 captions differ, mean caption length %.1f"
+                  % (beamk, a.no_repeat_ngram, a.min_length, a.repetition_penalty, a.sample_method, mh * 1e3, min(th) * 1e3, max(th) * 1e3, mh / mp,
+                     sum(x != y for x, y in zip(capsh, caps)), sum(len(c) + 1 for c in capsh) / 64))
+            continue
         for _ in range(2):
             model.beam_decode(ann[:8], hw, beamk=beamk, max_gen_length=20)
         torch.cuda.synchronize(); t0 = time.perf_counter()

@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--topg", type=int, default=None, help="top-g clipping: only the G best words of every hypothesis are candidates (beam sampling)")
     ap.add_argument("--prefix", default=None, help='words every caption starts with, e.g. "a photo of" (each must be in the vocabulary)')
     ap.add_argument("--no-unk", action="store_true", help="never emit <UNK>")
+    ap.add_argument("--no-repeat-ngram", type=int, default=None, help="no n-gram of this size is said twice in a caption (0 / unset = off)")
+    ap.add_argument("--min-length", type=int, default=None, help="<END> stays masked until a caption has this many words")
+    ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's penalty on the logits of the words already said (1.0 = off)")
     a = ap.parse_args()
     if (a.idx is None) == (a.count is None):
         ap.error("give either --idx or --count")
@@ -65,7 +68,8 @@ def main():
         vis = model.visualize(paths, beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature, sample_method=a.sample_method,
                               sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise, rescore_method=None if a.rescore_method == "NONE" else a.rescore_method,
                               rescore_reward=a.rescore_reward, visual_size=a.visual_size, input_size=a.input_size, seed=a.seed, progressive=a.progressive,
-                              topg=a.topg, prefix=a.prefix, no_unk=a.no_unk)
+                              topg=a.topg, prefix=a.prefix, no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length,
+                              repetition_penalty=a.repetition_penalty)
         for j, i in enumerate(chunk):
             refs = [" ".join(ds.itos(t) for t in c[1:n]) for c, n in zip(ds.encoded_captions[i], ds.lengths[i])]
             name = os.path.join(a.out, "%s_result.jpg" % vis.names[j])
