@@ -375,6 +375,8 @@ int sat_beam_search_history(const sat_decoder_dims* d, const sat_decoder_params*
                             const sat_beam_constraints* constraints, const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row,
                             float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* A -inf logit gets the score -inf and leaves the rest of its row as torch.log_softmax does; a row of nothing but -inf gives NaN, as
+ * torch does.  Masked ids outside [0, V) mask nothing. */
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids /* device */,
                     int32_t n_masked, const float* parent_scores /* (beams) or NULL */, float* scores, void* stream);
 /* The score kernel of sat_beam_search_history on its own, every row at a free step: row r has said the first hist_len[r] words of
@@ -387,6 +389,9 @@ int sat_beam_history_scores(const float* logits /* (rows, V) */, int32_t rows, i
                             int32_t n_masked, const float* parent_scores /* (rows) or NULL */, const int32_t* hist /* (rows, hist_stride) */,
                             const int32_t* hist_len /* (rows) */, int32_t hist_stride, const sat_beam_history* rules, int32_t step, int32_t end_id,
                             float* scores, void* stream);
+/* The k largest of x (1 <= k <= n) in descending order, equal values in increasing index order, every index once: a stable descending
+ * sort cut at k.  -inf entries are ordinary values that sort last, so with fewer than k entries above -inf the result ends in the -inf
+ * entries of lowest index.  (torch.topk promises no order among equal values.)  NaN in x: the result is unspecified. */
 int sat_topk(const float* x, float* work /* n floats scratch */, int64_t n, int32_t k, float* values, int32_t* indices, void* stream);
 /* The key kernel of SAT_SAMPLE_NUCLEUS on its own, every row live: keys (rows, V) as above with `step` the divisor (> 0) and
  * `stream` the hash stream (the search passes the step); gumbel (rows, V) or NULL; nucleus_size (rows) or NULL receives |N| per row
@@ -573,9 +578,10 @@ int sat_init_lstm_bwd(const float* dinit, const float* mean, const float* f, con
                       int32_t n2, void* stream);
 
 /* nn.Embedding(V, m, max_norm, padding_idx) as the reference calls it (model.py:158-164; uses at 298, 526).  Forward: rows of `table`
- * gathered by token id (-1 = zero row); max_norm > 0 first renormalises, IN PLACE like torch, the table rows that occur in `tokens`
- * (flags_scratch: V ints).  Backward: dtable fully overwritten; rows of dY are added per vocabulary row in increasing row order (no
- * floating-point atomics), the padding row stays zero; scratch: 3 V + 1 + rows ints. */
+ * gathered by token id (-1, and any other id outside [0, V) = zero row: the ids the backward skips); max_norm > 0 first renormalises,
+ * IN PLACE like torch, the table rows that occur in `tokens` (flags_scratch: V ints).  Backward: dtable fully overwritten; rows of dY
+ * are added per vocabulary row in increasing row order (no floating-point atomics), the padding row stays zero; scratch:
+ * 3 V + 1 + rows ints. */
 int sat_embedding_fwd(float* table, const int32_t* tokens, float* out, int32_t rows, int32_t V, int32_t m, float max_norm, int32_t* flags_scratch, void* stream);
 int sat_embedding_bwd(const float* dY, const int32_t* tokens, float* dtable, int32_t rows, int32_t V, int32_t m, int32_t padding_idx, int32_t* scratch, void* stream);
 /* backward of the beta gate's Sigmoid (model.py:187-192): dpre = dy * y * (1 - y); the Linear around it is sat_gemm_f32 (epi 2 forward) */

@@ -470,7 +470,7 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     if (d.embed_max_norm > 0.f) SAT_TRY(dev_fill_bytes(st, w.flags, 0, (size_t)d.V * 4));
     if (ts > 0) {
         SAT_TRY(renorm(w.Tok, ts * N));
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(ts * N), dim3(64), 0, st, p.embedding, w.Tok, w.Y, ts * N, m, d.embedding_dropout, (unsigned long long)d.dropout_seed, 0L);
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(ts * N), dim3(64), 0, st, p.embedding, w.Tok, w.Y, ts * N, m, d.V, d.embedding_dropout, (unsigned long long)d.dropout_seed, 0L);
         SAT_TRY(launch_ok("embedding gather"));
         SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, w.GY, 4 * n, ts * N, 4 * n, m));
     }
@@ -486,7 +486,7 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                 hipLaunchKernelGGL(argmax_tokens_kernel, dim3(N), dim3(256), 0, st, logits, b.prow + (long)(t - 1) * N, b.lengths, w.Tok + (long)t * N, d.V, t);
                 SAT_TRY(launch_ok("argmax_tokens"));
                 SAT_TRY(renorm(w.Tok + (long)t * N, N));
-                hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, w.Tok + (long)t * N, w.Y + (long)t * N * m, N, m, d.embedding_dropout, (unsigned long long)d.dropout_seed, (long)t * N);
+                hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, w.Tok + (long)t * N, w.Y + (long)t * N * m, N, m, d.V, d.embedding_dropout, (unsigned long long)d.dropout_seed, (long)t * N);
                 SAT_TRY(launch_ok("embedding gather"));
             } else {                            // decision + embedding row in one launch
                 hipLaunchKernelGGL(argmax_gather_kernel, dim3(N), dim3(256), 0, st, logits, b.prow + (long)(t - 1) * N, b.lengths, w.Tok + (long)t * N, d.V, t, p.embedding,
@@ -747,7 +747,7 @@ int decoder_infer_step(const sat_decoder_dims& d, const sat_decoder_params& p, c
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && K <= Kmax, "decoder_infer_step: workspace or beam count");
     t_bf16_mfma = d.precision ? 1 : 0;
     const int n = d.n, A = d.A, D = d.D, m = d.m, HCW = A + D + 4 * n;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(K), dim3(64), 0, st, p.embedding, tokens, w.Y, K, m, 0.f, 0ull, 0L);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(K), dim3(64), 0, st, p.embedding, tokens, w.Y, K, m, d.V, 0.f, 0ull, 0L);
     SAT_TRY(launch_ok("embedding gather"));
     if (NL == 1) {
         SAT_TRY(gemm(st, A_ROW, B_ROW, h, n, w.Wcat, n, w.hc, HCW, K, HCW, n, 0, EPI_BIAS_SIGMOID_RANGE, w.bcat, nullptr, nullptr, nullptr, 0, A, A + D));
@@ -938,7 +938,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, B, K);
         SAT_TRY(launch_ok("beam_live"));
         // ---- model.py:298-327 for all rows (dead rows: zero attention, state carried, ignored below)
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, tok, w.Y, N, m, 0.f, 0ull, 0L);
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, tok, w.Y, N, m, d.V, 0.f, 0ull, 0L);
         SAT_TRY(launch_ok("embedding gather"));
         const bool noisy = smp && smp->decoder_noise != 0.f;
         if (noisy) {        // model.py:322-324: randn * decoder_noise / (step + 1) joins h of every layer before the LSTM
@@ -1230,7 +1230,7 @@ int embedding_fwd(float* table, const int* tokens, float* out, int rows, int V, 
         hipLaunchKernelGGL(embedding_renorm_kernel, dim3(V), dim3(64), 0, st, table, flags, m, max_norm);
         SAT_TRY(launch_ok("embedding_renorm"));
     }
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(64), 0, st, table, tokens, out, rows, m, 0.f, 0ull, 0L);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(64), 0, st, table, tokens, out, rows, m, V, 0.f, 0ull, 0L);
     return launch_ok("embedding gather");
 }
 // its gradient: rows of dY added into the table rows of their tokens in increasing row order (no floating-point atomics); padding row zero

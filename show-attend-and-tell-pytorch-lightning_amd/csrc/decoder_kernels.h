@@ -69,14 +69,14 @@ __device__ __forceinline__ float dropout_scale(unsigned long long seed, unsigned
     return (u >= p) ? 1.0f / (1.0f - p) : 0.f;
 }
 
-// dst[r, :] = table[tok[r], :] (embedding gather; tok < 0 -> zeros), with embedding_dropout when p > 0
-__global__ void gather_rows_kernel(const float* __restrict__ table, const int* __restrict__ tok, float* __restrict__ out, int rows, int width,
+// dst[r, :] = table[tok[r], :] (embedding gather; tok outside [0, V) -> zeros, the ids the gradient skips), with embedding_dropout when p > 0
+__global__ void gather_rows_kernel(const float* __restrict__ table, const int* __restrict__ tok, float* __restrict__ out, int rows, int width, int V,
                                    float p, unsigned long long seed, long row0) {
     int r = blockIdx.x;
     if (r >= rows) return;
     int t = tok[r];
     for (int c = threadIdx.x; c < width; c += blockDim.x) {
-        float v = (t >= 0) ? table[(long)t * width + c] : 0.f;
+        float v = (t >= 0 && t < V) ? table[(long)t * width + c] : 0.f;
         if (p > 0.f) v *= dropout_scale(seed, 1, (unsigned long long)(row0 + r) * width + c, p);
         out[(long)r * width + c] = v;
     }
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void argmax_gather_kernel(const float* __restr
     } else if (threadIdx.x == 0) tok[i] = -1;
     const int t = live ? s_tok : -1;
     for (int c = threadIdx.x; c < width; c += 256) {
-        float v = (t >= 0) ? table[(long)t * width + c] : 0.f;
+        float v = (t >= 0 && t < V) ? table[(long)t * width + c] : 0.f;          // a row without a maximum (all NaN) leaves t = INT_MAX
         if (p > 0.f) v *= dropout_scale(seed, 1, (unsigned long long)(row0 + i) * width + c, p);
         out[(long)i * width + c] = v;
     }
@@ -1200,11 +1200,14 @@ __global__ void scatter_rows_kernel(const float* __restrict__ src, const int* __
 // The row's arithmetic (shared by the constrained kernel below, so that a word has the same float in both searches).
 // x and o may be the same row (beam_history_scores_kernel normalises its penalised copy in place): every element is read in the
 // first pass, and the last pass reads and writes element v from the same thread.
+// A -inf logit gives a -inf score and leaves the other scores as they are without it; a row of nothing but -inf gives NaN
+// (torch.log_softmax does both).
 __device__ __forceinline__ void beam_scores_row(const float* x, int V, float inv_temp, float add, float* o, int tid) {
     __shared__ float s_m[4], s_s[4];
     float mx = -INFINITY, sum = 0.f;
     for (int v = tid; v < V; v += 256) {
         float xv = x[v] * inv_temp;
+        if (xv == -INFINITY) continue;          // exp(-inf - mx) = 0; with mx still -inf the difference would be NaN
         if (xv > mx) { sum = sum * __expf(mx - xv) + 1.f; mx = xv; } else sum += __expf(xv - mx);
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -1230,17 +1233,18 @@ __global__ __launch_bounds__(256) void beam_scores_kernel(const float* __restric
     for (int k = tid; k < n_masked; k += 256) { int id = masked[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
 }
 
-// top-k of a flat array, descending, ties to the lowest index (torch.topk on the flattened beam scores, model.py:359).
-// Single block; `work` is a scratch copy of x that gets the winners knocked out.
-__global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ x, float* __restrict__ work, long n, int k,
-                                                    float* __restrict__ values, int* __restrict__ indices) {
+// top-k of a flat array of n >= k floats by a single block of 1024 threads: descending, ties to the lowest index, every index at
+// most once.  wk is a scratch copy of x in which a winner is marked as taken with NaN, which the scan skips -- apart from the -inf
+// of masked, banned and out-of-nucleus entries, so once fewer than k entries above -inf are left the rest of the result is the
+// -inf entries in increasing index order (a stable descending sort).  NaN in x is not supported.
+__device__ __forceinline__ void beam_block_topk(const float* __restrict__ x, float* __restrict__ wk, long n, int k, float* __restrict__ values,
+                                                int* __restrict__ indices, int tid) {
     __shared__ float s_v[16]; __shared__ long s_i[16];
-    const int tid = threadIdx.x;
-    for (long i = tid; i < n; i += 1024) work[i] = x[i];
+    for (long i = tid; i < n; i += 1024) wk[i] = x[i];
     __syncthreads();
     for (int it = 0; it < k; ++it) {
         float bv = -INFINITY; long bi = 0x7fffffffffffffffL;
-        for (long i = tid; i < n; i += 1024) { float v = work[i]; if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
+        for (long i = tid; i < n; i += 1024) { float v = wk[i]; if (v != v) continue; if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
         for (int o = 32; o > 0; o >>= 1) {
             float ov = __shfl_xor(bv, o, 64); long oi = __shfl_xor(bi, o, 64);
             if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
@@ -1250,10 +1254,15 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ x,
         if (tid == 0) {
             for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
             values[it] = bv; indices[it] = (int)bi;
-            if (bi < n) work[bi] = -INFINITY;
+            if (bi < n) wk[bi] = __int_as_float(0x7fc00000);
         }
         __syncthreads();
     }
+}
+// torch.topk on the flattened beam scores of one image (model.py:359), with the tie rule above.  Single block.
+__global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ x, float* __restrict__ work, long n, int k,
+                                                    float* __restrict__ values, int* __restrict__ indices) {
+    beam_block_topk(x, work, n, k, values, indices, threadIdx.x);
 }
 
 
@@ -1280,30 +1289,8 @@ __global__ void beam_live_kernel(const int* __restrict__ klive, int* __restrict_
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B * K) live[i] = (i % K) < klive[i / K] ? 1 : 0;
 }
-// torch.topk of the flattened live scores of every image (model.py:343 at step 0: row 0 only; model.py:359 afterwards),
-// descending, ties to the lowest index.  One block per image; `work` (B, K*V) is scratch.
-__device__ __forceinline__ void beam_block_topk(const float* __restrict__ x, float* __restrict__ wk, long n, int k, float* __restrict__ values,
-                                                int* __restrict__ indices, int tid) {
-    __shared__ float s_v[16]; __shared__ long s_i[16];
-    for (long i = tid; i < n; i += 1024) wk[i] = x[i];
-    __syncthreads();
-    for (int it = 0; it < k; ++it) {
-        float bv = -INFINITY; long bi = 0x7fffffffffffffffL;
-        for (long i = tid; i < n; i += 1024) { float v = wk[i]; if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
-        for (int o = 32; o > 0; o >>= 1) {
-            float ov = __shfl_xor(bv, o, 64); long oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-            values[it] = bv; indices[it] = (int)bi;
-            if (bi < n) wk[bi] = -INFINITY;
-        }
-        __syncthreads();
-    }
-}
+// torch.topk of the flattened live scores of every image (model.py:343 at step 0: row 0 only; model.py:359 afterwards):
+// beam_block_topk, one block per image; `work` (B, K*V) is scratch.
 __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ scores, float* __restrict__ work, const int* __restrict__ klive,
                                                          int K, int V, int first_step, float* __restrict__ values, int* __restrict__ indices) {
     const int b = blockIdx.x, tid = threadIdx.x;

@@ -2,10 +2,11 @@
 n-gram.  Shapes, helpers and models of tests/test_gpu_constrained_search.py: V = 83 (every kernel's tail), 9 images x 4 beams, L = 12,
 max_gen_length = 9, temperatures [1.0, 0.7], one and two LSTM layers.
 
-The bound of test 1.  No test pins sat_beam_scores against float64, so the bound is derived here from the arithmetic of
-beam_scores_row, score = x * (1 / T) - (M + log S) + parent in fp32 with S a sum of V fast exponentials: a thread adds ceil(V / 256)
-terms, the wave and block reductions add 6 + 4 more, every term carries a few ulp of the fast exponential and of x * (1 / T), the fast
-logarithm, 1 / T, the penalty (one multiply or divide) and the three additions one rounding each.  With u = 2^-24 that is at most
+The bound of test 1 (test_gpu_decoder_entry_points.py holds sat_beam_scores itself to it, against float64, through _restate below).
+It is derived from the arithmetic of beam_scores_row, score = x * (1 / T) - (M + log S) + parent in fp32 with S a sum of V fast
+exponentials: a thread adds ceil(V / 256) terms, the wave and block reductions add 6 + 4 more, every term carries a few ulp of the
+fast exponential and of x * (1 / T), the fast logarithm, 1 / T, the penalty (one multiply or divide) and the three additions one
+rounding each.  With u = 2^-24 that is at most
 (ceil(V / 256) + 32) u relative to the magnitudes that enter the result, max|x| / T + |logsumexp| + |parent| + 1 of the row, taken
 from the float64 restatement.  The same bound holds with and without the penalty."""
 import ctypes as C
