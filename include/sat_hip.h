@@ -422,6 +422,21 @@ int sat_beam_select(const int32_t* tok_in, const int32_t* prev_row, const int32_
                     const float* fin_score, const float* fin_mean, const float* alpha_hist /* or NULL */, int32_t B, int32_t beamk,
                     int32_t max_gen_length, int32_t L, int32_t rescore_method, float rescore_reward, int32_t pad_id, int32_t* cap_tokens,
                     int32_t* cap_len, float* cap_score, float* cap_raw, int32_t* cap_step, float* cap_alpha /* or NULL */, void* stream);
+/* sat_beam_select with the winner given instead of computed (consensus reranking picks it: sat_caption_mbr below).  pick (B): a
+ * hypothesis index in append order, clamped into [0, max(fin_count[b] - 1, 0)]; pick_score (B, beamk) float64 or NULL: cap_score[b] is
+ * (float)pick_score[b][pick] when it is given and the raw score otherwise.  cap_tokens, cap_len, cap_raw, cap_step and the optional
+ * cap_alpha are sat_beam_select's for that hypothesis (one back-trace, shared by the two kernels); an image without a finished
+ * hypothesis gets the empty caption, raw 0 and, without pick_score, cap_score -inf, as there. */
+int sat_beam_select_at(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
+                       const float* fin_score, const float* alpha_hist /* or NULL */, const int32_t* pick, const double* pick_score /* or NULL */,
+                       int32_t B, int32_t beamk, int32_t max_gen_length, int32_t L, int32_t pad_id, int32_t* cap_tokens, int32_t* cap_len,
+                       float* cap_score, float* cap_raw, int32_t* cap_step, float* cap_alpha /* or NULL */, void* stream);
+/* The back-trace of EVERY finished hypothesis of every image, tokens only: one thread per (b, f) walks the parent rows as
+ * sat_beam_select does for the winner (steps and rows clamped before they address anything).
+ *   hyp_tokens (B, beamk, max_gen_length + 1)  tokens fed at steps 1..step of hypothesis f (append order), then pad_id
+ *   hyp_len (B, beamk)                         step; slots f >= fin_count[b]: length 0, all pad_id */
+int sat_beam_hypotheses(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
+                        int32_t B, int32_t beamk, int32_t max_gen_length, int32_t pad_id, int32_t* hyp_tokens, int32_t* hyp_len, void* stream);
 /* The integers nltk's corpus BLEU / GLEU sum per segment (sat_amd/metrics.py is the specification).  Hypothesis b = the first
  * cap_len[b] tokens of cap_tokens (B, cap_width); reference (b, r) = refs[b][r][1:ref_lengths[b][r]] of refs (B, R, T) (without START
  * and END, as score_captions slices them).  stats (B, 12) int32:
@@ -473,6 +488,24 @@ int sat_ngram_table_add(const int32_t* refs, const int32_t* ref_lengths, int32_t
 int sat_caption_consensus(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths,
                           int32_t B, int32_t R, int32_t T, const void* table, int64_t capacity, int64_t n_images, double sigma,
                           double* scores /* (B, 2) */, void* stream);
+
+/* ------------------------------------------------------------------ consensus (minimum-Bayes-risk) reranking of a beam
+ * (sat_amd/metrics.py is the specification: consensus_utilities).  Image b has hyp_count[b] hypotheses (clamped into [0, K]) in
+ * append order: hypothesis f = the first hyp_len[b][f] tokens (clamped into [0, width]) of hyp_tokens (B, K, width) -- the layout
+ * sat_beam_hypotheses leaves -- with raw scores hyp_logp (B, K) float32 (fin_score).  Against a document-frequency table of n_images
+ * images (above), with cider(i|j) / rouge(i|j) the CIDEr-D / ROUGE-L of hypothesis i taking hypothesis j as its single reference:
+ *   gain(i|j) = w_cider * cider(i|j) + w_rouge * rouge(i|j)      a weight of 0 skips its term, and its work
+ *   q_j       = exp(alpha * (s_j - max_k s_k)) in fp64           alpha = 0: every q_j = 1 and hyp_logp is not read (may be NULL)
+ *   U_i       = (sum over j != i of q_j * gain(i|j)) / (sum over j != i of q_j), j ascending; 0 when the denominator is 0 (one hypothesis)
+ *   winner    = the first i with U_i = max U (append order, as sat_beam_select breaks ties); 0 for an image without hypotheses
+ * utilities (B, K) float64, 0.0 in the slots f >= hyp_count[b]; winner (B) int32, ready for sat_beam_select_at.  One launch, one
+ * workgroup per image; fp64 throughout, every sum one thread's loop in a fixed order, no atomics: the same inputs give the same bits.
+ * SAT_EINVAL before any launch: a null pointer, K > SAT_MBR_MAX_HYPS, width > SAT_CAPTION_MAX_LEN, a refused capacity, n_images < 1,
+ * sigma <= 0, a weight or alpha that is negative or not finite, both weights 0, alpha != 0 without hyp_logp. */
+#define SAT_MBR_MAX_HYPS 32
+int sat_caption_mbr(const int32_t* hyp_tokens, const int32_t* hyp_len, const int32_t* hyp_count, const float* hyp_logp /* (B, K) or NULL */, int32_t B,
+                    int32_t K, int32_t width, const void* table, int64_t capacity, int64_t n_images, double sigma, double w_cider, double w_rouge,
+                    double alpha, double* utilities /* (B, K) */, int32_t* winner /* (B) */, void* stream);
 
 /* ------------------------------------------------------------------ chrF over the characters of the vocabulary's spelling
  * (sat_amd/metrics.py is the specification: chrf_text, chrf_stats, chrf_sentence, chrf; nltk's sentence_chrf with whitespace ignored).

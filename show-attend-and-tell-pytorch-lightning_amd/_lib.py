@@ -343,6 +343,12 @@ SYMBOLS.update({          # CIDEr-D / ROUGE-L against a reference corpus (evalua
     "sat_ngram_table_add": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "sat_caption_consensus": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.c_double, _vp, _vp]),
 })
+SYMBOLS.update({          # consensus (MBR) reranking of the finished beam (evaluation.finished_hypotheses, consensus_utilities, select_hypotheses)
+    "sat_beam_hypotheses": (C.c_int, [_vp] * 5 + [_i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "sat_caption_mbr": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64] + [C.c_double] * 4 + [_vp, _vp, _vp]),
+    "sat_beam_select_at": (C.c_int, [_vp] * 9 + [_i32, _i32, _i32, _i32, _i32] + [_vp] * 7),
+})
+MBR_MAX_HYPS = 32                                                               # SAT_MBR_MAX_HYPS
 SYMBOLS.update({          # chrF over the vocabulary's spelling (evaluation.VocabChars, chrf_scores)
     "sat_caption_chrf": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp]),
 })

@@ -73,6 +73,41 @@ def check_ancestral(sample_method, beamk, graph=False, topg=None, prefix=None, b
         raise ValueError("sample_method='ancestral' is not replayed from a graph (graph=True)")
 
 
+def check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, vocab_size, max_gen_length):
+    """``rescore_method="MBR"`` ("Consensus reranking"): every ``ValueError`` of the consensus selection, before any
+    launch; returns ``(w_cider, w_rouge, alpha)`` as floats, or ``None`` for any other method.  A corpus that was never checked is
+    checked here once per state (``ReferenceCorpus.check``, one host read, remembered by its image count): a table that dropped
+    n-grams would rerank by wrong document frequencies."""
+    if rescore_method != "MBR":
+        return None
+    if mbr_corpus is None:
+        raise ValueError("rescore_method='MBR' needs mbr_corpus (an evaluation.ReferenceCorpus): the document frequencies of the consensus metric")
+    if int(getattr(mbr_corpus, "images", 0)) < 1:
+        raise ValueError("rescore_method='MBR': mbr_corpus holds no image (ReferenceCorpus.add)")
+    if int(beamk) < 1 or int(beamk) > L.MBR_MAX_HYPS:
+        raise ValueError("rescore_method='MBR' is defined for beamk in 1..%d (beamk=%d)" % (L.MBR_MAX_HYPS, int(beamk)))
+    if int(vocab_size) > 65535:
+        raise ValueError("rescore_method='MBR': vocab_size=%d above 65535 (an n-gram key holds token + 1 in 16 bits per position)" % int(vocab_size))
+    if int(max_gen_length) < 1 or int(max_gen_length) + 1 > L.CAPTION_MAX_LEN:
+        raise ValueError("rescore_method='MBR' needs 1 <= max_gen_length and max_gen_length + 1 <= %d (max_gen_length=%d)"
+                         % (L.CAPTION_MAX_LEN, int(max_gen_length)))
+    try:
+        wc, wr = (float(x) for x in mbr_reward)
+        alpha = float(mbr_alpha)
+    except (TypeError, ValueError):
+        raise ValueError("mbr_reward=%r is (w_cider, w_rouge) and mbr_alpha=%r a number" % (mbr_reward, mbr_alpha))
+    if not all(x >= 0.0 and math.isfinite(x) for x in (wc, wr, alpha)):
+        raise ValueError("mbr_reward=%r and mbr_alpha=%r are finite numbers >= 0" % (mbr_reward, mbr_alpha))
+    if wc == 0.0 and wr == 0.0:
+        raise ValueError("mbr_reward=(0, 0): both weights are 0 (nothing to agree on)")
+    if getattr(mbr_corpus, "_checked_images", None) != mbr_corpus.images:
+        try:
+            mbr_corpus.check()
+        except L.SatHipError as e:
+            raise ValueError("rescore_method='MBR': %s" % e)
+    return wc, wr, alpha
+
+
 def _one_prefix(p, stoi):
     if isinstance(p, str):
         ids = []

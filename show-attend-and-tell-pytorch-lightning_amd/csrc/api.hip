@@ -255,6 +255,29 @@ int sat_beam_select(const int32_t* tok_in, const int32_t* prev_row, const int32_
     return beam_select(tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, fin_mean, alpha_hist, B, beamk, max_gen_length, L, rescore_method,
                        rescore_reward, pad_id, cap_tokens, cap_len, cap_score, cap_raw, cap_step, cap_alpha, (hipStream_t)stream);
 }
+int sat_beam_select_at(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row,
+                       const float* fin_score, const float* alpha_hist, const int32_t* pick, const double* pick_score, int32_t B, int32_t beamk,
+                       int32_t max_gen_length, int32_t L, int32_t pad_id, int32_t* cap_tokens, int32_t* cap_len, float* cap_score, float* cap_raw,
+                       int32_t* cap_step, float* cap_alpha, void* stream) {
+    if (!tok_in || !prev_row || !fin_count || !fin_step || !fin_row || !fin_score || !pick || !cap_tokens || !cap_len || !cap_score || !cap_raw || !cap_step)
+        return fail(SAT_EINVAL, "beam_select_at: null pointer");
+    if (cap_alpha && !alpha_hist) return fail(SAT_EINVAL, "beam_select_at: cap_alpha asked for without alpha_hist (null pointer)");
+    if (B < 1 || beamk < 1 || max_gen_length < 1 || (cap_alpha && L < 1))
+        return fail(SAT_EINVAL, "beam_select_at: non-positive size (B=%d beamk=%d max_gen_length=%d L=%d)", B, beamk, max_gen_length, L);
+    if (max_gen_length + 1 > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "beam_select_at: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length, SAT_CAPTION_MAX_LEN);
+    return beam_select_at(tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, alpha_hist, pick, pick_score, B, beamk, max_gen_length, L, pad_id,
+                          cap_tokens, cap_len, cap_score, cap_raw, cap_step, cap_alpha, (hipStream_t)stream);
+}
+int sat_beam_hypotheses(const int32_t* tok_in, const int32_t* prev_row, const int32_t* fin_count, const int32_t* fin_step, const int32_t* fin_row, int32_t B,
+                        int32_t beamk, int32_t max_gen_length, int32_t pad_id, int32_t* hyp_tokens, int32_t* hyp_len, void* stream) {
+    if (!tok_in || !prev_row || !fin_count || !fin_step || !fin_row || !hyp_tokens || !hyp_len) return fail(SAT_EINVAL, "beam_hypotheses: null pointer");
+    if (B < 1 || beamk < 1 || max_gen_length < 1)
+        return fail(SAT_EINVAL, "beam_hypotheses: non-positive size (B=%d beamk=%d max_gen_length=%d)", B, beamk, max_gen_length);
+    if (max_gen_length + 1 > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "beam_hypotheses: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length, SAT_CAPTION_MAX_LEN);
+    return beam_hypotheses(tok_in, prev_row, fin_count, fin_step, fin_row, B, beamk, max_gen_length, pad_id, hyp_tokens, hyp_len, (hipStream_t)stream);
+}
 static int check_caption_sizes(const char* what, int32_t cap_width, int32_t B, int32_t R, int32_t T) {
     if (B < 1 || R < 1 || T < 1 || cap_width < 1) return fail(SAT_EINVAL, "%s: non-positive size (B=%d R=%d T=%d cap_width=%d)", what, B, R, T, cap_width);
     if (R > SAT_CAPTION_MAX_REFS || T > SAT_CAPTION_MAX_LEN || cap_width > SAT_CAPTION_MAX_LEN)
@@ -310,6 +333,25 @@ int sat_caption_consensus(const int32_t* cap_tokens, const int32_t* cap_len, int
     if (!(sigma > 0.0)) return fail(SAT_EINVAL, "caption_consensus: sigma %g is not positive", sigma);
     return caption_consensus(cap_tokens, cap_len, cap_width, refs, ref_lengths, B, R, T, table, (long)capacity, (long)n_images, sigma, scores,
                              (hipStream_t)stream);
+}
+int sat_caption_mbr(const int32_t* hyp_tokens, const int32_t* hyp_len, const int32_t* hyp_count, const float* hyp_logp, int32_t B, int32_t K, int32_t width,
+                    const void* table, int64_t capacity, int64_t n_images, double sigma, double w_cider, double w_rouge, double alpha, double* utilities,
+                    int32_t* winner, void* stream) {
+    const double finite_max = 1.79769313486231570815e308;
+    if (!hyp_tokens || !hyp_len || !hyp_count || !utilities || !winner) return fail(SAT_EINVAL, "caption_mbr: null pointer");
+    SAT_TRY(check_table("caption_mbr", table, capacity));
+    if (B < 1 || K < 1 || width < 1) return fail(SAT_EINVAL, "caption_mbr: non-positive size (B=%d K=%d width=%d)", B, K, width);
+    if (K > SAT_MBR_MAX_HYPS || width > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "caption_mbr: over the limits (K=%d <= %d, width=%d <= %d)", K, SAT_MBR_MAX_HYPS, width, SAT_CAPTION_MAX_LEN);
+    if (n_images < 1) return fail(SAT_EINVAL, "caption_mbr: n_images %lld (the table holds no image)", (long long)n_images);
+    if (!(sigma > 0.0)) return fail(SAT_EINVAL, "caption_mbr: sigma %g is not positive", sigma);
+    if (!(w_cider >= 0.0) || w_cider > finite_max || !(w_rouge >= 0.0) || w_rouge > finite_max)
+        return fail(SAT_EINVAL, "caption_mbr: weights (%g, %g) are not finite numbers >= 0", w_cider, w_rouge);
+    if (w_cider == 0.0 && w_rouge == 0.0) return fail(SAT_EINVAL, "caption_mbr: both weights are 0 (nothing to agree on)");
+    if (!(alpha >= 0.0) || alpha > finite_max) return fail(SAT_EINVAL, "caption_mbr: alpha %g is not a finite number >= 0", alpha);
+    if (alpha != 0.0 && !hyp_logp) return fail(SAT_EINVAL, "caption_mbr: alpha %g needs hyp_logp (null pointer)", alpha);
+    return caption_mbr(hyp_tokens, hyp_len, hyp_count, hyp_logp, B, K, width, table, (long)capacity, (long)n_images, sigma, w_cider, w_rouge, alpha,
+                       utilities, winner, (hipStream_t)stream);
 }
 int sat_caption_chrf(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths, int32_t B,
                      int32_t R, int32_t T, const int32_t* word_offsets, const int32_t* word_chars, int32_t V, int32_t max_word_chars, double beta,

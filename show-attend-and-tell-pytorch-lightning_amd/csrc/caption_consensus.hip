@@ -22,41 +22,13 @@
 //                            match in the reference.  ROUGE-L: one wave per reference, the LCS row (<= 128 cells, two per lane) in
 //                            registers, one hypothesis token per step: new[j] = max over k <= j of (match ? old[k-1] + 1 : old[k]),
 //                            a wave prefix maximum.
+// The key packing, the hash, the plain-load probe, the n-gram weight and the wave LCS live in caption_ngram.h, shared with caption_mbr.hip.
 // Kernel launches only, no allocation, no host read: capturable.  Lengths read from device memory are clamped before they address
 // anything; the only other index that comes from memory is the hash, masked by the capacity.
-#include "caption_score.h"
-
-#include <math.h>
+#include "caption_ngram.h"
 
 namespace sat {
 namespace {
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// tokens as the keys see them: 1..65535 (0 is "no token")
-__device__ __forceinline__ int key_token(int tok) { return clampi(tok, 0, 65534) + 1; }
-
-__device__ __forceinline__ u64 pack_ngram(const int* g, int n) {
-    u64 k = 0;
-    for (int q = 0; q < n; ++q) k |= (u64)(unsigned)g[q] << (16 * q);
-    return k;
-}
-
-__device__ __forceinline__ bool same_ngram(const int* a, const int* b, int n) {
-    bool eq = true;
-    for (int q = 0; q < n; ++q) eq = eq && (a[q] == b[q]);
-    return eq;
-}
-
-// murmur3's 64-bit finaliser
-__device__ __forceinline__ u64 hash_key(u64 k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL;
-    k ^= k >> 33;
-    return k;
-}
 
 __global__ __launch_bounds__(256) void ngram_table_clear_kernel(u64* __restrict__ keys, unsigned* __restrict__ counts, long capacity) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < capacity; i += (long)gridDim.x * 256) { keys[i] = 0; counts[i] = 0; }
@@ -106,12 +78,6 @@ __global__ __launch_bounds__(256) void ngram_table_add_kernel(const int* __restr
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // v[k] of thread t belongs to order (t >> 7) + 2 k: out[n] = the sum over the two waves that own order n, every thread gets all four
 __device__ __forceinline__ void order_sums(const double (&v)[2], double (*s_red)[2], double (&out)[4]) {
     const double a = wave_sum_f64(v[0]), c = wave_sum_f64(v[1]);
@@ -120,43 +86,6 @@ __device__ __forceinline__ void order_sums(const double (&v)[2], double (*s_red)
 #pragma unroll
     for (int n = 0; n < 4; ++n) out[n] = s_red[2 * (n & 1)][n >> 1] + s_red[2 * (n & 1) + 1][n >> 1];
     __syncthreads();
-}
-
-// document frequency of `key`: plain loads, the table is complete
-__device__ __forceinline__ unsigned table_lookup(const u64* __restrict__ keys, const unsigned* __restrict__ counts, long capacity, u64 key) {
-    const u64 mask = (u64)capacity - 1;
-    u64 slot = hash_key(key) & mask;
-    for (long probe = 0; probe < capacity; ++probe) {
-        const u64 k = keys[slot];
-        if (k == key) return counts[slot];
-        if (k == 0ULL) return 0u;
-        slot = (slot + 1) & mask;
-    }
-    return 0u;
-}
-
-// weight of the n-gram at position i of seq[0..len): tf * (log N - log max(1, df)) at its first occurrence (`first`), else 0
-__device__ __forceinline__ double ngram_weight(const int* seq, int len, int i, int n, const u64* __restrict__ keys,
-                                               const unsigned* __restrict__ counts, long capacity, double log_n, bool& first) {
-    first = false;
-    if (i + n > len) return 0.0;
-    const int* g = seq + i;
-    for (int j = 0; j < i; ++j)
-        if (same_ngram(seq + j, g, n)) return 0.0;
-    first = true;
-    int tf = 1;
-    for (int j = i + 1; j + n <= len; ++j) tf += same_ngram(seq + j, g, n) ? 1 : 0;
-    const unsigned df = table_lookup(keys, counts, capacity, pack_ngram(g, n));
-    return (double)tf * (log_n - log(df > 1u ? (double)df : 1.0));
-}
-
-__device__ __forceinline__ int wave_prefix_max(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v = t > v ? t : v;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(256) void caption_consensus_kernel(const int* __restrict__ cap_tokens, const int* __restrict__ cap_len, int W,
@@ -181,19 +110,7 @@ __global__ __launch_bounds__(256) void caption_consensus_kernel(const int* __res
 
     // ROUGE-L: wave w takes the references w, w + 4, ...; lane l holds the cells j = l and j = 64 + l of the LCS row
     for (int r = wave; r < R; r += 4) {
-        const int rl = s_rl[r];
-        const int t0 = lane < rl ? s_ref[r * T + lane] : -1, t1 = 64 + lane < rl ? s_ref[r * T + 64 + lane] : -1;      // -1 matches nothing
-        int c0 = 0, c1 = 0;
-        for (int i = 0; i < H; ++i) {
-            const int h = s_hyp[i];
-            const int u0 = __shfl_up(c0, 1, 64), u1 = __shfl_up(c1, 1, 64), e0 = __shfl(c0, 63, 64);
-            const int d0 = lane ? u0 : 0, d1 = lane ? u1 : e0;                 // the old row one cell to the left
-            const int p0 = wave_prefix_max(h == t0 ? d0 + 1 : c0, lane);
-            const int p1 = wave_prefix_max(h == t1 ? d1 + 1 : c1, lane);
-            const int top = __shfl(p0, 63, 64);
-            c0 = p0; c1 = p1 > top ? p1 : top;
-        }
-        const int lcs = __shfl(c1, 63, 64);            // cells beyond the reference's end never match: the last cell holds the result
+        const int lcs = wave_lcs(s_hyp, H, s_ref + r * T, s_rl[r], lane);
         if (lane == 0) s_lcs[r] = lcs;
     }
 

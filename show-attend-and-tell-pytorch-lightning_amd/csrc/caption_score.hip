@@ -6,6 +6,8 @@
 //                          first maximum in append order (list.index(max(...))), walk the parent rows from the step it ended at
 //                          down to step 1 (at most max_gen_length + 1 dependent loads, one lane) and gather its tokens and,
 //                          when asked, its attention maps.
+//   beam_select_at_kernel  the same back-trace and gather (beam_trace_gather) for a winner the caller names (consensus reranking).
+//   beam_hypotheses_kernel one thread per (image, finished slot): the back-trace of every finished hypothesis, tokens only.
 //   caption_stats_kernel   one workgroup per image: the integers nltk's corpus BLEU and GLEU sum per segment (metrics.py is the
 //                          specification).  Hypothesis and references are staged in LDS; one thread per (order n, hypothesis
 //                          position i): if i is the first occurrence of its n-gram in the hypothesis it counts the n-gram in the
@@ -28,6 +30,38 @@ namespace {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The back-trace and the gather of hypothesis `bi` of image b (-1: none, an empty caption), shared by beam_select_kernel and
+// beam_select_at_kernel; called by the whole workgroup, `bv` is the score thread 0 reports.
+__device__ __forceinline__ void beam_trace_gather(const int* __restrict__ tok_in, const int* __restrict__ prev_row, const int* __restrict__ fin_step,
+                                                  const int* __restrict__ fin_row, const float* __restrict__ fin_score,
+                                                  const float* __restrict__ alpha_hist, int B, int K, int S, int L, int pad_id, int b, int bi, float bv,
+                                                  int* __restrict__ cap_tokens, int* __restrict__ cap_len, float* __restrict__ cap_score,
+                                                  float* __restrict__ cap_raw, int* __restrict__ cap_step, float* __restrict__ cap_alpha, int* s_rows,
+                                                  int* s_step) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int step = 0, cur = 0; float raw = 0.f;
+        if (bi >= 0) { step = clampi(fin_step[b * K + bi], 0, S); cur = clampi(fin_row[b * K + bi], 0, K - 1); raw = fin_score[b * K + bi]; }
+        for (int s = step; s >= 0; --s) {
+            s_rows[s] = cur;
+            if (s > 0) cur = clampi(prev_row[((long)s * B + b) * K + cur], 0, K - 1);
+        }
+        *s_step = step;
+        cap_len[b] = step; cap_step[b] = step; cap_score[b] = bv; cap_raw[b] = raw;
+    }
+    __syncthreads();
+    const int step = *s_step, W = S + 1;
+    // tokens fed at steps 1..step (top_preds[:, i][1:-1], model.py:412): without START and without the last prediction
+    for (int j = tid; j < W; j += 256)
+        cap_tokens[(long)b * W + j] = j < step ? tok_in[((long)(j + 1) * B + b) * K + s_rows[j + 1]] : pad_id;
+    if (cap_alpha) {                                   // maps of steps 0..step-1 (alphas[:, i][1:-1], model.py:413), zero beyond
+        for (int idx = tid; idx < S * L; idx += 256) {
+            const int s = idx / L, l = idx - s * L;
+            cap_alpha[(long)b * S * L + idx] = s < step ? alpha_hist[(((long)s * B + b) * K + s_rows[s]) * L + l] : 0.f;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void beam_select_kernel(const int* __restrict__ tok_in, const int* __restrict__ prev_row, const int* __restrict__ fin_count,
                                                           const int* __restrict__ fin_step, const int* __restrict__ fin_row,
                                                           const float* __restrict__ fin_score, const float* __restrict__ fin_mean,
@@ -37,9 +71,9 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const int* __restrict_
     __shared__ int s_rows[kCaptionMaxLen];
     __shared__ int s_step;
     const int b = blockIdx.x, tid = threadIdx.x;
+    float bv = 0.f; int bi = -1;
     if (tid < 64) {
         const int fc = clampi(fin_count[b], 0, K);
-        float bv = 0.f; int bi = -1;
         for (int f = tid; f < fc; f += 64) {
             const float s = fin_score[b * K + f];
             const float stepf = (float)fin_step[b * K + f];
@@ -54,29 +88,51 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const int* __restrict_
             const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
             if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
         }
-        if (tid == 0) {
-            int step = 0, cur = 0; float raw = 0.f;
-            if (bi >= 0) { step = clampi(fin_step[b * K + bi], 0, S); cur = clampi(fin_row[b * K + bi], 0, K - 1); raw = fin_score[b * K + bi]; }
-            else bv = -INFINITY;                       // no finished hypothesis (cannot happen for max_gen_length >= 1): an empty caption
-            for (int s = step; s >= 0; --s) {
-                s_rows[s] = cur;
-                if (s > 0) cur = clampi(prev_row[((long)s * B + b) * K + cur], 0, K - 1);
-            }
-            s_step = step;
-            cap_len[b] = step; cap_step[b] = step; cap_score[b] = bv; cap_raw[b] = raw;
-        }
+        if (bi < 0) bv = -INFINITY;                    // no finished hypothesis (cannot happen for max_gen_length >= 1): an empty caption
     }
-    __syncthreads();
-    const int step = s_step, W = S + 1;
-    // tokens fed at steps 1..step (top_preds[:, i][1:-1], model.py:412): without START and without the last prediction
-    for (int j = tid; j < W; j += 256)
-        cap_tokens[(long)b * W + j] = j < step ? tok_in[((long)(j + 1) * B + b) * K + s_rows[j + 1]] : pad_id;
-    if (cap_alpha) {                                   // maps of steps 0..step-1 (alphas[:, i][1:-1], model.py:413), zero beyond
-        for (int idx = tid; idx < S * L; idx += 256) {
-            const int s = idx / L, l = idx - s * L;
-            cap_alpha[(long)b * S * L + idx] = s < step ? alpha_hist[(((long)s * B + b) * K + s_rows[s]) * L + l] : 0.f;
-        }
+    beam_trace_gather(tok_in, prev_row, fin_step, fin_row, fin_score, alpha_hist, B, K, S, L, pad_id, b, bi, bv, cap_tokens, cap_len, cap_score, cap_raw,
+                      cap_step, cap_alpha, s_rows, &s_step);
+}
+
+// sat_beam_select with the winner given: pick[b] clamped into the finished hypotheses of image b
+__global__ __launch_bounds__(256) void beam_select_at_kernel(const int* __restrict__ tok_in, const int* __restrict__ prev_row, const int* __restrict__ fin_count,
+                                                             const int* __restrict__ fin_step, const int* __restrict__ fin_row,
+                                                             const float* __restrict__ fin_score, const float* __restrict__ alpha_hist,
+                                                             const int* __restrict__ pick, const double* __restrict__ pick_score, int B, int K, int S, int L,
+                                                             int pad_id, int* __restrict__ cap_tokens, int* __restrict__ cap_len, float* __restrict__ cap_score,
+                                                             float* __restrict__ cap_raw, int* __restrict__ cap_step, float* __restrict__ cap_alpha) {
+    __shared__ int s_rows[kCaptionMaxLen];
+    __shared__ int s_step;
+    const int b = blockIdx.x;
+    float bv = 0.f; int bi = -1;
+    if (threadIdx.x == 0) {
+        const int fc = clampi(fin_count[b], 0, K);
+        const int p = clampi(pick[b], 0, fc > 0 ? fc - 1 : 0);
+        if (fc > 0) bi = p;
+        if (pick_score) bv = (float)pick_score[b * K + p];
+        else bv = bi >= 0 ? fin_score[b * K + bi] : -INFINITY;         // no finished hypothesis: as beam_select_kernel
     }
+    beam_trace_gather(tok_in, prev_row, fin_step, fin_row, fin_score, alpha_hist, B, K, S, L, pad_id, b, bi, bv, cap_tokens, cap_len, cap_score, cap_raw,
+                      cap_step, cap_alpha, s_rows, &s_step);
+}
+
+// every finished hypothesis of every image: one thread per (image, finished slot) walks the parent rows from the step the hypothesis
+// ended at down to step 1, as beam_trace_gather does for the winner, and writes the token of every step on the way
+__global__ __launch_bounds__(256) void beam_hypotheses_kernel(const int* __restrict__ tok_in, const int* __restrict__ prev_row, const int* __restrict__ fin_count,
+                                                              const int* __restrict__ fin_step, const int* __restrict__ fin_row, int B, int K, int S,
+                                                              int pad_id, int* __restrict__ hyp_tokens, int* __restrict__ hyp_len) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)B * K) return;
+    const int b = (int)(idx / K), f = (int)(idx - (long)b * K), W = S + 1;
+    int step = 0, cur = 0;
+    if (f < clampi(fin_count[b], 0, K)) { step = clampi(fin_step[idx], 0, S); cur = clampi(fin_row[idx], 0, K - 1); }
+    int* out = hyp_tokens + idx * W;
+    for (int j = W - 1; j >= step; --j) out[j] = pad_id;
+    for (int s = step; s >= 1; --s) {
+        out[s - 1] = tok_in[((long)s * B + b) * K + cur];
+        cur = clampi(prev_row[((long)s * B + b) * K + cur], 0, K - 1);
+    }
+    hyp_len[idx] = step;
 }
 
 __device__ __forceinline__ bool same_ngram(const int* a, const int* b, int n) {
@@ -230,6 +286,22 @@ int beam_select(const int* tok_in, const int* prev_row, const int* fin_count, co
     hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, st, tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, fin_mean, alpha_hist, B, K, S,
                        L, method, reward, pad_id, cap_tokens, cap_len, cap_score, cap_raw, cap_step, cap_alpha);
     return launch_ok("beam_select");
+}
+
+int beam_select_at(const int* tok_in, const int* prev_row, const int* fin_count, const int* fin_step, const int* fin_row, const float* fin_score,
+                   const float* alpha_hist, const int* pick, const double* pick_score, int B, int K, int S, int L, int pad_id, int* cap_tokens, int* cap_len,
+                   float* cap_score, float* cap_raw, int* cap_step, float* cap_alpha, hipStream_t st) {
+    hipLaunchKernelGGL(beam_select_at_kernel, dim3(B), dim3(256), 0, st, tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, alpha_hist, pick,
+                       pick_score, B, K, S, L, pad_id, cap_tokens, cap_len, cap_score, cap_raw, cap_step, cap_alpha);
+    return launch_ok("beam_select_at");
+}
+
+int beam_hypotheses(const int* tok_in, const int* prev_row, const int* fin_count, const int* fin_step, const int* fin_row, int B, int K, int S, int pad_id,
+                    int* hyp_tokens, int* hyp_len, hipStream_t st) {
+    const long n = (long)B * K;
+    hipLaunchKernelGGL(beam_hypotheses_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tok_in, prev_row, fin_count, fin_step, fin_row, B, K, S,
+                       pad_id, hyp_tokens, hyp_len);
+    return launch_ok("beam_hypotheses");
 }
 
 int caption_stats(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, int* stats, hipStream_t st) {

@@ -19,6 +19,11 @@ specification).  The document frequency of every 1..4-gram of a split's referenc
 Opt-in, ``chrf=VocabChars``: chrF (csrc/caption_chrf.hip; ``metrics.chrf`` is the specification), the one metric here that looks inside
 words.  The vocabulary's spelling is put on the device once (``VocabChars``); ``chrf_scores`` scores a batch over the characters of its
 tokens in one launch, and the same three carry the sum along.  Without ``chrf`` nothing changes.
+
+Opt-in, ``rescore_method="MBR"`` with ``mbr_corpus=ReferenceCorpus``: consensus reranking of the finished beam (csrc/caption_mbr.hip;
+``metrics.consensus_utilities`` is the specification).  ``finished_hypotheses`` traces every finished hypothesis back on the device,
+``consensus_utilities`` scores them against each other, ``select_hypotheses`` gathers the winner: three launches, no host read.  The
+reference's four rules (None / "LN" / "WR" / "BAR") stay on ``sat_beam_select``.
 """
 import numpy as np
 import torch
@@ -36,18 +41,67 @@ NOTEBOOK_SPACE = dict(beamks=[5, 20], temperatures=(0.7, 1.2), sample_methods=["
                       rescore_methods=["LN", "BAR"], rescore_rewards=(0.6, 1.3), max_gen_length=32)
 
 
-def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, with_alpha=False):
-    """``sat_beam_select`` on the buffers ``SATDecoder._beam_search_device`` returns: the best hypothesis of every image as
-    ``dict(tokens (B, S + 1) int32 padded with pad_id, lengths (B) int32, scores (B) rescored, raw (B), steps (B), alphas (B, S, L) or None)``."""
-    if rescore_method not in L.RESCORE:
-        raise ValueError("rescore_method=%r (None, 'LN', 'WR', 'BAR')" % (rescore_method,))
-    tok_in, alpha_hist = buffers["tok_in"], buffers["alpha_hist"]
+def finished_hypotheses(buffers, pad_id):
+    """``sat_beam_hypotheses`` on the buffers ``SATDecoder._beam_search_device`` returns: the back-trace of EVERY finished hypothesis
+    on the device, ``(hyp_tokens (B, beamk, S + 1) int32 padded with pad_id, hyp_len (B, beamk) int32)`` in append order; the slots
+    beyond ``fin_count`` are empty.  One launch, no host read."""
+    tok_in = buffers["tok_in"]
     L.require_gpu(tok_in)
+    S, (B, K) = tok_in.shape[0] - 2, tok_in.shape[1:]
+    hyp_tokens = torch.empty(B, K, S + 1, dtype=torch.int32, device=tok_in.device)
+    hyp_len = torch.empty(B, K, dtype=torch.int32, device=tok_in.device)
+    L.check(L.lib().sat_beam_hypotheses(L.ptr(tok_in), L.ptr(buffers["prev_row"]), L.ptr(buffers["fin_count"]), L.ptr(buffers["fin_step"]),
+                                        L.ptr(buffers["fin_row"]), B, K, S, int(pad_id), L.ptr(hyp_tokens), L.ptr(hyp_len), L.stream_ptr()),
+            "sat_beam_hypotheses")
+    return hyp_tokens, hyp_len
+
+
+def consensus_utilities(hyp_tokens, hyp_len, counts, logp, corpus, reward=(1.0, 0.0), alpha=0.0, sigma=6.0):
+    """``sat_caption_mbr``: ``(utilities (B, K) float64, winner (B) int32)`` on the device of the hypotheses ``hyp_tokens (B, K, W)`` /
+    ``hyp_len (B, K)`` / ``counts (B)`` (int32) with raw scores ``logp (B, K)`` float32 (``None`` goes with ``alpha=0``), against the
+    document frequencies of ``corpus``; ``metrics.consensus_utilities`` is the specification.  One launch, no host read."""
+    L.require_gpu(hyp_tokens, hyp_len, counts)
+    for t in (hyp_tokens, hyp_len, counts):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    if logp is not None:
+        L.require_gpu(logp)
+        assert logp.dtype == torch.float32 and logp.is_contiguous()
+    if corpus.images < 1 or corpus._table is None:
+        raise ValueError("consensus_utilities: the corpus holds no image (ReferenceCorpus.add)")
+    B, K, W = hyp_tokens.shape
+    utilities = torch.empty(B, K, dtype=torch.float64, device=hyp_tokens.device)
+    winner = torch.empty(B, dtype=torch.int32, device=hyp_tokens.device)
+    L.check(L.lib().sat_caption_mbr(L.ptr(hyp_tokens), L.ptr(hyp_len), L.ptr(counts), L.ptr(logp), B, K, W, L.ptr(corpus._table), corpus.capacity,
+                                    corpus.images, float(sigma), float(reward[0]), float(reward[1]), float(alpha), L.ptr(utilities), L.ptr(winner),
+                                    L.stream_ptr()), "sat_caption_mbr")
+    return utilities, winner
+
+
+def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, with_alpha=False, mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
+    """``sat_beam_select`` on the buffers ``SATDecoder._beam_search_device`` returns: the best hypothesis of every image as
+    ``dict(tokens (B, S + 1) int32 padded with pad_id, lengths (B) int32, scores (B) rescored, raw (B), steps (B), alphas (B, S, L) or None)``.
+    ``rescore_method="MBR"``: consensus reranking against ``mbr_corpus`` (``sat_beam_hypotheses`` -> ``sat_caption_mbr`` ->
+    ``sat_beam_select_at``, three launches and no host read); ``scores`` is then the winner's utility."""
+    tok_in, alpha_hist = buffers["tok_in"], buffers["alpha_hist"]
     S, (B, K), Lc = tok_in.shape[0] - 2, tok_in.shape[1:], alpha_hist.shape[-1]
+    mbr = constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, K, 1, S)      # the caller's vocabulary built the corpus
+    if mbr is None and rescore_method not in L.RESCORE:
+        raise ValueError("rescore_method=%r (None, 'LN', 'WR', 'BAR', 'MBR')" % (rescore_method,))
+    L.require_gpu(tok_in)
     dev = tok_in.device
     i32 = dict(dtype=torch.int32, device=dev); f32 = dict(dtype=torch.float32, device=dev)
     out = dict(tokens=torch.empty(B, S + 1, **i32), lengths=torch.empty(B, **i32), scores=torch.empty(B, **f32), raw=torch.empty(B, **f32),
                steps=torch.empty(B, **i32), alphas=torch.empty(B, S, Lc, **f32) if with_alpha else None)
+    if mbr is not None:
+        hyp_tokens, hyp_len = finished_hypotheses(buffers, pad_id)
+        utilities, winner = consensus_utilities(hyp_tokens, hyp_len, buffers["fin_count"], buffers["fin_score"], mbr_corpus, mbr[:2], mbr[2])
+        L.check(L.lib().sat_beam_select_at(L.ptr(tok_in), L.ptr(buffers["prev_row"]), L.ptr(buffers["fin_count"]), L.ptr(buffers["fin_step"]),
+                                           L.ptr(buffers["fin_row"]), L.ptr(buffers["fin_score"]), L.ptr(alpha_hist) if with_alpha else None,
+                                           L.ptr(winner), L.ptr(utilities), B, K, S, Lc, int(pad_id), L.ptr(out["tokens"]), L.ptr(out["lengths"]),
+                                           L.ptr(out["scores"]), L.ptr(out["raw"]), L.ptr(out["steps"]), L.ptr(out["alphas"]), L.stream_ptr()),
+                "sat_beam_select_at")
+        out.update(hyp_tokens=hyp_tokens, hyp_len=hyp_len, utilities=utilities, winner=winner)
+        return out
     L.check(L.lib().sat_beam_select(L.ptr(tok_in), L.ptr(buffers["prev_row"]), L.ptr(buffers["fin_count"]), L.ptr(buffers["fin_step"]),
                                     L.ptr(buffers["fin_row"]), L.ptr(buffers["fin_score"]), L.ptr(buffers["fin_mean"]),
                                     L.ptr(alpha_hist) if with_alpha else None, B, K, S, Lc, L.RESCORE[rescore_method], float(rescore_reward), int(pad_id),
@@ -58,14 +112,19 @@ def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, 
 
 @torch.no_grad()
 def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                   rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
+                   mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None):
     """``SAT.caption(..., return_all=False)`` with the result left on the device: ``(tokens (B, max_gen_length + 1) int32 padded with
     <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises.
     ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``); ``sample_topp`` belongs to
     ``sample_method="nucleus"``; ``sample_method="ancestral"`` (``beamk=1``, no constraint, no graph) is pure sampling;
-    ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` are the history rules ("History rules")."""
+    ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` are the history rules ("History rules").
+    ``rescore_method="MBR"`` with ``mbr_corpus`` (``corpus`` when that is None) / ``mbr_reward`` / ``mbr_alpha``: consensus reranking
+    ("Consensus reranking"); ``scores`` is then the utility.  Launches only, like the rest."""
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
+    mbr_corpus = corpus if mbr_corpus is None else mbr_corpus
+    constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, model.hp.vocab_size, max_gen_length)      # refuse before any launch
     con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
                repetition_penalty=repetition_penalty)
     constraints.check_ancestral(str(sample_method), beamk, graph, **con)
@@ -74,7 +133,7 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     ann_bld, _ = model.encode(img)
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
                                   graph, sample_topp=sample_topp, **con)
-    sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward)
+    sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha)
     ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
     return sel["tokens"], sel["lengths"], sel["scores"], ppl
 
@@ -125,6 +184,7 @@ class ReferenceCorpus:
         self.vocab_size, self.device, self.images = int(vocab_size), torch.device(device), 0
         self.capacity = int(capacity) if capacity is not None else _pow2_at_least(2 * int(expected_positions or self.DEFAULT_POSITIONS))
         self._table = self._flag = None
+        self._checked_images = None            # the image count at the last check() that passed
 
     def _allocate(self):
         if self.device.type != "cuda":
@@ -179,6 +239,7 @@ class ReferenceCorpus:
         if self._flag is not None and int(self._flag.item()) != 0:
             raise L.SatHipError("ReferenceCorpus: the table overflowed (capacity %d): document frequencies are incomplete; "
                                 "rebuild with a larger capacity" % self.capacity)
+        self._checked_images = self.images
         return self
 
     def to_dict(self):
@@ -329,16 +390,18 @@ class CaptionStats:
 @torch.no_grad()
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                     rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
-                    sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                    sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None,
+                    mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
     """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
     with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue, with ``chrf`` (a ``VocabChars``) chrF
     with ``chrf_beta``.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search, ``no_repeat_ngram`` / ``min_length`` /
-    ``repetition_penalty`` are its history rules (``SATDecoder.beam_decode_batched``)."""
+    ``repetition_penalty`` are its history rules (``SATDecoder.beam_decode_batched``).  ``rescore_method="MBR"`` reranks by consensus
+    against ``mbr_corpus`` (``corpus`` when that is None) with ``mbr_reward`` / ``mbr_alpha``."""
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
     tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                                           rescore_method, rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram,
-                                          min_length, repetition_penalty)
+                                          min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus)
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())
@@ -355,8 +418,8 @@ def evaluate(model, loader, max_batches=None, seed=None, corpus=None, chrf=None,
     ``seed``: batch i of a sampled search draws with ``seed + i``.  ``corpus`` (a ``ReferenceCorpus``): both dicts gain "cider" and
     "rouge_l" (means over images), ``chrf`` (a ``VocabChars``; ``chrf_beta`` travels in ``decode``): both gain "chrf"; still one host
     read.  ``decode`` takes every keyword of ``val_batch_stats``, the search constraints
-    ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` and the history rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``
-    among them."""
+    ``topg`` / ``prefix`` / ``banned`` / ``no_unk``, the history rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` and
+    ``rescore_method="MBR"`` with ``mbr_corpus`` (``corpus`` when that is None) / ``mbr_reward`` / ``mbr_alpha`` among them."""
     if corpus is not None:
         decode["corpus"] = corpus
     if chrf is not None:
@@ -396,14 +459,22 @@ def draw_decode_params(rs, space=NOTEBOOK_SPACE):
     return row
 
 
-def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4, corpus=None, chrf=None, chrf_beta=3.0):
+def random_search(model, loader, trials, space=NOTEBOOK_SPACE, seed=None, max_batches=4, corpus=None, chrf=None, chrf_beta=3.0, mbr_corpus=None,
+                  mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
     """evaluate.ipynb's random search: ``trials`` draws from one ``np.random.RandomState(seed)``, each scored over the first
     ``max_batches`` batches.  Rows carry the notebook's 13 columns (the metrics are its batch means) plus ``<metric>_corpus``; with
     ``corpus`` (a ``ReferenceCorpus``, built once and reused by every trial) also cider, rouge_l, cider_corpus, rouge_l_corpus; with
-    ``chrf`` (a ``VocabChars``, likewise) also chrf and chrf_corpus; with ``space["topgs"]`` also a ``topg`` column (``draw_decode_params``)."""
+    ``chrf`` (a ``VocabChars``, likewise) also chrf and chrf_corpus; with ``space["topgs"]`` also a ``topg`` column (``draw_decode_params``).
+    ``"MBR"`` may stand in ``space["rescore_methods"]`` when ``mbr_corpus`` (or ``corpus``) is given: such a trial reranks by consensus
+    with ``mbr_reward`` / ``mbr_alpha`` (its drawn ``rescore_reward`` is unused).  Without ``"MBR"`` in the space nothing changes."""
+    with_mbr = "MBR" in list(space["rescore_methods"])
+    if with_mbr and mbr_corpus is None and corpus is None:
+        raise ValueError("random_search: 'MBR' in space['rescore_methods'] needs mbr_corpus (or corpus)")
     rs = np.random.RandomState(seed)
     rows = []
     extra = {} if corpus is None else {"corpus": corpus}
+    if with_mbr:
+        extra.update(mbr_corpus=mbr_corpus if mbr_corpus is not None else corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha)
     if chrf is not None:
         extra.update(chrf=chrf, chrf_beta=chrf_beta)
     for trial in range(int(trials)):

@@ -198,6 +198,50 @@ def rouge_l(references, hypothesis, beta=1.2):
     return 0.0
 
 
+# ----------------------------------------------------------------------------- consensus (minimum-Bayes-risk) reranking
+# The captioning literature's way to choose among the finished hypotheses of a beam (Devlin et al. 2015; MBR decoding in MT): keep the
+# one that agrees most with the others under the metric the captions are evaluated on.  The specification of sat_caption_mbr
+# (csrc/caption_mbr.hip): the two functions above with "the references" of hypothesis i being one other hypothesis j at a time.
+
+def consensus_utilities(hyps, logps, df, n_images, reward=(1.0, 0.0), alpha=0.0, sigma=6.0):
+    """``U_i`` of every hypothesis of ONE image (token lists without START / END, in append order; ``logps`` their raw scores):
+
+        gain(i|j) = wc * cider_d([[h_j]], [h_i])[0] + wr * rouge_l([h_j], h_i)      a weight of 0 skips its term
+        q_j       = exp(alpha * (s_j - max_k s_k))                                 alpha = 0: every q_j = 1 (uniform consensus)
+        U_i       = (sum_{j != i} q_j * gain(i|j)) / (sum_{j != i} q_j)            j ascending; 0 when the denominator is 0 (F = 1)
+
+    with the document frequencies ``df`` of a corpus of ``n_images`` images.  The winner is the first maximum:
+    ``u.index(max(u))``."""
+    wc, wr, alpha = float(reward[0]), float(reward[1]), float(alpha)
+    for x in (wc, wr, alpha):
+        if not (x >= 0.0 and x < math.inf):
+            raise ValueError("consensus_utilities: weights and alpha are finite numbers >= 0 (reward=%r alpha=%r)" % (reward, alpha))
+    if wc == 0.0 and wr == 0.0:
+        raise ValueError("consensus_utilities: both weights are 0 (nothing to agree on)")
+    F = len(hyps)
+    if alpha != 0.0:
+        assert len(logps) == F, "one raw score per hypothesis"
+        top = max(float(s) for s in logps) if F else 0.0
+        q = [math.exp(alpha * (float(s) - top)) for s in logps]
+    else:
+        q = [1.0] * F
+    out = []
+    for i in range(F):
+        num = den = 0.0
+        for j in range(F):
+            if j == i:
+                continue
+            gain = 0.0
+            if wc != 0.0:
+                gain = gain + wc * cider_d([[hyps[j]]], [hyps[i]], df=df, n_images=n_images, sigma=sigma)[0]
+            if wr != 0.0:
+                gain = gain + wr * rouge_l([hyps[j]], hyps[i])
+            num += q[j] * gain
+            den += q[j]
+        out.append(num / den if den != 0.0 else 0.0)
+    return out
+
+
 # ----------------------------------------------------------------------------- chrF: character n-gram F-score
 # chrF (Popovic 2015) as nltk's ``chrf_score.py`` computes it (``sentence_chrf`` / ``corpus_chrf`` with ``min_len=1, max_len=6,
 # beta=3.0, ignore_whitespace=True``): restated over lists of word strings, nltk being absent here.  It is the specification of

@@ -180,6 +180,8 @@ class SATDecoder(nn.Module):
         import ctypes as C
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
+        if rescore_method == "MBR":
+            raise ValueError("rescore_method='MBR' (consensus reranking) runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         if sample_method == "ancestral":
             raise ValueError("sample_method='ancestral' runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         multinomial = multinomial or torch.multinomial
@@ -455,7 +457,8 @@ class SATDecoder(nn.Module):
     @torch.no_grad()
     def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
                             return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False,
-                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
+                            mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
         """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
         (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
         completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
@@ -479,8 +482,13 @@ class SATDecoder(nn.Module):
         History rules ("History rules"), in the same call and with every method but "ancestral": ``repetition_penalty``
         theta (CTRL) divides the positive and multiplies the negative raw logits of the words a hypothesis has already said,
         ``min_length`` keeps <END> masked until a caption has that many words, ``no_repeat_ngram=n`` masks every word that would say an
-        n-gram of the hypothesis a second time.  Forced prefix words count as history but are obeyed.  Eager, like the constraints."""
+        n-gram of the hypothesis a second time.  Forced prefix words count as history but are obeyed.  Eager, like the constraints.
+        ``rescore_method="MBR"`` ("Consensus reranking"): the finished hypotheses of an image are scored against each other
+        on the device (``mbr_reward`` = the weights of CIDEr-D and ROUGE-L with the document frequencies of ``mbr_corpus``, an
+        ``evaluation.ReferenceCorpus``; ``mbr_alpha`` weighs a hypothesis's vote by exp(alpha * (its raw score - the best))); the
+        returned scores are the utilities, the captions come from the device back-trace, ``return_all`` orders by utility."""
         import numpy as np
+        mbr = constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, self.embedding.weight.shape[0], max_gen_length)
         o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
                                      topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length, repetition_penalty)
         B = ann_bld.shape[0]
@@ -488,6 +496,11 @@ class SATDecoder(nn.Module):
         K, S = int(beamk), int(max_gen_length)
         tok_in, prev_row, alpha_hist = o["tok_in"], o["prev_row"], o["alpha_hist"]
         fin_count, fin_step, fin_row, fin_score, fin_mean = o["fin_count"], o["fin_step"], o["fin_row"], o["fin_score"], o["fin_mean"]
+        if mbr is not None:                        # three launches behind the search; read with everything else below
+            from . import evaluation
+            hyp_tokens, hyp_len = evaluation.finished_hypotheses(o, self.pad_idx)
+            utilities, _ = evaluation.consensus_utilities(hyp_tokens, hyp_len, fin_count, fin_score, mbr_corpus, mbr[:2], mbr[2])
+            hyp_tokens, utilities = hyp_tokens.cpu().numpy(), utilities.cpu().numpy()
         tok_in, prev_row = tok_in.cpu().numpy(), prev_row.cpu().numpy()
         alpha_np = alpha_hist.cpu().numpy()
         fin_count, fin_step, fin_row = fin_count.cpu().numpy(), fin_step.cpu().numpy(), fin_row.cpu().numpy()
@@ -512,6 +525,8 @@ class SATDecoder(nn.Module):
             resc = fin_score[bidx, fidx] + rescore_reward * torch.from_numpy(hstep).float()
         elif rescore_method == "BAR":
             resc = fin_score[bidx, fidx] + rescore_reward * (-fin_mean[bidx, fidx])
+        elif mbr is not None:
+            resc = torch.from_numpy(utilities[bidx, fidx])
         else:
             resc = fin_score[bidx, fidx]
         ppl_all = torch.exp(-fin_score[bidx, fidx] / torch.from_numpy(hstep).float())
@@ -523,12 +538,14 @@ class SATDecoder(nn.Module):
             for f in range(int(fin_count[b])):
                 hh, step = hpos + f, int(hstep[hpos + f])
                 # top_preds[:, i][1:-1] / alphas[:, i][1:-1] (model.py:412-413): without START / the zero map and without the last step
-                fin_caps.append(toks_all[1:step + 1, hh].tolist())
+                fin_caps.append(toks_all[1:step + 1, hh].tolist() if mbr is None else hyp_tokens[b, f, :step].tolist())
                 fin_alphas.append(als_all[:step, hh].reshape(-1, Hh, Ww).clone())
                 fin_scores.append(resc[hh]); fin_ppl.append(ppl_all[hh])
             hpos += int(fin_count[b])
             if return_all:
                 order = [i for _, i in sorted([[fin_scores[i], i] for i in range(len(fin_scores))], reverse=True)]
+                if mbr is not None:                # utility descending, append order among equals
+                    order = sorted(range(len(fin_scores)), key=lambda i: -fin_scores[i])
                 captions.append([fin_caps[i] for i in order]); cap_alphas.append([fin_alphas[i] for i in order])
                 cap_scores.append([fin_scores[i] for i in order]); cap_ppl.append([fin_ppl[i] for i in order])
             else:
@@ -640,16 +657,18 @@ class SAT(SATDecoder, _Base):
     @torch.no_grad()
     def caption(self, img_tensor, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
                 decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False,
-                sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
-        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` / ``sample_topp`` and the history
-        rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``: ``beam_decode_batched``."""
+                sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
+        """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` / ``sample_topp``, the history
+        rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` and ``rescore_method="MBR"`` with ``mbr_corpus`` /
+        ``mbr_reward`` / ``mbr_alpha``: ``beam_decode_batched``."""
         self.eval()
         return self.forward(img_tensor, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                             rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
-                            repetition_penalty)
+                            repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha)
 
     def forward(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
+                mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
         """Inference only (model.py:237-472): encode the batch once, then beam-search every image."""
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
@@ -659,12 +678,14 @@ class SAT(SATDecoder, _Base):
         if sample_method == "ancestral" and max_gen_length < 1:
             raise ValueError("sample_method='ancestral' runs in the batched search only (max_gen_length >= 1)")
         constraints.resolve_all(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
+        constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, self.hp.vocab_size, max_gen_length)
         with torch.no_grad():
             ann_bld, hw = self.encode(img)
             if max_gen_length >= 1:        # every image at once; sampled continuations and decoder noise draw from the device generator
                 return self.beam_decode_batched(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, rescore_method, rescore_reward, return_all,
                                                 sample_method=sample_method, sample_topk=sample_topk, decoder_noise=decoder_noise,
-                                                graph=bool(self.__dict__.get("beam_graph", False)), sample_topp=sample_topp, **con)  # model.beam_graph = True: hipGraph replay
+                                                graph=bool(self.__dict__.get("beam_graph", False)), sample_topp=sample_topp, mbr_corpus=mbr_corpus,
+                                                mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, **con)  # model.beam_graph = True: hipGraph replay
             return self.beam_decode(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, sample_method, sample_topk,
                                     decoder_noise, rescore_method, rescore_reward, return_all, sample_topp=sample_topp, **con)
 
@@ -842,43 +863,48 @@ class SAT(SATDecoder, _Base):
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
 
     def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
-                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                       rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
+                       mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None):
         """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
         from . import evaluation
         return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                          rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
-                                         repetition_penalty)
+                                         repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                         rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
-                        sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                        sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None,
+                        mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
         (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L; with ``chrf``, an ``evaluation.VocabChars``, also chrF)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                           rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp, chrf, chrf_beta,
-                                          no_repeat_ngram, min_length, repetition_penalty)
+                                          no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False,
-                  sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None, **render):
+                  sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0,
+                  **render):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
         attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
         ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
         from . import visualize
         return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                    rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, sample_topp=sample_topp,
-                                   no_repeat_ngram=no_repeat_ngram, min_length=min_length, repetition_penalty=repetition_penalty, **render)
+                                   no_repeat_ngram=no_repeat_ngram, min_length=min_length, repetition_penalty=repetition_penalty, mbr_corpus=mbr_corpus,
+                                   mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                       rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
-                      topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None):
+                      topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
+                      mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
         """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
         ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
         from . import visualize
         return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                        rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk, sample_topp,
-                                       no_repeat_ngram, min_length, repetition_penalty)
+                                       no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

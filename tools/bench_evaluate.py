@@ -13,7 +13,11 @@ on the host as lists: the read-back is not counted), and the one-off build of th
 spelled with pseudo-words of 1..12 letters (5 on average, about an English caption's), drawn from a seed.
     python tools/bench_evaluate.py [--beams 5 20] [--batches 4] [--images 128] [--repeats 5] [--precision bf16] [--json]
     python tools/bench_evaluate.py --cider [--split-images 5000] [--batches 4] [--images 128] [--repeats 5] [--json]
+--mbr measures consensus reranking (``rescore_method="MBR"``) at beam 5 and beam 20: the per-batch time of ``val_batch_stats`` with
+``"LN"`` (today's path) and with ``"MBR"`` at rewards (1, 0) and (0.5, 0.5) in alternating rounds (hipEvents), the three new launches
+on their own on one batch's search buffers, and the host clock of ``metrics.consensus_utilities`` on the same hypotheses.
     python tools/bench_evaluate.py --chrf [--batches 4] [--images 128] [--repeats 5] [--json]
+    python tools/bench_evaluate.py --mbr [--beams 5 20] [--split-images 5000] [--batches 4] [--images 128] [--repeats 5] [--json]
 """
 import argparse
 import json
@@ -173,6 +177,74 @@ def bench_chrf(a, model, batches, hp, T, R):
     print("  chrF device %.12f host %.12f" % (res["chrf_device"], res["chrf_host"]))
 
 
+def bench_mbr(a, model, batches, hp, T, R):
+    """--mbr: val_batch_stats with "LN" and with "MBR", the three launches alone, the host specification on the same hypotheses"""
+    n_chunks = max(1, a.split_images // a.images)
+    rc = E.ReferenceCorpus(hp["vocab_size"], expected_positions=n_chunks * a.images * R * 4 * T)
+    for i in range(n_chunks):
+        caps, lengths = bench.synthetic_batch(a.images, R, T, hp["vocab_size"], 500 + i, ragged=True, px=8)[1:]
+        rc.add(caps.cuda(), lengths.cuda())
+    rc.check()
+    df = rc.to_dict()
+    spread = lambda v: dict(median=statistics.median(v), min=min(v), max=max(v))
+    rewards = {"mbr_cider": (1.0, 0.0), "mbr_mixed": (0.5, 0.5)}
+    for beamk in a.beams:
+        kw = dict(beamk=beamk, max_gen_length=a.max_gen_length, temperature=1.0)
+        paths = {"ln": lambda: E.evaluate(model, batches, rescore_method="LN", **kw)}
+        for name, reward in rewards.items():
+            paths[name] = (lambda reward: lambda: E.evaluate(model, batches, rescore_method="MBR", mbr_corpus=rc, mbr_reward=reward, **kw))(reward)
+        for fn in paths.values():                        # warm-up: code objects, allocator
+            fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in paths}
+        for _ in range(a.repeats):                       # alternating rounds
+            for k, fn in paths.items():
+                ms[k].append(event_ms(fn)[0] / a.batches)
+        # the three launches alone, on the buffers one batch's search leaves
+        with torch.no_grad():
+            ann, _ = model.encode(batches[0][0])
+            o = model._beam_search_device(ann.contiguous(), beamk, a.max_gen_length, 1.0, "beam", 3, None, None, None, None, False)
+        launches = {"hypotheses": [], "mbr_cider": [], "mbr_mixed": [], "select_at": []}
+        sel = E.select_hypotheses(o, model.pad_idx, "MBR", mbr_corpus=rc)
+        for _ in range(a.repeats + 1):                   # the first round warms up
+            t, (ht, hl) = event_ms(lambda: E.finished_hypotheses(o, model.pad_idx)); launches["hypotheses"].append(t)
+            for name, reward in rewards.items():
+                launches[name].append(event_ms(lambda: E.consensus_utilities(ht, hl, o["fin_count"], o["fin_score"], rc, reward, 0.0))[0])
+            launches["select_at"].append(event_ms(lambda: E.select_hypotheses(o, model.pad_idx, "MBR", mbr_corpus=rc))[0])
+        launches = {k: v[1:] for k, v in launches.items()}
+        launches["select_at"] = [max(0.0, t - h - c) for t, h, c in zip(launches["select_at"], launches["hypotheses"], launches["mbr_cider"])]
+        # the host specification on the same hypotheses (already on the host as lists: the read-back is not counted)
+        tok, ln, cnt, lp = ht.cpu().tolist(), hl.cpu().tolist(), o["fin_count"].cpu().tolist(), o["fin_score"].cpu().tolist()
+        hyps = [[tok[b][f][:ln[b][f]] for f in range(cnt[b])] for b in range(len(cnt))]
+        host = {}
+        for name, reward in rewards.items():
+            t0 = time.perf_counter()
+            us = [metrics.consensus_utilities(h, s[:len(h)], df, rc.images, reward, 0.0) for h, s in zip(hyps, lp)]
+            host[name] = (time.perf_counter() - t0) * 1e3
+        dev = E.consensus_utilities(ht, hl, o["fin_count"], o["fin_score"], rc, rewards["mbr_mixed"], 0.0)[0].cpu().tolist()
+        worst = max([abs(g - w) for gu, wu in zip(dev, us) for g, w in zip(gu, wu)] or [0.0])
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        res = dict(beamk=beamk, images=a.images, references=R, batches=a.batches, max_gen_length=a.max_gen_length, precision=a.precision, repeats=a.repeats,
+                   corpus_images=rc.images, val_batch_stats_ms_per_batch={k: spread(v) for k, v in ms.items()},
+                   mbr_increment_ms={k: med[k] - med["ln"] for k in rewards}, mbr_ratio_to_ln={k: med[k] / med["ln"] for k in rewards},
+                   launches_ms={k: spread(v) for k, v in launches.items()}, host_consensus_utilities_ms_per_batch=host,
+                   finished_hypotheses_mean=sum(cnt) / len(cnt), worst_device_minus_host=worst, winners_not_first_finished=int((sel["winner"] != 0).sum()))
+        if a.json:
+            print(json.dumps(res))
+            continue
+        print("beam %d, %d batches of %d images x %d references, max_gen_length %d, %s; corpus of %d images; %.1f finished hypotheses per image" %
+              (beamk, a.batches, a.images, R, a.max_gen_length, a.precision, rc.images, res["finished_hypotheses_mean"]))
+        for k, label in (("ln", 'val_batch_stats(rescore_method="LN")'), ("mbr_cider", '"MBR", reward (1, 0)'), ("mbr_mixed", '"MBR", reward (0.5, 0.5)')):
+            extra = "" if k == "ln" else "   %+.3f ms, %.3fx of LN" % (res["mbr_increment_ms"][k], res["mbr_ratio_to_ln"][k])
+            print("  %-40s %8.3f ms per batch (min %.3f, max %.3f)%s" % (label, med[k], min(ms[k]), max(ms[k]), extra))
+        for k, label in (("hypotheses", "sat_beam_hypotheses"), ("mbr_cider", "sat_caption_mbr (1, 0)"), ("mbr_mixed", "sat_caption_mbr (0.5, 0.5)"),
+                         ("select_at", "sat_beam_select_at (by difference)")):
+            v = res["launches_ms"][k]
+            print("  %-40s %8.3f ms (min %.3f, max %.3f)" % (label, v["median"], v["min"], v["max"]))
+        print("  host metrics.consensus_utilities: %.1f ms (1, 0), %.1f ms (0.5, 0.5) per batch; worst |device - host| %.2e" %
+              (host["mbr_cider"], host["mbr_mixed"], worst))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beams", type=int, nargs="+", default=[5, 20])
@@ -184,7 +256,8 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--cider", action="store_true", help="measure CIDEr-D / ROUGE-L: val_batch_stats with and without corpus=, the host scorer, the build")
     ap.add_argument("--chrf", action="store_true", help="measure chrF: val_batch_stats with and without chrf=, the host scorer, the VocabChars build")
-    ap.add_argument("--split-images", type=int, default=5000, help="--cider: images in the corpus the table is built from")
+    ap.add_argument("--mbr", action="store_true", help="measure consensus reranking: val_batch_stats with LN and with MBR, the three launches, the host")
+    ap.add_argument("--split-images", type=int, default=5000, help="--cider / --mbr: images in the corpus the table is built from")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_evaluate.py measures on the GPU; there is no CPU path")
@@ -200,6 +273,8 @@ def main():
         return bench_cider(a, model, batches, hp, T, R)
     if a.chrf:
         return bench_chrf(a, model, batches, hp, T, R)
+    if a.mbr:
+        return bench_mbr(a, model, batches, hp, T, R)
     for beamk in a.beams:
         kw = dict(beamk=beamk, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
 

@@ -6,6 +6,9 @@ parameter ranges, each scored over the first --max-batches batches), written as 
 (``evaluation.ReferenceCorpus``) and every batch and trial is scored against them (columns cider, rouge_l, cider_corpus, rouge_l_corpus).
 --chrf [--chrf-beta 3.0]: chrF as well (character n-grams, n = 1..6, across word boundaries); the vocabulary's spelling is put on the
 device once (``evaluation.VocabChars``) and every batch and trial is scored over it (columns chrf, chrf_corpus).  Combinable with --cider.
+--rescore-method MBR [--mbr-split train --mbr-reward 1.0 0.0 --mbr-alpha 0.0]: consensus reranking of every beam; the document
+frequencies come from the named split's references (one more ``ReferenceCorpus``, built once).  With --trials, "MBR" joins the
+notebook's rescore methods.
 All work is in sat_amd/evaluation.py: a batch is decoded and scored on the device, one host read per pass.
     python tools/evaluate.py CHECKPOINT [--json DATASET.json] [--root IMAGE_DIR] [--split test] [--batch N] [--max-batches M]
                              [--trials N --seed S --out results.csv]  [--cider]  [--chrf --chrf-beta 3.0]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
@@ -48,8 +51,11 @@ def main():
     ap.add_argument("--sample-topk", type=int, default=3)
     ap.add_argument("--sample-topp", type=float, default=0.9, help="nucleus sampling: the share of the probability mass the candidates of a hypothesis carry, (0, 1]")
     ap.add_argument("--decoder-noise", type=float, default=0.0)
-    ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
+    ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR", "MBR"])
     ap.add_argument("--rescore-reward", type=float, default=0.5)
+    ap.add_argument("--mbr-split", default="train", help="MBR: the split whose references give the document frequencies")
+    ap.add_argument("--mbr-reward", type=float, nargs=2, default=[1.0, 0.0], metavar=("W_CIDER", "W_ROUGE"), help="MBR: the weights of CIDEr-D and ROUGE-L in the gain")
+    ap.add_argument("--mbr-alpha", type=float, default=0.0, help="MBR: a hypothesis votes with exp(alpha * (its raw score - the best)); 0 = uniform")
     ap.add_argument("--topg", type=int, default=None, help="top-g clipping: only the G best words of every hypothesis are candidates (beam sampling)")
     ap.add_argument("--no-unk", action="store_true", help="never emit <UNK>")
     ap.add_argument("--no-repeat-ngram", type=int, default=None, help="no n-gram of this size is said twice in a caption (0 / unset = off)")
@@ -65,9 +71,16 @@ def main():
     loader = D.DeviceLoader(ds, a.batch or model.hparams.batch, D.BatchTransform(model.hparams.input_size, train=False), workers=a.workers)
     corpus = E.ReferenceCorpus.from_dataset(ds).check() if a.cider else None
     chars = E.VocabChars.from_model(model) if a.chrf else None
+    mbr = {}
+    if a.rescore_method == "MBR":
+        mbr_ds = ds if a.mbr_split == a.split else D.CocoCaptionDataset(a.json or model.hparams.json, a.mbr_split, root=a.root)
+        mbr = dict(mbr_corpus=corpus if (corpus is not None and mbr_ds is ds) else E.ReferenceCorpus.from_dataset(mbr_ds).check(),
+                   mbr_reward=tuple(a.mbr_reward), mbr_alpha=a.mbr_alpha)
     shown = E.HEADERS + (list(E.CONSENSUS_KEYS) if a.cider else []) + (list(E.CHRF_KEYS) if a.chrf else [])
     if a.trials > 0:
-        rows = E.random_search(model, loader, a.trials, seed=a.seed, max_batches=a.max_batches or 4, corpus=corpus, chrf=chars, chrf_beta=a.chrf_beta)
+        space = dict(E.NOTEBOOK_SPACE, rescore_methods=E.NOTEBOOK_SPACE["rescore_methods"] + ["MBR"]) if mbr else E.NOTEBOOK_SPACE
+        rows = E.random_search(model, loader, a.trials, space=space, seed=a.seed, max_batches=a.max_batches or 4, corpus=corpus, chrf=chars,
+                               chrf_beta=a.chrf_beta, **mbr)
         cols = list(rows[0])
         for r in sorted(rows, key=lambda r: -r["bleu4"]):
             print("  ".join("%s=%s" % (k, ("%.4f" % r[k]) if isinstance(r[k], float) else r[k]) for k in shown))
@@ -79,7 +92,7 @@ def main():
     res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, **(dict(chrf=chars, chrf_beta=a.chrf_beta) if a.chrf else {}), beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
                      sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise,
                      rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward, topg=a.topg,
-                     no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty)
+                     no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty, **mbr)
     print("%d images in %d batches" % (res["images"], res["batches"]))
     for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()) + (E.CHRF_KEYS if a.chrf else ()):
         print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))

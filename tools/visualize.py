@@ -5,6 +5,8 @@ panels out with Pillow.
     python tools/visualize.py CHECKPOINT [--json DATASET.json] [--root IMAGE_DIR] [--split test] (--idx I [I ...] | --count N [--seed S])
                               --out DIR [--batch 32] [--visual-size 256] [--input-size 224] [--beamk 3 --temperature 1.0
                               --sample-method beam --sample-topk 3 --decoder-noise 0.0 --rescore-method LN --rescore-reward 1.0]
+                              [--rescore-method MBR --mbr-split train --mbr-reward 1.0 0.0 --mbr-alpha 0.0]   consensus reranking: the caption
+                              that agrees most with the rest of its beam; document frequencies from the named split's references
 """
 import argparse
 import os
@@ -42,8 +44,11 @@ def main():
     ap.add_argument("--sample-topk", type=int, default=3)
     ap.add_argument("--sample-topp", type=float, default=0.9, help="nucleus sampling: the share of the probability mass the candidates of a hypothesis carry, (0, 1]")
     ap.add_argument("--decoder-noise", type=float, default=0.0)
-    ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR"])
+    ap.add_argument("--rescore-method", default="LN", choices=["NONE", "LN", "WR", "BAR", "MBR"])
     ap.add_argument("--rescore-reward", type=float, default=1.0)
+    ap.add_argument("--mbr-split", default="train", help="MBR: the split whose references give the document frequencies")
+    ap.add_argument("--mbr-reward", type=float, nargs=2, default=[1.0, 0.0], metavar=("W_CIDER", "W_ROUGE"), help="MBR: the weights of CIDEr-D and ROUGE-L in the gain")
+    ap.add_argument("--mbr-alpha", type=float, default=0.0, help="MBR: a hypothesis votes with exp(alpha * (its raw score - the best)); 0 = uniform")
     ap.add_argument("--progressive", action="store_true", help="decode progressive JPEG files on the GPU as well (default: Pillow decodes them)")
     ap.add_argument("--topg", type=int, default=None, help="top-g clipping: only the G best words of every hypothesis are candidates (beam sampling)")
     ap.add_argument("--prefix", default=None, help='words every caption starts with, e.g. "a photo of" (each must be in the vocabulary)')
@@ -60,6 +65,11 @@ def main():
     model.load_state_dict(ckpt["state_dict"])
     model = model.cuda()
     ds = D.CocoCaptionDataset(a.json or model.hparams.json, a.split, root=a.root)
+    mbr = {}
+    if a.rescore_method == "MBR":
+        from sat_amd import evaluation as E
+        mbr_ds = ds if a.mbr_split == a.split else D.CocoCaptionDataset(a.json or model.hparams.json, a.mbr_split, root=a.root)
+        mbr = dict(mbr_corpus=E.ReferenceCorpus.from_dataset(mbr_ds).check(), mbr_reward=tuple(a.mbr_reward), mbr_alpha=a.mbr_alpha)
     idx = a.idx if a.idx is not None else np.random.RandomState(a.seed).randint(0, len(ds), a.count).tolist()
     os.makedirs(a.out, exist_ok=True)
     for start in range(0, len(idx), a.batch):
@@ -69,7 +79,7 @@ def main():
                               sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise, rescore_method=None if a.rescore_method == "NONE" else a.rescore_method,
                               rescore_reward=a.rescore_reward, visual_size=a.visual_size, input_size=a.input_size, seed=a.seed, progressive=a.progressive,
                               topg=a.topg, prefix=a.prefix, no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length,
-                              repetition_penalty=a.repetition_penalty)
+                              repetition_penalty=a.repetition_penalty, **mbr)
         for j, i in enumerate(chunk):
             refs = [" ".join(ds.itos(t) for t in c[1:n]) for c, n in zip(ds.encoded_captions[i], ds.lengths[i])]
             name = os.path.join(a.out, "%s_result.jpg" % vis.names[j])
