@@ -375,6 +375,43 @@ int sat_beam_search_history(const sat_decoder_dims* d, const sat_decoder_params*
                             const sat_beam_constraints* constraints, const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row,
                             float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Diverse (group) beam search: Hamming diversity between the groups of a beam (Vijayakumar et al. 2016; DESIGN.md 5, "Diverse beam
+ * search").  beamk = K rows of an image are G = groups groups of Kg = K / G rows (K % G == 0); rows g * Kg .. (g + 1) * Kg - 1 belong to
+ * group g for the whole search.  A group is a beam of its own: its own live count, its own parents (a hypothesis descends from a row of
+ * its group only), its own finished list, its own cut at max_gen_length, and the initial state of a plain search at beamk = Kg (the
+ * reshape of the initial state acts on the group's Kg rows).  At a step the groups of an image select in the order
+ * g = 0 .. G - 1; group g ranks its candidates (row j of the group, word v) by
+ *   pen = s[j, v] - lambda * c[v]
+ * with s the score of every search above (log-softmax, parent score, masks, banned ids, history rules) and c[v] the number of
+ * hypotheses the groups < g of this image kept AT THIS STEP with word v (END included; a group without a live row adds nothing).  pen
+ * is fp32 with two roundings, the product then the difference, so c == 0 or lambda == 0 leaves s bit for bit.  The group keeps its
+ * klive best candidates by pen descending, ties to the lower flat index j * V + v (sat_topk's rule, its -inf behaviour included); at
+ * step 0 it selects from its first row only.  A hypothesis CARRIES s, NOT pen: fin_score, the parent scores, perplexity and every
+ * rescoring stay sums of model log-probabilities; fin_mean is the mean over the group's kept hypotheses at that moment.
+ * The layout of the results is the one above: tok_in / prev_row / alpha_hist (., B, K[, L]) with image-level parent rows in prev_row,
+ * fin_* (B, K) compacted per image (group ascending, inside a group the append order), fin_row image-level, fin_count[b] ends at K.
+ * groups = NULL, or groups->groups 0 or 1, enqueues exactly what sat_beam_search_history enqueues.  SAT_EINVAL before any launch: groups
+ * < 0, diversity_penalty negative or not finite; and with groups > 1: beamk % groups != 0, beamk > 1024, a sampling method other than
+ * SAT_SAMPLE_BEAM, decoder_noise, topg, a forced prefix, a stream that is being captured.  Banned ids and the history rules combine.
+ * Workspace: sat_beam_search_groups_workspace_bytes (sat_beam_search_history_workspace_bytes with topg = 0, plus the live counts and
+ * the finished lists per group; it serves the call with groups off as well). */
+typedef struct sat_beam_groups {
+    int32_t groups;              /* 0 or 1 = off, else a divisor of beamk */
+    float   diversity_penalty;   /* lambda: finite, >= 0 */
+} sat_beam_groups;
+size_t sat_beam_search_groups_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t groups, int32_t max_gen_length);
+int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                           const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                           const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_groups* groups, int32_t* tok_in,
+                           int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score,
+                           float* fin_mean, void* workspace, size_t workspace_bytes, void* stream);
+/* The selection kernel of sat_beam_search_groups on its own: scores (B, beamk, V), klive (B, groups) live rows per group (clamped to
+ * 0 .. beamk / groups), first_step != 0 selects from each group's first row only.  Slot g * Kg + t of image b receives the group's t-th
+ * pick: values the UNPENALISED score, indices the group-local flat index row * V + word; slots past klive stay untouched.  work is
+ * scratch, (B, beamk, V) floats.  No atomics: same input, same bits.  SAT_EINVAL before the launch: a null pointer, a size < 1,
+ * beamk % groups != 0, beamk > 1024, beamk / groups > V, diversity_penalty negative or not finite.  NaN in scores: unspecified. */
+int sat_beam_group_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t groups, int32_t V, int32_t first_step,
+                          float diversity_penalty, float* work, float* values, int32_t* indices, void* stream);
 /* A -inf logit gets the score -inf and leaves the rest of its row as torch.log_softmax does; a row of nothing but -inf gives NaN, as
  * torch does.  Masked ids outside [0, V) mask nothing. */
 int sat_beam_scores(const float* logits, int32_t beams, int32_t V, float temperature, const int32_t* masked_ids /* device */,

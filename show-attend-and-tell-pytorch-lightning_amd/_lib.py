@@ -94,6 +94,11 @@ class BeamHistory(C.Structure):
     _fields_ = [("no_repeat_ngram", C.c_int32), ("min_length", C.c_int32), ("repetition_penalty", C.c_float), ("reserved", C.c_int32)]
 
 
+class BeamGroups(C.Structure):
+    """sat_beam_groups (include/sat_hip.h)"""
+    _fields_ = [("groups", C.c_int32), ("diversity_penalty", C.c_float)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [("offset", C.c_int64)] + [(k, C.c_int32) for k in ("height", "width", "crop_top", "crop_left", "crop_h", "crop_w", "resized_h",
                                                                   "resized_w", "out_top", "out_left", "flip", "reserved")]
@@ -265,6 +270,11 @@ SYMBOLS.update({
     "sat_beam_search_history": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _i32, _i32, C.POINTER(C.c_float), _i32,
                                           C.POINTER(C.c_int32), C.POINTER(BeamSampling), C.POINTER(BeamConstraints), C.POINTER(BeamHistory), _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_beam_search_groups_workspace_bytes": (C.c_size_t, [C.POINTER(DecoderDims), _i32, _i32, _i32]),
+    "sat_beam_search_groups": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _i32, _i32, C.POINTER(C.c_float), _i32,
+                                         C.POINTER(C.c_int32), C.POINTER(BeamSampling), C.POINTER(BeamConstraints), C.POINTER(BeamHistory),
+                                         C.POINTER(BeamGroups), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_beam_group_select": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp]),
     "sat_beam_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp]),
     "sat_beam_history_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp, _i32, C.POINTER(BeamHistory), _i32, _i32, _vp, _vp]),
     "sat_topk": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),

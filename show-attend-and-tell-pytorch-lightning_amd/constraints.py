@@ -198,6 +198,60 @@ def resolve_history(V, beamk, max_gen_length, sample_method, topg, n_banned, no_
     return HistoryRules(n, m, theta)
 
 
+class BeamGroups:
+    """groups: G > 1; diversity_penalty: lambda >= 0 ("Diverse beam search")"""
+
+    def __init__(self, groups, diversity_penalty):
+        self.groups, self.diversity_penalty = int(groups), float(diversity_penalty)
+
+    def device_struct(self):
+        """sat_beam_groups"""
+        return L.BeamGroups(groups=self.groups, diversity_penalty=self.diversity_penalty)
+
+
+#: beam_group_select_kernel keeps the words kept at a step in a table of this many entries
+GROUPS_MAX_BEAMK = 1024
+
+
+def resolve_groups(beamk, beam_groups=None, diversity_penalty=0.5, sample_method="beam", decoder_noise=None, topg=None, prefix=None, graph=False,
+                   batched=True, V=None):
+    """The checked groups of one search, or ``None`` when the beam is not split (``beam_groups`` ``None``, 0 or 1: today's search,
+    whatever ``diversity_penalty`` says).  Every ``ValueError`` of the diverse beam search ("Diverse beam search"), each
+    naming its argument; ``batched=False`` is the per-image loop ``beam_decode``, which has no groups.  Touches no GPU."""
+    if beam_groups is None:
+        return None
+    G, K = int(beam_groups), int(beamk)
+    if G < 0:
+        raise ValueError("beam_groups=%d is negative (None, 0 or 1 = off)" % G)
+    if G <= 1:
+        return None
+    try:
+        lam = float(diversity_penalty)
+    except (TypeError, ValueError):
+        raise ValueError("diversity_penalty=%r is not a number" % (diversity_penalty,))
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("diversity_penalty=%r is not a finite number >= 0" % (diversity_penalty,))
+    if not batched:
+        raise ValueError("beam_groups=%d runs in the batched search only (beam_decode_batched), not in the per-image loop beam_decode" % G)
+    if sample_method != "beam":
+        raise ValueError("beam_groups combines with sample_method='beam' only, not %r" % (sample_method,))
+    if decoder_noise:
+        raise ValueError("beam_groups does not combine with decoder_noise=%r" % (decoder_noise,))
+    if topg is not None:
+        raise ValueError("beam_groups does not combine with topg=%r" % (topg,))
+    if prefix is not None:
+        raise ValueError("beam_groups does not combine with a forced prefix (prefix=%r)" % (prefix,))
+    if graph:
+        raise ValueError("beam_groups is not replayed from a graph (graph=True)")
+    if K < 1 or K % G != 0:
+        raise ValueError("beam_groups=%d does not divide beamk=%d" % (G, K))
+    if K > GROUPS_MAX_BEAMK:
+        raise ValueError("beam_groups needs beamk <= %d (beamk=%d)" % (GROUPS_MAX_BEAMK, K))
+    if V is not None and K // G > int(V):
+        raise ValueError("beam_groups=%d: beamk / beam_groups = %d above V=%d" % (G, K // G, int(V)))
+    return BeamGroups(G, lam)
+
+
 def resolve_all(stoi, V, B, beamk, max_gen_length, sample_method="beam", topg=None, prefix=None, banned=None, no_unk=False, no_repeat_ngram=None,
                 min_length=None, repetition_penalty=None):
     """``(resolve(...), resolve_history(...))``: every ``ValueError`` of both, before any launch"""

@@ -227,6 +227,34 @@ int sat_beam_search_history(const sat_decoder_dims* d, const sat_decoder_params*
     return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history);
 }
+size_t sat_beam_search_groups_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t groups, int32_t max_gen_length) {
+    if (check_dims(d) != SAT_OK || beamk < 1) return 0;
+    if (groups < 0 || (groups > 1 && beamk % groups != 0)) {
+        fail(SAT_EINVAL, "beam_search_groups_workspace_bytes: beamk %d is not a multiple of groups %d (0 or 1 = off)", beamk, groups);
+        return 0;
+    }
+    if (max_gen_length < 0) { fail(SAT_EINVAL, "beam_search_groups_workspace_bytes: max_gen_length %d is negative", max_gen_length); return 0; }
+    // room for the history tables too where the history rules can run at all (max_gen_length + 1 <= SAT_CAPTION_MAX_LEN)
+    return decoder_beam_workspace_bytes(*d, beamk, 0, max_gen_length + 1 <= SAT_CAPTION_MAX_LEN ? max_gen_length + 1 : 0, groups);
+}
+int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                           const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                           const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_groups* groups, int32_t* tok_in,
+                           int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_groups"));
+    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
+        return fail(SAT_EINVAL, "beam_search_groups: null pointer");
+    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_groups: temperature %g", temperatures_host[i]);
+    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
+                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history,
+                                groups);
+}
+int sat_beam_group_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t groups, int32_t V, int32_t first_step,
+                          float diversity_penalty, float* work, float* values, int32_t* indices, void* stream) {
+    if (!scores || !klive || !work || !values || !indices) return fail(SAT_EINVAL, "beam_group_select: null pointer");
+    return beam_group_select(scores, klive, B, beamk, groups, V, first_step, diversity_penalty, work, values, indices, (hipStream_t)stream);
+}
 int sat_beam_history_scores(const float* logits, int32_t rows, int32_t V, float temperature, const int32_t* masked_ids, int32_t n_masked,
                             const float* parent_scores, const int32_t* hist, const int32_t* hist_len, int32_t hist_stride, const sat_beam_history* rules,
                             int32_t step, int32_t end_id, float* scores, void* stream) {

@@ -30,13 +30,15 @@ int decoder_infer_begin(const sat_decoder_dims& d, const sat_decoder_params& p, 
                         char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_infer_step(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, const int* tokens, int K, int Kmax,
                        float* h, float* c, float* logits, float* alpha, const float* h_noise, char* ws, size_t ws_bytes, hipStream_t st);
-size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg = 0, int hist_stride = 0);
+size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg = 0, int hist_stride = 0, int groups = 1);
+int beam_groups_check(const sat_beam_groups* g, const char* what);
 bool beam_history_on(const sat_beam_history* h);
 int beam_history_check(const sat_beam_history* h, int max_gen_length, const char* what);
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row,
                          float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
-                         const sat_beam_constraints* constraints = nullptr, const sat_beam_history* history = nullptr);
+                         const sat_beam_constraints* constraints = nullptr, const sat_beam_history* history = nullptr,
+                         const sat_beam_groups* groups = nullptr);
 int launch_attention_bwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
                          const float* alphas, const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
                          int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, void* dhcb = nullptr, const void* annb = nullptr);
@@ -61,6 +63,8 @@ int sigmoid_bwd(const float* dy, const float* y, float* dpre, long n, hipStream_
 int beam_scores(const float* logits, int K, int V, float temperature, const int* masked, int n_masked, const float* parent, float* scores, hipStream_t st);
 int beam_history_scores(const float* logits, int rows, int V, float temperature, const int* masked, int n_masked, const float* parent, const int* hist,
                         const int* hist_len, int hist_stride, const sat_beam_history& rules, int step, int end_id, float* scores, hipStream_t st);
+int beam_group_select(const float* scores, const int* klive, int B, int K, int G, int V, int first_step, float lambda, float* work, float* values, int* indices,
+                      hipStream_t st);
 int topk(const float* x, float* work, long n, int k, float* values, int* indices, hipStream_t st);
 int nucleus_keys(const float* scores, int rows, int V, float topp, float step, unsigned long long seed, unsigned long long stream, const float* gumbel,
                  float* keys, int* nucleus_size, hipStream_t st);

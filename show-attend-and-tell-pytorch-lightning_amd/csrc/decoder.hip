@@ -790,8 +790,9 @@ struct BeamWs {
     int *live, *klive, *inds, *gmap, *mask_first, *mask_rest;
     float* cand_val; int* cand_idx;        // top-g clipping only: (B*K, topg) candidates, after everything the plain search uses
     int *hist_a, *hist_b;                  // history rules only: (B*K, hist_stride) words every row has said, double-buffered, after the candidates
+    int *g_count, *g_step, *g_row; float *g_score, *g_mean;   // groups only: the finished lists of the (image, group) pairs, (B*G) and (B*G, K/G)
 };
-static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg = 0, int hist_stride = 0) {
+static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg = 0, int hist_stride = 0, int groups = 1) {
     BeamWs w; size_t off = 0;
     const long HCW = d.A + d.D + 4L * d.n, N = (long)d.B * K;
     auto take = [&](size_t elems) { size_t o = off; off += (elems * 4 + 255) & ~(size_t)255; return base ? base + o : (char*)nullptr; };
@@ -804,15 +805,21 @@ static BeamWs beam_layout(const sat_decoder_dims& d, int K, char* base, int topg
     w.h2 = (float*)take((size_t)d.layers * N * d.n); w.c2 = (float*)take((size_t)d.layers * N * d.n);
     w.logits = (float*)take((size_t)N * d.V); w.scores = (float*)take((size_t)N * d.V); w.work = (float*)take((size_t)N * d.V); w.keys = (float*)take((size_t)N * d.V); w.noise = (float*)take((size_t)d.layers * N * d.n);
     w.vals = (float*)take(N); w.top = (float*)take(N); w.sc = (float*)take((size_t)N * d.L);
-    w.live = (int*)take(N); w.klive = (int*)take(d.B); w.inds = (int*)take(N); w.gmap = (int*)take(N); w.mask_first = (int*)take(4); w.mask_rest = (int*)take(4);
+    w.live = (int*)take(N); w.klive = (int*)take((size_t)d.B * groups); w.inds = (int*)take(N); w.gmap = (int*)take(N); w.mask_first = (int*)take(4); w.mask_rest = (int*)take(4);
     w.cand_val = nullptr; w.cand_idx = nullptr;
     if (topg > 0) { w.cand_val = (float*)take((size_t)N * topg); w.cand_idx = (int*)take((size_t)N * topg); }
     w.hist_a = nullptr; w.hist_b = nullptr;
     if (hist_stride > 0) { w.hist_a = (int*)take((size_t)N * hist_stride); w.hist_b = (int*)take((size_t)N * hist_stride); }
+    w.g_count = w.g_step = w.g_row = nullptr; w.g_score = w.g_mean = nullptr;
+    if (groups > 1) {
+        w.g_count = (int*)take((size_t)d.B * groups); w.g_step = (int*)take(N); w.g_row = (int*)take(N); w.g_score = (float*)take(N); w.g_mean = (float*)take(N);
+    }
     w.total = off;
     return w;
 }
-size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg, int hist_stride) { return beam_layout(d, K, nullptr, topg, hist_stride).total; }
+size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg, int hist_stride, int groups) {
+    return beam_layout(d, K, nullptr, topg, hist_stride, groups < 1 ? 1 : groups).total;
+}
 
 // sat_beam_history: which rules are on, and are they well-formed (include/sat_hip.h)
 bool beam_history_on(const sat_beam_history* h) {
@@ -844,10 +851,22 @@ static int launch_nucleus_keys(hipStream_t st, const float* scores, const int* k
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
                          int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
-                         const sat_beam_constraints* con, const sat_beam_history* hist) {
+                         const sat_beam_constraints* con, const sat_beam_history* hist, const sat_beam_groups* grp) {
     // no constraint at all: exactly the launches of the plain / sampled search
     if (con && con->topg == 0 && con->max_prefix == 0 && con->n_banned == 0) con = nullptr;
     const int method = smp ? smp->method : 0;
+    SAT_TRY(beam_groups_check(grp, "beam_groups"));
+    const int G = grp && grp->groups > 1 ? grp->groups : 1;        // 1: today's search, the same launches
+    const float lambda = G > 1 ? grp->diversity_penalty : 0.f;
+    if (G > 1) {                                           // the groups select in the constrained search's place ("Diverse beam search")
+        SAT_REQUIRE(K >= 1 && K % G == 0, "beam_groups: beamk %d is not a multiple of groups %d", K, G);
+        SAT_REQUIRE(K <= SAT_BEAM_GROUP_MAX_K && K / G <= d.V, "beam_groups: beamk %d above %d, or beamk / groups above V=%d", K, SAT_BEAM_GROUP_MAX_K, d.V);
+        SAT_REQUIRE(method == SAT_SAMPLE_BEAM, "beam_groups: groups combine with \"beam\" sampling only (method %d)", method);
+        SAT_REQUIRE(!smp || smp->decoder_noise == 0.f, "beam_groups: groups do not combine with decoder_noise");
+        SAT_REQUIRE(!con || con->topg == 0, "beam_groups: groups do not combine with topg %d", con ? con->topg : 0);
+        SAT_REQUIRE(!con || con->max_prefix == 0, "beam_groups: groups do not combine with a forced prefix (max_prefix %d)", con ? con->max_prefix : 0);
+        SAT_TRY(not_capturing(st, "beam_groups"));
+    }
     SAT_TRY(beam_history_check(hist, max_gen_length, "beam_history"));
     const bool hist_on = beam_history_on(hist);
     const sat_beam_constraints no_constraint = {};
@@ -858,6 +877,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         SAT_TRY(not_capturing(st, "beam_history"));
         if (!con) con = &no_constraint;
     }
+    if (G > 1 && !con) con = &no_constraint;
     const int hist_stride = hist_on ? max_gen_length + 1 : 0;
     const float theta = hist_on && hist->repetition_penalty != 0.f ? hist->repetition_penalty : 1.0f;
     if (con) {
@@ -872,7 +892,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     }
     const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
     const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
-    BeamWs w = beam_layout(d, K, ws, topg, hist_stride);
+    BeamWs w = beam_layout(d, K, ws, topg, hist_stride, G);
     SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_ANCESTRAL && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
                 "beam_batched: sampling method %d, sample_topk %d", method, smp ? smp->sample_topk : 0);
     if (method == SAT_SAMPLE_ANCESTRAL) {
@@ -913,9 +933,18 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     SAT_TRY(launch_ok("ann_mean"));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.mean, D, p.init_f_w, D, w.f, m, B, m, D, 0, EPI_BIAS, p.init_f_b));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.f, m, p.init_i_w, m, w.init_img, 2 * n * NL, B, 2 * n * NL, m, 0, EPI_BIAS, p.init_i_b));
-    hipLaunchKernelGGL(init_expand_images_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, K, n, NL);
-    SAT_TRY(launch_ok("init_expand_images"));
-    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, w.klive, (long)B, K);
+    if (G > 1) {           // a group starts as a beam of K / G rows does (the F3 reshape depends on the row count)
+        hipLaunchKernelGGL(init_expand_groups_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, G, K / G, n, NL);
+        SAT_TRY(launch_ok("init_expand_groups"));
+    } else {
+        hipLaunchKernelGGL(init_expand_images_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, K, n, NL);
+        SAT_TRY(launch_ok("init_expand_images"));
+    }
+    // the bookkeeping below the selection sees (image, group) pairs as Bv images of Kv rows; without groups these are B and K
+    const int Bv = B * G, Kv = K / G;
+    int* const f_count = G > 1 ? w.g_count : fin_count; int* const f_step = G > 1 ? w.g_step : fin_step; int* const f_row = G > 1 ? w.g_row : fin_row;
+    float* const f_score = G > 1 ? w.g_score : fin_score; float* const f_mean = G > 1 ? w.g_mean : fin_mean;
+    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(Bv, 256)), dim3(256), 0, st, w.klive, (long)Bv, Kv);
     SAT_TRY(launch_ok("fill klive"));
     zero_w(tok_in, (long)(max_gen_length + 2) * N);       // rows that are not live still index the embedding table
     zero_w(prev_row, (long)(max_gen_length + 2) * N);
@@ -924,7 +953,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     zero_w(w.h2, (long)NL * N * n);
     zero_w(w.c2, (long)NL * N * n);
     zero_w(w.top, N);
-    zero_w(fin_count, B);
+    zero_w(f_count, Bv);
     if (hist_on) { zero_w(w.hist_a, (long)N * hist_stride); zero_w(w.hist_b, (long)N * hist_stride); }
     SAT_TRY(launch_ok("beam: clears"));
 
@@ -935,7 +964,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         float* alpha = alpha_hist + (long)step * N * d.L;
         const long KS = (long)N * n;
         float* htop = h + (NL - 1) * KS;
-        hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, B, K);
+        hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, Bv, Kv);
         SAT_TRY(launch_ok("beam_live"));
         // ---- model.py:298-327 for all rows (dead rows: zero attention, state carried, ignored below)
         hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, tok, w.Y, N, m, d.V, 0.f, 0ull, 0L);
@@ -997,9 +1026,14 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                                    gstride, w.keys);
                 SAT_TRY(launch_ok("beam_sample_keys"));
             }
-            hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, drawn ? w.keys : (const float*)nullptr, w.cand_val, w.cand_idx, topg, w.work,
-                               w.klive, K, V, step, max_prefix > 0 ? con->prefix : (const int*)nullptr, prefix_len, max_prefix, w.vals, w.inds);
-            SAT_TRY(launch_ok("beam_select"));
+            if (G > 1) {
+                hipLaunchKernelGGL(beam_group_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, G, V, step == 0 ? 1 : 0, lambda, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_group_select"));
+            } else {
+                hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, drawn ? w.keys : (const float*)nullptr, w.cand_val, w.cand_idx, topg,
+                                   w.work, w.klive, K, V, step, max_prefix > 0 ? con->prefix : (const int*)nullptr, prefix_len, max_prefix, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_select"));
+            }
             if (drawn) {
                 hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
                 SAT_TRY(launch_ok("beam_take_scores"));
@@ -1035,25 +1069,47 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                 SAT_TRY(launch_ok("beam_take_scores"));
             }
         }
-        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, B, K, V, step, max_gen_length, END, prefix_len, max_prefix,
-                           tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, fin_count, fin_step, fin_row, fin_score, fin_mean);
+        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(Bv, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, Bv, Kv, V, step, max_gen_length, END, prefix_len, max_prefix,
+                           tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, f_count, f_step, f_row, f_score, f_mean);
         SAT_TRY(launch_ok("beam_update"));
         if (hist_on && step < max_gen_length) {
             hipLaunchKernelGGL(beam_history_advance_kernel, dim3(cdiv((long)N * (step + 1), 256)), dim3(256), 0, st, hcur, hnext, tok_in + (long)(step + 1) * N,
-                               prev_row + (long)(step + 1) * N, w.klive, B, K, hist_stride, step);
+                               prev_row + (long)(step + 1) * N, w.klive, Bv, Kv, hist_stride, step);
             SAT_TRY(launch_ok("beam_history_advance"));
             int* t0 = hcur; hcur = hnext; hnext = t0;
         }
         if (step < max_gen_length) {
             const long tot = (long)NL * N * n;
-            hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, h, h2, w.gmap, w.klive, B, K, n, NL);
+            hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, h, h2, w.gmap, w.klive, Bv, Kv, n, NL);
             SAT_TRY(launch_ok("beam_gather h"));
-            hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, c, c2, w.gmap, w.klive, B, K, n, NL);
+            hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, c, c2, w.gmap, w.klive, Bv, Kv, n, NL);
             SAT_TRY(launch_ok("beam_gather c"));
             float* t1 = h; h = h2; h2 = t1; t1 = c; c = c2; c2 = t1;
         }
     }
+    if (G > 1) {                                           // group-local parents and per-group finished lists -> the caller's image-level layout
+        const long n_prev = (long)(max_gen_length + 1) * N;
+        hipLaunchKernelGGL(beam_group_merge_kernel, dim3(cdiv(n_prev > Bv ? n_prev : (long)Bv, 256)), dim3(256), 0, st, prev_row + N, n_prev, B, K, G, w.g_count,
+                           w.g_step, w.g_row, w.g_score, w.g_mean, fin_count, fin_step, fin_row, fin_score, fin_mean);
+        SAT_TRY(launch_ok("beam_group_merge"));
+    }
     return SAT_OK;
+}
+// sat_beam_groups: well-formed?  (groups 0 and 1 are both "off")
+int beam_groups_check(const sat_beam_groups* g, const char* what) {
+    if (!g) return SAT_OK;
+    SAT_REQUIRE(g->groups >= 0, "%s: groups %d is negative (0 or 1 = off)", what, g->groups);
+    const float t = g->diversity_penalty;
+    SAT_REQUIRE(t >= 0.f && t < INFINITY, "%s: diversity_penalty %g is not a finite number >= 0", what, (double)t);
+    return SAT_OK;
+}
+int beam_group_select(const float* scores, const int* klive, int B, int K, int G, int V, int first_step, float lambda, float* work, float* values, int* indices,
+                      hipStream_t st) {
+    SAT_REQUIRE(B >= 1 && K >= 1 && G >= 1 && V >= 1 && K % G == 0, "beam_group_select: bad sizes (B=%d beamk=%d groups=%d V=%d; beamk %% groups == 0)", B, K, G, V);
+    SAT_REQUIRE(K <= SAT_BEAM_GROUP_MAX_K && K / G <= V, "beam_group_select: beamk %d above %d, or beamk / groups above V=%d", K, SAT_BEAM_GROUP_MAX_K, V);
+    SAT_REQUIRE(lambda >= 0.f && lambda < INFINITY, "beam_group_select: diversity_penalty %g is not a finite number >= 0", (double)lambda);
+    hipLaunchKernelGGL(beam_group_select_kernel, dim3(B), dim3(1024), 0, st, scores, work, klive, K, G, V, first_step ? 1 : 0, lambda, values, indices);
+    return launch_ok("beam_group_select");
 }
 
 int beam_scores(const float* logits, int K, int V, float temperature, const int* masked, int n_masked, const float* parent, float* scores, hipStream_t st) {

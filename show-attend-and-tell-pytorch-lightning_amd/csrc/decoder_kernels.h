@@ -1784,4 +1784,108 @@ __global__ void beam_history_advance_kernel(const int* __restrict__ cur, int* __
     next[(long)i * stride + p] = cur[((long)b * K + parent) * stride + p];
 }
 
+// ---- diverse (group) beam search: Hamming diversity between the groups of a beam ("Diverse beam search").
+// The K rows of an image are G groups of Kg = K / G rows, each a beam of its own; everything but this selection and the final merge
+// treats (image, group) as an image of Kg rows.
+#define SAT_BEAM_GROUP_MAX_K 1024
+// init_expand_images_kernel for groups: the raw reshape of F3 acts on the (Kg, 2*layers*n) buffer of every (image, group) pair, as it
+// does for a beam of Kg rows, so that a group starts exactly like the plain search at beamk = Kg.  Pair p = b * G + g reads image b.
+__global__ void init_expand_groups_kernel(const float* __restrict__ init_img, float* __restrict__ h0, float* __restrict__ c0, int B, int G, int Kg, int n,
+                                          int layers) {
+    const long per = 2L * layers * Kg * n;                     // flat elements of one pair
+    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= per * B * G) return;
+    const int p = (int)(e / per); const long f = e - (long)p * per;
+    const long w2 = 2L * layers * n, slab_sz = (long)Kg * n;
+    const float v = init_img[(long)(p / G) * w2 + f % w2];
+    const long slab = f / slab_sz, within = f - slab * slab_sz;
+    const long row = within / n, col = within - row * n;
+    const long N = (long)B * G * Kg;
+    if (slab < layers) h0[(slab * N + (long)p * Kg + row) * n + col] = v;
+    else c0[((slab - layers) * N + (long)p * Kg + row) * n + col] = v;
+}
+// The selection of one step, one block per image, its groups one after the other.  Group g ranks its candidates (row j of the group,
+// word v) by pen = s[j, v] - lambda * c[v], c[v] = how many hypotheses the groups before it kept with word v at this step (s_word, at
+// most K entries, so c is a count over that short list); two roundings, multiply then subtract, so c == 0 or lambda == 0 leaves s as
+// it is.  beam_block_topk's loop on the penalised copy in `work` (descending, ties to the lower flat index, -inf entries last in index
+// order); values is the UNPENALISED s at the winner, indices the group-local parent * V + word, both where beam_update_kernel reads
+// them with (B * G, Kg).  klive (B, G) is clamped to 0..Kg.  No atomics, no dependence on arrival order.
+__global__ __launch_bounds__(1024) void beam_group_select_kernel(const float* __restrict__ scores, float* __restrict__ work, const int* __restrict__ klive,
+                                                                 int K, int G, int V, int first_step, float lambda, float* __restrict__ values,
+                                                                 int* __restrict__ indices) {
+    __shared__ int s_word[SAT_BEAM_GROUP_MAX_K];
+    __shared__ float s_v[16]; __shared__ long s_i[16];
+    const int b = blockIdx.x, tid = threadIdx.x, Kg = K / G;
+    int kept = 0;                                          // the same in every thread: klive is read by all
+    for (int g = 0; g < G; ++g) {
+        int k = klive[b * G + g];
+        k = k < 0 ? 0 : (k > Kg ? Kg : k);
+        if (k <= 0) continue;
+        const long base = ((long)b * K + (long)g * Kg) * V;
+        const float* x = scores + base; float* wk = work + base;
+        const long n = first_step ? (long)V : (long)k * V;
+        if (kept > 0 && lambda != 0.f) {
+            for (long i = tid; i < n; i += 1024) {
+                const int v = (int)(i % V);
+                int c = 0;
+                for (int q = 0; q < kept; ++q) c += s_word[q] == v ? 1 : 0;
+                wk[i] = __fsub_rn(x[i], __fmul_rn(lambda, (float)c));
+            }
+        } else {
+            for (long i = tid; i < n; i += 1024) wk[i] = x[i];
+        }
+        __syncthreads();
+        for (int it = 0; it < k; ++it) {
+            float bv = -INFINITY; long bi = 0x7fffffffffffffffL;
+            for (long i = tid; i < n; i += 1024) { float v = wk[i]; if (v != v) continue; if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
+            for (int o = 32; o > 0; o >>= 1) {
+                float ov = __shfl_xor(bv, o, 64); long oi = __shfl_xor(bi, o, 64);
+                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
+                const bool found = bi < n;                 // k <= n: only a group asked for more picks than it has candidates misses
+                const int o = b * K + g * Kg + it;
+                values[o] = found ? x[bi] : -INFINITY; indices[o] = found ? (int)bi : 0;
+                s_word[kept + it] = found ? (int)(bi % V) : -1;
+                if (found) wk[bi] = __int_as_float(0x7fc00000);
+            }
+            __syncthreads();
+        }
+        kept += k;
+    }
+}
+// After the last step: prev_row of steps 1 .. S + 1 from group-local to image-level rows (row j of an image belongs to group j / Kg),
+// and the finished lists of the (image, group) pairs, g_* (B * G, Kg), compacted into the caller's (B, K) arrays: group ascending,
+// inside a group the append order; fin_row image-level.  Thread e translates one prev_row entry; threads e < B * G copy one list.
+__global__ void beam_group_merge_kernel(int* __restrict__ prev_row, long n_prev, int B, int K, int G, const int* __restrict__ g_count,
+                                        const int* __restrict__ g_step, const int* __restrict__ g_row, const float* __restrict__ g_score,
+                                        const float* __restrict__ g_mean, int* __restrict__ fin_count, int* __restrict__ fin_step,
+                                        int* __restrict__ fin_row, float* __restrict__ fin_score, float* __restrict__ fin_mean) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int Kg = K / G;
+    if (e < n_prev) {
+        const int j = (int)(e % K);
+        int p = prev_row[e];
+        p = p < 0 ? 0 : (p >= Kg ? Kg - 1 : p);
+        prev_row[e] = (j / Kg) * Kg + p;
+    }
+    if (e < (long)B * G) {
+        const int b = (int)(e / G), g = (int)(e - (long)b * G);
+        int off = 0;
+        for (int q = 0; q < g; ++q) { int c = g_count[b * G + q]; off += c < 0 ? 0 : (c > Kg ? Kg : c); }
+        int cnt = g_count[b * G + g];
+        cnt = cnt < 0 ? 0 : (cnt > Kg ? Kg : cnt);
+        for (int f = 0; f < cnt; ++f) {
+            const long s = (long)e * Kg + f, d = (long)b * K + off + f;
+            int r = g_row[s];
+            r = r < 0 ? 0 : (r >= Kg ? Kg - 1 : r);
+            fin_step[d] = g_step[s]; fin_row[d] = g * Kg + r; fin_score[d] = g_score[s]; fin_mean[d] = g_mean[s];
+        }
+        if (g == G - 1) fin_count[b] = off + cnt;
+    }
+}
+
 }  // namespace sat

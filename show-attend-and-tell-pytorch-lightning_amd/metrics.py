@@ -297,3 +297,14 @@ def corpus_chrf(list_of_references, hypotheses, beta=3.0):
     assert len(list_of_references) == len(hypotheses), "one reference set per hypothesis"
     scores = [chrf(references, hypothesis, beta) for references, hypothesis in zip(list_of_references, hypotheses)]
     return sum(scores) / len(scores)
+
+
+def distinct_n(captions, n):
+    """distinct-n of a list of captions (lists of tokens or words): the number of different n-grams over the number of n-grams, pooled
+    over the list (Li et al. 2016).  1.0: no n-gram occurs twice; a list of k copies of one caption without inner repeats gives 1 / k.
+    0.0 when no caption has n tokens.  What a diverse beam buys over a plain one ("Diverse beam search")."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("distinct_n: n=%d is not positive" % n)
+    grams = [g for c in captions for g in _ngrams(list(c), n)]
+    return len(set(grams)) / len(grams) if grams else 0.0

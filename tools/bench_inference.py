@@ -6,7 +6,11 @@ prefix of an image is the first P words of its unconstrained caption; the result
 generator from a fixed seed: the median of ``--repeats`` timed calls after two warm-up calls.
 ``--no-repeat-ngram N`` / ``--min-length M`` / ``--repetition-penalty X`` time the batched search under the history rules (DESIGN.md 5,
 "History rules") next to the plain batched search, alternating the two over ``--repeats`` calls each; ``--skip-loop`` leaves the
-per-image loop (the slowest line, and the check of the result) out."""
+per-image loop (the slowest line, and the check of the result) out.
+``--beam-groups G [G ...]`` / ``--diversity-penalty X`` time the diverse beam search ("Diverse beam search") next to the plain
+batched search at the same beam, alternating over ``--repeats`` calls each (every G must divide the beam); the lines report distinct-1 /
+distinct-2 of the images' full beams (``metrics.distinct_n``, means over the 64 images) and the selection kernel's own time, taken with
+events around ``sat_beam_group_select`` on scores of the search's shape, times the steps of the search."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,10 +32,32 @@ ap.add_argument("--no-repeat-ngram", type=int, default=None, help="no n-gram of 
 ap.add_argument("--min-length", type=int, default=None, help="<END> stays masked until a caption has this many words")
 ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's penalty on the logits of the words already said (1.0 = off)")
 ap.add_argument("--skip-loop", action="store_true")
+ap.add_argument("--beam-groups", type=int, nargs="+", default=None, help="groups of the diverse beam search, each a divisor of every beam (1 = the plain search)")
+ap.add_argument("--diversity-penalty", type=float, default=0.5, help="what a group pays per hypothesis an earlier group kept with the same word at a step")
 a = ap.parse_args()
 constrained = a.topg is not None or a.prefix_len > 0 or a.no_unk
 history = dict(no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty)
 history_on = any(v is not None for v in history.values())
+
+
+
+def select_kernel_ms(beamk, groups, V, steps, lam):
+    """beam_group_select_kernel alone: ``steps`` launches on (64, beamk, V) scores between two events, every group full"""
+    from sat_amd import _lib as L
+    sc = torch.randn(64, beamk, V, device="cuda")
+    kl = torch.full((64, groups), beamk // groups, dtype=torch.int32, device="cuda")
+    work, vals, inds = torch.empty_like(sc), torch.empty(64, beamk, device="cuda"), torch.empty(64, beamk, dtype=torch.int32, device="cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for rep in range(5):
+        e0.record()
+        for _ in range(steps):
+            L.check(L.lib().sat_beam_group_select(L.ptr(sc), L.ptr(kl), 64, beamk, groups, V, 0, lam, L.ptr(work), L.ptr(vals), L.ptr(inds), L.stream_ptr()),
+                    "sat_beam_group_select")
+        e1.record(); torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return statistics.median(out[1:])
+
 
 hp, T, B, R = bench.hparams("c2")
 torch.manual_seed(42)
@@ -41,6 +67,31 @@ with torch.no_grad():
     ann, hw = model.encode(img)
     ann = ann.contiguous()
     for beamk in a.beams:
+        if a.beam_groups:
+            from sat_amd.metrics import distinct_n
+            settings = [("plain", dict(beamk=beamk, max_gen_length=20))]
+            settings += [("G=%d" % g, dict(beamk=beamk, max_gen_length=20, beam_groups=g, diversity_penalty=a.diversity_penalty)) for g in a.beam_groups]
+            times, div = {name: [] for name, _ in settings}, {}
+            for name, kw in settings:
+                for _ in range(2):
+                    every = model.beam_decode_batched(ann, hw, return_all=True, **kw)[0]
+                div[name] = [sum(distinct_n(caps, n) for caps in every) / 64 for n in (1, 2)]
+            for _ in range(a.repeats):                  # alternate, so that every line sees the same machine
+                for name, kw in settings:
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    model.beam_decode_batched(ann, hw, **kw)
+                    torch.cuda.synchronize(); times[name].append(time.perf_counter() - t0)
+            mp = statistics.median(times["plain"])
+            for name, kw in settings:
+                t = times[name]
+                extra = ""
+                if name != "plain":
+                    extra = ", %.3fx the plain line, selection kernel alone %.2f ms for 21 steps" % (
+                        statistics.median(t) / mp, select_kernel_ms(beamk, kw["beam_groups"], hp["vocab_size"], 21, a.diversity_penalty))
+                print("beam %d %s (diversity_penalty=%g): median %.2f ms (min %.2f, max %.2f) per 64 images incl. host back-trace over %d calls, "
+                      "distinct-1 %.3f distinct-2 %.3f%s" % (beamk, name, a.diversity_penalty, statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3,
+                                                              a.repeats, div[name][0], div[name][1], extra))
+            continue
         if history_on:
             plain_kw = dict(beamk=beamk, max_gen_length=20)
             rule_kw = dict(plain_kw, sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, topg=a.topg, no_unk=a.no_unk, **history)

@@ -61,6 +61,8 @@ def main():
     ap.add_argument("--no-repeat-ngram", type=int, default=None, help="no n-gram of this size is said twice in a caption (0 / unset = off)")
     ap.add_argument("--min-length", type=int, default=None, help="<END> stays masked until a caption has this many words")
     ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's penalty on the logits of the words already said (1.0 = off)")
+    ap.add_argument("--beam-groups", type=int, default=None, help="diverse beam search: split the beam into this many groups (a divisor of --beamk; beam sampling)")
+    ap.add_argument("--diversity-penalty", type=float, default=0.5, help="what a group pays per hypothesis an earlier group kept with the same word at a step")
     a = ap.parse_args()
 
     ckpt = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
@@ -92,7 +94,8 @@ def main():
     res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, **(dict(chrf=chars, chrf_beta=a.chrf_beta) if a.chrf else {}), beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
                      sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise,
                      rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward, topg=a.topg,
-                     no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty, **mbr)
+                     no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty,
+                     beam_groups=a.beam_groups, diversity_penalty=a.diversity_penalty, **mbr)
     print("%d images in %d batches" % (res["images"], res["batches"]))
     for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()) + (E.CHRF_KEYS if a.chrf else ()):
         print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))
