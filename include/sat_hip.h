@@ -405,6 +405,47 @@ int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* 
                            const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_groups* groups, int32_t* tok_in,
                            int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score,
                            float* fin_mean, void* workspace, size_t workspace_bytes, void* stream);
+/* Ensemble decoding: ONE beam search over several captioning models ("Ensemble decoding").  Members i = 0 .. M - 1 are
+ * whole decoders, each with its own sizes (L, D, A, m, n, layers, deep_output, precision), parameters and annotations (B, L_i, D_i) of
+ * the same B images; they share the vocabulary (V and the four special ids).  weight[i] >= 0, summing to 1 within 1e-5.  Every member
+ * is fed the same tokens.  At a step with temperature T, for every hypothesis row, with l_i = log_softmax(z_i / T) of member i's logits:
+ *   SAT_ENSEMBLE_ARITHMETIC  a mixture of the distributions: c_v = log sum_i w_i exp(l_i,v), evaluated per word as
+ *                            mx + log sum_i exp(l_i,v + log w_i - mx) with mx the largest exponent
+ *   SAT_ENSEMBLE_GEOMETRIC   a product of experts:           c_v = sum_i w_i l_i,v
+ * members with weight 0 are skipped in both.  The step's score is parent + log_softmax(c)_v (for the mixture that normalisation is zero
+ * up to rounding, for the product it makes c a distribution); the masks, banned ids and history rules then apply as in every search.
+ * That is: the ensemble is a model whose logits are c, searched at temperature 1 with the kernels of the searches above.  After the
+ * update every member's state is gathered through the same parent map.  The outputs have sat_beam_search_batched's layout;
+ * alpha_hist (max_gen_length + 1, B, beamk, L_0) holds member 0's attention (the members' L differ, so there is no common map).
+ * "beam" sampling only.  constraints may carry banned ids; history may carry min_length and no_repeat_ngram; either may be NULL.
+ * SAT_EINVAL before any launch: members outside 1..SAT_ENSEMBLE_MAX, a null member pointer (dims / params / ann), members that differ
+ * in B or V, a weight that is negative or not finite, weights that do not sum to 1 within 1e-5, an unknown combine, topg > 0,
+ * max_prefix > 0, a repetition_penalty other than all-zero bits or 1.0f, a stream that is being captured.
+ * Workspace: sat_beam_search_ensemble_workspace_bytes (the members' search workspaces, the combined logits and one step of attention
+ * maps for every member but the first; it holds the history tables wherever the history rules can run). */
+#define SAT_ENSEMBLE_MAX 8
+#define SAT_ENSEMBLE_ARITHMETIC 0
+#define SAT_ENSEMBLE_GEOMETRIC 1
+typedef struct sat_beam_ensemble {
+    int32_t members;                                     /* 1..SAT_ENSEMBLE_MAX */
+    int32_t combine;                                     /* SAT_ENSEMBLE_* */
+    const sat_decoder_dims* dims[SAT_ENSEMBLE_MAX];      /* per member; B and V agree */
+    const sat_decoder_params* params[SAT_ENSEMBLE_MAX];
+    const float* ann[SAT_ENSEMBLE_MAX];                  /* device (B, L_i, D_i) */
+    float weight[SAT_ENSEMBLE_MAX];                      /* host; >= 0, sum 1 */
+} sat_beam_ensemble;
+size_t sat_beam_search_ensemble_workspace_bytes(const sat_beam_ensemble* ensemble, int32_t beamk, int32_t max_gen_length);
+int sat_beam_search_ensemble(const sat_beam_ensemble* ensemble, int32_t beamk, int32_t max_gen_length, const float* temperatures_host,
+                             int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_constraints* constraints,
+                             const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
+                             int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
+                             void* stream);
+/* The combine kernel of sat_beam_search_ensemble on its own: combined (rows, V) = c as above from `members` device arrays (rows, V).
+ * logits is a HOST array of device pointers, weights a HOST array.  Finite logits give finite output (no -inf, no NaN), however
+ * peaked a member is; a -inf logit contributes no mass.  No atomics: same input, same bits.  SAT_EINVAL before the launch: a null
+ * pointer, members / weights / combine as above, rows or V < 1, a temperature that is not positive. */
+int sat_beam_ensemble_scores(const float* const* logits, const float* weights, int32_t members, int32_t combine, int32_t rows, int32_t V,
+                             float temperature, float* combined, void* stream);
 /* The selection kernel of sat_beam_search_groups on its own: scores (B, beamk, V), klive (B, groups) live rows per group (clamped to
  * 0 .. beamk / groups), first_step != 0 selects from each group's first row only.  Slot g * Kg + t of image b receives the group's t-th
  * pick: values the UNPENALISED score, indices the group-local flat index row * V + word; slots past klive stay untouched.  work is

@@ -99,6 +99,16 @@ class BeamGroups(C.Structure):
     _fields_ = [("groups", C.c_int32), ("diversity_penalty", C.c_float)]
 
 
+ENSEMBLE_MAX = 8                                                                # SAT_ENSEMBLE_MAX
+ENSEMBLE_COMBINE = {"arithmetic": 0, "geometric": 1}                            # SAT_ENSEMBLE_*
+
+
+class BeamEnsemble(C.Structure):
+    """sat_beam_ensemble (include/sat_hip.h)"""
+    _fields_ = [("members", C.c_int32), ("combine", C.c_int32), ("dims", C.POINTER(DecoderDims) * ENSEMBLE_MAX),
+                ("params", C.POINTER(DecoderParams) * ENSEMBLE_MAX), ("ann", C.c_void_p * ENSEMBLE_MAX), ("weight", C.c_float * ENSEMBLE_MAX)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [("offset", C.c_int64)] + [(k, C.c_int32) for k in ("height", "width", "crop_top", "crop_left", "crop_h", "crop_w", "resized_h",
                                                                   "resized_w", "out_top", "out_left", "flip", "reserved")]
@@ -276,6 +286,10 @@ SYMBOLS.update({
                                          C.POINTER(BeamGroups), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "sat_beam_group_select": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp]),
     "sat_beam_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp]),
+    "sat_beam_search_ensemble_workspace_bytes": (C.c_size_t, [C.POINTER(BeamEnsemble), _i32, _i32]),
+    "sat_beam_search_ensemble": (C.c_int, [C.POINTER(BeamEnsemble), _i32, _i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_int32), C.POINTER(BeamConstraints),
+                                           C.POINTER(BeamHistory), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_beam_ensemble_scores": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i32, _i32, _i32, _i32, _f, _vp, _vp]),
     "sat_beam_history_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp, _i32, C.POINTER(BeamHistory), _i32, _i32, _vp, _vp]),
     "sat_topk": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "sat_nucleus_keys": (C.c_int, [_vp, _i32, _i32, _f, _f, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),

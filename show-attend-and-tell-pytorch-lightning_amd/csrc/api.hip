@@ -250,6 +250,34 @@ int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* 
                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history,
                                 groups);
 }
+static int check_ensemble(const sat_beam_ensemble* e, const char* what) {
+    SAT_TRY(beam_ensemble_check(e, what));
+    for (int i = 0; i < e->members; ++i) { SAT_TRY(check_dims(e->dims[i])); SAT_TRY(check_params(e->dims[i], e->params[i], what)); }
+    return SAT_OK;
+}
+size_t sat_beam_search_ensemble_workspace_bytes(const sat_beam_ensemble* ensemble, int32_t beamk, int32_t max_gen_length) {
+    if (beam_ensemble_check(ensemble, "beam_search_ensemble_workspace_bytes") != SAT_OK) return 0;
+    for (int i = 0; i < ensemble->members; ++i) if (check_dims(ensemble->dims[i]) != SAT_OK) return 0;
+    if (beamk < 1 || max_gen_length < 0) { fail(SAT_EINVAL, "beam_search_ensemble_workspace_bytes: beamk %d, max_gen_length %d", beamk, max_gen_length); return 0; }
+    return decoder_beam_ensemble_workspace_bytes(*ensemble, beamk, max_gen_length + 1 <= SAT_CAPTION_MAX_LEN ? max_gen_length + 1 : 0);
+}
+int sat_beam_search_ensemble(const sat_beam_ensemble* ensemble, int32_t beamk, int32_t max_gen_length, const float* temperatures_host,
+                             int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_constraints* constraints,
+                             const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
+                             int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    SAT_TRY(check_ensemble(ensemble, "beam_search_ensemble"));
+    if (!temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
+        return fail(SAT_EINVAL, "beam_search_ensemble: null pointer");
+    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_ensemble: temperature %g", temperatures_host[i]);
+    return decoder_beam_ensemble(*ensemble, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
+                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, constraints, history);
+}
+int sat_beam_ensemble_scores(const float* const* logits, const float* weights, int32_t members, int32_t combine, int32_t rows, int32_t V,
+                             float temperature, float* combined, void* stream) {
+    if (!logits || !weights || !combined) return fail(SAT_EINVAL, "beam_ensemble_scores: null pointer");
+    return beam_ensemble_scores(logits, weights, members, combine, rows, V, temperature, combined, (hipStream_t)stream);
+}
 int sat_beam_group_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t groups, int32_t V, int32_t first_step,
                           float diversity_penalty, float* work, float* values, int32_t* indices, void* stream) {
     if (!scores || !klive || !work || !values || !indices) return fail(SAT_EINVAL, "beam_group_select: null pointer");

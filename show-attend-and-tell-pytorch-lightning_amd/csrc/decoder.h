@@ -39,6 +39,13 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                          float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
                          const sat_beam_constraints* constraints = nullptr, const sat_beam_history* history = nullptr,
                          const sat_beam_groups* groups = nullptr);
+int beam_ensemble_check(const sat_beam_ensemble* e, const char* what);
+size_t decoder_beam_ensemble_workspace_bytes(const sat_beam_ensemble& e, int K, int hist_stride);
+int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length, const float* temps_host, int n_temps, const int* special_host, int* tok_in,
+                          int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws,
+                          size_t ws_bytes, hipStream_t st, const sat_beam_constraints* constraints, const sat_beam_history* history);
+int beam_ensemble_scores(const float* const* logits, const float* weight, int members, int combine, int rows, int V, float temperature, float* combined,
+                         hipStream_t st);
 int launch_attention_bwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
                          const float* alphas, const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
                          int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, void* dhcb = nullptr, const void* annb = nullptr);

@@ -848,6 +848,107 @@ static int launch_nucleus_keys(hipStream_t st, const float* scores, const int* k
     return launch_ok("beam_nucleus_keys");
 }
 
+// words (floats or ints) copied / cleared by a launch
+static void beam_copy_words(hipStream_t st, float* dst, const float* src, long n_) {
+    hipLaunchKernelGGL(copy_words_kernel, dim3(cdiv(n_, 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(dst), reinterpret_cast<const unsigned*>(src), n_);
+}
+static void beam_zero_words(hipStream_t st, void* dst, long n_) {
+    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(n_, 256)), dim3(256), 0, st, reinterpret_cast<int*>(dst), n_, 0);
+}
+// The three parts of the batched search that belong to ONE model; the ensemble search (decoder_beam_ensemble) runs them once per member.
+// once per batch: stacked step weights, the masks, att_enc, the initial states of the K copies (G groups of K / G) of every image
+static int beam_member_begin(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, const BeamWs& w, int K, int G, const int* special_host,
+                             hipStream_t st) {
+    auto copy_f = [&](float* dst, const float* src, long n_) { beam_copy_words(st, dst, src, n_); };
+    auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
+    t_bf16_mfma = d.precision ? 1 : 0;
+    const int B = d.B, N = B * K, n = d.n, A = d.A, D = d.D, m = d.m, NL = d.layers;
+    const int START = special_host[0], PAD = special_host[1], END = special_host[2], UNK = special_host[3];
+    // ---- once per batch: stacked step weights, att_enc, initial states of the K copies of every image
+    copy_f(w.Wcat, p.att_dec, (long)A * n);
+    copy_f(w.Wcat + (long)A * n, p.beta_w, (long)D * n);
+    copy_f(w.Wcat + (long)(A + D) * n, p.w_hh, 4L * n * n);
+    zero_w(w.bcat, A);
+    copy_f(w.bcat + A, p.beta_b, D);
+    SAT_TRY(launch_ok("beam: step weights"));
+    hipLaunchKernelGGL(add_kernel, dim3(cdiv(4 * n, 256)), dim3(256), 0, st, w.bcat + A + D, p.b_ih, p.b_hh, (long)4 * n);
+    SAT_TRY(launch_ok("bias add"));
+    for (int l = 1; l < NL; ++l) {
+        hipLaunchKernelGGL(add_kernel, dim3(cdiv(4 * n, 256)), dim3(256), 0, st, w.bup + (long)(l - 1) * 4 * n, p.up_b_ih[l - 1], p.up_b_hh[l - 1], (long)4 * n);
+        SAT_TRY(launch_ok("bias add (stacked layer)"));
+    }
+    hipLaunchKernelGGL(set4_int_kernel, dim3(1), dim3(1), 0, st, w.mask_first, START, PAD, END, UNK);
+    hipLaunchKernelGGL(set4_int_kernel, dim3(1), dim3(1), 0, st, w.mask_rest, START, PAD, -1, -1);
+    SAT_TRY(launch_ok("beam masks"));
+    SAT_TRY(gemm(st, A_ROW, B_ROW, ann, D, p.att_enc, D, w.U, A, B * d.L, A, D));
+    hipLaunchKernelGGL(ann_mean_kernel, dim3(B), dim3(256), 0, st, ann, w.mean, d.L, D);
+    SAT_TRY(launch_ok("ann_mean"));
+    SAT_TRY(gemm(st, A_ROW, B_ROW, w.mean, D, p.init_f_w, D, w.f, m, B, m, D, 0, EPI_BIAS, p.init_f_b));
+    SAT_TRY(gemm(st, A_ROW, B_ROW, w.f, m, p.init_i_w, m, w.init_img, 2 * n * NL, B, 2 * n * NL, m, 0, EPI_BIAS, p.init_i_b));
+    if (G > 1) {           // a group starts as a beam of K / G rows does (the F3 reshape depends on the row count)
+        hipLaunchKernelGGL(init_expand_groups_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, G, K / G, n, NL);
+        SAT_TRY(launch_ok("init_expand_groups"));
+    } else {
+        hipLaunchKernelGGL(init_expand_images_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, K, n, NL);
+        SAT_TRY(launch_ok("init_expand_images"));
+    }
+    return SAT_OK;
+}
+// one decode step of one model for all rows: w.logits (N, V) and the attention maps alpha (N, L) from the tokens and h, c (updated in place)
+static int beam_member_step(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, const BeamWs& w, const int* tok, float* alpha, float* h,
+                            float* c, const int* live, int K, const sat_beam_sampling* smp, int step, hipStream_t st) {
+    t_bf16_mfma = d.precision ? 1 : 0;
+    const int B = d.B, N = B * K, n = d.n, A = d.A, D = d.D, m = d.m, V = d.V, NL = d.layers, HCW = A + D + 4 * n;
+    const long KS = (long)N * n;
+    float* htop = h + (NL - 1) * KS;
+    // ---- model.py:298-327 for all rows (dead rows: zero attention, state carried, ignored below)
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, tok, w.Y, N, m, d.V, 0.f, 0ull, 0L);
+    SAT_TRY(launch_ok("embedding gather"));
+    const bool noisy = smp && smp->decoder_noise != 0.f;
+    if (noisy) {        // model.py:322-324: randn * decoder_noise / (step + 1) joins h of every layer before the LSTM
+        const long tot = (long)NL * N * n;
+        hipLaunchKernelGGL(beam_state_noise_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, w.noise, live, (long)N, n, NL, smp->decoder_noise / (float)(step + 1),
+                           (unsigned long long)smp->seed, 0x1000ull + step, smp->normals ? smp->normals + (long)step * tot : (const float*)nullptr);
+        SAT_TRY(launch_ok("beam_state_noise"));
+    }
+    if (NL == 1) {
+        SAT_TRY(gemm(st, A_ROW, B_ROW, h, n, w.Wcat, n, w.hc, HCW, N, HCW, n, 0, EPI_BIAS_SIGMOID_RANGE, w.bcat, nullptr, nullptr, nullptr, 0, A, A + D));
+    } else {
+        SAT_TRY(gemm(st, A_ROW, B_ROW, htop, n, w.Wcat, n, w.hc, HCW, N, A + D, n, 0, EPI_BIAS_SIGMOID_RANGE, w.bcat, nullptr, nullptr, nullptr, 0, A, A + D));
+        SAT_TRY(gemm(st, A_ROW, B_ROW, h, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, N, 4 * n, n, 0, EPI_BIAS, w.bcat + A + D));
+    }
+    SAT_TRY(launch_attention_fwd(st, ann, w.U, w.hc, HCW, p.att_f, live, 0, alpha, 1, w.Z, w.XZ, B, K, d.L, D, A, w.sc));
+    if (noisy) SAT_TRY(gemm(st, A_ROW, B_ROW, w.noise, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, N, 4 * n, n, 1));
+    SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, w.hc + A + D, HCW, N, 4 * n, m, 1));
+    SAT_TRY(gemm(st, A_ROW, B_ROW, w.XZ, D, p.w_ih + m, m + D, w.hc + A + D, HCW, N, 4 * n, D, 1));
+    hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, w.hc + A + D, HCW, (const float*)nullptr, c, h, c, h, live, 0, N, n);
+    SAT_TRY(launch_ok("lstm_cell_fwd"));
+    for (int l = 1; l < NL; ++l) {
+        float* hl = h + l * KS; float* cl = c + l * KS;
+        SAT_TRY(gemm(st, A_ROW, B_ROW, hl - KS, n, p.up_w_ih[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 0, EPI_BIAS, w.bup + (long)(l - 1) * 4 * n));
+        SAT_TRY(gemm(st, A_ROW, B_ROW, hl, n, p.up_w_hh[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 1));
+        if (noisy) SAT_TRY(gemm(st, A_ROW, B_ROW, w.noise + l * KS, n, p.up_w_hh[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 1));
+        hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, w.gu, 4 * n, (const float*)nullptr, cl, hl, cl, hl, live, 0, N, n);
+        SAT_TRY(launch_ok("lstm_cell_fwd (stacked layer)"));
+    }
+    SAT_TRY(gemm(st, A_ROW, B_ROW, htop, n, p.out_hidden, n, w.u, m, N, m, n));
+    if (d.deep_output) SAT_TRY(gemm(st, A_ROW, B_ROW, w.Z, D, p.out_context, D, w.u, m, N, m, D, 1, EPI_ADD_TANH, nullptr, nullptr, nullptr, w.Y, m));
+    SAT_TRY(gemm(st, A_ROW, B_ROW, w.u, m, p.out_w, m, w.logits, V, N, V, m, 0, p.out_b ? EPI_BIAS : EPI_NONE, p.out_b));
+    return SAT_OK;
+}
+// the kept hypotheses' parents' states: h, c (layers, N, n) gathered through gmap into h2, c2; the pairs swap
+static int beam_member_gather(const sat_decoder_dims& d, const int* gmap, const int* klive, int Bv, int Kv, int N, float*& h, float*& c, float*& h2, float*& c2,
+                              hipStream_t st) {
+    const int n = d.n, NL = d.layers;
+    const long tot = (long)NL * N * n;
+    hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, h, h2, gmap, klive, Bv, Kv, n, NL);
+    SAT_TRY(launch_ok("beam_gather h"));
+    hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, c, c2, gmap, klive, Bv, Kv, n, NL);
+    SAT_TRY(launch_ok("beam_gather c"));
+    float* t1 = h; h = h2; h2 = t1; t1 = c; c = c2; c2 = t1;
+    return SAT_OK;
+}
+
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
                          int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
@@ -905,41 +1006,10 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     SAT_REQUIRE(method != SAT_SAMPLE_NUCLEUS || (smp->sample_topp > 0.f && smp->sample_topp <= 1.f),
                 "beam_batched: sample_topp %g outside (0, 1] (nucleus sampling)", smp ? (double)smp->sample_topp : 0.0);
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
-    t_bf16_mfma = d.precision ? 1 : 0;
-    const int B = d.B, N = B * K, n = d.n, A = d.A, D = d.D, m = d.m, V = d.V, NL = d.layers, HCW = A + D + 4 * n;
-    const int START = special_host[0], PAD = special_host[1], END = special_host[2], UNK = special_host[3];
-    // ---- once per batch: stacked step weights, att_enc, initial states of the K copies of every image
-    auto copy_f = [&](float* dst, const float* src, long n_) {
-        hipLaunchKernelGGL(copy_words_kernel, dim3(cdiv(n_, 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(dst), reinterpret_cast<const unsigned*>(src), n_);
-    };
-    auto zero_w = [&](void* dst, long n_) { hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(n_, 256)), dim3(256), 0, st, reinterpret_cast<int*>(dst), n_, 0); };
-    copy_f(w.Wcat, p.att_dec, (long)A * n);
-    copy_f(w.Wcat + (long)A * n, p.beta_w, (long)D * n);
-    copy_f(w.Wcat + (long)(A + D) * n, p.w_hh, 4L * n * n);
-    zero_w(w.bcat, A);
-    copy_f(w.bcat + A, p.beta_b, D);
-    SAT_TRY(launch_ok("beam: step weights"));
-    hipLaunchKernelGGL(add_kernel, dim3(cdiv(4 * n, 256)), dim3(256), 0, st, w.bcat + A + D, p.b_ih, p.b_hh, (long)4 * n);
-    SAT_TRY(launch_ok("bias add"));
-    for (int l = 1; l < NL; ++l) {
-        hipLaunchKernelGGL(add_kernel, dim3(cdiv(4 * n, 256)), dim3(256), 0, st, w.bup + (long)(l - 1) * 4 * n, p.up_b_ih[l - 1], p.up_b_hh[l - 1], (long)4 * n);
-        SAT_TRY(launch_ok("bias add (stacked layer)"));
-    }
-    hipLaunchKernelGGL(set4_int_kernel, dim3(1), dim3(1), 0, st, w.mask_first, START, PAD, END, UNK);
-    hipLaunchKernelGGL(set4_int_kernel, dim3(1), dim3(1), 0, st, w.mask_rest, START, PAD, -1, -1);
-    SAT_TRY(launch_ok("beam masks"));
-    SAT_TRY(gemm(st, A_ROW, B_ROW, ann, D, p.att_enc, D, w.U, A, B * d.L, A, D));
-    hipLaunchKernelGGL(ann_mean_kernel, dim3(B), dim3(256), 0, st, ann, w.mean, d.L, D);
-    SAT_TRY(launch_ok("ann_mean"));
-    SAT_TRY(gemm(st, A_ROW, B_ROW, w.mean, D, p.init_f_w, D, w.f, m, B, m, D, 0, EPI_BIAS, p.init_f_b));
-    SAT_TRY(gemm(st, A_ROW, B_ROW, w.f, m, p.init_i_w, m, w.init_img, 2 * n * NL, B, 2 * n * NL, m, 0, EPI_BIAS, p.init_i_b));
-    if (G > 1) {           // a group starts as a beam of K / G rows does (the F3 reshape depends on the row count)
-        hipLaunchKernelGGL(init_expand_groups_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, G, K / G, n, NL);
-        SAT_TRY(launch_ok("init_expand_groups"));
-    } else {
-        hipLaunchKernelGGL(init_expand_images_kernel, dim3(cdiv(2L * NL * N * n, 256)), dim3(256), 0, st, w.init_img, w.h, w.c, B, K, n, NL);
-        SAT_TRY(launch_ok("init_expand_images"));
-    }
+    const int B = d.B, N = B * K, n = d.n, V = d.V, NL = d.layers;
+    const int START = special_host[0], END = special_host[2];
+    SAT_TRY(beam_member_begin(d, p, ann, w, K, G, special_host, st));
+    auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
     // the bookkeeping below the selection sees (image, group) pairs as Bv images of Kv rows; without groups these are B and K
     const int Bv = B * G, Kv = K / G;
     int* const f_count = G > 1 ? w.g_count : fin_count; int* const f_step = G > 1 ? w.g_step : fin_step; int* const f_row = G > 1 ? w.g_row : fin_row;
@@ -962,43 +1032,9 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     for (int step = 0; step <= max_gen_length; ++step) {
         const int* tok = tok_in + (long)step * N;
         float* alpha = alpha_hist + (long)step * N * d.L;
-        const long KS = (long)N * n;
-        float* htop = h + (NL - 1) * KS;
         hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, Bv, Kv);
         SAT_TRY(launch_ok("beam_live"));
-        // ---- model.py:298-327 for all rows (dead rows: zero attention, state carried, ignored below)
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, tok, w.Y, N, m, d.V, 0.f, 0ull, 0L);
-        SAT_TRY(launch_ok("embedding gather"));
-        const bool noisy = smp && smp->decoder_noise != 0.f;
-        if (noisy) {        // model.py:322-324: randn * decoder_noise / (step + 1) joins h of every layer before the LSTM
-            const long tot = (long)NL * N * n;
-            hipLaunchKernelGGL(beam_state_noise_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, w.noise, w.live, (long)N, n, NL, smp->decoder_noise / (float)(step + 1),
-                               (unsigned long long)smp->seed, 0x1000ull + step, smp->normals ? smp->normals + (long)step * tot : (const float*)nullptr);
-            SAT_TRY(launch_ok("beam_state_noise"));
-        }
-        if (NL == 1) {
-            SAT_TRY(gemm(st, A_ROW, B_ROW, h, n, w.Wcat, n, w.hc, HCW, N, HCW, n, 0, EPI_BIAS_SIGMOID_RANGE, w.bcat, nullptr, nullptr, nullptr, 0, A, A + D));
-        } else {
-            SAT_TRY(gemm(st, A_ROW, B_ROW, htop, n, w.Wcat, n, w.hc, HCW, N, A + D, n, 0, EPI_BIAS_SIGMOID_RANGE, w.bcat, nullptr, nullptr, nullptr, 0, A, A + D));
-            SAT_TRY(gemm(st, A_ROW, B_ROW, h, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, N, 4 * n, n, 0, EPI_BIAS, w.bcat + A + D));
-        }
-        SAT_TRY(launch_attention_fwd(st, ann, w.U, w.hc, HCW, p.att_f, w.live, 0, alpha, 1, w.Z, w.XZ, B, K, d.L, D, A, w.sc));
-        if (noisy) SAT_TRY(gemm(st, A_ROW, B_ROW, w.noise, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, N, 4 * n, n, 1));
-        SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, w.hc + A + D, HCW, N, 4 * n, m, 1));
-        SAT_TRY(gemm(st, A_ROW, B_ROW, w.XZ, D, p.w_ih + m, m + D, w.hc + A + D, HCW, N, 4 * n, D, 1));
-        hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, w.hc + A + D, HCW, (const float*)nullptr, c, h, c, h, w.live, 0, N, n);
-        SAT_TRY(launch_ok("lstm_cell_fwd"));
-        for (int l = 1; l < NL; ++l) {
-            float* hl = h + l * KS; float* cl = c + l * KS;
-            SAT_TRY(gemm(st, A_ROW, B_ROW, hl - KS, n, p.up_w_ih[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 0, EPI_BIAS, w.bup + (long)(l - 1) * 4 * n));
-            SAT_TRY(gemm(st, A_ROW, B_ROW, hl, n, p.up_w_hh[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 1));
-            if (noisy) SAT_TRY(gemm(st, A_ROW, B_ROW, w.noise + l * KS, n, p.up_w_hh[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 1));
-            hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, w.gu, 4 * n, (const float*)nullptr, cl, hl, cl, hl, w.live, 0, N, n);
-            SAT_TRY(launch_ok("lstm_cell_fwd (stacked layer)"));
-        }
-        SAT_TRY(gemm(st, A_ROW, B_ROW, htop, n, p.out_hidden, n, w.u, m, N, m, n));
-        if (d.deep_output) SAT_TRY(gemm(st, A_ROW, B_ROW, w.Z, D, p.out_context, D, w.u, m, N, m, D, 1, EPI_ADD_TANH, nullptr, nullptr, nullptr, w.Y, m));
-        SAT_TRY(gemm(st, A_ROW, B_ROW, w.u, m, p.out_w, m, w.logits, V, N, V, m, 0, p.out_b ? EPI_BIAS : EPI_NONE, p.out_b));
+        SAT_TRY(beam_member_step(d, p, ann, w, tok, alpha, h, c, w.live, K, smp, step, st));
         // ---- model.py:330-359: log-softmax, special-token masks, parent scores, top-k per image
         const float T = temps_host[step % n_temps];
         if (con) {                                     // per image: forced word (step < P_b), row 0 (step == P_b), the free search after it
@@ -1078,14 +1114,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
             SAT_TRY(launch_ok("beam_history_advance"));
             int* t0 = hcur; hcur = hnext; hnext = t0;
         }
-        if (step < max_gen_length) {
-            const long tot = (long)NL * N * n;
-            hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, h, h2, w.gmap, w.klive, Bv, Kv, n, NL);
-            SAT_TRY(launch_ok("beam_gather h"));
-            hipLaunchKernelGGL(beam_gather_state_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, c, c2, w.gmap, w.klive, Bv, Kv, n, NL);
-            SAT_TRY(launch_ok("beam_gather c"));
-            float* t1 = h; h = h2; h2 = t1; t1 = c; c = c2; c2 = t1;
-        }
+        if (step < max_gen_length) SAT_TRY(beam_member_gather(d, w.gmap, w.klive, Bv, Kv, N, h, c, h2, c2, st));
     }
     if (G > 1) {                                           // group-local parents and per-group finished lists -> the caller's image-level layout
         const long n_prev = (long)(max_gen_length + 1) * N;
@@ -1117,6 +1146,173 @@ int beam_scores(const float* logits, int K, int V, float temperature, const int*
     hipLaunchKernelGGL(beam_scores_kernel, dim3(K), dim3(256), 0, st, logits, V, 1.0f / temperature, masked, n_masked, parent, scores);
     return launch_ok("beam_scores");
 }
+// ------------------------------------------------------------------ ensemble decoding ("Ensemble decoding")
+// weights and combine of an ensemble: well-formed?  (include/sat_hip.h, sat_beam_ensemble)
+int beam_ensemble_check_weights(const float* weight, int members, int combine, const char* what) {
+    SAT_REQUIRE(members >= 1 && members <= SAT_ENSEMBLE_MAX, "%s: members %d outside 1..%d", what, members, SAT_ENSEMBLE_MAX);
+    SAT_REQUIRE(combine == SAT_ENSEMBLE_ARITHMETIC || combine == SAT_ENSEMBLE_GEOMETRIC, "%s: combine %d is neither arithmetic (%d) nor geometric (%d)", what,
+                combine, SAT_ENSEMBLE_ARITHMETIC, SAT_ENSEMBLE_GEOMETRIC);
+    double sum = 0.0;
+    for (int i = 0; i < members; ++i) {
+        SAT_REQUIRE(weight[i] >= 0.f && weight[i] < INFINITY, "%s: weight[%d] = %g is negative or not finite", what, i, (double)weight[i]);
+        sum += weight[i];
+    }
+    SAT_REQUIRE(fabs(sum - 1.0) <= 1e-5, "%s: the weight entries sum to %.9g, not to 1 (within 1e-5)", what, sum);
+    return SAT_OK;
+}
+int beam_ensemble_check(const sat_beam_ensemble* e, const char* what) {
+    SAT_REQUIRE(e, "%s: null ensemble struct", what);
+    SAT_REQUIRE(e->members >= 1 && e->members <= SAT_ENSEMBLE_MAX, "%s: members %d outside 1..%d", what, e->members, SAT_ENSEMBLE_MAX);
+    for (int i = 0; i < e->members; ++i)
+        SAT_REQUIRE(e->dims[i] && e->params[i] && e->ann[i], "%s: null pointer for member %d (dims / params / ann)", what, i);
+    for (int i = 1; i < e->members; ++i)
+        SAT_REQUIRE(e->dims[i]->B == e->dims[0]->B && e->dims[i]->V == e->dims[0]->V, "%s: member %d has B=%d V=%d, member 0 has B=%d V=%d (one batch, one vocabulary)",
+                    what, i, e->dims[i]->B, e->dims[i]->V, e->dims[0]->B, e->dims[0]->V);
+    return beam_ensemble_check_weights(e->weight, e->members, e->combine, what);
+}
+static EnsembleArgs ensemble_args(const float* const* logits, const float* weight, int members) {
+    EnsembleArgs a;
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) {
+        a.z[i] = i < members ? logits[i] : nullptr;
+        a.w[i] = i < members ? weight[i] : 0.f;
+        a.logw[i] = i < members && weight[i] > 0.f ? logf(weight[i]) : 0.f;
+    }
+    return a;
+}
+int beam_ensemble_scores(const float* const* logits, const float* weight, int members, int combine, int rows, int V, float temperature, float* combined,
+                         hipStream_t st) {
+    SAT_TRY(beam_ensemble_check_weights(weight, members, combine, "beam_ensemble_scores"));
+    SAT_REQUIRE(rows > 0 && V > 0 && temperature > 0.f, "beam_ensemble_scores: bad arguments (rows=%d V=%d temperature=%g)", rows, V, (double)temperature);
+    for (int i = 0; i < members; ++i) SAT_REQUIRE(logits[i], "beam_ensemble_scores: null logits pointer for member %d", i);
+    hipLaunchKernelGGL(beam_ensemble_combine_kernel, dim3(rows), dim3(256), 0, st, ensemble_args(logits, weight, members), members,
+                       combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, V, 1.0f / temperature, combined);
+    return launch_ok("beam_ensemble_combine");
+}
+// the members' search workspaces one after the other (member 0's with the history tables), then the combined logits (N, V) and, for
+// every member but the first, one step's attention maps (N, L_i): alpha_hist is member 0's, the members' L differ
+struct EnsembleWs { size_t total; size_t member[SAT_ENSEMBLE_MAX], alpha[SAT_ENSEMBLE_MAX], combined; };
+static EnsembleWs ensemble_layout(const sat_beam_ensemble& e, int K, int hist_stride) {
+    EnsembleWs w; size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t N = (size_t)e.dims[0]->B * K;
+    for (int i = 0; i < e.members; ++i) w.member[i] = take(beam_layout(*e.dims[i], K, nullptr, 0, i == 0 ? hist_stride : 0).total);
+    w.combined = take(N * e.dims[0]->V * 4);
+    for (int i = 0; i < e.members; ++i) w.alpha[i] = i == 0 ? 0 : take(N * e.dims[i]->L * 4);
+    w.total = off;
+    return w;
+}
+size_t decoder_beam_ensemble_workspace_bytes(const sat_beam_ensemble& e, int K, int hist_stride) { return ensemble_layout(e, K, hist_stride).total; }
+
+// decoder_beam_batched ("beam" sampling; banned ids and the history rules) over M models: every member runs its own once-per-batch
+// block, step and state gather (the three helpers above) on the shared tokens; the members' logits are combined, and the score
+// kernels, the selection, beam_update and the history advance run ONCE, on the combined logits at temperature 1, in member 0's workspace.
+int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length, const float* temps_host, int n_temps, const int* special_host, int* tok_in,
+                          int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws,
+                          size_t ws_bytes, hipStream_t st, const sat_beam_constraints* con, const sat_beam_history* hist) {
+    SAT_TRY(beam_ensemble_check(&e, "beam_ensemble"));
+    const int M = e.members;
+    const sat_decoder_dims& d0 = *e.dims[0];
+    SAT_REQUIRE(!con || con->topg == 0, "beam_ensemble: topg %d does not combine with an ensemble", con ? con->topg : 0);
+    SAT_REQUIRE(!con || con->max_prefix == 0, "beam_ensemble: a forced prefix (max_prefix %d) does not combine with an ensemble", con ? con->max_prefix : 0);
+    SAT_REQUIRE(!hist || hist->repetition_penalty == 0.f || hist->repetition_penalty == 1.0f,
+                "beam_ensemble: repetition_penalty %g does not combine with an ensemble (0 or 1 = off)", hist ? (double)hist->repetition_penalty : 0.0);
+    SAT_TRY(not_capturing(st, "beam_ensemble"));
+    if (con && con->n_banned == 0) con = nullptr;
+    SAT_TRY(beam_history_check(hist, max_gen_length, "beam_history"));
+    const bool hist_on = beam_history_on(hist);
+    const sat_beam_constraints no_constraint = {};
+    if (hist_on) {
+        SAT_REQUIRE(max_gen_length + 1 <= SAT_BEAM_HIST_MAX, "beam_history: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length,
+                    SAT_BEAM_HIST_MAX);
+        if (!con) con = &no_constraint;
+    }
+    if (con) {
+        SAT_REQUIRE(K <= 1024, "beam_constrained: beamk %d above 1024 (one thread per row in the forced steps)", K);
+        SAT_REQUIRE(con->n_banned >= 0 && con->n_banned <= d0.V && (con->n_banned == 0 || con->banned), "beam_constrained: n_banned %d outside 0..V=%d, or null banned",
+                    con->n_banned, d0.V);
+    }
+    const int hist_stride = hist_on ? max_gen_length + 1 : 0;
+    const EnsembleWs lay = ensemble_layout(e, K, hist_stride);
+    SAT_REQUIRE(ws_bytes >= lay.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_ensemble: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes,
+                lay.total, K, max_gen_length);
+    const int B = d0.B, N = B * K, V = d0.V;
+    const int START = special_host[0], END = special_host[2];
+    BeamWs mw[SAT_ENSEMBLE_MAX];
+    float *h[SAT_ENSEMBLE_MAX], *c[SAT_ENSEMBLE_MAX], *h2[SAT_ENSEMBLE_MAX], *c2[SAT_ENSEMBLE_MAX], *scratch_alpha[SAT_ENSEMBLE_MAX];
+    const float* zs[SAT_ENSEMBLE_MAX];
+    for (int i = 0; i < M; ++i) {
+        mw[i] = beam_layout(*e.dims[i], K, ws + lay.member[i], 0, i == 0 ? hist_stride : 0);
+        h[i] = mw[i].h; c[i] = mw[i].c; h2[i] = mw[i].h2; c2[i] = mw[i].c2; zs[i] = mw[i].logits;
+        scratch_alpha[i] = i == 0 ? nullptr : reinterpret_cast<float*>(ws + lay.alpha[i]);
+    }
+    float* const combined = reinterpret_cast<float*>(ws + lay.combined);
+    const BeamWs& w = mw[0];
+    const EnsembleArgs args = ensemble_args(zs, e.weight, M);
+    for (int i = 0; i < M; ++i) SAT_TRY(beam_member_begin(*e.dims[i], *e.params[i], e.ann[i], mw[i], K, 1, special_host, st));
+    auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
+    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, w.klive, (long)B, K);
+    SAT_TRY(launch_ok("fill klive"));
+    zero_w(tok_in, (long)(max_gen_length + 2) * N);
+    zero_w(prev_row, (long)(max_gen_length + 2) * N);
+    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, tok_in, (long)N, START);
+    SAT_TRY(launch_ok("fill start tokens"));
+    for (int i = 0; i < M; ++i) {
+        zero_w(h2[i], (long)e.dims[i]->layers * N * e.dims[i]->n);
+        zero_w(c2[i], (long)e.dims[i]->layers * N * e.dims[i]->n);
+    }
+    zero_w(w.top, N);
+    zero_w(fin_count, B);
+    if (hist_on) { zero_w(w.hist_a, (long)N * hist_stride); zero_w(w.hist_b, (long)N * hist_stride); }
+    SAT_TRY(launch_ok("beam: clears"));
+
+    int *hcur = w.hist_a, *hnext = w.hist_b;
+    for (int step = 0; step <= max_gen_length; ++step) {
+        const int* tok = tok_in + (long)step * N;
+        hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, B, K);
+        SAT_TRY(launch_ok("beam_live"));
+        for (int i = 0; i < M; ++i)
+            SAT_TRY(beam_member_step(*e.dims[i], *e.params[i], e.ann[i], mw[i], tok, i == 0 ? alpha_hist + (long)step * N * d0.L : scratch_alpha[i], h[i], c[i],
+                                     w.live, K, nullptr, step, st));
+        hipLaunchKernelGGL(beam_ensemble_combine_kernel, dim3(N), dim3(256), 0, st, args, M, e.combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, V,
+                           1.0f / temps_host[step % n_temps], combined);
+        SAT_TRY(launch_ok("beam_ensemble_combine"));
+        // the search of a model whose logits are `combined`, at temperature 1
+        if (con) {
+            if (hist_on) {
+                hipLaunchKernelGGL(beam_history_scores_kernel, dim3(N), dim3(256), 0, st, combined, K, V, 1.0f, w.mask_first, 4, w.mask_rest, 2, step,
+                                   (const int*)nullptr, 0, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, hcur, (const int*)nullptr,
+                                   hist_stride, hist->no_repeat_ngram, hist->min_length, 1.0f, END, w.scores);
+                SAT_TRY(launch_ok("beam_scores (history)"));
+            } else {
+                hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, combined, K, V, 1.0f, w.mask_first, w.mask_rest, step,
+                                   (const int*)nullptr, 0, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, w.scores);
+                SAT_TRY(launch_ok("beam_scores (constrained)"));
+            }
+            hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, (const float*)nullptr, w.cand_val, w.cand_idx, 0, w.work, w.klive, K, V, step,
+                               (const int*)nullptr, (const int*)nullptr, 0, w.vals, w.inds);
+            SAT_TRY(launch_ok("beam_select"));
+        } else {
+            hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, combined, V, 1.0f, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2,
+                               step == 0 ? (const float*)nullptr : w.top, w.scores);
+            SAT_TRY(launch_ok("beam_scores"));
+            hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
+            SAT_TRY(launch_ok("beam_topk"));
+        }
+        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, B, K, V, step, max_gen_length, END, (const int*)nullptr, 0,
+                           tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, fin_count, fin_step, fin_row, fin_score, fin_mean);
+        SAT_TRY(launch_ok("beam_update"));
+        if (hist_on && step < max_gen_length) {
+            hipLaunchKernelGGL(beam_history_advance_kernel, dim3(cdiv((long)N * (step + 1), 256)), dim3(256), 0, st, hcur, hnext, tok_in + (long)(step + 1) * N,
+                               prev_row + (long)(step + 1) * N, w.klive, B, K, hist_stride, step);
+            SAT_TRY(launch_ok("beam_history_advance"));
+            int* t0 = hcur; hcur = hnext; hnext = t0;
+        }
+        if (step < max_gen_length)
+            for (int i = 0; i < M; ++i) SAT_TRY(beam_member_gather(*e.dims[i], w.gmap, w.klive, B, K, N, h[i], c[i], h2[i], c2[i], st));
+    }
+    return SAT_OK;
+}
+
 int beam_history_scores(const float* logits, int rows, int V, float temperature, const int* masked, int n_masked, const float* parent, const int* hist,
                         const int* hist_len, int hist_stride, const sat_beam_history& rules, int step, int end_id, float* scores, hipStream_t st) {
     SAT_TRY(not_capturing(st, "beam_history_scores"));

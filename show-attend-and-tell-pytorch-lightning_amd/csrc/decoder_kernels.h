@@ -1233,6 +1233,113 @@ __global__ __launch_bounds__(256) void beam_scores_kernel(const float* __restric
     for (int k = tid; k < n_masked; k += 256) { int id = masked[k]; if (id >= 0 && id < V) o[id] = -INFINITY; }
 }
 
+// Ensemble decoding ("Ensemble decoding"): combined[r, v] of M members' logits for the same hypothesis row, the logits of
+// the model the shared search then runs on at temperature 1.  With l_i = log_softmax(z_i * inv_temp) of member i's row:
+//   arithmetic (mixture)         c_v = log sum_i w_i exp(l_i,v), as mx + log sum_i exp(l_i,v + log w_i - mx), mx the largest term's exponent
+//   geometric (product of experts) c_v = sum_i w_i l_i,v
+// Members with w_i == 0 are skipped in both (their logw is unused).  One block per row: sweep 1 reads every member's value of a word
+// and keeps M online (max, sum-exp) pairs, reduced over the wave by shuffles and over the four waves through LDS; sweep 2 reads the
+// row again (L2-resident) and writes c.  Finite logits give finite c: every l_i,v is finite, the mixture's sum holds the term 1, and
+// the product is a finite sum.  16-byte loads and stores where every member's row and the output row start 16-byte aligned; the
+// words past the last whole float4, or every word of an unaligned row, go one by one.  No atomics: same input, same bits.
+struct EnsembleArgs {
+    const float* z[SAT_ENSEMBLE_MAX];
+    float w[SAT_ENSEMBLE_MAX];
+    float logw[SAT_ENSEMBLE_MAX];
+};
+__device__ __forceinline__ void ensemble_online(float xv, float& mx, float& sum) {
+    if (xv == -INFINITY) return;                // as beam_scores_row: exp(-inf - mx) = 0
+    if (xv > mx) { sum = sum * __expf(mx - xv) + 1.f; mx = xv; } else sum += __expf(xv - mx);
+}
+__device__ __forceinline__ float ensemble_word(const float (&x)[SAT_ENSEMBLE_MAX], const float (&lse)[SAT_ENSEMBLE_MAX], const EnsembleArgs& a, int M,
+                                               int geometric, float inv_temp) {
+    float t[SAT_ENSEMBLE_MAX];
+    if (geometric) {
+        float c = 0.f;
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M && a.w[i] != 0.f) c += a.w[i] * (x[i] * inv_temp - lse[i]);
+        return c;
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M && a.w[i] != 0.f) { t[i] = x[i] * inv_temp - lse[i] + a.logw[i]; mx = fmaxf(mx, t[i]); }
+    if (mx == -INFINITY) return mx;             // only from -inf logits: every member gives this word no mass
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M && a.w[i] != 0.f) s += __expf(t[i] - mx);
+    return mx + __logf(s);
+}
+__global__ __launch_bounds__(256) void beam_ensemble_combine_kernel(EnsembleArgs a, int M, int geometric, int V, float inv_temp, float* __restrict__ combined) {
+    __shared__ float s_m[SAT_ENSEMBLE_MAX][4], s_s[SAT_ENSEMBLE_MAX][4];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* z[SAT_ENSEMBLE_MAX];
+    float* o = combined + (long)r * V;
+    unsigned long long low = (unsigned long long)o;
+#pragma unroll
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) { z[i] = i < M ? a.z[i] + (long)r * V : nullptr; if (i < M) low |= (unsigned long long)z[i]; }
+    const int n4 = (low & 15) == 0 ? V >> 2 : 0;       // float4 of the row's body; the rest is the scalar tail
+    float mx[SAT_ENSEMBLE_MAX], sum[SAT_ENSEMBLE_MAX];
+#pragma unroll
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) { mx[i] = -INFINITY; sum[i] = 0.f; }
+    for (int q = tid; q < n4; q += 256) {
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) {
+            const float4 v = reinterpret_cast<const float4*>(z[i])[q];
+            ensemble_online(v.x * inv_temp, mx[i], sum[i]); ensemble_online(v.y * inv_temp, mx[i], sum[i]);
+            ensemble_online(v.z * inv_temp, mx[i], sum[i]); ensemble_online(v.w * inv_temp, mx[i], sum[i]);
+        }
+    }
+    for (int v = 4 * n4 + tid; v < V; v += 256) {
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) ensemble_online(z[i][v] * inv_temp, mx[i], sum[i]);
+    }
+    float lse[SAT_ENSEMBLE_MAX];
+#pragma unroll
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) {
+        for (int s = 32; s > 0; s >>= 1) {
+            float om = __shfl_xor(mx[i], s, 64), os = __shfl_xor(sum[i], s, 64);
+            float nm = fmaxf(mx[i], om);
+            float fa = (mx[i] == nm) ? 1.f : __expf(mx[i] - nm), fb = (om == nm) ? 1.f : __expf(om - nm);
+            sum[i] = sum[i] * fa + os * fb; mx[i] = nm;
+        }
+        if ((tid & 63) == 0) { s_m[i][tid >> 6] = mx[i]; s_s[i][tid >> 6] = sum[i]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) {
+        lse[i] = 0.f;
+        if (i < M) {
+            float Mx = fmaxf(fmaxf(s_m[i][0], s_m[i][1]), fmaxf(s_m[i][2], s_m[i][3])), S = 0.f;
+            for (int k = 0; k < 4; ++k) S += (s_m[i][k] == Mx) ? s_s[i][k] : s_s[i][k] * __expf(s_m[i][k] - Mx);
+            lse[i] = Mx + __logf(S);
+        }
+    }
+    float x[SAT_ENSEMBLE_MAX];
+    for (int q = tid; q < n4; q += 256) {
+        float4 v[SAT_ENSEMBLE_MAX], c;
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) v[i] = i < M ? reinterpret_cast<const float4*>(z[i])[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].x;
+        c.x = ensemble_word(x, lse, a, M, geometric, inv_temp);
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].y;
+        c.y = ensemble_word(x, lse, a, M, geometric, inv_temp);
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].z;
+        c.z = ensemble_word(x, lse, a, M, geometric, inv_temp);
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].w;
+        c.w = ensemble_word(x, lse, a, M, geometric, inv_temp);
+        reinterpret_cast<float4*>(o)[q] = c;
+    }
+    for (int v = 4 * n4 + tid; v < V; v += 256) {
+#pragma unroll
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = i < M ? z[i][v] : 0.f;
+        o[v] = ensemble_word(x, lse, a, M, geometric, inv_temp);
+    }
+}
+
 // top-k of a flat array of n >= k floats by a single block of 1024 threads: descending, ties to the lowest index, every index at
 // most once.  wk is a scratch copy of x in which a winner is marked as taken with NaN, which the scan skips -- apart from the -inf
 // of masked, banned and out-of-nucleus entries, so once fewer than k entries above -inf are left the rest of the result is the

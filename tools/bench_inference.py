@@ -10,7 +10,11 @@ per-image loop (the slowest line, and the check of the result) out.
 ``--beam-groups G [G ...]`` / ``--diversity-penalty X`` time the diverse beam search ("Diverse beam search") next to the plain
 batched search at the same beam, alternating over ``--repeats`` calls each (every G must divide the beam); the lines report distinct-1 /
 distinct-2 of the images' full beams (``metrics.distinct_n``, means over the 64 images) and the selection kernel's own time, taken with
-events around ``sat_beam_group_select`` on scores of the search's shape, times the steps of the search."""
+events around ``sat_beam_group_select`` on scores of the search's shape, times the steps of the search.
+``--ensemble M [M ...]`` / ``--ensemble-combine arithmetic|geometric`` time ensemble decoding ("Ensemble decoding") over M
+differently seeded bench models, each on its own encoder's annotations, next to the plain batched search of the first model, alternating
+over ``--repeats`` calls each; the lines report the ratio to M plain searches and the combine kernel's own time and bandwidth, taken with
+events around ``sat_beam_ensemble_scores`` on logits of the search's shape, times the steps of the search."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,6 +38,8 @@ ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's p
 ap.add_argument("--skip-loop", action="store_true")
 ap.add_argument("--beam-groups", type=int, nargs="+", default=None, help="groups of the diverse beam search, each a divisor of every beam (1 = the plain search)")
 ap.add_argument("--diversity-penalty", type=float, default=0.5, help="what a group pays per hypothesis an earlier group kept with the same word at a step")
+ap.add_argument("--ensemble", type=int, nargs="+", default=None, help="member counts of the ensemble search (1 = one model, which delegates to the plain search)")
+ap.add_argument("--ensemble-combine", default="arithmetic", choices=["arithmetic", "geometric"])
 a = ap.parse_args()
 constrained = a.topg is not None or a.prefix_len > 0 or a.no_unk
 history = dict(no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty)
@@ -59,6 +65,25 @@ def select_kernel_ms(beamk, groups, V, steps, lam):
     return statistics.median(out[1:])
 
 
+def combine_kernel_ms(members, rows, V, steps, combine):
+    """beam_ensemble_combine_kernel alone: ``steps`` launches on ``members`` x (rows, V) logits between two events"""
+    import ctypes as C
+    from sat_amd import _lib as L
+    zs = [torch.randn(rows, V, device="cuda") for _ in range(members)]
+    out = torch.empty(rows, V, device="cuda")
+    arr = (C.c_void_p * members)(*[z.data_ptr() for z in zs]); wts = (C.c_float * members)(*([1.0 / members] * members))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for rep in range(5):
+        e0.record()
+        for _ in range(steps):
+            L.check(L.lib().sat_beam_ensemble_scores(arr, wts, members, L.ENSEMBLE_COMBINE[combine], rows, V, 1.0, L.ptr(out), L.stream_ptr()),
+                    "sat_beam_ensemble_scores")
+        e1.record(); torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return statistics.median(times[1:])
+
+
 hp, T, B, R = bench.hparams("c2")
 torch.manual_seed(42)
 model = M.SAT(**hp).cuda().eval(); model.set_precision(a.precision)
@@ -66,7 +91,40 @@ img = torch.rand(64, 3, hp["input_size"], hp["input_size"], device="cuda")
 with torch.no_grad():
     ann, hw = model.encode(img)
     ann = ann.contiguous()
+    members = []
+    if a.ensemble:
+        from sat_amd.ensemble import Ensemble
+        members = [(model, ann)]
+        for i in range(1, max(a.ensemble)):
+            torch.manual_seed(42 + i)
+            other = M.SAT(**hp).cuda().eval(); other.set_precision(a.precision)
+            members.append((other, other.encode(img)[0].contiguous()))
     for beamk in a.beams:
+        if a.ensemble:
+            settings = [("plain", model, ann)]
+            settings += [("M=%d" % m, Ensemble([x[0] for x in members[:m]], combine=a.ensemble_combine), [x[1] for x in members[:m]]) for m in a.ensemble]
+            times, caps = {name: [] for name, _, _ in settings}, {}
+            for name, mod, anns in settings:
+                for _ in range(2):
+                    caps[name] = mod.beam_decode_batched(anns, hw, beamk=beamk, max_gen_length=20)[0]
+            for _ in range(a.repeats):                  # alternate, so that every line sees the same machine
+                for name, mod, anns in settings:
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    mod.beam_decode_batched(anns, hw, beamk=beamk, max_gen_length=20)
+                    torch.cuda.synchronize(); times[name].append(time.perf_counter() - t0)
+            mp = statistics.median(times["plain"])
+            for (name, _, _), m in zip(settings, [0] + list(a.ensemble)):
+                t = times[name]
+                extra = ""
+                if m >= 1:
+                    rows, V = 64 * beamk, hp["vocab_size"]
+                    ms = combine_kernel_ms(m, rows, V, 21, a.ensemble_combine)
+                    extra = (", %.3fx of %d plain searches, %d of 64 captions differ from the first model's, combine kernel alone %.3f ms for 21 steps "
+                             "(%.0f GB/s of (M + 1) N V 4 bytes)" % (statistics.median(t) / (m * mp), m, sum(x != y for x, y in zip(caps[name], caps["plain"])), ms,
+                                                                  21 * (m + 1) * rows * V * 4 / (ms * 1e-3) / 1e9))
+                print("beam %d %s (%s): median %.2f ms (min %.2f, max %.2f) per 64 images incl. host back-trace over %d calls%s"
+                      % (beamk, name, a.ensemble_combine, statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3, a.repeats, extra))
+            continue
         if a.beam_groups:
             from sat_amd.metrics import distinct_n
             settings = [("plain", dict(beamk=beamk, max_gen_length=20))]

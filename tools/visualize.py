@@ -58,6 +58,9 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's penalty on the logits of the words already said (1.0 = off)")
     ap.add_argument("--beam-groups", type=int, default=None, help="diverse beam search: split the beam into this many groups (a divisor of --beamk; beam sampling)")
     ap.add_argument("--diversity-penalty", type=float, default=0.5, help="what a group pays per hypothesis an earlier group kept with the same word at a step")
+    ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="ensemble decoding: further checkpoints over the same vocabulary; one search over all of them (beam sampling)")
+    ap.add_argument("--ensemble-weights", type=float, nargs="+", default=None, help="one weight per model, CHECKPOINT first (default: uniform; normalised to sum 1)")
+    ap.add_argument("--ensemble-combine", default="arithmetic", choices=["arithmetic", "geometric"], help="mix the models' distributions, or multiply them")
     a = ap.parse_args()
     if (a.idx is None) == (a.count is None):
         ap.error("give either --idx or --count")
@@ -66,6 +69,9 @@ def main():
     model = SAT(**dict(ckpt["hyper_parameters"]))
     model.load_state_dict(ckpt["state_dict"])
     model = model.cuda()
+    if a.ensemble:
+        from sat_amd.ensemble import Ensemble
+        model = Ensemble([model] + Ensemble.from_checkpoints(a.ensemble).models, a.ensemble_weights, a.ensemble_combine)
     ds = D.CocoCaptionDataset(a.json or model.hparams.json, a.split, root=a.root)
     mbr = {}
     if a.rescore_method == "MBR":
