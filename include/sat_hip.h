@@ -210,6 +210,40 @@ int sat_scst_prepare(const int32_t* cap_tokens, const int32_t* cap_len, const do
                      float* baseline /* or NULL */, float* advantage, int32_t* caps, int32_t* lengths, float* step_weight, int32_t* count,
                      void* stream);
 
+/* ------------------------------------------------------------------ distillation loss (Hinton et al. 2015; DESIGN.md 5, "Distillation")
+ * Word-level knowledge distillation of M teachers into one student over packed rows.  logits z (P, V): the student's; teachers: a HOST
+ * array of `members` device pointers t_i (P, V); weights: a HOST array, >= 0, summing to 1 within 1e-5; combine: SAT_ENSEMBLE_*;
+ * targets y (P); inv_tau = 1 / tau > 0, the distillation temperature of student and teachers alike; alpha in [0, 1]; smoothing in
+ * [0, 1).  Per row p, with l_i = log_softmax(t_i[p] * inv_tau):
+ *   c      = the combination of the l_i exactly as sat_beam_search_ensemble defines it (mixture or product; members of weight 0 are
+ *            skipped and their logits are not read)
+ *   log q  = log_softmax(c),   s = log_softmax(z[p] * inv_tau)
+ *   soft_p = sum_v q_v (log q_v - s_v) = KL(q || softmax(z[p] * inv_tau)); a word with q_v == 0 adds exactly 0, so finite logits give a
+ *            finite loss and gradient however peaked a teacher is
+ *   hard_p = the row loss of sat_ce_label_smooth_fwd on z[p], y[p], smoothing (NaN for a target outside [0, V): never a stray read);
+ *            the correct-prediction flag is that entry point's too
+ *   out[0] = (1 - alpha) mean_p hard_p + alpha tau^2 mean_p soft_p;  out[1] = mean_p hard_p;  out[2] = mean_p soft_p;  out[3] = accuracy
+ *   dlogits[p][v] = gscale[0] / P * [ (1 - alpha) (softmax(z[p])_v - h_v) + alpha tau (softmax(z[p] * inv_tau)_v - q_v) ], h the smoothed
+ *            target distribution of sat_ce_label_smooth_bwd (a target outside [0, V) leaves its one-hot out)
+ * alpha == 0: the teachers are not read, soft rows and out[2] are 0.  alpha == 1: the hard term is skipped, hard rows and out[1] are 0
+ * (accuracy is still reported).  The row terms are summed in double in a fixed order without atomics: the same input gives the same bits.
+ * Row scratch, written by the forward and read by the backward so that no reduction is redone: lse_rows (P, 2) = logsumexp(z[p]),
+ * logsumexp(z[p] * inv_tau); teacher_lse_rows (P, members) = logsumexp(t_i[p] * inv_tau) (0 for a member that is not read);
+ * cnorm_rows (P) = logsumexp(c); loss_rows (P, 2) = hard_p, soft_p; correct_rows (P).
+ * sat_distill_fwd with dlogits != NULL also writes the gradient for gscale = 1 in the same launch (the rows are still in the cache);
+ * sat_distill_bwd with dlogits_from_fwd != 0 is then the in-place scale by gscale[0] and nothing more (gscale == NULL: no launch).
+ * With dlogits_from_fwd == 0 it produces dlogits from the logits and the scratch.  gscale: device pointer or NULL = 1.
+ * One 256-thread block per row; 16-byte accesses when V % 4 == 0 and the student's, every read teacher's and the gradient's pointer are
+ * 16-byte aligned, 4-byte ones otherwise.  SAT_EINVAL before any launch: a null pointer (a teacher's included), P, V or members < 1,
+ * members > SAT_ENSEMBLE_MAX, a weight that is negative or not finite, weights that do not sum to 1 within 1e-5, an unknown combine,
+ * an inv_tau that is not a positive finite number, alpha outside [0, 1], smoothing outside [0, 1). */
+int sat_distill_fwd(const float* logits, const float* const* teachers, const float* weights, int32_t members, int32_t combine, const int32_t* targets,
+                    int32_t P, int32_t V, float inv_tau, float alpha, float smoothing, float* lse_rows, float* teacher_lse_rows, float* cnorm_rows,
+                    float* loss_rows, int32_t* correct_rows, float* out, float* dlogits /* or NULL */, void* stream);
+int sat_distill_bwd(const float* logits, const float* const* teachers, const float* weights, int32_t members, int32_t combine, const int32_t* targets,
+                    int32_t P, int32_t V, float inv_tau, float alpha, float smoothing, const float* lse_rows, const float* teacher_lse_rows,
+                    const float* cnorm_rows, const float* gscale, int32_t dlogits_from_fwd, float* dlogits, void* stream);
+
 /* ------------------------------------------------------------------ temperature-scaling calibration (temperature_scaling.py:51-59)
  * For packed logits (P, V) and targets (P):  loss(T) = F.cross_entropy(logits / T, targets)  and its derivative
  * dloss/dT = mean_i [ x_iy - sum_j softmax(x_i / T)_j x_ij ] / T^2.  The row maximum does not depend on T > 0, so it is taken once;

@@ -383,6 +383,10 @@ SYMBOLS.update({          # self-critical sequence training (scst.py): the row-w
 })
 SCST_BASELINES = {"greedy": 0, "mean": 1}                                       # SAT_SCST_BASELINE_*
 SCST_MAX_SAMPLES = 256                                                          # SAT_SCST_MAX_SAMPLES
+SYMBOLS.update({          # distillation (distill.py): teachers is a host array of device pointers, weights a host array
+    "sat_distill_fwd": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i32, _i32, _vp, _i32, _i32, _f, _f, _f] + [_vp] * 8),
+    "sat_distill_bwd": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i32, _i32, _vp, _i32, _i32, _f, _f, _f, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+})
 SYMBOLS.update({          # attention overlays (visualize.py)
     "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
     "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),

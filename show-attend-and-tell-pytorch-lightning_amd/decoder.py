@@ -289,6 +289,68 @@ class PolicyNLLFn(torch.autograd.Function):
         return dlogits, None, None, None, None, None, None
 
 
+class DistillFn(torch.autograd.Function):
+    """The distillation loss on packed rows (include/sat_hip.h, sat_distill_fwd):
+    ``(1 - alpha) * CE_smoothed(logits, targets) + alpha * tau^2 * KL(q || softmax(logits / tau))`` with ``q`` the combination of the
+    teachers' distributions at ``tau`` (``combine``: "arithmetic" / "geometric", the ensemble search's).  ``teachers``: a list of (P, V)
+    float32 tensors, ``weights`` host floats summing to 1.  Returns ``(loss, hard, soft, accuracy)``; differentiable in ``logits`` only,
+    the last three are marked non-differentiable.  ``fuse_gradient``: the forward writes the gradient while the rows are in the cache
+    and the backward only scales it in place.  Off by default: measured at C2's (P, V) with 1, 2 and 4 teachers it is no faster than the
+    backward that rebuilds the gradient from the row scratch ("Distillation"), and it keeps one more (P, V) buffer alive
+    between the two."""
+
+    @staticmethod
+    def forward(ctx, logits, targets_i32, teachers, weights, combine, inv_tau, alpha, smoothing, fuse_gradient=False):
+        lib = L.lib()
+        teachers = [t.contiguous() for t in teachers]
+        L.require_gpu(logits, targets_i32, *teachers)
+        logits = logits.contiguous()
+        P, V = logits.shape
+        M = len(teachers)
+        if combine not in L.ENSEMBLE_COMBINE:
+            raise ValueError("DistillFn: combine=%r is none of %r" % (combine, tuple(L.ENSEMBLE_COMBINE)))
+        if not 1 <= M <= L.ENSEMBLE_MAX or len(weights) != M:
+            raise ValueError("DistillFn: %d teachers (1..%d) with %d weights" % (M, L.ENSEMBLE_MAX, len(weights)))
+        if logits.dtype != torch.float32 or targets_i32.dtype != torch.int32 or any(t.dtype != torch.float32 for t in teachers):
+            raise ValueError("DistillFn: logits and teachers are float32, targets are int32")
+        if targets_i32.numel() != P or any(tuple(t.shape) != (P, V) for t in teachers):
+            raise ValueError("DistillFn: %d targets and teachers %s for student logits (%d, %d)" % (targets_i32.numel(), [tuple(t.shape) for t in teachers], P, V))
+        targets_i32 = targets_i32.contiguous()
+        fused = bool(fuse_gradient) and bool(ctx.needs_input_grad[0])
+        f32 = dict(dtype=torch.float32, device=logits.device)
+        lse, tlse, cnorm, rows = torch.empty(P, 2, **f32), torch.empty(P, M, **f32), torch.empty(P, **f32), torch.empty(P, 2, **f32)
+        correct = torch.empty(P, dtype=torch.int32, device=logits.device)
+        out = torch.empty(4, **f32)
+        dlogits = torch.empty_like(logits) if fused else None
+        tarr = (C.c_void_p * M)(*[t.data_ptr() for t in teachers])
+        warr = (C.c_float * M)(*[float(w) for w in weights])
+        args = (M, L.ENSEMBLE_COMBINE[combine], P, V, float(inv_tau), float(alpha), float(smoothing))
+        L.check(lib.sat_distill_fwd(L.ptr(logits), tarr, warr, args[0], args[1], L.ptr(targets_i32), P, V, args[4], args[5], args[6], L.ptr(lse), L.ptr(tlse),
+                                    L.ptr(cnorm), L.ptr(rows), L.ptr(correct), L.ptr(out), L.ptr(dlogits), L.stream_ptr()), "sat_distill_fwd")
+        ctx.save_for_backward(logits, targets_i32, lse, tlse, cnorm)
+        ctx.teachers, ctx.weights, ctx.args, ctx.dlogits, ctx.fused = teachers, [float(w) for w in weights], args, dlogits, fused
+        loss, hard, soft, acc = out[0].clone(), out[1].clone(), out[2].clone(), out[3].clone()
+        ctx.mark_non_differentiable(hard, soft, acc)
+        return loss, hard, soft, acc
+
+    @staticmethod
+    def backward(ctx, gloss, _ghard, _gsoft, _gacc):
+        lib = L.lib()
+        logits, targets, lse, tlse, cnorm = ctx.saved_tensors
+        M, combine, P, V, inv_tau, alpha, smoothing = ctx.args
+        fused = ctx.fused
+        if fused and ctx.dlogits is None:
+            raise RuntimeError("DistillFn: the fused gradient was consumed by an earlier backward")
+        dlogits = ctx.dlogits if fused else torch.empty_like(logits)
+        ctx.dlogits = None                     # scaled in place: a second backward would scale it twice
+        g = gloss.reshape(1).to(torch.float32).contiguous()
+        tarr = (C.c_void_p * M)(*[t.data_ptr() for t in ctx.teachers])
+        warr = (C.c_float * M)(*ctx.weights)
+        L.check(lib.sat_distill_bwd(L.ptr(logits), tarr, warr, M, combine, L.ptr(targets), P, V, inv_tau, alpha, smoothing, L.ptr(lse), L.ptr(tlse), L.ptr(cnorm),
+                                    L.ptr(g), int(fused), L.ptr(dlogits), L.stream_ptr()), "sat_distill_bwd")
+        return dlogits, None, None, None, None, None, None, None, None
+
+
 class DoublyStochasticFn(torch.autograd.Function):
     """model.py:594: gamma * ((1 - alphas.sum(dim=1)) ** 2).mean(), fixed-order reduction."""
 

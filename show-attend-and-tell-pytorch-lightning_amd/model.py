@@ -830,6 +830,19 @@ class SAT(SATDecoder, _Base):
         self._step_end(gstep)
         return out
 
+    def distill_step(self, batch, teacher, alpha=0.5, temperature=2.0, targets="references", beamk=3, max_gen_length=20):
+        """Knowledge distillation (Hinton et al. 2015; DESIGN.md 5, "Distillation"): the counterpart of ``training_step`` with a teacher,
+        ``distill.step`` with this module's two host halves around it.  ``teacher``: another ``SAT`` or an ``Ensemble``; ``batch`` is
+        ``training_step``'s.  ``targets="teacher"`` trains on the teacher's best beam caption (``beamk``, ``max_gen_length``) in place of
+        the references.  Returns ``{"loss", "hard", "soft", "accuracy"}`` (device scalars: the loss the trainer back-propagates, the
+        label-smoothed cross entropy, the KL to the teacher and the next-word accuracy)."""
+        from . import distill
+        distill.check_step_args(self, teacher, alpha, temperature, targets, beamk, max_gen_length)        # refuse before any launch
+        _, gstep = self._step_begin()
+        out = distill.step(self, batch, teacher, alpha, temperature, targets, beamk, max_gen_length)
+        self._step_end(gstep)
+        return out
+
     # ------------------------------------------------------------------ validation (model.py:630-718)
     def _log_scalar(self, key, val, step):
         """tensorboard scalar when a Lightning-style logger is attached (model.py:611, 635, 708); a no-op otherwise"""
