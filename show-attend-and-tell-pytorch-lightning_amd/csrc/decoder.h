@@ -39,6 +39,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                          float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
                          const sat_beam_constraints* constraints = nullptr, const sat_beam_history* history = nullptr,
                          const sat_beam_groups* groups = nullptr);
+int beam_ensemble_check_weights(const float* weight, int members, int combine, const char* what);
 int beam_ensemble_check(const sat_beam_ensemble* e, const char* what);
 size_t decoder_beam_ensemble_workspace_bytes(const sat_beam_ensemble& e, int K, int hist_stride);
 int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length, const float* temps_host, int n_temps, const int* special_host, int* tok_in,

@@ -841,11 +841,19 @@ static int not_capturing(hipStream_t st, const char* what) {
     return SAT_OK;
 }
 
-// the keys of one free step of the "nucleus" search: method 1's table layout and hash indexing, (step, row, word)
-static int launch_nucleus_keys(hipStream_t st, const float* scores, const int* klive, int N, int K, int V, const sat_beam_sampling& smp, int step, float* keys) {
-    hipLaunchKernelGGL(beam_nucleus_keys_kernel, dim3(N), dim3(256), 0, st, scores, klive, K, V, smp.sample_topp, (float)step, (unsigned long long)smp.seed,
-                       (unsigned long long)step, smp.gumbel ? smp.gumbel + (long)step * N * V : (const float*)nullptr, keys, (int*)nullptr);
-    return launch_ok("beam_nucleus_keys");
+// the keys of one free step of a sampled search, (step, row, word): "nucleus", or "multinomial" / "topk" (method 1 reads its table by
+// word, method 2 by rank)
+static int launch_sample_keys(hipStream_t st, const float* scores, const int* klive, int N, int K, int V, const sat_beam_sampling& smp, int step, float* keys) {
+    if (smp.method == SAT_SAMPLE_NUCLEUS) {
+        hipLaunchKernelGGL(beam_nucleus_keys_kernel, dim3(N), dim3(256), 0, st, scores, klive, K, V, smp.sample_topp, (float)step, (unsigned long long)smp.seed,
+                           (unsigned long long)step, smp.gumbel ? smp.gumbel + (long)step * N * V : (const float*)nullptr, keys, (int*)nullptr);
+        return launch_ok("beam_nucleus_keys");
+    }
+    const int gstride = smp.method == 1 ? V : smp.sample_topk;
+    hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, scores, klive, K, V, smp.method, smp.sample_topk, (float)step,
+                       (unsigned long long)smp.seed, (unsigned long long)step, smp.gumbel ? smp.gumbel + (long)step * N * gstride : (const float*)nullptr, gstride,
+                       keys);
+    return launch_ok("beam_sample_keys");
 }
 
 // words (floats or ints) copied / cleared by a launch
@@ -949,6 +957,135 @@ static int beam_member_gather(const sat_decoder_dims& d, const int* gmap, const 
     return SAT_OK;
 }
 
+// One model of a search: what the three helpers above need, and where its attention maps go.
+struct BeamMember {
+    const sat_decoder_dims* d; const sat_decoder_params* p; const float* ann;
+    BeamWs w;                                  // h / h2 and c / c2 swap here as the states are gathered
+    float* alpha; long alpha_step;             // step s writes alpha + s * alpha_step (0: one step's scratch)
+};
+// The combine stage of an ensemble: the members' logits at 1 / T -> `combined`, the logits the search then scores at temperature 1.
+struct BeamCombine { EnsembleArgs args; int geometric; float* combined; };
+
+// The search loop of decoder_beam_batched and decoder_beam_ensemble, after their argument checks: M members step on the shared tokens,
+// the scores come from member 0's logits at 1 / T (comb == NULL: the single-model search) or from the combined logits; the score
+// kernels, the selection, beam_update and the history advance run once, in member 0's workspace.  con: NULL, or the constrained
+// search's per-image selection (which the history rules and the groups run in as well); hist: NULL, or the rules that are on.
+static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, int K, int G, float lambda, int max_gen_length, const float* temps_host, int n_temps,
+                            const int* special_host, int* tok_in, int* prev_row, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean,
+                            hipStream_t st, const sat_beam_sampling* smp, const sat_beam_constraints* con, const sat_beam_history* hist) {
+    const BeamWs& w = mem[0].w;
+    const int B = mem[0].d->B, N = B * K, V = mem[0].d->V;
+    const int START = special_host[0], END = special_host[2];
+    const int method = smp ? smp->method : 0;
+    const bool hist_on = hist != nullptr;
+    const int hist_stride = hist_on ? max_gen_length + 1 : 0;
+    const float theta = hist_on && hist->repetition_penalty != 0.f ? hist->repetition_penalty : 1.0f;
+    const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
+    const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
+    for (int i = 0; i < M; ++i) SAT_TRY(beam_member_begin(*mem[i].d, *mem[i].p, mem[i].ann, mem[i].w, K, G, special_host, st));
+    auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
+    // the bookkeeping below the selection sees (image, group) pairs as Bv images of Kv rows; without groups these are B and K
+    const int Bv = B * G, Kv = K / G;
+    int* const f_count = G > 1 ? w.g_count : fin_count; int* const f_step = G > 1 ? w.g_step : fin_step; int* const f_row = G > 1 ? w.g_row : fin_row;
+    float* const f_score = G > 1 ? w.g_score : fin_score; float* const f_mean = G > 1 ? w.g_mean : fin_mean;
+    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(Bv, 256)), dim3(256), 0, st, w.klive, (long)Bv, Kv);
+    SAT_TRY(launch_ok("fill klive"));
+    zero_w(tok_in, (long)(max_gen_length + 2) * N);       // rows that are not live still index the embedding table
+    zero_w(prev_row, (long)(max_gen_length + 2) * N);
+    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, tok_in, (long)N, START);
+    SAT_TRY(launch_ok("fill start tokens"));
+    for (int i = 0; i < M; ++i) {
+        zero_w(mem[i].w.h2, (long)mem[i].d->layers * N * mem[i].d->n);
+        zero_w(mem[i].w.c2, (long)mem[i].d->layers * N * mem[i].d->n);
+    }
+    zero_w(w.top, N);
+    zero_w(f_count, Bv);
+    if (hist_on) { zero_w(w.hist_a, (long)N * hist_stride); zero_w(w.hist_b, (long)N * hist_stride); }
+    SAT_TRY(launch_ok("beam: clears"));
+
+    int *hcur = w.hist_a, *hnext = w.hist_b;
+    for (int step = 0; step <= max_gen_length; ++step) {
+        const int* tok = tok_in + (long)step * N;
+        hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, Bv, Kv);
+        SAT_TRY(launch_ok("beam_live"));
+        for (int i = 0; i < M; ++i)
+            SAT_TRY(beam_member_step(*mem[i].d, *mem[i].p, mem[i].ann, mem[i].w, tok, mem[i].alpha + step * mem[i].alpha_step, mem[i].w.h, mem[i].w.c, w.live, K,
+                                     smp, step, st));
+        // ---- model.py:330-359: log-softmax, special-token masks, parent scores, top-k per image
+        const float inv_T = 1.0f / temps_host[step % n_temps];
+        if (comb) {
+            hipLaunchKernelGGL(beam_ensemble_combine_kernel, dim3(N), dim3(256), 0, st, comb->args, M, comb->geometric, V, inv_T, comb->combined);
+            SAT_TRY(launch_ok("beam_ensemble_combine"));
+        }
+        const float* z = comb ? comb->combined : w.logits;
+        const float inv_temp = comb ? 1.0f : inv_T;
+        const float* parent = step == 0 ? (const float*)nullptr : w.top;
+        const bool drawn = method != 0 && method != SAT_SAMPLE_ANCESTRAL && step > 0;      // the first step always takes the top beamk words (model.py:343)
+        if (con) {                                     // per image: forced word (step < P_b), row 0 (step == P_b), the free search after it
+            if (hist_on) {
+                hipLaunchKernelGGL(beam_history_scores_kernel, dim3(N), dim3(256), 0, st, z, K, V, inv_temp, w.mask_first, 4, w.mask_rest, 2, step, prefix_len,
+                                   max_prefix, con->banned, con->n_banned, parent, hcur, (const int*)nullptr, hist_stride, hist->no_repeat_ngram,
+                                   hist->min_length, theta, END, w.scores);
+                SAT_TRY(launch_ok("beam_scores (history)"));
+            } else {
+                hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, z, K, V, inv_temp, w.mask_first, w.mask_rest, step, prefix_len,
+                                   max_prefix, con->banned, con->n_banned, parent, w.scores);
+                SAT_TRY(launch_ok("beam_scores (constrained)"));
+            }
+            if (topg > 0 && step > 0) {
+                hipLaunchKernelGGL(beam_row_topg_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, topg, step, prefix_len, max_prefix, w.cand_val, w.cand_idx);
+                SAT_TRY(launch_ok("beam_row_topg"));
+            }
+            if (drawn) SAT_TRY(launch_sample_keys(st, w.scores, w.klive, N, K, V, *smp, step, w.keys));
+            if (G > 1) {
+                hipLaunchKernelGGL(beam_group_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, G, V, step == 0 ? 1 : 0, lambda, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_group_select"));
+            } else {
+                hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, drawn ? w.keys : (const float*)nullptr, w.cand_val, w.cand_idx, topg,
+                                   w.work, w.klive, K, V, step, max_prefix > 0 ? con->prefix : (const int*)nullptr, prefix_len, max_prefix, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_select"));
+            }
+        } else {
+            hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, z, V, inv_temp, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2, parent, w.scores);
+            SAT_TRY(launch_ok("beam_scores"));
+            if (method == SAT_SAMPLE_ANCESTRAL) {          // beamk == 1: every step, the first included, is one draw from the row's own distribution
+                hipLaunchKernelGGL(beam_ancestral_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, (unsigned long long)smp->seed,
+                                   (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * V : (const float*)nullptr, w.keys);
+                SAT_TRY(launch_ok("beam_ancestral_keys"));
+            } else if (drawn) {                            // model.py:360-379: draw the continuing hypotheses (Gumbel-top-k == multinomial without replacement)
+                SAT_TRY(launch_sample_keys(st, w.scores, w.klive, N, K, V, *smp, step, w.keys));
+            }
+            const bool keyed = drawn || method == SAT_SAMPLE_ANCESTRAL;
+            hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, keyed ? w.keys : w.scores, w.work, w.klive, K, V, !keyed && step == 0 ? 1 : 0, w.vals,
+                               w.inds);
+            SAT_TRY(launch_ok(keyed ? "beam_topk (keys)" : "beam_topk"));
+        }
+        if (drawn || method == SAT_SAMPLE_ANCESTRAL) {     // the kept hypotheses carry their scores, not their keys
+            hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
+            SAT_TRY(launch_ok("beam_take_scores"));
+        }
+        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(Bv, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, Bv, Kv, V, step, max_gen_length, END, prefix_len, max_prefix,
+                           tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, f_count, f_step, f_row, f_score, f_mean);
+        SAT_TRY(launch_ok("beam_update"));
+        if (hist_on && step < max_gen_length) {
+            hipLaunchKernelGGL(beam_history_advance_kernel, dim3(cdiv((long)N * (step + 1), 256)), dim3(256), 0, st, hcur, hnext, tok_in + (long)(step + 1) * N,
+                               prev_row + (long)(step + 1) * N, w.klive, Bv, Kv, hist_stride, step);
+            SAT_TRY(launch_ok("beam_history_advance"));
+            int* t0 = hcur; hcur = hnext; hnext = t0;
+        }
+        if (step < max_gen_length)
+            for (int i = 0; i < M; ++i)
+                SAT_TRY(beam_member_gather(*mem[i].d, w.gmap, w.klive, Bv, Kv, N, mem[i].w.h, mem[i].w.c, mem[i].w.h2, mem[i].w.c2, st));
+    }
+    if (G > 1) {                                           // group-local parents and per-group finished lists -> the caller's image-level layout
+        const long n_prev = (long)(max_gen_length + 1) * N;
+        hipLaunchKernelGGL(beam_group_merge_kernel, dim3(cdiv(n_prev > Bv ? n_prev : (long)Bv, 256)), dim3(256), 0, st, prev_row + N, n_prev, B, K, G, w.g_count,
+                           w.g_step, w.g_row, w.g_score, w.g_mean, fin_count, fin_step, fin_row, fin_score, fin_mean);
+        SAT_TRY(launch_ok("beam_group_merge"));
+    }
+    return SAT_OK;
+}
+
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
                          int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
@@ -980,7 +1117,6 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     }
     if (G > 1 && !con) con = &no_constraint;
     const int hist_stride = hist_on ? max_gen_length + 1 : 0;
-    const float theta = hist_on && hist->repetition_penalty != 0.f ? hist->repetition_penalty : 1.0f;
     if (con) {
         SAT_REQUIRE(K <= 1024, "beam_constrained: beamk %d above 1024 (one thread per row in the forced steps)", K);
         SAT_REQUIRE(con->topg >= 0 && con->topg <= d.V, "beam_constrained: topg %d outside 1..V=%d (0 = off)", con->topg, d.V);
@@ -991,9 +1127,7 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         SAT_REQUIRE((con->max_prefix == 0 || (con->prefix && con->prefix_len)) && (con->n_banned == 0 || con->banned),
                     "beam_constrained: null pointer (prefix / prefix_len with max_prefix %d, banned with n_banned %d)", con->max_prefix, con->n_banned);
     }
-    const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
-    const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
-    BeamWs w = beam_layout(d, K, ws, topg, hist_stride, G);
+    const BeamWs w = beam_layout(d, K, ws, con ? con->topg : 0, hist_stride, G);
     SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_ANCESTRAL && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
                 "beam_batched: sampling method %d, sample_topk %d", method, smp ? smp->sample_topk : 0);
     if (method == SAT_SAMPLE_ANCESTRAL) {
@@ -1006,123 +1140,9 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     SAT_REQUIRE(method != SAT_SAMPLE_NUCLEUS || (smp->sample_topp > 0.f && smp->sample_topp <= 1.f),
                 "beam_batched: sample_topp %g outside (0, 1] (nucleus sampling)", smp ? (double)smp->sample_topp : 0.0);
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
-    const int B = d.B, N = B * K, n = d.n, V = d.V, NL = d.layers;
-    const int START = special_host[0], END = special_host[2];
-    SAT_TRY(beam_member_begin(d, p, ann, w, K, G, special_host, st));
-    auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
-    // the bookkeeping below the selection sees (image, group) pairs as Bv images of Kv rows; without groups these are B and K
-    const int Bv = B * G, Kv = K / G;
-    int* const f_count = G > 1 ? w.g_count : fin_count; int* const f_step = G > 1 ? w.g_step : fin_step; int* const f_row = G > 1 ? w.g_row : fin_row;
-    float* const f_score = G > 1 ? w.g_score : fin_score; float* const f_mean = G > 1 ? w.g_mean : fin_mean;
-    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(Bv, 256)), dim3(256), 0, st, w.klive, (long)Bv, Kv);
-    SAT_TRY(launch_ok("fill klive"));
-    zero_w(tok_in, (long)(max_gen_length + 2) * N);       // rows that are not live still index the embedding table
-    zero_w(prev_row, (long)(max_gen_length + 2) * N);
-    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, tok_in, (long)N, START);
-    SAT_TRY(launch_ok("fill start tokens"));
-    zero_w(w.h2, (long)NL * N * n);
-    zero_w(w.c2, (long)NL * N * n);
-    zero_w(w.top, N);
-    zero_w(f_count, Bv);
-    if (hist_on) { zero_w(w.hist_a, (long)N * hist_stride); zero_w(w.hist_b, (long)N * hist_stride); }
-    SAT_TRY(launch_ok("beam: clears"));
-
-    float *h = w.h, *c = w.c, *h2 = w.h2, *c2 = w.c2;
-    int *hcur = w.hist_a, *hnext = w.hist_b;
-    for (int step = 0; step <= max_gen_length; ++step) {
-        const int* tok = tok_in + (long)step * N;
-        float* alpha = alpha_hist + (long)step * N * d.L;
-        hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, Bv, Kv);
-        SAT_TRY(launch_ok("beam_live"));
-        SAT_TRY(beam_member_step(d, p, ann, w, tok, alpha, h, c, w.live, K, smp, step, st));
-        // ---- model.py:330-359: log-softmax, special-token masks, parent scores, top-k per image
-        const float T = temps_host[step % n_temps];
-        if (con) {                                     // per image: forced word (step < P_b), row 0 (step == P_b), the free search after it
-            if (hist_on) {
-                hipLaunchKernelGGL(beam_history_scores_kernel, dim3(N), dim3(256), 0, st, w.logits, K, V, 1.0f / T, w.mask_first, 4, w.mask_rest, 2, step, prefix_len,
-                                   max_prefix, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, hcur, (const int*)nullptr, hist_stride,
-                                   hist->no_repeat_ngram, hist->min_length, theta, END, w.scores);
-                SAT_TRY(launch_ok("beam_scores (history)"));
-            } else {
-                hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, w.logits, K, V, 1.0f / T, w.mask_first, w.mask_rest, step, prefix_len,
-                                   max_prefix, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, w.scores);
-                SAT_TRY(launch_ok("beam_scores (constrained)"));
-            }
-            const bool drawn = method != 0 && step > 0;
-            if (topg > 0 && step > 0) {
-                hipLaunchKernelGGL(beam_row_topg_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, topg, step, prefix_len, max_prefix, w.cand_val, w.cand_idx);
-                SAT_TRY(launch_ok("beam_row_topg"));
-            }
-            if (drawn && method == SAT_SAMPLE_NUCLEUS) {
-                SAT_TRY(launch_nucleus_keys(st, w.scores, w.klive, N, K, V, *smp, step, w.keys));
-            } else if (drawn) {
-                const int gstride = method == 1 ? V : smp->sample_topk;
-                hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
-                                   (unsigned long long)smp->seed, (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr,
-                                   gstride, w.keys);
-                SAT_TRY(launch_ok("beam_sample_keys"));
-            }
-            if (G > 1) {
-                hipLaunchKernelGGL(beam_group_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, G, V, step == 0 ? 1 : 0, lambda, w.vals, w.inds);
-                SAT_TRY(launch_ok("beam_group_select"));
-            } else {
-                hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, drawn ? w.keys : (const float*)nullptr, w.cand_val, w.cand_idx, topg,
-                                   w.work, w.klive, K, V, step, max_prefix > 0 ? con->prefix : (const int*)nullptr, prefix_len, max_prefix, w.vals, w.inds);
-                SAT_TRY(launch_ok("beam_select"));
-            }
-            if (drawn) {
-                hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
-                SAT_TRY(launch_ok("beam_take_scores"));
-            }
-        } else {
-            hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, w.logits, V, 1.0f / T, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2,
-                               step == 0 ? (const float*)nullptr : w.top, w.scores);
-            SAT_TRY(launch_ok("beam_scores"));
-            if (method == SAT_SAMPLE_ANCESTRAL) {          // beamk == 1: every step, the first included, is one draw from the row's own distribution
-                hipLaunchKernelGGL(beam_ancestral_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, (unsigned long long)smp->seed,
-                                   (unsigned long long)step, smp->gumbel ? smp->gumbel + (long)step * N * V : (const float*)nullptr, w.keys);
-                SAT_TRY(launch_ok("beam_ancestral_keys"));
-                hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.keys, w.work, w.klive, K, V, 0, w.vals, w.inds);
-                SAT_TRY(launch_ok("beam_topk (keys)"));
-                hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
-                SAT_TRY(launch_ok("beam_take_scores"));
-            } else if (method == 0 || step == 0) {         // the first step always takes the top beamk words (model.py:343)
-                hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
-                SAT_TRY(launch_ok("beam_topk"));
-            } else {                                       // model.py:360-379: draw the continuing hypotheses (Gumbel-top-k == multinomial without replacement)
-                if (method == SAT_SAMPLE_NUCLEUS) {
-                    SAT_TRY(launch_nucleus_keys(st, w.scores, w.klive, N, K, V, *smp, step, w.keys));
-                } else {
-                    const int gstride = method == 1 ? V : smp->sample_topk;
-                    hipLaunchKernelGGL(beam_sample_keys_kernel, dim3(N), dim3(256), 0, st, w.scores, w.klive, K, V, method, smp->sample_topk, (float)step,
-                                       (unsigned long long)smp->seed, (unsigned long long)step,
-                                       smp->gumbel ? smp->gumbel + (long)step * N * gstride : (const float*)nullptr, gstride, w.keys);
-                    SAT_TRY(launch_ok("beam_sample_keys"));
-                }
-                hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.keys, w.work, w.klive, K, V, 0, w.vals, w.inds);
-                SAT_TRY(launch_ok("beam_topk (keys)"));
-                hipLaunchKernelGGL(beam_take_scores_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.scores, w.inds, w.klive, B, K, V, w.vals);
-                SAT_TRY(launch_ok("beam_take_scores"));
-            }
-        }
-        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(Bv, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, Bv, Kv, V, step, max_gen_length, END, prefix_len, max_prefix,
-                           tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, f_count, f_step, f_row, f_score, f_mean);
-        SAT_TRY(launch_ok("beam_update"));
-        if (hist_on && step < max_gen_length) {
-            hipLaunchKernelGGL(beam_history_advance_kernel, dim3(cdiv((long)N * (step + 1), 256)), dim3(256), 0, st, hcur, hnext, tok_in + (long)(step + 1) * N,
-                               prev_row + (long)(step + 1) * N, w.klive, Bv, Kv, hist_stride, step);
-            SAT_TRY(launch_ok("beam_history_advance"));
-            int* t0 = hcur; hcur = hnext; hnext = t0;
-        }
-        if (step < max_gen_length) SAT_TRY(beam_member_gather(d, w.gmap, w.klive, Bv, Kv, N, h, c, h2, c2, st));
-    }
-    if (G > 1) {                                           // group-local parents and per-group finished lists -> the caller's image-level layout
-        const long n_prev = (long)(max_gen_length + 1) * N;
-        hipLaunchKernelGGL(beam_group_merge_kernel, dim3(cdiv(n_prev > Bv ? n_prev : (long)Bv, 256)), dim3(256), 0, st, prev_row + N, n_prev, B, K, G, w.g_count,
-                           w.g_step, w.g_row, w.g_score, w.g_mean, fin_count, fin_step, fin_row, fin_score, fin_mean);
-        SAT_TRY(launch_ok("beam_group_merge"));
-    }
-    return SAT_OK;
+    BeamMember mem = {&d, &p, ann, w, alpha_hist, (long)d.B * K * d.L};
+    return beam_search_loop(&mem, 1, nullptr, K, G, lambda, max_gen_length, temps_host, n_temps, special_host, tok_in, prev_row, fin_count, fin_step, fin_row,
+                            fin_score, fin_mean, st, smp, con, hist_on ? hist : nullptr);
 }
 // sat_beam_groups: well-formed?  (groups 0 and 1 are both "off")
 int beam_groups_check(const sat_beam_groups* g, const char* what) {
@@ -1169,15 +1189,6 @@ int beam_ensemble_check(const sat_beam_ensemble* e, const char* what) {
         SAT_REQUIRE(e->dims[i]->B == e->dims[0]->B && e->dims[i]->V == e->dims[0]->V, "%s: member %d has B=%d V=%d, member 0 has B=%d V=%d (one batch, one vocabulary)",
                     what, i, e->dims[i]->B, e->dims[i]->V, e->dims[0]->B, e->dims[0]->V);
     return beam_ensemble_check_weights(e->weight, e->members, e->combine, what);
-}
-static EnsembleArgs ensemble_args(const float* const* logits, const float* weight, int members) {
-    EnsembleArgs a;
-    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) {
-        a.z[i] = i < members ? logits[i] : nullptr;
-        a.w[i] = i < members ? weight[i] : 0.f;
-        a.logw[i] = i < members && weight[i] > 0.f ? logf(weight[i]) : 0.f;
-    }
-    return a;
 }
 int beam_ensemble_scores(const float* const* logits, const float* weight, int members, int combine, int rows, int V, float temperature, float* combined,
                          hipStream_t st) {
@@ -1235,82 +1246,17 @@ int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length,
     const EnsembleWs lay = ensemble_layout(e, K, hist_stride);
     SAT_REQUIRE(ws_bytes >= lay.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_ensemble: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes,
                 lay.total, K, max_gen_length);
-    const int B = d0.B, N = B * K, V = d0.V;
-    const int START = special_host[0], END = special_host[2];
-    BeamWs mw[SAT_ENSEMBLE_MAX];
-    float *h[SAT_ENSEMBLE_MAX], *c[SAT_ENSEMBLE_MAX], *h2[SAT_ENSEMBLE_MAX], *c2[SAT_ENSEMBLE_MAX], *scratch_alpha[SAT_ENSEMBLE_MAX];
+    const size_t N = (size_t)d0.B * K;
+    BeamMember mem[SAT_ENSEMBLE_MAX];
     const float* zs[SAT_ENSEMBLE_MAX];
-    for (int i = 0; i < M; ++i) {
-        mw[i] = beam_layout(*e.dims[i], K, ws + lay.member[i], 0, i == 0 ? hist_stride : 0);
-        h[i] = mw[i].h; c[i] = mw[i].c; h2[i] = mw[i].h2; c2[i] = mw[i].c2; zs[i] = mw[i].logits;
-        scratch_alpha[i] = i == 0 ? nullptr : reinterpret_cast<float*>(ws + lay.alpha[i]);
+    for (int i = 0; i < M; ++i) {              // alpha_hist is member 0's; the other members' maps (their L differ) are one step's scratch
+        mem[i] = {e.dims[i], e.params[i], e.ann[i], beam_layout(*e.dims[i], K, ws + lay.member[i], 0, i == 0 ? hist_stride : 0),
+                  i == 0 ? alpha_hist : reinterpret_cast<float*>(ws + lay.alpha[i]), i == 0 ? (long)N * d0.L : 0L};
+        zs[i] = mem[i].w.logits;
     }
-    float* const combined = reinterpret_cast<float*>(ws + lay.combined);
-    const BeamWs& w = mw[0];
-    const EnsembleArgs args = ensemble_args(zs, e.weight, M);
-    for (int i = 0; i < M; ++i) SAT_TRY(beam_member_begin(*e.dims[i], *e.params[i], e.ann[i], mw[i], K, 1, special_host, st));
-    auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
-    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, w.klive, (long)B, K);
-    SAT_TRY(launch_ok("fill klive"));
-    zero_w(tok_in, (long)(max_gen_length + 2) * N);
-    zero_w(prev_row, (long)(max_gen_length + 2) * N);
-    hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, tok_in, (long)N, START);
-    SAT_TRY(launch_ok("fill start tokens"));
-    for (int i = 0; i < M; ++i) {
-        zero_w(h2[i], (long)e.dims[i]->layers * N * e.dims[i]->n);
-        zero_w(c2[i], (long)e.dims[i]->layers * N * e.dims[i]->n);
-    }
-    zero_w(w.top, N);
-    zero_w(fin_count, B);
-    if (hist_on) { zero_w(w.hist_a, (long)N * hist_stride); zero_w(w.hist_b, (long)N * hist_stride); }
-    SAT_TRY(launch_ok("beam: clears"));
-
-    int *hcur = w.hist_a, *hnext = w.hist_b;
-    for (int step = 0; step <= max_gen_length; ++step) {
-        const int* tok = tok_in + (long)step * N;
-        hipLaunchKernelGGL(beam_live_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, w.klive, w.live, B, K);
-        SAT_TRY(launch_ok("beam_live"));
-        for (int i = 0; i < M; ++i)
-            SAT_TRY(beam_member_step(*e.dims[i], *e.params[i], e.ann[i], mw[i], tok, i == 0 ? alpha_hist + (long)step * N * d0.L : scratch_alpha[i], h[i], c[i],
-                                     w.live, K, nullptr, step, st));
-        hipLaunchKernelGGL(beam_ensemble_combine_kernel, dim3(N), dim3(256), 0, st, args, M, e.combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, V,
-                           1.0f / temps_host[step % n_temps], combined);
-        SAT_TRY(launch_ok("beam_ensemble_combine"));
-        // the search of a model whose logits are `combined`, at temperature 1
-        if (con) {
-            if (hist_on) {
-                hipLaunchKernelGGL(beam_history_scores_kernel, dim3(N), dim3(256), 0, st, combined, K, V, 1.0f, w.mask_first, 4, w.mask_rest, 2, step,
-                                   (const int*)nullptr, 0, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, hcur, (const int*)nullptr,
-                                   hist_stride, hist->no_repeat_ngram, hist->min_length, 1.0f, END, w.scores);
-                SAT_TRY(launch_ok("beam_scores (history)"));
-            } else {
-                hipLaunchKernelGGL(beam_scores_constrained_kernel, dim3(N), dim3(256), 0, st, combined, K, V, 1.0f, w.mask_first, w.mask_rest, step,
-                                   (const int*)nullptr, 0, con->banned, con->n_banned, step == 0 ? (const float*)nullptr : w.top, w.scores);
-                SAT_TRY(launch_ok("beam_scores (constrained)"));
-            }
-            hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, (const float*)nullptr, w.cand_val, w.cand_idx, 0, w.work, w.klive, K, V, step,
-                               (const int*)nullptr, (const int*)nullptr, 0, w.vals, w.inds);
-            SAT_TRY(launch_ok("beam_select"));
-        } else {
-            hipLaunchKernelGGL(beam_scores_kernel, dim3(N), dim3(256), 0, st, combined, V, 1.0f, step == 0 ? w.mask_first : w.mask_rest, step == 0 ? 4 : 2,
-                               step == 0 ? (const float*)nullptr : w.top, w.scores);
-            SAT_TRY(launch_ok("beam_scores"));
-            hipLaunchKernelGGL(beam_topk_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, V, step == 0 ? 1 : 0, w.vals, w.inds);
-            SAT_TRY(launch_ok("beam_topk"));
-        }
-        hipLaunchKernelGGL(beam_update_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, w.vals, w.inds, w.klive, B, K, V, step, max_gen_length, END, (const int*)nullptr, 0,
-                           tok_in + (long)(step + 1) * N, prev_row + (long)(step + 1) * N, w.top, w.gmap, fin_count, fin_step, fin_row, fin_score, fin_mean);
-        SAT_TRY(launch_ok("beam_update"));
-        if (hist_on && step < max_gen_length) {
-            hipLaunchKernelGGL(beam_history_advance_kernel, dim3(cdiv((long)N * (step + 1), 256)), dim3(256), 0, st, hcur, hnext, tok_in + (long)(step + 1) * N,
-                               prev_row + (long)(step + 1) * N, w.klive, B, K, hist_stride, step);
-            SAT_TRY(launch_ok("beam_history_advance"));
-            int* t0 = hcur; hcur = hnext; hnext = t0;
-        }
-        if (step < max_gen_length)
-            for (int i = 0; i < M; ++i) SAT_TRY(beam_member_gather(*e.dims[i], w.gmap, w.klive, B, K, N, h[i], c[i], h2[i], c2[i], st));
-    }
-    return SAT_OK;
+    const BeamCombine comb = {ensemble_args(zs, e.weight, M), e.combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, reinterpret_cast<float*>(ws + lay.combined)};
+    return beam_search_loop(mem, M, &comb, K, 1, 0.f, max_gen_length, temps_host, n_temps, special_host, tok_in, prev_row, fin_count, fin_step, fin_row, fin_score,
+                            fin_mean, st, nullptr, con, hist_on ? hist : nullptr);
 }
 
 int beam_history_scores(const float* logits, int rows, int V, float temperature, const int* masked, int n_masked, const float* parent, const int* hist,

@@ -12,6 +12,7 @@
 //   time-major padded buffers (T1, N, .) for everything saved for backward.
 #pragma once
 #include "common.h"
+#include "row_reduce.h"
 
 namespace sat {
 
@@ -893,44 +894,33 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
                 const int v = v0 + 256 * u;
                 if (v >= V4) continue;
                 const float e[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                float m4 = fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3]));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {           // ascending index: the first maximum wins, as torch.argmax
                     tot += e[i];
                     if (e[i] > bv) { bv = e[i]; bi = 4 * v + i; }
                 }
-                if (m4 > mx) { sum *= __expf(mx - m4); mx = m4; }          // exp(-inf) = 0 on the first trip
-                if (mx != -INFINITY) sum += (__expf(e[0] - mx) + __expf(e[1] - mx)) + (__expf(e[2] - mx) + __expf(e[3] - mx));
+                lse_unit4(e, mx, sum);
             }
         }
     } else {
         for (int v = tid; v < V; v += 256) {
             float xv = x[v];
             tot += xv;
-            if (xv > bv || (xv == bv && v < bi)) { bv = xv; bi = v; }
-            if (xv > mx) { sum = sum * __expf(mx - xv) + 1.f; mx = xv; } else sum += __expf(xv - mx);
+            if (arg_before(xv, v, bv, bi)) { bv = xv; bi = v; }
+            lse_word(xv, mx, sum);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sum, o, 64);
-        float nm = fmaxf(mx, om);
-        float fa = (mx == nm) ? 1.f : __expf(mx - nm), fb = (om == nm) ? 1.f : __expf(om - nm);   // (-inf) - (-inf) guard
-        sum = sum * fa + os * fb; mx = nm;
-        tot += __shfl_xor(tot, o, 64);
-        float ob = __shfl_xor(bv, o, 64); int oi = __shfl_xor(bi, o, 64);
-        if (ob > bv || (ob == bv && oi < bi)) { bv = ob; bi = oi; }
-    }
-    const int w = tid >> 6;
-    if ((tid & 63) == 0) { s_m[w] = mx; s_s[w] = sum; s_t[w] = tot; s_b[w] = bv; s_i[w] = bi; }
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+    wave_argbest(bv, bi);
+    if ((tid & 63) == 0) { s_t[tid >> 6] = tot; s_b[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+    lse_wave_put(mx, sum, s_m, s_s, tid);
     __syncthreads();
     if (tid == 0) {
-        float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float S = 0.f, Tt = 0.f, Bv = -INFINITY; int Bi = 0x7fffffff;
-        for (int k = 0; k < 4; ++k) {
-            S += (s_m[k] == M) ? s_s[k] : s_s[k] * __expf(s_m[k] - M); Tt += s_t[k];
-            if (s_b[k] > Bv || (s_b[k] == Bv && s_i[k] < Bi)) { Bv = s_b[k]; Bi = s_i[k]; }
-        }
-        const float lse = M + __logf(S);
+        float Tt = 0.f;
+        for (int k = 0; k < 4; ++k) Tt += s_t[k];
+        int Bi = bi;
+        argbest_merge<4>(bv, Bi, s_b, s_i);
+        const float lse = lse_block(s_m, s_s);
         const int t = target[p];
         float nll = lse - x[t];
         float smooth = lse - Tt / (float)V;
@@ -974,13 +964,12 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ 
 
 // out[0] = mean(loss_rows), out[1] = #correct / P   (single block, fixed-order tree)
 __global__ void ce_finish_kernel(const float* __restrict__ loss_rows, const int* __restrict__ correct_rows, int P, float* __restrict__ out) {
-    __shared__ double s_l[256]; __shared__ int s_c[256];
+    __shared__ double s_l[256], s_c[256];
     double s = 0.0; int c = 0;
     for (int p = threadIdx.x; p < P; p += 256) { s += (double)loss_rows[p]; c += correct_rows[p]; }
-    s_l[threadIdx.x] = s; s_c[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) { s_l[threadIdx.x] += s_l[threadIdx.x + o]; s_c[threadIdx.x] += s_c[threadIdx.x + o]; } __syncthreads(); }
-    if (threadIdx.x == 0) { out[0] = (float)(s_l[0] / (double)P); out[1] = (float)s_c[0] / (float)P; }
+    s = block_tree_sum_d(s, s_l);
+    const int correct = (int)block_tree_sum_d((double)c, s_c);             // a count: exact in double in any order
+    if (threadIdx.x == 0) { out[0] = (float)(s / (double)P); out[1] = (float)correct / (float)P; }
 }
 
 // Doubly-stochastic term (model.py:594).  asum[i,l] = sum_t alphas[i,t,l]; part[block] = sum (1-asum)^2
@@ -1004,10 +993,8 @@ __global__ void ds_finish_kernel(const float* __restrict__ part, int nparts, flo
     __shared__ double s_p[256];
     double s = 0.0;
     for (int p = threadIdx.x; p < nparts; p += 256) s += (double)part[p];
-    s_p[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s_p[threadIdx.x] += s_p[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) out[0] = gamma * (float)(s_p[0] / (double)count);
+    s = block_tree_sum_d(s, s_p);
+    if (threadIdx.x == 0) out[0] = gamma * (float)(s / (double)count);
 }
 // dalphas[i,t,l] = gscale[0] * gamma * 2 (asum[i,l] - 1) / (N L)   for every t
 __global__ void ds_grad_kernel(const float* __restrict__ asum, const float* __restrict__ gscale, float gamma, float* __restrict__ dalphas, int N, int T1, int L) {
@@ -1205,22 +1192,10 @@ __global__ void scatter_rows_kernel(const float* __restrict__ src, const int* __
 __device__ __forceinline__ void beam_scores_row(const float* x, int V, float inv_temp, float add, float* o, int tid) {
     __shared__ float s_m[4], s_s[4];
     float mx = -INFINITY, sum = 0.f;
-    for (int v = tid; v < V; v += 256) {
-        float xv = x[v] * inv_temp;
-        if (xv == -INFINITY) continue;          // exp(-inf - mx) = 0; with mx still -inf the difference would be NaN
-        if (xv > mx) { sum = sum * __expf(mx - xv) + 1.f; mx = xv; } else sum += __expf(xv - mx);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sum, o, 64);
-        float nm = fmaxf(mx, om);
-        float fa = (mx == nm) ? 1.f : __expf(mx - nm), fb = (om == nm) ? 1.f : __expf(om - nm);
-        sum = sum * fa + os * fb; mx = nm;
-    }
-    if ((tid & 63) == 0) { s_m[tid >> 6] = mx; s_s[tid >> 6] = sum; }
+    for (int v = tid; v < V; v += 256) lse_word(x[v] * inv_temp, mx, sum);
+    lse_wave_put<true>(mx, sum, s_m, s_s, tid);
     __syncthreads();
-    float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3])), S = 0.f;
-    for (int k = 0; k < 4; ++k) S += (s_m[k] == M) ? s_s[k] : s_s[k] * __expf(s_m[k] - M);
-    const float lse = M + __logf(S);
+    const float lse = lse_block(s_m, s_s);
     for (int v = tid; v < V; v += 256) o[v] = x[v] * inv_temp - lse + add;
     __syncthreads();
 }
@@ -1242,33 +1217,6 @@ __global__ __launch_bounds__(256) void beam_scores_kernel(const float* __restric
 // row again (L2-resident) and writes c.  Finite logits give finite c: every l_i,v is finite, the mixture's sum holds the term 1, and
 // the product is a finite sum.  16-byte loads and stores where every member's row and the output row start 16-byte aligned; the
 // words past the last whole float4, or every word of an unaligned row, go one by one.  No atomics: same input, same bits.
-struct EnsembleArgs {
-    const float* z[SAT_ENSEMBLE_MAX];
-    float w[SAT_ENSEMBLE_MAX];
-    float logw[SAT_ENSEMBLE_MAX];
-};
-__device__ __forceinline__ void ensemble_online(float xv, float& mx, float& sum) {
-    if (xv == -INFINITY) return;                // as beam_scores_row: exp(-inf - mx) = 0
-    if (xv > mx) { sum = sum * __expf(mx - xv) + 1.f; mx = xv; } else sum += __expf(xv - mx);
-}
-__device__ __forceinline__ float ensemble_word(const float (&x)[SAT_ENSEMBLE_MAX], const float (&lse)[SAT_ENSEMBLE_MAX], const EnsembleArgs& a, int M,
-                                               int geometric, float inv_temp) {
-    float t[SAT_ENSEMBLE_MAX];
-    if (geometric) {
-        float c = 0.f;
-#pragma unroll
-        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M && a.w[i] != 0.f) c += a.w[i] * (x[i] * inv_temp - lse[i]);
-        return c;
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M && a.w[i] != 0.f) { t[i] = x[i] * inv_temp - lse[i] + a.logw[i]; mx = fmaxf(mx, t[i]); }
-    if (mx == -INFINITY) return mx;             // only from -inf logits: every member gives this word no mass
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M && a.w[i] != 0.f) s += __expf(t[i] - mx);
-    return mx + __logf(s);
-}
 __global__ __launch_bounds__(256) void beam_ensemble_combine_kernel(EnsembleArgs a, int M, int geometric, int V, float inv_temp, float* __restrict__ combined) {
     __shared__ float s_m[SAT_ENSEMBLE_MAX][4], s_s[SAT_ENSEMBLE_MAX][4];
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -1285,35 +1233,21 @@ __global__ __launch_bounds__(256) void beam_ensemble_combine_kernel(EnsembleArgs
 #pragma unroll
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) {
             const float4 v = reinterpret_cast<const float4*>(z[i])[q];
-            ensemble_online(v.x * inv_temp, mx[i], sum[i]); ensemble_online(v.y * inv_temp, mx[i], sum[i]);
-            ensemble_online(v.z * inv_temp, mx[i], sum[i]); ensemble_online(v.w * inv_temp, mx[i], sum[i]);
+            lse_word(v.x * inv_temp, mx[i], sum[i]); lse_word(v.y * inv_temp, mx[i], sum[i]);
+            lse_word(v.z * inv_temp, mx[i], sum[i]); lse_word(v.w * inv_temp, mx[i], sum[i]);
         }
     }
     for (int v = 4 * n4 + tid; v < V; v += 256) {
 #pragma unroll
-        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) ensemble_online(z[i][v] * inv_temp, mx[i], sum[i]);
+        for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) lse_word(z[i][v] * inv_temp, mx[i], sum[i]);
     }
     float lse[SAT_ENSEMBLE_MAX];
 #pragma unroll
-    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M) {
-        for (int s = 32; s > 0; s >>= 1) {
-            float om = __shfl_xor(mx[i], s, 64), os = __shfl_xor(sum[i], s, 64);
-            float nm = fmaxf(mx[i], om);
-            float fa = (mx[i] == nm) ? 1.f : __expf(mx[i] - nm), fb = (om == nm) ? 1.f : __expf(om - nm);
-            sum[i] = sum[i] * fa + os * fb; mx[i] = nm;
-        }
-        if ((tid & 63) == 0) { s_m[i][tid >> 6] = mx[i]; s_s[i][tid >> 6] = sum[i]; }
-    }
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) if (i < M)
+        lse_wave_put(mx[i], sum[i], s_m[i], s_s[i], tid);
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) {
-        lse[i] = 0.f;
-        if (i < M) {
-            float Mx = fmaxf(fmaxf(s_m[i][0], s_m[i][1]), fmaxf(s_m[i][2], s_m[i][3])), S = 0.f;
-            for (int k = 0; k < 4; ++k) S += (s_m[i][k] == Mx) ? s_s[i][k] : s_s[i][k] * __expf(s_m[i][k] - Mx);
-            lse[i] = Mx + __logf(S);
-        }
-    }
+    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) lse[i] = i < M ? lse_block(s_m[i], s_s[i]) : 0.f;
     float x[SAT_ENSEMBLE_MAX];
     for (int q = tid; q < n4; q += 256) {
         float4 v[SAT_ENSEMBLE_MAX], c;
@@ -1321,22 +1255,22 @@ __global__ __launch_bounds__(256) void beam_ensemble_combine_kernel(EnsembleArgs
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) v[i] = i < M ? reinterpret_cast<const float4*>(z[i])[q] : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].x;
-        c.x = ensemble_word(x, lse, a, M, geometric, inv_temp);
+        c.x = ensemble_word<SAT_ENSEMBLE_MAX>(x, lse, a, M, geometric, inv_temp);
 #pragma unroll
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].y;
-        c.y = ensemble_word(x, lse, a, M, geometric, inv_temp);
+        c.y = ensemble_word<SAT_ENSEMBLE_MAX>(x, lse, a, M, geometric, inv_temp);
 #pragma unroll
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].z;
-        c.z = ensemble_word(x, lse, a, M, geometric, inv_temp);
+        c.z = ensemble_word<SAT_ENSEMBLE_MAX>(x, lse, a, M, geometric, inv_temp);
 #pragma unroll
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = v[i].w;
-        c.w = ensemble_word(x, lse, a, M, geometric, inv_temp);
+        c.w = ensemble_word<SAT_ENSEMBLE_MAX>(x, lse, a, M, geometric, inv_temp);
         reinterpret_cast<float4*>(o)[q] = c;
     }
     for (int v = 4 * n4 + tid; v < V; v += 256) {
 #pragma unroll
         for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) x[i] = i < M ? z[i][v] : 0.f;
-        o[v] = ensemble_word(x, lse, a, M, geometric, inv_temp);
+        o[v] = ensemble_word<SAT_ENSEMBLE_MAX>(x, lse, a, M, geometric, inv_temp);
     }
 }
 
@@ -1346,25 +1280,9 @@ __global__ __launch_bounds__(256) void beam_ensemble_combine_kernel(EnsembleArgs
 // -inf entries in increasing index order (a stable descending sort).  NaN in x is not supported.
 __device__ __forceinline__ void beam_block_topk(const float* __restrict__ x, float* __restrict__ wk, long n, int k, float* __restrict__ values,
                                                 int* __restrict__ indices, int tid) {
-    __shared__ float s_v[16]; __shared__ long s_i[16];
     for (long i = tid; i < n; i += 1024) wk[i] = x[i];
     __syncthreads();
-    for (int it = 0; it < k; ++it) {
-        float bv = -INFINITY; long bi = 0x7fffffffffffffffL;
-        for (long i = tid; i < n; i += 1024) { float v = wk[i]; if (v != v) continue; if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
-        for (int o = 32; o > 0; o >>= 1) {
-            float ov = __shfl_xor(bv, o, 64); long oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-            values[it] = bv; indices[it] = (int)bi;
-            if (bi < n) wk[bi] = __int_as_float(0x7fc00000);
-        }
-        __syncthreads();
-    }
+    block_picks_marking(wk, n, k, [&](int it, float bv, long bi) { values[it] = bv; indices[it] = (int)bi; }, tid);
 }
 // torch.topk on the flattened beam scores of one image (model.py:359), with the tie rule above.  Single block.
 __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ x, float* __restrict__ work, long n, int k,
@@ -1429,7 +1347,7 @@ __global__ __launch_bounds__(256) void beam_sample_keys_kernel(const float* __re
     const int i = blockIdx.x, b = i / K, j = i - b * K, tid = threadIdx.x;
     if (j >= klive[b]) return;
     const float* s = scores + (long)i * V; float* key = keys + (long)i * V;
-    __shared__ float s_v[4]; __shared__ int s_i[4]; __shared__ float s_b; __shared__ int s_bi;
+    __shared__ float s_v[4];
     if (method == 1) {
         const float sc = 20.0f / step;
         float mx = -INFINITY;
@@ -1452,33 +1370,13 @@ __global__ __launch_bounds__(256) void beam_sample_keys_kernel(const float* __re
     } else {
         for (int v = tid; v < V; v += 256) key[v] = -INFINITY;
         __syncthreads();
-        // the row's best sample_topk candidates, one per pass: descending value, ties to the lowest index
-        float lastv = INFINITY; int lasti = -1;
-        for (int t = 0; t < sample_topk; ++t) {
-            float bv = -INFINITY; int bi = 0x7fffffff;
-            for (int v = tid; v < V; v += 256) {
-                const float x = s[v];
-                const bool after = x < lastv || (x == lastv && v > lasti);      // strictly after the previous pick in (value desc, index asc) order
-                if (after && (x > bv || (x == bv && v < bi))) { bv = x; bi = v; }
+        // the row's best sample_topk candidates, one per pass: descending value, ties to the lowest index; stops once none is left
+        block_picks_in_order<4>(V, sample_topk, true, [&](int v, float& x, int& id) { x = s[v]; id = v; }, [&](int t, float bv, int bi) {
+            if (bi < V) {
+                const float g = gumbel ? gumbel[(long)i * gstride + t] : gumbel_of(hash_uniform(seed, stream, (unsigned long long)i * V + t));
+                key[bi] = bv / step + g;
             }
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 1; w < 4; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-                s_b = bv; s_bi = bi;
-                if (bi < V) {
-                    const float g = gumbel ? gumbel[(long)i * gstride + t] : gumbel_of(hash_uniform(seed, stream, (unsigned long long)i * V + t));
-                    key[bi] = bv / step + g;
-                }
-            }
-            __syncthreads();
-            lastv = s_b; lasti = s_bi;
-            if (lasti >= V) break;                        // fewer than sample_topk finite candidates
-        }
+        }, tid);
     }
 }
 // ---- method 4 ("ancestral", DESIGN.md 5 "Self-critical training"): keys[i, v] = s[v] + G[v] for live row i, every step: the arg-max
@@ -1668,29 +1566,9 @@ __global__ __launch_bounds__(256) void beam_row_topg_kernel(const float* __restr
     const int i = blockIdx.x, b = i / K, j = i - b * K, tid = threadIdx.x;
     if (j >= klive[b] || step <= beam_prefix_len(prefix_len, b, max_prefix)) return;
     const float* s = scores + (long)i * V;
-    __shared__ float s_v[4]; __shared__ int s_i[4]; __shared__ float s_b; __shared__ int s_bi;
-    float lastv = INFINITY; int lasti = -1;
-    for (int t = 0; t < g; ++t) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int v = tid; v < V; v += 256) {
-            const float x = s[v];
-            const bool after = x < lastv || (x == lastv && v > lasti);
-            if (after && (x > bv || (x == bv && v < bi))) { bv = x; bi = v; }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-            s_b = bv; s_bi = bi;
-            cand_val[(long)i * g + t] = bv; cand_idx[(long)i * g + t] = bi < V ? j * V + bi : 0x7fffffff;   // g <= V: the row never runs out
-        }
-        __syncthreads();
-        lastv = s_b; lasti = s_bi;
-    }
+    block_picks_in_order<4>(V, g, false, [&](int v, float& x, int& id) { x = s[v]; id = v; }, [&](int t, float bv, int bi) {
+        cand_val[(long)i * g + t] = bv; cand_idx[(long)i * g + t] = bi < V ? j * V + bi : 0x7fffffff;   // g <= V: the row never runs out
+    }, tid);
 }
 // The selection of one step with the per-image branch; one block per image, writes what beam_topk_kernel writes (values and
 // flat indices parent * V + word of the k kept hypotheses).  keys: the sampled search's keys (free steps draw from them) or
@@ -1717,31 +1595,10 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const float* __restri
         beam_block_topk(src + (long)b * K * V, work + (long)b * K * V, step == P ? (long)V : (long)k * V, k, values + b * K, indices + b * K, tid);
         return;
     }
-    __shared__ float s_v[16]; __shared__ int s_i[16]; __shared__ float s_b; __shared__ int s_bi;
     const float* cv = cand_val + (long)b * K * g; const int* ci = cand_idx + (long)b * K * g;
-    const int n = k * g;
-    float lastv = INFINITY; int lasti = -1;
-    for (int it = 0; it < k; ++it) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < n; i += 1024) {
-            const float x = cv[i]; const int id = ci[i];
-            const bool after = x < lastv || (x == lastv && id > lasti);
-            if (after && (x > bv || (x == bv && id < bi))) { bv = x; bi = id; }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-            s_b = bv; s_bi = bi;
-            values[b * K + it] = bv; indices[b * K + it] = bi < K * V ? bi : 0;
-        }
-        __syncthreads();
-        lastv = s_b; lasti = s_bi;
-    }
+    block_picks_in_order<16>(k * g, k, false, [&](int i, float& x, int& id) { x = cv[i]; id = ci[i]; }, [&](int it, float bv, int bi) {
+        values[b * K + it] = bv; indices[b * K + it] = bi < K * V ? bi : 0;
+    }, tid);
 }
 // decoder noise (model.py:322-324): out = N(0, 1) * scale for every layer and live row (0 for dead rows); normals from the table
 // or the hash (Box-Muller).  The noise joins h after attention and the gate were taken from the clean state, so it reaches the
@@ -1914,14 +1771,13 @@ __global__ void init_expand_groups_kernel(const float* __restrict__ init_img, fl
 // The selection of one step, one block per image, its groups one after the other.  Group g ranks its candidates (row j of the group,
 // word v) by pen = s[j, v] - lambda * c[v], c[v] = how many hypotheses the groups before it kept with word v at this step (s_word, at
 // most K entries, so c is a count over that short list); two roundings, multiply then subtract, so c == 0 or lambda == 0 leaves s as
-// it is.  beam_block_topk's loop on the penalised copy in `work` (descending, ties to the lower flat index, -inf entries last in index
+// it is.  beam_block_topk's loop (block_picks_marking) on the penalised copy in `work` (descending, ties to the lower flat index, -inf entries last in index
 // order); values is the UNPENALISED s at the winner, indices the group-local parent * V + word, both where beam_update_kernel reads
 // them with (B * G, Kg).  klive (B, G) is clamped to 0..Kg.  No atomics, no dependence on arrival order.
 __global__ __launch_bounds__(1024) void beam_group_select_kernel(const float* __restrict__ scores, float* __restrict__ work, const int* __restrict__ klive,
                                                                  int K, int G, int V, int first_step, float lambda, float* __restrict__ values,
                                                                  int* __restrict__ indices) {
     __shared__ int s_word[SAT_BEAM_GROUP_MAX_K];
-    __shared__ float s_v[16]; __shared__ long s_i[16];
     const int b = blockIdx.x, tid = threadIdx.x, Kg = K / G;
     int kept = 0;                                          // the same in every thread: klive is read by all
     for (int g = 0; g < G; ++g) {
@@ -1942,25 +1798,12 @@ __global__ __launch_bounds__(1024) void beam_group_select_kernel(const float* __
             for (long i = tid; i < n; i += 1024) wk[i] = x[i];
         }
         __syncthreads();
-        for (int it = 0; it < k; ++it) {
-            float bv = -INFINITY; long bi = 0x7fffffffffffffffL;
-            for (long i = tid; i < n; i += 1024) { float v = wk[i]; if (v != v) continue; if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
-            for (int o = 32; o > 0; o >>= 1) {
-                float ov = __shfl_xor(bv, o, 64); long oi = __shfl_xor(bi, o, 64);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 1; w < 16; ++w) if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-                const bool found = bi < n;                 // k <= n: only a group asked for more picks than it has candidates misses
-                const int o = b * K + g * Kg + it;
-                values[o] = found ? x[bi] : -INFINITY; indices[o] = found ? (int)bi : 0;
-                s_word[kept + it] = found ? (int)(bi % V) : -1;
-                if (found) wk[bi] = __int_as_float(0x7fc00000);
-            }
-            __syncthreads();
-        }
+        block_picks_marking(wk, n, k, [&](int it, float, long bi) {
+            const bool found = bi < n;                     // k <= n: only a group asked for more picks than it has candidates misses
+            const int o = b * K + g * Kg + it;
+            values[o] = found ? x[bi] : -INFINITY; indices[o] = found ? (int)bi : 0;
+            s_word[kept + it] = found ? (int)(bi % V) : -1;
+        }, tid);
         kept += k;
     }
 }

@@ -7,7 +7,7 @@
 // them again from the cache (the same block touched them a moment ago) and folds q, log q - s into one online (max, sum, weighted sum)
 // triple, so the row normaliser of c never needs a pass of its own; sweep 3, when the gradient is asked for, is the third touch.
 // Every sweep issues the loads of U units (a unit: VEC = 4 words of every row read, or 1 on the 4-byte path) before it works on any,
-// ce_rows_kernel's way of keeping loads in flight; the kernels are compiled for MC = 1, 2, 4, 8 members so that the per-member
+// ce_rows_kernel's way of keeping loads in flight (the recurrences themselves are row_reduce.h's); the kernels are compiled for MC = 1, 2, 4, 8 members so that the per-member
 // registers are those of the members there are, and U shrinks as MC grows.
 #include <math.h>
 
@@ -15,15 +15,12 @@
 
 #include "../../include/sat_hip.h"
 #include "common.h"
+#include "decoder.h"
+#include "row_reduce.h"
 
 namespace sat {
 namespace {
 
-struct DistillTeachers {
-    const float* t[SAT_ENSEMBLE_MAX];
-    float w[SAT_ENSEMBLE_MAX];
-    float logw[SAT_ENSEMBLE_MAX];
-};
 struct DistillParams {
     int V, M, geometric;
     float inv_tau, tau, alpha, smoothing, inv_rows;
@@ -46,60 +43,21 @@ __device__ __forceinline__ void store_unit(float* __restrict__ g, int u, const f
     else g[u] = e[0];
 }
 
-// one unit of words e * s into an online (max, sum of exp) pair: one rescale per unit (ce_rows_kernel's recurrence); a -inf word carries
-// no mass.  The student's pair at tau and the teachers' pairs go through this one function, so a teacher that is the student gets the
-// student's bits.
+// one unit of words e * s into an online (max, sum of exp) pair (row_reduce.h).  The student's pair at tau and the teachers' pairs go
+// through this one function, so a teacher that is the student gets the student's bits.
 template <int VEC>
 __device__ __forceinline__ void lse_unit(const float (&e)[VEC], float s, float& mx, float& sum) {
-    float x[VEC], m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) { x[j] = e[j] * s; m = fmaxf(m, x[j]); }
-    if (m > mx) { sum *= __expf(mx - m); mx = m; }              // exp(-inf) = 0 on the first trip
-    if (mx != -INFINITY) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) sum += __expf(x[j] - mx);
+    if constexpr (VEC == 4) {
+        const float x[4] = {e[0] * s, e[1] * s, e[2] * s, e[3] * s};
+        lse_unit4(x, mx, sum);
+    } else {
+        lse_word(e[0] * s, mx, sum);
     }
-}
-// the pair over the wave, then lane 0 of each wave leaves it in s_m[0..3] / s_s[0..3]
-__device__ __forceinline__ void lse_wave(float mx, float sum, float* s_m, float* s_s, int tid) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sum, o, 64);
-        const float nm = fmaxf(mx, om);
-        const float fa = (mx == nm) ? 1.f : __expf(mx - nm), fb = (om == nm) ? 1.f : __expf(om - nm);   // (-inf) - (-inf) guard
-        sum = sum * fa + os * fb; mx = nm;
-    }
-    if ((tid & 63) == 0) { s_m[tid >> 6] = mx; s_s[tid >> 6] = sum; }
-}
-__device__ __forceinline__ float lse_block(const float* s_m, const float* s_s) {
-    const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    float S = 0.f;
-    for (int k = 0; k < 4; ++k) S += (s_m[k] == M) ? s_s[k] : s_s[k] * __expf(s_m[k] - M);
-    return M + __logf(S);
-}
-
-// c of one word from the members' raw logits x and log-sum-exps at tau, as sat_beam_search_ensemble defines it
-template <int MC>
-__device__ __forceinline__ float combine_word(const float (&x)[MC], const float (&lse)[MC], const DistillTeachers& a, int M, int geometric, float inv_tau) {
-    if (geometric) {
-        float c = 0.f;
-#pragma unroll
-        for (int i = 0; i < MC; ++i) if (i < M && a.w[i] != 0.f) c += a.w[i] * (x[i] * inv_tau - lse[i]);
-        return c;
-    }
-    float t[MC];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < MC; ++i) if (i < M && a.w[i] != 0.f) { t[i] = x[i] * inv_tau - lse[i] + a.logw[i]; mx = fmaxf(mx, t[i]); }
-    if (mx == -INFINITY) return mx;             // only from -inf logits: no member gives this word any mass
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MC; ++i) if (i < M && a.w[i] != 0.f) s += __expf(t[i] - mx);
-    return mx + __logf(s);
 }
 
 // U units of the student's row and of every read teacher's, all loads issued before any is used
 template <int VEC, int MC, int U>
-__device__ __forceinline__ void load_batch(const float* __restrict__ z, const float* const (&t)[MC], const DistillTeachers& a, int M, bool soft, int u0, int n,
+__device__ __forceinline__ void load_batch(const float* __restrict__ z, const float* const (&t)[MC], const EnsembleArgs& a, int M, bool soft, int u0, int n,
                                            float (&zx)[U][VEC], float (&tx)[MC][U][VEC]) {
 #pragma unroll
     for (int k = 0; k < U; ++k) {
@@ -116,7 +74,7 @@ __device__ __forceinline__ void load_batch(const float* __restrict__ z, const fl
 // the row's gradient: g[v] = sc * ((1 - alpha) (softmax(z)_v - h_v) + alpha tau (softmax(z inv_tau)_v - q_v)); a target outside [0, V)
 // equals no column, so its one-hot is left out
 template <int VEC, int MC>
-__device__ __forceinline__ void grad_row(const float* __restrict__ z, const float* const (&t)[MC], const DistillTeachers& a, const float (&tlse)[MC],
+__device__ __forceinline__ void grad_row(const float* __restrict__ z, const float* const (&t)[MC], const EnsembleArgs& a, const float (&tlse)[MC],
                                          const DistillParams& k, float lse1, float lse_tau, float cnorm, int target, float sc, float* __restrict__ g,
                                          int tid) {
     constexpr int U = InFlight<MC>::U;
@@ -140,7 +98,7 @@ __device__ __forceinline__ void grad_row(const float* __restrict__ z, const floa
                     float x[MC];
 #pragma unroll
                     for (int i = 0; i < MC; ++i) x[i] = (i < k.M && a.w[i] != 0.f) ? tx[i][b][j] : 0.f;
-                    const float c = combine_word<MC>(x, tlse, a, k.M, k.geometric, k.inv_tau);
+                    const float c = ensemble_word<MC>(x, tlse, a, k.M, k.geometric, k.inv_tau);
                     r += sc_soft * (__expf(zx[b][j] * k.inv_tau - lse_tau) - __expf(c - cnorm));
                 }
                 o[j] = r;
@@ -154,7 +112,7 @@ __device__ __forceinline__ void grad_row(const float* __restrict__ z, const floa
 // weight 0, or when alpha == 0); cnorm_rows[p] = logsumexp(c); loss_rows[2p] = hard, [2p + 1] = soft; correct_rows[p].  A part that
 // alpha switches off is written as 0 and its inputs are not read.  dlogits (or NULL): the gradient with gscale = 1.
 template <int VEC, int MC>
-__global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restrict__ logits, DistillTeachers a, const int* __restrict__ targets, DistillParams k,
+__global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restrict__ logits, EnsembleArgs a, const int* __restrict__ targets, DistillParams k,
                                                            float* __restrict__ lse_rows, float* __restrict__ tlse_rows, float* __restrict__ cnorm_rows,
                                                            float* __restrict__ loss_rows, int* __restrict__ correct_rows, float* __restrict__ dlogits) {
     constexpr int U = InFlight<MC>::U;
@@ -165,7 +123,7 @@ __global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restri
     const float* z = logits + (long)p * V;
     const float* t[MC];
 #pragma unroll
-    for (int i = 0; i < MC; ++i) t[i] = (soft && i < M && a.w[i] != 0.f) ? a.t[i] + (long)p * V : nullptr;
+    for (int i = 0; i < MC; ++i) t[i] = (soft && i < M && a.w[i] != 0.f) ? a.z[i] + (long)p * V : nullptr;
     const int n = V / VEC;
 
     // sweep 1: the log-sum-exps, the row sum and the argmax
@@ -185,7 +143,7 @@ __global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restri
             for (int j = 0; j < VEC; ++j) {                     // ascending index: the first maximum wins, as torch.argmax
                 const float xv = zx[b][j];
                 const int v = u * VEC + j;
-                if (xv > bv || (xv == bv && v < bi)) { bv = xv; bi = v; }
+                if (arg_before(xv, v, bv, bi)) { bv = xv; bi = v; }
                 if (hard) tot += xv;
             }
             if (hard) lse_unit<VEC>(zx[b], 1.f, mx1, sum1);
@@ -196,16 +154,13 @@ __global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restri
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        tot += __shfl_xor(tot, o, 64);
-        const float ob = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ob > bv || (ob == bv && oi < bi)) { bv = ob; bi = oi; }
-    }
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+    wave_argbest(bv, bi);
     if ((tid & 63) == 0) { s_t[tid >> 6] = tot; s_b[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-    lse_wave(mx1, sum1, s_m[MC], s_s[MC], tid);
-    lse_wave(mxt, sumt, s_m[MC + 1], s_s[MC + 1], tid);
+    lse_wave_put(mx1, sum1, s_m[MC], s_s[MC], tid);
+    lse_wave_put(mxt, sumt, s_m[MC + 1], s_s[MC + 1], tid);
 #pragma unroll
-    for (int i = 0; i < MC; ++i) if (soft && i < M && a.w[i] != 0.f) lse_wave(tm[i], ts[i], s_m[i], s_s[i], tid);
+    for (int i = 0; i < MC; ++i) if (soft && i < M && a.w[i] != 0.f) lse_wave_put(tm[i], ts[i], s_m[i], s_s[i], tid);
     __syncthreads();
     const float lse1 = hard ? lse_block(s_m[MC], s_s[MC]) : 0.f;
     const float lse_tau = soft ? lse_block(s_m[MC + 1], s_s[MC + 1]) : 0.f;
@@ -230,7 +185,7 @@ __global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restri
                     float x[MC];
 #pragma unroll
                     for (int i = 0; i < MC; ++i) x[i] = (i < M && a.w[i] != 0.f) ? tx[i][b][j] : 0.f;
-                    c[j] = combine_word<MC>(x, tlse, a, M, k.geometric, k.inv_tau);
+                    c[j] = ensemble_word<MC>(x, tlse, a, M, k.geometric, k.inv_tau);
                     d[j] = c[j] - (zx[b][j] * k.inv_tau - lse_tau);
                     m = fmaxf(m, c[j]);
                 }
@@ -272,8 +227,8 @@ __global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restri
             const float Tt = (s_t[0] + s_t[1]) + (s_t[2] + s_t[3]);
             hl = (target >= 0 && target < V) ? (1.f - k.smoothing) * (lse1 - z[target]) + k.smoothing * (lse1 - Tt / (float)V) : NAN;
         }
-        float Bv = -INFINITY; int Bi = 0x7fffffff;
-        for (int w = 0; w < 4; ++w) if (s_b[w] > Bv || (s_b[w] == Bv && s_i[w] < Bi)) { Bv = s_b[w]; Bi = s_i[w]; }
+        int Bi = bi;
+        argbest_merge<4>(bv, Bi, s_b, s_i);
         lse_rows[2 * (long)p] = lse1; lse_rows[2 * (long)p + 1] = lse_tau;
 #pragma unroll
         for (int i = 0; i < MC; ++i) if (i < M) tlse_rows[(long)p * M + i] = tlse[i];
@@ -286,7 +241,7 @@ __global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restri
 }
 
 template <int VEC, int MC>
-__global__ __launch_bounds__(256) void distill_grad_kernel(const float* __restrict__ logits, DistillTeachers a, const int* __restrict__ targets, DistillParams k,
+__global__ __launch_bounds__(256) void distill_grad_kernel(const float* __restrict__ logits, EnsembleArgs a, const int* __restrict__ targets, DistillParams k,
                                                            const float* __restrict__ lse_rows, const float* __restrict__ tlse_rows,
                                                            const float* __restrict__ cnorm_rows, const float* __restrict__ gscale, float* __restrict__ dlogits) {
     const int p = blockIdx.x, V = k.V, M = k.M;
@@ -296,7 +251,7 @@ __global__ __launch_bounds__(256) void distill_grad_kernel(const float* __restri
 #pragma unroll
     for (int i = 0; i < MC; ++i) {
         const bool used = soft && i < M && a.w[i] != 0.f;
-        t[i] = used ? a.t[i] + (long)p * V : nullptr;
+        t[i] = used ? a.z[i] + (long)p * V : nullptr;
         tlse[i] = used ? tlse_rows[(long)p * M + i] : 0.f;
     }
     const float sc = k.inv_rows * (gscale ? gscale[0] : 1.f);
@@ -323,22 +278,17 @@ __global__ __launch_bounds__(256) void distill_scale_kernel(float* __restrict__ 
 // fixed-order tree.  A part that alpha switches off enters as exactly 0 (its rows are 0, and 0 * NaN cannot arise: the weight is skipped).
 __global__ __launch_bounds__(256) void distill_finish_kernel(const float* __restrict__ loss_rows, const int* __restrict__ correct_rows, int P, float alpha, float tau,
                                                              float* __restrict__ out) {
-    __shared__ double s_h[256], s_k[256];
-    __shared__ int s_c[256];
+    __shared__ double s_h[256], s_k[256], s_c[256];
     double h = 0.0, kl = 0.0; int c = 0;
     for (int p = threadIdx.x; p < P; p += 256) { h += (double)loss_rows[2 * (long)p]; kl += (double)loss_rows[2 * (long)p + 1]; c += correct_rows[p]; }
-    s_h[threadIdx.x] = h; s_k[threadIdx.x] = kl; s_c[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s_h[threadIdx.x] += s_h[threadIdx.x + o]; s_k[threadIdx.x] += s_k[threadIdx.x + o]; s_c[threadIdx.x] += s_c[threadIdx.x + o]; }
-        __syncthreads();
-    }
+    h = block_tree_sum_d(h, s_h); kl = block_tree_sum_d(kl, s_k);
+    const int correct = (int)block_tree_sum_d((double)c, s_c);             // a count: exact in double in any order
     if (threadIdx.x == 0) {
-        const double hm = s_h[0] / (double)P, km = s_k[0] / (double)P;
+        const double hm = h / (double)P, km = kl / (double)P;
         double total = 0.0;
         if (alpha != 1.f) total += (1.0 - (double)alpha) * hm;
         if (alpha != 0.f) total += (double)alpha * (double)tau * (double)tau * km;
-        out[0] = (float)total; out[1] = (float)hm; out[2] = (float)km; out[3] = (float)s_c[0] / (float)P;
+        out[0] = (float)total; out[1] = (float)hm; out[2] = (float)km; out[3] = (float)correct / (float)P;
     }
 }
 
@@ -365,37 +315,20 @@ static int distill_check(const char* what, const float* logits, const float* con
                          const void* cnorm_rows) {
     if (!logits || !teachers || !weights || !targets || !lse_rows || !tlse_rows || !cnorm_rows) return fail(SAT_EINVAL, "%s: null pointer", what);
     if (P < 1 || V < 1) return fail(SAT_EINVAL, "%s: empty input (P=%d V=%d)", what, P, V);
-    if (members < 1 || members > SAT_ENSEMBLE_MAX) return fail(SAT_EINVAL, "%s: members %d outside 1..%d", what, members, SAT_ENSEMBLE_MAX);
-    if (combine != SAT_ENSEMBLE_ARITHMETIC && combine != SAT_ENSEMBLE_GEOMETRIC)
-        return fail(SAT_EINVAL, "%s: combine %d is neither arithmetic (%d) nor geometric (%d)", what, combine, SAT_ENSEMBLE_ARITHMETIC, SAT_ENSEMBLE_GEOMETRIC);
-    double sum = 0.0;
-    for (int i = 0; i < members; ++i) {
+    SAT_TRY(beam_ensemble_check_weights(weights, members, combine, what));
+    for (int i = 0; i < members; ++i)
         if (!teachers[i]) return fail(SAT_EINVAL, "%s: null logits pointer for teacher %d", what, i);
-        if (!(weights[i] >= 0.f && weights[i] < INFINITY)) return fail(SAT_EINVAL, "%s: weight[%d] = %g is negative or not finite", what, i, (double)weights[i]);
-        sum += weights[i];
-    }
-    if (!(fabs(sum - 1.0) <= 1e-5)) return fail(SAT_EINVAL, "%s: the weight entries sum to %.9g, not to 1 (within 1e-5)", what, sum);
     if (!(inv_tau > 0.f) || !(inv_tau < INFINITY)) return fail(SAT_EINVAL, "%s: inv_tau %g is not a positive finite number", what, (double)inv_tau);
     if (!(alpha >= 0.f && alpha <= 1.f)) return fail(SAT_EINVAL, "%s: alpha %g outside [0, 1]", what, (double)alpha);
     if (!(smoothing >= 0.f && smoothing < 1.f)) return fail(SAT_EINVAL, "%s: smoothing %g outside [0, 1)", what, (double)smoothing);
     return SAT_OK;
 }
 
-static DistillTeachers distill_teachers(const float* const* teachers, const float* weights, int members) {
-    DistillTeachers a;
-    for (int i = 0; i < SAT_ENSEMBLE_MAX; ++i) {
-        a.t[i] = i < members ? teachers[i] : nullptr;
-        a.w[i] = i < members ? weights[i] : 0.f;
-        a.logw[i] = i < members && weights[i] > 0.f ? logf(weights[i]) : 0.f;
-    }
-    return a;
-}
-
 // 16-byte accesses: V % 4 == 0 and every array a sweep touches starts 16-byte aligned (the teachers only when they are read)
-static bool distill_wide(const float* logits, const DistillTeachers& a, int members, float alpha, int V, const float* dlogits) {
+static bool distill_wide(const float* logits, const EnsembleArgs& a, int members, float alpha, int V, const float* dlogits) {
     uintptr_t low = (uintptr_t)logits | (uintptr_t)dlogits;
     if (alpha != 0.f)
-        for (int i = 0; i < members; ++i) if (a.w[i] != 0.f) low |= (uintptr_t)a.t[i];
+        for (int i = 0; i < members; ++i) if (a.w[i] != 0.f) low |= (uintptr_t)a.z[i];
     return V % 4 == 0 && low % 16 == 0;
 }
 
@@ -408,7 +341,7 @@ int sat_distill_fwd(const float* logits, const float* const* teachers, const flo
                           cnorm_rows));
     if (!loss_rows || !correct_rows || !out) return fail(SAT_EINVAL, "distill_fwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const DistillTeachers a = distill_teachers(teachers, weights, members);
+    const EnsembleArgs a = ensemble_args(teachers, weights, members);
     const DistillParams k = {V, members, combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, inv_tau, 1.0f / inv_tau, alpha, smoothing, 1.0f / (float)P};
     with_form(distill_wide(logits, a, members, alpha, V, dlogits), members, [&](auto vec, auto mc) {
         hipLaunchKernelGGL((distill_rows_kernel<decltype(vec)::value, decltype(mc)::value>), dim3(P), dim3(256), 0, st, logits, a, targets, k, lse_rows,
@@ -436,7 +369,7 @@ int sat_distill_bwd(const float* logits, const float* const* teachers, const flo
         else hipLaunchKernelGGL(distill_scale_kernel<1>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, dlogits, units, gscale);
         return launch_ok("distill_scale");
     }
-    const DistillTeachers a = distill_teachers(teachers, weights, members);
+    const EnsembleArgs a = ensemble_args(teachers, weights, members);
     const DistillParams k = {V, members, combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, inv_tau, 1.0f / inv_tau, alpha, smoothing, 1.0f / (float)P};
     with_form(distill_wide(logits, a, members, alpha, V, dlogits), members, [&](auto vec, auto mc) {
         hipLaunchKernelGGL((distill_grad_kernel<decltype(vec)::value, decltype(mc)::value>), dim3(P), dim3(256), 0, st, logits, a, targets, k, lse_rows,

@@ -6,6 +6,7 @@
 
 #include "../../include/sat_hip.h"
 #include "common.h"
+#include "row_reduce.h"
 
 namespace sat {
 namespace {
@@ -24,7 +25,7 @@ __device__ __forceinline__ RowMask row_mask(const int* __restrict__ masked_ids, 
 }
 
 // lse_rows[p] = logsumexp over the unmasked v of x[v] = logits[p, v] * inv_temp; logq_rows[p] = x[target] - lse (NaN for a target
-// that is out of range or masked).  One block per packed row, ce_rows_kernel's online log-sum-exp and its two load forms.
+// that is out of range or masked).  One block per packed row, row_reduce.h's online log-sum-exp in ce_rows_kernel's two load forms.
 template <int VEC>
 __global__ __launch_bounds__(256) void policy_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target, int V, float inv_temp,
                                                           const int* __restrict__ masked_ids, int n_first_rows, float* __restrict__ lse_rows,
@@ -51,31 +52,19 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(const float* __restric
                 float e[4] = {q[u].x * inv_temp, q[u].y * inv_temp, q[u].z * inv_temp, q[u].w * inv_temp};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) if (mk.has(4 * v + i)) e[i] = -INFINITY;
-                const float m4 = fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3]));
-                if (m4 > mx) { sum *= __expf(mx - m4); mx = m4; }          // exp(-inf) = 0 on the first trip
-                if (mx != -INFINITY) sum += (__expf(e[0] - mx) + __expf(e[1] - mx)) + (__expf(e[2] - mx) + __expf(e[3] - mx));
+                lse_unit4(e, mx, sum);
             }
         }
     } else {
         for (int v = tid; v < V; v += 256) {
             if (mk.has(v)) continue;
-            const float xv = x[v] * inv_temp;
-            if (xv > mx) { sum = sum * __expf(mx - xv) + 1.f; mx = xv; } else if (mx != -INFINITY) sum += __expf(xv - mx);
+            lse_word(x[v] * inv_temp, mx, sum);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(mx, o, 64), os = __shfl_xor(sum, o, 64);
-        const float nm = fmaxf(mx, om);
-        const float fa = (mx == nm) ? 1.f : __expf(mx - nm), fb = (om == nm) ? 1.f : __expf(om - nm);   // (-inf) - (-inf) guard
-        sum = sum * fa + os * fb; mx = nm;
-    }
-    if ((tid & 63) == 0) { s_m[tid >> 6] = mx; s_s[tid >> 6] = sum; }
+    lse_wave_put(mx, sum, s_m, s_s, tid);
     __syncthreads();
     if (tid == 0) {
-        const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float S = 0.f;
-        for (int k = 0; k < 4; ++k) S += (s_m[k] == M) ? s_s[k] : s_s[k] * __expf(s_m[k] - M);
-        const float lse = M + __logf(S);
+        const float lse = lse_block(s_m, s_s);
         const int t = target[p];
         lse_rows[p] = lse;
         logq_rows[p] = (t >= 0 && t < V && !mk.has(t)) ? x[t] * inv_temp - lse : NAN;
@@ -88,10 +77,8 @@ __global__ __launch_bounds__(256) void policy_finish_kernel(const float* __restr
     __shared__ double s_l[256];
     double s = 0.0;
     for (int p = threadIdx.x; p < P; p += 256) { const float w = row_weight[p]; if (w != 0.f) s += (double)w * (double)logq_rows[p]; }
-    s_l[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s_l[threadIdx.x] += s_l[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) out[0] = (float)(-(double)scale * s_l[0]);
+    s = block_tree_sum_d(s, s_l);
+    if (threadIdx.x == 0) out[0] = (float)(-(double)scale * s);
 }
 
 // dlogits[p, v] = g * scale * w_p * inv_temp * (softmax_U(x)[v] - [v == target]) for the unmasked v, 0 for the masked ones; a row of

@@ -23,6 +23,7 @@
 // tensor) and appends T and the loss to the device-side traces.  If T leaves (0, inf) the latch is set: later row / finish
 // launches return at once, T stays, the T trace repeats it and the loss trace gets NaN, which is how the caller sees it.
 #include "temperature.h"
+#include "row_reduce.h"
 
 #include <math.h>
 
@@ -181,13 +182,8 @@ __global__ __launch_bounds__(256) void temperature_finish_kernel(const double* _
     const double* q = part + (long)blockIdx.x * nb * 2;
     double L = 0.0, G = 0.0;
     for (int b = threadIdx.x; b < nb; b += 256) { L += q[2 * b]; G += q[2 * b + 1]; }
-    s_l[threadIdx.x] = L; s_g[threadIdx.x] = G;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s_l[threadIdx.x] += s_l[threadIdx.x + o]; s_g[threadIdx.x] += s_g[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { loss_out[blockIdx.x] = (float)(s_l[0] / (double)P); grad_out[blockIdx.x] = (float)(s_g[0] / (double)P); }
+    L = block_tree_sum_d(L, s_l); G = block_tree_sum_d(G, s_g);
+    if (threadIdx.x == 0) { loss_out[blockIdx.x] = (float)(L / (double)P); grad_out[blockIdx.x] = (float)(G / (double)P); }
 }
 
 __device__ __forceinline__ void set_coef(TempCoef* coef, float T) {
