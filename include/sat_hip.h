@@ -897,6 +897,22 @@ int sat_bn_train_bwd_t(int32_t dtype, const void* dy, const void* x, const void*
                        void* dres, int32_t dres_accumulate,
                        const uint8_t* relu_mask /* or NULL: the forward's sign mask, read instead of y (which may then be NULL) */,
                        float* scratch, void* stream);
+/* The launch plan a training-mode BatchNorm call takes for a shape, without touching a device (callable on a machine without a GPU).  It is
+ * the function the launchers and sat_bn_scratch_bytes read, under the current bn_vpt / bn_onepass debug options and the SAT_BN_* environment
+ * values latched at first use.  backward: 0 forward, 1 backward; dtype: 0 fp32, 1 bf16; tile_rows: 0 = statistics from a pass over the
+ * activation (sat_bn_train_fwd_t / _bwd_t), > 0 = from ceil(rows / tile_rows) tile statistics (the *_tiles_bf16 entry points, bf16 only);
+ * resbn: 1 = sat_bn_train_fwd_tiles_bf16_resbn (forward on tile statistics only).  out =
+ *   [0] statistics form: 0 column-statistics pass + finalize, 1 tile finish <8 channels, 8 loads>, 2 tile finish <4, 16>, 3 fused tile
+ *       finalize (forward only), 4 tile reduce + finalize pair
+ *   [1] CV: vector columns (16 bytes each) per block of the column pass, a divisor of 256; channels per block for the tile forms
+ *   [2] blocks along the channels
+ *   [3] row parts = partials per channel in the scratch (form 4: tile parts; forms 1 - 3 finish in one launch: 0)
+ *   [4] rows per part; -1 = groups of rows dealt round-robin to the parts (backward pass); form 4: tiles per part; forms 1 - 3: 0
+ *   [5] tiles (0 for form 0)
+ *   [6] apply kernel: vectors per thread VPT (1, 2, 4)   [7] ... which lie ceil(rows / VPT) rows apart (the last part is short when VPT
+ *       does not divide rows)
+ * Validates like the entry points (positive sizes, C % 4 | 8 by dtype); on an error out is all zero. */
+int sat_bn_plan(int32_t backward, int32_t dtype, int64_t rows, int32_t C, int32_t tile_rows, int32_t resbn, int64_t out[8]);
 int sat_maxpool3x3s2_fwd_t(int32_t dtype, const void* x, void* y, uint8_t* argmax, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 int sat_maxpool3x3s2_bwd_t(int32_t dtype, const void* dy, const uint8_t* argmax, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 /* bf16 plumbing: fp32 -> bf16 copies of filters/gradients (n % 4 == 0); Normalize fused with NCHW -> NHWC and

@@ -216,6 +216,7 @@ SYMBOLS.update({
     "sat_image_normalize_nhwc4": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
     "sat_pad_channels_3to4": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "sat_bn_scratch_bytes": (C.c_size_t, [_i64, _i32]),
+    "sat_bn_plan": (C.c_int, [_i32, _i32, _i64, _i32, _i32, _i32, C.POINTER(_i64)]),
     "sat_bn_train_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sat_bn_eval_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _f, _vp, _vp, _vp, _i32, _vp, _vp]),
     "sat_colsum": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp]),

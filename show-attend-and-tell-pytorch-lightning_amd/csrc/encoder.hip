@@ -382,9 +382,12 @@ __global__ __launch_bounds__(256) void bn_tile_finish_kernel(const float* __rest
 // measured per launch inside the C2 step: <8, 8> 5.7 us (fused kernel before: 9.1), <4, 16> 9.3 us (reduce + finalize pair: 10.8 forward, 16.4
 // backward); above 2048 tiles a 2-channel form took 20 us against the pair's 11 - 16, so those keep the pair.
 static inline bool bn_tile_finish_ok(int ntiles) { return ntiles <= 2048; }
-static inline void launch_bn_tile_finish(const float* tiles, int ntiles, int C, int mode, long rows, float eps, float momentum, float* out0, float* out1,
+// the statistics forms of a BatchNorm call (bn_plan below chooses, sat_bn_plan reports): a pass over the activation, or one of the reducers of
+// the convolution epilogue's tile statistics
+enum { BN_STATS_COLS = 0, BN_STATS_FINISH8 = 1, BN_STATS_FINISH4 = 2, BN_STATS_FUSED = 3, BN_STATS_PAIR = 4 };
+static inline void launch_bn_tile_finish(int form, const float* tiles, int ntiles, int C, int mode, long rows, float eps, float momentum, float* out0, float* out1,
                                          float* running_mean, float* running_var, hipStream_t st) {
-    if (ntiles > 256)
+    if (form == BN_STATS_FINISH4)
         hipLaunchKernelGGL((bn_tile_finish_kernel<4, 16>), dim3(cdiv(C, 4)), dim3(256), 0, st, tiles, ntiles, C, mode, rows, eps, momentum, out0, out1, running_mean, running_var);
     else
         hipLaunchKernelGGL((bn_tile_finish_kernel<8, 8>), dim3(cdiv(C, 8)), dim3(256), 0, st, tiles, ntiles, C, mode, rows, eps, momentum, out0, out1, running_mean, running_var);
@@ -556,15 +559,13 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict
 template <typename T>
 static inline void launch_bn_bwd_apply(const T* x, const T* dy, const T* y, const uint8_t* rmask, const float* mean, const float* invstd, const float* gamma,
                                        const float* dbeta, const float* dgamma, int relu, float inv_rows, T* dx, T* dres, int dres_accumulate, long rows, int CV,
-                                       hipStream_t st) {
+                                       int vpt, long part_rows, hipStream_t st) {          // vpt, part_rows: bn_plan's
     const long totalv = rows * CV;
-    const int vpt = dev_switch(SW_BN_VPT);
-    if (vpt >= 4 && rows >= 16384) {
-        const long part = ((rows + 3) / 4) * CV;
+    const long part = part_rows * CV;
+    if (vpt == 4) {
         hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 4>), dim3(cdiv(part, 256)), dim3(256), 0, st, x, dy, y, rmask, mean, invstd, gamma, dbeta, dgamma, relu, inv_rows, dx, dres,
                            dres_accumulate, totalv, CV, part);
-    } else if (vpt >= 2 && rows >= 4096) {
-        const long part = ((rows + 1) / 2) * CV;
+    } else if (vpt == 2) {
         hipLaunchKernelGGL((bn_bwd_apply_kernel<T, 2>), dim3(cdiv(part, 256)), dim3(256), 0, st, x, dy, y, rmask, mean, invstd, gamma, dbeta, dgamma, relu, inv_rows, dx, dres,
                            dres_accumulate, totalv, CV, part);
     } else {
@@ -1130,34 +1131,84 @@ static void bn_grid(long rows, int C, int E, int& CV, long& rows_per, int& npart
     nparts = cdiv(rows, rows_per);
 }
 
+// The launch plan of a training-mode BatchNorm call: the one place where the statistics form, its grid and the apply kernel's vectors per
+// thread are decided.  The forward and backward launchers, sat_bn_scratch_bytes and the query sat_bn_plan all read it from here.
+struct BnPlan {
+    int stats;         // BN_STATS_*
+    int CV;            // column pass: vector columns per block (a divisor of 256); tile reducers: channels per block (8, 4, 32, 32)
+    int colblocks;     // blocks along the channels
+    int nparts;        // partials per channel in the scratch = blocks along the rows (0: a tile reducer that finishes in one launch)
+    long rows_per;     // column pass: rows per part, -1 = row groups dealt round-robin (backward); tile pair: tiles per part; else 0
+    int ntiles;        // 0 on the column pass
+    int vpt;           // apply kernel: vectors per thread (1, 2, 4) ...
+    long part_rows;    // ... `part_rows` rows apart = ceil(rows / vpt)
+};
+static BnPlan bn_plan(int backward, int E, long rows, int C, int tile_rows, bool resbn) {
+    static const int fuse_upto = getenv("SAT_BN_FUSE_TILES") ? atoi(getenv("SAT_BN_FUSE_TILES")) : 256;
+    static const int inter = getenv("SAT_BN_INTERLEAVE") ? atoi(getenv("SAT_BN_INTERLEAVE")) : 1;      // row groups dealt round-robin to the parts (-5 %)
+    BnPlan p{};
+    int CV, nparts; long rp; bn_grid(rows, C, E, CV, rp, nparts, backward);
+    if (tile_rows > 0) {        // statistics per row tile came out of a convolution's epilogue: combine the tiles, no pass over the activation
+        const int ntiles = (int)cdiv(rows, (long)tile_rows);
+        p.ntiles = ntiles;
+        if (dev_switch(SW_BN_ONEPASS) && bn_tile_finish_ok(ntiles)) {
+            p.stats = ntiles > 256 ? BN_STATS_FINISH4 : BN_STATS_FINISH8;
+            p.CV = ntiles > 256 ? 4 : 8;
+        } else if (!backward && ntiles <= fuse_upto) {
+            p.stats = BN_STATS_FUSED; p.CV = 32;
+        } else {
+            int np = cdiv(ntiles, 64); if (np > nparts) np = nparts; if (np < 1) np = 1;          // partials fit the scratch sized for nparts
+            const int per = cdiv(ntiles, np); np = cdiv(ntiles, per);
+            p.stats = BN_STATS_PAIR; p.CV = 32; p.nparts = np; p.rows_per = per;
+        }
+        p.colblocks = cdiv(C, p.CV);
+    } else {
+        p.stats = BN_STATS_COLS; p.CV = CV; p.colblocks = cdiv(C / E, CV); p.nparts = nparts;
+        p.rows_per = (backward && inter) ? -1L : rp;
+    }
+    const int vpt = dev_switch(SW_BN_VPT);
+    p.vpt = (vpt >= 4 && rows >= 16384 && !resbn) ? 4 : (vpt >= 2 && rows >= 4096) ? 2 : 1;      // (the projection-shortcut form has no VPT = 4 instantiation)
+    p.part_rows = (rows + p.vpt - 1) / p.vpt;
+    return p;
+}
+
 extern "C" size_t sat_bn_scratch_bytes(int64_t rows, int32_t C) {
     if (rows <= 0 || C <= 0 || C % 4) return 0;
     int np = 0;
     for (int bwd = 0; bwd < 2; ++bwd) {            // the largest partial count of the forward / backward grids at either vector width
-        int CV, nparts; long rp; bn_grid(rows, C, 4, CV, rp, nparts, bwd);
+        const int nparts = bn_plan(bwd, 4, rows, C, 0, false).nparts;          // (the tile pair never takes more parts than the column pass)
         if (nparts > np) np = nparts;
-        if (C % 8 == 0) { bn_grid(rows, C, 8, CV, rp, nparts, bwd); if (nparts > np) np = nparts; }
+        if (C % 8 == 0) { const int n8 = bn_plan(bwd, 8, rows, C, 0, false).nparts; if (n8 > np) np = n8; }
     }
     return (size_t)np * C * 2 * sizeof(double) + 64 + ((size_t)cdiv(C, 32) * sizeof(int) + 63) / 64 * 64;      // partials + one ticket per 32 channels
 }
 
+extern "C" int sat_bn_plan(int32_t backward, int32_t dtype, int64_t rows, int32_t C, int32_t tile_rows, int32_t resbn, int64_t out[8]) {
+    if (!out) return fail(SAT_EINVAL, "bn_plan: null pointer");
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    SAT_REQUIRE((backward == 0 || backward == 1) && (dtype == 0 || dtype == 1), "bn_plan: backward=%d (0 | 1) dtype=%d (0 fp32, 1 bf16)", backward, dtype);
+    const int E = dtype ? 8 : 4;
+    SAT_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && C % E == 0, "bn_plan: rows=%ld C=%d (C must be a multiple of %d for this storage type)", (long)rows, C, E);
+    SAT_REQUIRE(tile_rows >= 0 && (tile_rows == 0 || dtype == 1), "bn_plan: tile_rows=%d (tile statistics are a bf16 path)", tile_rows);
+    SAT_REQUIRE(!resbn || (tile_rows > 0 && !backward), "bn_plan: the projection-shortcut form is a forward call on tile statistics");
+    const BnPlan p = bn_plan(backward, E, rows, C, tile_rows, resbn != 0);
+    out[0] = p.stats; out[1] = p.CV; out[2] = p.colblocks; out[3] = p.nparts; out[4] = p.rows_per; out[5] = p.ntiles; out[6] = p.vpt; out[7] = p.part_rows;
+    return SAT_OK;
+}
+
 template <typename T>
 static inline void launch_bn_apply_train(const T* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const T* residual, int relu, T* y,
-                                         uint8_t* relu_mask, long totalv, int CV, ResBn rbn, hipStream_t st) {
-    const long rows = totalv / CV;
-    const int vpt = dev_switch(SW_BN_VPT);
-    if (rbn.mean && vpt >= 2 && rows >= 4096) {
-        const long part = ((rows + 1) / 2) * CV;
+                                         uint8_t* relu_mask, long totalv, int CV, ResBn rbn, const BnPlan& pl, hipStream_t st) {
+    const long part = pl.part_rows * CV;
+    if (rbn.mean && pl.vpt == 2)
         hipLaunchKernelGGL((bn_apply_kernel<T, false, true, 2>), dim3(cdiv(part, 256)), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, relu, y, relu_mask, totalv, CV, -1.0f, rbn, part);
-    } else if (rbn.mean)
+    else if (rbn.mean)
         hipLaunchKernelGGL((bn_apply_kernel<T, false, true>), dim3(cdiv(totalv, 256)), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, relu, y, relu_mask, totalv, CV, -1.0f, rbn, totalv);
-    else if (vpt >= 4 && rows >= 16384) {
-        const long part = ((rows + 3) / 4) * CV;
+    else if (pl.vpt == 4)
         hipLaunchKernelGGL((bn_apply_kernel<T, false, false, 4>), dim3(cdiv(part, 256)), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, relu, y, relu_mask, totalv, CV, -1.0f, rbn, part);
-    } else if (vpt >= 2 && rows >= 4096) {
-        const long part = ((rows + 1) / 2) * CV;
+    else if (pl.vpt == 2)
         hipLaunchKernelGGL((bn_apply_kernel<T, false, false, 2>), dim3(cdiv(part, 256)), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, relu, y, relu_mask, totalv, CV, -1.0f, rbn, part);
-    } else
+    else
         hipLaunchKernelGGL((bn_apply_kernel<T, false, false>), dim3(cdiv(totalv, 256)), dim3(256), 0, st, x, mean, invstd, gamma, beta, residual, relu, y, relu_mask, totalv, CV, -1.0f, rbn, totalv);
 }
 
@@ -1173,50 +1224,42 @@ static int bn_train_fwd_t(const T* x, int64_t rows, int32_t C, const float* gamm
     constexpr int E = EPT<T>::n;
     SAT_REQUIRE(C % E == 0, "bn_train_fwd: C=%d must be a multiple of %d for this storage type", C, E);
     SAT_REQUIRE(!relu_mask || (relu && C % 8 == 0), "bn_train_fwd: the ReLU sign mask needs relu and C %% 8 == 0 (C=%d)", C);
-    int CV, nparts; long rp; bn_grid(rows, C, E, CV, rp, nparts);
-    double* p0 = reinterpret_cast<double*>(scratch); double* p1 = p0 + (long)nparts * C;
+    SAT_REQUIRE(!tile_stats || tile_rows > 0, "bn_train_fwd: tile_rows=%d", tile_rows);
+    const BnPlan pl = bn_plan(0, E, rows, C, tile_stats ? tile_rows : 0, rbn.mean != nullptr);
+    double* p0 = reinterpret_cast<double*>(scratch); double* p1 = p0 + (long)pl.nparts * C;
     const T* shift_src = x;
-    if (tile_stats) {        // statistics came out of the convolution's epilogue: combine the row tiles, no pass over x
-        SAT_REQUIRE(tile_rows > 0, "bn_train_fwd: tile_rows=%d", tile_rows);
-        const int ntiles = (int)cdiv(rows, (long)tile_rows);
-        static const int fuse_upto = getenv("SAT_BN_FUSE_TILES") ? atoi(getenv("SAT_BN_FUSE_TILES")) : 256;
-        if (dev_switch(SW_BN_ONEPASS) && bn_tile_finish_ok(ntiles)) {
-            launch_bn_tile_finish(tile_stats, ntiles, C, 0, (long)rows, eps, momentum, save_mean, save_invstd, running_mean, running_var, st);
-            SAT_TRY(launch_ok("bn_tile_finish"));
-            if (!y) return SAT_OK;                   // statistics only: the caller normalises inside its own kernel (stem tail)
-            long totalv = rows * (C / E);
-            ProfScope prof("bn_apply_fwd", 0.0, (double)rows * C * (sizeof(T) * (residual ? 3 : 2) + (relu_mask ? 0.125 : 0.0)), st);
-            launch_bn_apply_train<T>(x, save_mean, save_invstd, gamma, beta, residual, relu, y, relu_mask, totalv, C / E, rbn, st);
-            return launch_ok("bn_apply");
-        }
-        if (ntiles <= fuse_upto) {
-            hipLaunchKernelGGL(bn_tile_finalize_kernel, dim3(cdiv(C, 32)), dim3(256), 0, st, tile_stats, ntiles, C, (long)rows, eps, momentum, save_mean, save_invstd,
+    if (pl.stats == BN_STATS_FINISH8 || pl.stats == BN_STATS_FINISH4 || pl.stats == BN_STATS_FUSED) {
+        // statistics came out of the convolution's epilogue and one launch combines the row tiles: no pass over x, no partials
+        if (pl.stats == BN_STATS_FUSED) {
+            hipLaunchKernelGGL(bn_tile_finalize_kernel, dim3(pl.colblocks), dim3(256), 0, st, tile_stats, pl.ntiles, C, (long)rows, eps, momentum, save_mean, save_invstd,
                                running_mean, running_var);
             SAT_TRY(launch_ok("bn_tile_finalize"));
-            if (!y) return SAT_OK;                   // statistics only: the caller normalises inside its own kernel (stem tail)
-            long totalv = rows * (C / E);
-            ProfScope prof("bn_apply_fwd", 0.0, (double)rows * C * (sizeof(T) * (residual ? 3 : 2) + (relu_mask ? 0.125 : 0.0)), st);
-            launch_bn_apply_train<T>(x, save_mean, save_invstd, gamma, beta, residual, relu, y, relu_mask, totalv, C / E, rbn, st);
-            return launch_ok("bn_apply");
+        } else {
+            launch_bn_tile_finish(pl.stats, tile_stats, pl.ntiles, C, 0, (long)rows, eps, momentum, save_mean, save_invstd, running_mean, running_var, st);
+            SAT_TRY(launch_ok("bn_tile_finish"));
         }
-        int np = cdiv(ntiles, 64); if (np > nparts) np = nparts; if (np < 1) np = 1;          // partials fit the scratch sized for nparts
-        const int per = cdiv(ntiles, np); np = cdiv(ntiles, per);
-        p1 = p0 + (long)np * C;
-        hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3(cdiv(C, 32), np), dim3(256), 0, st, tile_stats, ntiles, C, per, p0, p1);
+        if (!y) return SAT_OK;                   // statistics only: the caller normalises inside its own kernel (stem tail)
+        long totalv = rows * (C / E);
+        ProfScope prof("bn_apply_fwd", 0.0, (double)rows * C * (sizeof(T) * (residual ? 3 : 2) + (relu_mask ? 0.125 : 0.0)), st);
+        launch_bn_apply_train<T>(x, save_mean, save_invstd, gamma, beta, residual, relu, y, relu_mask, totalv, C / E, rbn, pl, st);
+        return launch_ok("bn_apply");
+    }
+    if (pl.stats == BN_STATS_PAIR) {
+        hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3(pl.colblocks, pl.nparts), dim3(256), 0, st, tile_stats, pl.ntiles, C, (int)pl.rows_per, p0, p1);
         SAT_TRY(launch_ok("bn_tile_reduce"));
-        nparts = np; shift_src = nullptr;
+        shift_src = nullptr;
     } else {
         ProfScope prof("bn_stats_fwd", 0.0, (double)rows * C * sizeof(T), st);
-        hipLaunchKernelGGL((bn_colstats_kernel<0, T>), dim3(cdiv(C / E, CV), nparts), dim3(256), 0, st, x, (const T*)nullptr, (const T*)nullptr,
-                           (const unsigned char*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (long)rows, C, CV, rp, p0, p1);
+        hipLaunchKernelGGL((bn_colstats_kernel<0, T>), dim3(pl.colblocks, pl.nparts), dim3(256), 0, st, x, (const T*)nullptr, (const T*)nullptr,
+                           (const unsigned char*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (long)rows, C, pl.CV, pl.rows_per, p0, p1);
         SAT_TRY(launch_ok("bn_colstats<0>"));
     }
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel<T>, dim3(cdiv(C, 4)), dim3(256), 0, st, p0, p1, shift_src, nparts, C, (long)rows, eps, momentum, save_mean, save_invstd, running_mean, running_var);
+    hipLaunchKernelGGL(bn_fwd_finalize_kernel<T>, dim3(cdiv(C, 4)), dim3(256), 0, st, p0, p1, shift_src, pl.nparts, C, (long)rows, eps, momentum, save_mean, save_invstd, running_mean, running_var);
     SAT_TRY(launch_ok("bn_fwd_finalize"));
     if (!y) return SAT_OK;
     long totalv = rows * (C / E);
     ProfScope prof("bn_apply_fwd", 0.0, (double)rows * C * (sizeof(T) * (residual ? 3 : 2) + (relu_mask ? 0.125 : 0.0)), st);
-    launch_bn_apply_train<T>(x, save_mean, save_invstd, gamma, beta, residual, relu, y, relu_mask, totalv, C / E, rbn, st);
+    launch_bn_apply_train<T>(x, save_mean, save_invstd, gamma, beta, residual, relu, y, relu_mask, totalv, C / E, rbn, pl, st);
     return launch_ok("bn_apply");
 }
 
@@ -1243,36 +1286,27 @@ static int bn_train_bwd_t(const T* dy, const T* x, const T* y, int64_t rows, int
     SAT_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, "bn_train_bwd: bad shape");
     constexpr int E = EPT<T>::n;
     SAT_REQUIRE(C % E == 0, "bn_train_bwd: C=%d must be a multiple of %d for this storage type", C, E);
-    int CV, nparts; long rp; bn_grid(rows, C, E, CV, rp, nparts, 1);
-    double* p0 = reinterpret_cast<double*>(scratch); double* p1 = p0 + (long)nparts * C;
-    bool tiles_done = false;
-    if (tile_stats) {        // (sum g, sum g * xhat) per row tile came out of the epilogue of the data-gradient launch that wrote dy: no pass over dy / x
-        SAT_REQUIRE(tile_rows > 0, "bn_train_bwd: tile_rows=%d", tile_rows);
-        const int ntiles = (int)cdiv(rows, (long)tile_rows);
-        int np = cdiv(ntiles, 64); if (np > nparts) np = nparts; if (np < 1) np = 1;
-        const int per = cdiv(ntiles, np); np = cdiv(ntiles, per);
-        p1 = p0 + (long)np * C;
-        if (dev_switch(SW_BN_ONEPASS) && bn_tile_finish_ok(ntiles)) {
-            launch_bn_tile_finish(tile_stats, ntiles, C, 1, (long)rows, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr, st);
-            SAT_TRY(launch_ok("bn_tile_finish (backward)"));
-            tiles_done = true;
-        } else {
-            hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3(cdiv(C, 32), np), dim3(256), 0, st, tile_stats, ntiles, C, per, p0, p1);
-            SAT_TRY(launch_ok("bn_tile_reduce (backward)"));
-        }
-        nparts = np;
+    SAT_REQUIRE(!tile_stats || tile_rows > 0, "bn_train_bwd: tile_rows=%d", tile_rows);
+    const BnPlan pl = bn_plan(1, E, rows, C, tile_stats ? tile_rows : 0, false);
+    double* p0 = reinterpret_cast<double*>(scratch); double* p1 = p0 + (long)pl.nparts * C;
+    if (pl.stats == BN_STATS_FINISH8 || pl.stats == BN_STATS_FINISH4) {
+        // (sum g, sum g * xhat) per row tile came out of the epilogue of the data-gradient launch that wrote dy: no pass over dy / x
+        launch_bn_tile_finish(pl.stats, tile_stats, pl.ntiles, C, 1, (long)rows, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr, st);
+        SAT_TRY(launch_ok("bn_tile_finish (backward)"));
     } else {
-        ProfScope prof("bn_stats_bwd", 0.0, (double)rows * C * (sizeof(T) * 2 + (relu ? (relu_mask ? 0.125 : (double)sizeof(T)) : 0.0)), st);
-        static const int inter = getenv("SAT_BN_INTERLEAVE") ? atoi(getenv("SAT_BN_INTERLEAVE")) : 1;      // row groups dealt round-robin to the parts (-5 %)
-        hipLaunchKernelGGL((bn_colstats_kernel<1, T>), dim3(cdiv(C / E, CV), nparts), dim3(256), 0, st, x, dy, y, relu_mask, save_mean, save_invstd, relu, (long)rows, C, CV, inter ? -1L : rp, p0, p1);
-        SAT_TRY(launch_ok("bn_colstats<1>"));
-    }
-    if (!tiles_done) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, p0, p1, nparts, C, dbeta, dgamma);
+        if (pl.stats == BN_STATS_PAIR) {
+            hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3(pl.colblocks, pl.nparts), dim3(256), 0, st, tile_stats, pl.ntiles, C, (int)pl.rows_per, p0, p1);
+            SAT_TRY(launch_ok("bn_tile_reduce (backward)"));
+        } else {
+            ProfScope prof("bn_stats_bwd", 0.0, (double)rows * C * (sizeof(T) * 2 + (relu ? (relu_mask ? 0.125 : (double)sizeof(T)) : 0.0)), st);
+            hipLaunchKernelGGL((bn_colstats_kernel<1, T>), dim3(pl.colblocks, pl.nparts), dim3(256), 0, st, x, dy, y, relu_mask, save_mean, save_invstd, relu, (long)rows, C, pl.CV, pl.rows_per, p0, p1);
+            SAT_TRY(launch_ok("bn_colstats<1>"));
+        }
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, p0, p1, pl.nparts, C, dbeta, dgamma);
         SAT_TRY(launch_ok("bn_bwd_finalize"));
     }
     ProfScope prof("bn_apply_bwd", 0.0, (double)rows * C * (sizeof(T) * (3 + (dres ? (dres_accumulate ? 2 : 1) : 0)) + (relu ? (relu_mask ? 0.125 : (double)sizeof(T)) : 0.0)), st);
-    launch_bn_bwd_apply<T>(x, dy, y, relu_mask, save_mean, save_invstd, gamma, dbeta, dgamma, relu, 1.0f / (float)rows, dx, dres, dres_accumulate, (long)rows, C / E, st);
+    launch_bn_bwd_apply<T>(x, dy, y, relu_mask, save_mean, save_invstd, gamma, dbeta, dgamma, relu, 1.0f / (float)rows, dx, dres, dres_accumulate, (long)rows, C / E, pl.vpt, pl.part_rows, st);
     return launch_ok("bn_bwd_apply");
 }
 
