@@ -439,6 +439,66 @@ int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* 
                            const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_groups* groups, int32_t* tok_in,
                            int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score,
                            float* fin_mean, void* workspace, size_t workspace_bytes, void* stream);
+/* Required words: a caption must contain the words of its image (Anderson et al. 2017, constrained beam search; Post & Vilar 2018,
+ * dynamic beam allocation; DESIGN.md 5, "Required words").  Image b requires its C_b = n_words[b] words q_0 .. q_{C_b - 1} (n_words is
+ * clamped to 0 .. max_required on the device; a word id outside [0, V) requires nothing: it is dropped from the image's list and C_b
+ * counts the rest).  A step runs as in sat_beam_search_history, with the history tables on even when every rule is off, up to the
+ * scores s[j, v] (log-softmax at the step's temperature, parent score, masks, banned ids, history rules) of the image's
+ * k = clamp(klive[b], 0, K) live rows (row 0 alone at step 0).  Then, per image:
+ *   met(j)       the set of c for which q_c is among the words row j has said (its `step` history entries)
+ *   END held     s'[j, v] = s[j, v], except s'[j, END] = -inf while met(j) is not all of 0 .. C_b - 1: a hypothesis that ends by saying
+ *                <END> contains every required word; the cut at max_gen_length records whatever is live, as in every search
+ *   candidates   the union, by flat index j * V + v, of  A: the k picks of sat_topk's rule over s' (value descending, ties to the lower
+ *                flat index), those at -inf dropped;  R: (j, q_c) for every row j and every c not in met(j), where s' > -inf;
+ *                M: every row's single best word (the lowest v on ties), where s' > -inf
+ *   bank(j, v)   |met(j) U {c : q_c == v}|, in 0 .. C_b; at the last step (step == max_gen_length) |met(j)|: the word picked there is
+ *                not part of the caption (it is <END>, or the cut drops it), and counting it would let a hypothesis that completes its
+ *                words with the dropped word push a complete one out of the beam
+ *   allocation   round robin from the fullest bank: a pointer p starts at C_b; for pick t = 0 .. k - 1 walk the banks p, p - 1, .., 0,
+ *                C_b, .., p + 1 to the first that still holds an untaken candidate, take its best one (value descending, ties to the
+ *                lower flat index), set p = (that bank - 1) mod (C_b + 1); nothing left: -inf / index 0 (the groups' rule)
+ *   stores       the pick's s', unchanged, and its image-level flat index: a hypothesis carries model log-probabilities, the allocation
+ *                steers the selection only
+ * An image with C_b == 0 takes sat_topk's picks exactly (its -inf behaviour included), so in a mixed batch it gets the result of
+ * sat_beam_search_history.  No atomics: same input, same bits.  After the last step one kernel back-traces every finished hypothesis
+ * (as sat_beam_hypotheses does), counts the required words it contains, writes req_met[b] = the largest count of image b and compacts
+ * the image's fin_* lists, order kept, to the hypotheses that reach it; fin_count[b] becomes their number (>= 1).  Every consumer of
+ * the lists then chooses among the captions that meet the most words.
+ * Guarantee: if beamk >= 1, max_gen_length >= C_b and a required word a row has not said is never at -inf (not masked, banned, or
+ * blocked by no_repeat_ngram == 1 after it was said), the fullest bank gains a word every step until it is complete and always holds
+ * slot 0, so req_met[b] == C_b.
+ * Banned ids, the three history rules, temperature lists, layers > 1, deep output and bf16 combine.  required == NULL or max_required
+ * == 0 enqueues exactly what sat_beam_search_history enqueues; req_met may then be NULL and is not written.  SAT_EINVAL before any
+ * launch: max_required outside 0 .. SAT_BEAM_REQUIRED_MAX; and with max_required > 0: a null words / n_words / req_met, beamk >
+ * SAT_BEAM_REQUIRED_MAX_K, max_required > max_gen_length, max_gen_length + 1 > SAT_CAPTION_MAX_LEN (the history table), a sampling
+ * method other than SAT_SAMPLE_BEAM, decoder_noise, topg, a forced prefix, a stream that is being captured.  Workspace:
+ * sat_beam_search_required_workspace_bytes (sat_beam_search_history_workspace_bytes with topg = 0; it refuses the sizes the search
+ * refuses and serves the call with required words off as well). */
+#define SAT_BEAM_REQUIRED_MAX   8      /* required words per image */
+#define SAT_BEAM_REQUIRED_MAX_K 256    /* beamk with required words on: K * (MAX + 2) candidates live in LDS */
+typedef struct sat_beam_required {
+    int32_t max_required;        /* C: 0 = off, else 1..SAT_BEAM_REQUIRED_MAX; row stride of `words` */
+    int32_t reserved;
+    const int32_t* words;        /* device (B, C): image b's required ids, its first n_words[b] entries */
+    const int32_t* n_words;      /* device (B): 0..C; an image with 0 is searched as today */
+} sat_beam_required;
+size_t sat_beam_search_required_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t max_gen_length, int32_t max_required);
+int sat_beam_search_required(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                             const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                             const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_required* required,
+                             int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row,
+                             float* fin_score, float* fin_mean, int32_t* req_met /* (B) */, void* workspace, size_t workspace_bytes, void* stream);
+/* The selection kernel of sat_beam_search_required on its own: scores (B, beamk, V), klive (B) live rows (clamped to 0 .. beamk; an
+ * image with none keeps its slots untouched), hist (B * beamk, hist_stride) the words every row has said, its first hist_len entries
+ * (clamped to 0 .. hist_stride; hist may be NULL with hist_stride 0); first_step & 1 selects from row 0 only, first_step & 2 is the
+ * search's last step (banks of |met(j)|).  Slot t of image b
+ * receives its t-th pick: values the score, indices the flat index row * V + word.  work is scratch, (B, beamk, V) floats.
+ * required->max_required == 0 gives every image sat_topk's picks.  No atomics: same input, same bits.  SAT_EINVAL before the launch: a
+ * null pointer, a size < 1, beamk > SAT_BEAM_REQUIRED_MAX_K, max_required outside 0 .. SAT_BEAM_REQUIRED_MAX, hist_stride outside
+ * 0 .. SAT_CAPTION_MAX_LEN.  NaN in scores: unspecified. */
+int sat_beam_required_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t V, const int32_t* hist, int32_t hist_stride,
+                             int32_t hist_len, int32_t first_step, const sat_beam_required* required, int32_t end_id, float* work, float* values,
+                             int32_t* indices, void* stream);
 /* Ensemble decoding: ONE beam search over several captioning models ("Ensemble decoding").  Members i = 0 .. M - 1 are
  * whole decoders, each with its own sizes (L, D, A, m, n, layers, deep_output, precision), parameters and annotations (B, L_i, D_i) of
  * the same B images; they share the vocabulary (V and the four special ids).  weight[i] >= 0, summing to 1 within 1e-5.  Every member

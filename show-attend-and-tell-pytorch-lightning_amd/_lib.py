@@ -109,6 +109,11 @@ class BeamEnsemble(C.Structure):
                 ("params", C.POINTER(DecoderParams) * ENSEMBLE_MAX), ("ann", C.c_void_p * ENSEMBLE_MAX), ("weight", C.c_float * ENSEMBLE_MAX)]
 
 
+class BeamRequired(C.Structure):
+    """sat_beam_required (include/sat_hip.h)"""
+    _fields_ = [("max_required", C.c_int32), ("reserved", C.c_int32), ("words", C.c_void_p), ("n_words", C.c_void_p)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [("offset", C.c_int64)] + [(k, C.c_int32) for k in ("height", "width", "crop_top", "crop_left", "crop_h", "crop_w", "resized_h",
                                                                   "resized_w", "out_top", "out_left", "flip", "reserved")]
@@ -286,6 +291,11 @@ SYMBOLS.update({
                                          C.POINTER(C.c_int32), C.POINTER(BeamSampling), C.POINTER(BeamConstraints), C.POINTER(BeamHistory),
                                          C.POINTER(BeamGroups), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "sat_beam_group_select": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp]),
+    "sat_beam_search_required_workspace_bytes": (C.c_size_t, [C.POINTER(DecoderDims), _i32, _i32, _i32]),
+    "sat_beam_search_required": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _i32, _i32, C.POINTER(C.c_float), _i32,
+                                           C.POINTER(C.c_int32), C.POINTER(BeamSampling), C.POINTER(BeamConstraints), C.POINTER(BeamHistory),
+                                           C.POINTER(BeamRequired), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_beam_required_select": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, C.POINTER(BeamRequired), _i32, _vp, _vp, _vp, _vp]),
     "sat_beam_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp]),
     "sat_beam_search_ensemble_workspace_bytes": (C.c_size_t, [C.POINTER(BeamEnsemble), _i32, _i32]),
     "sat_beam_search_ensemble": (C.c_int, [C.POINTER(BeamEnsemble), _i32, _i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_int32), C.POINTER(BeamConstraints),

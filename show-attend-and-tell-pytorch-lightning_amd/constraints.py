@@ -7,7 +7,8 @@ arrays, the per-image loop (``SATDecoder.beam_decode``) applies the same rules w
 
 ``resolve_history`` does the same for the rules that read what a hypothesis has already said ("History rules"):
 ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` become one checked ``HistoryRules`` (or ``None``), handed to
-``sat_beam_search_history`` as a ``sat_beam_history``; ``resolve_all`` runs both."""
+``sat_beam_search_history`` as a ``sat_beam_history``; ``resolve_all`` runs both.  ``resolve_groups`` checks the diverse beam search,
+``resolve_required`` the words a caption must contain ("Required words"), handed to ``sat_beam_search_required``."""
 import math
 
 import torch
@@ -250,6 +251,124 @@ def resolve_groups(beamk, beam_groups=None, diversity_penalty=0.5, sample_method
     if V is not None and K // G > int(V):
         raise ValueError("beam_groups=%d: beamk / beam_groups = %d above V=%d" % (G, K // G, int(V)))
     return BeamGroups(G, lam)
+
+
+class Required:
+    """words: one list of distinct token ids per image ("Required words"); an empty list searches that image as today"""
+
+    def __init__(self, words):
+        self.words = [list(w) for w in words]
+        self.max_required = max([len(w) for w in self.words] or [0])
+
+    def device_struct(self, dev):
+        """(sat_beam_required, the tensors it points into)"""
+        C = self.max_required
+        rows = [w + [0] * (C - len(w)) for w in self.words]
+        words = torch.tensor(rows, dtype=torch.int32).reshape(len(rows), C).to(dev)
+        n_words = torch.tensor([len(w) for w in self.words], dtype=torch.int32).to(dev)
+        return L.BeamRequired(max_required=C, words=words.data_ptr(), n_words=n_words.data_ptr()), [words, n_words]
+
+
+#: sat_beam_search_required: SAT_BEAM_REQUIRED_MAX words per image, beamk <= SAT_BEAM_REQUIRED_MAX_K (include/sat_hip.h)
+REQUIRED_MAX = 8
+REQUIRED_MAX_BEAMK = 256
+
+
+def _one_required(r, stoi):
+    if torch.is_tensor(r):
+        r = r.reshape(-1).tolist()
+    ids = []
+    for word in (r.split() if isinstance(r, str) else r):
+        if isinstance(word, str) and stoi is not None:
+            if word not in stoi:
+                raise ValueError("required word %r is not in the vocabulary" % word)
+            word = int(stoi[word])
+        ids.append(word if isinstance(word, str) else int(word))
+    return ids
+
+
+def _required_lists(required, B, stoi):
+    """one list per image from one list / string for every image, or one list / string per image"""
+    if isinstance(required, str) or torch.is_tensor(required) and required.dim() == 1 or (
+            isinstance(required, (list, tuple)) and all(isinstance(t, int) for t in required)):
+        return [_one_required(required, stoi)] * B
+    req = [_one_required(r, stoi) for r in required]
+    if len(req) != B:
+        raise ValueError("required: %d word lists for %d images" % (len(req), B))
+    return req
+
+
+def resolve_required(stoi, V, B, beamk, max_gen_length, required=None, sample_method="beam", decoder_noise=None, topg=None, prefix=None, banned=None,
+                     no_unk=False, beam_groups=None, graph=False, batched=True):
+    """The checked required words of one search over ``B`` images ("Required words"), or ``None`` when nothing is required
+    (``None``, ``[]``, or an empty list / string for every image: today's search).  ``required``: one list of ids or one string of words
+    for every image, or one list / string per image (ragged); a string is split on whitespace, as ``prefix`` is.  Every ``ValueError`` of
+    the feature, each naming its argument; ``batched=False`` is the per-image loop ``beam_decode``.  Touches no GPU."""
+    if required is None:
+        return None
+    V, K, S, B = int(V), int(beamk), int(max_gen_length), int(B)
+    req = _required_lists(required, B, stoi)
+    if not any(req):
+        return None
+    if not batched:
+        raise ValueError("required words run in the batched search only (beam_decode_batched, max_gen_length >= 1), not in the per-image loop beam_decode")
+    ids = {s: int(stoi[s]) for s in SPECIALS}
+    names = {v: k for k, v in ids.items()}
+    ban = set(int(t) for t in (banned.reshape(-1).tolist() if torch.is_tensor(banned) else (banned or [])))
+    if no_unk:
+        ban.add(ids["<UNK>"])
+    for b, words in enumerate(req):
+        for t in words:
+            if not 0 <= t < V:
+                raise ValueError("required id %d outside [0, V=%d)" % (t, V))
+            if t in names:
+                raise ValueError("%s (id %d) among the required words" % (names[t], t))
+            if t in ban:
+                raise ValueError("banned id %d among the required words" % t)
+        if len(set(words)) != len(words):
+            raise ValueError("required words of image %d repeat an id (%r)" % (b, words))
+        if len(words) > REQUIRED_MAX:
+            raise ValueError("required: image %d has %d words, at most %d" % (b, len(words), REQUIRED_MAX))
+        if len(words) > S:
+            raise ValueError("required: image %d has %d words, max_gen_length is %d" % (b, len(words), S))
+    if K > REQUIRED_MAX_BEAMK:
+        raise ValueError("required needs beamk <= %d (beamk=%d)" % (REQUIRED_MAX_BEAMK, K))
+    if sample_method != "beam":
+        raise ValueError("required combines with sample_method='beam' only, not %r" % (sample_method,))
+    if decoder_noise:
+        raise ValueError("required does not combine with decoder_noise=%r" % (decoder_noise,))
+    if topg is not None:
+        raise ValueError("required does not combine with topg=%r" % (topg,))
+    if prefix is not None:
+        raise ValueError("required does not combine with a forced prefix (prefix=%r)" % (prefix,))
+    if beam_groups is not None and int(beam_groups) > 1:
+        raise ValueError("required does not combine with beam_groups=%d" % int(beam_groups))
+    if graph:
+        raise ValueError("required is not replayed from a graph (graph=True)")
+    if S + 1 > HISTORY_MAX_LEN:
+        raise ValueError("required needs max_gen_length + 1 <= %d (max_gen_length=%d): the history tables" % (HISTORY_MAX_LEN, S))
+    left = V - len(SPECIALS) - len(ban - set(ids.values())) - S
+    if left < K:
+        raise ValueError("required: %d unmasked ids left after max_gen_length=%d blocked words, the search needs beamk = %d" % (left, S, K))
+    return Required(req)
+
+
+def required_coverage(captions, required, stoi=None):
+    """Per image, the fraction of its required words that its caption says (1.0 for an image without required words).  ``captions``: one
+    caption per image, a list of words or ids or a string; ``required``: what ``resolve_required`` takes.  With ``stoi`` the words of both
+    are compared as ids (a word outside the vocabulary is <UNK>), otherwise as given.  A host helper: no GPU, no checks of the search."""
+    def norm(seq):
+        seq = seq.split() if isinstance(seq, str) else (seq.reshape(-1).tolist() if torch.is_tensor(seq) else list(seq))
+        if stoi is None:
+            return seq
+        return [int(stoi.get(t, stoi["<UNK>"])) if isinstance(t, str) else int(t) for t in seq]
+    B = len(captions)
+    req = [[] for _ in range(B)] if required is None else _required_lists(required, B, None)
+    out = []
+    for cap, words in zip(captions, req):
+        said, words = set(norm(cap)), norm(words)
+        out.append(sum(1 for w in words if w in said) / len(words) if words else 1.0)
+    return out
 
 
 def resolve_all(stoi, V, B, beamk, max_gen_length, sample_method="beam", topg=None, prefix=None, banned=None, no_unk=False, no_repeat_ngram=None,

@@ -250,6 +250,33 @@ int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* 
                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history,
                                 groups);
 }
+size_t sat_beam_search_required_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t max_gen_length, int32_t max_required) {
+    if (check_dims(d) != SAT_OK || beamk < 1) return 0;
+    if (max_gen_length < 0) { fail(SAT_EINVAL, "beam_search_required_workspace_bytes: max_gen_length %d is negative", max_gen_length); return 0; }
+    const sat_beam_required shape = {max_required, 0, (const int32_t*)d, (const int32_t*)d};      // the sizes only: the pointers are not read
+    if (beam_required_check(&shape, beamk, max_gen_length, "beam_search_required_workspace_bytes") != SAT_OK) return 0;
+    // room for the history tables where they can exist at all (required words off and max_gen_length + 1 > SAT_CAPTION_MAX_LEN: none)
+    return decoder_beam_workspace_bytes(*d, beamk, 0, max_gen_length + 1 <= SAT_CAPTION_MAX_LEN ? max_gen_length + 1 : 0);
+}
+int sat_beam_search_required(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
+                             const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
+                             const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_required* required,
+                             int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row,
+                             float* fin_score, float* fin_mean, int32_t* req_met, void* workspace, size_t workspace_bytes, void* stream) {
+    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_required"));
+    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
+        return fail(SAT_EINVAL, "beam_search_required: null pointer");
+    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_required: temperature %g", temperatures_host[i]);
+    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
+                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history,
+                                nullptr, required, req_met);
+}
+int sat_beam_required_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t V, const int32_t* hist, int32_t hist_stride,
+                             int32_t hist_len, int32_t first_step, const sat_beam_required* required, int32_t end_id, float* work, float* values,
+                             int32_t* indices, void* stream) {
+    if (!scores || !klive || !required || !work || !values || !indices) return fail(SAT_EINVAL, "beam_required_select: null pointer");
+    return beam_required_select(scores, klive, B, beamk, V, hist, hist_stride, hist_len, first_step, *required, end_id, work, values, indices, (hipStream_t)stream);
+}
 static int check_ensemble(const sat_beam_ensemble* e, const char* what) {
     SAT_TRY(beam_ensemble_check(e, what));
     for (int i = 0; i < e->members; ++i) { SAT_TRY(check_dims(e->dims[i])); SAT_TRY(check_params(e->dims[i], e->params[i], what)); }

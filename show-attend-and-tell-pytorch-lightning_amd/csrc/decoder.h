@@ -38,7 +38,8 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
                          int n_temps, const int* special_host, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row,
                          float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
                          const sat_beam_constraints* constraints = nullptr, const sat_beam_history* history = nullptr,
-                         const sat_beam_groups* groups = nullptr);
+                         const sat_beam_groups* groups = nullptr, const sat_beam_required* required = nullptr, int* req_met = nullptr);
+int beam_required_check(const sat_beam_required* r, int K, int max_gen_length, const char* what);
 int beam_ensemble_check_weights(const float* weight, int members, int combine, const char* what);
 int beam_ensemble_check(const sat_beam_ensemble* e, const char* what);
 size_t decoder_beam_ensemble_workspace_bytes(const sat_beam_ensemble& e, int K, int hist_stride);
@@ -73,6 +74,8 @@ int beam_history_scores(const float* logits, int rows, int V, float temperature,
                         const int* hist_len, int hist_stride, const sat_beam_history& rules, int step, int end_id, float* scores, hipStream_t st);
 int beam_group_select(const float* scores, const int* klive, int B, int K, int G, int V, int first_step, float lambda, float* work, float* values, int* indices,
                       hipStream_t st);
+int beam_required_select(const float* scores, const int* klive, int B, int K, int V, const int* hist, int hist_stride, int hist_len, int first_step,
+                         const sat_beam_required& req, int end_id, float* work, float* values, int* indices, hipStream_t st);
 int topk(const float* x, float* work, long n, int k, float* values, int* indices, hipStream_t st);
 int nucleus_keys(const float* scores, int rows, int V, float topp, float step, unsigned long long seed, unsigned long long stream, const float* gumbel,
                  float* keys, int* nucleus_size, hipStream_t st);

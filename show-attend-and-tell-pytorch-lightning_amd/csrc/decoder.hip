@@ -969,10 +969,12 @@ struct BeamCombine { EnsembleArgs args; int geometric; float* combined; };
 // The search loop of decoder_beam_batched and decoder_beam_ensemble, after their argument checks: M members step on the shared tokens,
 // the scores come from member 0's logits at 1 / T (comb == NULL: the single-model search) or from the combined logits; the score
 // kernels, the selection, beam_update and the history advance run once, in member 0's workspace.  con: NULL, or the constrained
-// search's per-image selection (which the history rules and the groups run in as well); hist: NULL, or the rules that are on.
+// search's per-image selection (which the history rules and the groups run in as well); hist: NULL, or the rules that are on (all
+// off with the tables on: required words); req: NULL, or the required words, which select in beam_select_kernel's place.
 static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, int K, int G, float lambda, int max_gen_length, const float* temps_host, int n_temps,
                             const int* special_host, int* tok_in, int* prev_row, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean,
-                            hipStream_t st, const sat_beam_sampling* smp, const sat_beam_constraints* con, const sat_beam_history* hist) {
+                            hipStream_t st, const sat_beam_sampling* smp, const sat_beam_constraints* con, const sat_beam_history* hist,
+                            const sat_beam_required* req = nullptr, int* req_met = nullptr) {
     const BeamWs& w = mem[0].w;
     const int B = mem[0].d->B, N = B * K, V = mem[0].d->V;
     const int START = special_host[0], END = special_host[2];
@@ -1040,6 +1042,10 @@ static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, int
             if (G > 1) {
                 hipLaunchKernelGGL(beam_group_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, K, G, V, step == 0 ? 1 : 0, lambda, w.vals, w.inds);
                 SAT_TRY(launch_ok("beam_group_select"));
+            } else if (req) {
+                hipLaunchKernelGGL(beam_required_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, w.work, w.klive, hcur, hist_stride, step, req->words,
+                                   req->n_words, req->max_required, K, V, (step == 0 ? 1 : 0) | (step == max_gen_length ? 2 : 0), END, w.vals, w.inds);
+                SAT_TRY(launch_ok("beam_required_select"));
             } else {
                 hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(1024), 0, st, w.scores, drawn ? w.keys : (const float*)nullptr, w.cand_val, w.cand_idx, topg,
                                    w.work, w.klive, K, V, step, max_prefix > 0 ? con->prefix : (const int*)nullptr, prefix_len, max_prefix, w.vals, w.inds);
@@ -1083,13 +1089,19 @@ static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, int
                            w.g_step, w.g_row, w.g_score, w.g_mean, fin_count, fin_step, fin_row, fin_score, fin_mean);
         SAT_TRY(launch_ok("beam_group_merge"));
     }
+    if (req) {                                             // the finished lists keep the hypotheses that contain the most required words
+        hipLaunchKernelGGL(beam_required_finish_kernel, dim3(B), dim3(256), 0, st, tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, fin_mean,
+                           req->words, req->n_words, req->max_required, B, K, max_gen_length, V, req_met);
+        SAT_TRY(launch_ok("beam_required_finish"));
+    }
     return SAT_OK;
 }
 
 int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
                          int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
                          int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
-                         const sat_beam_constraints* con, const sat_beam_history* hist, const sat_beam_groups* grp) {
+                         const sat_beam_constraints* con, const sat_beam_history* hist, const sat_beam_groups* grp, const sat_beam_required* req,
+                         int* req_met) {
     // no constraint at all: exactly the launches of the plain / sampled search
     if (con && con->topg == 0 && con->max_prefix == 0 && con->n_banned == 0) con = nullptr;
     const int method = smp ? smp->method : 0;
@@ -1105,8 +1117,21 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         SAT_REQUIRE(!con || con->max_prefix == 0, "beam_groups: groups do not combine with a forced prefix (max_prefix %d)", con ? con->max_prefix : 0);
         SAT_TRY(not_capturing(st, "beam_groups"));
     }
+    SAT_TRY(beam_required_check(req, K, max_gen_length, "beam_required"));
+    if (req && req->max_required == 0) req = nullptr;      // off: today's search, the same launches
+    if (req) {                                             // the words select in the constrained search's place ("Required words")
+        SAT_REQUIRE(req_met, "beam_required: null pointer (req_met with max_required %d)", req->max_required);
+        SAT_REQUIRE(method == SAT_SAMPLE_BEAM, "beam_required: required words combine with \"beam\" sampling only (method %d)", method);
+        SAT_REQUIRE(!smp || smp->decoder_noise == 0.f, "beam_required: required words do not combine with decoder_noise");
+        SAT_REQUIRE(!con || con->topg == 0, "beam_required: required words do not combine with topg %d", con ? con->topg : 0);
+        SAT_REQUIRE(!con || con->max_prefix == 0, "beam_required: required words do not combine with a forced prefix (max_prefix %d)", con ? con->max_prefix : 0);
+        SAT_REQUIRE(G == 1, "beam_required: required words do not combine with groups %d", G);
+        SAT_TRY(not_capturing(st, "beam_required"));
+    }
     SAT_TRY(beam_history_check(hist, max_gen_length, "beam_history"));
-    const bool hist_on = beam_history_on(hist);
+    static const sat_beam_history no_rules = {};
+    if (req && !beam_history_on(hist)) hist = &no_rules;   // the history tables are on, every rule off: the constrained search's scores
+    const bool hist_on = req || beam_history_on(hist);
     const sat_beam_constraints no_constraint = {};
     if (hist_on) {                                         // the history rules run in the constrained search's per-image selection
         SAT_REQUIRE(max_gen_length + 1 <= SAT_BEAM_HIST_MAX, "beam_history: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length,
@@ -1142,7 +1167,33 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
     SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
     BeamMember mem = {&d, &p, ann, w, alpha_hist, (long)d.B * K * d.L};
     return beam_search_loop(&mem, 1, nullptr, K, G, lambda, max_gen_length, temps_host, n_temps, special_host, tok_in, prev_row, fin_count, fin_step, fin_row,
-                            fin_score, fin_mean, st, smp, con, hist_on ? hist : nullptr);
+                            fin_score, fin_mean, st, smp, con, hist_on ? hist : nullptr, req, req_met);
+}
+// sat_beam_required: well-formed for a search of K rows and max_gen_length steps?  (max_required 0 is "off" and asks nothing)
+int beam_required_check(const sat_beam_required* r, int K, int max_gen_length, const char* what) {
+    if (!r) return SAT_OK;
+    SAT_REQUIRE(r->max_required >= 0 && r->max_required <= SAT_BEAM_REQUIRED_MAX, "%s: max_required %d outside 0..%d", what, r->max_required,
+                SAT_BEAM_REQUIRED_MAX);
+    if (r->max_required == 0) return SAT_OK;
+    SAT_REQUIRE(r->words && r->n_words, "%s: null pointer (words / n_words with max_required %d)", what, r->max_required);
+    SAT_REQUIRE(K <= SAT_BEAM_REQUIRED_MAX_K, "%s: beamk %d above %d", what, K, SAT_BEAM_REQUIRED_MAX_K);
+    SAT_REQUIRE(r->max_required <= max_gen_length, "%s: max_required %d above max_gen_length %d", what, r->max_required, max_gen_length);
+    SAT_REQUIRE(max_gen_length + 1 <= SAT_BEAM_HIST_MAX, "%s: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", what, max_gen_length,
+                SAT_BEAM_HIST_MAX);
+    return SAT_OK;
+}
+int beam_required_select(const float* scores, const int* klive, int B, int K, int V, const int* hist, int hist_stride, int hist_len, int first_step,
+                         const sat_beam_required& req, int end_id, float* work, float* values, int* indices, hipStream_t st) {
+    SAT_REQUIRE(B >= 1 && K >= 1 && V >= 1, "beam_required_select: non-positive size (B=%d beamk=%d V=%d)", B, K, V);
+    SAT_REQUIRE(K <= SAT_BEAM_REQUIRED_MAX_K, "beam_required_select: beamk %d above %d", K, SAT_BEAM_REQUIRED_MAX_K);
+    SAT_REQUIRE(req.max_required >= 0 && req.max_required <= SAT_BEAM_REQUIRED_MAX, "beam_required_select: max_required %d outside 0..%d", req.max_required,
+                SAT_BEAM_REQUIRED_MAX);
+    SAT_REQUIRE(hist_stride >= 0 && hist_stride <= SAT_BEAM_HIST_MAX, "beam_required_select: hist_stride %d outside 0..%d", hist_stride, SAT_BEAM_HIST_MAX);
+    SAT_REQUIRE((req.max_required == 0 || (req.words && req.n_words)) && (hist_stride == 0 || hist),
+                "beam_required_select: null pointer (words / n_words with max_required %d, hist with hist_stride %d)", req.max_required, hist_stride);
+    hipLaunchKernelGGL(beam_required_select_kernel, dim3(B), dim3(1024), 0, st, scores, work, klive, hist, hist_stride, hist_len, req.words, req.n_words,
+                       req.max_required, K, V, first_step & 3, end_id, values, indices);
+    return launch_ok("beam_required_select");
 }
 // sat_beam_groups: well-formed?  (groups 0 and 1 are both "off")
 int beam_groups_check(const sat_beam_groups* g, const char* what) {

@@ -1838,4 +1838,173 @@ __global__ void beam_group_merge_kernel(int* __restrict__ prev_row, long n_prev,
     }
 }
 
+// ---- required words: a caption must contain the words of its image ("Required words"; Anderson et al. 2017, Post & Vilar
+// 2018).  Everything but this selection and the kernel after the loop is the search with the history tables on.
+#define SAT_BEAM_REQUIRED_CAND (SAT_BEAM_REQUIRED_MAX_K * (SAT_BEAM_REQUIRED_MAX + 2))
+// image b's required words that can be said at all (ids inside [0, V)), in their order, in s_q; thread 0, the caller syncs.  Returns nothing:
+// *s_nq is their number.
+__device__ __forceinline__ void beam_required_words(const int* __restrict__ words, const int* __restrict__ n_words, int C, int b, int V, int* s_q, int* s_nq) {
+    int nq = 0;
+    if (C > 0) {
+        int cb = n_words[b];
+        cb = cb < 0 ? 0 : (cb > C ? C : cb);
+        cb = cb > SAT_BEAM_REQUIRED_MAX ? SAT_BEAM_REQUIRED_MAX : cb;
+        for (int c = 0; c < cb; ++c) { const int w = words[(long)b * C + c]; if (w >= 0 && w < V) s_q[nq++] = w; }
+    }
+    *s_nq = nq;
+}
+// The selection of one step, one block per image (include/sat_hip.h, sat_beam_search_required).  met(j): which of the image's words row j
+// has said, a scan of its history slice.  END is held back (-inf in the working copy) in the rows that miss a word.  The candidates are
+// the union by flat index of A, the k picks of beam_block_topk over that copy, R, every row's unmet words, and M, every row's best word;
+// a wave per row finds M while it writes the working copy, so the only other pass over k * V floats is the block top-k.  The candidates
+// sit in LDS at fixed slots (A: t; R: k + j * C_b + c; M: k + rows * C_b + j), a slot that holds nothing (a -inf score, or a candidate an
+// earlier slot already holds: A marks its picks with NaN in the working copy) has no bank.  bank = how many words the extended
+// hypothesis has met; at the last step (first_step & 2) the picked word is dropped from the caption (<END>, or the cut), so the bank is
+// |met(j)| and a complete row keeps slot 0.  first_step & 1: row 0 alone.  Then k picks round robin from the fullest bank: a block arg-max over the slots of the chosen bank, value
+// descending, ties to the lower flat index; nothing left: -inf / index 0.  values is the score at the pick, unchanged.  An image
+// without words takes beam_block_topk's picks.  No atomics; counts and ids read from memory are clamped or skipped.
+__global__ __launch_bounds__(1024) void beam_required_select_kernel(const float* __restrict__ scores, float* __restrict__ work, const int* __restrict__ klive,
+                                                                    const int* __restrict__ hist, int hist_stride, int hist_len,
+                                                                    const int* __restrict__ words, const int* __restrict__ n_words, int C, int K, int V,
+                                                                    int first_step, int end_id, float* __restrict__ values, int* __restrict__ indices) {
+    __shared__ float s_val[SAT_BEAM_REQUIRED_CAND]; __shared__ int s_idx[SAT_BEAM_REQUIRED_CAND]; __shared__ unsigned char s_bank[SAT_BEAM_REQUIRED_CAND];
+    __shared__ int s_q[SAT_BEAM_REQUIRED_MAX]; __shared__ int s_nq;
+    __shared__ unsigned s_met[SAT_BEAM_REQUIRED_MAX_K]; __shared__ float s_mv[SAT_BEAM_REQUIRED_MAX_K]; __shared__ int s_mi[SAT_BEAM_REQUIRED_MAX_K];
+    __shared__ int s_cnt[SAT_BEAM_REQUIRED_MAX + 1]; __shared__ int s_p;
+    __shared__ float s_bv[16]; __shared__ long s_bi[16];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int k = klive[b];
+    k = k < 0 ? 0 : (k > K ? K : k);
+    if (k <= 0) return;
+    const float* x = scores + (long)b * K * V; float* wk = work + (long)b * K * V;
+    if (tid == 0) beam_required_words(words, n_words, C, b, V, s_q, &s_nq);
+    __syncthreads();
+    const int nq = s_nq, rows = (first_step & 1) ? 1 : k;
+    const bool last = (first_step & 2) != 0;              // the word picked now is not part of the caption: the banks count met(j) alone
+    const long n = (long)rows * V;
+    if (nq == 0) {                                         // nothing required of this image: today's picks
+        beam_block_topk(x, wk, n, k, values + b * K, indices + b * K, tid);
+        return;
+    }
+    const unsigned full = (1u << nq) - 1u;
+    if (tid < rows) {
+        const int len = hist_len < 0 ? 0 : (hist_len > hist_stride ? hist_stride : hist_len);
+        const int* hrow = hist + ((long)b * K + tid) * hist_stride;
+        unsigned m = 0;
+        for (int p = 0; p < len; ++p) { const int w = hrow[p]; for (int c = 0; c < nq; ++c) m |= (w == s_q[c]) ? (1u << c) : 0u; }
+        s_met[tid] = m;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int j = wave; j < rows; j += 16) {                // the working copy with END held back, and M on the way
+        const bool hold = s_met[j] != full;
+        float bv = -INFINITY; int bi = 0x7fffffff;
+        for (int v = lane; v < V; v += 64) {
+            float s = x[(long)j * V + v];
+            if (hold && v == end_id) s = -INFINITY;
+            wk[(long)j * V + v] = s;
+            if (s == s && arg_before(s, v, bv, bi)) { bv = s; bi = v; }
+        }
+        wave_argbest(bv, bi);
+        if (lane == 0) { s_mv[j] = bv; s_mi[j] = bi; }
+    }
+    __syncthreads();
+    block_picks_marking(wk, n, k, [&](int it, float bv, long bi) { s_val[it] = bv; s_idx[it] = (bi < n && bv > -INFINITY) ? (int)bi : -1; }, tid);   // A
+    const int nR = rows * nq, nC = k + nR + rows;
+    for (int i = tid; i < nC; i += 1024) {
+        int flat = -1; float val = -INFINITY;
+        if (i < k) { flat = s_idx[i]; val = s_val[i]; }
+        else if (i < k + nR) {                             // R: (row j, its unmet word c), the first of equal words only
+            const int e = i - k, j = e / nq, c = e - j * nq, q = s_q[c];
+            bool take = ((s_met[j] >> c) & 1u) == 0u;
+            for (int c2 = 0; c2 < c; ++c2) take = take && s_q[c2] != q;
+            if (take) { const float s = wk[(long)j * V + q]; if (s == s && s > -INFINITY) { flat = j * V + q; val = s; } }
+        } else {                                           // M: (row j, its best word) unless A or R holds it
+            const int j = i - k - nR, v = s_mi[j];
+            const float s = s_mv[j];
+            if (s > -INFINITY && v < V) {
+                const float m = wk[(long)j * V + v];
+                bool take = m == m;
+                for (int c = 0; c < nq; ++c) take = take && !(s_q[c] == v && ((s_met[j] >> c) & 1u) == 0u);
+                if (take) { flat = j * V + v; val = s; }
+            }
+        }
+        int bank = 0xff;
+        if (flat >= 0) {
+            const int j = flat / V, v = flat - j * V;
+            unsigned m = s_met[j];
+            if (!last) for (int c = 0; c < nq; ++c) m |= (s_q[c] == v) ? (1u << c) : 0u;
+            bank = __popc(m);
+        }
+        s_idx[i] = flat; s_val[i] = val; s_bank[i] = (unsigned char)bank;
+    }
+    __syncthreads();
+    if (wave <= nq) {                                      // wave w counts bank w
+        int c = 0;
+        for (int i = lane; i < nC; i += 64) c += s_bank[i] == wave ? 1 : 0;
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) s_cnt[wave] = c;
+    }
+    if (tid == 0) s_p = nq;
+    __syncthreads();
+    for (int t = 0; t < k; ++t) {
+        const int p = s_p;
+        int beta = -1;
+        for (int u = 0; u <= nq && beta < 0; ++u) { const int bk = p - u < 0 ? p - u + nq + 1 : p - u; if (s_cnt[bk] > 0) beta = bk; }
+        float bv = -INFINITY; long bi = 0x7fffffffffffffffL;
+        if (beta >= 0)
+            for (int i = tid; i < nC; i += 1024)
+                if (s_bank[i] == beta) { const long key = (long)s_idx[i] * 4096 + i; if (arg_before(s_val[i], key, bv, bi)) { bv = s_val[i]; bi = key; } }
+        block_argbest<16>(bv, bi, s_bv, s_bi, tid);
+        if (tid == 0) {
+            const bool found = beta >= 0 && bi != 0x7fffffffffffffffL;
+            values[b * K + t] = found ? bv : -INFINITY; indices[b * K + t] = found ? (int)(bi >> 12) : 0;
+            if (found) { s_bank[(int)(bi & 4095)] = 0xff; s_cnt[beta] -= 1; s_p = beta == 0 ? nq : beta - 1; }
+        }
+        __syncthreads();
+    }
+}
+// After the last step, one block per image, thread f its f-th finished hypothesis: the back-trace of beam_hypotheses_kernel counts the
+// required words the hypothesis contains; req_met[b] is the largest count, and the fin_* lists are compacted in place to the hypotheses
+// that reach it, order kept (every thread reads its entry before the barrier and writes it after).  K <= 256 = the block.
+__global__ __launch_bounds__(256) void beam_required_finish_kernel(const int* __restrict__ tok_in, const int* __restrict__ prev_row, int* __restrict__ fin_count,
+                                                                   int* __restrict__ fin_step, int* __restrict__ fin_row, float* __restrict__ fin_score,
+                                                                   float* __restrict__ fin_mean, const int* __restrict__ words, const int* __restrict__ n_words,
+                                                                   int C, int B, int K, int S, int V, int* __restrict__ req_met) {
+    __shared__ int s_q[SAT_BEAM_REQUIRED_MAX]; __shared__ int s_nq; __shared__ int s_c[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) beam_required_words(words, n_words, C, b, V, s_q, &s_nq);
+    __syncthreads();
+    const int nq = s_nq;
+    int fc = fin_count[b];
+    fc = fc < 0 ? 0 : (fc > K ? K : fc);
+    fc = fc > 256 ? 256 : fc;
+    int cnt = -1, st = 0, row = 0; float sc = 0.f, mn = 0.f;
+    if (tid < fc) {
+        const long idx = (long)b * K + tid;
+        st = fin_step[idx]; row = fin_row[idx]; sc = fin_score[idx]; mn = fin_mean[idx];
+        const int step = st < 0 ? 0 : (st > S ? S : st);
+        int cur = row < 0 ? 0 : (row >= K ? K - 1 : row);
+        unsigned m = 0;
+        for (int s = step; s >= 1; --s) {
+            const long at = ((long)s * B + b) * K + cur;
+            const int w = tok_in[at];
+            for (int c = 0; c < nq; ++c) m |= (w == s_q[c]) ? (1u << c) : 0u;
+            cur = prev_row[at];
+            cur = cur < 0 ? 0 : (cur >= K ? K - 1 : cur);
+        }
+        cnt = __popc(m);
+    }
+    s_c[tid] = cnt;
+    __syncthreads();
+    int best = 0, dst = 0, total = 0;
+    for (int f = 0; f < fc; ++f) best = s_c[f] > best ? s_c[f] : best;
+    for (int f = 0; f < fc; ++f) { const int keep = s_c[f] == best ? 1 : 0; total += keep; dst += f < tid ? keep : 0; }
+    if (tid < fc && cnt == best) {
+        const long o = (long)b * K + dst;
+        fin_step[o] = st; fin_row[o] = row; fin_score[o] = sc; fin_mean[o] = mn;
+    }
+    if (tid == 0) { req_met[b] = best; if (fc > 0) fin_count[b] = total; }
+}
+
 }  // namespace sat

@@ -41,7 +41,7 @@ def _bound(fn, args, kw):
     return a
 
 
-def check_decode_args(sample_method="beam", topg=None, prefix=None, repetition_penalty=None, beam_groups=None, decoder_noise=None, graph=False, **_):
+def check_decode_args(sample_method="beam", topg=None, prefix=None, repetition_penalty=None, beam_groups=None, decoder_noise=None, graph=False, required=None, **_):
     """``ValueError`` for every keyword an ensemble does not decode with, each naming its argument.  Touches no GPU."""
     if str(sample_method) != "beam":
         raise ValueError("an ensemble decodes with sample_method='beam' only, not %r" % (sample_method,))
@@ -57,6 +57,9 @@ def check_decode_args(sample_method="beam", topg=None, prefix=None, repetition_p
         raise ValueError("an ensemble does not combine with decoder_noise=%r" % (decoder_noise,))
     if graph:
         raise ValueError("an ensemble search is not replayed from a graph (graph=True)")
+    if required is not None and len(required) > 0 and (isinstance(required, str) or torch.is_tensor(required) or any(
+            not isinstance(r, (str, list, tuple)) or len(r) > 0 for r in required)):
+        raise ValueError("an ensemble does not search with required words (required=%r)" % (required,))
 
 
 class Ensemble:
@@ -141,10 +144,10 @@ class Ensemble:
 
     def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
                             topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                            beam_groups=None, diversity_penalty=0.5):
+                            beam_groups=None, diversity_penalty=0.5, required=None):
         """``SATDecoder._beam_search_device`` for the ensemble: ``ann_bld`` is the list of the members' annotations (B, L_i, D_i); the
         same dict of device buffers comes back (``alpha_hist`` holds member 0's maps).  Launches only."""
-        check_decode_args(sample_method, topg, prefix, repetition_penalty, beam_groups, decoder_noise, graph)
+        check_decode_args(sample_method, topg, prefix, repetition_penalty, beam_groups, decoder_noise, graph, required)
         one = self._single()
         if one is not None:
             ann = ann_bld[0] if isinstance(ann_bld, (list, tuple)) else ann_bld

@@ -113,7 +113,7 @@ def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, 
 @torch.no_grad()
 def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                    rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                   mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None, beam_groups=None, diversity_penalty=0.5):
+                   mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None, beam_groups=None, diversity_penalty=0.5, required=None):
     """``SAT.caption(..., return_all=False)`` with the result left on the device: ``(tokens (B, max_gen_length + 1) int32 padded with
     <PAD>, lengths (B) int32, scores (B), perplexities (B))``.  Nothing is copied to the host and nothing synchronises.
     ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search (``SATDecoder.beam_decode_batched``); ``sample_topp`` belongs to
@@ -121,7 +121,8 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` are the history rules ("History rules").
     ``rescore_method="MBR"`` with ``mbr_corpus`` (``corpus`` when that is None) / ``mbr_reward`` / ``mbr_alpha``: consensus reranking
     ("Consensus reranking"); ``scores`` is then the utility.  ``beam_groups`` / ``diversity_penalty``: the diverse beam
-    search ("Diverse beam search").  Launches only, like the rest."""
+    search ("Diverse beam search"); ``required``: the words every caption must contain ("Required words").
+    Launches only, like the rest."""
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
     mbr_corpus = corpus if mbr_corpus is None else mbr_corpus
@@ -131,10 +132,12 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     constraints.check_ancestral(str(sample_method), beamk, graph, **con)
     constraints.resolve_all(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length, str(sample_method), **con)   # refuse before any launch
     constraints.resolve_groups(beamk, beam_groups, diversity_penalty, str(sample_method), decoder_noise, topg, prefix, graph, V=model.hp.vocab_size)
+    constraints.resolve_required(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length, required, str(sample_method), decoder_noise,
+                                 topg, prefix, banned, no_unk, beam_groups, graph)
     model.eval()
     ann_bld, _ = model.encode(img)
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
-                                  graph, sample_topp=sample_topp, beam_groups=beam_groups, diversity_penalty=diversity_penalty, **con)
+                                  graph, sample_topp=sample_topp, beam_groups=beam_groups, diversity_penalty=diversity_penalty, required=required, **con)
     sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha)
     ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
     return sel["tokens"], sel["lengths"], sel["scores"], ppl
@@ -393,18 +396,18 @@ class CaptionStats:
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                     rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
                     sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None,
-                    mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5):
+                    mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
     """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
     with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue, with ``chrf`` (a ``VocabChars``) chrF
     with ``chrf_beta``.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search, ``no_repeat_ngram`` / ``min_length`` /
     ``repetition_penalty`` are its history rules (``SATDecoder.beam_decode_batched``).  ``rescore_method="MBR"`` reranks by consensus
     against ``mbr_corpus`` (``corpus`` when that is None) with ``mbr_reward`` / ``mbr_alpha``.  ``beam_groups`` / ``diversity_penalty``: the
-    diverse beam search."""
+    diverse beam search; ``required``: the words every caption must contain."""
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
     tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                                           rescore_method, rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram,
-                                          min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus, beam_groups, diversity_penalty)
+                                          min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus, beam_groups, diversity_penalty, required)
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())

@@ -164,7 +164,7 @@ class SATDecoder(nn.Module):
     def beam_decode(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
                     decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, multinomial=None, randn=None,
                     topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, nucleus_log=None, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                    beam_groups=None, diversity_penalty=0.5):
+                    beam_groups=None, diversity_penalty=0.5, required=None):
         """SAT.forward's per-image beam search (model.py:260-472) on annotations (B, L, D).  The decode step,
         log-softmax / masking and top-k run in the library; the beam bookkeeping (which hypotheses to keep, finished
         lists, rescoring) stays on the host like in the reference.  ``sample_method`` "multinomial" / "topk"
@@ -187,6 +187,7 @@ class SATDecoder(nn.Module):
             raise ValueError("sample_method='ancestral' runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         multinomial = multinomial or torch.multinomial
         constraints.resolve_groups(beamk, beam_groups, diversity_penalty, batched=False)     # the groups run in the batched search only
+        constraints.resolve_required(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, required, batched=False)
         con, hist = constraints.resolve_all(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
                                             topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
         lib = L.lib()
@@ -350,7 +351,7 @@ class SATDecoder(nn.Module):
 
     def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
                             topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                            beam_groups=None, diversity_penalty=0.5):
+                            beam_groups=None, diversity_penalty=0.5, required=None):
         """The device half of ``beam_decode_batched``: enqueue the whole search for annotations (B, L, D) (eagerly, or as the replay of
         its cached hipGraph) and return the buffers it leaves on the device (tok_in, prev_row, alpha_hist, fin_*: include/sat_hip.h,
         sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted).
@@ -361,7 +362,9 @@ class SATDecoder(nn.Module):
         from the model's own distribution; ``gumbel`` is then (max_gen_length + 1, B, V).
         With a history rule on (``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``) the call is sat_beam_search_history, eager too.
         ``beam_groups`` > 1 ("Diverse beam search"): sat_beam_search_groups, eager; ``constraints.resolve_groups`` refuses
-        what does not combine with it."""
+        what does not combine with it.  ``required`` ("Required words"): sat_beam_search_required, eager; the buffers gain
+        "req_met" (B), the most required words a finished hypothesis of the image contains (no such key without required words), and the
+        fin_* lists hold the hypotheses that reach it."""
         import ctypes as C
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
@@ -370,6 +373,8 @@ class SATDecoder(nn.Module):
                                             topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
         grp = constraints.resolve_groups(beamk, beam_groups, diversity_penalty, sample_method, decoder_noise, topg, prefix, graph,
                                          V=self.embedding.weight.shape[0])
+        req = constraints.resolve_required(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, required,
+                                           sample_method, decoder_noise, topg, prefix, banned, no_unk, beam_groups, graph)
         lib = L.lib()
         L.require_gpu(ann_bld)
         hp = self.hp
@@ -400,6 +405,10 @@ class SATDecoder(nn.Module):
         if grp is not None:
             gst = grp.device_struct()
             ws_bytes = lib.sat_beam_search_groups_workspace_bytes(C.byref(dims), K, grp.groups, S)
+        rst = None
+        if req is not None:
+            rst, _keep_req = req.device_struct(dev)
+            ws_bytes = lib.sat_beam_search_required_workspace_bytes(C.byref(dims), K, S, req.max_required)
         smp = None
         seeded = seed is not None
         if sample_method != "beam" or decoder_noise:
@@ -415,12 +424,22 @@ class SATDecoder(nn.Module):
                                  normals=(normals.data_ptr() if normals is not None else None))
 
         def buffers():
-            return dict(ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev), tok_in=torch.empty(S + 2, B, K, **i32),
+            o = dict(ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev), tok_in=torch.empty(S + 2, B, K, **i32),
                         prev_row=torch.empty(S + 2, B, K, **i32), alpha_hist=torch.empty(S + 1, B, K, Lc, **f32), fin_count=torch.empty(B, **i32),
                         fin_step=torch.empty(B, K, **i32), fin_row=torch.empty(B, K, **i32), fin_score=torch.empty(B, K, **f32),
                         fin_mean=torch.empty(B, K, **f32))
+            if rst is not None:
+                o["req_met"] = torch.empty(B, **i32)
+            return o
 
         def enqueue(ann, o):
+            if rst is not None:
+                L.check(lib.sat_beam_search_required(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
+                                                     C.byref(cst) if cst is not None else None, C.byref(hst) if hst is not None else None, C.byref(rst),
+                                                     L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]),
+                                                     L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["req_met"]), L.ptr(o["ws"]),
+                                                     ws_bytes, L.stream_ptr()), "sat_beam_search_required")
+                return
             if gst is not None:
                 L.check(lib.sat_beam_search_groups(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
                                                    C.byref(cst) if cst is not None else None, C.byref(hst) if hst is not None else None, C.byref(gst),
@@ -447,7 +466,7 @@ class SATDecoder(nn.Module):
                     "sat_beam_search_sampled")
 
         replayable = smp is None or (sample_method == "nucleus" and seeded and gumbel is None and normals is None)
-        if graph and replayable and cst is None and hst is None and gst is None:
+        if graph and replayable and cst is None and hst is None and gst is None and rst is None:
             cache = self.__dict__.setdefault("_beam_graphs", {})
             key = (B, Lc, D, K, S, tuple(float(t) for t in temps), int(dims.precision), str(dev), tuple(t.data_ptr() for t in _keep.values() if torch.is_tensor(t)))
             if smp is not None:
@@ -476,7 +495,7 @@ class SATDecoder(nn.Module):
     def beam_decode_batched(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, rescore_method=None, rescore_reward=0.5,
                             return_all=False, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None, normals=None, graph=False,
                             topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                            mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5):
+                            mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """The same beam search as ``beam_decode`` ("beam" sampling, no decoder noise) for ALL images of the batch at once
         (SURVEY 8f row 2): one library call enqueues every decode step for the (B, beamk) hypothesis rows -- per-image top-k,
         completed hypotheses leaving their image's beam, cut at ``max_gen_length`` -- without a host round trip; the host reads
@@ -509,11 +528,19 @@ class SATDecoder(nn.Module):
         each a beam of its own; at a step the groups select one after the other and a group pays lambda for every hypothesis an earlier
         group kept with the same word at this step.  The penalty steers the selection only: scores stay model log-probabilities.
         "beam" sampling only; banned ids, ``no_unk``, the history rules, temperature lists and every ``rescore_method`` combine,
-        ``topg`` / ``prefix`` / ``decoder_noise`` / ``graph=True`` raise ``ValueError``.  ``None``, 0 or 1: today's search."""
+        ``topg`` / ``prefix`` / ``decoder_noise`` / ``graph=True`` raise ``ValueError``.  ``None``, 0 or 1: today's search.
+        ``required`` ("Required words"): the words a caption must contain, one list of ids or one string of words for every
+        image, or one per image (ragged; an empty one searches that image as today).  <END> is held back in a hypothesis until it has
+        said them all, and the beam keeps room for the hypotheses that have said the most (dynamic beam allocation); at the end the
+        finished list of an image keeps the hypotheses that contain the most required words, and every ``rescore_method`` picks among
+        those.  Scores stay model log-probabilities.  "beam" sampling only; banned ids, ``no_unk``, the history rules and temperature lists
+        combine, ``topg`` / ``prefix`` / ``decoder_noise`` / ``beam_groups`` / ``graph=True`` raise ``ValueError``
+        (``constraints.resolve_required``).  ``None`` or empty: today's search."""
         import numpy as np
         mbr = constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, self.embedding.weight.shape[0], max_gen_length)
         o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                                     topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length, repetition_penalty, beam_groups, diversity_penalty)
+                                     topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length, repetition_penalty, beam_groups, diversity_penalty,
+                                     required)
         B = ann_bld.shape[0]
         Hh, Ww = hw
         K, S = int(beamk), int(max_gen_length)
@@ -681,18 +708,18 @@ class SAT(SATDecoder, _Base):
     def caption(self, img_tensor, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
                 decoder_noise=None, rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False,
                 sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0,
-                beam_groups=None, diversity_penalty=0.5):
+                beam_groups=None, diversity_penalty=0.5, required=None):
         """model.py:214-235: eval mode, then forward.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` / ``sample_topp``, the history
         rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` and ``rescore_method="MBR"`` with ``mbr_corpus`` /
         ``mbr_reward`` / ``mbr_alpha``, and the diverse beam search ``beam_groups`` / ``diversity_penalty``: ``beam_decode_batched``."""
         self.eval()
         return self.forward(img_tensor, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                             rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
-                            repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty)
+                            repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty, required)
 
     def forward(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                 rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5):
+                mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """Inference only (model.py:237-472): encode the batch once, then beam-search every image."""
         assert sample_method in SAMPLE_METHODS
         check_sample_topp(sample_method, sample_topp)
@@ -705,6 +732,8 @@ class SAT(SATDecoder, _Base):
         constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, self.hp.vocab_size, max_gen_length)
         constraints.resolve_groups(beamk, beam_groups, diversity_penalty, sample_method, decoder_noise, topg, prefix, bool(self.__dict__.get("beam_graph", False)),
                                    batched=max_gen_length >= 1, V=self.hp.vocab_size)
+        constraints.resolve_required(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, required, sample_method, decoder_noise, topg,
+                                     prefix, banned, no_unk, beam_groups, bool(self.__dict__.get("beam_graph", False)), batched=max_gen_length >= 1)
         with torch.no_grad():
             ann_bld, hw = self.encode(img)
             if max_gen_length >= 1:        # every image at once; sampled continuations and decoder noise draw from the device generator
@@ -712,7 +741,7 @@ class SAT(SATDecoder, _Base):
                                                 sample_method=sample_method, sample_topk=sample_topk, decoder_noise=decoder_noise,
                                                 graph=bool(self.__dict__.get("beam_graph", False)), sample_topp=sample_topp, mbr_corpus=mbr_corpus,
                                                 mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, beam_groups=beam_groups, diversity_penalty=diversity_penalty,
-                                                **con)  # model.beam_graph = True: hipGraph replay
+                                                required=required, **con)  # model.beam_graph = True: hipGraph replay
             return self.beam_decode(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, sample_method, sample_topk,
                                     decoder_noise, rescore_method, rescore_reward, return_all, sample_topp=sample_topp, **con)
 
@@ -894,40 +923,41 @@ class SAT(SATDecoder, _Base):
 
     def val_batch(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                  beam_groups=None, diversity_penalty=0.5):
+                  beam_groups=None, diversity_penalty=0.5, required=None):
         """model.py:684-691"""
         img, encoded_captions, lengths = batch
         captions, scores, alphas, perplexities = self.caption(img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
                                                               rescore_method, rescore_reward, return_all=False, topg=topg, prefix=prefix, banned=banned,
                                                               no_unk=no_unk, sample_topp=sample_topp, no_repeat_ngram=no_repeat_ngram,
                                                               min_length=min_length, repetition_penalty=repetition_penalty, beam_groups=beam_groups,
-                                                              diversity_penalty=diversity_penalty)
+                                                              diversity_penalty=diversity_penalty, required=required)
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
 
     def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                       mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None, beam_groups=None, diversity_penalty=0.5):
+                       mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None, beam_groups=None, diversity_penalty=0.5, required=None):
         """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
         from . import evaluation
         return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                          rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
-                                         repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus, beam_groups, diversity_penalty)
+                                         repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus, beam_groups, diversity_penalty, required)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                         rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
                         sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None,
-                        mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5):
+                        mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
         (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L; with ``chrf``, an ``evaluation.VocabChars``, also chrF)"""
         from . import evaluation
         return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                           rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp, chrf, chrf_beta,
-                                          no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty)
+                                          no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty,
+                                          required)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False,
                   sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0,
-                  beam_groups=None, diversity_penalty=0.5, **render):
+                  beam_groups=None, diversity_penalty=0.5, required=None, **render):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
         attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
         ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
@@ -935,18 +965,19 @@ class SAT(SATDecoder, _Base):
         return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                    rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, sample_topp=sample_topp,
                                    no_repeat_ngram=no_repeat_ngram, min_length=min_length, repetition_penalty=repetition_penalty, mbr_corpus=mbr_corpus,
-                                   mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, beam_groups=beam_groups, diversity_penalty=diversity_penalty, **render)
+                                   mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, beam_groups=beam_groups, diversity_penalty=diversity_penalty, required=required, **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                       rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
                       topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                      mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5):
+                      mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
         ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
         from . import visualize
         return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
                                        rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk, sample_topp,
-                                       no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty)
+                                       no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty,
+                                       required)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

@@ -14,7 +14,12 @@ events around ``sat_beam_group_select`` on scores of the search's shape, times t
 ``--ensemble M [M ...]`` / ``--ensemble-combine arithmetic|geometric`` time ensemble decoding ("Ensemble decoding") over M
 differently seeded bench models, each on its own encoder's annotations, next to the plain batched search of the first model, alternating
 over ``--repeats`` calls each; the lines report the ratio to M plain searches and the combine kernel's own time and bandwidth, taken with
-events around ``sat_beam_ensemble_scores`` on logits of the search's shape, times the steps of the search."""
+events around ``sat_beam_ensemble_scores`` on logits of the search's shape, times the steps of the search.
+``--required C [C ...]`` times the search with required words ("Required words") next to the plain batched search at the same
+beam, alternating over ``--repeats`` calls each: every image gets C distinct random non-special ids from a fixed seed.  The lines report the
+ratio to the plain line, the coverage (``constraints.required_coverage``, mean over the 64 images) of the plain and of the required
+search's captions, and the selection kernel's own time next to the block top-k of ``beam_select_kernel`` on the same scores, each taken
+with events around 21 launches."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -40,6 +45,7 @@ ap.add_argument("--beam-groups", type=int, nargs="+", default=None, help="groups
 ap.add_argument("--diversity-penalty", type=float, default=0.5, help="what a group pays per hypothesis an earlier group kept with the same word at a step")
 ap.add_argument("--ensemble", type=int, nargs="+", default=None, help="member counts of the ensemble search (1 = one model, which delegates to the plain search)")
 ap.add_argument("--ensemble-combine", default="arithmetic", choices=["arithmetic", "geometric"])
+ap.add_argument("--required", type=int, nargs="+", default=None, help="required words per image: distinct random non-special ids, fixed seed")
 a = ap.parse_args()
 constrained = a.topg is not None or a.prefix_len > 0 or a.no_unk
 history = dict(no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty)
@@ -63,6 +69,53 @@ def select_kernel_ms(beamk, groups, V, steps, lam):
         e1.record(); torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1))
     return statistics.median(out[1:])
+
+
+def required_words(n_images, count, V, special, seed=1234):
+    """``count`` distinct non-special ids per image from a fixed seed"""
+    g = torch.Generator().manual_seed(seed + count)
+    ok = torch.tensor([t for t in range(V) if t not in special])
+    return [ok[torch.randperm(len(ok), generator=g)[:count]].tolist() for _ in range(n_images)]
+
+
+def required_kernel_ms(beamk, V, steps, words, end_id):
+    """(beam_required_select_kernel with the words, and without any: the block top-k that beam_select_kernel runs at a free step) alone:
+    ``steps`` launches each on the same (64, beamk, V) scores between two events, every row live; the rows have said ``steps // 2`` random
+    words and, every second row, the image's first required word"""
+    import ctypes as C
+    from sat_amd import _lib as L
+    lib = L.lib()
+    n = len(words)
+    sc = torch.randn(n, beamk, V, device="cuda")
+    kl = torch.full((n,), beamk, dtype=torch.int32, device="cuda")
+    stride, said = steps, steps // 2
+    hist = torch.randint(0, V, (n * beamk, stride), dtype=torch.int32, device="cuda")
+    wd = torch.tensor(words, dtype=torch.int32, device="cuda")
+    hist.view(n, beamk, stride)[:, ::2, 0] = wd[:, :1]
+    nw = torch.full((n,), wd.shape[1], dtype=torch.int32, device="cuda")
+    req = L.BeamRequired(max_required=wd.shape[1], words=wd.data_ptr(), n_words=nw.data_ptr())
+    off = L.BeamRequired(max_required=0)
+    work, vals, inds = torch.empty_like(sc), torch.empty(n, beamk, device="cuda"), torch.empty(n, beamk, dtype=torch.int32, device="cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def required():
+        L.check(lib.sat_beam_required_select(L.ptr(sc), L.ptr(kl), n, beamk, V, L.ptr(hist), stride, said, 0, C.byref(req), end_id, L.ptr(work), L.ptr(vals),
+                                             L.ptr(inds), L.stream_ptr()), "sat_beam_required_select")
+
+    def plain():                                            # no words: beam_block_topk over the k * V scores, beam_select_kernel's free step
+        L.check(lib.sat_beam_required_select(L.ptr(sc), L.ptr(kl), n, beamk, V, L.ptr(hist), stride, said, 0, C.byref(off), end_id, L.ptr(work), L.ptr(vals),
+                                             L.ptr(inds), L.stream_ptr()), "sat_beam_required_select")
+    out = []
+    for launch in (required, plain):
+        times = []
+        for rep in range(5):
+            e0.record()
+            for _ in range(steps):
+                launch()
+            e1.record(); torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1))
+        out.append(statistics.median(times[1:]))
+    return out
 
 
 def combine_kernel_ms(members, rows, V, steps, combine):
@@ -124,6 +177,34 @@ with torch.no_grad():
                                                                   21 * (m + 1) * rows * V * 4 / (ms * 1e-3) / 1e9))
                 print("beam %d %s (%s): median %.2f ms (min %.2f, max %.2f) per 64 images incl. host back-trace over %d calls%s"
                       % (beamk, name, a.ensemble_combine, statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3, a.repeats, extra))
+            continue
+        if a.required:
+            from sat_amd.constraints import required_coverage
+            special = {int(hp["vocab_stoi"][s]) for s in ("<START>", "<PAD>", "<END>", "<UNK>")}
+            words = {c: required_words(64, c, hp["vocab_size"], special) for c in a.required}
+            settings = [("plain", dict(beamk=beamk, max_gen_length=20))]
+            settings += [("C=%d" % c, dict(beamk=beamk, max_gen_length=20, required=words[c])) for c in a.required]
+            times, caps = {name: [] for name, _ in settings}, {}
+            for name, kw in settings:
+                for _ in range(2):
+                    caps[name] = model.beam_decode_batched(ann, hw, **kw)[0]
+            for _ in range(a.repeats):                  # alternate, so that every line sees the same machine
+                for name, kw in settings:
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    model.beam_decode_batched(ann, hw, **kw)
+                    torch.cuda.synchronize(); times[name].append(time.perf_counter() - t0)
+            mp = statistics.median(times["plain"])
+            for (name, kw), c in zip(settings, [0] + list(a.required)):
+                t = times[name]
+                extra = ""
+                if c:
+                    ms_req, ms_plain = required_kernel_ms(beamk, hp["vocab_size"], 21, words[c], int(hp["vocab_stoi"]["<END>"]))
+                    extra = (", %.3fx the plain line, coverage %.3f (the plain search's captions: %.3f), selection kernel alone %.2f ms for 21 steps "
+                             "(beam_select_kernel's block top-k on the same scores: %.2f ms)"
+                             % (statistics.median(t) / mp, sum(required_coverage(caps[name], words[c])) / 64,
+                                sum(required_coverage(caps["plain"], words[c])) / 64, ms_req, ms_plain))
+                print("beam %d %s: median %.2f ms (min %.2f, max %.2f) per 64 images incl. host back-trace over %d calls%s"
+                      % (beamk, name, statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3, a.repeats, extra))
             continue
         if a.beam_groups:
             from sat_amd.metrics import distinct_n

@@ -58,6 +58,7 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=None, help="CTRL's penalty on the logits of the words already said (1.0 = off)")
     ap.add_argument("--beam-groups", type=int, default=None, help="diverse beam search: split the beam into this many groups (a divisor of --beamk; beam sampling)")
     ap.add_argument("--diversity-penalty", type=float, default=0.5, help="what a group pays per hypothesis an earlier group kept with the same word at a step")
+    ap.add_argument("--required", default=None, help='words every caption must contain, e.g. "dog frisbee" (the same for every picture; beam sampling)')
     ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="ensemble decoding: further checkpoints over the same vocabulary; one search over all of them (beam sampling)")
     ap.add_argument("--ensemble-weights", type=float, nargs="+", default=None, help="one weight per model, CHECKPOINT first (default: uniform; normalised to sum 1)")
     ap.add_argument("--ensemble-combine", default="arithmetic", choices=["arithmetic", "geometric"], help="mix the models' distributions, or multiply them")
@@ -87,7 +88,7 @@ def main():
                               sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise, rescore_method=None if a.rescore_method == "NONE" else a.rescore_method,
                               rescore_reward=a.rescore_reward, visual_size=a.visual_size, input_size=a.input_size, seed=a.seed, progressive=a.progressive,
                               topg=a.topg, prefix=a.prefix, no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length,
-                              repetition_penalty=a.repetition_penalty, beam_groups=a.beam_groups, diversity_penalty=a.diversity_penalty, **mbr)
+                              repetition_penalty=a.repetition_penalty, beam_groups=a.beam_groups, diversity_penalty=a.diversity_penalty, required=a.required, **mbr)
         for j, i in enumerate(chunk):
             refs = [" ".join(ds.itos(t) for t in c[1:n]) for c, n in zip(ds.encoded_captions[i], ds.lengths[i])]
             name = os.path.join(a.out, "%s_result.jpg" % vis.names[j])
