@@ -800,7 +800,8 @@ typedef struct sat_conv_geom {
     int32_t N, H, W, C;     /* input  (N, H, W, C), C % 4 == 0                    */
     int32_t K, R, S;        /* filter (K, R, S, C), K % 4 == 0                    */
     int32_t stride, pad;    /* output (N, P, Q, K), P = (H + 2 pad - R)/stride + 1 */
-    int32_t stride_w;       /* 0: = stride.  Otherwise the horizontal stride (bf16 forward / weight gradient only): the stem's tap-pair view */
+    int32_t stride_w;       /* 0: = stride.  Otherwise the horizontal stride (bf16 forward / weight gradient only): the stem's tap-pair view.
+                             * The fp32 forward / weight gradient and every data gradient return SAT_EINVAL for a stride_w that differs from stride */
 } sat_conv_geom;
 /* nn.Conv2d forward / autograd (input gradient, weight gradient) as implicit GEMMs on MFMA */
 int sat_conv2d_fwd(const float* x, const float* w, const float* bias /* or NULL */, float* y, const sat_conv_geom* g, void* stream);

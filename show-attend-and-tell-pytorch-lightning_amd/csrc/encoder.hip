@@ -977,6 +977,7 @@ static int conv_fwd_any(const void* x, const void* w, const float* bias, void* y
                         float* tile_stats = nullptr, int* tile_rows = nullptr) {
     ConvGeom g; SAT_TRY(conv_geom(geom, g, bf16 ? 8 : 4));
     if (!x || !w || !y) return fail(SAT_EINVAL, "conv2d_fwd: null pointer");
+    if (!bf16 && g.sw) return fail(SAT_EINVAL, "conv2d_fwd: stride_w=%d differs from stride=%d: the fp32 kernel has one stride (bf16 storage only)", g.sw, g.stride);
     GemmArgs a; a.a_bf16 = a.b_bf16 = a.c_bf16 = a.bf16_mfma = bf16;
     a.M = g.N * g.P * g.Q; a.N = g.K; a.K = g.R * g.S * g.C;
     a.B = w; a.ldb = a.K; a.bmode = B_ROW; a.C = y; a.ldc = g.K; a.g = g;
@@ -1009,6 +1010,7 @@ static int conv_dgrad_any(const void* dy, const void* w, void* dx, const sat_con
                           const BnBwdStats* bs = nullptr, const void* add_src = nullptr, const uint8_t* add_mask = nullptr) {
     ConvGeom g; SAT_TRY(conv_geom(geom, g, bf16 ? 8 : 4));
     if (!dy || !w || !dx) return fail(SAT_EINVAL, "conv2d_dgrad: null pointer");
+    if (g.sw) return fail(SAT_EINVAL, "conv2d_dgrad: stride_w=%d differs from stride=%d: no data gradient reads it (bf16 forward / weight gradient only)", g.sw, g.stride);
     GemmArgs a; a.a_bf16 = a.b_bf16 = a.c_bf16 = a.bf16_mfma = bf16;
     a.accumulate = accumulate; a.C = dx; a.ldc = g.C; a.g = g;
     if (add_src) {
@@ -1079,6 +1081,7 @@ int sat_conv2d_dgrad_bf16_bnstats(const void* dy, const void* w, void* dx, const
 static int conv_wgrad_any(const void* dy, const void* x, float* dw, const sat_conv_geom* geom, float* slab, int64_t slab_elems, int bf16, void* stream) {
     ConvGeom g; SAT_TRY(conv_geom(geom, g, bf16 ? 8 : 4));
     if (!dy || !x || !dw) return fail(SAT_EINVAL, "conv2d_wgrad: null pointer");
+    if (!bf16 && g.sw) return fail(SAT_EINVAL, "conv2d_wgrad: stride_w=%d differs from stride=%d: the fp32 kernel has one stride (bf16 storage only)", g.sw, g.stride);
     if (bf16 && wgrad3x3_eligible(g)) return launch_wgrad3x3(dy, x, dw, g, slab, (long)slab_elems, (hipStream_t)stream);      // all nine taps per workgroup (wgrad3x3.hip)
     GemmArgs a; a.a_bf16 = a.b_bf16 = a.bf16_mfma = bf16; a.c_bf16 = 0;
     a.M = g.K; a.N = g.R * g.S * g.C; a.K = g.N * g.P * g.Q;

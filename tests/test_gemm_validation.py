@@ -1,6 +1,7 @@
 """CPU: sat_gemm_f32 / sat_gemm_ex refuse a launch whose epilogue operand, epilogue number or split-K slab is unusable BEFORE any kernel is
 chosen - for the bf16 kernels as for the fp32 one.  Nothing is launched here: the operand addresses are dummies, every status below
-comes from the argument checks of launch_gemm (csrc/gemm.hip)."""
+comes from the argument checks of launch_gemm (csrc/gemm.hip).  Likewise the convolution entry points refuse a stride_w that no kernel of theirs
+reads (conv_*_any, csrc/encoder.hip)."""
 import ctypes
 
 import pytest
@@ -73,3 +74,39 @@ def test_checks_apply_to_the_strided_and_k_major_forms_too(L):
     for amode, bmode in ((0, 1), (1, 1)):
         rc, msg = _call(L, "bf16_f32_out", amode=amode, bmode=bmode, epi=5, lda=72, ldb=72, ldc=68)
         assert rc != 0 and "bias" in msg, (amode, bmode, rc, msg)
+
+
+# ----------------------------------------------------------------------------- sat_conv_geom.stride_w
+def _geom(L, **over):
+    kw = dict(N=2, H=21, W=14, C=8, K=64, R=7, S=4, stride=2, pad=0, stride_w=1)
+    kw.update(over)
+    return L.ConvGeom(**kw)
+
+
+def _conv_call(L, name, geom):
+    lib = L.lib()
+    g = ctypes.byref(geom)
+    if "fwd" in name:
+        rc = getattr(lib, name)(DUMMY, 2 * DUMMY, None, 3 * DUMMY, g, None)
+    elif "dgrad" in name:
+        rc = getattr(lib, name)(DUMMY, 2 * DUMMY, 3 * DUMMY, g, 0, None)
+    else:
+        rc = getattr(lib, name)(DUMMY, 2 * DUMMY, 3 * DUMMY, g, None, 0, None)
+    return rc, lib.sat_last_error().decode()
+
+
+@pytest.mark.parametrize("name", ["sat_conv2d_fwd", "sat_conv2d_wgrad", "sat_conv2d_dgrad", "sat_conv2d_dgrad_bf16"])
+def test_stride_w_is_refused_where_no_kernel_reads_it(L, name):
+    """stride_w is the bf16 forward / filter-gradient stem view.  The fp32 kernel has one stride and no data gradient looks at it: such a
+    call used to return SAT_OK with an output of the anisotropic shape holding another convolution's values."""
+    rc, msg = _conv_call(L, name, _geom(L))
+    assert rc == 1 and "stride_w" in msg, (rc, msg)          # SAT_EINVAL
+
+
+@pytest.mark.parametrize("name", ["sat_conv2d_fwd", "sat_conv2d_wgrad", "sat_conv2d_dgrad", "sat_conv2d_dgrad_bf16"])
+@pytest.mark.parametrize("stride_w", [0, 2])
+def test_stride_w_equal_to_stride_or_zero_is_not_refused_for_it(L, name, stride_w):
+    """0 and the value of stride itself mean "isotropic": the stride_w check lets them through (the call then stops at the next check, an
+    empty output, before anything is launched)"""
+    rc, msg = _conv_call(L, name, _geom(L, stride_w=stride_w, H=3))
+    assert rc != 0 and "stride_w" not in msg and "empty output" in msg, (rc, msg)
