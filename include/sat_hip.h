@@ -285,7 +285,8 @@ int sat_decoder_infer_step(const sat_decoder_dims* d, const sat_decoder_params* 
  *   alpha_hist (max_gen_length + 1, B, beamk, L)  attention weights of each step's rows
  *   fin_*    (B, beamk)  finished hypotheses in the reference's append order: step at which they ended, the row they came from, raw score,
  *            mean beam score at that moment (for "BAR" rescoring); fin_count (B)
- * temperatures and special ids {START, PAD, END, UNK} are HOST arrays (read while enqueueing). */
+ * temperatures and special ids {START, PAD, END, UNK} are HOST arrays (read while enqueueing).
+ * This entry point and the six sat_beam_search_* below it are adapters over sat_beam_search (further down), kept for existing callers. */
 size_t sat_beam_search_workspace_bytes(const sat_decoder_dims* d, int32_t beamk);
 int sat_beam_search_batched(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann /* (B, L, D) */, int32_t beamk,
                             int32_t max_gen_length, const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host,
@@ -534,6 +535,43 @@ int sat_beam_search_ensemble(const sat_beam_ensemble* ensemble, int32_t beamk, i
                              const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
                              int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
                              void* stream);
+/* One search descriptor ("One search descriptor"): everything a batched search is asked to do, named once.  sat_beam_search
+ * runs what the entry points above run - the same checks in the same order, the same launches, the same bits - for the single-model
+ * search (d, w, ann) or the ensemble search (ensemble != NULL; d, w and ann are then NULL).  sampling / constraints / history / groups /
+ * required: NULL is off, and each struct's specification is the comment at its typedef above; the outputs have
+ * sat_beam_search_batched's layout, req_met is sat_beam_search_required's.  SAT_EINVAL before any launch: a null descriptor or output
+ * struct, whatever the entry points above refuse, and with an ensemble: a non-NULL d / w / ann, a sampling method other than
+ * SAT_SAMPLE_BEAM, decoder_noise, groups > 1, max_required > 0 (each message names its field).
+ * sat_beam_search_desc_workspace_bytes is the figure sat_beam_search compares workspace_bytes against: both come from one plan of
+ * the descriptor, so the query is exact and refuses (0, with sat_last_error set) every descriptor the search refuses; it reads no
+ * output, no workspace and no stream, so "the stream is being captured" is the search's refusal alone.
+ * The seven sat_beam_search_* entry points above are adapters kept for existing callers: each fills a descriptor and runs this path
+ * under its own name.  Their six workspace queries keep their documented figures; for the call a query was written for, its figure is
+ * never below this one (the groups, required and ensemble queries add history tables that a search without a rule does not use). */
+typedef struct sat_beam_search_desc {
+    const sat_decoder_dims*   d;        /* single model: d, w, ann; all three NULL with an ensemble */
+    const sat_decoder_params* w;
+    const float*              ann;      /* device (B, L, D) */
+    const sat_beam_ensemble*  ensemble; /* or NULL */
+    int32_t beamk, max_gen_length;
+    const float*   temperatures_host;
+    int32_t n_temperatures, reserved;
+    const int32_t* special_ids_host;    /* {START, PAD, END, UNK} */
+    const sat_beam_sampling*    sampling;
+    const sat_beam_constraints* constraints;
+    const sat_beam_history*     history;
+    const sat_beam_groups*      groups;
+    const sat_beam_required*    required;
+} sat_beam_search_desc;
+typedef struct sat_beam_search_out {
+    int32_t *tok_in, *prev_row;
+    float* alpha_hist;
+    int32_t *fin_count, *fin_step, *fin_row;
+    float *fin_score, *fin_mean;
+    int32_t* req_met;                   /* (B); NULL unless required words are on */
+} sat_beam_search_out;
+size_t sat_beam_search_desc_workspace_bytes(const sat_beam_search_desc* s);
+int sat_beam_search(const sat_beam_search_desc* s, const sat_beam_search_out* o, void* workspace, size_t workspace_bytes, void* stream);
 /* The combine kernel of sat_beam_search_ensemble on its own: combined (rows, V) = c as above from `members` device arrays (rows, V).
  * logits is a HOST array of device pointers, weights a HOST array.  Finite logits give finite output (no -inf, no NaN), however
  * peaked a member is; a -inf logit contributes no mass.  No atomics: same input, same bits.  SAT_EINVAL before the launch: a null

@@ -114,6 +114,24 @@ class BeamRequired(C.Structure):
     _fields_ = [("max_required", C.c_int32), ("reserved", C.c_int32), ("words", C.c_void_p), ("n_words", C.c_void_p)]
 
 
+class BeamSearchDesc(C.Structure):
+    """sat_beam_search_desc (include/sat_hip.h): one batched search, single-model (d, w, ann) or ensemble"""
+    _fields_ = [("d", C.POINTER(DecoderDims)), ("w", C.POINTER(DecoderParams)), ("ann", C.c_void_p), ("ensemble", C.POINTER(BeamEnsemble)),
+                ("beamk", C.c_int32), ("max_gen_length", C.c_int32), ("temperatures_host", C.POINTER(C.c_float)), ("n_temperatures", C.c_int32),
+                ("reserved", C.c_int32), ("special_ids_host", C.POINTER(C.c_int32)), ("sampling", C.POINTER(BeamSampling)),
+                ("constraints", C.POINTER(BeamConstraints)), ("history", C.POINTER(BeamHistory)), ("groups", C.POINTER(BeamGroups)),
+                ("required", C.POINTER(BeamRequired))]
+
+
+#: the buffers a search leaves on the device, in sat_beam_search_out's order (req_met: with required words only)
+SEARCH_OUTPUTS = ("tok_in", "prev_row", "alpha_hist", "fin_count", "fin_step", "fin_row", "fin_score", "fin_mean", "req_met")
+
+
+class BeamSearchOut(C.Structure):
+    """sat_beam_search_out (include/sat_hip.h)"""
+    _fields_ = [(k, C.c_void_p) for k in SEARCH_OUTPUTS]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [("offset", C.c_int64)] + [(k, C.c_int32) for k in ("height", "width", "crop_top", "crop_left", "crop_h", "crop_w", "resized_h",
                                                                   "resized_w", "out_top", "out_left", "flip", "reserved")]
@@ -300,6 +318,8 @@ SYMBOLS.update({
     "sat_beam_search_ensemble_workspace_bytes": (C.c_size_t, [C.POINTER(BeamEnsemble), _i32, _i32]),
     "sat_beam_search_ensemble": (C.c_int, [C.POINTER(BeamEnsemble), _i32, _i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_int32), C.POINTER(BeamConstraints),
                                            C.POINTER(BeamHistory), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sat_beam_search_desc_workspace_bytes": (C.c_size_t, [C.POINTER(BeamSearchDesc)]),
+    "sat_beam_search": (C.c_int, [C.POINTER(BeamSearchDesc), C.POINTER(BeamSearchOut), _vp, C.c_size_t, _vp]),
     "sat_beam_ensemble_scores": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i32, _i32, _i32, _i32, _f, _vp, _vp]),
     "sat_beam_history_scores": (C.c_int, [_vp, _i32, _i32, _f, _vp, _i32, _vp, _vp, _vp, _i32, C.POINTER(BeamHistory), _i32, _i32, _vp, _vp]),
     "sat_topk": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),

@@ -8,7 +8,12 @@ arrays, the per-image loop (``SATDecoder.beam_decode``) applies the same rules w
 ``resolve_history`` does the same for the rules that read what a hypothesis has already said ("History rules"):
 ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` become one checked ``HistoryRules`` (or ``None``), handed to
 ``sat_beam_search_history`` as a ``sat_beam_history``; ``resolve_all`` runs both.  ``resolve_groups`` checks the diverse beam search,
-``resolve_required`` the words a caption must contain ("Required words"), handed to ``sat_beam_search_required``."""
+``resolve_required`` the words a caption must contain ("Required words"), handed to ``sat_beam_search_required``.
+
+``SearchOptions`` names the options of a search once; ``SearchOptions.resolve`` is the one refusal sequence every caller runs before
+any launch."""
+import dataclasses
+import inspect
 import math
 
 import torch
@@ -55,6 +60,12 @@ class HistoryRules:
 
 #: sat_beam_search_history keeps a row's history in a table of SAT_CAPTION_MAX_LEN words (include/sat_hip.h)
 HISTORY_MAX_LEN = 128
+
+
+def check_sample_topp(sample_method, sample_topp):
+    """``sample_topp`` of "nucleus" sampling is a finite share in (0, 1] (include/sat_hip.h refuses the same values)"""
+    if sample_method == "nucleus" and not (0.0 < float(sample_topp) <= 1.0):
+        raise ValueError("sample_topp %r outside (0, 1] (sample_method='nucleus')" % (sample_topp,))
 
 
 def check_ancestral(sample_method, beamk, graph=False, topg=None, prefix=None, banned=None, no_unk=False, no_repeat_ngram=None, min_length=None,
@@ -378,3 +389,58 @@ def resolve_all(stoi, V, B, beamk, max_gen_length, sample_method="beam", topg=No
     special = {int(stoi[s]) for s in SPECIALS}
     n_banned = len([t for t in con.banned if t not in special]) if con is not None else 0
     return con, resolve_history(V, beamk, max_gen_length, sample_method, topg, n_banned, no_repeat_ngram, min_length, repetition_penalty)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class SearchOptions:
+    """The options of one search (``SATDecoder.beam_decode_batched`` documents them), with the defaults of every public signature.
+    Callers build one from their own keywords (``from_kwargs(locals())``) and pass it on whole, so no option travels by position."""
+    sample_method: str = "beam"
+    sample_topk: int = 3
+    sample_topp: float = 0.9
+    decoder_noise: object = None
+    seed: object = None
+    gumbel: object = None
+    normals: object = None
+    graph: bool = False
+    topg: object = None
+    prefix: object = None
+    banned: object = None
+    no_unk: bool = False
+    no_repeat_ngram: object = None
+    min_length: object = None
+    repetition_penalty: object = None
+    beam_groups: object = None
+    diversity_penalty: float = 0.5
+    required: object = None
+
+    @classmethod
+    def from_kwargs(cls, kw, **over):
+        """the options among the keywords ``kw`` (a caller's ``locals()``), ``over`` on top; ``sample_method`` as a string"""
+        names = {f.name for f in dataclasses.fields(cls)}
+        o = {k: v for k, v in dict(kw, **over).items() if k in names}
+        if "sample_method" in o:
+            o["sample_method"] = str(o["sample_method"])
+        return cls(**o)
+
+    def kwargs(self, fn):
+        """the options the public function ``fn`` takes one by one, as keywords"""
+        names = inspect.signature(fn).parameters
+        return {f.name: getattr(self, f.name) for f in dataclasses.fields(self) if f.name in names}
+
+    def resolve(self, stoi, V, B, beamk, max_gen_length, batched=True):
+        """Every ``ValueError`` of a search over ``B`` images, before any launch and touching no GPU, in one order: ``sample_topp``, what
+        "ancestral" sampling refuses, the constraints and history rules, the groups, the required words.  ``batched=False`` is the
+        per-image loop ``beam_decode``, which has neither groups nor required words.  Returns ``(con, hist, grp, req)``, each ``None``
+        when off."""
+        assert self.sample_method in L.SAMPLE_METHODS
+        check_sample_topp(self.sample_method, self.sample_topp)
+        check_ancestral(self.sample_method, beamk, self.graph, self.topg, self.prefix, self.banned, self.no_unk, self.no_repeat_ngram, self.min_length,
+                        self.repetition_penalty)
+        con, hist = resolve_all(stoi, V, B, beamk, max_gen_length, self.sample_method, self.topg, self.prefix, self.banned, self.no_unk, self.no_repeat_ngram,
+                                self.min_length, self.repetition_penalty)
+        grp = resolve_groups(beamk, self.beam_groups, self.diversity_penalty, self.sample_method, self.decoder_noise, self.topg, self.prefix, self.graph,
+                             batched=batched, V=V)
+        req = resolve_required(stoi, V, B, beamk, max_gen_length, self.required, self.sample_method, self.decoder_noise, self.topg, self.prefix, self.banned,
+                               self.no_unk, self.beam_groups, self.graph, batched=batched)
+        return con, hist, grp, req

@@ -164,47 +164,71 @@ int sat_decoder_infer_step(const sat_decoder_dims* d, const sat_decoder_params* 
     if (!ann || !tokens || !h || !c || !logits || !alpha || !workspace) return fail(SAT_EINVAL, "decoder_infer_step: null pointer");
     return decoder_infer_step(*d, *w, ann, tokens, beams, max_beams, h, c, logits, alpha, h_noise, (char*)workspace, workspace_bytes, (hipStream_t)stream);
 }
+// ---- the batched search: one descriptor, one plan (decoder.hip: beam_plan), one entry point
+static int check_ensemble(const sat_beam_ensemble* e, const char* what) {
+    SAT_TRY(beam_ensemble_check(e, what));
+    for (int i = 0; i < e->members; ++i) { SAT_TRY(check_dims(e->dims[i])); SAT_TRY(check_params(e->dims[i], e->params[i], what)); }
+    return SAT_OK;
+}
+// what every search entry checks in front of the plan, under the caller's name; o == NULL: the workspace query, which has no outputs
+static int check_search(const sat_beam_search_desc* s, const sat_beam_search_out* o, const void* workspace, const char* what) {
+    if (s->ensemble) SAT_TRY(check_ensemble(s->ensemble, what));
+    else { SAT_TRY(check_dims(s->d)); SAT_TRY(check_params(s->d, s->w, what)); }
+    if ((!s->ensemble && !s->ann) || !s->temperatures_host || !s->special_ids_host ||
+        (o && (!o->tok_in || !o->prev_row || !o->alpha_hist || !o->fin_count || !o->fin_step || !o->fin_row || !o->fin_score || !o->fin_mean || !workspace)))
+        return fail(SAT_EINVAL, "%s: null pointer", what);
+    for (int i = 0; i < s->n_temperatures; ++i) if (!(s->temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "%s: temperature %g", what, s->temperatures_host[i]);
+    return SAT_OK;
+}
+static int search_as(const char* what, const sat_beam_search_desc& s, const sat_beam_search_out& o, void* workspace, size_t workspace_bytes, void* stream) {
+    SAT_TRY(check_search(&s, &o, workspace, what));
+    return beam_search(s, o, (char*)workspace, workspace_bytes, (hipStream_t)stream);
+}
+size_t sat_beam_search_desc_workspace_bytes(const sat_beam_search_desc* s) {
+    size_t total = 0;
+    if (!s) { fail(SAT_EINVAL, "beam_search_desc_workspace_bytes: null descriptor"); return 0; }
+    if (check_search(s, nullptr, nullptr, "beam_search_desc_workspace_bytes") != SAT_OK || beam_search_workspace_bytes(*s, total) != SAT_OK) return 0;
+    return total;
+}
+int sat_beam_search(const sat_beam_search_desc* s, const sat_beam_search_out* o, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!s) return fail(SAT_EINVAL, "beam_search: null descriptor");
+    if (!o) return fail(SAT_EINVAL, "beam_search: null output struct");
+    return search_as("beam_search", *s, *o, workspace, workspace_bytes, stream);
+}
+// ---- the entry points and queries from before the descriptor, kept for existing callers: each search fills a descriptor and runs the
+// shared path under its own name; each query keeps its documented figure (an upper bound of the plan's for the features it names)
+#define SAT_SINGLE_DESC(sampling, constraints, history, groups, required) \
+    {d, w, ann, nullptr, beamk, max_gen_length, temperatures_host, n_temperatures, 0, special_ids_host, sampling, constraints, history, groups, required}
+#define SAT_SEARCH_OUT(req_met) {tok_in, prev_row, alpha_hist, fin_count, fin_step, fin_row, fin_score, fin_mean, req_met}
 size_t sat_beam_search_workspace_bytes(const sat_decoder_dims* d, int32_t beamk) {
     if (check_dims(d) != SAT_OK || beamk < 1) return 0;
-    return decoder_beam_workspace_bytes(*d, beamk);
+    return decoder_beam_workspace_bytes(*d, beamk, 0, 0, 1);
 }
 int sat_beam_search_batched(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
                             const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, int32_t* tok_in, int32_t* prev_row,
                             float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_batched"));
-    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_batched: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_batched: temperature %g", temperatures_host[i]);
-    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+    const sat_beam_search_desc s = SAT_SINGLE_DESC(nullptr, nullptr, nullptr, nullptr, nullptr);
+    return search_as("beam_search_batched", s, SAT_SEARCH_OUT(nullptr), workspace, workspace_bytes, stream);
 }
 int sat_beam_search_sampled(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
                             const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
                             int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score,
                             float* fin_mean, void* workspace, size_t workspace_bytes, void* stream) {
-    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_sampled"));
-    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_sampled: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_sampled: temperature %g", temperatures_host[i]);
-    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling);
+    const sat_beam_search_desc s = SAT_SINGLE_DESC(sampling, nullptr, nullptr, nullptr, nullptr);
+    return search_as("beam_search_sampled", s, SAT_SEARCH_OUT(nullptr), workspace, workspace_bytes, stream);
 }
 size_t sat_beam_search_constrained_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t topg) {
     if (check_dims(d) != SAT_OK || beamk < 1) return 0;
     if (topg < 0 || topg > d->V) { fail(SAT_EINVAL, "beam_search_constrained_workspace_bytes: topg %d outside 0..V=%d", topg, d->V); return 0; }
-    return decoder_beam_workspace_bytes(*d, beamk, topg);
+    return decoder_beam_workspace_bytes(*d, beamk, topg, 0, 1);
 }
 int sat_beam_search_constrained(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
                                 const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
                                 const sat_beam_constraints* constraints, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
                                 int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes, void* stream) {
-    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_constrained"));
-    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_constrained: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_constrained: temperature %g", temperatures_host[i]);
-    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints);
+    const sat_beam_search_desc s = SAT_SINGLE_DESC(sampling, constraints, nullptr, nullptr, nullptr);
+    return search_as("beam_search_constrained", s, SAT_SEARCH_OUT(nullptr), workspace, workspace_bytes, stream);
 }
 size_t sat_beam_search_history_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t topg, int32_t max_gen_length) {
     if (check_dims(d) != SAT_OK || beamk < 1) return 0;
@@ -213,19 +237,15 @@ size_t sat_beam_search_history_workspace_bytes(const sat_decoder_dims* d, int32_
         fail(SAT_EINVAL, "beam_search_history_workspace_bytes: max_gen_length %d outside 0..%d", max_gen_length, SAT_CAPTION_MAX_LEN - 1);
         return 0;
     }
-    return decoder_beam_workspace_bytes(*d, beamk, topg, max_gen_length + 1);
+    return decoder_beam_workspace_bytes(*d, beamk, topg, max_gen_length + 1, 1);
 }
 int sat_beam_search_history(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
                             const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
                             const sat_beam_constraints* constraints, const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row, float* alpha_hist,
                             int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
                             void* stream) {
-    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_history"));
-    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_history: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_history: temperature %g", temperatures_host[i]);
-    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history);
+    const sat_beam_search_desc s = SAT_SINGLE_DESC(sampling, constraints, history, nullptr, nullptr);
+    return search_as("beam_search_history", s, SAT_SEARCH_OUT(nullptr), workspace, workspace_bytes, stream);
 }
 size_t sat_beam_search_groups_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t groups, int32_t max_gen_length) {
     if (check_dims(d) != SAT_OK || beamk < 1) return 0;
@@ -242,13 +262,8 @@ int sat_beam_search_groups(const sat_decoder_dims* d, const sat_decoder_params* 
                            const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_groups* groups, int32_t* tok_in,
                            int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean,
                            void* workspace, size_t workspace_bytes, void* stream) {
-    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_groups"));
-    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_groups: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_groups: temperature %g", temperatures_host[i]);
-    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history,
-                                groups);
+    const sat_beam_search_desc s = SAT_SINGLE_DESC(sampling, constraints, history, groups, nullptr);
+    return search_as("beam_search_groups", s, SAT_SEARCH_OUT(nullptr), workspace, workspace_bytes, stream);
 }
 size_t sat_beam_search_required_workspace_bytes(const sat_decoder_dims* d, int32_t beamk, int32_t max_gen_length, int32_t max_required) {
     if (check_dims(d) != SAT_OK || beamk < 1) return 0;
@@ -256,31 +271,15 @@ size_t sat_beam_search_required_workspace_bytes(const sat_decoder_dims* d, int32
     const sat_beam_required shape = {max_required, 0, (const int32_t*)d, (const int32_t*)d};      // the sizes only: the pointers are not read
     if (beam_required_check(&shape, beamk, max_gen_length, "beam_search_required_workspace_bytes") != SAT_OK) return 0;
     // room for the history tables where they can exist at all (required words off and max_gen_length + 1 > SAT_CAPTION_MAX_LEN: none)
-    return decoder_beam_workspace_bytes(*d, beamk, 0, max_gen_length + 1 <= SAT_CAPTION_MAX_LEN ? max_gen_length + 1 : 0);
+    return decoder_beam_workspace_bytes(*d, beamk, 0, max_gen_length + 1 <= SAT_CAPTION_MAX_LEN ? max_gen_length + 1 : 0, 1);
 }
 int sat_beam_search_required(const sat_decoder_dims* d, const sat_decoder_params* w, const float* ann, int32_t beamk, int32_t max_gen_length,
                              const float* temperatures_host, int32_t n_temperatures, const int32_t* special_ids_host, const sat_beam_sampling* sampling,
                              const sat_beam_constraints* constraints, const sat_beam_history* history, const sat_beam_required* required,
                              int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count, int32_t* fin_step, int32_t* fin_row,
                              float* fin_score, float* fin_mean, int32_t* req_met, void* workspace, size_t workspace_bytes, void* stream) {
-    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "beam_search_required"));
-    if (!ann || !temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_required: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_required: temperature %g", temperatures_host[i]);
-    return decoder_beam_batched(*d, *w, ann, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, sampling, constraints, history,
-                                nullptr, required, req_met);
-}
-int sat_beam_required_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t V, const int32_t* hist, int32_t hist_stride,
-                             int32_t hist_len, int32_t first_step, const sat_beam_required* required, int32_t end_id, float* work, float* values,
-                             int32_t* indices, void* stream) {
-    if (!scores || !klive || !required || !work || !values || !indices) return fail(SAT_EINVAL, "beam_required_select: null pointer");
-    return beam_required_select(scores, klive, B, beamk, V, hist, hist_stride, hist_len, first_step, *required, end_id, work, values, indices, (hipStream_t)stream);
-}
-static int check_ensemble(const sat_beam_ensemble* e, const char* what) {
-    SAT_TRY(beam_ensemble_check(e, what));
-    for (int i = 0; i < e->members; ++i) { SAT_TRY(check_dims(e->dims[i])); SAT_TRY(check_params(e->dims[i], e->params[i], what)); }
-    return SAT_OK;
+    const sat_beam_search_desc s = SAT_SINGLE_DESC(sampling, constraints, history, nullptr, required);
+    return search_as("beam_search_required", s, SAT_SEARCH_OUT(req_met), workspace, workspace_bytes, stream);
 }
 size_t sat_beam_search_ensemble_workspace_bytes(const sat_beam_ensemble* ensemble, int32_t beamk, int32_t max_gen_length) {
     if (beam_ensemble_check(ensemble, "beam_search_ensemble_workspace_bytes") != SAT_OK) return 0;
@@ -293,12 +292,18 @@ int sat_beam_search_ensemble(const sat_beam_ensemble* ensemble, int32_t beamk, i
                              const sat_beam_history* history, int32_t* tok_in, int32_t* prev_row, float* alpha_hist, int32_t* fin_count,
                              int32_t* fin_step, int32_t* fin_row, float* fin_score, float* fin_mean, void* workspace, size_t workspace_bytes,
                              void* stream) {
-    SAT_TRY(check_ensemble(ensemble, "beam_search_ensemble"));
-    if (!temperatures_host || !special_ids_host || !tok_in || !prev_row || !alpha_hist || !fin_count || !fin_step || !fin_row || !fin_score || !fin_mean || !workspace)
-        return fail(SAT_EINVAL, "beam_search_ensemble: null pointer");
-    for (int i = 0; i < n_temperatures; ++i) if (!(temperatures_host[i] > 0.f)) return fail(SAT_EINVAL, "beam_search_ensemble: temperature %g", temperatures_host[i]);
-    return decoder_beam_ensemble(*ensemble, beamk, max_gen_length, temperatures_host, n_temperatures, special_ids_host, tok_in, prev_row, alpha_hist, fin_count,
-                                 fin_step, fin_row, fin_score, fin_mean, (char*)workspace, workspace_bytes, (hipStream_t)stream, constraints, history);
+    if (!ensemble) return beam_ensemble_check(ensemble, "beam_search_ensemble");        // "null ensemble struct": a descriptor without one is a single-model search
+    const sat_beam_search_desc s = {nullptr, nullptr, nullptr, ensemble, beamk, max_gen_length, temperatures_host, n_temperatures, 0, special_ids_host,
+                                    nullptr, constraints, history, nullptr, nullptr};
+    return search_as("beam_search_ensemble", s, SAT_SEARCH_OUT(nullptr), workspace, workspace_bytes, stream);
+}
+#undef SAT_SINGLE_DESC
+#undef SAT_SEARCH_OUT
+int sat_beam_required_select(const float* scores, const int32_t* klive, int32_t B, int32_t beamk, int32_t V, const int32_t* hist, int32_t hist_stride,
+                             int32_t hist_len, int32_t first_step, const sat_beam_required* required, int32_t end_id, float* work, float* values,
+                             int32_t* indices, void* stream) {
+    if (!scores || !klive || !required || !work || !values || !indices) return fail(SAT_EINVAL, "beam_required_select: null pointer");
+    return beam_required_select(scores, klive, B, beamk, V, hist, hist_stride, hist_len, first_step, *required, end_id, work, values, indices, (hipStream_t)stream);
 }
 int sat_beam_ensemble_scores(const float* const* logits, const float* weights, int32_t members, int32_t combine, int32_t rows, int32_t V,
                              float temperature, float* combined, void* stream) {

@@ -23,34 +23,30 @@ struct AttPlan {
 };
 int attention_plan(int op, int R, int L, int D, int A, int hc_ld, int T1, unsigned flags, AttPlan& plan, const char* who);
 int launch_attention_fwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf,
-                         const int* lengths, int step, float* alphas, int T1, float* Z, float* XZ, int B, int R, int L, int D, int A, float* sc = nullptr, void* xzb = nullptr,
-                         const void* annb = nullptr);
+                         const int* lengths, int step, float* alphas, int T1, float* Z, float* XZ, int B, int R, int L, int D, int A, float* sc, void* xzb,
+                         const void* annb);
 size_t decoder_infer_workspace_bytes(const sat_decoder_dims& d, int Kmax);
 int decoder_infer_begin(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int Kmax, float* h, float* c,
                         char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_infer_step(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, const int* tokens, int K, int Kmax,
                        float* h, float* c, float* logits, float* alpha, const float* h_noise, char* ws, size_t ws_bytes, hipStream_t st);
-size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg = 0, int hist_stride = 0, int groups = 1);
+size_t decoder_beam_workspace_bytes(const sat_decoder_dims& d, int K, int topg, int hist_stride, int groups);
 int beam_groups_check(const sat_beam_groups* g, const char* what);
 bool beam_history_on(const sat_beam_history* h);
 int beam_history_check(const sat_beam_history* h, int max_gen_length, const char* what);
-int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
-                         int n_temps, const int* special_host, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row,
-                         float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* sampling,
-                         const sat_beam_constraints* constraints = nullptr, const sat_beam_history* history = nullptr,
-                         const sat_beam_groups* groups = nullptr, const sat_beam_required* required = nullptr, int* req_met = nullptr);
+// one batched search, single-model or ensemble, described once (include/sat_hip.h, sat_beam_search_desc): the query returns the
+// `total` the search compares its workspace against, and both refuse the same descriptors
+int beam_search_workspace_bytes(const sat_beam_search_desc& s, size_t& total);
+int beam_search(const sat_beam_search_desc& s, const sat_beam_search_out& o, char* ws, size_t ws_bytes, hipStream_t st);
 int beam_required_check(const sat_beam_required* r, int K, int max_gen_length, const char* what);
 int beam_ensemble_check_weights(const float* weight, int members, int combine, const char* what);
 int beam_ensemble_check(const sat_beam_ensemble* e, const char* what);
 size_t decoder_beam_ensemble_workspace_bytes(const sat_beam_ensemble& e, int K, int hist_stride);
-int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length, const float* temps_host, int n_temps, const int* special_host, int* tok_in,
-                          int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws,
-                          size_t ws_bytes, hipStream_t st, const sat_beam_constraints* constraints, const sat_beam_history* history);
 int beam_ensemble_scores(const float* const* logits, const float* weight, int members, int combine, int rows, int V, float temperature, float* combined,
                          hipStream_t st);
 int launch_attention_bwd(hipStream_t st, const float* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
                          const float* alphas, const float* dalphas, int T1, const float* Z, const float* dZ, const float* dXZ, float* DZ, float* dhc,
-                         int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, void* dhcb = nullptr, const void* annb = nullptr);
+                         int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, void* dhcb, const void* annb);
 int attention_context_bwd(const float* alphas, const float* DZ, const int* lengths, float* dann, int accumulate, int B, int R, int T1, int L, int D, hipStream_t st);
 int lstm_cell_fwd(const float* x, int in, const float* h_prev, const float* c_prev, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                   float* gates, float* h_new, float* c_new, float* bias_scratch, int N, int n, hipStream_t st);

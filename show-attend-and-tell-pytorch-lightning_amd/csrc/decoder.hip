@@ -758,7 +758,7 @@ int decoder_infer_step(const sat_decoder_dims& d, const sat_decoder_params& p, c
     // decoder_noise (model.py:322-324): the noise joins h after attention and the gate were taken from the clean state, so
     // it reaches the step through the recurrent products only: gates += noise * W_hh^T (the GEMM is linear in h)
     if (h_noise) SAT_TRY(gemm(st, A_ROW, B_ROW, h_noise, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, K, 4 * n, n, 1));
-    SAT_TRY(launch_attention_fwd(st, ann, w.U, w.hc, HCW, p.att_f, w.ones, 0, alpha, 1, w.Z, w.XZ, 1, K, d.L, D, A, w.sc));
+    SAT_TRY(launch_attention_fwd(st, ann, w.U, w.hc, HCW, p.att_f, w.ones, 0, alpha, 1, w.Z, w.XZ, 1, K, d.L, D, A, w.sc, nullptr, nullptr));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, w.hc + A + D, HCW, K, 4 * n, m, 1));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.XZ, D, p.w_ih + m, m + D, w.hc + A + D, HCW, K, 4 * n, D, 1));
     hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)K * n, 256)), dim3(256), 0, st, w.hc + A + D, HCW, (const float*)nullptr, c, h, c, h, w.ones, 0, K, n);
@@ -925,7 +925,7 @@ static int beam_member_step(const sat_decoder_dims& d, const sat_decoder_params&
         SAT_TRY(gemm(st, A_ROW, B_ROW, htop, n, w.Wcat, n, w.hc, HCW, N, A + D, n, 0, EPI_BIAS_SIGMOID_RANGE, w.bcat, nullptr, nullptr, nullptr, 0, A, A + D));
         SAT_TRY(gemm(st, A_ROW, B_ROW, h, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, N, 4 * n, n, 0, EPI_BIAS, w.bcat + A + D));
     }
-    SAT_TRY(launch_attention_fwd(st, ann, w.U, w.hc, HCW, p.att_f, live, 0, alpha, 1, w.Z, w.XZ, B, K, d.L, D, A, w.sc));
+    SAT_TRY(launch_attention_fwd(st, ann, w.U, w.hc, HCW, p.att_f, live, 0, alpha, 1, w.Z, w.XZ, B, K, d.L, D, A, w.sc, nullptr, nullptr));
     if (noisy) SAT_TRY(gemm(st, A_ROW, B_ROW, w.noise, n, w.Wcat + (long)(A + D) * n, n, w.hc + A + D, HCW, N, 4 * n, n, 1));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, w.hc + A + D, HCW, N, 4 * n, m, 1));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.XZ, D, p.w_ih + m, m + D, w.hc + A + D, HCW, N, 4 * n, D, 1));
@@ -966,23 +966,36 @@ struct BeamMember {
 // The combine stage of an ensemble: the members' logits at 1 / T -> `combined`, the logits the search then scores at temperature 1.
 struct BeamCombine { EnsembleArgs args; int geometric; float* combined; };
 
-// The search loop of decoder_beam_batched and decoder_beam_ensemble, after their argument checks: M members step on the shared tokens,
-// the scores come from member 0's logits at 1 / T (comb == NULL: the single-model search) or from the combined logits; the score
-// kernels, the selection, beam_update and the history advance run once, in member 0's workspace.  con: NULL, or the constrained
-// search's per-image selection (which the history rules and the groups run in as well); hist: NULL, or the rules that are on (all
-// off with the tables on: required words); req: NULL, or the required words, which select in beam_select_kernel's place.
-static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, int K, int G, float lambda, int max_gen_length, const float* temps_host, int n_temps,
-                            const int* special_host, int* tok_in, int* prev_row, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean,
-                            hipStream_t st, const sat_beam_sampling* smp, const sat_beam_constraints* con, const sat_beam_history* hist,
-                            const sat_beam_required* req = nullptr, int* req_met = nullptr) {
+// What a search runs, decided once from its descriptor by beam_plan: the workspace query returns `total`, the search lays its workspace
+// out from the same fields and compares `total` with the bytes it was given.  smp: NULL = "beam" sampling without noise; con: NULL, or
+// the constrained search's per-image selection (the history rules, the groups and the required words run in it as well); hist: NULL, or
+// the rules with the history tables on (every rule off with them on: required words); req: NULL, or the required words, which select
+// in beam_select_kernel's place; G groups (1 = off) with diversity penalty lambda.
+struct BeamPlan {
+    const sat_beam_sampling* smp; const sat_beam_constraints* con; const sat_beam_history* hist; const sat_beam_required* req;
+    int G; float lambda; int topg, hist_stride; size_t total;
+};
+// the call a plan is made for: NULL for the workspace query, which has no outputs, no workspace and no stream to refuse
+struct BeamCall { const sat_beam_search_out* o; size_t ws_bytes; hipStream_t st; };
+
+// The search loop of decoder_beam_batched and decoder_beam_ensemble, after beam_plan: M members step on the shared tokens, the scores
+// come from member 0's logits at 1 / T (comb == NULL: the single-model search) or from the combined logits; the score kernels, the
+// selection, beam_update and the history advance run once, in member 0's workspace.
+static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, const sat_beam_search_desc& s, const sat_beam_search_out& o, const BeamPlan& plan,
+                            hipStream_t st) {
+    const int K = s.beamk, G = plan.G, max_gen_length = s.max_gen_length, n_temps = s.n_temperatures, hist_stride = plan.hist_stride, topg = plan.topg;
+    const float lambda = plan.lambda, *const temps_host = s.temperatures_host;
+    const int* special_host = s.special_ids_host;
+    int *const tok_in = o.tok_in, *const prev_row = o.prev_row, *const fin_count = o.fin_count, *const fin_step = o.fin_step, *const fin_row = o.fin_row;
+    float *const fin_score = o.fin_score, *const fin_mean = o.fin_mean;
+    const sat_beam_sampling* smp = plan.smp; const sat_beam_constraints* con = plan.con; const sat_beam_history* hist = plan.hist; const sat_beam_required* req = plan.req;
     const BeamWs& w = mem[0].w;
     const int B = mem[0].d->B, N = B * K, V = mem[0].d->V;
     const int START = special_host[0], END = special_host[2];
     const int method = smp ? smp->method : 0;
     const bool hist_on = hist != nullptr;
-    const int hist_stride = hist_on ? max_gen_length + 1 : 0;
     const float theta = hist_on && hist->repetition_penalty != 0.f ? hist->repetition_penalty : 1.0f;
-    const int topg = con ? con->topg : 0, max_prefix = con ? con->max_prefix : 0;
+    const int max_prefix = con ? con->max_prefix : 0;
     const int* prefix_len = max_prefix > 0 ? con->prefix_len : nullptr;
     for (int i = 0; i < M; ++i) SAT_TRY(beam_member_begin(*mem[i].d, *mem[i].p, mem[i].ann, mem[i].w, K, G, special_host, st));
     auto zero_w = [&](void* dst, long n_) { beam_zero_words(st, dst, n_); };
@@ -1091,17 +1104,18 @@ static int beam_search_loop(BeamMember* mem, int M, const BeamCombine* comb, int
     }
     if (req) {                                             // the finished lists keep the hypotheses that contain the most required words
         hipLaunchKernelGGL(beam_required_finish_kernel, dim3(B), dim3(256), 0, st, tok_in, prev_row, fin_count, fin_step, fin_row, fin_score, fin_mean,
-                           req->words, req->n_words, req->max_required, B, K, max_gen_length, V, req_met);
+                           req->words, req->n_words, req->max_required, B, K, max_gen_length, V, o.req_met);
         SAT_TRY(launch_ok("beam_required_finish"));
     }
     return SAT_OK;
 }
 
-int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int K, int max_gen_length, const float* temps_host,
-                         int n_temps, const int* special_host /* START, PAD, END, UNK */, int* tok_in, int* prev_row, float* alpha_hist, int* fin_count,
-                         int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws, size_t ws_bytes, hipStream_t st, const sat_beam_sampling* smp,
-                         const sat_beam_constraints* con, const sat_beam_history* hist, const sat_beam_groups* grp, const sat_beam_required* req,
-                         int* req_met) {
+// The plan of a single-model search: which of the features are on, every refusal they have (in this order), and the workspace they need.
+static int beam_plan_single(const sat_beam_search_desc& s, const BeamCall* call, BeamPlan& plan) {
+    const sat_decoder_dims& d = *s.d;
+    const int K = s.beamk, max_gen_length = s.max_gen_length;
+    const sat_beam_sampling* smp = s.sampling; const sat_beam_constraints* con = s.constraints; const sat_beam_history* hist = s.history;
+    const sat_beam_groups* grp = s.groups; const sat_beam_required* req = s.required;
     // no constraint at all: exactly the launches of the plain / sampled search
     if (con && con->topg == 0 && con->max_prefix == 0 && con->n_banned == 0) con = nullptr;
     const int method = smp ? smp->method : 0;
@@ -1115,29 +1129,29 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         SAT_REQUIRE(!smp || smp->decoder_noise == 0.f, "beam_groups: groups do not combine with decoder_noise");
         SAT_REQUIRE(!con || con->topg == 0, "beam_groups: groups do not combine with topg %d", con ? con->topg : 0);
         SAT_REQUIRE(!con || con->max_prefix == 0, "beam_groups: groups do not combine with a forced prefix (max_prefix %d)", con ? con->max_prefix : 0);
-        SAT_TRY(not_capturing(st, "beam_groups"));
+        if (call) SAT_TRY(not_capturing(call->st, "beam_groups"));
     }
     SAT_TRY(beam_required_check(req, K, max_gen_length, "beam_required"));
     if (req && req->max_required == 0) req = nullptr;      // off: today's search, the same launches
     if (req) {                                             // the words select in the constrained search's place ("Required words")
-        SAT_REQUIRE(req_met, "beam_required: null pointer (req_met with max_required %d)", req->max_required);
+        SAT_REQUIRE(!call || call->o->req_met, "beam_required: null pointer (req_met with max_required %d)", req->max_required);
         SAT_REQUIRE(method == SAT_SAMPLE_BEAM, "beam_required: required words combine with \"beam\" sampling only (method %d)", method);
         SAT_REQUIRE(!smp || smp->decoder_noise == 0.f, "beam_required: required words do not combine with decoder_noise");
         SAT_REQUIRE(!con || con->topg == 0, "beam_required: required words do not combine with topg %d", con ? con->topg : 0);
         SAT_REQUIRE(!con || con->max_prefix == 0, "beam_required: required words do not combine with a forced prefix (max_prefix %d)", con ? con->max_prefix : 0);
         SAT_REQUIRE(G == 1, "beam_required: required words do not combine with groups %d", G);
-        SAT_TRY(not_capturing(st, "beam_required"));
+        if (call) SAT_TRY(not_capturing(call->st, "beam_required"));
     }
     SAT_TRY(beam_history_check(hist, max_gen_length, "beam_history"));
     static const sat_beam_history no_rules = {};
     if (req && !beam_history_on(hist)) hist = &no_rules;   // the history tables are on, every rule off: the constrained search's scores
     const bool hist_on = req || beam_history_on(hist);
-    const sat_beam_constraints no_constraint = {};
+    static const sat_beam_constraints no_constraint = {};
     if (hist_on) {                                         // the history rules run in the constrained search's per-image selection
         SAT_REQUIRE(max_gen_length + 1 <= SAT_BEAM_HIST_MAX, "beam_history: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length,
                     SAT_BEAM_HIST_MAX);
         SAT_REQUIRE(method != SAT_SAMPLE_ANCESTRAL, "beam_history: ancestral sampling does not combine with the history rules");
-        SAT_TRY(not_capturing(st, "beam_history"));
+        if (call) SAT_TRY(not_capturing(call->st, "beam_history"));
         if (!con) con = &no_constraint;
     }
     if (G > 1 && !con) con = &no_constraint;
@@ -1152,22 +1166,27 @@ int decoder_beam_batched(const sat_decoder_dims& d, const sat_decoder_params& p,
         SAT_REQUIRE((con->max_prefix == 0 || (con->prefix && con->prefix_len)) && (con->n_banned == 0 || con->banned),
                     "beam_constrained: null pointer (prefix / prefix_len with max_prefix %d, banned with n_banned %d)", con->max_prefix, con->n_banned);
     }
-    const BeamWs w = beam_layout(d, K, ws, con ? con->topg : 0, hist_stride, G);
     SAT_REQUIRE(method >= 0 && method <= SAT_SAMPLE_ANCESTRAL && (method != 2 || (smp->sample_topk >= 1 && smp->sample_topk <= d.V)),
                 "beam_batched: sampling method %d, sample_topk %d", method, smp ? smp->sample_topk : 0);
     if (method == SAT_SAMPLE_ANCESTRAL) {
         SAT_REQUIRE(K == 1, "beam_batched: ancestral sampling is defined for beamk == 1 (beamk %d): samples are rows of the batch", K);
         SAT_REQUIRE(!con, "beam_batched: ancestral sampling does not combine with constraints (topg / prefix / banned ids)");
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+        if (call && hipStreamIsCapturing(call->st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
         SAT_REQUIRE(cap == hipStreamCaptureStatusNone, "beam_batched: ancestral sampling is not replayed from a graph (the stream is being captured)");
     }
     SAT_REQUIRE(method != SAT_SAMPLE_NUCLEUS || (smp->sample_topp > 0.f && smp->sample_topp <= 1.f),
                 "beam_batched: sample_topp %g outside (0, 1] (nucleus sampling)", smp ? (double)smp->sample_topp : 0.0);
-    SAT_REQUIRE(ws_bytes >= w.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes, w.total, K, max_gen_length);
-    BeamMember mem = {&d, &p, ann, w, alpha_hist, (long)d.B * K * d.L};
-    return beam_search_loop(&mem, 1, nullptr, K, G, lambda, max_gen_length, temps_host, n_temps, special_host, tok_in, prev_row, fin_count, fin_step, fin_row,
-                            fin_score, fin_mean, st, smp, con, hist_on ? hist : nullptr, req, req_met);
+    plan = {smp, con, hist_on ? hist : nullptr, req, G, lambda, con ? con->topg : 0, hist_stride, 0};
+    plan.total = beam_layout(d, K, nullptr, plan.topg, hist_stride, G).total;
+    const size_t ws_bytes = call ? call->ws_bytes : plan.total;
+    SAT_REQUIRE(ws_bytes >= plan.total && K >= 1 && max_gen_length >= 0 && s.n_temperatures >= 1, "beam_batched: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes,
+                plan.total, K, max_gen_length);
+    return SAT_OK;
+}
+static int decoder_beam_batched(const sat_beam_search_desc& s, const sat_beam_search_out& o, const BeamPlan& plan, char* ws, hipStream_t st) {
+    BeamMember mem = {s.d, s.w, s.ann, beam_layout(*s.d, s.beamk, ws, plan.topg, plan.hist_stride, plan.G), o.alpha_hist, (long)s.d->B * s.beamk * s.d->L};
+    return beam_search_loop(&mem, 1, nullptr, s, o, plan, st);
 }
 // sat_beam_required: well-formed for a search of K rows and max_gen_length steps?  (max_required 0 is "off" and asks nothing)
 int beam_required_check(const sat_beam_required* r, int K, int max_gen_length, const char* what) {
@@ -1265,24 +1284,28 @@ static EnsembleWs ensemble_layout(const sat_beam_ensemble& e, int K, int hist_st
 }
 size_t decoder_beam_ensemble_workspace_bytes(const sat_beam_ensemble& e, int K, int hist_stride) { return ensemble_layout(e, K, hist_stride).total; }
 
-// decoder_beam_batched ("beam" sampling; banned ids and the history rules) over M models: every member runs its own once-per-batch
-// block, step and state gather (the three helpers above) on the shared tokens; the members' logits are combined, and the score
-// kernels, the selection, beam_update and the history advance run ONCE, on the combined logits at temperature 1, in member 0's workspace.
-int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length, const float* temps_host, int n_temps, const int* special_host, int* tok_in,
-                          int* prev_row, float* alpha_hist, int* fin_count, int* fin_step, int* fin_row, float* fin_score, float* fin_mean, char* ws,
-                          size_t ws_bytes, hipStream_t st, const sat_beam_constraints* con, const sat_beam_history* hist) {
-    SAT_TRY(beam_ensemble_check(&e, "beam_ensemble"));
-    const int M = e.members;
-    const sat_decoder_dims& d0 = *e.dims[0];
+// The plan of an ensemble search ("beam" sampling; banned ids, min_length and no_repeat_ngram): what does not combine with an ensemble,
+// then the refusals of the features that do, in the single-model search's words.
+static int beam_plan_ensemble(const sat_beam_search_desc& s, const BeamCall* call, BeamPlan& plan) {
+    const sat_beam_ensemble& e = *s.ensemble;
+    const int K = s.beamk, max_gen_length = s.max_gen_length, V = e.dims[0]->V;
+    const sat_beam_constraints* con = s.constraints; const sat_beam_history* hist = s.history;
+    const int method = s.sampling ? s.sampling->method : 0, G = s.groups ? s.groups->groups : 0, C = s.required ? s.required->max_required : 0;
+    SAT_REQUIRE(!s.d && !s.w && !s.ann, "beam_ensemble: d / w / ann are set together with ensemble (all three are NULL with an ensemble)");
+    SAT_REQUIRE(method == SAT_SAMPLE_BEAM, "beam_ensemble: sampling method %d does not combine with an ensemble (\"beam\" only)", method);
+    SAT_REQUIRE(!s.sampling || s.sampling->decoder_noise == 0.f, "beam_ensemble: sampling decoder_noise %g does not combine with an ensemble",
+                s.sampling ? (double)s.sampling->decoder_noise : 0.0);
+    SAT_REQUIRE(G <= 1, "beam_ensemble: groups %d do not combine with an ensemble (0 or 1 = off)", G);
+    SAT_REQUIRE(C <= 0, "beam_ensemble: required words (max_required %d) do not combine with an ensemble", C);
     SAT_REQUIRE(!con || con->topg == 0, "beam_ensemble: topg %d does not combine with an ensemble", con ? con->topg : 0);
     SAT_REQUIRE(!con || con->max_prefix == 0, "beam_ensemble: a forced prefix (max_prefix %d) does not combine with an ensemble", con ? con->max_prefix : 0);
     SAT_REQUIRE(!hist || hist->repetition_penalty == 0.f || hist->repetition_penalty == 1.0f,
                 "beam_ensemble: repetition_penalty %g does not combine with an ensemble (0 or 1 = off)", hist ? (double)hist->repetition_penalty : 0.0);
-    SAT_TRY(not_capturing(st, "beam_ensemble"));
+    if (call) SAT_TRY(not_capturing(call->st, "beam_ensemble"));
     if (con && con->n_banned == 0) con = nullptr;
     SAT_TRY(beam_history_check(hist, max_gen_length, "beam_history"));
     const bool hist_on = beam_history_on(hist);
-    const sat_beam_constraints no_constraint = {};
+    static const sat_beam_constraints no_constraint = {};
     if (hist_on) {
         SAT_REQUIRE(max_gen_length + 1 <= SAT_BEAM_HIST_MAX, "beam_history: max_gen_length %d is over the limit (max_gen_length + 1 <= %d)", max_gen_length,
                     SAT_BEAM_HIST_MAX);
@@ -1290,24 +1313,52 @@ int decoder_beam_ensemble(const sat_beam_ensemble& e, int K, int max_gen_length,
     }
     if (con) {
         SAT_REQUIRE(K <= 1024, "beam_constrained: beamk %d above 1024 (one thread per row in the forced steps)", K);
-        SAT_REQUIRE(con->n_banned >= 0 && con->n_banned <= d0.V && (con->n_banned == 0 || con->banned), "beam_constrained: n_banned %d outside 0..V=%d, or null banned",
-                    con->n_banned, d0.V);
+        SAT_REQUIRE(con->n_banned >= 0 && con->n_banned <= V && (con->n_banned == 0 || con->banned), "beam_constrained: n_banned %d outside 0..V=%d, or null banned",
+                    con->n_banned, V);
     }
-    const int hist_stride = hist_on ? max_gen_length + 1 : 0;
-    const EnsembleWs lay = ensemble_layout(e, K, hist_stride);
-    SAT_REQUIRE(ws_bytes >= lay.total && K >= 1 && max_gen_length >= 0 && n_temps >= 1, "beam_ensemble: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes,
-                lay.total, K, max_gen_length);
+    plan = {nullptr, con, hist_on ? hist : nullptr, nullptr, 1, 0.f, 0, hist_on ? max_gen_length + 1 : 0, 0};
+    plan.total = ensemble_layout(e, K, plan.hist_stride).total;
+    const size_t ws_bytes = call ? call->ws_bytes : plan.total;
+    SAT_REQUIRE(ws_bytes >= plan.total && K >= 1 && max_gen_length >= 0 && s.n_temperatures >= 1, "beam_ensemble: workspace %zu < %zu, K=%d, max_gen_length=%d", ws_bytes,
+                plan.total, K, max_gen_length);
+    return SAT_OK;
+}
+// decoder_beam_batched over M models: every member runs its own once-per-batch block, step and state gather (the three helpers above)
+// on the shared tokens; the members' logits are combined, and the score kernels, the selection, beam_update and the history advance
+// run ONCE, on the combined logits at temperature 1, in member 0's workspace.
+static int decoder_beam_ensemble(const sat_beam_search_desc& s, const sat_beam_search_out& o, const BeamPlan& plan, char* ws, hipStream_t st) {
+    const sat_beam_ensemble& e = *s.ensemble;
+    const int M = e.members, K = s.beamk;
+    const sat_decoder_dims& d0 = *e.dims[0];
+    const EnsembleWs lay = ensemble_layout(e, K, plan.hist_stride);
     const size_t N = (size_t)d0.B * K;
     BeamMember mem[SAT_ENSEMBLE_MAX];
     const float* zs[SAT_ENSEMBLE_MAX];
     for (int i = 0; i < M; ++i) {              // alpha_hist is member 0's; the other members' maps (their L differ) are one step's scratch
-        mem[i] = {e.dims[i], e.params[i], e.ann[i], beam_layout(*e.dims[i], K, ws + lay.member[i], 0, i == 0 ? hist_stride : 0),
-                  i == 0 ? alpha_hist : reinterpret_cast<float*>(ws + lay.alpha[i]), i == 0 ? (long)N * d0.L : 0L};
+        mem[i] = {e.dims[i], e.params[i], e.ann[i], beam_layout(*e.dims[i], K, ws + lay.member[i], 0, i == 0 ? plan.hist_stride : 0),
+                  i == 0 ? o.alpha_hist : reinterpret_cast<float*>(ws + lay.alpha[i]), i == 0 ? (long)N * d0.L : 0L};
         zs[i] = mem[i].w.logits;
     }
     const BeamCombine comb = {ensemble_args(zs, e.weight, M), e.combine == SAT_ENSEMBLE_GEOMETRIC ? 1 : 0, reinterpret_cast<float*>(ws + lay.combined)};
-    return beam_search_loop(mem, M, &comb, K, 1, 0.f, max_gen_length, temps_host, n_temps, special_host, tok_in, prev_row, fin_count, fin_step, fin_row, fin_score,
-                            fin_mean, st, nullptr, con, hist_on ? hist : nullptr);
+    return beam_search_loop(mem, M, &comb, s, o, plan, st);
+}
+
+// One plan for the workspace query and the search (include/sat_hip.h, sat_beam_search_desc): the query is the figure the search
+// compares its workspace against, and refuses what the search refuses.
+static int beam_plan(const sat_beam_search_desc& s, const BeamCall* call, BeamPlan& plan) {
+    return s.ensemble ? beam_plan_ensemble(s, call, plan) : beam_plan_single(s, call, plan);
+}
+int beam_search_workspace_bytes(const sat_beam_search_desc& s, size_t& total) {
+    BeamPlan plan;
+    SAT_TRY(beam_plan(s, nullptr, plan));
+    total = plan.total;
+    return SAT_OK;
+}
+int beam_search(const sat_beam_search_desc& s, const sat_beam_search_out& o, char* ws, size_t ws_bytes, hipStream_t st) {
+    BeamPlan plan;
+    const BeamCall call = {&o, ws_bytes, st};
+    SAT_TRY(beam_plan(s, &call, plan));
+    return s.ensemble ? decoder_beam_ensemble(s, o, plan, ws, st) : decoder_beam_batched(s, o, plan, ws, st);
 }
 
 int beam_history_scores(const float* logits, int rows, int V, float temperature, const int* masked, int n_masked, const float* parent, const int* hist,

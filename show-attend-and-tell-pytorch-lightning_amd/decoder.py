@@ -127,6 +127,44 @@ def layers_of(n_params):
     return 1 + extra // len(L.UP_FIELDS)
 
 
+def search_desc(stoi, beamk, max_gen_length, temperature, dev, con=None, hist=None, grp=None, req=None, smp=None):
+    """The model-independent half of a ``sat_beam_search_desc``: sizes, the HOST temperature and special-id arrays, the checked options of
+    ``constraints.SearchOptions.resolve`` as their structs and a ``BeamSampling``.  The caller adds ``d`` / ``w`` / ``ann`` or ``ensemble``;
+    what the descriptor points into lives as long as it does (``_keep``)."""
+    temps = temperature if isinstance(temperature, list) else [temperature]
+    tarr = (C.c_float * len(temps))(*[float(t) for t in temps])
+    ids = (C.c_int32 * 4)(*[int(stoi[s]) for s in ("<START>", "<PAD>", "<END>", "<UNK>")])
+    desc = L.BeamSearchDesc(beamk=int(beamk), max_gen_length=int(max_gen_length), temperatures_host=tarr, n_temperatures=len(temps), special_ids_host=ids)
+    parts = dict(sampling=smp, constraints=con and con.device_struct(dev), history=hist and hist.device_struct(), groups=grp and grp.device_struct(),
+                 required=req and req.device_struct(dev))           # a struct, or (struct, the tensors it points into)
+    desc._keep = [tarr, ids, parts]
+    for field, st in parts.items():
+        if st is not None:
+            setattr(desc, field, C.pointer(st[0] if isinstance(st, tuple) else st))
+    return desc
+
+
+def beam_search(desc, B, Lc, dev, o=None):
+    """``sat_beam_search`` over ``B`` images with ``Lc`` attention locations: allocates the output buffers (``_lib.SEARCH_OUTPUTS``; "req_met"
+    with required words only) and the workspace ``sat_beam_search_desc_workspace_bytes`` asks for, enqueues, returns the dict.  ``o``: the
+    dict of an earlier call, to enqueue into the same buffers again (graph capture).  A refused descriptor raises the library's message."""
+    lib = L.lib()
+    if o is None:
+        ws_bytes = lib.sat_beam_search_desc_workspace_bytes(C.byref(desc))
+        if ws_bytes == 0:
+            L.check(1, "sat_beam_search_desc_workspace_bytes")
+        K, S = desc.beamk, desc.max_gen_length
+        i32 = dict(dtype=torch.int32, device=dev); f32 = dict(dtype=torch.float32, device=dev)
+        o = dict(ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev), tok_in=torch.empty(S + 2, B, K, **i32), prev_row=torch.empty(S + 2, B, K, **i32),
+                 alpha_hist=torch.empty(S + 1, B, K, Lc, **f32), fin_count=torch.empty(B, **i32), fin_step=torch.empty(B, K, **i32),
+                 fin_row=torch.empty(B, K, **i32), fin_score=torch.empty(B, K, **f32), fin_mean=torch.empty(B, K, **f32))
+        if desc.required:
+            o["req_met"] = torch.empty(B, **i32)
+    out = L.BeamSearchOut(*[L.ptr(o.get(k)) for k in L.SEARCH_OUTPUTS])
+    L.check(lib.sat_beam_search(C.byref(desc), C.byref(out), L.ptr(o["ws"]), o["ws"].numel(), L.stream_ptr()), "sat_beam_search")
+    return o
+
+
 def _check_param(name, t, shape):
     if t is None:
         return

@@ -136,42 +136,35 @@ class Ensemble:
             raise ValueError("an ensemble runs in the batched search only (max_gen_length >= 1), not in the per-image loop beam_decode")
         V = self.embedding.weight.shape[0]
         if batch_size is not None:
-            constraints.resolve_all(self.hp.vocab_stoi, V, batch_size, a["beamk"], a["max_gen_length"], "beam", None, None, a.get("banned"), a.get("no_unk", False),
-                                    a.get("no_repeat_ngram"), a.get("min_length"), None)
+            constraints.SearchOptions.from_kwargs(a).resolve(self.hp.vocab_stoi, V, batch_size, a["beamk"], a["max_gen_length"])
         if "mbr_corpus" in a:
             corpus = a["mbr_corpus"] if a["mbr_corpus"] is not None else a.get("corpus")
             constraints.check_mbr(a.get("rescore_method"), corpus, a["mbr_reward"], a["mbr_alpha"], a["beamk"], V, a["max_gen_length"])
 
-    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                            beam_groups=None, diversity_penalty=0.5, required=None):
+    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None,
+                            normals=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None,
+                            min_length=None, repetition_penalty=None, beam_groups=None, diversity_penalty=0.5, required=None, options=None):
         """``SATDecoder._beam_search_device`` for the ensemble: ``ann_bld`` is the list of the members' annotations (B, L_i, D_i); the
         same dict of device buffers comes back (``alpha_hist`` holds member 0's maps).  Launches only."""
-        check_decode_args(sample_method, topg, prefix, repetition_penalty, beam_groups, decoder_noise, graph, required)
+        opt = options if options is not None else constraints.SearchOptions.from_kwargs(locals())
+        check_decode_args(**opt.kwargs(check_decode_args))
         one = self._single()
         if one is not None:
             ann = ann_bld[0] if isinstance(ann_bld, (list, tuple)) else ann_bld
-            return one._beam_search_device(ann, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                                           topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length, repetition_penalty, beam_groups,
-                                           diversity_penalty)
+            return one._beam_search_device(ann, beamk, max_gen_length, temperature, options=opt)
         anns = [a.contiguous() for a in ann_bld]
         if len(anns) != len(self.models):
             raise ValueError("%d annotation tensors for %d members" % (len(anns), len(self.models)))
         B = anns[0].shape[0]
         if any(a.dim() != 3 or a.shape[0] != B for a in anns):
             raise ValueError("every member's annotations are (B, L_i, D_i) of the same B images")
-        hp = self.hp
         V = self.embedding.weight.shape[0]
         K, S = int(beamk), int(max_gen_length)
-        con, hist = constraints.resolve_all(hp.vocab_stoi, V, B, K, S, "beam", None, None, banned, no_unk, no_repeat_ngram, min_length, None)
-        lib = L.lib()
+        con, hist, _, _ = opt.resolve(self.hp.vocab_stoi, V, B, K, S)
         L.require_gpu(*anns)
         dev = anns[0].device
-        temps = temperature if isinstance(temperature, list) else [temperature]
-        tarr = (C.c_float * len(temps))(*[float(t) for t in temps])
-        ids = (C.c_int32 * 4)(*[int(hp.vocab_stoi[s]) for s in constraints.SPECIALS])
         ens = L.BeamEnsemble(members=len(self.models), combine=L.ENSEMBLE_COMBINE[self.combine])
-        keep = []
+        keep = [ens]
         for i, (m, ann, wt) in enumerate(zip(self.models, anns, self.weights)):
             _, Lc, D = ann.shape
             dims = Dk.decoder_dims(B, K, 2, Lc, D, m.attention.decoder_att.weight.shape[0], m.embedding.weight.shape[1], m.lstm.weight_hh_l0.shape[1], V, 0,
@@ -179,24 +172,10 @@ class Ensemble:
             w, tens = m._params_struct()
             keep += [dims, w, tens]
             ens.dims[i], ens.params[i], ens.ann[i], ens.weight[i] = C.pointer(dims), C.pointer(w), ann.data_ptr(), wt
-        cst = hst = None
-        if con is not None:
-            cst, keep_con = con.device_struct(dev)
-            keep.append(keep_con)
-        if hist is not None:
-            hst = hist.device_struct()
-        ws_bytes = lib.sat_beam_search_ensemble_workspace_bytes(C.byref(ens), K, S)
-        if ws_bytes == 0:
-            L.check(1, "sat_beam_search_ensemble_workspace_bytes")
-        i32 = dict(dtype=torch.int32, device=dev); f32 = dict(dtype=torch.float32, device=dev)
-        o = dict(ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev), tok_in=torch.empty(S + 2, B, K, **i32), prev_row=torch.empty(S + 2, B, K, **i32),
-                 alpha_hist=torch.empty(S + 1, B, K, anns[0].shape[1], **f32), fin_count=torch.empty(B, **i32), fin_step=torch.empty(B, K, **i32),
-                 fin_row=torch.empty(B, K, **i32), fin_score=torch.empty(B, K, **f32), fin_mean=torch.empty(B, K, **f32))
-        L.check(lib.sat_beam_search_ensemble(C.byref(ens), K, S, tarr, len(temps), ids, C.byref(cst) if cst is not None else None,
-                                             C.byref(hst) if hst is not None else None, L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]),
-                                             L.ptr(o["fin_count"]), L.ptr(o["fin_step"]), L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]),
-                                             L.ptr(o["ws"]), ws_bytes, L.stream_ptr()), "sat_beam_search_ensemble")
-        return o
+        desc = Dk.search_desc(self.hp.vocab_stoi, K, S, temperature, dev, con, hist)
+        desc.ensemble = C.pointer(ens)
+        desc._keep += keep
+        return Dk.beam_search(desc, B, anns[0].shape[1], dev)
 
     def beam_decode_batched(self, ann_bld, hw, *args, **kw):
         """``SATDecoder.beam_decode_batched`` (same arguments, same four lists) on the list of the members' annotations"""

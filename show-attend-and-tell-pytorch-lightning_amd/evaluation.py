@@ -123,21 +123,15 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     ("Consensus reranking"); ``scores`` is then the utility.  ``beam_groups`` / ``diversity_penalty``: the diverse beam
     search ("Diverse beam search"); ``required``: the words every caption must contain ("Required words").
     Launches only, like the rest."""
+    opt = constraints.SearchOptions.from_kwargs(locals())
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
     mbr_corpus = corpus if mbr_corpus is None else mbr_corpus
     constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, model.hp.vocab_size, max_gen_length)      # refuse before any launch
-    con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
-               repetition_penalty=repetition_penalty)
-    constraints.check_ancestral(str(sample_method), beamk, graph, **con)
-    constraints.resolve_all(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length, str(sample_method), **con)   # refuse before any launch
-    constraints.resolve_groups(beamk, beam_groups, diversity_penalty, str(sample_method), decoder_noise, topg, prefix, graph, V=model.hp.vocab_size)
-    constraints.resolve_required(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length, required, str(sample_method), decoder_noise,
-                                 topg, prefix, banned, no_unk, beam_groups, graph)
+    opt.resolve(model.hp.vocab_stoi, model.hp.vocab_size, img.shape[0], beamk, max_gen_length)                                   # refuse before any launch
     model.eval()
     ann_bld, _ = model.encode(img)
-    o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
-                                  graph, sample_topp=sample_topp, beam_groups=beam_groups, diversity_penalty=diversity_penalty, required=required, **con)
+    o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, options=opt)
     sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha)
     ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
     return sel["tokens"], sel["lengths"], sel["scores"], ppl
@@ -403,11 +397,12 @@ def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, s
     ``repetition_penalty`` are its history rules (``SATDecoder.beam_decode_batched``).  ``rescore_method="MBR"`` reranks by consensus
     against ``mbr_corpus`` (``corpus`` when that is None) with ``mbr_reward`` / ``mbr_alpha``.  ``beam_groups`` / ``diversity_penalty``: the
     diverse beam search; ``required``: the words every caption must contain."""
+    opt = constraints.SearchOptions.from_kwargs(locals())
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
-    tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                                          rescore_method, rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram,
-                                          min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus, beam_groups, diversity_penalty, required)
+    tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk=beamk, max_gen_length=max_gen_length, temperature=temperature, rescore_method=rescore_method,
+                                          rescore_reward=rescore_reward, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, corpus=corpus,
+                                          **opt.kwargs(caption_tokens))
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())

@@ -58,12 +58,12 @@ class LabelSmoothing(nn.Module):
 SAMPLE_METHODS = tuple(L.SAMPLE_METHODS)
 
 
-def check_sample_topp(sample_method, sample_topp):
-    """``sample_topp`` of "nucleus" sampling is a finite share in (0, 1] (include/sat_hip.h refuses the same values)"""
-    if sample_method == "nucleus" and not (0.0 < float(sample_topp) <= 1.0):
-        raise ValueError("sample_topp %r outside (0, 1] (sample_method='nucleus')" % (sample_topp,))
+def _named(kw):
+    """a method's own arguments (its ``locals()`` on entry) by name, for the function that takes the same keywords"""
+    return {k: v for k, v in kw.items() if k != "self"}
 
 
+check_sample_topp = constraints.check_sample_topp
 check_ancestral = constraints.check_ancestral
 
 
@@ -179,17 +179,13 @@ class SATDecoder(nn.Module):
         ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``: the history rules ("History rules") with torch ops
         on ``top_preds`` and the logits; the implementation ``beam_decode_batched``'s kernels are tested against."""
         import ctypes as C
-        assert sample_method in SAMPLE_METHODS
-        check_sample_topp(sample_method, sample_topp)
         if rescore_method == "MBR":
             raise ValueError("rescore_method='MBR' (consensus reranking) runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         if sample_method == "ancestral":
             raise ValueError("sample_method='ancestral' runs in the batched search only (beam_decode_batched, max_gen_length >= 1)")
         multinomial = multinomial or torch.multinomial
-        constraints.resolve_groups(beamk, beam_groups, diversity_penalty, batched=False)     # the groups run in the batched search only
-        constraints.resolve_required(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, required, batched=False)
-        con, hist = constraints.resolve_all(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
-                                            topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
+        con, hist, _, _ = constraints.SearchOptions.from_kwargs(locals()).resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk,
+                                                                                  max_gen_length, batched=False)      # groups and required words: batched only
         lib = L.lib()
         L.require_gpu(ann_bld)
         hp = self.hp
@@ -349,33 +345,24 @@ class SATDecoder(nn.Module):
                 cap_scores.append(fin_scores[best]); cap_ppl.append(fin_ppl[best])
         return captions, cap_scores, cap_alphas, cap_ppl
 
-    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                            topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-                            beam_groups=None, diversity_penalty=0.5, required=None):
+    def _beam_search_device(self, ann_bld, beamk, max_gen_length, temperature, sample_method="beam", sample_topk=3, decoder_noise=None, seed=None, gumbel=None,
+                            normals=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None,
+                            min_length=None, repetition_penalty=None, beam_groups=None, diversity_penalty=0.5, required=None, options=None):
         """The device half of ``beam_decode_batched``: enqueue the whole search for annotations (B, L, D) (eagerly, or as the replay of
         its cached hipGraph) and return the buffers it leaves on the device (tok_in, prev_row, alpha_hist, fin_*: include/sat_hip.h,
         sat_beam_search_batched).  No device-to-host copy and no synchronisation (the first call of a shape with ``graph=True`` excepted).
-        With a constraint (``topg`` / ``prefix`` / ``banned`` / ``no_unk``) the call is sat_beam_search_constrained and runs eagerly.
+        ``options``: a ``constraints.SearchOptions`` in place of the option keywords; ``SearchOptions.resolve`` refuses what does not
+        combine, and the call is one ``sat_beam_search`` whatever the options.
         ``graph=True`` replays the "beam" search without noise, and the "nucleus" search drawn by the device generator from a
-        given ``seed`` (the seed and ``sample_topp`` are arguments of the captured launches, so both are part of the cache key).
-        ``sample_method="ancestral"`` (``beamk == 1``, no constraint, no graph: ``check_ancestral``) draws every word, the first included,
-        from the model's own distribution; ``gumbel`` is then (max_gen_length + 1, B, V).
-        With a history rule on (``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty``) the call is sat_beam_search_history, eager too.
-        ``beam_groups`` > 1 ("Diverse beam search"): sat_beam_search_groups, eager; ``constraints.resolve_groups`` refuses
-        what does not combine with it.  ``required`` ("Required words"): sat_beam_search_required, eager; the buffers gain
-        "req_met" (B), the most required words a finished hypothesis of the image contains (no such key without required words), and the
-        fin_* lists hold the hypotheses that reach it."""
+        given ``seed`` (the seed and ``sample_topp`` are arguments of the captured launches, so both are part of the cache key); a
+        constraint, a history rule, groups or required words run eagerly.
+        ``sample_method="ancestral"`` (``beamk == 1``, no constraint, no graph) draws every word, the first included, from the model's
+        own distribution; ``gumbel`` is then (max_gen_length + 1, B, V).
+        With ``required`` ("Required words") the buffers gain "req_met" (B), the most required words a finished hypothesis
+        of the image contains (no such key without required words), and the fin_* lists hold the hypotheses that reach it."""
         import ctypes as C
-        assert sample_method in SAMPLE_METHODS
-        check_sample_topp(sample_method, sample_topp)
-        check_ancestral(sample_method, beamk, graph, topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
-        con, hist = constraints.resolve_all(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, sample_method,
-                                            topg, prefix, banned, no_unk, no_repeat_ngram, min_length, repetition_penalty)
-        grp = constraints.resolve_groups(beamk, beam_groups, diversity_penalty, sample_method, decoder_noise, topg, prefix, graph,
-                                         V=self.embedding.weight.shape[0])
-        req = constraints.resolve_required(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length, required,
-                                           sample_method, decoder_noise, topg, prefix, banned, no_unk, beam_groups, graph)
-        lib = L.lib()
+        opt = options if options is not None else constraints.SearchOptions.from_kwargs(locals())
+        con, hist, grp, req = opt.resolve(self.hp.vocab_stoi, self.embedding.weight.shape[0], ann_bld.shape[0], beamk, max_gen_length)
         L.require_gpu(ann_bld)
         hp = self.hp
         dev = ann_bld.device
@@ -385,97 +372,41 @@ class SATDecoder(nn.Module):
         n = self.lstm.weight_hh_l0.shape[1]
         A = self.attention.decoder_att.weight.shape[0]
         K, S = int(beamk), int(max_gen_length)
-        temps = temperature if isinstance(temperature, list) else [temperature]
-        tarr = (C.c_float * len(temps))(*[float(t) for t in temps])
-        ids = (C.c_int32 * 4)(int(hp.vocab_stoi["<START>"]), int(hp.vocab_stoi["<PAD>"]), int(hp.vocab_stoi["<END>"]), int(hp.vocab_stoi["<UNK>"]))
         dims = Dk.decoder_dims(B, K, 2, Lc, D, A, m, n, V, 0, hp.deep_output, self.pad_idx, int(getattr(self, "sat_precision", "fp32") == "bf16"),
                                layers=int(hp.decoder_layers))
         w, _keep = self._params_struct()
-        ws_bytes = lib.sat_beam_search_workspace_bytes(C.byref(dims), K)
-        i32 = dict(dtype=torch.int32, device=dev); f32 = dict(dtype=torch.float32, device=dev)
-        cst = None
-        if con is not None:
-            cst, _keep_con = con.device_struct(dev)
-            ws_bytes = lib.sat_beam_search_constrained_workspace_bytes(C.byref(dims), K, con.topg)
-        hst = None
-        if hist is not None:
-            hst = hist.device_struct()
-            ws_bytes = lib.sat_beam_search_history_workspace_bytes(C.byref(dims), K, con.topg if con is not None else 0, S)
-        gst = None
-        if grp is not None:
-            gst = grp.device_struct()
-            ws_bytes = lib.sat_beam_search_groups_workspace_bytes(C.byref(dims), K, grp.groups, S)
-        rst = None
-        if req is not None:
-            rst, _keep_req = req.device_struct(dev)
-            ws_bytes = lib.sat_beam_search_required_workspace_bytes(C.byref(dims), K, S, req.max_required)
         smp = None
+        seed, gumbel, normals = opt.seed, opt.gumbel, opt.normals
         seeded = seed is not None
-        if sample_method != "beam" or decoder_noise:
+        if opt.sample_method != "beam" or opt.decoder_noise:
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)))
             for t in (gumbel, normals):
                 if t is not None:
                     L.require_gpu(t)
                     assert t.dtype == torch.float32 and t.is_contiguous()
-            smp = L.BeamSampling(method=L.SAMPLE_METHODS[sample_method], sample_topk=int(sample_topk), seed=int(seed),
-                                 gumbel=(gumbel.data_ptr() if gumbel is not None else None), decoder_noise=float(decoder_noise or 0.0),
-                                 sample_topp=(float(sample_topp) if sample_method == "nucleus" else 0.0),
+            smp = L.BeamSampling(method=L.SAMPLE_METHODS[opt.sample_method], sample_topk=int(opt.sample_topk), seed=int(seed),
+                                 gumbel=(gumbel.data_ptr() if gumbel is not None else None), decoder_noise=float(opt.decoder_noise or 0.0),
+                                 sample_topp=(float(opt.sample_topp) if opt.sample_method == "nucleus" else 0.0),
                                  normals=(normals.data_ptr() if normals is not None else None))
+        desc = Dk.search_desc(hp.vocab_stoi, K, S, temperature, dev, con, hist, grp, req, smp)
+        desc.d, desc.w = C.pointer(dims), C.pointer(w)
 
-        def buffers():
-            o = dict(ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev), tok_in=torch.empty(S + 2, B, K, **i32),
-                        prev_row=torch.empty(S + 2, B, K, **i32), alpha_hist=torch.empty(S + 1, B, K, Lc, **f32), fin_count=torch.empty(B, **i32),
-                        fin_step=torch.empty(B, K, **i32), fin_row=torch.empty(B, K, **i32), fin_score=torch.empty(B, K, **f32),
-                        fin_mean=torch.empty(B, K, **f32))
-            if rst is not None:
-                o["req_met"] = torch.empty(B, **i32)
-            return o
+        def enqueue(ann, o=None):
+            desc.ann = ann.data_ptr()
+            return Dk.beam_search(desc, B, Lc, dev, o)
 
-        def enqueue(ann, o):
-            if rst is not None:
-                L.check(lib.sat_beam_search_required(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
-                                                     C.byref(cst) if cst is not None else None, C.byref(hst) if hst is not None else None, C.byref(rst),
-                                                     L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]),
-                                                     L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["req_met"]), L.ptr(o["ws"]),
-                                                     ws_bytes, L.stream_ptr()), "sat_beam_search_required")
-                return
-            if gst is not None:
-                L.check(lib.sat_beam_search_groups(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
-                                                   C.byref(cst) if cst is not None else None, C.byref(hst) if hst is not None else None, C.byref(gst),
-                                                   L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]),
-                                                   L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]), ws_bytes, L.stream_ptr()),
-                        "sat_beam_search_groups")
-                return
-            if hst is not None:
-                L.check(lib.sat_beam_search_history(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
-                                                    C.byref(cst) if cst is not None else None, C.byref(hst), L.ptr(o["tok_in"]), L.ptr(o["prev_row"]),
-                                                    L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]), L.ptr(o["fin_row"]),
-                                                    L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]), ws_bytes, L.stream_ptr()),
-                        "sat_beam_search_history")
-                return
-            if cst is not None:
-                L.check(lib.sat_beam_search_constrained(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
-                                                        C.byref(cst), L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]),
-                                                        L.ptr(o["fin_step"]), L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]),
-                                                        ws_bytes, L.stream_ptr()), "sat_beam_search_constrained")
-                return
-            L.check(lib.sat_beam_search_sampled(C.byref(dims), C.byref(w), L.ptr(ann), K, S, tarr, len(temps), ids, C.byref(smp) if smp is not None else None,
-                                                L.ptr(o["tok_in"]), L.ptr(o["prev_row"]), L.ptr(o["alpha_hist"]), L.ptr(o["fin_count"]), L.ptr(o["fin_step"]),
-                                                L.ptr(o["fin_row"]), L.ptr(o["fin_score"]), L.ptr(o["fin_mean"]), L.ptr(o["ws"]), ws_bytes, L.stream_ptr()),
-                    "sat_beam_search_sampled")
-
-        replayable = smp is None or (sample_method == "nucleus" and seeded and gumbel is None and normals is None)
-        if graph and replayable and cst is None and hst is None and gst is None and rst is None:
+        replayable = smp is None or (opt.sample_method == "nucleus" and seeded and gumbel is None and normals is None)
+        if opt.graph and replayable and con is None and hist is None and grp is None and req is None:
             cache = self.__dict__.setdefault("_beam_graphs", {})
+            temps = temperature if isinstance(temperature, list) else [temperature]
             key = (B, Lc, D, K, S, tuple(float(t) for t in temps), int(dims.precision), str(dev), tuple(t.data_ptr() for t in _keep.values() if torch.is_tensor(t)))
             if smp is not None:
                 key += ("nucleus", float(smp.sample_topp), int(smp.seed), float(smp.decoder_noise))
             ent = cache.get(key)
             if ent is None:
-                o = buffers()
                 ann_s = ann_bld.clone()
-                enqueue(ann_s, o)                       # eager once: validates the arguments and sets the kernel attributes before the capture
+                o = enqueue(ann_s)                      # eager once: validates the arguments and sets the kernel attributes before the capture
                 torch.cuda.synchronize(dev)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
@@ -487,8 +418,7 @@ class SATDecoder(nn.Module):
             ann_s.copy_(ann_bld)
             g.replay()
         else:
-            o = buffers()
-            enqueue(ann_bld, o)
+            o = enqueue(ann_bld)
         return o
 
     @torch.no_grad()
@@ -538,9 +468,7 @@ class SATDecoder(nn.Module):
         (``constraints.resolve_required``).  ``None`` or empty: today's search."""
         import numpy as np
         mbr = constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, self.embedding.weight.shape[0], max_gen_length)
-        o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, seed, gumbel, normals, graph,
-                                     topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length, repetition_penalty, beam_groups, diversity_penalty,
-                                     required)
+        o = self._beam_search_device(ann_bld, beamk, max_gen_length, temperature, options=constraints.SearchOptions.from_kwargs(locals()))
         B = ann_bld.shape[0]
         Hh, Ww = hw
         K, S = int(beamk), int(max_gen_length)
@@ -713,37 +641,28 @@ class SAT(SATDecoder, _Base):
         rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` and ``rescore_method="MBR"`` with ``mbr_corpus`` /
         ``mbr_reward`` / ``mbr_alpha``, and the diverse beam search ``beam_groups`` / ``diversity_penalty``: ``beam_decode_batched``."""
         self.eval()
-        return self.forward(img_tensor, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                            rescore_method, rescore_reward, return_all, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
-                            repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty, required)
+        opt = constraints.SearchOptions.from_kwargs(locals())
+        return self.forward(img_tensor, beamk=beamk, max_gen_length=max_gen_length, temperature=temperature, rescore_method=rescore_method,
+                            rescore_reward=rescore_reward, return_all=return_all, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha,
+                            **opt.kwargs(SAT.forward))
 
     def forward(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                 rescore_method=None, rescore_reward=0.5, return_all=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
                 mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """Inference only (model.py:237-472): encode the batch once, then beam-search every image."""
-        assert sample_method in SAMPLE_METHODS
-        check_sample_topp(sample_method, sample_topp)
-        con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
-                   repetition_penalty=repetition_penalty)
-        check_ancestral(sample_method, beamk, bool(self.__dict__.get("beam_graph", False)), **con)
+        opt = constraints.SearchOptions.from_kwargs(locals(), graph=bool(self.__dict__.get("beam_graph", False)))      # model.beam_graph = True: hipGraph replay
+        opt.resolve(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, batched=max_gen_length >= 1)        # refuse before any launch
         if sample_method == "ancestral" and max_gen_length < 1:
             raise ValueError("sample_method='ancestral' runs in the batched search only (max_gen_length >= 1)")
-        constraints.resolve_all(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, sample_method, **con)     # refuse before any launch
         constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, self.hp.vocab_size, max_gen_length)
-        constraints.resolve_groups(beamk, beam_groups, diversity_penalty, sample_method, decoder_noise, topg, prefix, bool(self.__dict__.get("beam_graph", False)),
-                                   batched=max_gen_length >= 1, V=self.hp.vocab_size)
-        constraints.resolve_required(self.hp.vocab_stoi, self.hp.vocab_size, img.shape[0], beamk, max_gen_length, required, sample_method, decoder_noise, topg,
-                                     prefix, banned, no_unk, beam_groups, bool(self.__dict__.get("beam_graph", False)), batched=max_gen_length >= 1)
         with torch.no_grad():
             ann_bld, hw = self.encode(img)
             if max_gen_length >= 1:        # every image at once; sampled continuations and decoder noise draw from the device generator
-                return self.beam_decode_batched(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, rescore_method, rescore_reward, return_all,
-                                                sample_method=sample_method, sample_topk=sample_topk, decoder_noise=decoder_noise,
-                                                graph=bool(self.__dict__.get("beam_graph", False)), sample_topp=sample_topp, mbr_corpus=mbr_corpus,
-                                                mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, beam_groups=beam_groups, diversity_penalty=diversity_penalty,
-                                                required=required, **con)  # model.beam_graph = True: hipGraph replay
-            return self.beam_decode(ann_bld.contiguous(), hw, beamk, max_gen_length, temperature, sample_method, sample_topk,
-                                    decoder_noise, rescore_method, rescore_reward, return_all, sample_topp=sample_topp, **con)
+                return self.beam_decode_batched(ann_bld.contiguous(), hw, beamk=beamk, max_gen_length=max_gen_length, temperature=temperature,
+                                                rescore_method=rescore_method, rescore_reward=rescore_reward, return_all=return_all, mbr_corpus=mbr_corpus,
+                                                mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, **opt.kwargs(SATDecoder.beam_decode_batched))
+            return self.beam_decode(ann_bld.contiguous(), hw, beamk=beamk, max_gen_length=max_gen_length, temperature=temperature, rescore_method=rescore_method,
+                                    rescore_reward=rescore_reward, return_all=return_all, **opt.kwargs(SATDecoder.beam_decode))
 
     def train_batch(self, batch, epsilon=0, draw=None, teacher=None):
         img, encoded_captions, lengths = batch
@@ -925,22 +844,18 @@ class SAT(SATDecoder, _Base):
                   rescore_method=None, rescore_reward=0.5, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
                   beam_groups=None, diversity_penalty=0.5, required=None):
         """model.py:684-691"""
-        img, encoded_captions, lengths = batch
-        captions, scores, alphas, perplexities = self.caption(img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise,
-                                                              rescore_method, rescore_reward, return_all=False, topg=topg, prefix=prefix, banned=banned,
-                                                              no_unk=no_unk, sample_topp=sample_topp, no_repeat_ngram=no_repeat_ngram,
-                                                              min_length=min_length, repetition_penalty=repetition_penalty, beam_groups=beam_groups,
-                                                              diversity_penalty=diversity_penalty, required=required)
+        kw = _named(locals())
+        img, encoded_captions, lengths = kw.pop("batch")
+        captions, scores, alphas, perplexities = self.caption(img, return_all=False, **kw)
         return self.score_captions(captions, encoded_captions, lengths, perplexities)
 
     def caption_tokens(self, img, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                        rescore_method=None, rescore_reward=0.5, seed=None, graph=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
                        mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, corpus=None, beam_groups=None, diversity_penalty=0.5, required=None):
         """``caption(..., return_all=False)`` left on the device: (tokens, lengths, scores, perplexities), no host round trip (evaluation.py)"""
+        kw = _named(locals())
         from . import evaluation
-        return evaluation.caption_tokens(self, img, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                         rescore_reward, seed, graph, topg, prefix, banned, no_unk, sample_topp, no_repeat_ngram, min_length,
-                                         repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, corpus, beam_groups, diversity_penalty, required)
+        return evaluation.caption_tokens(self, **kw)
 
     def val_batch_stats(self, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                         rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
@@ -948,11 +863,9 @@ class SAT(SATDecoder, _Base):
                         mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """``val_batch`` as an ``evaluation.CaptionStats``: the batch is scored on the device; ``.metrics()`` gives ``val_batch``'s dict
         (with ``corpus``, an ``evaluation.ReferenceCorpus``, also CIDEr-D and ROUGE-L; with ``chrf``, an ``evaluation.VocabChars``, also chrF)"""
+        kw = _named(locals())
         from . import evaluation
-        return evaluation.val_batch_stats(self, batch, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                          rescore_reward, seed, graph, corpus, topg, prefix, banned, no_unk, sample_topp, chrf, chrf_beta,
-                                          no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty,
-                                          required)
+        return evaluation.val_batch_stats(self, **kw)
 
     def visualize(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                   rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, topg=None, prefix=None, banned=None, no_unk=False,
@@ -961,11 +874,10 @@ class SAT(SATDecoder, _Base):
         """visualize.ipynb's ``make_visual`` for a batch of picture files / bytes / arrays: load_square -> prepare_image -> search -> the
         attention overlays of every winning caption, rendered on the device.  Returns a ``visualize.Visual`` (visualize.py).
         ``progressive=True`` among ``render``: progressive JPEG files are decoded on the GPU too"""
+        kw = _named(locals())
+        render = kw.pop("render")
         from . import visualize
-        return visualize.visualize(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                   rescore_reward, visual_size, input_size, topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, sample_topp=sample_topp,
-                                   no_repeat_ngram=no_repeat_ngram, min_length=min_length, repetition_penalty=repetition_penalty, mbr_corpus=mbr_corpus,
-                                   mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, beam_groups=beam_groups, diversity_penalty=diversity_penalty, required=required, **render)
+        return visualize.visualize(self, **kw, **render)
 
     def caption_image(self, items, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3, decoder_noise=None,
                       rescore_method=None, rescore_reward=1.0, visual_size=256, input_size=None, seed=None, progressive=False,
@@ -973,11 +885,9 @@ class SAT(SATDecoder, _Base):
                       mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
         """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch: (captions, words, scores, perplexities).
         ``progressive``: progressive JPEG files are decoded on the GPU too (``jpeg.parse(progressive=True)``)"""
+        kw = _named(locals())
         from . import visualize
-        return visualize.caption_image(self, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, progressive, topg, prefix, banned, no_unk, sample_topp,
-                                       no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty,
-                                       required)
+        return visualize.caption_image(self, **kw)
 
     def validation_step(self, batch, batch_idx=0):
         """model.py:693-697"""

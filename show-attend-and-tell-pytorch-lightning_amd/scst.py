@@ -71,7 +71,7 @@ def sample(model, ann_bld, samples, max_gen_length, temperature=1.0, seed=None, 
     if K < 1:
         raise ValueError("scst.sample: samples=%d" % K)
     ann = ann_bld.repeat_interleave(K, 0).contiguous()
-    o = model._beam_search_device(ann, 1, int(max_gen_length), float(temperature), "ancestral", 3, None, seed, gumbel, None, False)
+    o = model._beam_search_device(ann, 1, int(max_gen_length), float(temperature), sample_method="ancestral", seed=seed, gumbel=gumbel)
     sel = evaluation.select_hypotheses(o, model.pad_idx)
     return sel["tokens"], sel["lengths"]
 
@@ -79,7 +79,7 @@ def sample(model, ann_bld, samples, max_gen_length, temperature=1.0, seed=None, 
 @torch.no_grad()
 def greedy(model, ann_bld, max_gen_length):
     """the beam-1 caption of every image: ``(tokens (B, max_gen_length + 1), lengths (B))`` on the device"""
-    o = model._beam_search_device(ann_bld.contiguous(), 1, int(max_gen_length), 1.0, "beam", 3, None, None, None, None, False)
+    o = model._beam_search_device(ann_bld.contiguous(), 1, int(max_gen_length), 1.0)
     sel = evaluation.select_hypotheses(o, model.pad_idx)
     return sel["tokens"], sel["lengths"]
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import constraints
 from . import jpeg as J
 
 
@@ -151,27 +152,21 @@ def _names(items):
 
 
 @torch.no_grad()
-def _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method, rescore_reward, visual_size,
-            input_size, seed, with_alpha, progressive=False, topg=None, prefix=None, banned=None, no_unk=False, sample_topp=0.9, no_repeat_ngram=None, min_length=None, repetition_penalty=None,
-            mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
-    """load_square -> prepare_image -> encoder -> batched search -> the winning hypothesis of every picture, all enqueued back to back"""
-    from . import constraints, evaluation as E
+def _search(model, items, opt, beamk, max_gen_length, temperature, rescore_method, rescore_reward, visual_size, input_size, with_alpha, progressive, mbr_corpus,
+            mbr_reward, mbr_alpha):
+    """load_square -> prepare_image -> encoder -> batched search -> the winning hypothesis of every picture, all enqueued back to back;
+    ``opt``: the caller's ``constraints.SearchOptions``"""
+    from . import evaluation as E
     if int(max_gen_length) < 1:
         raise ValueError("visualize: max_gen_length >= 1 (the batched search)")
-    con = dict(topg=topg, prefix=prefix, banned=banned, no_unk=no_unk, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
-               repetition_penalty=repetition_penalty)
-    constraints.resolve_all(model.hp.vocab_stoi, model.hp.vocab_size, len(items), beamk, max_gen_length, str(sample_method), **con)     # refuse before any launch
+    opt.resolve(model.hp.vocab_stoi, model.hp.vocab_size, len(items), beamk, max_gen_length)     # refuse before any launch, and before any picture is read
     constraints.check_mbr(rescore_method, mbr_corpus, mbr_reward, mbr_alpha, beamk, model.hp.vocab_size, max_gen_length)
-    constraints.resolve_groups(beamk, beam_groups, diversity_penalty, str(sample_method), decoder_noise, topg, prefix, V=model.hp.vocab_size)
-    constraints.resolve_required(model.hp.vocab_stoi, model.hp.vocab_size, len(items), beamk, max_gen_length, required, str(sample_method), decoder_noise,
-                                 topg, prefix, banned, no_unk, beam_groups)
     dev = model.embedding.weight.device
     model.eval()
     squares, status, index = _load_squares(items, visual_size, dev, progressive)
     img = prepare_image_batch(squares, input_size if input_size is not None else model.hp.get("input_size"))
     ann_bld, hw = model.encode(img)
-    o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, str(sample_method), sample_topk, decoder_noise, seed, None, None,
-                                  False, sample_topp=sample_topp, beam_groups=beam_groups, diversity_penalty=diversity_penalty, required=required, **con)
+    o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, options=opt)
     sel = E.select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward, with_alpha=with_alpha, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward,
                               mbr_alpha=mbr_alpha)
     return squares, hw, sel, status, index
@@ -207,10 +202,9 @@ def visualize(model, items, beamk=3, max_gen_length=32, temperature=1.0, sample_
     ``mbr_reward`` / ``mbr_alpha`` picks the caption by consensus (the score shown is its utility); ``beam_groups`` / ``diversity_penalty``: the
     diverse beam search ("Diverse beam search"); ``required`` (e.g. ``"dog frisbee"``): the words every caption must contain
     ("Required words")."""
-    squares, hw, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                              rescore_reward, visual_size, input_size, seed, True, progressive, topg, prefix, banned, no_unk, sample_topp,
-                                              no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups,
-                                              diversity_penalty, required)
+    squares, hw, sel, status, index = _search(model, items, constraints.SearchOptions.from_kwargs(locals()), beamk, max_gen_length, temperature, rescore_method,
+                                              rescore_reward, visual_size, input_size, with_alpha=True, progressive=progressive, mbr_corpus=mbr_corpus,
+                                              mbr_reward=mbr_reward, mbr_alpha=mbr_alpha)
     panels = attention_panels(squares, sel["alphas"], sel["lengths"], hw, power, opacity)
     captions, words, scores, ppl, lengths = _read(model, sel, status, index)
     return Visual(captions, words, scores, ppl, lengths, panels, _names(items))
@@ -222,10 +216,9 @@ def caption_image(model, items, beamk=3, max_gen_length=32, temperature=1.0, sam
                   mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
     """``caption(prepare_image(load_square(path, visual_size), input_size))`` for a batch, without panels:
     ``(captions, words, scores, perplexities)``, one entry per picture.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk``: as ``visualize``."""
-    _, _, sel, status, index = _search(model, items, beamk, max_gen_length, temperature, sample_method, sample_topk, decoder_noise, rescore_method,
-                                       rescore_reward, visual_size, input_size, seed, False, progressive, topg, prefix, banned, no_unk, sample_topp,
-                                       no_repeat_ngram, min_length, repetition_penalty, mbr_corpus, mbr_reward, mbr_alpha, beam_groups, diversity_penalty,
-                                       required)
+    _, _, sel, status, index = _search(model, items, constraints.SearchOptions.from_kwargs(locals()), beamk, max_gen_length, temperature, rescore_method, rescore_reward,
+                                       visual_size, input_size, with_alpha=False, progressive=progressive, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward,
+                                       mbr_alpha=mbr_alpha)
     captions, words, scores, ppl, _ = _read(model, sel, status, index)
     return captions, words, scores, ppl
 
