@@ -717,6 +717,35 @@ int sat_caption_mbr(const int32_t* hyp_tokens, const int32_t* hyp_len, const int
                     int32_t K, int32_t width, const void* table, int64_t capacity, int64_t n_images, double sigma, double w_cider, double w_rouge,
                     double alpha, double* utilities /* (B, K) */, int32_t* winner /* (B) */, void* stream);
 
+/* ------------------------------------------------------------------ diversity of a beam: distinct-n, mBLEU (self-BLEU), unique captions
+ * (sat_amd/metrics.py is the specification: diversity_stats, diversity_per_hypothesis, diversity_from_stats).  The hypotheses come in
+ * sat_caption_mbr's layout: image b has hyp_count[b] of them (clamped into [0, K]) in append order, hypothesis f = the first
+ * hyp_len[b][f] tokens (clamped into [0, width]) of hyp_tokens (B, K, width).  Tokens are compared as the n-gram keys above see them
+ * (clamped into [0, 65534]): out-of-range input gives a wrong count, never a stray access.  stats (B, SAT_DIVERSITY_STATS) int32:
+ *   [0..3]    distinct n-grams, n = 1..4, pooled over all hypotheses of the image
+ *   [4..7]    n-gram positions pooled: the sum over hypotheses of max(len - n + 1, 0); [n-1] / [3+n] is distinct-n (0 positions: 0.0)
+ *   [8]       number of hypotheses                 [9]  number of distinct hypotheses (equal token sequences; two empty ones count once)
+ *   [10..13]  sum over hypotheses i of the clipped n-gram matches of i against all the OTHER hypotheses as references (corpus BLEU's
+ *             numerator: per distinct n-gram min(count in i, largest count in another hypothesis)); duplicates and empty hypotheses
+ *             stay among the others
+ *   [14..17]  sum over i of max(1, len_i - n + 1), per segment as in sat_caption_stats [4..7]
+ *   [18]      sum over i of len_i                  [19] sum over i of the closest other length (a tie goes to the shorter)
+ * An image with fewer than 2 hypotheses has nothing to compare with: its columns 10..19 are 0.  per_hyp (B, K, 10) int32, optional:
+ * for hypothesis f the columns [0..9] of sat_caption_stats with the other hypotheses as its references; all 0 in the slots
+ * f >= hyp_count[b] and for an image with fewer than 2 hypotheses.  One launch, one workgroup per image: the n-gram positions of one
+ * order are sorted in LDS by (n-gram, hypothesis) and everything is read off the sorted runs; integers only, no atomics: the same
+ * input gives the same bits.  B == 0 returns SAT_OK without a launch.  SAT_EINVAL before any launch: a null pointer (per_hyp may be
+ * NULL), B < 0, K < 1, K > SAT_MBR_MAX_HYPS, width < 1, width > SAT_CAPTION_MAX_LEN. */
+#define SAT_DIVERSITY_STATS 20
+int sat_caption_diversity(const int32_t* hyp_tokens, const int32_t* hyp_len, const int32_t* hyp_count, int32_t B, int32_t K, int32_t width,
+                          int32_t* stats /* (B, 20) */, int32_t* per_hyp /* (B, K, 10) or NULL */, void* stream);
+/* The vocabulary captions use: counts[t] += 1 for each of the first cap_len[b] tokens t (cap_len clamped into [0, cap_width]) of
+ * cap_tokens (B, cap_width) that lies in [0, V); others are skipped.  counts (V) int32 is ADDED to (zero it before the first call).
+ * Integer atomicAdd on global memory: a sum, the same whatever the order.  B == 0 returns SAT_OK without a launch.  SAT_EINVAL before
+ * any launch: a null pointer, B < 0, V < 1, cap_width < 1 or above SAT_CAPTION_MAX_LEN. */
+int sat_caption_vocab_usage(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, int32_t B, int32_t V,
+                            int32_t* counts /* (V), added to */, void* stream);
+
 /* ------------------------------------------------------------------ chrF over the characters of the vocabulary's spelling
  * (sat_amd/metrics.py is the specification: chrf_text, chrf_stats, chrf_sentence, chrf; nltk's sentence_chrf with whitespace ignored).
  * Reference (b, r) and hypothesis b are sliced as in sat_caption_stats, with the same limits and SAT_EINVAL messages.  A sentence is

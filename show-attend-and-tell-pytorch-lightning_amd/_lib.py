@@ -404,6 +404,11 @@ SYMBOLS.update({          # consensus (MBR) reranking of the finished beam (eval
     "sat_beam_select_at": (C.c_int, [_vp] * 9 + [_i32, _i32, _i32, _i32, _i32] + [_vp] * 7),
 })
 MBR_MAX_HYPS = 32                                                               # SAT_MBR_MAX_HYPS
+SYMBOLS.update({          # diversity of the finished beam (evaluation.diversity_statistics, DiversityStats)
+    "sat_caption_diversity": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "sat_caption_vocab_usage": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+})
+DIVERSITY_STATS = 20                                                            # SAT_DIVERSITY_STATS
 SYMBOLS.update({          # chrF over the vocabulary's spelling (evaluation.VocabChars, chrf_scores)
     "sat_caption_chrf": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp]),
 })

@@ -441,6 +441,23 @@ int sat_caption_mbr(const int32_t* hyp_tokens, const int32_t* hyp_len, const int
     return caption_mbr(hyp_tokens, hyp_len, hyp_count, hyp_logp, B, K, width, table, (long)capacity, (long)n_images, sigma, w_cider, w_rouge, alpha,
                        utilities, winner, (hipStream_t)stream);
 }
+int sat_caption_diversity(const int32_t* hyp_tokens, const int32_t* hyp_len, const int32_t* hyp_count, int32_t B, int32_t K, int32_t width, int32_t* stats,
+                          int32_t* per_hyp, void* stream) {
+    if (!hyp_tokens || !hyp_len || !hyp_count || !stats) return fail(SAT_EINVAL, "caption_diversity: null pointer");
+    if (B < 0 || K < 1 || width < 1) return fail(SAT_EINVAL, "caption_diversity: bad size (B=%d >= 0, K=%d >= 1, width=%d >= 1)", B, K, width);
+    if (K > SAT_MBR_MAX_HYPS || width > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "caption_diversity: over the limits (K=%d <= %d, width=%d <= %d)", K, SAT_MBR_MAX_HYPS, width, SAT_CAPTION_MAX_LEN);
+    if (B == 0) return SAT_OK;
+    return caption_diversity(hyp_tokens, hyp_len, hyp_count, B, K, width, stats, per_hyp, (hipStream_t)stream);
+}
+int sat_caption_vocab_usage(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, int32_t B, int32_t V, int32_t* counts, void* stream) {
+    if (!cap_tokens || !cap_len || !counts) return fail(SAT_EINVAL, "caption_vocab_usage: null pointer");
+    if (B < 0 || V < 1) return fail(SAT_EINVAL, "caption_vocab_usage: bad size (B=%d >= 0, V=%d >= 1)", B, V);
+    if (cap_width < 1 || cap_width > SAT_CAPTION_MAX_LEN)
+        return fail(SAT_EINVAL, "caption_vocab_usage: cap_width %d outside 1..%d", cap_width, SAT_CAPTION_MAX_LEN);
+    if (B == 0) return SAT_OK;
+    return caption_vocab_usage(cap_tokens, cap_len, cap_width, B, V, counts, (hipStream_t)stream);
+}
 int sat_caption_chrf(const int32_t* cap_tokens, const int32_t* cap_len, int32_t cap_width, const int32_t* refs, const int32_t* ref_lengths, int32_t B,
                      int32_t R, int32_t T, const int32_t* word_offsets, const int32_t* word_chars, int32_t V, int32_t max_word_chars, double beta,
                      double* scores, int32_t* stats, void* stream) {

@@ -29,6 +29,10 @@ int caption_consensus(const int* cap_tokens, const int* cap_len, int W, const in
 constexpr int kMbrMaxHyps = 32;          // SAT_MBR_MAX_HYPS
 int caption_mbr(const int* hyp_tokens, const int* hyp_len, const int* hyp_count, const float* hyp_logp, int B, int K, int W, const void* table, long capacity,
                 long n_images, double sigma, double w_cider, double w_rouge, double alpha, double* utilities, int* winner, hipStream_t st);
+// caption_diversity.hip: the integers of distinct-n / mBLEU / unique captions over an image's hypotheses; the vocabulary captions use
+constexpr int kDiversityStats = 20;      // SAT_DIVERSITY_STATS
+int caption_diversity(const int* hyp_tokens, const int* hyp_len, const int* hyp_count, int B, int K, int W, int* stats, int* per_hyp, hipStream_t st);
+int caption_vocab_usage(const int* cap_tokens, const int* cap_len, int W, int B, int V, int* counts, hipStream_t st);
 // caption_chrf.hip: chrF over the characters of the vocabulary's spelling
 int caption_chrf(const int* cap_tokens, const int* cap_len, int W, const int* refs, const int* ref_len, int B, int R, int T, const int* word_offsets,
                  const int* word_chars, int V, int max_word_chars, double beta, double* scores, int* stats, hipStream_t st);

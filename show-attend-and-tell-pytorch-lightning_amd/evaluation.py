@@ -24,6 +24,11 @@ Opt-in, ``rescore_method="MBR"`` with ``mbr_corpus=ReferenceCorpus``: consensus 
 ``metrics.consensus_utilities`` is the specification).  ``finished_hypotheses`` traces every finished hypothesis back on the device,
 ``consensus_utilities`` scores them against each other, ``select_hypotheses`` gathers the winner: three launches, no host read.  The
 reference's four rules (None / "LN" / "WR" / "BAR") stay on ``sat_beam_select``.
+
+Opt-in, ``with_diversity=True``: how different the finished hypotheses of an image are (csrc/caption_diversity.hip;
+``metrics.diversity_stats`` is the specification): distinct-n, mBLEU and the share of unique captions over ``finished_hypotheses`` of the
+same search buffers, and the vocabulary the selected captions use.  ``diversity_statistics`` is one launch, ``val_batch_stats`` hangs a
+``DiversityStats`` on its ``CaptionStats``, ``evaluate`` sums them over the split and reads them once.  Without the flag nothing changes.
 """
 import numpy as np
 import torch
@@ -77,6 +82,60 @@ def consensus_utilities(hyp_tokens, hyp_len, counts, logp, corpus, reward=(1.0, 
     return utilities, winner
 
 
+def diversity_statistics(hyp_tokens, hyp_len, counts, per_hypothesis=False):
+    """``sat_caption_diversity``: ``stats (B, 20) int32`` on the device of the hypotheses ``hyp_tokens (B, K, W)`` / ``hyp_len (B, K)`` /
+    ``counts (B)`` (int32, the layout ``finished_hypotheses`` leaves) -- the columns of ``metrics.diversity_stats``, which is the
+    specification; ``per_hypothesis``: also ``per_hyp (B, K, 10) int32``, ``metrics.diversity_per_hypothesis``.  One launch, no host read."""
+    L.require_gpu(hyp_tokens, hyp_len, counts)
+    for t in (hyp_tokens, hyp_len, counts):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    B, K, W = hyp_tokens.shape
+    assert tuple(hyp_len.shape) == (B, K) and tuple(counts.shape) == (B,), "hyp_len is (B, K), counts is (B)"
+    stats = torch.empty(B, L.DIVERSITY_STATS, dtype=torch.int32, device=hyp_tokens.device)
+    per_hyp = torch.empty(B, K, 10, dtype=torch.int32, device=hyp_tokens.device) if per_hypothesis else None
+    L.check(L.lib().sat_caption_diversity(L.ptr(hyp_tokens), L.ptr(hyp_len), L.ptr(counts), B, K, W, L.ptr(stats), L.ptr(per_hyp), L.stream_ptr()),
+            "sat_caption_diversity")
+    return (stats, per_hyp) if per_hypothesis else stats
+
+
+def vocabulary_usage(tokens, lengths, vocab_size, counts=None):
+    """``sat_caption_vocab_usage``: ``counts (vocab_size) int32`` on the device, how often each word occurs in the captions ``tokens
+    (B, W)`` / ``lengths (B)`` (int32); ids outside the vocabulary are skipped.  A given ``counts`` is added to.  One launch (and the
+    clear of a fresh ``counts``), no host read."""
+    L.require_gpu(tokens, lengths)
+    for t in (tokens, lengths):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    B, W = tokens.shape
+    if counts is None:
+        counts = torch.zeros(int(vocab_size), dtype=torch.int32, device=tokens.device)
+    L.require_gpu(counts)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == int(vocab_size)
+    L.check(L.lib().sat_caption_vocab_usage(L.ptr(tokens), L.ptr(lengths), W, B, int(vocab_size), L.ptr(counts), L.stream_ptr()), "sat_caption_vocab_usage")
+    return counts
+
+
+class DiversityStats:
+    """Sums over images of the columns of ``sat_caption_diversity``: ``sums`` (20,) int64 and ``vocab_counts`` (vocab_size,) int64 (how
+    often the selected captions use each word) on the device, ``images`` and ``vocab_size`` host ints.  ``a + b`` adds; ``metrics()``
+    reads the device once and returns ``metrics.diversity_from_stats`` with ``vocabulary`` = the number of words used at least once."""
+
+    def __init__(self, sums, vocab_counts, images, vocab_size):
+        self.sums, self.vocab_counts, self.images, self.vocab_size = sums, vocab_counts, int(images), int(vocab_size)
+
+    def __add__(self, other):
+        if self.vocab_size != other.vocab_size:
+            raise ValueError("DiversityStats: vocabularies of %d and %d words" % (self.vocab_size, other.vocab_size))
+        return DiversityStats(self.sums + other.sums, self.vocab_counts + other.vocab_counts, self.images + other.images, self.vocab_size)
+
+    def vector(self):
+        """(21,) int64 on the device: the 20 sums, then the number of words with a non-zero count"""
+        return torch.cat([self.sums, (self.vocab_counts != 0).sum(dtype=torch.int64).reshape(1)])
+
+    def metrics(self):
+        v = self.vector().cpu().tolist()                                      # the one host read
+        return metrics.diversity_from_stats(v[:L.DIVERSITY_STATS], vocab_used=v[L.DIVERSITY_STATS])
+
+
 def select_hypotheses(buffers, pad_id, rescore_method=None, rescore_reward=0.5, with_alpha=False, mbr_corpus=None, mbr_reward=(1.0, 0.0), mbr_alpha=0.0):
     """``sat_beam_select`` on the buffers ``SATDecoder._beam_search_device`` returns: the best hypothesis of every image as
     ``dict(tokens (B, S + 1) int32 padded with pad_id, lengths (B) int32, scores (B) rescored, raw (B), steps (B), alphas (B, S, L) or None)``.
@@ -124,6 +183,13 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     search ("Diverse beam search"); ``required``: the words every caption must contain ("Required words").
     Launches only, like the rest."""
     opt = constraints.SearchOptions.from_kwargs(locals())
+    _, sel, ppl = _search_and_select(model, img, opt, beamk, max_gen_length, temperature, rescore_method, rescore_reward, mbr_corpus, mbr_reward, mbr_alpha,
+                                     corpus)
+    return sel["tokens"], sel["lengths"], sel["scores"], ppl
+
+
+def _search_and_select(model, img, opt, beamk, max_gen_length, temperature, rescore_method, rescore_reward, mbr_corpus, mbr_reward, mbr_alpha, corpus):
+    """``caption_tokens`` with the search buffers kept: ``(buffers, select_hypotheses' dict, perplexities (B))``"""
     if int(max_gen_length) < 1:
         raise ValueError("caption_tokens: max_gen_length >= 1 (the batched search)")
     mbr_corpus = corpus if mbr_corpus is None else mbr_corpus
@@ -134,7 +200,7 @@ def caption_tokens(model, img, beamk=3, max_gen_length=32, temperature=1.0, samp
     o = model._beam_search_device(ann_bld.contiguous(), beamk, max_gen_length, temperature, options=opt)
     sel = select_hypotheses(o, model.pad_idx, rescore_method, rescore_reward, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha)
     ppl = torch.exp(-sel["raw"] / sel["steps"].float())                      # model.py:415
-    return sel["tokens"], sel["lengths"], sel["scores"], ppl
+    return o, sel, ppl
 
 
 def caption_statistics(tokens, lengths, refs, ref_lengths, embedding):
@@ -356,21 +422,25 @@ def vector_keys(n):
 class CaptionStats:
     """Sums over images: ``counts`` (12,) int64 (the columns of sat_caption_stats), ``cosine_sum`` / ``perplexity_sum`` (float64
     scalars) on the device, ``images`` a host int; scored against a ``ReferenceCorpus`` also ``consensus_sum`` (2,) float64, the sums of
-    CIDEr-D and ROUGE-L; scored over a ``VocabChars`` also ``chrf_sum``, a float64 scalar.  ``a + b`` adds; ``metrics()`` reads the
-    device once."""
+    CIDEr-D and ROUGE-L; scored over a ``VocabChars`` also ``chrf_sum``, a float64 scalar; taken ``with_diversity`` also ``diversity``,
+    a ``DiversityStats`` (it has a vector and ``metrics()`` of its own: ``vector()`` here does not carry it).  ``a + b`` adds;
+    ``metrics()`` reads the device once."""
 
-    def __init__(self, counts, cosine_sum, perplexity_sum, images, consensus_sum=None, chrf_sum=None):
+    def __init__(self, counts, cosine_sum, perplexity_sum, images, consensus_sum=None, chrf_sum=None, diversity=None):
         self.counts, self.cosine_sum, self.perplexity_sum, self.images = counts, cosine_sum, perplexity_sum, int(images)
-        self.consensus_sum, self.chrf_sum = consensus_sum, chrf_sum
+        self.consensus_sum, self.chrf_sum, self.diversity = consensus_sum, chrf_sum, diversity
 
     def __add__(self, other):
         if (self.consensus_sum is None) != (other.consensus_sum is None):
             raise ValueError("CaptionStats: one side was scored against a ReferenceCorpus and the other was not")
         if (self.chrf_sum is None) != (other.chrf_sum is None):
             raise ValueError("CaptionStats: one side was scored with chrF (a VocabChars) and the other was not")
+        if (self.diversity is None) != (other.diversity is None):
+            raise ValueError("CaptionStats: one side carries diversity statistics (with_diversity) and the other does not")
         return CaptionStats(self.counts + other.counts, self.cosine_sum + other.cosine_sum, self.perplexity_sum + other.perplexity_sum,
                             self.images + other.images, None if self.consensus_sum is None else self.consensus_sum + other.consensus_sum,
-                            None if self.chrf_sum is None else self.chrf_sum + other.chrf_sum)
+                            None if self.chrf_sum is None else self.chrf_sum + other.chrf_sum,
+                            None if self.diversity is None else self.diversity + other.diversity)
 
     def vector(self):
         """(14,) float64 on the device: the counts (exact below 2^53), then the two sums; (16,) with the CIDEr-D and ROUGE-L sums; the
@@ -390,29 +460,37 @@ class CaptionStats:
 def val_batch_stats(model, batch, beamk=3, max_gen_length=32, temperature=0.5, sample_method="beam", sample_topk=3, decoder_noise=None,
                     rescore_method=None, rescore_reward=0.5, seed=None, graph=False, corpus=None, topg=None, prefix=None, banned=None, no_unk=False,
                     sample_topp=0.9, chrf=None, chrf_beta=3.0, no_repeat_ngram=None, min_length=None, repetition_penalty=None, mbr_corpus=None,
-                    mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None):
+                    mbr_reward=(1.0, 0.0), mbr_alpha=0.0, beam_groups=None, diversity_penalty=0.5, required=None, with_diversity=False):
     """``SAT.val_batch`` (model.py:684-691) as a ``CaptionStats``: search, selection, statistics and cosine enqueued back to back;
     with ``corpus`` (a ``ReferenceCorpus``) CIDEr-D and ROUGE-L against it in the same enqueue, with ``chrf`` (a ``VocabChars``) chrF
     with ``chrf_beta``.  ``topg`` / ``prefix`` / ``banned`` / ``no_unk`` constrain the search, ``no_repeat_ngram`` / ``min_length`` /
     ``repetition_penalty`` are its history rules (``SATDecoder.beam_decode_batched``).  ``rescore_method="MBR"`` reranks by consensus
     against ``mbr_corpus`` (``corpus`` when that is None) with ``mbr_reward`` / ``mbr_alpha``.  ``beam_groups`` / ``diversity_penalty``: the
-    diverse beam search; ``required``: the words every caption must contain."""
+    diverse beam search; ``required``: the words every caption must contain.  ``with_diversity``: the result carries ``.diversity``, a
+    ``DiversityStats`` of the batch: ``sat_caption_diversity`` over every finished hypothesis of the same search buffers (the search
+    is not run again; MBR's back-trace is reused) and the vocabulary usage of the selected captions: two or three more launches."""
     opt = constraints.SearchOptions.from_kwargs(locals())
     img, encoded_captions, lengths = batch
     dev = model.embedding.weight.device
-    tokens, lens, _, ppl = caption_tokens(model, img.to(dev), beamk=beamk, max_gen_length=max_gen_length, temperature=temperature, rescore_method=rescore_method,
-                                          rescore_reward=rescore_reward, mbr_corpus=mbr_corpus, mbr_reward=mbr_reward, mbr_alpha=mbr_alpha, corpus=corpus,
-                                          **opt.kwargs(caption_tokens))
+    buffers, sel, ppl = _search_and_select(model, img.to(dev), opt, beamk, max_gen_length, temperature, rescore_method, rescore_reward, mbr_corpus, mbr_reward,
+                                           mbr_alpha, corpus)
+    tokens, lens = sel["tokens"], sel["lengths"]
+    diversity = None
+    if with_diversity:
+        hyp_tokens, hyp_len = (sel["hyp_tokens"], sel["hyp_len"]) if "hyp_tokens" in sel else finished_hypotheses(buffers, model.pad_idx)
+        V = model.embedding.weight.shape[0]
+        diversity = DiversityStats(diversity_statistics(hyp_tokens, hyp_len, buffers["fin_count"]).sum(0, dtype=torch.int64),
+                                   vocabulary_usage(tokens, lens, V).to(torch.int64), tokens.shape[0], V)
     refs = torch.as_tensor(encoded_captions).to(device=dev, dtype=torch.int32).contiguous()
     ref_lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
     stats, best = caption_statistics(tokens, lens, refs, ref_lengths, model.embedding.weight.detach().contiguous())
     consensus = None if corpus is None else consensus_scores(tokens, lens, refs, ref_lengths, corpus).sum(0)
     chrf_sum = None if chrf is None else chrf_scores(tokens, lens, refs, ref_lengths, chrf, chrf_beta).sum()
     return CaptionStats(stats.sum(0, dtype=torch.int64), best.sum(dtype=torch.float64), ppl.sum(dtype=torch.float64), tokens.shape[0], consensus,
-                        chrf_sum)
+                        chrf_sum, diversity)
 
 
-def evaluate(model, loader, max_batches=None, seed=None, corpus=None, chrf=None, **decode):
+def evaluate(model, loader, max_batches=None, seed=None, corpus=None, chrf=None, with_diversity=False, **decode):
     """``val_batch_stats`` over the batches of ``loader`` (at most ``max_batches``).  Returns ``{"batch_mean": the notebook's protocol,
     the plain mean of the per-batch metric dicts, "corpus": BLEU / GLEU taken once from the statistics summed over every image (cosine and
     perplexity: means over images), "batches", "images"}``.  The per-batch statistics stay on the device and are read once at the end.
@@ -421,25 +499,34 @@ def evaluate(model, loader, max_batches=None, seed=None, corpus=None, chrf=None,
     read.  ``decode`` takes every keyword of ``val_batch_stats``, the search constraints
     ``topg`` / ``prefix`` / ``banned`` / ``no_unk``, the history rules ``no_repeat_ngram`` / ``min_length`` / ``repetition_penalty`` and
     ``rescore_method="MBR"`` with ``mbr_corpus`` (``corpus`` when that is None) / ``mbr_reward`` / ``mbr_alpha`` and the diverse beam search
-    ``beam_groups`` / ``diversity_penalty`` among them."""
+    ``beam_groups`` / ``diversity_penalty`` among them.  ``with_diversity``: the result gains "diversity", ``metrics.diversity_from_stats`` of
+    the sums over every image of the split (distinct-n, mBLEU, unique, hypotheses, vocabulary); the sums are added on the device batch
+    by batch and read once, behind the metric vectors.  Without it the result and the launches are exactly those of before."""
     if corpus is not None:
         decode["corpus"] = corpus
     if chrf is not None:
         decode["chrf"] = chrf
-    vecs, images = [], []
+    if with_diversity:
+        decode["with_diversity"] = True
+    vecs, images, diversity = [], [], None
     for i, batch in enumerate(loader):
         if max_batches is not None and i >= max_batches:
             break
         st = model.val_batch_stats(batch, seed=None if seed is None else int(seed) + i, **decode)
         vecs.append(st.vector()); images.append(st.images)
+        if with_diversity:
+            diversity = st.diversity if diversity is None else diversity + st.diversity
     if not vecs:
         raise ValueError("evaluate: the loader gave no batch")
     rows = torch.stack(vecs).cpu().tolist()                                  # the one host read
     per_batch = [metrics_from_vector(r, n) for r, n in zip(rows, images)]
     total = [sum(int(r[c]) for r in rows) for c in range(12)] + [sum(r[c] for r in rows) for c in range(12, len(rows[0]))]
     keys = vector_keys(len(rows[0]))
-    return {"batch_mean": {k: sum(d[k] for d in per_batch) / len(per_batch) for k in keys}, "corpus": metrics_from_vector(total, sum(images)),
-            "batches": len(per_batch), "images": sum(images)}
+    out = {"batch_mean": {k: sum(d[k] for d in per_batch) / len(per_batch) for k in keys}, "corpus": metrics_from_vector(total, sum(images)),
+           "batches": len(per_batch), "images": sum(images)}
+    if with_diversity:
+        out["diversity"] = diversity.metrics()                                # one more, at the end of the split (exact integers)
+    return out
 
 
 def draw_decode_params(rs, space=NOTEBOOK_SPACE):

@@ -308,3 +308,60 @@ def distinct_n(captions, n):
         raise ValueError("distinct_n: n=%d is not positive" % n)
     grams = [g for c in captions for g in _ngrams(list(c), n)]
     return len(set(grams)) / len(grams) if grams else 0.0
+
+
+# ----------------------------------------------------------------------------- diversity of a beam: distinct-n, mBLEU, unique captions
+# What the searches that return different captions are built to change, as integers up to one final division: distinct-n (Li et al.
+# 2016, the "Div-n" of the captioning papers), mBLEU / self-BLEU (every caption scored with the rest of its set as references:
+# Vijayakumar et al. 2018, Wang & Chan 2019) and the share of unique captions.  The specification of sat_caption_diversity
+# (csrc/caption_diversity.hip).  A hypothesis is the token list without START and END, as everywhere in this file.
+DIVERSITY_STATS = 20
+DIVERSITY_KEYS = ("distinct1", "distinct2", "distinct3", "distinct4", "mbleu1", "mbleu2", "mbleu3", "mbleu4", "unique", "hypotheses")
+#: the weights mBLEU-n is taken with: evaluation.BLEU_WEIGHTS (the reference's, model.py:651-654, bleu3 as written there), restated here
+#: because evaluation.py imports this file; tests/test_diversity.py holds the two together
+MBLEU_WEIGHTS = {"mbleu1": (1, 0, 0, 0), "mbleu2": (0.5, 0.5, 0, 0), "mbleu3": (0.33, 0.33, 0.33, 0), "mbleu4": (0.25, 0.25, 0.25, 0.25)}
+
+
+def diversity_per_hypothesis(hyps):
+    """per hypothesis of ONE image the 10 BLEU columns of sat_caption_stats with all the OTHER hypotheses as its references (duplicates
+    and empty ones stay among them): clipped matches n = 1..4, ``max(1, len - n + 1)`` n = 1..4, the length, the closest other length
+    (a tie goes to the shorter).  All 0 for an image with fewer than 2 hypotheses: there is nothing to compare with."""
+    hyps = [list(h) for h in hyps]
+    if len(hyps) < 2:
+        return [[0] * 10 for _ in hyps]
+    rows = []
+    for i, h in enumerate(hyps):
+        others = hyps[:i] + hyps[i + 1:]
+        pairs = [modified_precision(others, h, n) for n in range(1, 5)]
+        rows.append([p[0] for p in pairs] + [p[1] for p in pairs] + [len(h), closest_ref_length(others, len(h))])
+    return rows
+
+
+def diversity_stats(hyps):
+    """the 20 integers of ONE image's hypotheses (the columns of sat_caption_diversity, include/sat_hip.h): ``[0..3]`` distinct n-grams
+    pooled over the hypotheses, ``[4..7]`` n-gram positions pooled (``[n-1] / [3+n]`` is ``distinct_n(hyps, n)``), ``[8]`` hypotheses,
+    ``[9]`` distinct hypotheses, ``[10..19]`` the columns of ``diversity_per_hypothesis`` summed over the hypotheses."""
+    hyps = [list(h) for h in hyps]
+    out = [len(set(g for h in hyps for g in _ngrams(h, n))) for n in range(1, 5)]
+    out += [sum(max(len(h) - n + 1, 0) for h in hyps) for n in range(1, 5)]
+    out += [len(hyps), len(set(tuple(h) for h in hyps))]
+    rows = diversity_per_hypothesis(hyps)
+    return out + [sum(r[c] for r in rows) for c in range(10)]
+
+
+def diversity_from_stats(sums, vocab_used=None):
+    """the metric dict from the columns of ``diversity_stats`` summed over images: distinct1..4 (0.0 without a position), mbleu1..4
+    (``bleu_from_stats`` of the summed self-BLEU columns: the corpus BLEU of every hypothesis against the others of its image), unique
+    (distinct hypotheses / hypotheses, 0.0 without one), hypotheses; ``vocabulary`` (the number of different words used) when
+    ``vocab_used`` is given."""
+    s = [int(x) for x in sums]
+    if len(s) != DIVERSITY_STATS:
+        raise ValueError("diversity_from_stats: %d numbers (%d)" % (len(s), DIVERSITY_STATS))
+    out = {"distinct%d" % n: (s[n - 1] / s[3 + n] if s[3 + n] else 0.0) for n in range(1, 5)}
+    for k, w in MBLEU_WEIGHTS.items():
+        out[k] = bleu_from_stats(s[10:14], s[14:18], s[18], s[19], w)          # no match at all (all-zero sums included): 0
+    out["unique"] = s[9] / s[8] if s[8] else 0.0
+    out["hypotheses"] = s[8]
+    if vocab_used is not None:
+        out["vocabulary"] = int(vocab_used)
+    return out

@@ -18,6 +18,12 @@ spelled with pseudo-words of 1..12 letters (5 on average, about an English capti
 on their own on one batch's search buffers, and the host clock of ``metrics.consensus_utilities`` on the same hypotheses.
     python tools/bench_evaluate.py --chrf [--batches 4] [--images 128] [--repeats 5] [--json]
     python tools/bench_evaluate.py --mbr [--beams 5 20] [--split-images 5000] [--batches 4] [--images 128] [--repeats 5] [--json]
+--diversity measures the beam-diversity statistics (``with_diversity=True``) at beam 5 and beam 20: the per-batch time of
+``evaluation.evaluate`` without and with the flag in alternating rounds (hipEvents), the work it replaces -- one batch's finished
+hypotheses copied to the host, rebuilt as lists and put through ``metrics.diversity_stats`` (host clock, with and without the copy) --
+and ``sat_caption_diversity`` alone (20 launches between two hipEvents) on that batch's hypotheses and, once, on 128 synthetic images
+at the limits: 32 hypotheses of 128 tokens over 5 words (every sort at its full 4096 pairs).
+    python tools/bench_evaluate.py --diversity [--beams 5 20] [--batches 4] [--images 128] [--repeats 5] [--json]
 """
 import argparse
 import json
@@ -245,6 +251,73 @@ def bench_mbr(a, model, batches, hp, T, R):
               (host["mbr_cider"], host["mbr_mixed"], worst))
 
 
+def bench_diversity(a, model, batches, hp, T, R):
+    """--diversity: evaluate without / with the flag, the host specification on the same hypotheses, the kernel alone"""
+    import numpy as np
+    spread = lambda v: dict(median=statistics.median(v), min=min(v), max=max(v))
+
+    def kernel_ms(ht, hl, cnt, launches=20):
+        def run():
+            for _ in range(launches):
+                E.diversity_statistics(ht, hl, cnt)
+        run()
+        return spread([event_ms(run)[0] / launches for _ in range(a.repeats)])
+
+    rs = np.random.RandomState(3)
+    lim_tok = torch.from_numpy(rs.randint(0, 5, size=(a.images, 32, 128)).astype(np.int32)).cuda()
+    lim_len = torch.full((a.images, 32), 128, dtype=torch.int32, device="cuda")
+    lim_cnt = torch.full((a.images,), 32, dtype=torch.int32, device="cuda")
+    limits = kernel_ms(lim_tok, lim_len, lim_cnt)
+    for beamk in a.beams:
+        kw = dict(beamk=beamk, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
+        paths = {"off": lambda: E.evaluate(model, batches, **kw), "on": lambda: E.evaluate(model, batches, with_diversity=True, **kw)}
+        for fn in paths.values():                        # warm-up: code objects, allocator
+            fn()
+        got = paths["on"]()["diversity"]
+        torch.cuda.synchronize()
+        ms = {k: [] for k in paths}
+        for _ in range(a.repeats):                       # alternating rounds
+            for k, fn in paths.items():
+                ms[k].append(event_ms(fn)[0] / a.batches)
+        with torch.no_grad():
+            ann, _ = model.encode(batches[0][0])
+            o = model._beam_search_device(ann.contiguous(), beamk, a.max_gen_length, 1.0, "beam", 3, None, None, None, None, False)
+        ht, hl = E.finished_hypotheses(o, model.pad_idx)
+        alone = kernel_ms(ht, hl, o["fin_count"])
+
+        def host():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            tok, ln, cnt = ht.cpu().tolist(), hl.cpu().tolist(), o["fin_count"].cpu().tolist()
+            hyps = [[tok[b][f][:ln[b][f]] for f in range(cnt[b])] for b in range(len(cnt))]
+            t1 = time.perf_counter()
+            rows = [metrics.diversity_stats(h) for h in hyps]
+            t2 = time.perf_counter()
+            return (t2 - t0) * 1e3, (t2 - t1) * 1e3, rows, cnt
+
+        host_ms = [host() for _ in range(a.repeats)]
+        rows, cnt = host_ms[0][2], host_ms[0][3]
+        equal = E.diversity_statistics(ht, hl, o["fin_count"]).cpu().tolist() == rows
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        res = dict(beamk=beamk, images=a.images, references=R, batches=a.batches, max_gen_length=a.max_gen_length, precision=a.precision, repeats=a.repeats,
+                   evaluate_ms_per_batch={k: spread(v) for k, v in ms.items()}, increment_ms=med["on"] - med["off"], ratio=med["on"] / med["off"],
+                   host_copy_rebuild_stats_ms_per_batch=spread([t for t, _, _, _ in host_ms]), host_stats_only_ms_per_batch=spread([t for _, t, _, _ in host_ms]),
+                   kernel_ms=alone, kernel_at_limits_ms=limits, finished_hypotheses_mean=sum(cnt) / len(cnt), device_equals_host=equal, diversity=got)
+        if a.json:
+            print(json.dumps(res))
+            continue
+        print("beam %d, %d batches of %d images x %d references, max_gen_length %d, %s; %.1f finished hypotheses per image" %
+              (beamk, a.batches, a.images, R, a.max_gen_length, a.precision, res["finished_hypotheses_mean"]))
+        for k, label in (("off", "evaluate"), ("on", "evaluate(with_diversity=True)")):
+            extra = "" if k == "off" else "   %+.3f ms, %.4fx" % (res["increment_ms"], res["ratio"])
+            print("  %-44s %8.3f ms per batch (min %.3f, max %.3f)%s" % (label, med[k], min(ms[k]), max(ms[k]), extra))
+        for key, label in (("host_copy_rebuild_stats_ms_per_batch", "host: copy + lists + metrics.diversity_stats"), ("host_stats_only_ms_per_batch", "host: metrics.diversity_stats alone"),
+                           ("kernel_ms", "sat_caption_diversity, K = %d, width = %d" % (beamk, a.max_gen_length + 1)),
+                           ("kernel_at_limits_ms", "sat_caption_diversity, K = 32, width = 128")):
+            v = res[key]
+            print("  %-44s %8.3f ms (min %.3f, max %.3f)" % (label, v["median"], v["min"], v["max"]))
+        print("  device == host: %s; %s" % (equal, ", ".join("%s %s" % (k, ("%.4f" % v) if isinstance(v, float) else v) for k, v in got.items())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beams", type=int, nargs="+", default=[5, 20])
@@ -257,6 +330,7 @@ def main():
     ap.add_argument("--cider", action="store_true", help="measure CIDEr-D / ROUGE-L: val_batch_stats with and without corpus=, the host scorer, the build")
     ap.add_argument("--chrf", action="store_true", help="measure chrF: val_batch_stats with and without chrf=, the host scorer, the VocabChars build")
     ap.add_argument("--mbr", action="store_true", help="measure consensus reranking: val_batch_stats with LN and with MBR, the three launches, the host")
+    ap.add_argument("--diversity", action="store_true", help="measure the beam-diversity statistics: evaluate with and without with_diversity, the host, the kernel alone")
     ap.add_argument("--split-images", type=int, default=5000, help="--cider / --mbr: images in the corpus the table is built from")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -275,6 +349,8 @@ def main():
         return bench_chrf(a, model, batches, hp, T, R)
     if a.mbr:
         return bench_mbr(a, model, batches, hp, T, R)
+    if a.diversity:
+        return bench_diversity(a, model, batches, hp, T, R)
     for beamk in a.beams:
         kw = dict(beamk=beamk, max_gen_length=a.max_gen_length, temperature=1.0, rescore_method="LN")
 

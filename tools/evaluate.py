@@ -9,9 +9,12 @@ device once (``evaluation.VocabChars``) and every batch and trial is scored over
 --rescore-method MBR [--mbr-split train --mbr-reward 1.0 0.0 --mbr-alpha 0.0]: consensus reranking of every beam; the document
 frequencies come from the named split's references (one more ``ReferenceCorpus``, built once).  With --trials, "MBR" joins the
 notebook's rescore methods.
+--diversity: how different the finished hypotheses of an image are, over the whole split: distinct-1..4, mBLEU-1..4, the share of
+unique hypotheses, their number and the vocabulary the selected captions use (``evaluation.DiversityStats``; one pass only, not with
+--trials); printed, and written under "diversity" in --out.
 All work is in sat_amd/evaluation.py: a batch is decoded and scored on the device, one host read per pass.
     python tools/evaluate.py CHECKPOINT [--json DATASET.json] [--root IMAGE_DIR] [--split test] [--batch N] [--max-batches M]
-                             [--trials N --seed S --out results.csv]  [--cider]  [--chrf --chrf-beta 3.0]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
+                             [--trials N --seed S --out results.csv]  [--cider]  [--chrf --chrf-beta 3.0]  [--diversity]  [--beamk 5 --temperature 1.0 --rescore-method LN ...]
 """
 import argparse
 import csv
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--cider", action="store_true", help="also CIDEr-D and ROUGE-L against the document frequencies of the evaluated split")
     ap.add_argument("--chrf", action="store_true", help="also chrF over the characters of the vocabulary's spelling")
     ap.add_argument("--chrf-beta", type=float, default=3.0, help="chrF: the weight of recall over precision")
+    ap.add_argument("--diversity", action="store_true", help="also distinct-n, mBLEU, unique hypotheses and vocabulary over every finished hypothesis of the split")
     ap.add_argument("--beamk", type=int, default=5)
     ap.add_argument("--max-gen-length", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -67,6 +71,8 @@ def main():
     ap.add_argument("--ensemble-weights", type=float, nargs="+", default=None, help="one weight per model, CHECKPOINT first (default: uniform; normalised to sum 1)")
     ap.add_argument("--ensemble-combine", default="arithmetic", choices=["arithmetic", "geometric"], help="mix the models' distributions, or multiply them")
     a = ap.parse_args()
+    if a.diversity and a.trials > 0:
+        ap.error("--diversity goes with one pass over the split, not with --trials (the random search's table has no diversity columns)")
 
     ckpt = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     model = SAT(**dict(ckpt["hyper_parameters"]))
@@ -97,7 +103,7 @@ def main():
                 w = csv.DictWriter(f, fieldnames=cols)
                 w.writeheader(); w.writerows(rows)
         return
-    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, **(dict(chrf=chars, chrf_beta=a.chrf_beta) if a.chrf else {}), beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
+    res = E.evaluate(model, loader, max_batches=a.max_batches, seed=a.seed, corpus=corpus, with_diversity=a.diversity, **(dict(chrf=chars, chrf_beta=a.chrf_beta) if a.chrf else {}), beamk=a.beamk, max_gen_length=a.max_gen_length, temperature=a.temperature,
                      sample_method=a.sample_method, sample_topk=a.sample_topk, sample_topp=a.sample_topp, decoder_noise=a.decoder_noise,
                      rescore_method=None if a.rescore_method == "NONE" else a.rescore_method, rescore_reward=a.rescore_reward, topg=a.topg,
                      no_unk=a.no_unk, no_repeat_ngram=a.no_repeat_ngram, min_length=a.min_length, repetition_penalty=a.repetition_penalty,
@@ -105,6 +111,9 @@ def main():
     print("%d images in %d batches" % (res["images"], res["batches"]))
     for k in E.METRIC_KEYS + (E.CONSENSUS_KEYS if a.cider else ()) + (E.CHRF_KEYS if a.chrf else ()):
         print("%-18s batch mean %.6f   corpus %.6f" % (k, res["batch_mean"][k], res["corpus"][k]))
+    if a.diversity:
+        for k, v in res["diversity"].items():
+            print("%-18s %s" % (k, ("%.6f" % v) if isinstance(v, float) else v))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f)
