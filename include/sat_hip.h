@@ -19,7 +19,8 @@
  *     (step_offsets_host, teacher_host) are read while ENQUEUEING: they shape the launch sequence, so a captured train step
  *     is valid for that packing plan and those teacher-forcing flags (sat_amd/graph.py keys its graphs by them).  Tested under
  *     capture + replay: sat_beam_search_batched / _sampled (tests/test_gpu_inference.py) and the whole train step - encoder,
- *     sat_decoder_train_fwd / _bwd, the losses, sat_optimizer_step_dev - bit-equal to the eager step (tests/test_gpu_graph.py);
+ *     sat_decoder_train_fwd / _bwd, the losses, sat_optimizer_step_dev - bit-equal to the eager step (tests/test_gpu_graph.py),
+ *     likewise with sat_optimizer_step_avg_dev as its last launch (averaged weights, tests/test_gpu_averaging.py);
  *   - return 0 on success, non-zero otherwise with text in sat_last_error()
  *     (thread-local).  Nothing throws, nothing exits.
  */
@@ -1094,6 +1095,30 @@ int sat_optimizer_step(const sat_opt_tensor* tensors, const sat_opt_chunk* chunk
  * step count (bias corrections) and the clipping settings that the host writes there before every replay (sat_amd/graph.py)            */
 int sat_optimizer_step_dev(const sat_opt_tensor* tensors, const sat_opt_chunk* chunks, int32_t n_chunks, const sat_opt_hyper* hyper_dev,
                            const float* clip_coef, void* stream);
+/* ---- averaged weights (sat_amd/optim.py: kind="asgd", ema_decay=): the average is taken in the pass that updates p.
+ * `avg` is a DEVICE array of one float* per sat_opt_tensor (same order; NULL = this tensor keeps no average), each in the
+ * element order of its p.  After the update of an element:   a = (coef == 1) ? p : a + (p - a) * coef   (coef exactly 1
+ * stores p itself).  EMA over SGD / Adam / AdamW: coef = 1 - decay (1 on the first step: the average starts as a copy).
+ * SAT_OPT_ASGD is torch.optim.ASGD:  g += weight_decay * p;  p = p * (1 - lambd * eta) - eta * g  with the tensor's step size
+ * eta in sat_opt_tensor.lr (m and v are not read), coef = mu.  The kind is accepted by the _avg entry points only;
+ * sat_optimizer_step / _dev and their kernel are what they were.  8 more bytes per element than the plain step, no launch more. */
+#define SAT_OPT_ASGD 3
+typedef struct sat_opt_avg_hyper {
+    float coef;                /* in [0, 1]                                             */
+    float lambd;               /* >= 0; SAT_OPT_ASGD only                               */
+    int32_t flags, reserved;   /* 0                                                     */
+} sat_opt_avg_hyper;
+/* validated on the host before the launch: null tables, coef outside [0, 1], lambd < 0, an unknown kind -> SAT_EINVAL */
+int sat_optimizer_step_avg(const sat_opt_tensor* tensors, float* const* avg, const sat_opt_chunk* chunks, int32_t n_chunks,
+                           const sat_opt_hyper* hyper, const sat_opt_avg_hyper* avg_hyper, const float* clip_coef, void* stream);
+/* both hyper blocks in DEVICE memory (graph replay, as sat_optimizer_step_dev).  The host cannot read them here, so only the
+ * tables are validated: the caller checks coef / lambd / kind before it writes them there (FusedOptimizer does).          */
+int sat_optimizer_step_avg_dev(const sat_opt_tensor* tensors, float* const* avg, const sat_opt_chunk* chunks, int32_t n_chunks,
+                               const sat_opt_hyper* hyper_dev, const sat_opt_avg_hyper* avg_hyper_dev, const float* clip_coef,
+                               void* stream);
+/* p <-> its average, element by element, for every tensor whose avg entry is not NULL (g, m, v, lr of the table are not
+ * read); shadow_bf16, where set, is rewritten from the values that now sit in p.  Twice restores every bit.              */
+int sat_optimizer_swap(const sat_opt_tensor* tensors, float* const* avg, const sat_opt_chunk* chunks, int32_t n_chunks, void* stream);
 
 /* ---- input pipeline on device ------------------------------------------------------------------------
  * Replaces, per batch, the per-sample PIL / torchvision chain of train.py:208-233: T.RandomResizedCrop | T.Resize +

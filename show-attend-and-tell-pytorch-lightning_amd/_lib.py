@@ -73,6 +73,11 @@ class OptHyper(C.Structure):
                 ("clip_value", C.c_float)]
 
 
+class OptAvgHyper(C.Structure):
+    """sat_opt_avg_hyper (include/sat_hip.h)"""
+    _fields_ = [("coef", C.c_float), ("lambd", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BeamSampling(C.Structure):
     """sat_beam_sampling (include/sat_hip.h); sample_topp took the place of a reserved word: same size, same offsets"""
     _fields_ = [("method", C.c_int32), ("sample_topk", C.c_int32), ("seed", C.c_uint64), ("gumbel", C.c_void_p), ("decoder_noise", C.c_float),
@@ -328,7 +333,11 @@ SYMBOLS.update({
 SYMBOLS.update({"sat_optimizer_chunk_elems": (C.c_int32, []),
                 "sat_grad_clip_coef": (C.c_int, [_vp, _vp, _i32, _f, _vp, _vp, _vp]),
                 "sat_optimizer_step": (C.c_int, [_vp, _vp, _i32, C.POINTER(OptHyper), _vp, _vp]),
-                "sat_optimizer_step_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp])})
+                "sat_optimizer_step_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+                # averaged weights (optim.py: kind="asgd", ema_decay=): tensors, avg, chunks, n_chunks, ...
+                "sat_optimizer_step_avg": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(OptHyper), C.POINTER(OptAvgHyper), _vp, _vp]),
+                "sat_optimizer_step_avg_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+                "sat_optimizer_swap": (C.c_int, [_vp, _vp, _vp, _i32, _vp])})
 SYMBOLS.update({"sat_stem_tail_fwd_t": (C.c_int, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
                 "sat_stem_tail_bwd_t": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])})
 _u64 = C.c_uint64

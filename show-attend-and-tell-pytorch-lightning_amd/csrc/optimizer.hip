@@ -104,6 +104,109 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(const sat_opt_tenso
     }
 }
 
+// ---- averaged weights: the step above with one more stream, the average `a` of every element (ASGD's ax / an EMA), read and written in the
+// pass that updates p.  A kernel of its own, so that a step without averaging launches exactly the kernel above.
+// torch.optim.ASGD (single-tensor form): g += wd * p;  p *= 1 - lambd * eta;  p -= eta * g  (eta travels in the table's lr field)
+__device__ __forceinline__ void asgd_update(const sat_opt_hyper& h, float lambd, float eta, float wd, float coef, float& p, float g) {
+    g *= coef;
+    if (h.clip_value > 0.f) g = fminf(fmaxf(g, -h.clip_value), h.clip_value);
+    if (wd != 0.f) g = fmaf(wd, p, g);
+    p *= fmaf(-lambd, eta, 1.f);
+    p = fmaf(-eta, g, p);
+}
+__device__ __forceinline__ void avg_elem(const sat_opt_hyper& h, const sat_opt_avg_hyper& ah, float lr, float wd, float coef, float& p, float g,
+                                         float& m, float& v, float& a) {
+    if (h.kind == SAT_OPT_ASGD) asgd_update(h, ah.lambd, lr, wd, coef, p, g);
+    else opt_update(h, lr, wd, coef, p, g, m, v);
+    a = ah.coef == 1.f ? p : a + (p - a) * ah.coef;          // a coefficient of exactly 1 stores p itself: the average starts as a copy
+}
+
+__global__ __launch_bounds__(256) void optimizer_step_avg_kernel(const sat_opt_tensor* __restrict__ tensors, float* const* __restrict__ avg,
+                                                                 const sat_opt_chunk* __restrict__ chunks, sat_opt_hyper h,
+                                                                 const sat_opt_hyper* __restrict__ h_dev, sat_opt_avg_hyper ah,
+                                                                 const sat_opt_avg_hyper* __restrict__ ah_dev, const float* __restrict__ clip_coef) {
+    if (h_dev) { h = *h_dev; ah = *ah_dev; }
+    const sat_opt_chunk c = chunks[blockIdx.x];
+    const sat_opt_tensor t = tensors[c.tensor];
+    float* const ta = avg[c.tensor];
+    const long end = (c.start + OPT_CHUNK < t.n) ? c.start + OPT_CHUNK : t.n;
+    const float coef = clip_coef ? clip_coef[0] : 1.f;
+    const float lr = t.lr, wd = t.weight_decay;
+    const bool asgd = h.kind == SAT_OPT_ASGD;
+    const bool has_m = !asgd && t.m != nullptr, has_v = !asgd && t.v != nullptr, has_a = ta != nullptr;
+    // the vector path needs every stream of the tensor 16-byte aligned: a parameter that is a view at an odd storage offset has a
+    // freshly allocated (aligned) average, and the other way round after a loaded checkpoint
+    const bool vec = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | (has_m ? reinterpret_cast<uintptr_t>(t.m) : 0) |
+                       (has_v ? reinterpret_cast<uintptr_t>(t.v) : 0) | reinterpret_cast<uintptr_t>(ta)) & 15) == 0 &&
+                     (reinterpret_cast<uintptr_t>(t.shadow_bf16) & 7) == 0;
+    long i = c.start;
+    if (vec) {
+        const long nv = (end - c.start) / 4;
+        for (long q = threadIdx.x; q < nv; q += 256) {
+            const long e = c.start + q * 4;
+            float4 p4 = *reinterpret_cast<const float4*>(t.p + e);
+            const float4 g4 = *reinterpret_cast<const float4*>(t.g + e);
+            float4 m4 = has_m ? *reinterpret_cast<const float4*>(t.m + e) : make_float4(0, 0, 0, 0);
+            float4 v4 = has_v ? *reinterpret_cast<const float4*>(t.v + e) : make_float4(0, 0, 0, 0);
+            float4 a4 = has_a ? *reinterpret_cast<const float4*>(ta + e) : make_float4(0, 0, 0, 0);
+            avg_elem(h, ah, lr, wd, coef, p4.x, g4.x, m4.x, v4.x, a4.x); avg_elem(h, ah, lr, wd, coef, p4.y, g4.y, m4.y, v4.y, a4.y);
+            avg_elem(h, ah, lr, wd, coef, p4.z, g4.z, m4.z, v4.z, a4.z); avg_elem(h, ah, lr, wd, coef, p4.w, g4.w, m4.w, v4.w, a4.w);
+            *reinterpret_cast<float4*>(t.p + e) = p4;
+            if (t.shadow_bf16) {
+                typedef __bf16 b4 __attribute__((ext_vector_type(4)));
+                b4 o; o[0] = (__bf16)p4.x; o[1] = (__bf16)p4.y; o[2] = (__bf16)p4.z; o[3] = (__bf16)p4.w;
+                *reinterpret_cast<b4*>(reinterpret_cast<__bf16*>(t.shadow_bf16) + e) = o;
+            }
+            if (has_m) *reinterpret_cast<float4*>(t.m + e) = m4;
+            if (has_v) *reinterpret_cast<float4*>(t.v + e) = v4;
+            if (has_a) *reinterpret_cast<float4*>(ta + e) = a4;
+        }
+        i = c.start + nv * 4;
+    }
+    for (i += threadIdx.x; i < end; i += 256) {
+        float p = t.p[i], m = has_m ? t.m[i] : 0.f, v = has_v ? t.v[i] : 0.f, a = has_a ? ta[i] : 0.f;
+        avg_elem(h, ah, lr, wd, coef, p, t.g[i], m, v, a);
+        t.p[i] = p;
+        if (t.shadow_bf16) reinterpret_cast<__bf16*>(t.shadow_bf16)[i] = (__bf16)p;
+        if (has_m) t.m[i] = m;
+        if (has_v) t.v[i] = v;
+        if (has_a) ta[i] = a;
+    }
+}
+
+// p <-> a for every tensor that keeps an average; the bf16 filter copy follows the values that now sit in p
+__global__ __launch_bounds__(256) void optimizer_swap_kernel(const sat_opt_tensor* __restrict__ tensors, float* const* __restrict__ avg,
+                                                             const sat_opt_chunk* __restrict__ chunks) {
+    const sat_opt_chunk c = chunks[blockIdx.x];
+    const sat_opt_tensor t = tensors[c.tensor];
+    float* const ta = avg[c.tensor];
+    if (!ta) return;
+    const long end = (c.start + OPT_CHUNK < t.n) ? c.start + OPT_CHUNK : t.n;
+    const bool vec = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(ta)) & 15) == 0 && (reinterpret_cast<uintptr_t>(t.shadow_bf16) & 7) == 0;
+    long i = c.start;
+    if (vec) {
+        const long nv = (end - c.start) / 4;
+        for (long q = threadIdx.x; q < nv; q += 256) {
+            const long e = c.start + q * 4;
+            const float4 p4 = *reinterpret_cast<const float4*>(t.p + e);
+            const float4 a4 = *reinterpret_cast<const float4*>(ta + e);
+            *reinterpret_cast<float4*>(t.p + e) = a4;
+            *reinterpret_cast<float4*>(ta + e) = p4;
+            if (t.shadow_bf16) {
+                typedef __bf16 b4 __attribute__((ext_vector_type(4)));
+                b4 o; o[0] = (__bf16)a4.x; o[1] = (__bf16)a4.y; o[2] = (__bf16)a4.z; o[3] = (__bf16)a4.w;
+                *reinterpret_cast<b4*>(reinterpret_cast<__bf16*>(t.shadow_bf16) + e) = o;
+            }
+        }
+        i = c.start + nv * 4;
+    }
+    for (i += threadIdx.x; i < end; i += 256) {
+        const float p = t.p[i], a = ta[i];
+        t.p[i] = a; ta[i] = p;
+        if (t.shadow_bf16) reinterpret_cast<__bf16*>(t.shadow_bf16)[i] = (__bf16)a;
+    }
+}
+
 }  // namespace sat
 
 using namespace sat;
@@ -140,6 +243,38 @@ int sat_optimizer_step_dev(const sat_opt_tensor* tensors, const sat_opt_chunk* c
     sat_opt_hyper none = {};
     hipLaunchKernelGGL(optimizer_step_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, chunks, none, hyper_dev, clip_coef);
     return launch_ok("optimizer_step_dev");
+}
+
+int sat_optimizer_step_avg(const sat_opt_tensor* tensors, float* const* avg, const sat_opt_chunk* chunks, int32_t n_chunks,
+                           const sat_opt_hyper* hyper, const sat_opt_avg_hyper* avg_hyper, const float* clip_coef, void* stream) {
+    if (!tensors || !avg || !chunks || !hyper || !avg_hyper) return fail(SAT_EINVAL, "optimizer_step_avg: null pointer");
+    SAT_REQUIRE(hyper->kind >= SAT_OPT_SGD && hyper->kind <= SAT_OPT_ASGD, "optimizer_step_avg: kind %d", hyper->kind);
+    SAT_REQUIRE(avg_hyper->coef >= 0.f && avg_hyper->coef <= 1.f, "optimizer_step_avg: coefficient %g outside [0, 1]", avg_hyper->coef);
+    SAT_REQUIRE(avg_hyper->lambd >= 0.f, "optimizer_step_avg: lambd %g is negative", avg_hyper->lambd);
+    SAT_REQUIRE(hyper->kind == SAT_OPT_SGD || hyper->kind == SAT_OPT_ASGD || (hyper->bias_correction1 > 0.f && hyper->bias_correction2_sqrt > 0.f),
+                "optimizer_step_avg: bias corrections must be positive");
+    if (n_chunks <= 0) return SAT_OK;
+    hipLaunchKernelGGL(optimizer_step_avg_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, avg, chunks, *hyper,
+                       (const sat_opt_hyper*)nullptr, *avg_hyper, (const sat_opt_avg_hyper*)nullptr, clip_coef);
+    return launch_ok("optimizer_step_avg");
+}
+
+int sat_optimizer_step_avg_dev(const sat_opt_tensor* tensors, float* const* avg, const sat_opt_chunk* chunks, int32_t n_chunks,
+                               const sat_opt_hyper* hyper_dev, const sat_opt_avg_hyper* avg_hyper_dev, const float* clip_coef, void* stream) {
+    if (!tensors || !avg || !chunks || !hyper_dev || !avg_hyper_dev) return fail(SAT_EINVAL, "optimizer_step_avg_dev: null pointer");
+    if (n_chunks <= 0) return SAT_OK;
+    sat_opt_hyper none = {};
+    sat_opt_avg_hyper anone = {};
+    hipLaunchKernelGGL(optimizer_step_avg_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, avg, chunks, none, hyper_dev, anone,
+                       avg_hyper_dev, clip_coef);
+    return launch_ok("optimizer_step_avg_dev");
+}
+
+int sat_optimizer_swap(const sat_opt_tensor* tensors, float* const* avg, const sat_opt_chunk* chunks, int32_t n_chunks, void* stream) {
+    if (!tensors || !avg || !chunks) return fail(SAT_EINVAL, "optimizer_swap: null pointer");
+    if (n_chunks <= 0) return SAT_OK;
+    hipLaunchKernelGGL(optimizer_swap_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, tensors, avg, chunks);
+    return launch_ok("optimizer_swap");
 }
 
 }

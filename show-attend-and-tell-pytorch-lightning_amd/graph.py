@@ -10,7 +10,9 @@ images) step exactly as fast as Python can issue them.  Every entry point of the
 - is captured once into a hipGraph (``torch.cuda.CUDAGraph``: stream capture + the caching allocator's private pool) and replayed afterwards:
 one graph launch per step.  What stays on the host each step is what the reference does on the host too (model.py:559-586, 614-626): the
 teacher-forcing epsilon and its CPU-generator draws (F7), the learning-rate recipe, the optimizer's step count -> bias corrections, which
-reach the replayed update kernel through device memory (``sat_optimizer_step_dev``).
+reach the replayed update kernel through device memory (``sat_optimizer_step_dev``; with averaged weights - ``opt="asgd"`` / ``ema_decay`` -
+``sat_optimizer_step_avg_dev``, whose averaging coefficient travels the same way).  ``swap_averaged()`` between two replays exchanges
+contents, not tensors: every address a graph has baked in stays valid and the bf16 filter copies are marked current, so no graph is dropped.
 
 A graph is valid for one launch sequence, so graphs are keyed by everything that shapes it: tensor shapes, the packing plan (caption
 lengths), the teacher-forcing flags, precision, the set of trainable parameters.  The first step with a new key runs eagerly (it also warms

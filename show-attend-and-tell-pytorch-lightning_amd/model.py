@@ -711,6 +711,15 @@ class SAT(SATDecoder, _Base):
             return self.optimizers()
         return self.__dict__.get("_sat_optimizer")
 
+    def averaged_weights(self):
+        """``with model.averaged_weights():`` evaluate, caption or save with the averaged weights (``opt="asgd"`` / ``ema_decay``) in the
+        parameters: ``FusedOptimizer.averaged_weights`` of the optimizer ``configure_optimizers`` built.  BatchNorm's running statistics are
+        not averaged."""
+        opt = self._train_optimizer()
+        if not hasattr(opt, "averaged_weights"):
+            raise RuntimeError("averaged_weights: configure_optimizers has not built a FusedOptimizer")
+        return opt.averaged_weights()
+
     def step_learning_rate(self, gstep):
         """model.py:614-626, run at the end of every ``training_step`` with the optimizer steps taken so far: linear warm-up of
         every group's LR from ``opt_init_lr`` while ``gstep < lr_warmup_steps``; afterwards the per-batch schedulers
@@ -932,13 +941,18 @@ class SAT(SATDecoder, _Base):
             params += [{"params": self.embedding.parameters(), "lr": hp.embedding_lr, "weight_decay": 0.0}]
         if hp.encoder_finetune_after > 0 and hp.encoder_lr > 0:          # F10: mirrored as written
             params += groups([self.encoder], hp.weight_decay, hp.encoder_lr)
-        if hp.opt not in ("sgd", "adam", "adamw"):
+        if hp.opt not in ("sgd", "adam", "adamw", "asgd"):
             raise ValueError("opt=%r" % (hp.opt,))
+        # averaged weights (optim.py): opt="asgd" is torch.optim.ASGD, ema_decay keeps an exponential moving average beside the other three
+        asgd = dict(lambd=getattr(hp, "asgd_lambd", 1e-4), alpha=getattr(hp, "asgd_alpha", 0.75), t0=getattr(hp, "asgd_t0", 1e6))
         if getattr(hp, "fused_optimizer", True):
             # one launch over every parameter tensor (csrc/optimizer.hip), gradient clipping of train.py:93-96 folded in
             from .optim import FusedOptimizer
             opt = FusedOptimizer(params, kind=hp.opt, lr=hp.decoder_lr, betas=(hp.adam_b1, hp.adam_b2), momentum=hp.momentum, nesterov=hp.nesterov,
-                                 grad_clip=getattr(hp, "grad_clip", None), clip_value=getattr(hp, "clip_value", 0.0))
+                                 grad_clip=getattr(hp, "grad_clip", None), clip_value=getattr(hp, "clip_value", 0.0),
+                                 ema_decay=getattr(hp, "ema_decay", 0.0), **asgd)
+        elif hp.opt == "asgd":
+            opt = torch.optim.ASGD(params, lr=hp.decoder_lr, **asgd)
         elif hp.opt == "sgd":
             opt = torch.optim.SGD(params, lr=hp.decoder_lr, momentum=hp.momentum, nesterov=hp.nesterov)
         elif hp.opt == "adam":

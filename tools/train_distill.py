@@ -7,7 +7,9 @@ student's encoder stays frozen unless --train-encoder; Adam with a constant --lr
     python tools/train_distill.py STUDENT.ckpt --teacher A.ckpt [B.ckpt ...] --out DISTILLED.ckpt [--weights 1 1 ...]
                                   [--combine arithmetic|geometric] [--alpha 0.5] [--temperature 2.0] [--targets references|teacher]
                                   [--beamk 3] [--max-gen-length 20] [--json DATASET.json] [--root IMAGE_DIR] [--steps 1000] [--batch N]
-                                  [--lr 1e-4] [--log-every 20] [--train-encoder]
+                                  [--lr 1e-4] [--log-every 20] [--train-encoder] [--ema-decay D]
+--ema-decay D keeps an exponential moving average of the trained weights in the optimizer step (``FusedOptimizer(ema_decay=D)``; DESIGN.md 5,
+"Averaged weights") and writes the AVERAGED weights into the checkpoint.
 """
 import argparse
 import os
@@ -22,6 +24,7 @@ from sat_amd import data as D  # noqa: E402
 from sat_amd import distill  # noqa: E402
 from sat_amd.ensemble import Ensemble  # noqa: E402
 from sat_amd.model import SAT  # noqa: E402
+from sat_amd.optim import FusedOptimizer  # noqa: E402
 
 
 def main():
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--log-every", type=int, default=20)
     ap.add_argument("--train-encoder", action="store_true")
+    ap.add_argument("--ema-decay", type=float, default=0.0, help="in (0, 1): save the exponential moving average of the weights (0 = off)")
     a = ap.parse_args()
 
     ckpt = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
@@ -61,7 +65,8 @@ def main():
     ds = D.CocoCaptionDataset(a.json or model.hparams.json, "train", root=a.root)
     loader = D.DeviceLoader(ds, a.batch or model.hparams.batch, D.BatchTransform(model.hparams.input_size, train=True), shuffle=True, workers=a.workers,
                             drop_last=True)
-    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=a.lr)
+    trained = [p for p in model.parameters() if p.requires_grad]
+    opt = FusedOptimizer(trained, kind="adam", lr=a.lr, ema_decay=a.ema_decay) if a.ema_decay else torch.optim.Adam(trained, lr=a.lr)
     step, logs = 0, []
     while step < a.steps:
         for batch in loader:
@@ -77,11 +82,15 @@ def main():
                 print("step %6d  loss %.5f  cross entropy %.5f  KL %.5f  accuracy %.4f" % (step, *m), flush=True)
             if step >= a.steps:
                 break
-    ckpt["state_dict"] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    if a.ema_decay:         # the averaged weights go into the checkpoint: swap them in, save, swap back (BatchNorm buffers are the live ones)
+        with opt.averaged_weights():
+            ckpt["state_dict"] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    else:
+        ckpt["state_dict"] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     ckpt["distill"] = dict(steps=step, teachers=list(a.teacher), weights=teacher.weights, combine=a.combine, alpha=a.alpha, temperature=a.temperature,
-                           targets=a.targets, beamk=a.beamk, max_gen_length=a.max_gen_length, lr=a.lr)
+                           targets=a.targets, beamk=a.beamk, max_gen_length=a.max_gen_length, lr=a.lr, ema_decay=a.ema_decay)
     torch.save(ckpt, a.out)
-    print("wrote %s" % a.out)
+    print("wrote %s%s" % (a.out, " (exponential moving average of the weights, decay %g)" % a.ema_decay if a.ema_decay else ""))
 
 
 if __name__ == "__main__":

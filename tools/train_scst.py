@@ -5,7 +5,9 @@ back-propagates the advantage-weighted log-likelihood (``SAT.scst_step``; DESIGN
 frozen unless --train-encoder; Adam with a constant --lr drives the parameters that train.
     python tools/train_scst.py CHECKPOINT --out TUNED.ckpt [--json DATASET.json] [--root IMAGE_DIR] [--steps 1000] [--samples 5]
                                [--baseline mean|greedy] [--reward-cider 1.0 --reward-rouge 0.0] [--max-gen-length 20] [--temperature 1.0]
-                               [--batch N] [--lr 5e-5] [--seed S] [--log-every 20] [--train-encoder]
+                               [--batch N] [--lr 5e-5] [--seed S] [--log-every 20] [--train-encoder] [--ema-decay D]
+--ema-decay D keeps an exponential moving average of the trained weights in the optimizer step (``FusedOptimizer(ema_decay=D)``; DESIGN.md 5,
+"Averaged weights") and writes the AVERAGED weights into the checkpoint.
 """
 import argparse
 import os
@@ -19,6 +21,7 @@ import sat_amd  # noqa: E402,F401
 from sat_amd import data as D  # noqa: E402
 from sat_amd import evaluation as E  # noqa: E402
 from sat_amd.model import SAT  # noqa: E402
+from sat_amd.optim import FusedOptimizer  # noqa: E402
 
 
 def main():
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--seed", type=int, default=None, help="step i samples with seed + i")
     ap.add_argument("--log-every", type=int, default=20)
     ap.add_argument("--train-encoder", action="store_true")
+    ap.add_argument("--ema-decay", type=float, default=0.0, help="in (0, 1): save the exponential moving average of the weights (0 = off)")
     a = ap.parse_args()
 
     ckpt = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
@@ -52,7 +56,8 @@ def main():
     loader = D.DeviceLoader(ds, a.batch or model.hparams.batch, D.BatchTransform(model.hparams.input_size, train=True), shuffle=True, workers=a.workers,
                             drop_last=True)
     corpus = E.ReferenceCorpus.from_dataset(ds).check()
-    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=a.lr)
+    trained = [p for p in model.parameters() if p.requires_grad]
+    opt = FusedOptimizer(trained, kind="adam", lr=a.lr, ema_decay=a.ema_decay) if a.ema_decay else torch.optim.Adam(trained, lr=a.lr)
     step, logs = 0, []
     while step < a.steps:
         for batch in loader:
@@ -68,11 +73,15 @@ def main():
                 print("step %6d  loss %+.5f  reward %.4f  baseline %.4f  |advantage| %.4f  words %.2f" % (step, *m), flush=True)
             if step >= a.steps:
                 break
-    ckpt["state_dict"] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    if a.ema_decay:         # the averaged weights go into the checkpoint: swap them in, save, swap back (BatchNorm buffers are the live ones)
+        with opt.averaged_weights():
+            ckpt["state_dict"] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    else:
+        ckpt["state_dict"] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     ckpt["scst"] = dict(steps=step, samples=a.samples, baseline=a.baseline, reward=(a.reward_cider, a.reward_rouge), max_gen_length=a.max_gen_length,
-                        temperature=a.temperature, lr=a.lr)
+                        temperature=a.temperature, lr=a.lr, ema_decay=a.ema_decay)
     torch.save(ckpt, a.out)
-    print("wrote %s" % a.out)
+    print("wrote %s%s" % (a.out, " (exponential moving average of the weights, decay %g)" % a.ema_decay if a.ema_decay else ""))
 
 
 if __name__ == "__main__":
