@@ -1549,33 +1549,4 @@ int sigmoid_bwd(const float* dy, const float* y, float* dpre, long n, hipStream_
     return launch_ok("sigmoid_bwd");
 }
 
-// ------------------------------------------------------------------ losses
-int ce_fwd(const float* logits, const int* targets, int P, int V, float smoothing, float* lse_rows, float* loss_rows, int* correct_rows, float* out, hipStream_t st) {
-    SAT_REQUIRE(P > 0 && V > 0, "ce_fwd: empty input (P=%d V=%d)", P, V);
-    SAT_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "ce_fwd: smoothing %g out of range", smoothing);
-    if (V % 4 == 0 && (uintptr_t)logits % 16 == 0) hipLaunchKernelGGL(ce_rows_kernel<4>, dim3(P), dim3(256), 0, st, logits, targets, V, smoothing, lse_rows, loss_rows, correct_rows);
-    else hipLaunchKernelGGL(ce_rows_kernel<1>, dim3(P), dim3(256), 0, st, logits, targets, V, smoothing, lse_rows, loss_rows, correct_rows);
-    SAT_TRY(launch_ok("ce_rows"));
-    hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, st, loss_rows, correct_rows, P, out);
-    return launch_ok("ce_finish");
-}
-int ce_bwd(const float* logits, const int* targets, const float* lse_rows, int P, int V, float smoothing, const float* gscale, float* dlogits, hipStream_t st) {
-    SAT_REQUIRE(P > 0 && V > 0, "ce_bwd: empty input");
-    if (V % 4 == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)dlogits % 16 == 0) hipLaunchKernelGGL(ce_grad_kernel<4>, dim3(P), dim3(256), 0, st, logits, targets, lse_rows, V, smoothing, 1.0f / (float)P, gscale, dlogits);
-    else hipLaunchKernelGGL(ce_grad_kernel<1>, dim3(P), dim3(256), 0, st, logits, targets, lse_rows, V, smoothing, 1.0f / (float)P, gscale, dlogits);
-    return launch_ok("ce_grad");
-}
-int ds_fwd(const float* alphas, int N, int T1, int L, float gamma, float* asum, float* part, float* out, hipStream_t st) {
-    SAT_REQUIRE(N > 0 && T1 > 0 && L > 0, "ds_fwd: empty input");
-    const int nb = cdiv((long)N * L, 256);
-    hipLaunchKernelGGL(ds_rows_kernel, dim3(nb), dim3(256), 0, st, alphas, asum, part, N, T1, L);
-    SAT_TRY(launch_ok("ds_rows"));
-    hipLaunchKernelGGL(ds_finish_kernel, dim3(1), dim3(256), 0, st, part, nb, gamma, (long)N * L, out);
-    return launch_ok("ds_finish");
-}
-int ds_bwd(const float* asum, const float* gscale, int N, int T1, int L, float gamma, float* dalphas, hipStream_t st) {
-    hipLaunchKernelGGL(ds_grad_kernel, dim3(cdiv((long)N * T1 * L, 256)), dim3(256), 0, st, asum, gscale, gamma, dalphas, N, T1, L);
-    return launch_ok("ds_grad");
-}
-
 }  // namespace sat

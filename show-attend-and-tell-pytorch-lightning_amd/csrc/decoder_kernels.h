@@ -1,7 +1,7 @@
 // Device kernels of the SAT attention-LSTM decoder (forward and backward).
 // Reference semantics: model.py:76-81 (InitLSTM), 94-109 (SoftAttention),
-// 125-131 (DeepOutput), 187-192 (beta), 510-548 (train_batch loop),
-// util.py:105-112 (LabelSmoothing), model.py:594 (doubly stochastic term).
+// 125-131 (DeepOutput), 187-192 (beta), 510-548 (train_batch loop).
+// The two losses (util.py:105-112, model.py:594) are in ce_loss.hip.
 //
 // Layout (all fp32, row-major):
 //   ann    (B, L, D)   annotations, one row per location -- NHWC encoder output viewed flat.
@@ -863,146 +863,6 @@ __global__ void dann_add_mean_kernel(float* __restrict__ dann, const float* __re
     if (e >= total) return;
     long b = e / ((long)L * D); int d = (int)(e % D);
     dann[e] += dmean[b * D + d] / (float)L;
-}
-
-// ------------------------------------------------------------------ losses
-// Label-smoothed cross entropy over packed rows (util.py:105-112).  One block per packed token row:
-// online log-sum-exp, row argmax (accuracy, model.py:596-597) and the row loss; ce_finish_kernel reduces
-// loss_rows in a fixed order.  The gradient is a second kernel so that autograd's grad_output scales it.
-// VEC = 4: 16-byte loads, four of them in flight per thread (V % 4 == 0, i.e. rows stay 16-byte aligned); VEC = 1: any V.
-// (The first version read 4 bytes per lane per trip round the online-softmax recurrence: 144 us for the 54 MB of C2's logits.)
-template <int VEC>
-__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target, int V,
-                                                      float smoothing, float* __restrict__ lse_rows,
-                                                      float* __restrict__ loss_rows, int* __restrict__ correct_rows) {
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const float* x = logits + (long)p * V;
-    __shared__ float s_m[4], s_s[4], s_t[4], s_b[4]; __shared__ int s_i[4];
-    float mx = -INFINITY, sum = 0.f, tot = 0.f; int bi = 0x7fffffff; float bv = -INFINITY;
-    if (VEC == 4) {
-        constexpr int U = 4;
-        const int V4 = V >> 2;
-        for (int v0 = tid; v0 < V4; v0 += 256 * U) {
-            float4 q[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 256 * u;
-                q[u] = v < V4 ? reinterpret_cast<const float4*>(x)[v] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 256 * u;
-                if (v >= V4) continue;
-                const float e[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {           // ascending index: the first maximum wins, as torch.argmax
-                    tot += e[i];
-                    if (e[i] > bv) { bv = e[i]; bi = 4 * v + i; }
-                }
-                lse_unit4(e, mx, sum);
-            }
-        }
-    } else {
-        for (int v = tid; v < V; v += 256) {
-            float xv = x[v];
-            tot += xv;
-            if (arg_before(xv, v, bv, bi)) { bv = xv; bi = v; }
-            lse_word(xv, mx, sum);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
-    wave_argbest(bv, bi);
-    if ((tid & 63) == 0) { s_t[tid >> 6] = tot; s_b[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-    lse_wave_put(mx, sum, s_m, s_s, tid);
-    __syncthreads();
-    if (tid == 0) {
-        float Tt = 0.f;
-        for (int k = 0; k < 4; ++k) Tt += s_t[k];
-        int Bi = bi;
-        argbest_merge<4>(bv, Bi, s_b, s_i);
-        const float lse = lse_block(s_m, s_s);
-        const int t = target[p];
-        float nll = lse - x[t];
-        float smooth = lse - Tt / (float)V;
-        lse_rows[p] = lse;
-        loss_rows[p] = (1.f - smoothing) * nll + smoothing * smooth;
-        correct_rows[p] = (Bi == t) ? 1 : 0;
-    }
-}
-// dlogits[p, v] = g/P * (softmax - smoothing/V - (1-smoothing)[v == target])
-template <int VEC>
-__global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ logits, const int* __restrict__ target, const float* __restrict__ lse_rows,
-                                                      int V, float smoothing, float inv_rows, const float* __restrict__ gscale, float* __restrict__ dlogits) {
-    const int p = blockIdx.x;
-    const float* x = logits + (long)p * V; float* g = dlogits + (long)p * V;
-    const float lse = lse_rows[p], sv = smoothing / (float)V, conf = 1.f - smoothing;
-    const float sc = inv_rows * (gscale ? gscale[0] : 1.f);
-    const int t = target[p];
-    if (VEC == 4) {
-        constexpr int U = 4;
-        const int V4 = V >> 2;
-        for (int v0 = threadIdx.x; v0 < V4; v0 += 256 * U) {
-            float4 q[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) { const int v = v0 + 256 * u; if (v < V4) q[u] = reinterpret_cast<const float4*>(x)[v]; }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 256 * u;
-                if (v >= V4) continue;
-                float4 o;
-                o.x = (__expf(q[u].x - lse) - sv - ((4 * v == t) ? conf : 0.f)) * sc;
-                o.y = (__expf(q[u].y - lse) - sv - ((4 * v + 1 == t) ? conf : 0.f)) * sc;
-                o.z = (__expf(q[u].z - lse) - sv - ((4 * v + 2 == t) ? conf : 0.f)) * sc;
-                o.w = (__expf(q[u].w - lse) - sv - ((4 * v + 3 == t) ? conf : 0.f)) * sc;
-                reinterpret_cast<float4*>(g)[v] = o;
-            }
-        }
-    } else {
-        for (int v = threadIdx.x; v < V; v += 256) g[v] = (__expf(x[v] - lse) - sv - ((v == t) ? conf : 0.f)) * sc;
-    }
-}
-
-// out[0] = mean(loss_rows), out[1] = #correct / P   (single block, fixed-order tree)
-__global__ void ce_finish_kernel(const float* __restrict__ loss_rows, const int* __restrict__ correct_rows, int P, float* __restrict__ out) {
-    __shared__ double s_l[256], s_c[256];
-    double s = 0.0; int c = 0;
-    for (int p = threadIdx.x; p < P; p += 256) { s += (double)loss_rows[p]; c += correct_rows[p]; }
-    s = block_tree_sum_d(s, s_l);
-    const int correct = (int)block_tree_sum_d((double)c, s_c);             // a count: exact in double in any order
-    if (threadIdx.x == 0) { out[0] = (float)(s / (double)P); out[1] = (float)correct / (float)P; }
-}
-
-// Doubly-stochastic term (model.py:594).  asum[i,l] = sum_t alphas[i,t,l]; part[block] = sum (1-asum)^2
-__global__ void ds_rows_kernel(const float* __restrict__ alphas, float* __restrict__ asum, float* __restrict__ part, int N, int T1, int L) {
-    __shared__ float s_p[256];
-    long e = (long)blockIdx.x * 256 + threadIdx.x;
-    float v = 0.f;
-    if (e < (long)N * L) {
-        long i = e / L; int l = (int)(e % L);
-        float s = 0.f;
-        for (int t = 0; t < T1; ++t) s += alphas[(i * T1 + t) * L + l];
-        asum[e] = s;
-        v = (1.f - s) * (1.f - s);
-    }
-    s_p[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) s_p[threadIdx.x] += s_p[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) part[blockIdx.x] = s_p[0];
-}
-__global__ void ds_finish_kernel(const float* __restrict__ part, int nparts, float gamma, long count, float* __restrict__ out) {
-    __shared__ double s_p[256];
-    double s = 0.0;
-    for (int p = threadIdx.x; p < nparts; p += 256) s += (double)part[p];
-    s = block_tree_sum_d(s, s_p);
-    if (threadIdx.x == 0) out[0] = gamma * (float)(s / (double)count);
-}
-// dalphas[i,t,l] = gscale[0] * gamma * 2 (asum[i,l] - 1) / (N L)   for every t
-__global__ void ds_grad_kernel(const float* __restrict__ asum, const float* __restrict__ gscale, float gamma, float* __restrict__ dalphas, int N, int T1, int L) {
-    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long)N * T1 * L) return;
-    long i = e / ((long)T1 * L); int l = (int)(e % L);
-    float g = gscale ? gscale[0] : 1.f;
-    dalphas[e] = g * gamma * 2.f * (asum[i * L + l] - 1.f) / (float)((long)N * L);
 }
 
 // ------------------------------------------------------------------ reductions for bias grads

@@ -6,9 +6,10 @@
 // One 256-thread block per row.  Sweep 1 reads the student's and every used teacher's row once (online log-sum-exps), sweep 2 reads
 // them again from the cache (the same block touched them a moment ago) and folds q, log q - s into one online (max, sum, weighted sum)
 // triple, so the row normaliser of c never needs a pass of its own; sweep 3, when the gradient is asked for, is the third touch.
-// Every sweep issues the loads of U units (a unit: VEC = 4 words of every row read, or 1 on the 4-byte path) before it works on any,
-// ce_rows_kernel's way of keeping loads in flight (the recurrences themselves are row_reduce.h's); the kernels are compiled for MC = 1, 2, 4, 8 members so that the per-member
-// registers are those of the members there are, and U shrinks as MC grows.
+// Every sweep issues the loads of U units (a unit: VEC = 4 words of every row read, or 1 on the 4-byte path) before it works on any:
+// row_reduce.h's row sweep, widened to the several rows of a unit (load_batch below stands on its load_unit; the recurrences are
+// row_reduce.h's as well).  The kernels are compiled for MC = 1, 2, 4, 8 members so that the per-member registers are those of the
+// members there are, and U shrinks as MC grows.
 #include <math.h>
 
 #include <type_traits>
@@ -27,33 +28,6 @@ struct DistillParams {
 };
 // units in flight per thread and sweep, by the member capacity the kernel is compiled for
 template <int MC> struct InFlight { static constexpr int U = MC <= 2 ? 4 : (MC <= 4 ? 2 : 1); };
-
-template <int VEC>
-__device__ __forceinline__ void load_unit(const float* __restrict__ x, int u, float (&e)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 q = reinterpret_cast<const float4*>(x)[u];
-        e[0] = q.x; e[1] = q.y; e[2] = q.z; e[3] = q.w;
-    } else {
-        e[0] = x[u];
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void store_unit(float* __restrict__ g, int u, const float (&e)[VEC]) {
-    if constexpr (VEC == 4) reinterpret_cast<float4*>(g)[u] = make_float4(e[0], e[1], e[2], e[3]);
-    else g[u] = e[0];
-}
-
-// one unit of words e * s into an online (max, sum of exp) pair (row_reduce.h).  The student's pair at tau and the teachers' pairs go
-// through this one function, so a teacher that is the student gets the student's bits.
-template <int VEC>
-__device__ __forceinline__ void lse_unit(const float (&e)[VEC], float s, float& mx, float& sum) {
-    if constexpr (VEC == 4) {
-        const float x[4] = {e[0] * s, e[1] * s, e[2] * s, e[3] * s};
-        lse_unit4(x, mx, sum);
-    } else {
-        lse_word(e[0] * s, mx, sum);
-    }
-}
 
 // U units of the student's row and of every read teacher's, all loads issued before any is used
 template <int VEC, int MC, int U>
@@ -259,18 +233,18 @@ __global__ __launch_bounds__(256) void distill_grad_kernel(const float* __restri
                       dlogits + (long)p * V, threadIdx.x);
 }
 
-// dlogits *= gscale[0], in place
+// dlogits *= gscale[0], in place: the whole array as slabs of 256 units, one per block and trip, each a (one-trip) row sweep
 template <int VEC>
-__global__ __launch_bounds__(256) void distill_scale_kernel(float* __restrict__ g, long units, const float* __restrict__ gscale) {
+__global__ __launch_bounds__(256) void distill_scale_kernel(float* g, long units, const float* __restrict__ gscale) {
     const float s = gscale[0];
-    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < units; u += (long)gridDim.x * 256) {
-        if constexpr (VEC == 4) {
-            float4 q = reinterpret_cast<float4*>(g)[u];
-            q.x *= s; q.y *= s; q.z *= s; q.w *= s;
-            reinterpret_cast<float4*>(g)[u] = q;
-        } else {
-            g[u] *= s;
-        }
+    for (long u0 = (long)blockIdx.x * 256; u0 < units; u0 += (long)gridDim.x * 256) {
+        float* slab = g + u0 * VEC;
+        row_sweep<VEC, 1, 256>(slab, (int)(units - u0 < 256 ? units - u0 : 256), threadIdx.x, [&](int u, const float (&e)[VEC]) {
+            float o[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) o[j] = e[j] * s;
+            store_unit<VEC>(slab, u, o);
+        });
     }
 }
 
@@ -301,8 +275,7 @@ void with_form(bool wide, int members, F&& f) {
         else if (members <= 4) f(vec, std::integral_constant<int, 4>{});
         else f(vec, std::integral_constant<int, SAT_ENSEMBLE_MAX>{});
     };
-    if (wide) by_members(std::integral_constant<int, 4>{});
-    else by_members(std::integral_constant<int, 1>{});
+    with_width(wide, by_members);
 }
 
 }  // namespace
@@ -326,10 +299,10 @@ static int distill_check(const char* what, const float* logits, const float* con
 
 // 16-byte accesses: V % 4 == 0 and every array a sweep touches starts 16-byte aligned (the teachers only when they are read)
 static bool distill_wide(const float* logits, const EnsembleArgs& a, int members, float alpha, int V, const float* dlogits) {
-    uintptr_t low = (uintptr_t)logits | (uintptr_t)dlogits;
+    bool wide = rows_wide(V, logits, dlogits);
     if (alpha != 0.f)
-        for (int i = 0; i < members; ++i) if (a.w[i] != 0.f) low |= (uintptr_t)a.z[i];
-    return V % 4 == 0 && low % 16 == 0;
+        for (int i = 0; i < members; ++i) if (a.w[i] != 0.f) wide = wide && rows_wide(V, a.z[i]);
+    return wide;
 }
 
 extern "C" {
@@ -362,11 +335,10 @@ int sat_distill_bwd(const float* logits, const float* const* teachers, const flo
     if (dlogits_from_fwd) {                     // the forward wrote the gradient: the scale and nothing more
         if (!gscale) return SAT_OK;
         const long n = (long)P * V;
-        const bool wide = n % 4 == 0 && (uintptr_t)dlogits % 16 == 0;
-        const long units = wide ? n / 4 : n;
-        const long blocks = (units + 255) / 256;
-        if (wide) hipLaunchKernelGGL(distill_scale_kernel<4>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, dlogits, units, gscale);
-        else hipLaunchKernelGGL(distill_scale_kernel<1>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, dlogits, units, gscale);
+        with_width(rows_wide(n, dlogits), [&](auto vec) {          // the whole array as one row of P * V words
+            const long units = n / decltype(vec)::value, blocks = (units + 255) / 256;
+            hipLaunchKernelGGL(distill_scale_kernel<decltype(vec)::value>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, dlogits, units, gscale);
+        });
         return launch_ok("distill_scale");
     }
     const EnsembleArgs a = ensemble_args(teachers, weights, members);

@@ -25,7 +25,7 @@ __device__ __forceinline__ RowMask row_mask(const int* __restrict__ masked_ids, 
 }
 
 // lse_rows[p] = logsumexp over the unmasked v of x[v] = logits[p, v] * inv_temp; logq_rows[p] = x[target] - lse (NaN for a target
-// that is out of range or masked).  One block per packed row, row_reduce.h's online log-sum-exp in ce_rows_kernel's two load forms.
+// that is out of range or masked).  One block per packed row, row_reduce.h's online log-sum-exp over its row sweep.
 template <int VEC>
 __global__ __launch_bounds__(256) void policy_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target, int V, float inv_temp,
                                                           const int* __restrict__ masked_ids, int n_first_rows, float* __restrict__ lse_rows,
@@ -35,32 +35,12 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(const float* __restric
     const RowMask mk = row_mask(masked_ids, p < n_first_rows);
     __shared__ float s_m[4], s_s[4];
     float mx = -INFINITY, sum = 0.f;
-    if (VEC == 4) {
-        constexpr int U = 4;
-        const int V4 = V >> 2;
-        for (int v0 = tid; v0 < V4; v0 += 256 * U) {
-            float4 q[U];
+    row_sweep<VEC, kSweepDepth<VEC>, 256>(x, V / VEC, tid, [&](int u, const float (&q)[VEC]) {
+        float e[VEC];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 256 * u;
-                q[u] = v < V4 ? reinterpret_cast<const float4*>(x)[v] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 256 * u;
-                if (v >= V4) continue;
-                float e[4] = {q[u].x * inv_temp, q[u].y * inv_temp, q[u].z * inv_temp, q[u].w * inv_temp};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (mk.has(4 * v + i)) e[i] = -INFINITY;
-                lse_unit4(e, mx, sum);
-            }
-        }
-    } else {
-        for (int v = tid; v < V; v += 256) {
-            if (mk.has(v)) continue;
-            lse_word(x[v] * inv_temp, mx, sum);
-        }
-    }
+        for (int j = 0; j < VEC; ++j) e[j] = mk.has(u * VEC + j) ? -INFINITY : q[j] * inv_temp;          // a -inf word carries no mass
+        lse_unit<VEC>(e, mx, sum);
+    });
     lse_wave_put(mx, sum, s_m, s_s, tid);
     __syncthreads();
     if (tid == 0) {
@@ -95,35 +75,20 @@ __global__ __launch_bounds__(256) void policy_grad_kernel(const float* __restric
     const float lse = lse_rows[p];
     const float sc = (gscale ? gscale[0] : 1.f) * scale * w * inv_temp;
     const int t = target[p];
-    if (w == 0.f) {
-        if (VEC == 4) { for (int v = tid; v < (V >> 2); v += 256) reinterpret_cast<float4*>(g)[v] = make_float4(0.f, 0.f, 0.f, 0.f); }
-        else { for (int v = tid; v < V; v += 256) g[v] = 0.f; }
+    if (w == 0.f) {                            // nothing is read, so this is a plain strided loop of stores and no sweep
+        const float zero[VEC] = {};
+        for (int u = tid; u < V / VEC; u += 256) store_unit<VEC>(g, u, zero);
         return;
     }
-    if (VEC == 4) {
-        constexpr int U = 4;
-        const int V4 = V >> 2;
-        for (int v0 = tid; v0 < V4; v0 += 256 * U) {
-            float4 q[U];
+    row_sweep<VEC, kSweepDepth<VEC>, 256>(x, V / VEC, tid, [&](int u, const float (&e)[VEC]) {
+        float o[VEC];
 #pragma unroll
-            for (int u = 0; u < U; ++u) { const int v = v0 + 256 * u; if (v < V4) q[u] = reinterpret_cast<const float4*>(x)[v]; }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 256 * u;
-                if (v >= V4) continue;
-                const float e[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                float o[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int c = 4 * v + i;
-                    o[i] = mk.has(c) ? 0.f : (__expf(e[i] * inv_temp - lse) - ((c == t) ? 1.f : 0.f)) * sc;
-                }
-                reinterpret_cast<float4*>(g)[v] = make_float4(o[0], o[1], o[2], o[3]);
-            }
+        for (int j = 0; j < VEC; ++j) {
+            const int c = u * VEC + j;
+            o[j] = mk.has(c) ? 0.f : (__expf(e[j] * inv_temp - lse) - ((c == t) ? 1.f : 0.f)) * sc;
         }
-    } else {
-        for (int v = tid; v < V; v += 256) g[v] = mk.has(v) ? 0.f : (__expf(x[v] * inv_temp - lse) - ((v == t) ? 1.f : 0.f)) * sc;
-    }
+        store_unit<VEC>(g, u, o);
+    });
 }
 
 // One block per image: the K sampled captions of image b are rows b * K .. b * K + K - 1.
@@ -193,10 +158,10 @@ int sat_policy_nll_fwd(const float* logits, const int32_t* targets, const float*
     SAT_TRY(policy_check("policy_nll_fwd", logits, targets, row_weight, lse_rows, masked_ids, out, P, V, inv_temperature, n_first_rows, scale));
     if (!logq_rows) return fail(SAT_EINVAL, "policy_nll_fwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (V % 4 == 0 && (uintptr_t)logits % 16 == 0)
-        hipLaunchKernelGGL(policy_rows_kernel<4>, dim3(P), dim3(256), 0, st, logits, targets, V, inv_temperature, masked_ids, n_first_rows, lse_rows, logq_rows);
-    else
-        hipLaunchKernelGGL(policy_rows_kernel<1>, dim3(P), dim3(256), 0, st, logits, targets, V, inv_temperature, masked_ids, n_first_rows, lse_rows, logq_rows);
+    with_width(rows_wide(V, logits), [&](auto vec) {
+        hipLaunchKernelGGL(policy_rows_kernel<decltype(vec)::value>, dim3(P), dim3(256), 0, st, logits, targets, V, inv_temperature, masked_ids, n_first_rows,
+                           lse_rows, logq_rows);
+    });
     SAT_TRY(launch_ok("policy_rows"));
     hipLaunchKernelGGL(policy_finish_kernel, dim3(1), dim3(256), 0, st, logq_rows, row_weight, P, scale, out);
     return launch_ok("policy_finish");
@@ -207,12 +172,10 @@ int sat_policy_nll_bwd(const float* logits, const int32_t* targets, const float*
                        void* stream) {
     SAT_TRY(policy_check("policy_nll_bwd", logits, targets, row_weight, lse_rows, masked_ids, dlogits, P, V, inv_temperature, n_first_rows, scale));
     hipStream_t st = (hipStream_t)stream;
-    if (V % 4 == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)dlogits % 16 == 0)
-        hipLaunchKernelGGL(policy_grad_kernel<4>, dim3(P), dim3(256), 0, st, logits, targets, row_weight, lse_rows, V, inv_temperature, masked_ids, n_first_rows,
-                           scale, gscale, dlogits);
-    else
-        hipLaunchKernelGGL(policy_grad_kernel<1>, dim3(P), dim3(256), 0, st, logits, targets, row_weight, lse_rows, V, inv_temperature, masked_ids, n_first_rows,
-                           scale, gscale, dlogits);
+    with_width(rows_wide(V, logits, dlogits), [&](auto vec) {
+        hipLaunchKernelGGL(policy_grad_kernel<decltype(vec)::value>, dim3(P), dim3(256), 0, st, logits, targets, row_weight, lse_rows, V, inv_temperature, masked_ids,
+                           n_first_rows, scale, gscale, dlogits);
+    });
     return launch_ok("policy_grad");
 }
 

@@ -1,15 +1,61 @@
-// Device cores shared by the kernels that reduce a vocabulary row (decoder_kernels.h, policy_loss.hip, distill_loss.hip): the online
-// log-sum-exp, the block arg-best and its pick loops, the ensemble's word, and the double fixed-order tree of the finish kernels.
+// Device cores shared by the kernels that walk a vocabulary row (decoder_kernels.h, ce_loss.hip, policy_loss.hip, distill_loss.hip,
+// temperature.hip): the row sweep and its two access widths, the online log-sum-exp, the block arg-best and its pick loops, the
+// ensemble's word, and the double fixed-order tree of the finish kernels.
 // The bits depend on the shape of the float expressions, so the two FMAs of the recurrence are spelled out (left to contraction, the
 // compiler fused them in one kernel and not in the next); change them here and every user moves together.  A file built with
-// -ffp-contract=off takes nothing from here but block_tree_sum_d.
+// -ffp-contract=off takes only what has no floating-point arithmetic of its own to contract: the row sweep (load_unit, store_unit,
+// row_sweep, rows_wide, with_width) and block_tree_sum_d.
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "../../include/sat_hip.h"
 #include "common.h"
 
 namespace sat {
+
+// ------------------------------------------------------------------ the row sweep: a packed row as units of VEC words
+// VEC = 4: one 16-byte access per unit (rows_wide: V % 4 == 0, i.e. every row stays 16-byte aligned); VEC = 1: any V, any base.
+template <int VEC>
+__device__ __forceinline__ void load_unit(const float* __restrict__ x, int u, float (&e)[VEC]) {
+    if constexpr (VEC == 4) {
+        const float4 q = reinterpret_cast<const float4*>(x)[u];
+        e[0] = q.x; e[1] = q.y; e[2] = q.z; e[3] = q.w;
+    } else {
+        e[0] = x[u];
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void store_unit(float* __restrict__ g, int u, const float (&e)[VEC]) {
+    if constexpr (VEC == 4) reinterpret_cast<float4*>(g)[u] = make_float4(e[0], e[1], e[2], e[3]);
+    else g[u] = e[0];
+}
+// units in flight per thread of a single-row sweep.  (One 4-byte load per trip round the online-softmax recurrence was 144 us for the
+// 54 MB of C2's logits, four 16-byte loads in flight 66 us.)  The 4-byte form stays at one, the loop it has always been.
+template <int VEC> constexpr int kSweepDepth = VEC == 4 ? 4 : 1;
+// One thread's share of a row of `units` units: it starts at unit `first` and steps by THREADS * U; every trip issues the loads of its
+// (up to U) units inside the row before body(u, e) runs on them in ascending u -- the order a thread-local recurrence sees is that of
+// a plain strided loop.  A unit outside the row is neither loaded nor passed on.
+template <int VEC, int U, int THREADS, typename Body>
+__device__ __forceinline__ void row_sweep(const float* x, int units, int first, Body&& body) {
+    for (int u0 = first; u0 < units; u0 += THREADS * U) {
+        float e[U][VEC];
+#pragma unroll
+        for (int k = 0; k < U; ++k) if (u0 + THREADS * k < units) load_unit<VEC>(x, u0 + THREADS * k, e[k]);
+#pragma unroll
+        for (int k = 0; k < U; ++k) if (u0 + THREADS * k < units) body(u0 + THREADS * k, e[k]);
+    }
+}
+// host: rows of V words take the 16-byte form when V % 4 == 0 and every array a sweep touches starts 16-byte aligned ...
+template <typename... T>
+inline bool rows_wide(long V, const T*... base) { return V % 4 == 0 && (((uintptr_t)base | ... | (uintptr_t)0) % 16 == 0); }
+// ... and f(VEC) gets the width as an integral constant, so that a launcher names its kernel once
+template <typename F>
+inline void with_width(bool wide, F&& f) {
+    if (wide) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 1>{});
+}
 
 // ------------------------------------------------------------------ online log-sum-exp of a row: a (max, sum of exp(x - max)) pair
 // one word.  A -inf word carries no mass and is skipped: with mx still -inf the difference would be NaN.
@@ -22,6 +68,23 @@ __device__ __forceinline__ void lse_unit4(const float (&e)[4], float& mx, float&
     const float m4 = fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3]));
     if (m4 > mx) { sum *= __expf(mx - m4); mx = m4; }          // exp(-inf) = 0 on the first trip
     if (mx != -INFINITY) sum += (__expf(e[0] - mx) + __expf(e[1] - mx)) + (__expf(e[2] - mx) + __expf(e[3] - mx));
+}
+// one unit of a sweep, of either width ...
+template <int VEC>
+__device__ __forceinline__ void lse_unit(const float (&e)[VEC], float& mx, float& sum) {
+    if constexpr (VEC == 4) lse_unit4(e, mx, sum);
+    else lse_word(e[0], mx, sum);
+}
+// ... and of the words e * s.  The student's pair at tau and the teachers' pairs of the distillation loss go through this one function,
+// so a teacher that is the student gets the student's bits.
+template <int VEC>
+__device__ __forceinline__ void lse_unit(const float (&e)[VEC], float s, float& mx, float& sum) {
+    if constexpr (VEC == 4) {
+        const float x[4] = {e[0] * s, e[1] * s, e[2] * s, e[3] * s};
+        lse_unit4(x, mx, sum);
+    } else {
+        lse_word(e[0] * s, mx, sum);
+    }
 }
 // the pairs of a wave: xor butterfly, every lane ends with the wave's pair.  LAST_UNFUSED: the last step rounds both products before
 // the add.  That is the rounding beam_scores_row has had since the compiler first packed the two multiplies of that step (and only

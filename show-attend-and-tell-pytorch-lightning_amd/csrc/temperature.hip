@@ -54,22 +54,10 @@ __global__ __launch_bounds__(256) void temperature_rowmax_kernel(const float* __
     if (p >= P) return;
     const float* x = logits + (long)p * V;
     float mx = -INFINITY;
-    if (VEC == 4) {
-        constexpr int U = 4;
-        const int V4 = V >> 2;
-        for (int v0 = lane; v0 < V4; v0 += 64 * U) {
-            float4 q[U];
+    row_sweep<VEC, kSweepDepth<VEC>, 64>(x, V / VEC, lane, [&](int, const float (&e)[VEC]) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int v = v0 + 64 * u;
-                q[u] = v < V4 ? reinterpret_cast<const float4*>(x)[v] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) mx = fmaxf(mx, fmaxf(fmaxf(q[u].x, q[u].y), fmaxf(q[u].z, q[u].w)));
-        }
-    } else {
-        for (int v = lane; v < V; v += 64) mx = fmaxf(mx, x[v]);
-    }
+        for (int j = 0; j < VEC; ++j) mx = fmaxf(mx, e[j]);
+    });
     mx = wave_max(mx);
     if (lane == 0) {
         const int t = target[p];
@@ -230,18 +218,18 @@ TempWs carve(char* ws, int P) {
     return w;
 }
 
-bool vec4(const float* logits, int V) { return V % 4 == 0 && (uintptr_t)logits % 16 == 0; }
-
 int launch_rowmax(const float* logits, const int* targets, int P, int V, const TempWs& w, hipStream_t st) {
-    if (vec4(logits, V)) hipLaunchKernelGGL(temperature_rowmax_kernel<4>, dim3(w.nb), dim3(256), 0, st, logits, targets, P, V, w.rowmax, w.xt);
-    else hipLaunchKernelGGL(temperature_rowmax_kernel<1>, dim3(w.nb), dim3(256), 0, st, logits, targets, P, V, w.rowmax, w.xt);
+    with_width(rows_wide(V, logits), [&](auto vec) {
+        hipLaunchKernelGGL(temperature_rowmax_kernel<decltype(vec)::value>, dim3(w.nb), dim3(256), 0, st, logits, targets, P, V, w.rowmax, w.xt);
+    });
     return launch_ok("temperature_rowmax");
 }
 
 template <int NT>
 void launch_rows_nt(const float* logits, int P, int V, const TempWs& w, const int* latch, hipStream_t st) {
-    if (vec4(logits, V)) hipLaunchKernelGGL((temperature_rows_kernel<NT, 4>), dim3(w.nb), dim3(256), 0, st, logits, w.rowmax, w.xt, P, V, w.coef, latch, w.part);
-    else hipLaunchKernelGGL((temperature_rows_kernel<NT, 1>), dim3(w.nb), dim3(256), 0, st, logits, w.rowmax, w.xt, P, V, w.coef, latch, w.part);
+    with_width(rows_wide(V, logits), [&](auto vec) {
+        hipLaunchKernelGGL((temperature_rows_kernel<NT, decltype(vec)::value>), dim3(w.nb), dim3(256), 0, st, logits, w.rowmax, w.xt, P, V, w.coef, latch, w.part);
+    });
 }
 
 // loss and derivative at the n temperatures of w.coef: one read of the logits, then the fixed-order reduction

@@ -215,6 +215,66 @@ def test_label_smoothing_kernel_vector_and_scalar_paths(M, P, V):
     assert abs(float(crit.last_accuracy) - acc) < 1e-6
 
 
+CE_BAND = 64           # floats of NaN on either side of dlogits
+
+
+def ce_kernels(x, t, smoothing, g, logits_off=0, dlogits_off=0):
+    """sat_ce_label_smooth_fwd / _bwd through the C ABI; logits and dlogits start the given number of floats off their 16-byte alignment,
+    and dlogits lies inside a NaN-filled buffer.  Returns (out, lse, row losses, correct flags, dlogits, the whole buffer, its first index)."""
+    import sat_amd  # noqa: F401
+    from sat_amd import _lib as L
+    lib = L.lib()
+    P, V = x.shape
+    xbuf = torch.empty(P * V + 4, dtype=torch.float32, device="cuda")
+    xv = xbuf[logits_off:logits_off + P * V].view(P, V)
+    xv.copy_(x)
+    buf = torch.full((P * V + 2 * CE_BAND + 4,), float("nan"), dtype=torch.float32, device="cuda")
+    lo = CE_BAND + dlogits_off
+    dl = buf[lo:lo + P * V].view(P, V)
+    assert xbuf.data_ptr() % 16 == 0 and buf.data_ptr() % 16 == 0
+    assert (xv.data_ptr() % 16 != 0) == (logits_off != 0) and (dl.data_ptr() % 16 != 0) == (dlogits_off != 0)
+    td = t.to(torch.int32).cuda()
+    gd = torch.tensor([g], dtype=torch.float32, device="cuda")
+    lse, rows, out = torch.empty(P, device="cuda"), torch.empty(P, device="cuda"), torch.empty(2, device="cuda")
+    correct = torch.empty(P, dtype=torch.int32, device="cuda")
+    L.check(lib.sat_ce_label_smooth_fwd(L.ptr(xv), L.ptr(td), P, V, smoothing, L.ptr(lse), L.ptr(rows), L.ptr(correct), L.ptr(out), L.stream_ptr()),
+            "sat_ce_label_smooth_fwd")
+    L.check(lib.sat_ce_label_smooth_bwd(L.ptr(xv), L.ptr(td), L.ptr(lse), P, V, smoothing, L.ptr(gd), L.ptr(dl), L.stream_ptr()), "sat_ce_label_smooth_bwd")
+    torch.cuda.synchronize()
+    return out.cpu(), lse.cpu(), rows.cpu(), correct.cpu(), dl.cpu(), buf.cpu(), lo
+
+
+@pytest.mark.parametrize("P,V", [(7, 10000), (5, 1003), (3, 4), (9, 4100), (2, 1), (3, 4096), (3, 1028)])
+def test_label_smoothing_kernels_alignment_and_guard_bands(P, V):
+    """sat_ce_label_smooth_fwd / _bwd on the row sweep's two widths: aligned, with the logits one float off their 16-byte alignment, and with
+    only dlogits off it (V % 4 == 0 then runs a 16-byte forward and a 4-byte gradient).  V = 4096: exactly one full trip of the 16-byte
+    sweep; 1028: 257 units, one lane takes a second load.  Loss, log-sum-exps and gradient against float64 torch on the CPU, tolerance 5e-6
+    relative to the largest entry (that of test_label_smoothing_kernel_vector_and_scalar_paths); the NaN bands round dlogits stay NaN; a
+    second run gives the same bits."""
+    torch.manual_seed(P * 131 + V)
+    x = (torch.randn(P, V) * 3.0)
+    if V >= 4:
+        x[0, V // 2] = x[0].max() + 1.0; x[0, V - 1] = x[0, V // 2]              # a tie: the first one counts
+    t = torch.randint(0, V, (P,)); t[0] = V // 2
+    xd = x.double().requires_grad_()
+    lp = torch.log_softmax(xd, -1)
+    ref_rows = 0.9 * (-lp.gather(1, t[:, None])[:, 0]) + 0.1 * (-lp.mean(-1))
+    ref = ref_rows.mean()
+    (ref * 1.7).backward()
+    ref_lse = torch.logsumexp(x.double(), -1)
+    acc = float((x.argmax(1) == t).float().mean())
+    for what, lo_x, lo_g in (("aligned", 0, 0), ("logits off", 1, 0), ("dlogits off", 0, 1)):
+        out, lse, rows, correct, dl, buf, lo = ce_kernels(x, t, 0.1, 1.7, lo_x, lo_g)
+        what = "P=%d V=%d %s: " % (P, V, what)
+        close(out[0], ref.detach().float(), tol=5e-6, what=what + "loss"); close(rows, ref_rows.detach(), tol=5e-6, what=what + "row losses")
+        close(lse, ref_lse, tol=5e-6, what=what + "lse"); close(dl, xd.grad.float(), tol=5e-6, what=what + "gradient")
+        assert abs(float(out[1]) - acc) < 1e-6 and bool((correct == (x.argmax(1) == t).int()).all()), what + "accuracy"
+        assert bool(torch.isnan(buf[:lo]).all()) and bool(torch.isnan(buf[lo + P * V:]).all()), what + "the guard band was written"
+        again = ce_kernels(x, t, 0.1, 1.7, lo_x, lo_g)
+        for a, b in zip((out, lse, rows, correct, dl), again[:5]):
+            assert torch.equal(a, b), what + "two runs differ"
+
+
 def test_attention_step_fwd_bound_exactly_as_integration_md(golden_dir):
     """INTEGRATION.md section 2, verbatim: a bare ctypes binding of sat_attention_precompute / sat_attention_step_fwd inside a module
     with the reference's SoftAttention signature, checked against fixture G1."""

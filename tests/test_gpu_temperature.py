@@ -59,9 +59,15 @@ def make_logits(kind, P, V, seed):
 def test_nll_at_matches_float64(P, V, kind):
     """V % 4 != 0 (97), 6400, 10000, P = 1, P not a multiple of the 4 rows of a workgroup (7, 301, 130, 5, 3), 1 and 8 temperatures
     in one call (T from 0.25 to 4); 8 temperatures in one call equal 8 single calls bit for bit"""
-    C = cal()
     x, y = make_logits(kind, P, V, seed=100 + P + V)
-    xg, yg = x.to(DEV), y.to(DEV)
+    check_nll_at(x, y, x.to(DEV), y.to(DEV), kind)
+
+
+def check_nll_at(x, y, xg, yg, kind):
+    """nll_at on the device tensors xg, yg (the host tensors x, y) at 8 temperatures against the float64 restatement, within the bound of
+    the module docstring"""
+    C = cal()
+    P, V = x.shape
     loss8, grad8 = C.nll_at(xg, yg, EIGHT)
     assert loss8.shape == (8,) and grad8.shape == (8,) and loss8.dtype == torch.float32 and loss8.is_cuda
     worst = 0.0
@@ -79,6 +85,20 @@ def test_nll_at_matches_float64(P, V, kind):
         assert el <= bl and eg <= bg
         worst = max(worst, el / bl, eg / bg)
     print("P=%d V=%d %s: worst err / bound = %.3f" % (P, V, kind, worst))
+
+
+@pytest.mark.parametrize("P,V", [(3, 1028), (7, 97), (5, 4)])
+def test_nll_at_with_logits_off_their_alignment(P, V):
+    """the logits start one float past a 16-byte boundary, so the rows take the 4-byte sweep whatever V is: V % 4 == 0 on that form
+    (1028: 257 16-byte units when aligned, one lane's second load) is run by nothing else.  The aligned call gives the same row maxima
+    and sums in another order, so both are held to the same bound."""
+    x, y = make_logits("plain", P, V, seed=100 + P + V)
+    buf = torch.empty(P * V + 4, dtype=torch.float32, device=DEV)
+    xg = buf[1:1 + P * V].view(P, V)
+    xg.copy_(x)
+    assert buf.data_ptr() % 16 == 0 and xg.data_ptr() % 16 == 4 and xg.is_contiguous()
+    check_nll_at(x, y, xg, y.to(DEV), "plain, logits one float off")
+    check_nll_at(x, y, x.to(DEV), y.to(DEV), "plain, aligned")
 
 
 def test_nll_at_accepts_more_than_eight_and_rejects_bad_input():
