@@ -151,6 +151,16 @@ int sat_decoder_train_bwd(const sat_decoder_dims* d, const sat_decoder_params* w
                           const float* dlogits_packed, const float* alphas /* forward output */, const float* dalphas,
                           const sat_decoder_params* g, float* dann, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same backward with the parameter gradients on a second stream.  Only dann lies on the way to the encoder backward; every field of `g`
+ * feeds the optimizer alone.  With `side_stream` and `event` (a hipStream_t and a hipEvent_t, both or neither) the launches that lead to dann
+ * are issued first on `stream`; `event` is recorded on `stream` behind the last kernel whose output a parameter gradient reads, `side_stream`
+ * waits for it once, and every launch that writes into `g` goes to `side_stream`, with a split-K / column-sum scratch of its own inside the
+ * workspace.  The call returns WITHOUT joining: dann is ordered on `stream`; the caller makes `stream` wait for `side_stream` before anything
+ * reads `g`, and keeps dlogits_packed, the annotations and the workspace alive until then.  With both NULL this is sat_decoder_train_bwd. */
+int sat_decoder_train_bwd_fork(const sat_decoder_dims* d, const sat_decoder_params* w, const sat_decoder_batch* b,
+                               const float* dlogits_packed, const float* alphas, const float* dalphas, const sat_decoder_params* g,
+                               float* dann, void* workspace, size_t workspace_bytes, void* side_stream, void* event, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * LabelSmoothing.forward (util.py:105-112) over packed rows.  out[0] = loss, out[1] = accuracy
  * (model.py:596-597).  scratch: P floats lse + P floats loss + P ints. */

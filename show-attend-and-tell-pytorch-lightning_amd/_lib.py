@@ -196,6 +196,9 @@ SYMBOLS = {
     "sat_decoder_train_bwd": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), C.POINTER(DecoderBatch),
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DecoderParams), C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sat_decoder_train_bwd_fork": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), C.POINTER(DecoderBatch),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DecoderParams), C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sat_ce_label_smooth_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "sat_ce_label_smooth_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p,

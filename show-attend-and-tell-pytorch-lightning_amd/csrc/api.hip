@@ -104,6 +104,19 @@ int sat_decoder_train_bwd(const sat_decoder_dims* d, const sat_decoder_params* w
     return decoder_bwd(*d, *w, *b, dlogits_packed, alphas, dalphas, *g, dann, (char*)workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int sat_decoder_train_bwd_fork(const sat_decoder_dims* d, const sat_decoder_params* w, const sat_decoder_batch* b, const float* dlogits_packed,
+                               const float* alphas, const float* dalphas, const sat_decoder_params* g, float* dann, void* workspace,
+                               size_t workspace_bytes, void* side_stream, void* event, void* stream) {
+    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "decoder_train_bwd_fork")); SAT_TRY(check_params(d, g, "decoder_train_bwd_fork(grads)")); SAT_TRY(check_batch(b));
+    if (!alphas || !dann || !workspace || (d->P > 0 && !dlogits_packed)) return fail(SAT_EINVAL, "decoder_train_bwd_fork: null input/output/workspace");
+    if ((side_stream != nullptr) != (event != nullptr)) return fail(SAT_EINVAL, "decoder_train_bwd_fork: side stream and event go together (got %s only)", side_stream ? "a stream" : "an event");
+    if (side_stream && side_stream == stream) return fail(SAT_EINVAL, "decoder_train_bwd_fork: the side stream is the caller's stream");
+    if (workspace_bytes < decoder_workspace_bytes(*d))
+        return fail(SAT_EINVAL, "decoder_train_bwd_fork: workspace %zu < %zu bytes", workspace_bytes, decoder_workspace_bytes(*d));
+    return decoder_bwd(*d, *w, *b, dlogits_packed, alphas, dalphas, *g, dann, (char*)workspace, workspace_bytes, (hipStream_t)stream, (hipStream_t)side_stream,
+                       (hipEvent_t)event);
+}
+
 int sat_ce_label_smooth_fwd(const float* logits, const int32_t* targets, int32_t P, int32_t V, float smoothing, float* lse_rows,
                             float* loss_rows, int32_t* correct_rows, float* out, void* stream) {
     if (!logits || !targets || !lse_rows || !loss_rows || !correct_rows || !out) return fail(SAT_EINVAL, "ce_label_smooth_fwd: null pointer");

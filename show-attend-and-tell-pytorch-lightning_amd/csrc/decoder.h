@@ -10,7 +10,8 @@ size_t decoder_workspace_bytes(const sat_decoder_dims& d);
 int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, float* logits, float* alphas,
                 char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,
-                const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st);
+                const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st,
+                hipStream_t side = nullptr, hipEvent_t fork_event = nullptr);      // side: where the parameter gradients go (no join), see decoder.hip
 // launch plan of one attention step (decoder.hip: attention_plan decides it, the launchers and sat_attention_step_plan read it)
 enum { ATT_OP_FWD = 0, ATT_OP_BWD = 1, ATT_OP_CONTEXT_BWD = 2 };
 enum { ATT_FORM_SPLIT = 0, ATT_FORM_SINGLE = 1 };

@@ -3,6 +3,9 @@
 // No allocation, no synchronisation: everything lives in the caller's workspace.
 #include "../../include/sat_hip.h"
 #include <stdlib.h>
+#include <map>
+#include <mutex>
+#include <utility>
 #include "decoder.h"
 #include "profile.h"
 #include "decoder_kernels.h"
@@ -25,6 +28,8 @@ struct Ws {
     float *SC, *DA;                                              // attention: raw scores / score gradients of one step (N, L)
     // backward scratch
     float *dA, *dHout, *dZout, *DZ, *DHC, *dXZ, *dHc, *dCc, *dU, *dwf_part, *dY, *colpart, *dinit_img, *df, *dmean, *slab;
+    float *dmean_rows;                                           // dropout > 0: d(mean rows) of the InitLSTM backward
+    float *colpart2, *slab2;                                     // scratch of decoder_bwd's leaf part when it runs on a side stream
     char *zero_begin, *zero_end;                                 // [dHout .. dwf_part]: what decoder_bwd zeroes in one memset
     long slab_elems;
 };
@@ -55,10 +60,11 @@ Ws layout(const sat_decoder_dims& d, char* base) {
     w.Wcat = (float*)take((size_t)HCW * d.n);
     w.bcat = (float*)take((size_t)HCW);
     w.Tok = (int*)take((size_t)T1 * N);
-    w.Udrop = w.mean_rows = w.f_rows = w.init_rows = w.df_rows = nullptr;
+    w.Udrop = w.mean_rows = w.f_rows = w.init_rows = w.df_rows = w.dmean_rows = nullptr;
     if (d.dropout > 0.f) {
         w.Udrop = (float*)take((size_t)(d.P > 0 ? d.P : 1) * d.m); w.mean_rows = (float*)take((size_t)N * d.D); w.f_rows = (float*)take((size_t)N * d.m);
         w.init_rows = (float*)take((size_t)N * 2 * d.n * NL); w.df_rows = (float*)take((size_t)N * d.m);
+        w.dmean_rows = (float*)take((size_t)N * d.D);
     }
     w.Wb_out = w.Ub = nullptr;
     if (d.precision && d.m % 64 == 0 && d.V % 8 == 0) {           // operands of the vocabulary projection for the direct-to-LDS GEMM
@@ -97,6 +103,9 @@ Ws layout(const sat_decoder_dims& d, char* base) {
     w.dmean = (float*)take((size_t)d.B * d.D);
     w.slab_elems = 8L << 20;   // 32 MiB of split-K partials
     w.slab = (float*)take((size_t)w.slab_elems);
+    // a second column-sum and split-K scratch: the leaf part of decoder_bwd on its side stream runs while the main stream uses the first
+    w.colpart2 = (float*)take((size_t)cdiv(maxrows, 256) * maxcols);
+    w.slab2 = (float*)take((size_t)w.slab_elems);
     w.total = off;
     return w;
 }
@@ -227,6 +236,20 @@ int attention_plan(int op, int R, int L, int D, int A, int hc_ld, int T1, unsign
     return SAT_OK;
 }
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-kernel maximum that stays set: raise it when a launch needs more than any launch of that
+// kernel on this device did before, not at every time step (four host calls a step, ~170 per train step otherwise)
+static int ensure_dynamic_lds(const void* kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> granted;
+    int dev = 0;
+    SAT_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = granted[std::make_pair(dev, kernel)];
+    if (bytes <= have) return SAT_OK;
+    SAT_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    have = bytes;
+    return SAT_OK;
+}
 static bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 static bool ann_bf16_enabled() { static const bool off = getenv("SAT_ANN_BF16") && !atoi(getenv("SAT_ANN_BF16")); return !off; }      // dev switch
@@ -238,8 +261,8 @@ template <int RN, typename TA>
 static int attention_fwd_split(hipStream_t st, const TA* ann, const float* U, const float* hc, int hc_ld, const float* wf, const int* lengths, int step,
                                float* alphas, int T1, float* Z, float* XZ, int B, int R, int L, int D, int A, float* sc, __bf16* xzb, const AttPlan& pl) {
     const size_t lds_s = pl.lds0, lds_c = pl.lds1;
-    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_scores_kernel<RN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_context_kernel<RN, TA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(attention_scores_kernel<RN>), lds_s));
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(attention_context_kernel<RN, TA>), lds_c));
     // algorithmic bytes (per image-step): scores read att_enc U (L x A fp32) and the R query rows, write R x L raw scores; context streams the
     // image's annotations (L x D) ONCE for its R captions, reads scores + gates, writes alphas, z and the gated context
     const double N = (double)B * R;
@@ -291,7 +314,7 @@ int launch_attention_fwd(hipStream_t st, const float* ann, const float* U, const
     const int RN = pl.rn;
 #define SAT_ATTF(VWV, RNV)                                                                                                                  \
     case RNV:                                                                                                                               \
-        SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fwd_kernel<VWV, RNV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(attention_fwd_kernel<VWV, RNV>), lds)); \
         hipLaunchKernelGGL((attention_fwd_kernel<VWV, RNV>), grid, dim3(ATTF_THREADS), lds, st, ann, U, hc, hc_ld, wf, lengths, step, alphas, T1, Z, XZ, R, L, D, A, dchunk); \
         break;
     if (vec) {
@@ -308,8 +331,8 @@ static int attention_bwd_split_t(hipStream_t st, const TA* ann, const float* U, 
                                  const float* alphas, const float* dalphas, int T1, const float* Zs, const float* dZ_out, const float* dXZ, float* DZ, float* dhc,
                                  int dhc_ld, float* dU, float* dwf_part, float* da, int B, int R, int L, int D, int A, __bf16* dhcb, const AttPlan& pl) {
     const size_t lds_a = pl.lds0, lds_t = pl.lds1;
-    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_dalpha_kernel<RN, TA>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_tanh_kernel<RN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(attention_bwd_dalpha_kernel<RN, TA>), lds_a));
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(attention_bwd_tanh_kernel<RN>), lds_t));
     // algorithmic bytes: dalpha streams the annotations once per image, reads the R gradient rows of z / gated z / the gate (3 x D) and z, writes dz and
     // d(alpha); tanh reads att_enc and d(alpha), alphas, the queries, and adds into dU (read + write)
     const double N = (double)B * R;
@@ -349,7 +372,7 @@ int launch_attention_bwd(hipStream_t st, const float* ann, const float* U, const
         case 4: attb = attention_bwd_kernel<4>; break; case 5: attb = attention_bwd_kernel<5>; break; case 6: attb = attention_bwd_kernel<6>; break;
         case 7: attb = attention_bwd_kernel<7>; break; default: attb = attention_bwd_kernel<8>; break;
     }
-    SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds0));
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(attb), pl.lds0));
     hipLaunchKernelGGL(attb, dim3(B), dim3(ATTB_THREADS), pl.lds0, st, ann, U, hc, hc_ld, wf, lengths, step, alphas, dalphas, T1, Zs, dZ_out, dXZ, DZ, dhc, dhc_ld,
                        dU, dwf_part, R, L, D, A);
     return launch_ok("attention_bwd");
@@ -528,10 +551,33 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
 }
 
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,
-                       const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st) {
+                       const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st,
+                       hipStream_t side, hipEvent_t fork_event) {
     Ws w = layout(d, ws);
     t_bf16_mfma = d.precision ? 1 : 0;
     SAT_REQUIRE(ws_bytes >= w.total, "decoder_bwd: workspace %zu < %zu bytes", ws_bytes, w.total);
+    SAT_REQUIRE(!side || fork_event, "decoder_bwd: side stream without event");
+    // Everything after the time loop is either CRITICAL (on the way to dann, which the encoder backward waits for: dU * att_enc, the
+    // attention context backward, the InitLSTM data gradients down to dmean, dann_add_mean) or LEAF (writes a parameter gradient in g.* and
+    // feeds nothing else: the k-major weight-gradient products, the column sums, dY and the embedding gradient, the bias copies; also the
+    // output layer's three parameter gradients, whose operands are complete before the loop).  Without a side stream both run interleaved
+    // on `st`, as they always have.  With one, the critical part is issued first on `st`, `fork_event` is recorded on `st` behind the last
+    // kernel whose output the leaf part reads (the InitLSTM df product), `side` waits for it once, and the leaf part is issued on `side` in
+    // its old order with a scratch set of its own.  The call does not join: the caller makes `st` wait for `side` before g.* is read.
+    // What the leaf part reads, and why nothing on `st` can change it between the fork and the caller's join:
+    //   dlogits, Uact / Udrop, H_all, Z, Y, XZ, Tok, ann, f / mean (f_rows / mean_rows), parameters   written by the forward pass or the caller only
+    //   dY      scattered dA before the loop (on st); from then on read and written by leaf launches only
+    //   DHC, DGU  written by the time loop; read by leaf products only
+    //   dU, dwf_part  accumulated by the time loop; dU is read by both parts (dann and g.att_enc), written by neither
+    //   dinit_img, df (init_rows, df_rows)  written by the critical InitLSTM chain BEFORE the event, never again
+    //   mean_rows  the critical chain used to put d(mean rows) back into it while g.init_f_w still wants the forward's values: it has a
+    //              buffer of its own now (dmean_rows)
+    //   emb_count / emb_offset / emb_cursor / emb_list, colpart2, slab2   leaf scratch; st keeps colpart and slab
+    // The critical launches after the event write dmean, dmean_rows and dann only.
+    const bool fork = side != nullptr;
+    const hipStream_t ls = fork ? side : st;                    // where the leaf part goes
+    Ws wl = w;                                                  // ... and the scratch its column sums and split-K products use
+    if (fork) { wl.colpart = w.colpart2; wl.slab = w.slab2; }
     const int N = d.B * d.R, T1 = d.T - 1, HCW = d.A + d.D + 4 * d.n, n = d.n, A = d.A, D = d.D, m = d.m, V = d.V, P = d.P;
     const int ts = live_steps(d, b);
     const int KR = ts * N;                              // rows of the time-major padded buffers that were touched
@@ -549,6 +595,28 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     if (NL > 1 && KR < T1 * N) SAT_TRY(dev_fill_bytes(st, w.DGU, 0, (size_t)(NL - 1) * T1 * N * 4 * n * 4));
 
     // ---- output layer, all packed rows at once (DeepOutput backward)
+    float* const lslab = wl.slab;
+    // leaf: output.output.weight / bias
+    auto leaf_out_w = [&]() -> int {
+        if (P > 0) {
+            SAT_TRY(gemm(ls, A_KMAJOR, B_KMAJOR, dlogits, V, d.dropout > 0.f ? w.Udrop : w.Uact, m, g.out_w, m, V, m, P, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, lslab, se));
+            if (g.out_b) SAT_TRY(colsum(ls, wl, dlogits, V, P, V, g.out_b));
+        } else {
+            SAT_TRY(dev_fill_bytes(ls, g.out_w, 0, (size_t)V * m * 4));
+            if (g.out_b) SAT_TRY(dev_fill_bytes(ls, g.out_b, 0, (size_t)V * 4));
+        }
+        return SAT_OK;
+    };
+    // leaf: output.hidden.weight / output.context.weight from the scattered dA; dY then becomes the embedding gradient's accumulator
+    auto leaf_out_hidden = [&]() -> int {
+        const float* H1 = Hs(1, top);
+        SAT_TRY(gemm(ls, A_KMAJOR, B_KMAJOR, w.dY, m, H1, n, g.out_hidden, n, m, n, KR, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, lslab, se));
+        if (d.deep_output)
+            SAT_TRY(gemm(ls, A_KMAJOR, B_KMAJOR, w.dY, m, w.Z, D, g.out_context, D, m, D, KR, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, lslab, se));
+        else
+            SAT_TRY(dev_fill_bytes(ls, w.dY, 0, (size_t)T1 * N * m * 4));     // shallow output does not see the embedding
+        return SAT_OK;
+    };
     if (P > 0) {
         SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dlogits, V, p.out_w, m, w.dA, m, P, m, V, 0, d.deep_output ? EPI_MUL_DTANH : EPI_NONE, nullptr,
                      nullptr, nullptr, w.Uact, m, 0, 0, slab, se));           // few output tiles, long reduction over the vocabulary: split-K
@@ -557,24 +625,17 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                                (unsigned long long)d.dropout_seed, 2u, 0L);
             SAT_TRY(launch_ok("output dropout bwd"));
         }
-        SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, dlogits, V, d.dropout > 0.f ? w.Udrop : w.Uact, m, g.out_w, m, V, m, P, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
-        if (g.out_b) SAT_TRY(colsum(st, w, dlogits, V, P, V, g.out_b));
+    }
+    if (!fork) SAT_TRY(leaf_out_w());
+    if (P > 0) {
         SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dA, m, p.out_hidden, n, w.dHout, n, P, n, m, 0, EPI_NONE, nullptr, nullptr, b.src_row));
         if (d.deep_output)
             SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dA, m, p.out_context, D, w.dZout, D, P, D, m, 0, EPI_NONE, nullptr, nullptr, b.src_row));
-    } else {
-        SAT_TRY(dev_fill_bytes(st, g.out_w, 0, (size_t)V * m * 4));
-        if (g.out_b) SAT_TRY(dev_fill_bytes(st, g.out_b, 0, (size_t)V * 4));
     }
     // dA in time-major padded rows (zeros for finished captions): operand of the weight-grad GEMMs and of dY
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(T1 * N), dim3(64), 0, st, w.dA, b.prow, w.dY, T1 * N, m);
     SAT_TRY(launch_ok("scatter dA"));
-    const float* H1 = Hs(1, top);
-    SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.dY, m, H1, n, g.out_hidden, n, m, n, KR, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
-    if (d.deep_output)
-        SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.dY, m, w.Z, D, g.out_context, D, m, D, KR, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
-    else
-        SAT_TRY(dev_fill_bytes(st, w.dY, 0, (size_t)T1 * N * m * 4));     // shallow output does not see the embedding
+    if (!fork) SAT_TRY(leaf_out_hidden());
 
     // ---- back through time
     static const int att_fused = getenv("SAT_ATT_FUSED") ? atoi(getenv("SAT_ATT_FUSED")) : 0;
@@ -616,72 +677,105 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
 
     // ---- weight gradients, batched over every executed step (reduction length KR = ts*N)
     auto wgrad = [&](const float* dy, long ldy, const float* x, long ldx, float* out, long ldo, int M, int Nn) {
-        return gemm(st, A_KMAJOR, B_KMAJOR, dy, ldy, x, ldx, out, ldo, M, Nn, KR, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se);
+        return gemm(ls, A_KMAJOR, B_KMAJOR, dy, ldy, x, ldx, out, ldo, M, Nn, KR, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, lslab, se);
     };
     const float* dG = w.DHC + A + D;
-    SAT_TRY(wgrad(w.DHC, HCW, Hs(0, top), n, g.att_dec, n, A, n));
-    SAT_TRY(wgrad(w.DHC + A, HCW, Hs(0, top), n, g.beta_w, n, D, n));
-    SAT_TRY(wgrad(dG, HCW, Hs(0, 0), n, g.w_hh, n, 4 * n, n));
-    for (int l = 1; l < NL; ++l) {
-        const float* dgu = DGUs(0, l);
-        SAT_TRY(wgrad(dgu, 4 * n, Hs(1, l - 1), n, g.up_w_ih[l - 1], n, 4 * n, n));
-        SAT_TRY(wgrad(dgu, 4 * n, Hs(0, l), n, g.up_w_hh[l - 1], n, 4 * n, n));
-        SAT_TRY(colsum(st, w, dgu, 4 * n, KR, 4 * n, g.up_b_ih[l - 1]));
-        SAT_TRY(dev_copy_bytes(st, g.up_b_hh[l - 1], g.up_b_ih[l - 1], (size_t)4 * n * 4));
+    // leaf: the parameters of the time loop, the embedding table, the attention parameters
+    auto leaf_loop_params = [&]() -> int {
+        SAT_TRY(wgrad(w.DHC, HCW, Hs(0, top), n, g.att_dec, n, A, n));
+        SAT_TRY(wgrad(w.DHC + A, HCW, Hs(0, top), n, g.beta_w, n, D, n));
+        SAT_TRY(wgrad(dG, HCW, Hs(0, 0), n, g.w_hh, n, 4 * n, n));
+        for (int l = 1; l < NL; ++l) {
+            const float* dgu = DGUs(0, l);
+            SAT_TRY(wgrad(dgu, 4 * n, Hs(1, l - 1), n, g.up_w_ih[l - 1], n, 4 * n, n));
+            SAT_TRY(wgrad(dgu, 4 * n, Hs(0, l), n, g.up_w_hh[l - 1], n, 4 * n, n));
+            SAT_TRY(colsum(ls, wl, dgu, 4 * n, KR, 4 * n, g.up_b_ih[l - 1]));
+            SAT_TRY(dev_copy_bytes(ls, g.up_b_hh[l - 1], g.up_b_ih[l - 1], (size_t)4 * n * 4));
+        }
+        SAT_TRY(colsum(ls, wl, w.DHC + A, HCW, KR, D, g.beta_b));
+        SAT_TRY(colsum(ls, wl, dG, HCW, KR, 4 * n, g.b_ih));
+        SAT_TRY(dev_copy_bytes(ls, g.b_hh, g.b_ih, (size_t)4 * n * 4));
+        SAT_TRY(wgrad(dG, HCW, w.Y, m, g.w_ih, m + D, 4 * n, m));
+        SAT_TRY(wgrad(dG, HCW, w.XZ, D, g.w_ih + m, m + D, 4 * n, D));
+        // embedding: dY = dA (deep output) + dG * W_ih[:, :m], scattered into the table (padding row skipped)
+        SAT_TRY(gemm(ls, A_ROW, B_KMAJOR, dG, HCW, p.w_ih, m + D, w.dY, m, KR, m, 4 * n, 1));
+        if (d.embedding_dropout > 0.f && KR > 0) {
+            hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)KR * m, 256)), dim3(256), 0, ls, w.dY, w.dY, (long)KR * m, m, d.embedding_dropout,
+                               (unsigned long long)d.dropout_seed, 1u, 0L);
+            SAT_TRY(launch_ok("embedding dropout bwd"));
+        }
+        if (KR > 0) {
+            SAT_TRY(dev_fill_bytes(ls, w.emb_count, 0, (size_t)V * 4));
+            hipLaunchKernelGGL(embedding_count_kernel, dim3(cdiv(KR, 256)), dim3(256), 0, ls, w.Tok, KR, V, d.padding_idx, w.emb_count);
+            hipLaunchKernelGGL(embedding_scan_kernel, dim3(1), dim3(1024), 0, ls, w.emb_count, V, w.emb_offset, w.emb_cursor);
+            hipLaunchKernelGGL(embedding_place_kernel, dim3(cdiv(KR, 256)), dim3(256), 0, ls, w.Tok, KR, V, d.padding_idx, w.emb_offset, w.emb_cursor, w.emb_list);
+            hipLaunchKernelGGL(embedding_sum_kernel, dim3(V), dim3(256), 0, ls, w.dY, w.Tok, w.emb_offset, w.emb_list, g.embedding, KR, m, d.padding_idx);
+            SAT_TRY(launch_ok("embedding gradient"));
+        } else SAT_TRY(dev_fill_bytes(ls, g.embedding, 0, (size_t)V * m * 4));
+        SAT_TRY(colsum(ls, wl, w.dwf_part, A, d.B, A, g.att_f));
+        return gemm(ls, A_KMAJOR, B_KMAJOR, w.dU, A, b.ann, D, g.att_enc, D, A, D, d.B * d.L, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, lslab, se);
+    };
+    // critical: the annotation gradient through att_enc and through the context
+    auto crit_dann = [&]() -> int {
+        SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dU, A, p.att_enc, D, dann, D, d.B * d.L, D, A));
+        return attention_context_bwd(alphas, w.DZ, b.lengths, dann, 1, d.B, d.R, T1, d.L, D, st);
+    };
+    // InitLSTM backward (the raw reshape is a reinterpretation: gradients of the repeated rows add up per image).  dropout > 0: the
+    // per-caption-row path (see decoder_fwd); else one row per image.  dinit -> df -> dmean is critical, the four parameter gradients are leaf.
+    const bool rows = d.dropout > 0.f;
+    const int n2 = 2 * n * NL, IR = rows ? N : d.B;
+    const float* dinit = rows ? w.init_rows : w.dinit_img;
+    float* dfp = rows ? w.df_rows : w.df;
+    auto crit_dinit = [&]() -> int {
+        if (rows) {
+            SAT_TRY(dev_copy_bytes(st, w.init_rows, w.dHc, (size_t)NL * N * n * 4));
+            return dev_copy_bytes(st, w.init_rows + (long)NL * N * n, w.dCc, (size_t)NL * N * n * 4);
+        }
+        hipLaunchKernelGGL(init_expand_bwd_kernel, dim3(cdiv((long)d.B * n2, 256)), dim3(256), 0, st, w.dHc, w.dCc, w.dinit_img, d.B, d.R, n * NL);
+        return launch_ok("init_expand_bwd");
+    };
+    auto leaf_init_i = [&]() -> int {
+        SAT_TRY(gemm(ls, A_KMAJOR, B_KMAJOR, dinit, n2, rows ? w.f_rows : w.f, m, g.init_i_w, m, n2, m, IR));
+        return colsum(ls, wl, dinit, n2, IR, n2, g.init_i_b);
+    };
+    auto crit_df = [&]() -> int { return gemm(st, A_ROW, B_KMAJOR, dinit, n2, p.init_i_w, m, dfp, m, IR, m, n2); };
+    auto leaf_init_f = [&]() -> int {
+        SAT_TRY(gemm(ls, A_KMAJOR, B_KMAJOR, dfp, m, rows ? w.mean_rows : w.mean, D, g.init_f_w, D, m, D, IR));
+        return colsum(ls, wl, dfp, m, IR, m, g.init_f_b);
+    };
+    auto crit_dmean = [&]() -> int {
+        if (rows) {
+            SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.df_rows, m, p.init_f_w, D, w.dmean_rows, D, N, D, m));          // d(mean rows)
+            hipLaunchKernelGGL(init_mean_rows_bwd_kernel, dim3(cdiv((long)d.B * D, 256)), dim3(256), 0, st, w.dmean_rows, w.dmean, d.B, d.R, D, d.dropout,
+                               (unsigned long long)d.dropout_seed);
+            SAT_TRY(launch_ok("init_mean_rows_bwd"));
+        } else {
+            SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.df, m, p.init_f_w, D, w.dmean, D, d.B, D, m));
+        }
+        const long tot = (long)d.B * d.L * D;
+        hipLaunchKernelGGL(dann_add_mean_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, dann, w.dmean, d.L, D, tot);
+        return launch_ok("dann_add_mean");
+    };
+    if (!fork) {          // one stream: the two parts interleaved, each launch where it has always been
+        SAT_TRY(leaf_loop_params());
+        SAT_TRY(crit_dann());
+        SAT_TRY(crit_dinit());
+        SAT_TRY(leaf_init_i());
+        SAT_TRY(crit_df());
+        SAT_TRY(leaf_init_f());
+        return crit_dmean();
     }
-    SAT_TRY(colsum(st, w, w.DHC + A, HCW, KR, D, g.beta_b));
-    SAT_TRY(colsum(st, w, dG, HCW, KR, 4 * n, g.b_ih));
-    SAT_TRY(dev_copy_bytes(st, g.b_hh, g.b_ih, (size_t)4 * n * 4));
-    SAT_TRY(wgrad(dG, HCW, w.Y, m, g.w_ih, m + D, 4 * n, m));
-    SAT_TRY(wgrad(dG, HCW, w.XZ, D, g.w_ih + m, m + D, 4 * n, D));
-    // embedding: dY = dA (deep output) + dG * W_ih[:, :m], scattered into the table (padding row skipped)
-    SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dG, HCW, p.w_ih, m + D, w.dY, m, KR, m, 4 * n, 1));
-    if (d.embedding_dropout > 0.f && KR > 0) {
-        hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)KR * m, 256)), dim3(256), 0, st, w.dY, w.dY, (long)KR * m, m, d.embedding_dropout,
-                           (unsigned long long)d.dropout_seed, 1u, 0L);
-        SAT_TRY(launch_ok("embedding dropout bwd"));
-    }
-    if (KR > 0) {
-        SAT_TRY(dev_fill_bytes(st, w.emb_count, 0, (size_t)V * 4));
-        hipLaunchKernelGGL(embedding_count_kernel, dim3(cdiv(KR, 256)), dim3(256), 0, st, w.Tok, KR, V, d.padding_idx, w.emb_count);
-        hipLaunchKernelGGL(embedding_scan_kernel, dim3(1), dim3(1024), 0, st, w.emb_count, V, w.emb_offset, w.emb_cursor);
-        hipLaunchKernelGGL(embedding_place_kernel, dim3(cdiv(KR, 256)), dim3(256), 0, st, w.Tok, KR, V, d.padding_idx, w.emb_offset, w.emb_cursor, w.emb_list);
-        hipLaunchKernelGGL(embedding_sum_kernel, dim3(V), dim3(256), 0, st, w.dY, w.Tok, w.emb_offset, w.emb_list, g.embedding, KR, m, d.padding_idx);
-        SAT_TRY(launch_ok("embedding gradient"));
-    } else SAT_TRY(dev_fill_bytes(st, g.embedding, 0, (size_t)V * m * 4));
-    // attention parameters and the annotation gradient
-    SAT_TRY(colsum(st, w, w.dwf_part, A, d.B, A, g.att_f));
-    SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.dU, A, b.ann, D, g.att_enc, D, A, D, d.B * d.L, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
-    SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dU, A, p.att_enc, D, dann, D, d.B * d.L, D, A));
-    SAT_TRY(attention_context_bwd(alphas, w.DZ, b.lengths, dann, 1, d.B, d.R, T1, d.L, D, st));
-    // InitLSTM backward (the raw reshape is a reinterpretation: gradients of the repeated rows add up per image)
-    if (d.dropout > 0.f) {                 // per-caption-row path (see decoder_fwd)
-        const int n2 = 2 * n * NL;
-        SAT_TRY(dev_copy_bytes(st, w.init_rows, w.dHc, (size_t)NL * N * n * 4));
-        SAT_TRY(dev_copy_bytes(st, w.init_rows + (long)NL * N * n, w.dCc, (size_t)NL * N * n * 4));
-        SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.init_rows, n2, w.f_rows, m, g.init_i_w, m, n2, m, N));
-        SAT_TRY(colsum(st, w, w.init_rows, n2, N, n2, g.init_i_b));
-        SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.init_rows, n2, p.init_i_w, m, w.df_rows, m, N, m, n2));
-        SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.df_rows, m, w.mean_rows, D, g.init_f_w, D, m, D, N));
-        SAT_TRY(colsum(st, w, w.df_rows, m, N, m, g.init_f_b));
-        SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.df_rows, m, p.init_f_w, D, w.mean_rows, D, N, D, m));          // d(mean rows), reuses the buffer
-        hipLaunchKernelGGL(init_mean_rows_bwd_kernel, dim3(cdiv((long)d.B * D, 256)), dim3(256), 0, st, w.mean_rows, w.dmean, d.B, d.R, D, d.dropout,
-                           (unsigned long long)d.dropout_seed);
-        SAT_TRY(launch_ok("init_mean_rows_bwd"));
-    } else {
-    const int n2 = 2 * n * NL;
-    hipLaunchKernelGGL(init_expand_bwd_kernel, dim3(cdiv((long)d.B * n2, 256)), dim3(256), 0, st, w.dHc, w.dCc, w.dinit_img, d.B, d.R, n * NL);
-    SAT_TRY(launch_ok("init_expand_bwd"));
-    SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.dinit_img, n2, w.f, m, g.init_i_w, m, n2, m, d.B));
-    SAT_TRY(colsum(st, w, w.dinit_img, n2, d.B, n2, g.init_i_b));
-    SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dinit_img, n2, p.init_i_w, m, w.df, m, d.B, m, n2));
-    SAT_TRY(gemm(st, A_KMAJOR, B_KMAJOR, w.df, m, w.mean, D, g.init_f_w, D, m, D, d.B));
-    SAT_TRY(colsum(st, w, w.df, m, d.B, m, g.init_f_b));
-    SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.df, m, p.init_f_w, D, w.dmean, D, d.B, D, m));
-    }
-    const long tot = (long)d.B * d.L * D;
-    hipLaunchKernelGGL(dann_add_mean_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, dann, w.dmean, d.L, D, tot);
-    return launch_ok("dann_add_mean");
+    SAT_TRY(crit_dann());
+    SAT_TRY(crit_dinit());
+    SAT_TRY(crit_df());
+    SAT_CHECK_HIP(hipEventRecord(fork_event, st));              // df is the last thing the leaf part reads that st writes
+    SAT_TRY(crit_dmean());
+    SAT_CHECK_HIP(hipStreamWaitEvent(side, fork_event, 0));
+    SAT_TRY(leaf_out_w());
+    SAT_TRY(leaf_out_hidden());
+    SAT_TRY(leaf_loop_params());
+    SAT_TRY(leaf_init_i());
+    return leaf_init_f();
 }
 
 
@@ -1396,10 +1490,10 @@ int attention_context_bwd(const float* alphas, const float* DZ, const int* lengt
     SAT_TRY(attention_plan(ATT_OP_CONTEXT_BWD, R, L, D, 0, 0, T1, 0u, pl, "attention_context_bwd"));
     const size_t lds = pl.lds0;
     if (pl.nq == 13) {
-        SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dann_from_context_kernel<13>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(dann_from_context_kernel<13>), lds));
         hipLaunchKernelGGL(dann_from_context_kernel<13>, dim3(B, cdiv(D, 256)), dim3(256), lds, st, alphas, DZ, lengths, dann, accumulate, R, B * R, T1, L, D);
     } else {
-        SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dann_from_context_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(dann_from_context_kernel<16>), lds));
         hipLaunchKernelGGL(dann_from_context_kernel<16>, dim3(B, cdiv(D, 256)), dim3(256), lds, st, alphas, DZ, lengths, dann, accumulate, R, B * R, T1, L, D);
     }
     return launch_ok("dann_from_context");

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import encoder as E
 
 
 def _upload(t, dev):
@@ -174,11 +175,40 @@ def _check_param(name, t, shape):
         raise ValueError("decoder parameter %s must be contiguous fp32" % name)
 
 
+_leaf_events = {}          # device index -> (fork event, done event) of the decoder backward's side-stream fork
+_leaf_forks = [0]          # how many backward passes forked (tests and tools read it)
+
+
+def _leaf_side_events(dev, main):
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    evs = _leaf_events.get(key)
+    if evs is None:
+        evs = _leaf_events[key] = (torch.cuda.Event(), torch.cuda.Event())
+        evs[0].record(main)          # an event has no handle before its first record
+    return evs
+
+
+def _leaf_side_allowed(tens, n_distinct):
+    """what the fork cannot live with: anything that reads a parameter gradient on the main stream before the backward pass ends.  A tied
+    weight (autograd adds its two gradients as soon as both exist), a gradient already there (AccumulateGrad adds onto it), the bucket hooks
+    of a data-parallel exchange between several ranks, a stream capture (graph.py keeps the fork off by itself)."""
+    import torch.distributed as dist
+    if not E._DECODER_LEAF_SIDE or n_distinct < sum(t is not None for t in tens.values()):
+        return False
+    if any(t is not None and t.grad is not None for t in tens.values()):
+        return False
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return False
+    return not torch.cuda.is_current_stream_capturing()
+
+
 class DecoderTrainFn(torch.autograd.Function):
-    """logits_packed (P,V), alphas (N,T-1,L) = decoder(ann (B,L,D), captions) with BPTT backward."""
+    """logits_packed (P,V), alphas (N,T-1,L) = decoder(ann (B,L,D), captions) with BPTT backward.  ``leaf_side``: the caller knows that an
+    encoder backward with a side stream follows this Function's backward (``encoder.decoder_leaf_side_for``): the parameter gradients then go
+    to that stream and are joined when the backward pass ends, see ``backward``."""
 
     @staticmethod
-    def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, *params):
+    def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params):
         lib = L.lib()
         L.require_gpu(ann, caps_i32, *[p for p in params if p is not None])
         layers = layers_of(len(params))
@@ -216,7 +246,7 @@ class DecoderTrainFn(torch.autograd.Function):
         L.check(lib.sat_decoder_train_fwd(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(logits), L.ptr(alphas), L.ptr(ws), ws_bytes,
                                           L.stream_ptr()), "sat_decoder_train_fwd")
         ctx.dims, ctx.plan, ctx.teacher, ctx.ws, ctx.ws_bytes = dims, plan, teacher, ws, ws_bytes
-        ctx.caps, ctx.layers = caps_i32, layers
+        ctx.caps, ctx.layers, ctx.leaf_side = caps_i32, layers, bool(leaf_side)
         ctx.save_for_backward(ann, alphas, *[p for p in params if p is not None])
         ctx.present = [p is not None for p in params]
         return logits, alphas
@@ -249,9 +279,36 @@ class DecoderTrainFn(torch.autograd.Function):
                                src_row=plan.src_row.data_ptr(), step_offsets_host=plan.offsets_host.ctypes.data,
                                teacher_host=ctx.teacher.ctypes.data)
         w, g = _params_struct(tens, ctx.layers), _params_struct(grads, ctx.layers)
-        L.check(lib.sat_decoder_train_bwd(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(dlogits), L.ptr(alphas), L.ptr(dalphas),
-                                          C.byref(g), L.ptr(dann), L.ptr(ctx.ws), ctx.ws_bytes, L.stream_ptr()), "sat_decoder_train_bwd")
-        return (dann, None, None, None, None, None, None, None, None, None, *[grads[k] for k in names])
+        side_ptr = ev_ptr = None
+        if ctx.leaf_side and ctx.needs_input_grad[0] and _leaf_side_allowed(tens, len(taken)):
+            # dann is all the encoder backward waits for: the parameter gradients go to the encoder's side stream, ahead of its weight
+            # gradients, and the main stream waits for them when the backward pass ends (nothing may read a .grad before that)
+            dev = ann.device
+            main, side = torch.cuda.current_stream(dev), E.side_stream(dev)
+            fork_ev, done_ev = _leaf_side_events(dev, main)
+            side_ptr, ev_ptr = C.c_void_p(side.cuda_stream), C.c_void_p(fork_ev.cuda_event)
+        L.check(lib.sat_decoder_train_bwd_fork(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(dlogits), L.ptr(alphas), L.ptr(dalphas),
+                                               C.byref(g), L.ptr(dann), L.ptr(ctx.ws), ctx.ws_bytes, side_ptr, ev_ptr, L.stream_ptr()), "sat_decoder_train_bwd_fork")
+        if side_ptr is not None:
+            # what the side stream reads, and what it writes (autograd drops the gradient of a frozen parameter at once): the allocator must
+            # not hand these blocks out again before the side stream is done
+            for t in (ctx.ws, dlogits, ann, *grads.values()):
+                if t is not None:
+                    t.record_stream(side)
+            done_ev.record(side)
+            _leaf_forks[0] += 1
+
+            def join():
+                if E._JOIN_LAG is not None:          # dev (tools/join_lag.py)
+                    es, em = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    es.record(side); em.record(main)
+                    E._JOIN_LAG.append((em, es))
+                main.wait_event(done_ev)
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(join)          # runs when this backward pass has finished
+            except RuntimeError:                      # not called by the autograd engine
+                join()
+        return (dann, None, None, None, None, None, None, None, None, None, None, *[grads[k] for k in names])
 
 
 class LabelSmoothingFn(torch.autograd.Function):

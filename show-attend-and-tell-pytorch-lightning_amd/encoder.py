@@ -253,8 +253,38 @@ _WGRAD_SIDE_ONLY = int(os.environ.get("SAT_WGRAD_SIDE_ONLY", "0"))      # dev: w
 #: A version with ONE library call per fork and the tensors kept referenced until the join (no record_stream) measured SLOWER
 #: (C3 14.7 -> 17.6 .. 21 ms: the allocator then cycles through far more live blocks per backward).
 _WGRAD_SIDE_MIN_INPUT_PIXELS = int(os.environ.get("SAT_WGRAD_SIDE_MIN_INPUT_PIXELS", str(16 * 256 * 256)))
+#: the decoder's parameter gradients on the same side stream, ahead of the encoder's weight gradients (decoder.DecoderTrainFn.backward):
+#: like those they feed only the optimizer, and the encoder backward that follows them on the main stream starts with latency-bound kernels
+_DECODER_LEAF_SIDE = os.environ.get("SAT_DECODER_LEAF_SIDE", "1") != "0"
 _side_streams = {}
 _JOIN_LAG = None          # dev: a list collects (main-arrival, side-done) event pairs of every join
+
+
+def _side_batch(bf, pixels):
+    """the batches whose backward uses the side stream (see _WGRAD_SIDE_MIN_INPUT_PIXELS)"""
+    return bool(_WGRAD_STREAM and bf and pixels >= _WGRAD_SIDE_MIN_INPUT_PIXELS)
+
+
+def side_stream(device):
+    """the (first) side stream of ``device``: the one stream both backward passes fork to, so that its FIFO order puts the encoder's joins
+    behind the decoder's parameter gradients too"""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if not _side_streams.setdefault(key, []):
+        _side_streams[key].append(torch.cuda.Stream(device))
+    return _side_streams[key][0]
+
+
+def decoder_leaf_side_for(enc, img):
+    """True when the backward of ``enc(img)`` will fork its weight gradients to the side stream: the one place that knows both what the
+    decoder backward needs to know (its annotation gradient is wanted, and an encoder backward that overlaps the parameter gradients follows)"""
+    if not _DECODER_LEAF_SIDE or getattr(type(enc), "Fn", None) is not EncoderFn or not img.is_cuda or img.dim() != 4:
+        return False
+    if not (torch.is_grad_enabled() and enc.trunk_trainable):
+        return False
+    bf = enc.precision == "bf16"
+    N, _, H, W = img.shape
+    pairs = bf and _STEM_PAIRS and W % 2 == 0 and tuple(enc[1].weight.shape[1:]) == (3, 7, 7)
+    return _side_batch(bf, N * (H + 6) * ((W + 6) // 2) * 2 if pairs else N * H * W)
 
 
 class _SideQueue:
@@ -873,7 +903,7 @@ class EncoderFn(torch.autograd.Function):
                 acc += n; bounds.append(acc)
             tiles = None
             x0s = t["x0"].shape
-            queue = _SideQueue(d.device, _WGRAD_STREAM and bf and x0s[0] * x0s[1] * x0s[2] * (2 if t.get("stem_pairs") else 1) >= _WGRAD_SIDE_MIN_INPUT_PIXELS)
+            queue = _SideQueue(d.device, _side_batch(bf, x0s[0] * x0s[1] * x0s[2] * (2 if t.get("stem_pairs") else 1)))
             if t.get("loop") is not None:
                 arr, blocks, arena, nbytes, xin = t["loop"]
                 dests, per_block = [], []

@@ -146,7 +146,7 @@ class GraphedTrainStep:
             dctx = _Ctx()
             logits, alphas = Dk.DecoderTrainFn.forward(dctx, ann_bld, caps_i32, plan, teacher, bool(hp.deep_output), model.pad_idx, R,
                                                        int(model.sat_precision == "bf16"), getattr(hp, "embed_norm", None) or 0.0,
-                                                       model._dropout_args(None), *dec_params)
+                                                       model._dropout_args(None), False, *dec_params)      # no side-stream fork of the parameter gradients: no engine ends this backward
             targets = plan.pack(caps2[:, 1:].unsqueeze(-1)).squeeze(-1)
             cctx, sctx = _Ctx(), _Ctx()
             ce, acc = Dk.LabelSmoothingFn.forward(cctx, logits, targets.to(torch.int32), model.criterion.smoothing)
@@ -168,7 +168,7 @@ class GraphedTrainStep:
                 else:
                     grads[id(p)] = (p, g)
 
-            for p, g in zip(dec_params, douts[10:]):
+            for p, g in zip(dec_params, douts[11:]):
                 give(p, g)
             if any(p.requires_grad for p in enc_params):
                 eouts = enc.Fn.backward(ectx, dann.reshape(Bn, h, w, D).permute(0, 3, 1, 2))

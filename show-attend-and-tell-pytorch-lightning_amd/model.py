@@ -19,6 +19,7 @@ from torch.optim.lr_scheduler import MultiStepLR, ReduceLROnPlateau, Exponential
 from . import _lib as L
 from . import constraints
 from . import decoder as Dk
+from . import encoder as E
 from .modules import DeepOutput, Embedding, Gate, InitLSTM, LSTM, SoftAttention  # noqa: F401  (the reference's module names, model.py:66-131)
 from .encoder import get_encoder  # noqa: F401  (module-level name, as in the reference)
 
@@ -545,11 +546,12 @@ class SATDecoder(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,), generator=gen))
         return (p, pe, int(seed))
 
-    def train_decode(self, ann_bld, caps, lengths, epsilon=0, draw=None, with_loss=True, dropout_seed=None, teacher=None):
+    def train_decode(self, ann_bld, caps, lengths, epsilon=0, draw=None, with_loss=True, dropout_seed=None, teacher=None, leaf_side=False):
         """Decoder half of train_batch + the loss terms (model.py:487-557, 592-597).
 
         ann_bld (B, L, D) on the GPU; caps (B, R, T) int64; lengths (B, R) int64 (host or device).  ``teacher``: the scheduled-sampling
-        decisions of this batch when the caller has drawn them already (``PackPlan.teacher_flags``; graph.py keys its graphs by them)."""
+        decisions of this batch when the caller has drawn them already (``PackPlan.teacher_flags``; graph.py keys its graphs by them).
+        ``leaf_side``: ``ann_bld`` comes from an encoder whose backward forks to the side stream (``encoder.decoder_leaf_side_for``)."""
         B, R, T = caps.shape
         plan = Dk.PackPlan.cached(lengths.reshape(-1).cpu(), T, ann_bld.device)
         if teacher is None:
@@ -558,7 +560,7 @@ class SATDecoder(nn.Module):
         caps_i32 = caps2.to(device=ann_bld.device, dtype=torch.int32).contiguous()
         logits_packed, alphas = Dk.DecoderTrainFn.apply(ann_bld, caps_i32, plan, teacher, bool(self.hp.deep_output), self.pad_idx, R,
                                                         int(getattr(self, "sat_precision", "fp32") == "bf16"), getattr(self.hp, "embed_norm", None) or 0.0,
-                                                        self._dropout_args(dropout_seed), *self.param_list())
+                                                        self._dropout_args(dropout_seed), bool(leaf_side), *self.param_list())
         targets_packed = plan.pack(caps2[:, 1:].to(ann_bld.device).unsqueeze(-1)).squeeze(-1)
         if not with_loss:
             return dict(logits_packed=logits_packed, targets_packed=targets_packed, alphas=alphas, plan=plan)
@@ -667,7 +669,8 @@ class SAT(SATDecoder, _Base):
     def train_batch(self, batch, epsilon=0, draw=None, teacher=None):
         img, encoded_captions, lengths = batch
         ann_bld, _ = self.encode(img)
-        res = self.train_decode(ann_bld, encoded_captions, lengths, float(epsilon), draw, with_loss=False, teacher=teacher)
+        res = self.train_decode(ann_bld, encoded_captions, lengths, float(epsilon), draw, with_loss=False, teacher=teacher,
+                                leaf_side=E.decoder_leaf_side_for(self.encoder, img))
         plan = res["plan"]
         lp = PackedSequence(res["logits_packed"], plan.batch_sizes, plan.sorted_indices_dev, plan.unsorted_indices_dev)
         tp = PackedSequence(res["targets_packed"], plan.batch_sizes, plan.sorted_indices_dev, plan.unsorted_indices_dev)

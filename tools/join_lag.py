@@ -1,4 +1,5 @@
-"""Dev tool: how far the side stream (encoder weight gradients) lags behind the main stream at each join of one C2 backward."""
+"""Dev tool: how far the side stream (encoder weight gradients, and ahead of them the decoder's parameter gradients) lags behind the main
+stream at each join of one C2 backward.  The last pair of a step is the decoder's end-of-backward join (SAT_DECODER_LEAF_SIDE=0: absent)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
