@@ -1,4 +1,4 @@
-"""The shapes at which the decoder's sub-module entry points and search primitives are pinned (csrc/decoder_kernels.h, and csrc/ce_loss.hip
+"""The shapes at which the decoder's sub-module entry points and search primitives are pinned (csrc/decoder_kernels.h, csrc/decoder_search_kernels.h, and csrc/ce_loss.hip
 for the doubly-stochastic term, behind the sat_* names below), one table per entry point: the smallest shapes at which each loop, guard and branch of the kernels differs, each
 with the path it must take and why it is there.  test_decoder_entry_ref.py (no GPU) checks that the inputs drawn here make the
 float64 reference of tests/decoder_entry_ref.py notice a dropped last row, column, token occurrence or time step;

@@ -1,5 +1,6 @@
 """float64 restatements of the decoder's sub-module entry points and search primitives (csrc/decoder_kernels.h behind sat_colsum,
-sat_embedding_*, sat_lstm_cell_*, sat_deep_output_*, sat_init_lstm_*, sat_sigmoid_bwd, sat_topk and sat_beam_scores; csrc/ce_loss.hip
+sat_embedding_*, sat_lstm_cell_*, sat_deep_output_*, sat_init_lstm_*, sat_sigmoid_bwd; csrc/decoder_search_kernels.h behind sat_topk and
+sat_beam_scores; csrc/ce_loss.hip
 behind sat_doubly_stochastic_*), written out with torch double on the CPU, and the frames the GPU tests put their operands in.
 tests/decoder_entry_cases.py draws the inputs, test_decoder_entry_ref.py (no GPU) checks these functions against torch's own modules
 and the oracle, test_gpu_decoder_entry_points.py compares the kernels with them.
