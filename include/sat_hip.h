@@ -176,6 +176,33 @@ int sat_doubly_stochastic_fwd(const float* alphas, int32_t N, int32_t T1, int32_
 int sat_doubly_stochastic_bwd(const float* asum, const float* gscale, int32_t N, int32_t T1, int32_t L, float gamma,
                               float* dalphas, void* stream);
 
+/* ------------------------------------------------------------------ activation regularisation (Merity et al. 2017: AR / TAR)
+ * hidden (T1, N, n), time-major: hidden[t][i] = top-layer LSTM state of caption i after decode step t; live while t < lengths[i].  Rows
+ * that are not live are never read (they may hold anything) and never written.  With P = sum_i lengths[i] and
+ * Q = sum_i max(lengths[i] - 1, 0) (both given by the caller; 0 <= Q <= P <= N * T1):
+ *   out[0] = ar  = 1/(P n) sum_{live (t,i)}        |hidden[t][i]|^2                      (0 when P = 0)
+ *   out[1] = tar = 1/(Q n) sum_{live (t,i), t >= 1} |hidden[t][i] - hidden[t-1][i]|^2     (0 when Q = 0)
+ * Equal lengths: h.pow(2).mean() and (h[1:] - h[:-1]).pow(2).mean().  Squares and differences in fp32, sums in double in a fixed order
+ * (no atomics): bit-reproducible.  scratch: sat_activation_reg_scratch_bytes(N, T1, n) bytes, 8-byte aligned.
+ * _bwd ADDS gscale[0] * d ar / d hidden + gscale[1] * d tar / d hidden into the live rows of dH (T1, N, n); gscale: device, 2 floats.
+ * Every other element of dH keeps its bits. */
+size_t sat_activation_reg_scratch_bytes(int32_t N, int32_t T1, int32_t n);
+int sat_activation_reg_fwd(const float* hidden, const int32_t* lengths, int32_t N, int32_t T1, int32_t n, int64_t P, int64_t Q,
+                           void* scratch, float* out, void* stream);
+int sat_activation_reg_bwd(const float* hidden, const int32_t* lengths, int32_t N, int32_t T1, int32_t n, int64_t P, int64_t Q,
+                           const float* gscale, float* dH, void* stream);
+/* After sat_decoder_train_fwd on the same workspace: out (device, 2 floats) = ar / tar of that forward's top-layer states; P and Q
+ * come from d and b.step_offsets_host.  scratch: sat_activation_reg_scratch_bytes(B * R, T - 1, n) bytes. */
+int sat_decoder_train_reg_fwd(const sat_decoder_dims* d, const sat_decoder_batch* b, void* workspace, size_t workspace_bytes,
+                              void* scratch, float* out, void* stream);
+/* sat_decoder_train_bwd_fork plus reg_gscale (device, 2 floats: d loss / d ar, d loss / d tar) or NULL.  Given, the regularisers'
+ * direct gradient is added into the output layer's gradient of the top-layer states on `stream`, in front of the time loop, which
+ * carries it like any other; the parameter gradients on the side stream do not read it.  NULL: exactly sat_decoder_train_bwd_fork. */
+int sat_decoder_train_bwd_reg(const sat_decoder_dims* d, const sat_decoder_params* w, const sat_decoder_batch* b,
+                              const float* dlogits_packed, const float* alphas, const float* dalphas, const sat_decoder_params* g,
+                              float* dann, void* workspace, size_t workspace_bytes, void* side_stream, void* event, void* stream,
+                              const float* reg_gscale);
+
 /* ------------------------------------------------------------------ policy-gradient loss (self-critical sequence training; Rennie et al. 2017)
  * The REINFORCE surrogate over packed logits (P, V): every packed row p is one sampled action (targets[p]) with a weight of its own
  * (row_weight[p], the advantage of the caption it belongs to; any sign, 0 allowed).  The distribution differentiated is the one

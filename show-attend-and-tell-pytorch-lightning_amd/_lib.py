@@ -435,6 +435,14 @@ SYMBOLS.update({          # distillation (distill.py): teachers is a host array 
     "sat_distill_fwd": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i32, _i32, _vp, _i32, _i32, _f, _f, _f] + [_vp] * 8),
     "sat_distill_bwd": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i32, _i32, _vp, _i32, _i32, _f, _f, _f, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
 })
+SYMBOLS.update({          # activation regularisation (AR / TAR) of the decoder train step (decoder.DecoderTrainRegFn)
+    "sat_activation_reg_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "sat_activation_reg_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "sat_activation_reg_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "sat_decoder_train_reg_fwd": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderBatch), _vp, C.c_size_t, _vp, _vp, _vp]),
+    "sat_decoder_train_bwd_reg": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), C.POINTER(DecoderBatch), _vp, _vp, _vp,
+                                            C.POINTER(DecoderParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+})
 SYMBOLS.update({          # attention overlays (visualize.py)
     "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
     "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -117,6 +117,54 @@ int sat_decoder_train_bwd_fork(const sat_decoder_dims* d, const sat_decoder_para
                        (hipEvent_t)event);
 }
 
+int sat_decoder_train_bwd_reg(const sat_decoder_dims* d, const sat_decoder_params* w, const sat_decoder_batch* b, const float* dlogits_packed,
+                              const float* alphas, const float* dalphas, const sat_decoder_params* g, float* dann, void* workspace,
+                              size_t workspace_bytes, void* side_stream, void* event, void* stream, const float* reg_gscale) {
+    if (!reg_gscale)
+        return sat_decoder_train_bwd_fork(d, w, b, dlogits_packed, alphas, dalphas, g, dann, workspace, workspace_bytes, side_stream, event, stream);
+    SAT_TRY(check_dims(d)); SAT_TRY(check_params(d, w, "decoder_train_bwd_reg")); SAT_TRY(check_params(d, g, "decoder_train_bwd_reg(grads)")); SAT_TRY(check_batch(b));
+    if (!alphas || !dann || !workspace || (d->P > 0 && !dlogits_packed)) return fail(SAT_EINVAL, "decoder_train_bwd_reg: null input/output/workspace");
+    if ((side_stream != nullptr) != (event != nullptr)) return fail(SAT_EINVAL, "decoder_train_bwd_reg: side stream and event go together (got %s only)", side_stream ? "a stream" : "an event");
+    if (side_stream && side_stream == stream) return fail(SAT_EINVAL, "decoder_train_bwd_reg: the side stream is the caller's stream");
+    if (workspace_bytes < decoder_workspace_bytes(*d))
+        return fail(SAT_EINVAL, "decoder_train_bwd_reg: workspace %zu < %zu bytes", workspace_bytes, decoder_workspace_bytes(*d));
+    return decoder_bwd(*d, *w, *b, dlogits_packed, alphas, dalphas, *g, dann, (char*)workspace, workspace_bytes, (hipStream_t)stream, (hipStream_t)side_stream,
+                       (hipEvent_t)event, reg_gscale);
+}
+
+int sat_decoder_train_reg_fwd(const sat_decoder_dims* d, const sat_decoder_batch* b, void* workspace, size_t workspace_bytes, void* scratch, float* out,
+                              void* stream) {
+    SAT_TRY(check_dims(d)); SAT_TRY(check_batch(b));
+    if (!workspace || !scratch || !out) return fail(SAT_EINVAL, "decoder_train_reg_fwd: null workspace/scratch/out");
+    if (workspace_bytes < decoder_workspace_bytes(*d))
+        return fail(SAT_EINVAL, "decoder_train_reg_fwd: workspace %zu < %zu bytes", workspace_bytes, decoder_workspace_bytes(*d));
+    return decoder_reg_fwd(*d, *b, (char*)workspace, workspace_bytes, scratch, out, (hipStream_t)stream);
+}
+
+static int check_activation_reg(const char* what, const void* hidden, const void* lengths, const void* p2, const char* n2, const void* p3, const char* n3,
+                                int32_t N, int32_t T1, int32_t n, int64_t P, int64_t Q) {
+    if (!hidden || !lengths || !p2 || !p3)
+        return fail(SAT_EINVAL, "%s: null pointer (%s)", what, !hidden ? "hidden" : !lengths ? "lengths" : !p2 ? n2 : n3);
+    if (N <= 0 || T1 <= 0 || n <= 0) return fail(SAT_EINVAL, "%s: non-positive size (N=%d T1=%d n=%d)", what, N, T1, n);
+    if (P < 0 || Q < 0 || Q > P || P > (int64_t)N * T1)
+        return fail(SAT_EINVAL, "%s: live counts P=%lld Q=%lld outside 0 <= Q <= P <= N*T1=%lld", what, (long long)P, (long long)Q, (long long)N * T1);
+    return SAT_OK;
+}
+size_t sat_activation_reg_scratch_bytes(int32_t N, int32_t T1, int32_t n) {
+    if (N <= 0 || T1 <= 0 || n <= 0) { fail(SAT_EINVAL, "activation_reg_scratch_bytes: non-positive size (N=%d T1=%d n=%d)", N, T1, n); return 0; }
+    return activation_reg_scratch_bytes(N, T1, n);
+}
+int sat_activation_reg_fwd(const float* hidden, const int32_t* lengths, int32_t N, int32_t T1, int32_t n, int64_t P, int64_t Q, void* scratch, float* out,
+                           void* stream) {
+    SAT_TRY(check_activation_reg("activation_reg_fwd", hidden, lengths, scratch, "scratch", out, "out", N, T1, n, P, Q));
+    return activation_reg_fwd(hidden, lengths, N, T1, n, (long)P, (long)Q, scratch, out, (hipStream_t)stream);
+}
+int sat_activation_reg_bwd(const float* hidden, const int32_t* lengths, int32_t N, int32_t T1, int32_t n, int64_t P, int64_t Q, const float* gscale, float* dH,
+                           void* stream) {
+    SAT_TRY(check_activation_reg("activation_reg_bwd", hidden, lengths, gscale, "gscale", dH, "dH", N, T1, n, P, Q));
+    return activation_reg_bwd(hidden, lengths, N, T1, n, (long)P, (long)Q, gscale, dH, (hipStream_t)stream);
+}
+
 int sat_ce_label_smooth_fwd(const float* logits, const int32_t* targets, int32_t P, int32_t V, float smoothing, float* lse_rows,
                             float* loss_rows, int32_t* correct_rows, float* out, void* stream) {
     if (!logits || !targets || !lse_rows || !loss_rows || !correct_rows || !out) return fail(SAT_EINVAL, "ce_label_smooth_fwd: null pointer");

@@ -11,7 +11,13 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                 char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,
                 const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st,
-                hipStream_t side = nullptr, hipEvent_t fork_event = nullptr);      // side: where the parameter gradients go (no join), see decoder.hip
+                hipStream_t side = nullptr, hipEvent_t fork_event = nullptr,       // side: where the parameter gradients go (no join), see decoder.hip
+                const float* reg_gscale = nullptr);                                // device (2): d loss / d (ar, tar), added into dHout in front of the time loop
+// ar / tar of the top-layer states the last decoder_fwd left in ws (activation_reg.hip)
+int decoder_reg_fwd(const sat_decoder_dims& d, const sat_decoder_batch& b, char* ws, size_t ws_bytes, void* scratch, float* out, hipStream_t st);
+size_t activation_reg_scratch_bytes(int N, int T1, int n);
+int activation_reg_fwd(const float* hidden, const int* lengths, int N, int T1, int n, long P, long Q, void* scratch, float* out, hipStream_t st);
+int activation_reg_bwd(const float* hidden, const int* lengths, int N, int T1, int n, long P, long Q, const float* gscale, float* dH, hipStream_t st);
 // launch plan of one attention step (decoder.hip: attention_plan decides it, the launchers and sat_attention_step_plan read it)
 enum { ATT_OP_FWD = 0, ATT_OP_BWD = 1, ATT_OP_CONTEXT_BWD = 2 };
 enum { ATT_FORM_SPLIT = 0, ATT_FORM_SINGLE = 1 };

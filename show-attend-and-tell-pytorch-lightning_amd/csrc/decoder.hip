@@ -559,9 +559,21 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     return flush_outputs(st, d, p, b, w, logits, b.step_offsets_host[pending], b.step_offsets_host[ts]);
 }
 
+// Q of the activation regularisers: the (t - 1, t) pairs of live steps = P minus the captions that run at step 0
+static long reg_pairs(const sat_decoder_batch& b, long P) { return P - (b.step_offsets_host[1] - b.step_offsets_host[0]); }
+
+int decoder_reg_fwd(const sat_decoder_dims& d, const sat_decoder_batch& b, char* ws, size_t ws_bytes, void* scratch, float* out, hipStream_t st) {
+    Ws w = layout(d, ws);
+    SAT_REQUIRE(ws_bytes >= w.total, "decoder_reg_fwd: workspace %zu < %zu bytes", ws_bytes, w.total);
+    const int N = d.B * d.R, T1 = d.T - 1;
+    SAT_REQUIRE(b.step_offsets_host[T1] == d.P, "decoder_reg_fwd: step_offsets[T-1]=%d != P=%d", b.step_offsets_host[T1], d.P);
+    const float* H1 = w.H_all + ((long)(d.layers - 1) * d.T + 1) * N * d.n;    // top layer's hidden state after each step, as flush_outputs reads it
+    return activation_reg_fwd(H1, b.lengths, N, T1, d.n, d.P, reg_pairs(b, d.P), scratch, out, st);
+}
+
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,
                        const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st,
-                       hipStream_t side, hipEvent_t fork_event) {
+                       hipStream_t side, hipEvent_t fork_event, const float* reg_gscale) {
     Ws w = layout(d, ws);
     t_bf16_mfma = d.precision ? 1 : 0;
     SAT_REQUIRE(ws_bytes >= w.total, "decoder_bwd: workspace %zu < %zu bytes", ws_bytes, w.total);
@@ -641,6 +653,8 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         if (d.deep_output)
             SAT_TRY(gemm(st, A_ROW, B_KMAJOR, w.dA, m, p.out_context, D, w.dZout, D, P, D, m, 0, EPI_NONE, nullptr, nullptr, b.src_row));
     }
+    // AR / TAR: their direct gradient with respect to the top-layer states joins the output layer's in dHout; the time loop carries it on
+    if (reg_gscale && P > 0) SAT_TRY(activation_reg_bwd(Hs(1, top), b.lengths, N, T1, n, P, reg_pairs(b, P), reg_gscale, w.dHout, st));
     // dA in time-major padded rows (zeros for finished captions): operand of the weight-grad GEMMs and of dY
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(T1 * N), dim3(64), 0, st, w.dA, b.prow, w.dY, T1 * N, m);
     SAT_TRY(launch_ok("scatter dA"));

@@ -209,6 +209,15 @@ class DecoderTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params):
+        return DecoderTrainFn._forward(ctx, False, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params)
+
+    @staticmethod
+    def backward(ctx, dlogits, dalphas):
+        return DecoderTrainFn._backward(ctx, dlogits, dalphas, None)
+
+    @staticmethod
+    def _forward(ctx, with_reg, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params):
+        """the body of both Functions; ``with_reg``: a third output, the (ar, tar) pair of the top-layer states (``DecoderTrainRegFn``)"""
         lib = L.lib()
         L.require_gpu(ann, caps_i32, *[p for p in params if p is not None])
         layers = layers_of(len(params))
@@ -249,10 +258,17 @@ class DecoderTrainFn(torch.autograd.Function):
         ctx.caps, ctx.layers, ctx.leaf_side = caps_i32, layers, bool(leaf_side)
         ctx.save_for_backward(ann, alphas, *[p for p in params if p is not None])
         ctx.present = [p is not None for p in params]
-        return logits, alphas
+        if not with_reg:
+            return logits, alphas
+        scratch = torch.empty(lib.sat_activation_reg_scratch_bytes(N, T - 1, n), dtype=torch.uint8, device=ann.device)
+        reg = torch.empty(2, dtype=torch.float32, device=ann.device)
+        L.check(lib.sat_decoder_train_reg_fwd(C.byref(dims), C.byref(batch), L.ptr(ws), ws_bytes, L.ptr(scratch), L.ptr(reg), L.stream_ptr()),
+                "sat_decoder_train_reg_fwd")
+        return logits, alphas, reg
 
     @staticmethod
-    def backward(ctx, dlogits, dalphas):
+    def _backward(ctx, dlogits, dalphas, dreg):
+        """``dreg``: the gradient of the (ar, tar) output, device (2), or None: then the launches of the plain backward and no other"""
         lib = L.lib()
         saved = list(ctx.saved_tensors)
         ann, alphas = saved[0], saved[1]
@@ -287,8 +303,14 @@ class DecoderTrainFn(torch.autograd.Function):
             main, side = torch.cuda.current_stream(dev), E.side_stream(dev)
             fork_ev, done_ev = _leaf_side_events(dev, main)
             side_ptr, ev_ptr = C.c_void_p(side.cuda_stream), C.c_void_p(fork_ev.cuda_event)
-        L.check(lib.sat_decoder_train_bwd_fork(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(dlogits), L.ptr(alphas), L.ptr(dalphas),
-                                               C.byref(g), L.ptr(dann), L.ptr(ctx.ws), ctx.ws_bytes, side_ptr, ev_ptr, L.stream_ptr()), "sat_decoder_train_bwd_fork")
+        if dreg is None:
+            L.check(lib.sat_decoder_train_bwd_fork(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(dlogits), L.ptr(alphas), L.ptr(dalphas),
+                                                   C.byref(g), L.ptr(dann), L.ptr(ctx.ws), ctx.ws_bytes, side_ptr, ev_ptr, L.stream_ptr()), "sat_decoder_train_bwd_fork")
+        else:
+            dreg = dreg.to(torch.float32).contiguous()       # read on the main stream only, in front of the time loop
+            L.check(lib.sat_decoder_train_bwd_reg(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(dlogits), L.ptr(alphas), L.ptr(dalphas),
+                                                  C.byref(g), L.ptr(dann), L.ptr(ctx.ws), ctx.ws_bytes, side_ptr, ev_ptr, L.stream_ptr(), L.ptr(dreg)),
+                    "sat_decoder_train_bwd_reg")
         if side_ptr is not None:
             # what the side stream reads, and what it writes (autograd drops the gradient of a frozen parameter at once): the allocator must
             # not hand these blocks out again before the side stream is done
@@ -309,6 +331,20 @@ class DecoderTrainFn(torch.autograd.Function):
             except RuntimeError:                      # not called by the autograd engine
                 join()
         return (dann, None, None, None, None, None, None, None, None, None, None, *[grads[k] for k in names])
+
+
+class DecoderTrainRegFn(torch.autograd.Function):
+    """``DecoderTrainFn`` with a third output ``reg`` (2,) on the device: the activation regularisers ``(ar, tar)`` of the top-layer LSTM
+    states (include/sat_hip.h, sat_activation_reg_fwd; DESIGN.md 5, "Activation regularisation").  Its gradient travels to
+    ``sat_decoder_train_bwd_reg`` as a device pointer: no host read on the way there or back."""
+
+    @staticmethod
+    def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params):
+        return DecoderTrainFn._forward(ctx, True, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params)
+
+    @staticmethod
+    def backward(ctx, dlogits, dalphas, dreg):
+        return DecoderTrainFn._backward(ctx, dlogits, dalphas, dreg)
 
 
 class LabelSmoothingFn(torch.autograd.Function):

@@ -15,8 +15,10 @@ reach the replayed update kernel through device memory (``sat_optimizer_step_dev
 contents, not tensors: every address a graph has baked in stays valid and the bf16 filter copies are marked current, so no graph is dropped.
 
 A graph is valid for one launch sequence, so graphs are keyed by everything that shapes it: tensor shapes, the packing plan (caption
-lengths), the teacher-forcing flags, precision, the set of trainable parameters.  The first step with a new key runs eagerly (it also warms
-every cache the capture must not touch: plans, split-K scratch, kernel attributes), the second one captures, later ones replay.  Anything
+lengths), the teacher-forcing flags, precision, the set of trainable parameters, the activation regularisers' coefficients (``ar_alpha``,
+``tar_beta``: the regularised step has two more launches forward and one more backward, and its dict carries ``"ar"`` / ``"tar"``).  The
+first step with a new key runs eagerly (it also warms every cache the capture must not touch: plans, split-K scratch, kernel
+attributes), the second one captures, later ones replay.  Anything
 the graph cannot express falls back to the eager step for that call: more than one process (the gradient all-reduce is launched from
 autograd hooks), gradient accumulation, dropout (its seed is a launch argument), a parameter changed or moved behind the graph's back.
 
@@ -102,7 +104,7 @@ class GraphedTrainStep:
         if self.sync is not None:
             self.sync.finish()
         self.opt.step()
-        return {"loss": loss.detach(), "accuracy": acc, "epsilon_tf": float(epsilon)}
+        return {"loss": loss.detach(), "accuracy": acc, "epsilon_tf": float(epsilon), **self.model._reg_metrics()}
 
     def _capture_stream(self, dev):
         if self._stream is None:
@@ -144,19 +146,30 @@ class GraphedTrainStep:
             caps_i32 = caps2.to(dtype=torch.int32).contiguous()
             dec_params = model.param_list()
             dctx = _Ctx()
-            logits, alphas = Dk.DecoderTrainFn.forward(dctx, ann_bld, caps_i32, plan, teacher, bool(hp.deep_output), model.pad_idx, R,
-                                                       int(model.sat_precision == "bf16"), getattr(hp, "embed_norm", None) or 0.0,
-                                                       model._dropout_args(None), False, *dec_params)      # no side-stream fork of the parameter gradients: no engine ends this backward
+            ar_alpha, tar_beta = model.reg_coefficients()
+            with_reg = bool(ar_alpha or tar_beta)               # the activation regularisers: DecoderTrainRegFn's third output, as SAT._step_losses
+            logits, alphas, *reg = Dk.DecoderTrainFn._forward(dctx, with_reg, ann_bld, caps_i32, plan, teacher, bool(hp.deep_output), model.pad_idx, R,
+                                                              int(model.sat_precision == "bf16"), getattr(hp, "embed_norm", None) or 0.0,
+                                                              model._dropout_args(None), False, *dec_params)      # no side-stream fork of the parameter gradients: no engine ends this backward
             targets = plan.pack(caps2[:, 1:].unsqueeze(-1)).squeeze(-1)
             cctx, sctx = _Ctx(), _Ctx()
             ce, acc = Dk.LabelSmoothingFn.forward(cctx, logits, targets.to(torch.int32), model.criterion.smoothing)
             model.criterion.last_accuracy = acc
             ds = Dk.DoublyStochasticFn.forward(sctx, alphas, float(hp.att_gamma))
             loss = ce + ds
+            dreg = None
+            if with_reg:
+                loss = model.add_reg_terms(loss, reg[0])
+                model.__dict__["_sat_last_reg"] = (reg[0][0], reg[0][1])
+                # d loss / d (ar, tar): the coefficients themselves, as autograd hands them to DecoderTrainRegFn.backward
+                dreg = torch.cat([torch.full((1,), ar_alpha, dtype=torch.float32, device=img.device),
+                                  torch.full((1,), tar_beta, dtype=torch.float32, device=img.device)])
+            else:
+                model.__dict__["_sat_last_reg"] = None
             one = torch.ones((), dtype=torch.float32, device=img.device)
             dlogits = Dk.LabelSmoothingFn.backward(cctx, one, None)[0]
             dalphas = Dk.DoublyStochasticFn.backward(sctx, one)[0]
-            douts = Dk.DecoderTrainFn.backward(dctx, dlogits, dalphas)
+            douts = Dk.DecoderTrainFn._backward(dctx, dlogits, dalphas, dreg)
             dann = douts[0]
             grads = {}
 
@@ -195,7 +208,7 @@ class GraphedTrainStep:
                 self.sync.finish()                        # one process: gradients produced elsewhere move into their bucket slices
             self.opt.step_device()
         ent.graph = g
-        ent.out = {"loss": out_loss, "accuracy": acc, "epsilon_tf": float(epsilon)}
+        ent.out = {"loss": out_loss, "accuracy": acc, "epsilon_tf": float(epsilon), **self.model._reg_metrics()}
         ent.grads = [(p, p.grad) for p in self._params if p.grad is not None]
         # module-level caches the launches read through raw pointers: keep THESE tensors alive even if the caches grow and drop them
         ent.keep = [list(E._slabs.values()), list(E._bn_scratch_buf.values()), Dk.PackPlan.cached(lengths.reshape(-1), caps.shape[-1], dev), teacher]
@@ -222,7 +235,7 @@ class GraphedTrainStep:
             self.stats["eager: " + why] += 1
             return self._eager(batch, epsilon, gstep, teacher)
         key = (tuple(img.shape), tuple(caps.shape), lengths.numpy().tobytes(), np.asarray(teacher, np.int32).tobytes(), float(epsilon),
-               model.sat_precision, model.training, self._params_sig())
+               model.sat_precision, model.training, self._params_sig(), model.reg_coefficients())
         stale = self._stale_copies()
         if stale:
             self._graphs.clear()                          # filter copies are about to be remade: every graph points at the old ones

@@ -123,6 +123,10 @@ class SATDecoder(nn.Module):
         if not 1 <= hp.decoder_layers <= L.MAX_LSTM_LAYERS:
             raise NotImplementedError("HIP decoder: decoder_layers=%d (the library stacks 1..%d LSTM layers)" % (hp.decoder_layers, L.MAX_LSTM_LAYERS))
         assert 0 <= hp.label_smoothing < (hp.vocab_size - 1) / hp.vocab_size
+        for k in ("ar_alpha", "tar_beta"):                  # activation regularisation: coefficients of ar / tar in training_step's loss
+            v = getattr(hp, k, 0.0)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError("%s=%r: a finite coefficient >= 0 (0: off)" % (k, v))
         self.criterion = LabelSmoothing(hp.label_smoothing)
         self.pad_idx = int(hp.vocab_stoi["<PAD>"])
         if encoder_factory is not None:                     # registered here to keep the reference's module order
@@ -546,28 +550,49 @@ class SATDecoder(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,), generator=gen))
         return (p, pe, int(seed))
 
-    def train_decode(self, ann_bld, caps, lengths, epsilon=0, draw=None, with_loss=True, dropout_seed=None, teacher=None, leaf_side=False):
+    def reg_coefficients(self):
+        """(ar_alpha, tar_beta) of the activation regularisers; (0, 0): off, the step issues no launch for them"""
+        return float(getattr(self.hp, "ar_alpha", 0.0)), float(getattr(self.hp, "tar_beta", 0.0))
+
+    def add_reg_terms(self, loss, reg):
+        """loss + ar_alpha * ar + tar_beta * tar from the device pair ``reg``; a coefficient of zero adds no term"""
+        ar_alpha, tar_beta = self.reg_coefficients()
+        if ar_alpha:
+            loss = loss + ar_alpha * reg[0]
+        if tar_beta:
+            loss = loss + tar_beta * reg[1]
+        return loss
+
+    def train_decode(self, ann_bld, caps, lengths, epsilon=0, draw=None, with_loss=True, dropout_seed=None, teacher=None, leaf_side=False, with_reg=None):
         """Decoder half of train_batch + the loss terms (model.py:487-557, 592-597).
 
         ann_bld (B, L, D) on the GPU; caps (B, R, T) int64; lengths (B, R) int64 (host or device).  ``teacher``: the scheduled-sampling
         decisions of this batch when the caller has drawn them already (``PackPlan.teacher_flags``; graph.py keys its graphs by them).
-        ``leaf_side``: ``ann_bld`` comes from an encoder whose backward forks to the side stream (``encoder.decoder_leaf_side_for``)."""
+        ``leaf_side``: ``ann_bld`` comes from an encoder whose backward forks to the side stream (``encoder.decoder_leaf_side_for``).
+        ``with_reg``: also return ``reg``, the device pair (ar, tar) of the top-layer states, differentiable; by default with the loss
+        terms when ``ar_alpha`` or ``tar_beta`` is set, and then ``ar`` / ``tar`` (detached) come with them."""
         B, R, T = caps.shape
+        if with_reg is None:
+            with_reg = bool(with_loss) and any(self.reg_coefficients())
         plan = Dk.PackPlan.cached(lengths.reshape(-1).cpu(), T, ann_bld.device)
         if teacher is None:
             teacher = plan.teacher_flags(float(epsilon), draw)
         caps2 = caps.reshape(B * R, T)
         caps_i32 = caps2.to(device=ann_bld.device, dtype=torch.int32).contiguous()
-        logits_packed, alphas = Dk.DecoderTrainFn.apply(ann_bld, caps_i32, plan, teacher, bool(self.hp.deep_output), self.pad_idx, R,
-                                                        int(getattr(self, "sat_precision", "fp32") == "bf16"), getattr(self.hp, "embed_norm", None) or 0.0,
-                                                        self._dropout_args(dropout_seed), bool(leaf_side), *self.param_list())
+        fn = Dk.DecoderTrainRegFn if with_reg else Dk.DecoderTrainFn
+        logits_packed, alphas, *reg = fn.apply(ann_bld, caps_i32, plan, teacher, bool(self.hp.deep_output), self.pad_idx, R,
+                                               int(getattr(self, "sat_precision", "fp32") == "bf16"), getattr(self.hp, "embed_norm", None) or 0.0,
+                                               self._dropout_args(dropout_seed), bool(leaf_side), *self.param_list())
         targets_packed = plan.pack(caps2[:, 1:].to(ann_bld.device).unsqueeze(-1)).squeeze(-1)
+        extra = dict(reg=reg[0]) if with_reg else {}
         if not with_loss:
-            return dict(logits_packed=logits_packed, targets_packed=targets_packed, alphas=alphas, plan=plan)
+            return dict(logits_packed=logits_packed, targets_packed=targets_packed, alphas=alphas, plan=plan, **extra)
         ce = self.criterion(logits_packed, targets_packed)
         ds = Dk.DoublyStochasticFn.apply(alphas, float(self.hp.att_gamma))
+        if with_reg:
+            extra.update(ar=reg[0][0].detach(), tar=reg[0][1].detach())
         return dict(logits_packed=logits_packed, targets_packed=targets_packed, alphas=alphas, ce=ce, ds=ds,
-                    acc=self.criterion.last_accuracy, plan=plan)
+                    acc=self.criterion.last_accuracy, plan=plan, **extra)
 
 
 class SAT(SATDecoder, _Base):
@@ -586,7 +611,7 @@ class SAT(SATDecoder, _Base):
         for k, v in dict(encoder_size=None, embed_norm=None, pretrained_embedding=None, pretrained=False, decoder_tf=None,
                          decoder_tf_min=0.5, epochs=10, encoder_finetune_after=-1, att_gamma=1.0, label_smoothing=0.0,
                          dropout=0.0, embedding_dropout=0.0, weight_tying=False, deep_output=False, decoder_layers=1,
-                         lr_warmup_steps=0).items():
+                         lr_warmup_steps=0, ar_alpha=0.0, tar_beta=0.0).items():
             hp.setdefault(k, v)
         self.scheduler = None
         self.opt_init_lr = None
@@ -752,11 +777,27 @@ class SAT(SATDecoder, _Base):
         return epsilon, gstep
 
     def _step_losses(self, batch, epsilon, teacher=None):
-        """device half: forward + the two loss terms (model.py:588-597)"""
-        lp, tp, alphas = self.train_batch(batch, epsilon, teacher=teacher)
-        loss = self.criterion(lp.data, tp.data)                                   # model.py:592
-        loss = loss + Dk.DoublyStochasticFn.apply(alphas, float(self.hp.att_gamma))      # model.py:594
-        return loss
+        """device half: forward + the two loss terms (model.py:588-597); with ``ar_alpha`` / ``tar_beta`` set, plus the activation
+        regularisers, whose unweighted values it leaves in ``_sat_last_reg`` for the metrics"""
+        if not any(self.reg_coefficients()):
+            self.__dict__["_sat_last_reg"] = None
+            lp, tp, alphas = self.train_batch(batch, epsilon, teacher=teacher)
+            loss = self.criterion(lp.data, tp.data)                                   # model.py:592
+            loss = loss + Dk.DoublyStochasticFn.apply(alphas, float(self.hp.att_gamma))      # model.py:594
+            return loss
+        img, encoded_captions, lengths = batch                                    # train_batch, keeping the third output of the decoder
+        ann_bld, _ = self.encode(img)
+        res = self.train_decode(ann_bld, encoded_captions, lengths, float(epsilon), None, with_loss=False, teacher=teacher,
+                                leaf_side=E.decoder_leaf_side_for(self.encoder, img), with_reg=True)
+        loss = self.criterion(res["logits_packed"], res["targets_packed"])
+        loss = loss + Dk.DoublyStochasticFn.apply(res["alphas"], float(self.hp.att_gamma))
+        self.__dict__["_sat_last_reg"] = (res["reg"][0].detach(), res["reg"][1].detach())
+        return self.add_reg_terms(loss, res["reg"])
+
+    def _reg_metrics(self):
+        """{"ar", "tar"}: the unweighted regularisers of the last ``_step_losses`` (device scalars), or nothing when they are off"""
+        reg = self.__dict__.get("_sat_last_reg")
+        return {} if reg is None else {"ar": reg[0], "tar": reg[1]}
 
     def _step_end(self, gstep):
         """host half behind the device work (model.py:614-626): learning-rate recipe, optimizer-step count"""
@@ -770,11 +811,13 @@ class SAT(SATDecoder, _Base):
 
     def training_step(self, batch, batch_idx=0):
         """model.py:559-628: returns the metrics dict whose "loss" the trainer back-propagates.  (Split in three so that
-        ``graph.GraphedTrainStep`` can replay the device half from a hipGraph and still run the two host halves every step.)"""
+        ``graph.GraphedTrainStep`` can replay the device half from a hipGraph and still run the two host halves every step.)
+        With ``ar_alpha`` / ``tar_beta`` set (Merity et al.'s activation regularisers on the top-layer LSTM states) the loss gains
+        ``ar_alpha * ar + tar_beta * tar`` and the dict ``"ar"`` and ``"tar"``, the unweighted device scalars."""
         epsilon, gstep = self._step_begin()
         loss = self._step_losses(batch, epsilon)
         self._step_end(gstep)
-        return {"loss": loss, "accuracy": self.criterion.last_accuracy, "epsilon_tf": float(epsilon)}
+        return {"loss": loss, "accuracy": self.criterion.last_accuracy, "epsilon_tf": float(epsilon), **self._reg_metrics()}
 
     def scst_step(self, batch, corpus, samples=5, baseline="mean", reward=(1.0, 0.0), max_gen_length=20, temperature=1.0, seed=None):
         """Self-critical sequence training (Rennie et al. 2017; DESIGN.md 5, "Self-critical training"): the counterpart of
@@ -782,7 +825,8 @@ class SAT(SATDecoder, _Base):
         ``training_step``'s (img, references (B, R, T), lengths (B, R)); ``corpus`` a ``ReferenceCorpus`` holding the split's document
         frequencies.  Returns ``{"loss", "reward", "baseline_reward", "advantage_abs", "sample_length"}`` (device scalars: the loss the
         trainer back-propagates, and batch means) plus ``"samples"`` / ``"sample_lengths"`` / ``"rewards"`` / ``"advantages"``, the
-        device tensors they were taken from."""
+        device tensors they were taken from.  ``ar_alpha`` / ``tar_beta`` are not applied here: the activation regularisers belong to
+        ``training_step``'s loss alone."""
         from . import scst
         scst.check_step_args(self, corpus, samples, baseline, reward, max_gen_length, temperature)        # refuse before any launch
         _, gstep = self._step_begin()
@@ -795,7 +839,8 @@ class SAT(SATDecoder, _Base):
         ``distill.step`` with this module's two host halves around it.  ``teacher``: another ``SAT`` or an ``Ensemble``; ``batch`` is
         ``training_step``'s.  ``targets="teacher"`` trains on the teacher's best beam caption (``beamk``, ``max_gen_length``) in place of
         the references.  Returns ``{"loss", "hard", "soft", "accuracy"}`` (device scalars: the loss the trainer back-propagates, the
-        label-smoothed cross entropy, the KL to the teacher and the next-word accuracy)."""
+        label-smoothed cross entropy, the KL to the teacher and the next-word accuracy).  ``ar_alpha`` / ``tar_beta`` are not applied
+        here: the activation regularisers belong to ``training_step``'s loss alone."""
         from . import distill
         distill.check_step_args(self, teacher, alpha, temperature, targets, beamk, max_gen_length)        # refuse before any launch
         _, gstep = self._step_begin()
