@@ -282,6 +282,40 @@ int sat_distill_bwd(const float* logits, const float* const* teachers, const flo
                     int32_t P, int32_t V, float inv_tau, float alpha, float smoothing, const float* lse_rows, const float* teacher_lse_rows,
                     const float* cnorm_rows, const float* gscale, int32_t dlogits_from_fwd, float* dlogits, void* stream);
 
+/* ------------------------------------------------------------------ token losses ("Token losses")
+ * The label-smoothed cross entropy, focal loss (Lin et al. 2017) and token-level unlikelihood (Welleck et al. 2019) over packed logits
+ * (P, V) in one pass.  Per row p, with x = logits[p], y = targets[p], lse = logsumexp(x), p_v = exp(x_v - lse), q = p_y:
+ *   ce_p   = the row loss of sat_ce_label_smooth_fwd on x, y, smoothing (NaN for y outside [0, V): never a stray read)
+ *   fl_p   = (1 - q)^gamma (lse - x_y): the unsmoothed negative log-likelihood times the focal factor; gamma == 0: the plain one
+ *   C_p    = the negative candidates.  context (N, T) int32: the captions as sat_decoder_train_fwd takes them; src_row (P):
+ *            src_row[p] = t * N + i (the packing plan's): row p is decode step t of caption i.  C_p = the DISTINCT ids among
+ *            context[i][1 .. t] (the targets of the steps 0 .. t - 1) that are != y, != pad_id (-1: none) and inside [0, V).  A
+ *            src_row[p] outside [0, (T - 1) N) gives the row a NaN ul_p and nothing is read through it.
+ *   ul_p   = - sum_{c in C_p} log(max(1 - p_c, 1e-5)), 1 - p_c taken as -expm1(x_c - lse);   mass_p = sum_{c in C_p} p_c
+ *   out[0] = mean_p (ce_weight ce_p + focal_weight fl_p + ul_alpha ul_p);  out[1] = accuracy (sat_ce_label_smooth_fwd's);
+ *   out[2..5] = the means of ce_p, fl_p, ul_p, mass_p
+ *   dlogits[p][v] = gscale[0] / P * [ ce_weight (p_v - smoothing/V - (1 - smoothing) [v == y]) + focal_weight w_p (p_v - [v == y])
+ *                                     + ul_alpha ([v in C_p] r_v - p_v R_p) ]
+ *            w_p = (1 - q)^gamma - gamma q (1 - q)^(gamma - 1) log q   (1 at gamma == 0; 0 at q == 1 with gamma > 0)
+ *            r_c = p_c / (1 - p_c) where 1 - p_c >= 1e-5, else 0 (the clamp passes no gradient);  R_p = sum_{c in C_p} r_c
+ * A weight of zero skips its term: its rows and its mean are 0 and nothing is read for it; with ul_alpha == 0 context and src_row are
+ * not read and may be NULL.  With ce_weight 1 and the other two 0, out[0..1], lse_rows and dlogits are sat_ce_label_smooth_fwd / _bwd's
+ * bit for bit (one device code).  The row terms are summed in double in a fixed order without atomics: the same input gives the same bits.
+ * Row scratch, written by the forward and read by the backward so that no reduction is redone: lse_rows (P); aux_rows (P, 2) = w_p, R_p;
+ * loss_rows (P, 4) = ce_p, fl_p, ul_p, mass_p; correct_rows (P).  gscale: device pointer or NULL = 1.
+ * One 256-thread block per row, one thread per context id; 16-byte accesses when V % 4 == 0 and logits (and dlogits) are 16-byte
+ * aligned, 4-byte ones otherwise.  No (P, V) mask or temporary: the sweeps never ask whether a word is a candidate, the backward writes
+ * the target's and the candidates' entries whole behind its sweep.  SAT_EINVAL before any launch: a null pointer (context / src_row
+ * only with ul_alpha != 0), P or V < 1, smoothing outside [0, 1), a weight, gamma or alpha that is negative or not finite, all three
+ * weights zero, and with ul_alpha != 0: N < 1, T < 2 or T - 1 > 256. */
+int sat_token_loss_fwd(const float* logits, const int32_t* targets, int32_t P, int32_t V, float smoothing, float ce_weight, float focal_weight,
+                       float focal_gamma, float ul_alpha, const int32_t* context, const int32_t* src_row, int32_t N, int32_t T,
+                       int32_t pad_id /* -1: none */, float* lse_rows, float* aux_rows, float* loss_rows, int32_t* correct_rows, float* out /* 6 floats */,
+                       void* stream);
+int sat_token_loss_bwd(const float* logits, const int32_t* targets, int32_t P, int32_t V, float smoothing, float ce_weight, float focal_weight,
+                       float focal_gamma, float ul_alpha, const int32_t* context, const int32_t* src_row, int32_t N, int32_t T, int32_t pad_id,
+                       const float* lse_rows, const float* aux_rows, const float* gscale /* or NULL = 1 */, float* dlogits, void* stream);
+
 /* ------------------------------------------------------------------ temperature-scaling calibration (temperature_scaling.py:51-59)
  * For packed logits (P, V) and targets (P):  loss(T) = F.cross_entropy(logits / T, targets)  and its derivative
  * dloss/dT = mean_i [ x_iy - sum_j softmax(x_i / T)_j x_ij ] / T^2.  The row maximum does not depend on T > 0, so it is taken once;

@@ -443,6 +443,12 @@ SYMBOLS.update({          # activation regularisation (AR / TAR) of the decoder 
     "sat_decoder_train_bwd_reg": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), C.POINTER(DecoderBatch), _vp, _vp, _vp,
                                             C.POINTER(DecoderParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
 })
+SYMBOLS.update({          # token losses (decoder.TokenLossFn): cross entropy, focal loss and unlikelihood in one pass over the packed logits
+    "sat_token_loss_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _f, _f, _f, _f, _f, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sat_token_loss_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _f, _f, _f, _f, _f, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+})
+TOKEN_LOSSES = {"ce": (1.0, 0.0), "fl": (0.0, 1.0), "ce+fl": (1.0, 1.0)}        # hparam token_loss -> (ce_weight, focal_weight)
+TOKEN_LOSS_MAX_CONTEXT = 256                                                    # T - 1 context ids in a row: one per thread
 SYMBOLS.update({          # attention overlays (visualize.py)
     "sat_image_square_bicubic_workspace_bytes": (C.c_size_t, [_vp, _i32, _i32]),
     "sat_image_square_bicubic": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_size_t, _vp]),

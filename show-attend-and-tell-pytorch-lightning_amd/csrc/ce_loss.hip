@@ -7,48 +7,28 @@
 #include "../../include/sat_hip.h"
 #include "common.h"
 #include "decoder.h"
+#include "ce_row.h"
 #include "row_reduce.h"
 
 namespace sat {
 
-// One block per packed token row, one sweep (row_reduce.h): online log-sum-exp, row argmax and the row loss; ce_finish_kernel reduces
-// loss_rows in a fixed order.  The gradient is a second kernel so that autograd's grad_output scales it.
+// One block per packed token row, one sweep (ce_row.h, on row_reduce.h): online log-sum-exp, row argmax and the row loss; ce_finish_kernel
+// reduces loss_rows in a fixed order.  The gradient is a second kernel so that autograd's grad_output scales it.
 template <int VEC>
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target, int V,
                                                       float smoothing, float* __restrict__ lse_rows,
                                                       float* __restrict__ loss_rows, int* __restrict__ correct_rows) {
     const int p = blockIdx.x, tid = threadIdx.x;
     const float* x = logits + (long)p * V;
-    __shared__ float s_m[4], s_s[4], s_t[4], s_b[4]; __shared__ int s_i[4];
-    float mx = -INFINITY, sum = 0.f, tot = 0.f; int bi = 0x7fffffff; float bv = -INFINITY;
-    row_sweep<VEC, kSweepDepth<VEC>, 256>(x, V / VEC, tid, [&](int u, const float (&e)[VEC]) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {                 // ascending index: the first maximum wins, as torch.argmax
-            const int v = u * VEC + j;
-            tot += e[j];
-            // a row of nothing but -inf: the 4-byte form names column 0, the 16-byte form no column (open items)
-            const bool better = VEC == 1 ? arg_before(e[j], v, bv, bi) : e[j] > bv;
-            if (better) { bv = e[j]; bi = v; }
-        }
-        lse_unit<VEC>(e, mx, sum);
-    });
-    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
-    wave_argbest(bv, bi);
-    if ((tid & 63) == 0) { s_t[tid >> 6] = tot; s_b[tid >> 6] = bv; s_i[tid >> 6] = bi; }
-    lse_wave_put(mx, sum, s_m, s_s, tid);
-    __syncthreads();
+    __shared__ CeRowLds lds;
+    float bv; int bi;
+    ce_row_sweep<VEC>(x, V, tid, lds, bv, bi);
     if (tid == 0) {
-        float Tt = 0.f;
-        for (int k = 0; k < 4; ++k) Tt += s_t[k];
-        int Bi = bi;
-        argbest_merge<4>(bv, Bi, s_b, s_i);
-        const float lse = lse_block(s_m, s_s);
+        const float lse = ce_row_lse(lds);
         const int t = target[p];
-        float nll = lse - x[t];
-        float smooth = lse - Tt / (float)V;
         lse_rows[p] = lse;
-        loss_rows[p] = (1.f - smoothing) * nll + smoothing * smooth;
-        correct_rows[p] = (Bi == t) ? 1 : 0;
+        loss_rows[p] = ce_row_loss(lse, x[t], ce_row_total(lds), V, smoothing);
+        correct_rows[p] = (ce_row_argmax(lds, bv, bi) == t) ? 1 : 0;
     }
 }
 // dlogits[p, v] = g/P * (softmax - smoothing/V - (1-smoothing)[v == target])
@@ -63,7 +43,7 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ 
     row_sweep<VEC, kSweepDepth<VEC>, 256>(x, V / VEC, threadIdx.x, [&](int u, const float (&e)[VEC]) {
         float o[VEC];
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) o[j] = (__expf(e[j] - lse) - sv - ((u * VEC + j == t) ? conf : 0.f)) * sc;
+        for (int j = 0; j < VEC; ++j) o[j] = ce_grad_word(e[j], lse, sv, conf, u * VEC + j == t, sc);
         store_unit<VEC>(g, u, o);
     });
 }

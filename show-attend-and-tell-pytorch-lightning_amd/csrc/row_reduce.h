@@ -1,5 +1,5 @@
-// Device cores shared by the kernels that walk a vocabulary row (decoder_kernels.h, ce_loss.hip, policy_loss.hip, distill_loss.hip,
-// temperature.hip): the row sweep and its two access widths, the online log-sum-exp, the block arg-best and its pick loops, the
+// Device cores shared by the kernels that walk a vocabulary row (decoder_kernels.h, ce_loss.hip and token_loss.hip through ce_row.h,
+// policy_loss.hip, distill_loss.hip, temperature.hip): the row sweep and its two access widths, the online log-sum-exp, the block arg-best and its pick loops, the
 // ensemble's word, and the double fixed-order tree of the finish kernels.
 // The bits depend on the shape of the float expressions, so the two FMAs of the recurrence are spelled out (left to contraction, the
 // compiler fused them in one kernel and not in the next); change them here and every user moves together.  A file built with

@@ -380,6 +380,59 @@ class LabelSmoothingFn(torch.autograd.Function):
         return dlogits, None, None
 
 
+class TokenLossFn(torch.autograd.Function):
+    """The token losses on packed rows (include/sat_hip.h, sat_token_loss_fwd; DESIGN.md 5, "Token losses"):
+    ``ce_weight * CE_smoothed + focal_weight * focal(gamma) + ul_alpha * unlikelihood`` with the unlikelihood's negative candidates taken
+    from ``caps_i32`` (N, T) through ``src_row`` (``PackPlan.src_row``); both may be None when ``ul_alpha`` is 0.  Returns
+    ``(loss, accuracy, terms)`` with ``terms`` the means of (ce, fl, ul, repeat mass), unweighted; differentiable in ``logits`` only, the
+    last two are marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, targets_i32, smoothing, ce_weight, focal_weight, focal_gamma, ul_alpha, caps_i32, src_row, pad_id):
+        lib = L.lib()
+        L.require_gpu(logits, targets_i32)
+        logits = logits.contiguous()
+        P, V = logits.shape
+        if logits.dtype != torch.float32 or targets_i32.dtype != torch.int32 or targets_i32.numel() != P:
+            raise ValueError("TokenLossFn: float32 logits (P, V) and P int32 targets")
+        targets_i32 = targets_i32.contiguous()
+        N = T = 0
+        if float(ul_alpha) != 0.0:
+            if caps_i32 is None or src_row is None:
+                raise ValueError("TokenLossFn: ul_alpha=%g needs the captions and the packing plan's src_row" % float(ul_alpha))
+            L.require_gpu(caps_i32, src_row)
+            if caps_i32.dtype != torch.int32 or src_row.dtype != torch.int32 or caps_i32.dim() != 2 or src_row.numel() != P:
+                raise ValueError("TokenLossFn: int32 captions (N, T) and %d int32 src_row entries" % P)
+            caps_i32, src_row = caps_i32.contiguous(), src_row.contiguous()
+            N, T = caps_i32.shape
+        else:
+            caps_i32 = src_row = None
+        f32 = dict(dtype=torch.float32, device=logits.device)
+        lse, aux, rows = torch.empty(P, **f32), torch.empty(P, 2, **f32), torch.empty(P, 4, **f32)
+        correct = torch.empty(P, dtype=torch.int32, device=logits.device)
+        out = torch.empty(6, **f32)
+        args = (P, V, float(smoothing), float(ce_weight), float(focal_weight), float(focal_gamma), float(ul_alpha))
+        tail = (int(N), int(T), -1 if pad_id is None else int(pad_id))
+        L.check(lib.sat_token_loss_fwd(L.ptr(logits), L.ptr(targets_i32), *args, L.ptr(caps_i32), L.ptr(src_row), *tail, L.ptr(lse), L.ptr(aux), L.ptr(rows),
+                                       L.ptr(correct), L.ptr(out), L.stream_ptr()), "sat_token_loss_fwd")
+        ctx.save_for_backward(logits, targets_i32, lse, aux)
+        ctx.args, ctx.tail, ctx.context = args, tail, (caps_i32, src_row)
+        loss, acc, terms = out[0].clone(), out[1].clone(), out[2:].clone()
+        ctx.mark_non_differentiable(acc, terms)
+        return loss, acc, terms
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc, _gterms):
+        lib = L.lib()
+        logits, targets, lse, aux = ctx.saved_tensors
+        caps_i32, src_row = ctx.context
+        dlogits = torch.empty_like(logits)
+        g = gloss.reshape(1).to(torch.float32).contiguous()
+        L.check(lib.sat_token_loss_bwd(L.ptr(logits), L.ptr(targets), *ctx.args, L.ptr(caps_i32), L.ptr(src_row), *ctx.tail, L.ptr(lse), L.ptr(aux), L.ptr(g),
+                                       L.ptr(dlogits), L.stream_ptr()), "sat_token_loss_bwd")
+        return dlogits, None, None, None, None, None, None, None, None, None
+
+
 class PolicyNLLFn(torch.autograd.Function):
     """The row-weighted policy loss of self-critical training on packed rows (include/sat_hip.h, sat_policy_nll_fwd):
     ``-scale * sum_p row_weight[p] * log q(targets[p])`` with q the softmax of ``logits / temperature`` over the words the search leaves

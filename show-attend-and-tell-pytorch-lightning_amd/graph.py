@@ -16,7 +16,9 @@ contents, not tensors: every address a graph has baked in stays valid and the bf
 
 A graph is valid for one launch sequence, so graphs are keyed by everything that shapes it: tensor shapes, the packing plan (caption
 lengths), the teacher-forcing flags, precision, the set of trainable parameters, the activation regularisers' coefficients (``ar_alpha``,
-``tar_beta``: the regularised step has two more launches forward and one more backward, and its dict carries ``"ar"`` / ``"tar"``).  The
+``tar_beta``: the regularised step has two more launches forward and one more backward, and its dict carries ``"ar"`` / ``"tar"``), the
+token loss (``token_loss``, ``focal_gamma``, ``ul_alpha``: ``TokenLossFn`` is captured where ``LabelSmoothingFn`` is otherwise, and the
+dict carries ``"ce"`` / ``"fl"`` / ``"ul"`` / ``"repeat_mass"``).  The
 first step with a new key runs eagerly (it also warms every cache the capture must not touch: plans, split-K scratch, kernel
 attributes), the second one captures, later ones replay.  Anything
 the graph cannot express falls back to the eager step for that call: more than one process (the gradient all-reduce is launched from
@@ -153,8 +155,13 @@ class GraphedTrainStep:
                                                               model._dropout_args(None), False, *dec_params)      # no side-stream fork of the parameter gradients: no engine ends this backward
             targets = plan.pack(caps2[:, 1:].unsqueeze(-1)).squeeze(-1)
             cctx, sctx = _Ctx(), _Ctx()
-            ce, acc = Dk.LabelSmoothingFn.forward(cctx, logits, targets.to(torch.int32), model.criterion.smoothing)
-            model.criterion.last_accuracy = acc
+            token_loss = model.token_loss_on()                  # TokenLoss in the criterion's place, as SAT._step_losses
+            if token_loss:
+                ce, acc, terms = Dk.TokenLossFn.forward(cctx, logits, targets.to(torch.int32), *model.criterion.fn_args((caps_i32, plan)))
+                model.criterion.keep(acc, terms)
+            else:
+                ce, acc = Dk.LabelSmoothingFn.forward(cctx, logits, targets.to(torch.int32), model.criterion.smoothing)
+                model.criterion.last_accuracy = acc
             ds = Dk.DoublyStochasticFn.forward(sctx, alphas, float(hp.att_gamma))
             loss = ce + ds
             dreg = None
@@ -167,7 +174,7 @@ class GraphedTrainStep:
             else:
                 model.__dict__["_sat_last_reg"] = None
             one = torch.ones((), dtype=torch.float32, device=img.device)
-            dlogits = Dk.LabelSmoothingFn.backward(cctx, one, None)[0]
+            dlogits = Dk.TokenLossFn.backward(cctx, one, None, None)[0] if token_loss else Dk.LabelSmoothingFn.backward(cctx, one, None)[0]
             dalphas = Dk.DoublyStochasticFn.backward(sctx, one)[0]
             douts = Dk.DecoderTrainFn._backward(dctx, dlogits, dalphas, dreg)
             dann = douts[0]
@@ -235,7 +242,7 @@ class GraphedTrainStep:
             self.stats["eager: " + why] += 1
             return self._eager(batch, epsilon, gstep, teacher)
         key = (tuple(img.shape), tuple(caps.shape), lengths.numpy().tobytes(), np.asarray(teacher, np.int32).tobytes(), float(epsilon),
-               model.sat_precision, model.training, self._params_sig(), model.reg_coefficients())
+               model.sat_precision, model.training, self._params_sig(), model.reg_coefficients(), model.token_loss_key())
         stale = self._stale_copies()
         if stale:
             self._graphs.clear()                          # filter copies are about to be remade: every graph points at the old ones

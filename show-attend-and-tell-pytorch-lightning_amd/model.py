@@ -56,6 +56,49 @@ class LabelSmoothing(nn.Module):
         return loss
 
 
+class TokenLoss(nn.Module):
+    """The token losses on the HIP kernel ("Token losses"; ``Dk.TokenLossFn``): ``token_loss`` in "ce" / "fl" / "ce+fl"
+    chooses label-smoothed cross entropy, focal loss (Lin et al. 2017, ``focal_gamma``) or their sum; ``ul_alpha`` > 0 adds token-level
+    unlikelihood (Welleck et al. 2019) against the words the ground-truth caption has already said.  ``forward(x, target, context)``
+    returns the loss; ``context`` = (captions (N, T) int32 on the device, the ``PackPlan`` of ``x``'s rows) is needed when ``ul_alpha``
+    > 0.  ``last_accuracy`` is ``LabelSmoothing``'s, ``last_terms`` the dict of the unweighted means "ce" / "fl" / "ul" / "repeat_mass"
+    (detached device scalars; a term that is off is 0)."""
+
+    TERMS = ("ce", "fl", "ul", "repeat_mass")
+
+    def __init__(self, smoothing=0.0, token_loss="ce", focal_gamma=2.0, ul_alpha=0.0, pad_id=None):
+        super().__init__()
+        if token_loss not in L.TOKEN_LOSSES:
+            raise ValueError("token_loss=%r is none of %r" % (token_loss, tuple(L.TOKEN_LOSSES)))
+        for k, v in (("focal_gamma", focal_gamma), ("ul_alpha", ul_alpha)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError("%s=%r: a finite number >= 0" % (k, v))
+        self.confidence, self.smoothing = 1.0 - smoothing, smoothing
+        self.token_loss, self.focal_gamma, self.ul_alpha = token_loss, float(focal_gamma), float(ul_alpha)
+        self.ce_weight, self.focal_weight = L.TOKEN_LOSSES[token_loss]
+        self.pad_id = pad_id
+        self.last_accuracy = None
+        self.last_terms = None
+
+    def fn_args(self, context):
+        """the arguments of ``Dk.TokenLossFn`` behind (logits, targets): graph.py calls its forward with the same ones"""
+        caps_i32 = src_row = None
+        if self.ul_alpha:
+            if context is None:
+                raise ValueError("TokenLoss: ul_alpha=%g needs context=(captions, plan)" % self.ul_alpha)
+            caps_i32, src_row = context[0], context[1].src_row
+        return (self.smoothing, self.ce_weight, self.focal_weight, self.focal_gamma, self.ul_alpha, caps_i32, src_row, self.pad_id)
+
+    def keep(self, acc, terms):
+        self.last_accuracy = acc
+        self.last_terms = {k: terms[i] for i, k in enumerate(self.TERMS)}
+
+    def forward(self, x, target, context=None):
+        loss, acc, terms = Dk.TokenLossFn.apply(x, target.to(torch.int32), *self.fn_args(context))
+        self.keep(acc, terms)
+        return loss
+
+
 SAMPLE_METHODS = tuple(L.SAMPLE_METHODS)
 
 
@@ -127,8 +170,11 @@ class SATDecoder(nn.Module):
             v = getattr(hp, k, 0.0)
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
                 raise ValueError("%s=%r: a finite coefficient >= 0 (0: off)" % (k, v))
-        self.criterion = LabelSmoothing(hp.label_smoothing)
         self.pad_idx = int(hp.vocab_stoi["<PAD>"])
+        # token losses: the defaults keep the label-smoothed cross entropy and its launches
+        token_loss, focal_gamma, ul_alpha = getattr(hp, "token_loss", "ce"), getattr(hp, "focal_gamma", 2.0), getattr(hp, "ul_alpha", 0.0)
+        criterion = TokenLoss(hp.label_smoothing, token_loss, focal_gamma, ul_alpha, self.pad_idx)      # refuses what it cannot run
+        self.criterion = criterion if token_loss != "ce" or ul_alpha > 0 else LabelSmoothing(hp.label_smoothing)
         if encoder_factory is not None:                     # registered here to keep the reference's module order
             self.encoder = encoder_factory(hp)
         self.embedding = Embedding(hp.vocab_size, hp.embed_dim, max_norm=getattr(hp, "embed_norm", None), padding_idx=self.pad_idx)
@@ -563,6 +609,21 @@ class SATDecoder(nn.Module):
             loss = loss + tar_beta * reg[1]
         return loss
 
+    def token_loss_on(self):
+        """the criterion is ``TokenLoss`` (``token_loss`` other than "ce", or ``ul_alpha`` > 0)"""
+        return isinstance(self.criterion, TokenLoss)
+
+    def token_loss_key(self):
+        """(token_loss, focal_gamma, ul_alpha) as the criterion runs them: what a captured step depends on"""
+        c = self.criterion
+        return (c.token_loss, c.focal_gamma, c.ul_alpha) if self.token_loss_on() else ("ce", 0.0, 0.0)
+
+    def token_criterion(self, logits_packed, targets_packed, caps_i32, plan):
+        """the criterion on packed rows; ``TokenLoss`` also gets the ground-truth captions and the plan its candidates come from"""
+        if self.token_loss_on():
+            return self.criterion(logits_packed, targets_packed, (caps_i32, plan))
+        return self.criterion(logits_packed, targets_packed)
+
     def train_decode(self, ann_bld, caps, lengths, epsilon=0, draw=None, with_loss=True, dropout_seed=None, teacher=None, leaf_side=False, with_reg=None):
         """Decoder half of train_batch + the loss terms (model.py:487-557, 592-597).
 
@@ -570,7 +631,9 @@ class SATDecoder(nn.Module):
         decisions of this batch when the caller has drawn them already (``PackPlan.teacher_flags``; graph.py keys its graphs by them).
         ``leaf_side``: ``ann_bld`` comes from an encoder whose backward forks to the side stream (``encoder.decoder_leaf_side_for``).
         ``with_reg``: also return ``reg``, the device pair (ar, tar) of the top-layer states, differentiable; by default with the loss
-        terms when ``ar_alpha`` or ``tar_beta`` is set, and then ``ar`` / ``tar`` (detached) come with them."""
+        terms when ``ar_alpha`` or ``tar_beta`` is set, and then ``ar`` / ``tar`` (detached) come with them.  With ``TokenLoss`` as the
+        criterion ``ce`` is the whole token loss and ``token_terms`` its unweighted parts; without the loss terms ``caps_i32`` comes back
+        for the caller's criterion."""
         B, R, T = caps.shape
         if with_reg is None:
             with_reg = bool(with_loss) and any(self.reg_coefficients())
@@ -586,8 +649,10 @@ class SATDecoder(nn.Module):
         targets_packed = plan.pack(caps2[:, 1:].to(ann_bld.device).unsqueeze(-1)).squeeze(-1)
         extra = dict(reg=reg[0]) if with_reg else {}
         if not with_loss:
-            return dict(logits_packed=logits_packed, targets_packed=targets_packed, alphas=alphas, plan=plan, **extra)
-        ce = self.criterion(logits_packed, targets_packed)
+            return dict(logits_packed=logits_packed, targets_packed=targets_packed, alphas=alphas, plan=plan, caps_i32=caps_i32, **extra)
+        ce = self.token_criterion(logits_packed, targets_packed, caps_i32, plan)
+        if self.token_loss_on():
+            extra.update(token_terms=self.criterion.last_terms)
         ds = Dk.DoublyStochasticFn.apply(alphas, float(self.hp.att_gamma))
         if with_reg:
             extra.update(ar=reg[0][0].detach(), tar=reg[0][1].detach())
@@ -611,7 +676,7 @@ class SAT(SATDecoder, _Base):
         for k, v in dict(encoder_size=None, embed_norm=None, pretrained_embedding=None, pretrained=False, decoder_tf=None,
                          decoder_tf_min=0.5, epochs=10, encoder_finetune_after=-1, att_gamma=1.0, label_smoothing=0.0,
                          dropout=0.0, embedding_dropout=0.0, weight_tying=False, deep_output=False, decoder_layers=1,
-                         lr_warmup_steps=0, ar_alpha=0.0, tar_beta=0.0).items():
+                         lr_warmup_steps=0, ar_alpha=0.0, tar_beta=0.0, token_loss="ce", focal_gamma=2.0, ul_alpha=0.0).items():
             hp.setdefault(k, v)
         self.scheduler = None
         self.opt_init_lr = None
@@ -704,7 +769,8 @@ class SAT(SATDecoder, _Base):
     def calibrate_temperature(self, batches, max_batches=42, **fit_kwargs):
         """The reference's temperature_scaling.py in one call: teacher-forced logits of the frozen model over ``batches``, then the
         temperature fit (calibration.py).  Returns a ``TemperatureFit``; its ``temperature`` is what ``caption`` / ``val_batch`` take.
-        Changes no parameter, buffer or hyper-parameter."""
+        Changes no parameter, buffer or hyper-parameter.  The fit minimises the plain negative log-likelihood: ``token_loss`` /
+        ``focal_gamma`` / ``ul_alpha`` are not applied here."""
         from . import calibration
         return calibration.calibrate_temperature(self, batches, max_batches, **fit_kwargs)
 
@@ -778,8 +844,9 @@ class SAT(SATDecoder, _Base):
 
     def _step_losses(self, batch, epsilon, teacher=None):
         """device half: forward + the two loss terms (model.py:588-597); with ``ar_alpha`` / ``tar_beta`` set, plus the activation
-        regularisers, whose unweighted values it leaves in ``_sat_last_reg`` for the metrics"""
-        if not any(self.reg_coefficients()):
+        regularisers, whose unweighted values it leaves in ``_sat_last_reg`` for the metrics; with ``TokenLoss`` as the criterion the
+        token loss gets the ground-truth captions and the plan (whatever word was fed back, the candidates come from the references)"""
+        if not any(self.reg_coefficients()) and not self.token_loss_on():
             self.__dict__["_sat_last_reg"] = None
             lp, tp, alphas = self.train_batch(batch, epsilon, teacher=teacher)
             loss = self.criterion(lp.data, tp.data)                                   # model.py:592
@@ -788,16 +855,23 @@ class SAT(SATDecoder, _Base):
         img, encoded_captions, lengths = batch                                    # train_batch, keeping the third output of the decoder
         ann_bld, _ = self.encode(img)
         res = self.train_decode(ann_bld, encoded_captions, lengths, float(epsilon), None, with_loss=False, teacher=teacher,
-                                leaf_side=E.decoder_leaf_side_for(self.encoder, img), with_reg=True)
-        loss = self.criterion(res["logits_packed"], res["targets_packed"])
+                                leaf_side=E.decoder_leaf_side_for(self.encoder, img), with_reg=any(self.reg_coefficients()))
+        loss = self.token_criterion(res["logits_packed"], res["targets_packed"], res["caps_i32"], res["plan"])
         loss = loss + Dk.DoublyStochasticFn.apply(res["alphas"], float(self.hp.att_gamma))
+        if "reg" not in res:
+            self.__dict__["_sat_last_reg"] = None
+            return loss
         self.__dict__["_sat_last_reg"] = (res["reg"][0].detach(), res["reg"][1].detach())
         return self.add_reg_terms(loss, res["reg"])
 
     def _reg_metrics(self):
-        """{"ar", "tar"}: the unweighted regularisers of the last ``_step_losses`` (device scalars), or nothing when they are off"""
+        """{"ar", "tar"}: the unweighted regularisers of the last ``_step_losses`` (device scalars), or nothing when they are off; with
+        ``TokenLoss`` as the criterion also {"ce", "fl", "ul", "repeat_mass"}, the unweighted parts of the token loss"""
         reg = self.__dict__.get("_sat_last_reg")
-        return {} if reg is None else {"ar": reg[0], "tar": reg[1]}
+        out = {} if reg is None else {"ar": reg[0], "tar": reg[1]}
+        if self.token_loss_on():
+            out.update(self.criterion.last_terms)
+        return out
 
     def _step_end(self, gstep):
         """host half behind the device work (model.py:614-626): learning-rate recipe, optimizer-step count"""
@@ -813,7 +887,9 @@ class SAT(SATDecoder, _Base):
         """model.py:559-628: returns the metrics dict whose "loss" the trainer back-propagates.  (Split in three so that
         ``graph.GraphedTrainStep`` can replay the device half from a hipGraph and still run the two host halves every step.)
         With ``ar_alpha`` / ``tar_beta`` set (Merity et al.'s activation regularisers on the top-layer LSTM states) the loss gains
-        ``ar_alpha * ar + tar_beta * tar`` and the dict ``"ar"`` and ``"tar"``, the unweighted device scalars."""
+        ``ar_alpha * ar + tar_beta * tar`` and the dict ``"ar"`` and ``"tar"``, the unweighted device scalars.  With ``token_loss`` in
+        "fl" / "ce+fl" or ``ul_alpha`` > 0 ("Token losses") the cross entropy gives way to ``TokenLoss`` and the dict gains
+        ``"ce"``, ``"fl"``, ``"ul"`` and ``"repeat_mass"``, again unweighted device scalars."""
         epsilon, gstep = self._step_begin()
         loss = self._step_losses(batch, epsilon)
         self._step_end(gstep)
@@ -826,7 +902,7 @@ class SAT(SATDecoder, _Base):
         frequencies.  Returns ``{"loss", "reward", "baseline_reward", "advantage_abs", "sample_length"}`` (device scalars: the loss the
         trainer back-propagates, and batch means) plus ``"samples"`` / ``"sample_lengths"`` / ``"rewards"`` / ``"advantages"``, the
         device tensors they were taken from.  ``ar_alpha`` / ``tar_beta`` are not applied here: the activation regularisers belong to
-        ``training_step``'s loss alone."""
+        ``training_step``'s loss alone, and so do ``token_loss`` / ``focal_gamma`` / ``ul_alpha``."""
         from . import scst
         scst.check_step_args(self, corpus, samples, baseline, reward, max_gen_length, temperature)        # refuse before any launch
         _, gstep = self._step_begin()
@@ -840,7 +916,8 @@ class SAT(SATDecoder, _Base):
         ``training_step``'s.  ``targets="teacher"`` trains on the teacher's best beam caption (``beamk``, ``max_gen_length``) in place of
         the references.  Returns ``{"loss", "hard", "soft", "accuracy"}`` (device scalars: the loss the trainer back-propagates, the
         label-smoothed cross entropy, the KL to the teacher and the next-word accuracy).  ``ar_alpha`` / ``tar_beta`` are not applied
-        here: the activation regularisers belong to ``training_step``'s loss alone."""
+        here: the activation regularisers belong to ``training_step``'s loss alone, and so do ``token_loss`` / ``focal_gamma`` /
+        ``ul_alpha`` (the hard term stays the label-smoothed cross entropy)."""
         from . import distill
         distill.check_step_args(self, teacher, alpha, temperature, targets, beamk, max_gen_length)        # refuse before any launch
         _, gstep = self._step_begin()
