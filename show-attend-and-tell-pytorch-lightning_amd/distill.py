@@ -128,7 +128,7 @@ def loss(student, ann_bld, caps, lengths, teacher_logits, weights, combine, alph
     targets = res["targets_packed"].to(torch.int32).contiguous()
     dl, hard, soft, acc = Dk.DistillFn.apply(logits, targets, list(teacher_logits), list(weights), combine, 1.0 / float(temperature), float(alpha),
                                              float(student.criterion.smoothing))
-    total = dl + Dk.DoublyStochasticFn.apply(res["alphas"], float(student.hp.att_gamma))
+    total = dl + student.attention_term(res["alphas"])
     return (total, hard, soft, acc) if return_parts else total
 
 

@@ -624,6 +624,11 @@ class SATDecoder(nn.Module):
             return self.criterion(logits_packed, targets_packed, (caps_i32, plan))
         return self.criterion(logits_packed, targets_packed)
 
+    def attention_term(self, alphas):
+        """the doubly-stochastic attention term ``att_gamma * ((1 - alphas.sum(dim=1)) ** 2).mean()`` (model.py:594) of a loss built on
+        ``train_decode(with_loss=False)``: ``scst.loss`` and ``distill.loss`` add it to their own criterion"""
+        return Dk.DoublyStochasticFn.apply(alphas, float(self.hp.att_gamma))
+
     def train_decode(self, ann_bld, caps, lengths, epsilon=0, draw=None, with_loss=True, dropout_seed=None, teacher=None, leaf_side=False, with_reg=None):
         """Decoder half of train_batch + the loss terms (model.py:487-557, 592-597).
 

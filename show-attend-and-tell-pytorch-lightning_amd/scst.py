@@ -152,7 +152,7 @@ def loss(model, ann_bld, caps, lengths, step_weight, count=None, temperature=1.0
     n_first = int(plan.batch_sizes[0]) if plan.batch_sizes.numel() else 0            # the rows of decode step 0 come first: all N captions
     pl = Dk.PolicyNLLFn.apply(res["logits_packed"], targets, weight, 1.0 / float(temperature), _masked_ids(model, ann_bld.device), n_first,
                               1.0 / max(1, total))
-    return pl + Dk.DoublyStochasticFn.apply(res["alphas"], float(model.hp.att_gamma))
+    return pl + model.attention_term(res["alphas"])
 
 
 def step(model, batch, corpus, samples=5, baseline="mean", reward=(1.0, 0.0), max_gen_length=20, temperature=1.0, seed=None):

@@ -115,3 +115,56 @@ def test_what_a_graph_cannot_express_runs_eagerly():
         out = step(b, it)
         assert torch.isfinite(out["loss"])
     assert step.stats["eager: dropout"] == 3 and step.stats["replayed"] == 0
+
+
+EVERY_TERM = dict(token_loss="ce+fl", ul_alpha=1.0, label_smoothing=0.1, ar_alpha=2.0, tar_beta=1.0, decoder_layers=2)
+
+
+def _repeating(b, hp):
+    """the caption words remapped into 1..5, so that contexts repeat and the unlikelihood has candidates"""
+    img, caps, lengths = b
+    word = (caps > 0) & (caps < hp.vocab_size - 2)
+    return img, torch.where(word, 1 + (caps - 1) % 5, caps), lengths
+
+
+def test_every_optional_term_at_once_replays_bit_equal():
+    """the token losses and the activation regularisers are otherwise captured one at a time: this pins their composition, two LSTM layers deep, in one captured step"""
+    from sat_amd.graph import GraphedTrainStep
+    eager, hp = _make("fp32", EVERY_TERM)
+    graphed, _ = _make("fp32", EVERY_TERM)
+    opt_e, opt_g = eager.configure_optimizers(), graphed.configure_optimizers()
+    step = GraphedTrainStep(graphed, opt_g)
+    b = _repeating(_batch(hp, 11), hp)
+    keys = ("loss", "accuracy", "ce", "fl", "ul", "repeat_mass", "ar", "tar")
+    for it in range(4):          # step 0 warms eagerly, step 1 captures and replays, steps 2 and 3 replay
+        opt_e.zero_grad(set_to_none=True)
+        out_e = eager.training_step(b, it)
+        out_e["loss"].backward()
+        opt_e.step()
+        out_g = step(b, it)
+        assert set(out_g) == set(out_e) == set(keys) | {"epsilon_tf"} and out_g["epsilon_tf"] == out_e["epsilon_tf"]
+        for k in keys:
+            assert torch.equal(out_e[k].detach(), out_g[k]), "step %d: %s %r vs %r" % (it, k, float(out_e[k]), float(out_g[k]))
+        _same(_state(eager, opt_e), _state(graphed, opt_g), "after step %d" % it)
+        assert all(float(out_g[k]) > 0 for k in ("ul", "fl", "ar", "tar")), {k: float(out_g[k]) for k in keys}
+    assert step.stats["captured"] == 1 and step.stats["replayed"] == 3, dict(step.stats)
+
+
+def test_the_metrics_come_from_the_step_that_returned_them():
+    """validation code may call the criterion between a step and the reading of its metrics: the step's dict keeps the step's values"""
+    model, hp = _make("fp32", EVERY_TERM)
+    b = _repeating(_batch(hp, 11), hp)
+    out = model.training_step(b, 0)
+    keys = ("loss", "accuracy", "ce", "fl", "ul", "repeat_mass", "ar", "tar")
+    assert set(out) == set(keys) | {"epsilon_tf"}
+    before = {k: out[k].detach().clone() for k in keys}
+    from sat_amd.decoder import PackPlan
+    img, caps, lengths = b
+    plan = PackPlan.cached(lengths.reshape(-1), caps.shape[-1], img.device)
+    caps2 = caps.reshape(-1, caps.shape[-1])
+    with torch.no_grad():
+        logits = torch.randn(plan.P, hp.vocab_size, generator=torch.Generator().manual_seed(5)).cuda()
+        other = model.criterion(logits, plan.pack(caps2[:, 1:].unsqueeze(-1)).squeeze(-1), (caps2.to(torch.int32), plan))
+    assert not torch.equal(other, before["ce"]) and not torch.equal(model.criterion.last_terms["ce"], before["ce"])
+    for k in keys:
+        assert torch.equal(out[k].detach(), before[k]), k
