@@ -103,6 +103,8 @@ typedef struct sat_decoder_dims {
     float dropout;        /* nn.Dropout p of InitLSTM / DeepOutput (model.py:74,117) in training mode; 0: off     */
     float embedding_dropout; /* p of embedding_dropout (model.py:164); 0: off                                    */
     uint64_t dropout_seed;   /* masks = counter-based hash of (seed, stream, element): same seed for fwd and bwd */
+    float weight_drop;       /* train step only: DropConnect p on every lstm.weight_hh_l{l}, one mask per call (stream 3); 0: off */
+    int32_t variational_dropout; /* train step only: 1 = the embedding / DeepOutput masks keep one row per caption for all time steps */
 } sat_decoder_dims;
 
 /* state-dict tensors of the decoder; used for weights and, with the same
@@ -202,6 +204,18 @@ int sat_decoder_train_bwd_reg(const sat_decoder_dims* d, const sat_decoder_param
                               const float* dlogits_packed, const float* alphas, const float* dalphas, const sat_decoder_params* g,
                               float* dann, void* workspace, size_t workspace_bytes, void* side_stream, void* event, void* stream,
                               const float* reg_gscale);
+
+/* ------------------------------------------------------------------ weight-drop (Merity et al. 2017; Wan et al. 2013: DropConnect)
+ * The mask of the decoder train step's weight_drop on its own: for w (layers, rows, cols), element (l, r, c) has the scale
+ *   s = 0 or 1 / (1 - p), the counter hash of (seed, stream 3, index (l * rows + r) * cols + c)
+ * (the decoder: rows = 4n, cols = n, l = the LSTM layer).  0 <= p < 1; 1 <= layers <= SAT_MAX_LSTM_LAYERS.
+ * sat_weight_drop writes out_f32 = w * s and, when out_bf16 is not NULL, the bf16 rounding of the same fp32 product; out_f32 may be w.
+ * sat_weight_drop_grad multiplies g by s in place: the gradient with respect to w from the gradient with respect to w * s.
+ * sat_decoder_pack_weights: the packing launch of the train step on its own -- wcat (A + D + 4n, n) = [W_d ; W_beta ; W_hh * s(layer 0)]
+ * with d->weight_drop and d->dropout_seed (0: the plain pack), its bf16 copy (or NULL), bcat (A + D + 4n). */
+int sat_weight_drop(const float* w, float* out_f32, void* out_bf16, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream);
+int sat_weight_drop_grad(float* g, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream);
+int sat_decoder_pack_weights(const sat_decoder_dims* d, const sat_decoder_params* w, float* wcat, void* wcat_bf16, float* bcat, void* stream);
 
 /* ------------------------------------------------------------------ policy-gradient loss (self-critical sequence training; Rennie et al. 2017)
  * The REINFORCE surrogate over packed logits (P, V): every packed row p is one sampled action (targets[p]) with a weight of its own

@@ -25,7 +25,8 @@ class GemmDesc(C.Structure):
 
 class DecoderDims(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("B", "R", "T", "L", "D", "A", "m", "n", "V", "P", "deep_output", "padding_idx", "precision", "layers")] + \
-               [("embed_max_norm", C.c_float), ("dropout", C.c_float), ("embedding_dropout", C.c_float), ("dropout_seed", C.c_uint64)]
+               [("embed_max_norm", C.c_float), ("dropout", C.c_float), ("embedding_dropout", C.c_float), ("dropout_seed", C.c_uint64),
+                ("weight_drop", C.c_float), ("variational_dropout", C.c_int32)]
 
 
 PARAM_FIELDS = ("embedding", "init_f_w", "init_f_b", "init_i_w", "init_i_b", "w_ih", "w_hh", "b_ih", "b_hh",
@@ -442,6 +443,11 @@ SYMBOLS.update({          # activation regularisation (AR / TAR) of the decoder 
     "sat_decoder_train_reg_fwd": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderBatch), _vp, C.c_size_t, _vp, _vp, _vp]),
     "sat_decoder_train_bwd_reg": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), C.POINTER(DecoderBatch), _vp, _vp, _vp,
                                             C.POINTER(DecoderParams), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+})
+SYMBOLS.update({          # weight-drop on the hidden-to-hidden matrices (decoder.weight_drop / weight_drop_grad_)
+    "sat_weight_drop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f, _u64, _vp]),
+    "sat_weight_drop_grad": (C.c_int, [_vp, _i32, _i32, _i32, _f, _u64, _vp]),
+    "sat_decoder_pack_weights": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _vp, _vp, _vp]),
 })
 SYMBOLS.update({          # token losses (decoder.TokenLossFn): cross entropy, focal loss and unlikelihood in one pass over the packed logits
     "sat_token_loss_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _f, _f, _f, _f, _f, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

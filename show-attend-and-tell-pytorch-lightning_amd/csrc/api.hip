@@ -141,6 +141,31 @@ int sat_decoder_train_reg_fwd(const sat_decoder_dims* d, const sat_decoder_batch
     return decoder_reg_fwd(*d, *b, (char*)workspace, workspace_bytes, scratch, out, (hipStream_t)stream);
 }
 
+static int weight_drop_public(const char* what, const float* src, float* dst, void* dstb, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed,
+                              void* stream) {
+    if (!src || !dst) return fail(SAT_EINVAL, "%s: null pointer", what);
+    if (layers < 1 || layers > SAT_MAX_LSTM_LAYERS || rows <= 0 || cols <= 0)
+        return fail(SAT_EINVAL, "%s: layers=%d (1..%d) rows=%d cols=%d", what, layers, SAT_MAX_LSTM_LAYERS, rows, cols);
+    if (!(p >= 0.f && p < 1.f)) return fail(SAT_EINVAL, "%s: p=%g must lie in [0,1)", what, (double)p);
+    const long per = (long)rows * cols;
+    const float* s[SAT_MAX_LSTM_LAYERS] = {}; float* o[SAT_MAX_LSTM_LAYERS] = {}; __bf16* ob[SAT_MAX_LSTM_LAYERS] = {};
+    for (int l = 0; l < layers; ++l) { s[l] = src + l * per; o[l] = dst + l * per; ob[l] = dstb ? (__bf16*)dstb + l * per : nullptr; }
+    return weight_drop(s, o, ob, layers, per, 0, p, (unsigned long long)seed, (hipStream_t)stream);
+}
+int sat_weight_drop(const float* w, float* out_f32, void* out_bf16, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream) {
+    return weight_drop_public("weight_drop", w, out_f32, out_bf16, layers, rows, cols, p, seed, stream);
+}
+int sat_weight_drop_grad(float* g, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream) {
+    return weight_drop_public("weight_drop_grad", g, g, nullptr, layers, rows, cols, p, seed, stream);
+}
+
+int sat_decoder_pack_weights(const sat_decoder_dims* d, const sat_decoder_params* w, float* wcat, void* wcat_bf16, float* bcat, void* stream) {
+    SAT_TRY(check_dims(d));
+    if (!w || !w->att_dec || !w->beta_w || !w->w_hh || !w->beta_b || !w->b_ih || !w->b_hh || !wcat || !bcat)
+        return fail(SAT_EINVAL, "decoder_pack_weights: null tensor or output");
+    return pack_weights_public(*d, *w, wcat, wcat_bf16, bcat, (hipStream_t)stream);
+}
+
 static int check_activation_reg(const char* what, const void* hidden, const void* lengths, const void* p2, const char* n2, const void* p3, const char* n3,
                                 int32_t N, int32_t T1, int32_t n, int64_t P, int64_t Q) {
     if (!hidden || !lengths || !p2 || !p3)

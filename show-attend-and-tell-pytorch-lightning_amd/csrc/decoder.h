@@ -15,6 +15,11 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                 const float* reg_gscale = nullptr);                                // device (2): d loss / d (ar, tar), added into dHout in front of the time loop
 // ar / tar of the top-layer states the last decoder_fwd left in ws (activation_reg.hip)
 int decoder_reg_fwd(const sat_decoder_dims& d, const sat_decoder_batch& b, char* ws, size_t ws_bytes, void* scratch, float* out, hipStream_t st);
+// weight-drop (decoder.hip): dst[l] = src[l] * s[layer0 + l] for `layers` matrices of `per` elements, s = dropout_scale(seed, 3, L * per + k, p);
+// dst[l] may be src[l]; dstb (or its entries) may be NULL.  One launch.
+int weight_drop(const float* const* src, float* const* dst, __bf16* const* dstb, int layers, long per, int layer0, float p, unsigned long long seed, hipStream_t st);
+// the packing launch of the train step alone (layer 0: Wcat, its bf16 copy or NULL, bcat) under d.weight_drop / d.dropout_seed
+int pack_weights_public(const sat_decoder_dims& d, const sat_decoder_params& p, float* wcat, void* wcat_b, float* bcat, hipStream_t st);
 size_t activation_reg_scratch_bytes(int N, int T1, int n);
 int activation_reg_fwd(const float* hidden, const int* lengths, int N, int T1, int n, long P, long Q, void* scratch, float* out, hipStream_t st);
 int activation_reg_bwd(const float* hidden, const int* lengths, int N, int T1, int n, long P, long Q, const float* gscale, float* dH, hipStream_t st);

@@ -29,6 +29,7 @@ struct Ws {
     float *dA, *dHout, *dZout, *DZ, *DHC, *dXZ, *dHc, *dCc, *dU, *dwf_part, *dY, *colpart, *dinit_img, *df, *dmean, *slab;
     float *dmean_rows;                                           // dropout > 0: d(mean rows) of the InitLSTM backward
     float *colpart2, *slab2;                                     // scratch of decoder_bwd's leaf part when it runs on a side stream
+    float *Wup;                                                  // weight_drop > 0, layers > 1: masked W_hh of the stacked layers, [layers - 1][4n][n]
     char *zero_begin, *zero_end;                                 // [dHout .. dwf_part]: what decoder_bwd zeroes in one memset
     long slab_elems;
 };
@@ -105,6 +106,7 @@ Ws layout(const sat_decoder_dims& d, char* base) {
     // a second column-sum and split-K scratch: the leaf part of decoder_bwd on its side stream runs while the main stream uses the first
     w.colpart2 = (float*)take((size_t)cdiv(maxrows, 256) * maxcols);
     w.slab2 = (float*)take((size_t)w.slab_elems);
+    w.Wup = (d.weight_drop > 0.f && NL > 1) ? (float*)take((size_t)(NL - 1) * 4 * d.n * d.n) : nullptr;
     w.total = off;
     return w;
 }
@@ -116,6 +118,7 @@ int check_dims(const sat_decoder_dims* d) {
     SAT_REQUIRE(d->P >= 0 && (long)d->P <= (long)d->B * d->R * (d->T - 1), "decoder: packed token count %d out of range", d->P);
     SAT_REQUIRE(d->layers >= 1 && d->layers <= SAT_MAX_LSTM_LAYERS, "decoder: layers=%d outside 1..%d", d->layers, SAT_MAX_LSTM_LAYERS);
     SAT_REQUIRE(d->dropout >= 0.f && d->dropout < 1.f && d->embedding_dropout >= 0.f && d->embedding_dropout < 1.f, "decoder: dropout must lie in [0,1)");
+    SAT_REQUIRE(d->weight_drop >= 0.f && d->weight_drop < 1.f, "decoder: weight_drop=%g must lie in [0,1)", (double)d->weight_drop);
     return SAT_OK;
 }
 
@@ -158,17 +161,31 @@ static int colsum(hipStream_t st, const Ws& w, const float* x, long ld, int rows
     return launch_ok("colsum_finish");
 }
 
+// weight-drop: `layers` matrices of `per` elements, dst[l] = src[l] * mask layer (layer0 + l); one launch
+int weight_drop(const float* const* src, float* const* dst, __bf16* const* dstb, int layers, long per, int layer0, float p, unsigned long long seed, hipStream_t st) {
+    SAT_REQUIRE(layers >= 1 && layers <= SAT_MAX_LSTM_LAYERS && layer0 >= 0 && per > 0, "weight_drop: layers=%d (1..%d) layer0=%d per=%ld", layers, SAT_MAX_LSTM_LAYERS, layer0, per);
+    WeightDropLayers w = {};
+    for (int l = 0; l < layers; ++l) { w.src[l] = src[l]; w.dst[l] = dst[l]; w.dstb[l] = dstb ? dstb[l] : nullptr; }
+    hipLaunchKernelGGL(weight_drop_kernel, dim3(cdiv(layers * per, 256)), dim3(256), 0, st, w, layers, per, layer0, p, seed);
+    return launch_ok("weight_drop");
+}
+
 // ------------------------------------------------------------------ what the caption searches share with the train loop (decoder_step.h)
-int pack_step_weights(const sat_decoder_dims& d, const sat_decoder_params& p, float* Wcat, __bf16* Wcat_b, float* bcat, float* bup, hipStream_t st) {
+int pack_step_weights(const sat_decoder_dims& d, const sat_decoder_params& p, float* Wcat, __bf16* Wcat_b, float* bcat, float* bup, hipStream_t st,
+                      float weight_drop_p, unsigned long long seed) {
     const int n = d.n, HCW = d.A + d.D + 4 * n;
     hipLaunchKernelGGL(pack_wcat_kernel, dim3(cdiv((long)HCW * n + HCW, 256)), dim3(256), 0, st, p.att_dec, p.beta_w, p.w_hh, p.beta_b, p.b_ih, p.b_hh, Wcat, Wcat_b,
-                       bcat, d.A, d.D, n);
+                       bcat, d.A, d.D, n, weight_drop_p, seed);
     SAT_TRY(launch_ok("pack Wcat"));
     for (int l = 1; l < d.layers; ++l) {
         hipLaunchKernelGGL(add_kernel, dim3(cdiv(4 * n, 256)), dim3(256), 0, st, bup + (long)(l - 1) * 4 * n, p.up_b_ih[l - 1], p.up_b_hh[l - 1], (long)4 * n);
         SAT_TRY(launch_ok("bias add (stacked layer)"));
     }
     return SAT_OK;
+}
+int pack_weights_public(const sat_decoder_dims& d, const sat_decoder_params& p, float* wcat, void* wcat_b, float* bcat, hipStream_t st) {
+    sat_decoder_dims d0 = d; d0.layers = 1;          // the stacked layers' bias sums are not part of the packing launch
+    return pack_step_weights(d0, p, wcat, (__bf16*)wcat_b, bcat, nullptr, st, d.weight_drop, (unsigned long long)d.dropout_seed);
 }
 int image_begin(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int images, float* U, float* mean, float* f, float* init_img,
                 hipStream_t st) {
@@ -417,7 +434,7 @@ static int flush_outputs(hipStream_t st, const sat_decoder_dims& d, const sat_de
     if (d.dropout > 0.f) {                       // DeepOutput.dropout (model.py:130) on the packed rows
         float* ud = w.Udrop + (long)p0 * d.m;
         hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)rows * d.m, 256)), dim3(256), 0, st, u, ud, (long)rows * d.m, d.m, d.dropout,
-                           (unsigned long long)d.dropout_seed, 2u, (long)p0);
+                           (unsigned long long)d.dropout_seed, 2u, (long)p0, d.variational_dropout ? b.src_row : (const int*)nullptr, d.variational_dropout ? (int)N : 0);
         SAT_TRY(launch_ok("output dropout"));
         uin = ud;
     }
@@ -450,7 +467,16 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
 
     // packed parameters: Wcat = [W_d ; W_beta ; W_hh] (HCW, n), bcat = [0 ; b_beta ; b_ih + b_hh]
     const bool use_b = w.Hb != nullptr && attention_split_enabled();
-    SAT_TRY(pack_step_weights(d, p, w.Wcat, use_b ? w.Wcat_b : (__bf16*)nullptr, w.bcat, w.bup, st));
+    SAT_TRY(pack_step_weights(d, p, w.Wcat, use_b ? w.Wcat_b : (__bf16*)nullptr, w.bcat, w.bup, st, d.weight_drop, (unsigned long long)d.dropout_seed));
+    // weight-drop on the stacked layers: masked fp32 copies for this call, one launch (layer 0's mask went into Wcat above)
+    const float* up_w_hh[SAT_MAX_LSTM_LAYERS] = {};
+    for (int l = 1; l < NL; ++l) up_w_hh[l - 1] = w.Wup ? w.Wup + (long)(l - 1) * 4 * n * n : p.up_w_hh[l - 1];
+    if (w.Wup) {
+        float* dst[SAT_MAX_LSTM_LAYERS] = {};
+        for (int l = 1; l < NL; ++l) dst[l - 1] = w.Wup + (long)(l - 1) * 4 * n * n;
+        SAT_TRY(weight_drop(p.up_w_hh, dst, nullptr, NL - 1, 4L * n * n, 1, d.weight_drop, (unsigned long long)d.dropout_seed, st));
+    }
+    const int vper = d.variational_dropout ? N : 0;         // variational dropout: one embedding / output mask row per caption (mask_row)
 
     // att_enc and the annotation mean; without dropout InitLSTM (model.py:76-81) on the B images, then the raw reshape over the repeated rows (F3)
     SAT_TRY(image_begin(d, p, b.ann, d.B, w.U, w.mean, d.dropout > 0.f ? nullptr : w.f, w.init_img, st));
@@ -502,7 +528,7 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     if (d.embed_max_norm > 0.f) SAT_TRY(dev_fill_bytes(st, w.flags, 0, (size_t)d.V * 4));
     if (ts > 0) {
         SAT_TRY(renorm(w.Tok, ts * N));
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(ts * N), dim3(64), 0, st, p.embedding, w.Tok, w.Y, ts * N, m, d.V, d.embedding_dropout, (unsigned long long)d.dropout_seed, 0L);
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(ts * N), dim3(64), 0, st, p.embedding, w.Tok, w.Y, ts * N, m, d.V, d.embedding_dropout, (unsigned long long)d.dropout_seed, 0L, vper);
         SAT_TRY(launch_ok("embedding gather"));
         SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, w.GY, 4 * n, ts * N, 4 * n, m));
     }
@@ -518,11 +544,11 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                 hipLaunchKernelGGL(argmax_tokens_kernel, dim3(N), dim3(256), 0, st, logits, b.prow + (long)(t - 1) * N, b.lengths, w.Tok + (long)t * N, d.V, t);
                 SAT_TRY(launch_ok("argmax_tokens"));
                 SAT_TRY(renorm(w.Tok + (long)t * N, N));
-                hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, w.Tok + (long)t * N, w.Y + (long)t * N * m, N, m, d.V, d.embedding_dropout, (unsigned long long)d.dropout_seed, (long)t * N);
+                hipLaunchKernelGGL(gather_rows_kernel, dim3(N), dim3(64), 0, st, p.embedding, w.Tok + (long)t * N, w.Y + (long)t * N * m, N, m, d.V, d.embedding_dropout, (unsigned long long)d.dropout_seed, (long)t * N, vper);
                 SAT_TRY(launch_ok("embedding gather"));
             } else {                            // decision + embedding row in one launch
                 hipLaunchKernelGGL(argmax_gather_kernel, dim3(N), dim3(256), 0, st, logits, b.prow + (long)(t - 1) * N, b.lengths, w.Tok + (long)t * N, d.V, t, p.embedding,
-                                   w.Y + (long)t * N * m, m, d.embedding_dropout, (unsigned long long)d.dropout_seed, (long)t * N);
+                                   w.Y + (long)t * N * m, m, d.embedding_dropout, (unsigned long long)d.dropout_seed, (long)t * N, vper);
                 SAT_TRY(launch_ok("argmax + embedding gather"));
             }
             SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y + (long)t * N * m, m, p.w_ih, m + D, w.GY + (long)t * N * 4 * n, 4 * n, N, 4 * n, m));
@@ -550,7 +576,7 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         for (int l = 1; l < NL; ++l) {          // stacked layers: input = the layer below's new h (nn.LSTM, no inter-layer dropout: model.py:175-180)
             float* gu = GUs(t, l);
             SAT_TRY(gemm(st, A_ROW, B_ROW, Hs(t + 1, l - 1), n, p.up_w_ih[l - 1], n, gu, 4 * n, N, 4 * n, n, 0, EPI_BIAS, w.bup + (long)(l - 1) * 4 * n));
-            SAT_TRY(gemm(st, A_ROW, B_ROW, Hs(t, l), n, p.up_w_hh[l - 1], n, gu, 4 * n, N, 4 * n, n, 1));
+            SAT_TRY(gemm(st, A_ROW, B_ROW, Hs(t, l), n, up_w_hh[l - 1], n, gu, 4 * n, N, 4 * n, n, 1));
             hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, gu, 4 * n, (const float*)nullptr,
                                Cs(t, l), Hs(t, l), Cs(t + 1, l), Hs(t + 1, l), b.lengths, t, N, n);
             SAT_TRY(launch_ok("lstm_cell_fwd (stacked layer)"));
@@ -611,6 +637,9 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     auto dHcs = [&](int l) { return w.dHc + (long)l * N * n; };
     auto dCcs = [&](int l) { return w.dCc + (long)l * N * n; };
     float* const slab = w.slab; const long se = w.slab_elems;
+    // weight-drop: the state gradients flow through the masked matrices the forward left in the workspace (Wcat, Wup)
+    const float* up_w_hh[SAT_MAX_LSTM_LAYERS] = {};
+    for (int l = 1; l < NL; ++l) up_w_hh[l - 1] = w.Wup ? w.Wup + (long)(l - 1) * 4 * n * n : p.up_w_hh[l - 1];
 
     SAT_TRY(dev_fill_bytes(st, w.zero_begin, 0, (size_t)(w.zero_end - w.zero_begin)));       // dHout, dZout, dHc, dCc, dU, dwf_part
     if (NL > 1 && KR < T1 * N) SAT_TRY(dev_fill_bytes(st, w.DGU, 0, (size_t)(NL - 1) * T1 * N * 4 * n * 4));
@@ -643,7 +672,7 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                      nullptr, nullptr, w.Uact, m, 0, 0, slab, se));           // few output tiles, long reduction over the vocabulary: split-K
         if (d.dropout > 0.f) {
             hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)P * m, 256)), dim3(256), 0, st, w.dA, w.dA, (long)P * m, m, d.dropout,
-                               (unsigned long long)d.dropout_seed, 2u, 0L);
+                               (unsigned long long)d.dropout_seed, 2u, 0L, d.variational_dropout ? b.src_row : (const int*)nullptr, d.variational_dropout ? N : 0);
             SAT_TRY(launch_ok("output dropout bwd"));
         }
     }
@@ -673,7 +702,7 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
                                l == top ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(l), dCcs(l), dgu, 4 * n, b.lengths, t, N, n);
             SAT_TRY(launch_ok("lstm_cell_bwd (stacked layer)"));
             SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dgu, 4 * n, p.up_w_ih[l - 1], n, dHcs(l - 1), n, N, n, 4 * n, 1, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
-            SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dgu, 4 * n, p.up_w_hh[l - 1], n, dHcs(l), n, N, n, 4 * n, 1, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
+            SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dgu, 4 * n, up_w_hh[l - 1], n, dHcs(l), n, N, n, 4 * n, 1, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
         }
         hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, hc + A + D, HCW, Cs(t, 0),
                            Cs(t + 1, 0), top == 0 ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(0), dCcs(0), dhc + A + D, HCW, b.lengths, t, N, n,
@@ -715,6 +744,11 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
             SAT_TRY(colsum(ls, wl, dgu, 4 * n, KR, 4 * n, g.up_b_ih[l - 1]));
             SAT_TRY(dev_copy_bytes(ls, g.up_b_hh[l - 1], g.up_b_ih[l - 1], (size_t)4 * n * 4));
         }
+        if (d.weight_drop > 0.f) {      // the products above are gradients w.r.t. the MASKED matrices: times the same mask, all layers in one launch
+            float* gw[SAT_MAX_LSTM_LAYERS] = {g.w_hh};
+            for (int l = 1; l < NL; ++l) gw[l] = g.up_w_hh[l - 1];
+            SAT_TRY(weight_drop(gw, gw, nullptr, NL, 4L * n * n, 0, d.weight_drop, (unsigned long long)d.dropout_seed, ls));
+        }
         SAT_TRY(colsum(ls, wl, w.DHC + A, HCW, KR, D, g.beta_b));
         SAT_TRY(colsum(ls, wl, dG, HCW, KR, 4 * n, g.b_ih));
         SAT_TRY(dev_copy_bytes(ls, g.b_hh, g.b_ih, (size_t)4 * n * 4));
@@ -724,7 +758,7 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         SAT_TRY(gemm(ls, A_ROW, B_KMAJOR, dG, HCW, p.w_ih, m + D, w.dY, m, KR, m, 4 * n, 1));
         if (d.embedding_dropout > 0.f && KR > 0) {
             hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)KR * m, 256)), dim3(256), 0, ls, w.dY, w.dY, (long)KR * m, m, d.embedding_dropout,
-                               (unsigned long long)d.dropout_seed, 1u, 0L);
+                               (unsigned long long)d.dropout_seed, 1u, 0L, (const int*)nullptr, d.variational_dropout ? N : 0);
             SAT_TRY(launch_ok("embedding dropout bwd"));
         }
         if (KR > 0) {
@@ -877,7 +911,7 @@ int deep_output_fwd(const float* prev_embed, const float* hidden, const float* c
     }
     const float* uin = u;
     if (dropout > 0.f) {
-        hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)N * m, 256)), dim3(256), 0, st, u, udrop, (long)N * m, m, dropout, seed, 2u, 0L);
+        hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)N * m, 256)), dim3(256), 0, st, u, udrop, (long)N * m, m, dropout, seed, 2u, 0L, (const int*)nullptr, 0);
         SAT_TRY(launch_ok("output dropout"));
         uin = udrop;
     }
@@ -892,7 +926,7 @@ int deep_output_bwd(const float* dlogits, const float* hidden, const float* cont
     float* du = d_prev_embed;                 // gradient of the pre-tanh sum = gradient of the embedding input (deep); scratch of the same shape (shallow)
     if (dropout > 0.f) {
         SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dlogits, V, w_out, m, du, m, N, m, V));
-        hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)N * m, 256)), dim3(256), 0, st, du, du, (long)N * m, m, dropout, seed, 2u, 0L);
+        hipLaunchKernelGGL(dropout_rows_kernel, dim3(cdiv((long)N * m, 256)), dim3(256), 0, st, du, du, (long)N * m, m, dropout, seed, 2u, 0L, (const int*)nullptr, 0);
         SAT_TRY(launch_ok("output dropout bwd"));
         if (deep) {
             hipLaunchKernelGGL(mul_dtanh_kernel, dim3(cdiv((long)N * m, 256)), dim3(256), 0, st, du, u, (long)N * m);
@@ -956,7 +990,7 @@ int embedding_fwd(float* table, const int* tokens, float* out, int rows, int V, 
         hipLaunchKernelGGL(embedding_renorm_kernel, dim3(V), dim3(64), 0, st, table, flags, m, max_norm);
         SAT_TRY(launch_ok("embedding_renorm"));
     }
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(64), 0, st, table, tokens, out, rows, m, V, 0.f, 0ull, 0L);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(64), 0, st, table, tokens, out, rows, m, V, 0.f, 0ull, 0L, 0);
     return launch_ok("embedding gather");
 }
 // its gradient: rows of dY added into the table rows of their tokens in increasing row order (no floating-point atomics); padding row zero

@@ -49,7 +49,8 @@ __global__ void cast_block_bf16_kernel(const float* __restrict__ src, long ld, _
 
 // ---- dropout (nn.Dropout in training mode: model.py:74/78, 117/130, 164/526).  The mask is a counter-based hash of
 // (seed, stream, element index): no state, recomputed wherever it is needed (forward, backward), reproducible.
-// streams: 0 = InitLSTM mean, 1 = embedding, 2 = DeepOutput.  keep-probability 1-p, kept values scaled by 1/(1-p).
+// streams: 0 = InitLSTM mean, 1 = embedding, 2 = DeepOutput, 3 = weight-drop on the hidden-to-hidden matrices.  keep-probability 1-p,
+// kept values scaled by 1/(1-p).
 __device__ __forceinline__ float dropout_scale(unsigned long long seed, unsigned stream, unsigned long long idx, float p) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(stream + 1) + idx * 0xD1342543DE82EF95ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -59,23 +60,37 @@ __device__ __forceinline__ float dropout_scale(unsigned long long seed, unsigned
     return (u >= p) ? 1.0f / (1.0f - p) : 0.f;
 }
 
+// Which row of a mask a buffer row reads.  Per-step dropout: its own, row0 + r.  Variational (locked) dropout keeps one mask row per
+// caption for all of its time steps: `period` = N > 0 folds a time-major row t * N + i onto i, and `row_map` (the packing plan's src_row,
+// t * N + i of every packed row) takes a packed row there first.
+__device__ __forceinline__ long mask_row(long r, const int* __restrict__ row_map, int period) {
+    if (row_map) r = row_map[r];
+    return period > 0 ? r % period : r;
+}
 // dst[r, :] = table[tok[r], :] (embedding gather; tok outside [0, V) -> zeros, the ids the gradient skips), with embedding_dropout when p > 0
 __global__ void gather_rows_kernel(const float* __restrict__ table, const int* __restrict__ tok, float* __restrict__ out, int rows, int width, int V,
-                                   float p, unsigned long long seed, long row0) {
+                                   float p, unsigned long long seed, long row0, int period) {
     int r = blockIdx.x;
     if (r >= rows) return;
     int t = tok[r];
+    const long mr = mask_row(row0 + r, nullptr, period);
     for (int c = threadIdx.x; c < width; c += blockDim.x) {
         float v = (t >= 0 && t < V) ? table[(long)t * width + c] : 0.f;
-        if (p > 0.f) v *= dropout_scale(seed, 1, (unsigned long long)(row0 + r) * width + c, p);
+        if (p > 0.f) v *= dropout_scale(seed, 1, (unsigned long long)mr * width + c, p);
         out[(long)r * width + c] = v;
     }
 }
-// y[r, c] = x[r, c] * mask(stream, (row0 + r) * width + c)   (in place allowed)
+// y[r, c] = x[r, c] * mask(stream, mask_row(row0 + r) * width + c)   (in place allowed)
 __global__ void dropout_rows_kernel(const float* __restrict__ x, float* __restrict__ y, long total, int width, float p,
-                                    unsigned long long seed, unsigned stream, long row0) {
+                                    unsigned long long seed, unsigned stream, long row0, const int* __restrict__ row_map, int period) {
     long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < total) y[e] = x[e] * dropout_scale(seed, stream, (unsigned long long)row0 * width + e, p);
+    if (e >= total) return;
+    unsigned long long idx = (unsigned long long)row0 * width + e;
+    if (row_map || period > 0) {
+        const long r = e / width;
+        idx = (unsigned long long)mask_row(row0 + r, row_map, period) * width + (e - r * width);
+    }
+    y[e] = x[e] * dropout_scale(seed, stream, idx, p);
 }
 // InitLSTM with dropout: the mean of the REPEATED annotations is dropped per caption row (model.py:78 after 487)
 __global__ void init_mean_rows_kernel(const float* __restrict__ mean, float* __restrict__ out, int N, int R, int D, float p, unsigned long long seed) {
@@ -95,20 +110,47 @@ __global__ void init_mean_rows_bwd_kernel(const float* __restrict__ drows, float
 }
 
 // Packed per-step parameters in one launch: Wcat = [W_d ; W_beta ; W_hh] (A + D + 4n rows of n), its bf16 copy when the per-step GEMMs read
-// bf16 operands, and bcat = [0 ; b_beta ; b_ih + b_hh].
+// bf16 operands, and bcat = [0 ; b_beta ; b_ih + b_hh].  wd_p > 0: weight-drop, the W_hh rows (and only they) are written as W_hh * s with
+// s = dropout_scale(seed, 3, index inside W_hh = layer 0 of the (layers, 4n, n) mask, wd_p).
 __global__ void pack_wcat_kernel(const float* __restrict__ att_dec, const float* __restrict__ beta_w, const float* __restrict__ w_hh,
                                  const float* __restrict__ beta_b, const float* __restrict__ b_ih, const float* __restrict__ b_hh, float* __restrict__ Wcat,
-                                 __bf16* __restrict__ Wcat_b, float* __restrict__ bcat, int A, int D, int n) {
+                                 __bf16* __restrict__ Wcat_b, float* __restrict__ bcat, int A, int D, int n, float wd_p, unsigned long long seed) {
     const long HCW = (long)A + D + 4L * n, nw = HCW * n, e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < nw) {
         const long r = e / n;
-        const float v = r < A ? att_dec[e] : (r < A + D ? beta_w[e - (long)A * n] : w_hh[e - (long)(A + D) * n]);
+        float v;
+        if (r < A) v = att_dec[e];
+        else if (r < A + D) v = beta_w[e - (long)A * n];
+        else {
+            const long k = e - (long)(A + D) * n;
+            v = w_hh[k];
+            if (wd_p > 0.f) v *= dropout_scale(seed, 3, (unsigned long long)k, wd_p);
+        }
         Wcat[e] = v;
         if (Wcat_b) Wcat_b[e] = (__bf16)v;
     } else if (e < nw + HCW) {
         const long r = e - nw;
         bcat[r] = r < A ? 0.f : (r < A + D ? beta_b[r - A] : b_ih[r - A - D] + b_hh[r - A - D]);
     }
+}
+
+// Weight-drop (DropConnect on the hidden-to-hidden matrices) outside the pack: dst[l] = src[l] * s[layer0 + l] for `layers` matrices of
+// `per` elements each, s[L][k] = dropout_scale(seed, 3, L * per + k, p).  dst[l] may be src[l] (the weight gradients are masked in
+// place); dstb[l], when given, gets the bf16 copy of the same product.
+struct WeightDropLayers {
+    const float* src[SAT_MAX_LSTM_LAYERS]; float* dst[SAT_MAX_LSTM_LAYERS]; __bf16* dstb[SAT_MAX_LSTM_LAYERS];
+};
+__global__ void weight_drop_kernel(WeightDropLayers w, int layers, long per, int layer0, float p, unsigned long long seed) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= layers * per) return;
+    const int l = (int)(e / per); const long k = e - l * per;
+    const float* src = w.src[0]; float* dst = w.dst[0]; __bf16* dstb = w.dstb[0];
+#pragma unroll
+    for (int j = 1; j < SAT_MAX_LSTM_LAYERS; ++j)
+        if (l == j) { src = w.src[j]; dst = w.dst[j]; dstb = w.dstb[j]; }
+    const float v = src[k] * dropout_scale(seed, 3, (unsigned long long)(layer0 + l) * per + k, p);
+    dst[k] = v;
+    if (dstb) dstb[k] = (__bf16)v;
 }
 
 // token ids of step `step` for every caption row (teacher forcing): tok[i] = caps[i*T + step]
@@ -150,7 +192,7 @@ __global__ void argmax_tokens_kernel(const float* __restrict__ logits, const int
 // token of caption i at `step` = first maximum of its previous logits row, y[i, :] = embedding[token] (zeros for finished captions)
 __global__ __launch_bounds__(256) void argmax_gather_kernel(const float* __restrict__ logits, const int* __restrict__ prow_prev, const int* __restrict__ lengths,
                                                             int* __restrict__ tok, int V, int step, const float* __restrict__ table, float* __restrict__ out, int width,
-                                                            float p, unsigned long long seed, long row0) {
+                                                            float p, unsigned long long seed, long row0, int period) {
     const int i = blockIdx.x;
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -181,7 +223,7 @@ __global__ __launch_bounds__(256) void argmax_gather_kernel(const float* __restr
     const int t = live ? s_tok : -1;
     for (int c = threadIdx.x; c < width; c += 256) {
         float v = (t >= 0 && t < V) ? table[(long)t * width + c] : 0.f;          // a row without a maximum (all NaN) leaves t = INT_MAX
-        if (p > 0.f) v *= dropout_scale(seed, 1, (unsigned long long)(row0 + i) * width + c, p);
+        if (p > 0.f) v *= dropout_scale(seed, 1, (unsigned long long)mask_row(row0 + i, nullptr, period) * width + c, p);
         out[(long)i * width + c] = v;
     }
 }

@@ -23,8 +23,10 @@ inline int gemm(hipStream_t st, int amode, int bmode, const float* A, long lda, 
 
 // The start-up every decoder shares, training forward and search alike (decoder.hip).
 // Packed step weights in one launch: Wcat = [W_d ; W_beta ; W_hh] (A + D + 4n, n) with its bf16 copy (or NULL), bcat = [0 ; b_beta ;
-// b_ih + b_hh]; then bup[l - 1] = b_ih + b_hh of every stacked layer l >= 1.
-int pack_step_weights(const sat_decoder_dims& d, const sat_decoder_params& p, float* Wcat, __bf16* Wcat_b, float* bcat, float* bup, hipStream_t st);
+// b_ih + b_hh]; then bup[l - 1] = b_ih + b_hh of every stacked layer l >= 1.  weight_drop_p > 0 (the train step only; the searches never
+// pass it): the W_hh rows are written under the weight-drop mask of (seed, stream 3).
+int pack_step_weights(const sat_decoder_dims& d, const sat_decoder_params& p, float* Wcat, __bf16* Wcat_b, float* bcat, float* bup, hipStream_t st,
+                      float weight_drop_p = 0.f, unsigned long long seed = 0);
 // Per image: U = ann * W_e^T (att_enc, hoisted out of the steps) and the annotation mean; with f != NULL also InitLSTM's two Linears
 // on the `images` mean rows, f (images, m) and init_img (images, 2 * layers * n).
 int image_begin(const sat_decoder_dims& d, const sat_decoder_params& p, const float* ann, int images, float* U, float* mean, float* f, float* init_img,

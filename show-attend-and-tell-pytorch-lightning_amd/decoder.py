@@ -100,12 +100,21 @@ class PackPlan:
 
 
 def decoder_dims(B, R, T, Lc, D, A, m, n, V, P, deep, padding_idx, precision=0, embed_max_norm=0.0, dropout=0.0,
-                 embedding_dropout=0.0, dropout_seed=0, layers=1):
+                 embedding_dropout=0.0, dropout_seed=0, layers=1, weight_drop=0.0, variational_dropout=False):
     if not 1 <= int(layers) <= L.MAX_LSTM_LAYERS:
         raise ValueError("decoder_layers=%d: the library is built for 1..%d stacked LSTM layers" % (layers, L.MAX_LSTM_LAYERS))
+    check_weight_drop(weight_drop)
     return L.DecoderDims(B=B, R=R, T=T, L=Lc, D=D, A=A, m=m, n=n, V=V, P=P, deep_output=int(bool(deep)), padding_idx=padding_idx,
                          precision=int(precision), layers=int(layers), embed_max_norm=float(embed_max_norm or 0.0), dropout=float(dropout),
-                         embedding_dropout=float(embedding_dropout), dropout_seed=int(dropout_seed))
+                         embedding_dropout=float(embedding_dropout), dropout_seed=int(dropout_seed), weight_drop=float(weight_drop),
+                         variational_dropout=int(bool(variational_dropout)))
+
+
+def check_weight_drop(p):
+    """``weight_drop``: a probability in [0, 1) (0: off)"""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p < 1.0:
+        raise ValueError("weight_drop=%r: a probability in [0, 1) (0: off)" % (p,))
+    return float(p)
 
 
 def _params_struct(tensors, layers=1):
@@ -240,7 +249,11 @@ class DecoderTrainFn(torch.autograd.Function):
             _check_param(k, tens[k], shapes[k])
             if tens[k] is None and k not in ("out_context", "out_b"):
                 raise ValueError("decoder parameter %s is missing" % k)
-        dims = decoder_dims(B, R, T, Lc, D, A, m, n, V, plan.P, deep, padding_idx, precision, embed_max_norm, *dropout, layers=layers)
+        # dropout: (p, p_embedding, seed), or with weight-drop / variational dropout (p, p_embedding, seed, weight_drop, variational_dropout)
+        p_out, p_emb, seed, *more = dropout
+        weight_drop, variational = more if more else (0.0, False)
+        dims = decoder_dims(B, R, T, Lc, D, A, m, n, V, plan.P, deep, padding_idx, precision, embed_max_norm, p_out, p_emb, seed, layers=layers,
+                            weight_drop=weight_drop, variational_dropout=variational)
         ws_bytes = lib.sat_decoder_workspace_bytes(C.byref(dims))
         if ws_bytes == 0:
             raise L.SatHipError("sat_decoder_workspace_bytes: %s" % lib.sat_last_error().decode())
@@ -576,6 +589,44 @@ def dropout_scale_reference(seed, stream, idx, p):
         z ^= z >> np.uint64(31)
     u = (z >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
     return np.where(u >= np.float32(p), np.float32(1.0) / (np.float32(1.0) - np.float32(p)), np.float32(0.0)).astype(np.float32)
+
+
+def weight_drop_scale_reference(seed, layers, n, p, rows=None, layer0=0):
+    """the weight-drop scales of the decoder on the host, built on ``dropout_scale_reference``: (layers, rows, n) float32 with
+    ``s[l, r, c] = dropout_scale(seed, 3, ((layer0 + l) * rows + r) * n + c, p)``; ``rows`` defaults to the LSTM's 4n.  ``layer0``: the
+    slice of a taller mask that starts at that layer, computed alone."""
+    rows = 4 * int(n) if rows is None else int(rows)
+    per = rows * int(n)
+    idx = np.arange(int(layer0) * per, (int(layer0) + int(layers)) * per, dtype=np.uint64)
+    return dropout_scale_reference(seed, 3, idx, p).reshape(int(layers), rows, int(n))
+
+
+def _weight_drop_args(t, what):
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError("%s: a contiguous float32 (layers, rows, cols) or (rows, cols) tensor" % what)
+    L.require_gpu(t)
+    return t.shape
+
+
+def weight_drop(w, p, seed, out=None, out_bf16=None):
+    """``sat_weight_drop``: (w * s, out_bf16) for w (layers, rows, cols) with the scales of ``weight_drop_scale_reference``; ``out_bf16``,
+    when given, receives the bf16 rounding of the same product"""
+    layers, rows, cols = _weight_drop_args(w, "weight_drop")
+    out = torch.empty_like(w) if out is None else out
+    for t, dt in ((out, torch.float32), (out_bf16, torch.bfloat16)):
+        if t is not None and (t.dtype != dt or t.numel() != w.numel() or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError("weight_drop: outputs are contiguous device tensors of w's size (float32, bfloat16)")
+    L.check(L.lib().sat_weight_drop(L.ptr(w), L.ptr(out), L.ptr(out_bf16), layers, rows, cols, float(p), int(seed), L.stream_ptr()), "sat_weight_drop")
+    return out, out_bf16
+
+
+def weight_drop_grad_(g, p, seed):
+    """``sat_weight_drop_grad``: g *= s in place (the gradient w.r.t. w from the gradient w.r.t. w * s); returns g"""
+    layers, rows, cols = _weight_drop_args(g, "weight_drop_grad_")
+    L.check(L.lib().sat_weight_drop_grad(L.ptr(g), layers, rows, cols, float(p), int(seed), L.stream_ptr()), "sat_weight_drop_grad")
+    return g
 
 
 def gemm(A, B, *, amode=0, bmode=0, M=None, N=None, K=None, out=None, accumulate=False, epi=0, bias=None, e0=None, c0=0, c1=0,

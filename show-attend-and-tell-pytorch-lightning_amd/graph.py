@@ -79,8 +79,8 @@ class GraphedTrainStep:
             return "more than one process"                # the all-reduce is launched from autograd hooks, bucket by bucket
         if int(getattr(hp, "accumulate", 1) or 1) > 1:
             return "gradient accumulation"
-        if self.model.training and (float(hp.dropout) > 0.0 or float(hp.embedding_dropout) > 0.0):
-            return "dropout"                              # the mask seed of the step is a launch argument
+        if self.model.training and (float(hp.dropout) > 0.0 or float(hp.embedding_dropout) > 0.0 or float(getattr(hp, "weight_drop", 0.0)) > 0.0):
+            return "dropout"                              # the mask seed of the step is a launch argument (weight-drop's as well)
         if not hasattr(self.opt, "step_device"):
             return "optimizer is not a FusedOptimizer"
         return None

@@ -170,6 +170,9 @@ class SATDecoder(nn.Module):
             v = getattr(hp, k, 0.0)
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
                 raise ValueError("%s=%r: a finite coefficient >= 0 (0: off)" % (k, v))
+        Dk.check_weight_drop(getattr(hp, "weight_drop", 0.0))      # weight-drop and variational dropout: train_decode in training mode
+        if not isinstance(getattr(hp, "variational_dropout", False), (bool, int)):
+            raise ValueError("variational_dropout=%r: True or False" % (getattr(hp, "variational_dropout"),))
         self.pad_idx = int(hp.vocab_stoi["<PAD>"])
         # token losses: the defaults keep the label-smoothed cross entropy and its launches
         token_loss, focal_gamma, ul_alpha = getattr(hp, "token_loss", "ce"), getattr(hp, "focal_gamma", 2.0), getattr(hp, "ul_alpha", 0.0)
@@ -583,18 +586,27 @@ class SATDecoder(nn.Module):
                 cap_scores.append(fin_scores[best]); cap_ppl.append(fin_ppl[best])
         return captions, cap_scores, cap_alphas, cap_ppl
 
+    def weight_drop_args(self):
+        """(weight_drop, variational_dropout) as hyper-parameters; like nn.Dropout they act in training mode only"""
+        return float(getattr(self.hp, "weight_drop", 0.0)), bool(getattr(self.hp, "variational_dropout", False))
+
     def _dropout_args(self, seed=None):
-        """(p, p_embedding, seed) of this call: nn.Dropout is the identity in eval mode; the seed comes from a generator of
-        its own so that the CPU generator stream of scheduled sampling (F7) stays exactly the reference's."""
+        """(p, p_embedding, seed) of this call, or (p, p_embedding, seed, weight_drop, variational_dropout) when one of the last two is
+        on: nn.Dropout is the identity in eval mode, and so are they; the seed comes from a generator of its own so that the CPU generator
+        stream of scheduled sampling (F7) stays exactly the reference's."""
         p, pe = float(self.hp.dropout), float(self.hp.embedding_dropout)
-        if not self.training or (p == 0.0 and pe == 0.0):
+        wd, var = self.weight_drop_args()
+        var = var and (p > 0.0 or pe > 0.0)                 # locks the masks of those two rates: nothing to lock without them
+        if not self.training or (p == 0.0 and pe == 0.0 and wd == 0.0):
             return (0.0, 0.0, 0)
         if seed is None:
             gen = self.__dict__.get("_dropout_gen")
             if gen is None:
                 gen = self.__dict__["_dropout_gen"] = torch.Generator().manual_seed(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
             seed = int(torch.randint(0, 2 ** 62, (1,), generator=gen))
-        return (p, pe, int(seed))
+        if wd == 0.0 and not var:
+            return (p, pe, int(seed))
+        return (p, pe, int(seed), wd, var)
 
     def reg_coefficients(self):
         """(ar_alpha, tar_beta) of the activation regularisers; (0, 0): off, the step issues no launch for them"""
@@ -681,7 +693,8 @@ class SAT(SATDecoder, _Base):
         for k, v in dict(encoder_size=None, embed_norm=None, pretrained_embedding=None, pretrained=False, decoder_tf=None,
                          decoder_tf_min=0.5, epochs=10, encoder_finetune_after=-1, att_gamma=1.0, label_smoothing=0.0,
                          dropout=0.0, embedding_dropout=0.0, weight_tying=False, deep_output=False, decoder_layers=1,
-                         lr_warmup_steps=0, ar_alpha=0.0, tar_beta=0.0, token_loss="ce", focal_gamma=2.0, ul_alpha=0.0).items():
+                         lr_warmup_steps=0, ar_alpha=0.0, tar_beta=0.0, token_loss="ce", focal_gamma=2.0, ul_alpha=0.0,
+                         weight_drop=0.0, variational_dropout=False).items():
             hp.setdefault(k, v)
         self.scheduler = None
         self.opt_init_lr = None
