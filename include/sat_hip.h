@@ -126,6 +126,11 @@ typedef struct sat_decoder_params {
     /* stacked layers l = 1 .. layers-1 at index l-1: lstm.weight_ih_l{l} (4n, n), weight_hh_l{l} (4n, n), bias_ih_l{l}, bias_hh_l{l} (4n) */
     float* up_w_ih[SAT_MAX_LSTM_LAYERS - 1]; float* up_w_hh[SAT_MAX_LSTM_LAYERS - 1];
     float* up_b_ih[SAT_MAX_LSTM_LAYERS - 1]; float* up_b_hh[SAT_MAX_LSTM_LAYERS - 1];
+    /* layer-normalised LSTM cell (lstm_layer_norm; see "layer-normalised LSTM cell" below), one entry per layer l = 0 .. layers-1:
+     * lstm_ln.gates_l{l}.weight / .bias (4n), lstm_ln.cell_l{l}.weight / .bias (n).  These are the switch: all NULL (a zero-initialised
+     * struct) = the plain cell; all non-NULL for l < layers = the normalised cell; a mixture is refused. */
+    float* ln_gate_w[SAT_MAX_LSTM_LAYERS]; float* ln_gate_b[SAT_MAX_LSTM_LAYERS];
+    float* ln_cell_w[SAT_MAX_LSTM_LAYERS]; float* ln_cell_b[SAT_MAX_LSTM_LAYERS];
 } sat_decoder_params;
 
 typedef struct sat_decoder_batch {
@@ -216,6 +221,44 @@ int sat_decoder_train_bwd_reg(const sat_decoder_dims* d, const sat_decoder_param
 int sat_weight_drop(const float* w, float* out_f32, void* out_bf16, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream);
 int sat_weight_drop_grad(float* g, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream);
 int sat_decoder_pack_weights(const sat_decoder_dims* d, const sat_decoder_params* w, float* wcat, void* wcat_bf16, float* bcat, void* stream);
+
+/* ------------------------------------------------------------------ layer-normalised LSTM cell (Ba et al. 2016)
+ * With the pre-activation a = x W_ih^T + b_ih + h W_hh^T + b_hh (gate order i, f, g, o; width 4n) summed exactly as for the plain cell:
+ *   a^_k = LN(a_k; gamma_k, beta_k) over the n units of gate k;  i, f, o = sigmoid(a^), g = tanh(a^_g)
+ *   c_t = f c_{t-1} + i g (carried un-normalised);  h_t = o tanh(LN(c_t; gamma_c, beta_c))
+ * LN = layer_norm with biased variance and eps = 1e-5 (a constant of the library).  Every decoder entry point (train forward / backward,
+ * the searches, the infer step) runs this cell, still one launch per cell and step, when sat_decoder_params carries the ln_* tensors.
+ * The train step then needs a larger workspace: sat_decoder_workspace_bytes_ln (w NULL or without ln_*: sat_decoder_workspace_bytes).
+ * The searches' workspaces do not change.
+ *
+ * The two launches on caller-supplied gates:
+ * sat_lstm_ln_cell_fwd: gates (rows, 4n; row stride g_ld >= 4n) hold a, gy (rows, 4n) or NULL is added to it; rows with live[i] <= 0 carry
+ *   h and c and get zero gates (live NULL: all live); activated gates are written back in place; c_new / h_new may be c_prev / h_prev;
+ *   h_bf16 (rows, n) or NULL: bf16 copy of h_new; xhat (rows, 5n) = [x^_i x^_f x^_g x^_o c^] and rstd (rows, 5) or both NULL: what the
+ *   backward needs (live rows only).
+ * sat_lstm_ln_cell_bwd: dh_carry / dc_carry (rows, n) are read and updated as by the plain cell (dc_carry <- dc f, dh_carry <- 0 on live
+ *   rows); dh_out (rows, n) or NULL joins dh_carry; dgates (rows, 4n; stride dg_ld) = gradient of the PRE-NORM sum a, zero on dead rows;
+ *   dgates_bf16: copy with the same stride, or NULL.  part (sat_lstm_ln_slots(rows), 10n) or NULL: each block ADDS its rows' partial sums
+ *   [dgamma_gates 4n | dbeta_gates 4n | dgamma_cell n | dbeta_cell n] into its own slot (zero it before the first step; no atomics).
+ * sat_lstm_ln_param_grads: the sum over the slots in slot order into the four gradients; scratch: 16n floats.  Bit-reproducible. */
+/* The plain cell's pointwise pair on caller-supplied gates, with the arguments of the two launches above that it shares (c_new: the forward's
+ * output, read by the backward): what the time loops launch without the norm.  tools/bench_lstm_layer_norm.py times the two pairs side by side. */
+int sat_lstm_cell_pointwise_fwd(float* gates, int32_t g_ld, const float* gy, const float* c_prev, const float* h_prev, float* c_new, float* h_new,
+                                const int32_t* live, void* h_bf16, int32_t rows, int32_t n, void* stream);
+int sat_lstm_cell_pointwise_bwd(const float* gates, int32_t g_ld, const float* c_prev, const float* c_new, const float* dh_out, float* dh_carry,
+                                float* dc_carry, float* dgates, int32_t dg_ld, const int32_t* live, void* dgates_bf16, int32_t rows, int32_t n,
+                                void* stream);
+size_t sat_decoder_workspace_bytes_ln(const sat_decoder_dims* d, const sat_decoder_params* w);
+int32_t sat_lstm_ln_slots(int32_t rows);
+int sat_lstm_ln_cell_fwd(float* gates, int32_t g_ld, const float* gy, const float* c_prev, const float* h_prev, float* c_new, float* h_new,
+                         const int32_t* live, void* h_bf16, const float* ln_gate_w, const float* ln_gate_b, const float* ln_cell_w,
+                         const float* ln_cell_b, float* xhat, float* rstd, int32_t rows, int32_t n, void* stream);
+int sat_lstm_ln_cell_bwd(const float* gates, int32_t g_ld, const float* c_prev, const float* xhat, const float* rstd, const float* dh_out,
+                         float* dh_carry, float* dc_carry, float* dgates, int32_t dg_ld, const int32_t* live, void* dgates_bf16,
+                         const float* ln_gate_w, const float* ln_cell_w, const float* ln_cell_b, float* part, int32_t rows, int32_t n,
+                         void* stream);
+int sat_lstm_ln_param_grads(const float* part, int32_t slots, int32_t n, float* d_gate_w, float* d_gate_b, float* d_cell_w, float* d_cell_b,
+                            float* scratch, void* stream);
 
 /* ------------------------------------------------------------------ policy-gradient loss (self-critical sequence training; Rennie et al. 2017)
  * The REINFORCE surrogate over packed logits (P, V): every packed row p is one sampled action (targets[p]) with a weight of its own

@@ -59,8 +59,26 @@ def param_key(name):
     return UP_KEYS["up_" + base] % int(l)
 
 
+#: layer-normalised LSTM cell (lstm_layer_norm): pointer arrays indexed by the layer l >= 0, the last four fields of sat_decoder_params.
+#: They are NOT part of the decoder parameter list (``param_names``): a length of 22 means two layers, never one layer plus its norm.
+LN_FIELDS = ("ln_gate_w", "ln_gate_b", "ln_cell_w", "ln_cell_b")
+LN_KEYS = dict(ln_gate_w="lstm_ln.gates_l%d.weight", ln_gate_b="lstm_ln.gates_l%d.bias", ln_cell_w="lstm_ln.cell_l%d.weight", ln_cell_b="lstm_ln.cell_l%d.bias")
+
+
+def ln_param_names(layers=1):
+    """Order of the layer-norm group that travels next to the decoder parameter list: four tensors per layer, layer 0 first."""
+    return ["%s_l%d" % (k, l) for l in range(layers) for k in LN_FIELDS]
+
+
+def ln_param_key(name):
+    """layer-norm parameter name -> state-dict key"""
+    base, l = name.rsplit("_l", 1)
+    return LN_KEYS[base] % int(l)
+
+
 class DecoderParams(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in PARAM_FIELDS] + [(k, C.c_void_p * (MAX_LSTM_LAYERS - 1)) for k in UP_FIELDS]
+    _fields_ = [(k, C.c_void_p) for k in PARAM_FIELDS] + [(k, C.c_void_p * (MAX_LSTM_LAYERS - 1)) for k in UP_FIELDS] + \
+               [(k, C.c_void_p * MAX_LSTM_LAYERS) for k in LN_FIELDS]
 
 
 class OptTensor(C.Structure):
@@ -448,6 +466,15 @@ SYMBOLS.update({          # weight-drop on the hidden-to-hidden matrices (decode
     "sat_weight_drop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f, _u64, _vp]),
     "sat_weight_drop_grad": (C.c_int, [_vp, _i32, _i32, _i32, _f, _u64, _vp]),
     "sat_decoder_pack_weights": (C.c_int, [C.POINTER(DecoderDims), C.POINTER(DecoderParams), _vp, _vp, _vp, _vp]),
+})
+SYMBOLS.update({          # layer-normalised LSTM cell (lstm_layer_norm): the train workspace with it, the two cell launches, the finishing reduce
+    "sat_decoder_workspace_bytes_ln": (C.c_size_t, [C.POINTER(DecoderDims), C.POINTER(DecoderParams)]),
+    "sat_lstm_cell_pointwise_fwd": (C.c_int, [_vp, _i32] + [_vp] * 7 + [_i32, _i32, _vp]),
+    "sat_lstm_cell_pointwise_bwd": (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i32, _vp, _vp, _i32, _i32, _vp]),
+    "sat_lstm_ln_slots": (C.c_int32, [_i32]),
+    "sat_lstm_ln_cell_fwd": (C.c_int, [_vp, _i32] + [_vp] * 13 + [_i32, _i32, _vp]),
+    "sat_lstm_ln_cell_bwd": (C.c_int, [_vp, _i32] + [_vp] * 7 + [_i32] + [_vp] * 6 + [_i32, _i32, _vp]),
+    "sat_lstm_ln_param_grads": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 })
 SYMBOLS.update({          # token losses (decoder.TokenLossFn): cross entropy, focal loss and unlikelihood in one pass over the packed logits
     "sat_token_loss_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _f, _f, _f, _f, _f, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -3,6 +3,7 @@
 
 #include "../../include/sat_hip.h"
 #include "decoder.h"
+#include "decoder_step.h"
 #include "gemm.h"
 #include "gemm_bf16_common.h"
 #include "temperature.h"
@@ -72,6 +73,11 @@ size_t sat_decoder_workspace_bytes(const sat_decoder_dims* d) {
     return decoder_workspace_bytes(*d);
 }
 
+size_t sat_decoder_workspace_bytes_ln(const sat_decoder_dims* d, const sat_decoder_params* w) {
+    if (check_dims(d) != SAT_OK) return 0;
+    return decoder_workspace_bytes(*d, w && ln_on(*w));
+}
+
 static int check_params(const sat_decoder_dims* d, const sat_decoder_params* w, const char* what) {
     if (!w) return fail(SAT_EINVAL, "%s: null parameter struct", what);
     if (!w->embedding || !w->init_f_w || !w->init_f_b || !w->init_i_w || !w->init_i_b || !w->w_ih || !w->w_hh || !w->b_ih || !w->b_hh ||
@@ -81,6 +87,12 @@ static int check_params(const sat_decoder_dims* d, const sat_decoder_params* w, 
     for (int l = 1; l < d->layers; ++l)
         if (!w->up_w_ih[l - 1] || !w->up_w_hh[l - 1] || !w->up_b_ih[l - 1] || !w->up_b_hh[l - 1])
             return fail(SAT_EINVAL, "%s: null tensor for LSTM layer %d", what, l);
+    // the layer-norm tensors are the switch of the normalised cell: all of them for the layers in use, or none
+    int ln_set = 0;
+    for (int l = 0; l < d->layers; ++l) ln_set += (w->ln_gate_w[l] != nullptr) + (w->ln_gate_b[l] != nullptr) + (w->ln_cell_w[l] != nullptr) + (w->ln_cell_b[l] != nullptr);
+    if (ln_set != 0 && ln_set != 4 * d->layers)
+        return fail(SAT_EINVAL, "%s: %d of the %d layer-norm tensors (ln_gate_w / ln_gate_b / ln_cell_w / ln_cell_b of %d layers) are set: all or none", what, ln_set,
+                    4 * d->layers, d->layers);
     return SAT_OK;
 }
 static int check_batch(const sat_decoder_batch* b) {
@@ -157,6 +169,46 @@ int sat_weight_drop(const float* w, float* out_f32, void* out_bf16, int32_t laye
 }
 int sat_weight_drop_grad(float* g, int32_t layers, int32_t rows, int32_t cols, float p, uint64_t seed, void* stream) {
     return weight_drop_public("weight_drop_grad", g, g, nullptr, layers, rows, cols, p, seed, stream);
+}
+
+int sat_lstm_cell_pointwise_fwd(float* gates, int32_t g_ld, const float* gy, const float* c_prev, const float* h_prev, float* c_new, float* h_new,
+                                const int32_t* live, void* h_bf16, int32_t rows, int32_t n, void* stream) {
+    if (!gates || !c_prev || !h_prev || !c_new || !h_new) return fail(SAT_EINVAL, "lstm_cell_pointwise_fwd: null pointer");
+    if (rows < 1 || n < 1 || g_ld < 4 * (int64_t)n) return fail(SAT_EINVAL, "lstm_cell_pointwise_fwd: bad shape (rows=%d n=%d g_ld=%d)", rows, n, g_ld);
+    return lstm_cell_plain_fwd(gates, g_ld, gy, c_prev, h_prev, c_new, h_new, live, 0, rows, n, h_bf16, (hipStream_t)stream);
+}
+int sat_lstm_cell_pointwise_bwd(const float* gates, int32_t g_ld, const float* c_prev, const float* c_new, const float* dh_out, float* dh_carry, float* dc_carry,
+                                float* dgates, int32_t dg_ld, const int32_t* live, void* dgates_bf16, int32_t rows, int32_t n, void* stream) {
+    if (!gates || !c_prev || !c_new || !dh_carry || !dc_carry || !dgates) return fail(SAT_EINVAL, "lstm_cell_pointwise_bwd: null pointer");
+    if (rows < 1 || n < 1 || g_ld < 4 * (int64_t)n || dg_ld < 4 * (int64_t)n)
+        return fail(SAT_EINVAL, "lstm_cell_pointwise_bwd: bad shape (rows=%d n=%d g_ld=%d dg_ld=%d)", rows, n, g_ld, dg_ld);
+    return lstm_cell_plain_bwd(gates, g_ld, c_prev, c_new, dh_out, dh_carry, dc_carry, dgates, dg_ld, live, 0, rows, n, dgates_bf16, (hipStream_t)stream);
+}
+int32_t sat_lstm_ln_slots(int32_t rows) { return ln_slots(rows); }
+int sat_lstm_ln_cell_fwd(float* gates, int32_t g_ld, const float* gy, const float* c_prev, const float* h_prev, float* c_new, float* h_new, const int32_t* live,
+                         void* h_bf16, const float* ln_gate_w, const float* ln_gate_b, const float* ln_cell_w, const float* ln_cell_b, float* xhat, float* rstd,
+                         int32_t rows, int32_t n, void* stream) {
+    if (!gates || !c_prev || !h_prev || !c_new || !h_new || !ln_gate_w || !ln_gate_b || !ln_cell_w || !ln_cell_b) return fail(SAT_EINVAL, "lstm_ln_cell_fwd: null pointer");
+    if ((xhat != nullptr) != (rstd != nullptr)) return fail(SAT_EINVAL, "lstm_ln_cell_fwd: xhat and rstd go together");
+    if (rows < 1 || n < 1 || g_ld < 4 * (int64_t)n) return fail(SAT_EINVAL, "lstm_ln_cell_fwd: bad shape (rows=%d n=%d g_ld=%d)", rows, n, g_ld);
+    const LnCell ln{ln_gate_w, ln_gate_b, ln_cell_w, ln_cell_b};
+    return lstm_ln_cell_fwd(gates, g_ld, gy, c_prev, h_prev, c_new, h_new, live, 0, rows, n, h_bf16, ln, xhat, rstd, (hipStream_t)stream);
+}
+int sat_lstm_ln_cell_bwd(const float* gates, int32_t g_ld, const float* c_prev, const float* xhat, const float* rstd, const float* dh_out, float* dh_carry,
+                         float* dc_carry, float* dgates, int32_t dg_ld, const int32_t* live, void* dgates_bf16, const float* ln_gate_w, const float* ln_cell_w,
+                         const float* ln_cell_b, float* part, int32_t rows, int32_t n, void* stream) {
+    if (!gates || !c_prev || !xhat || !rstd || !dh_carry || !dc_carry || !dgates || !ln_gate_w || !ln_cell_w || !ln_cell_b)
+        return fail(SAT_EINVAL, "lstm_ln_cell_bwd: null pointer");
+    if (rows < 1 || n < 1 || g_ld < 4 * (int64_t)n || dg_ld < 4 * (int64_t)n)
+        return fail(SAT_EINVAL, "lstm_ln_cell_bwd: bad shape (rows=%d n=%d g_ld=%d dg_ld=%d)", rows, n, g_ld, dg_ld);
+    const LnCell ln{ln_gate_w, nullptr, ln_cell_w, ln_cell_b};
+    return lstm_ln_cell_bwd(gates, g_ld, c_prev, xhat, rstd, dh_out, dh_carry, dc_carry, dgates, dg_ld, live, 0, rows, n, dgates_bf16, ln, part, (hipStream_t)stream);
+}
+int sat_lstm_ln_param_grads(const float* part, int32_t slots, int32_t n, float* d_gate_w, float* d_gate_b, float* d_cell_w, float* d_cell_b, float* scratch,
+                            void* stream) {
+    if (!part || !d_gate_w || !d_gate_b || !d_cell_w || !d_cell_b || !scratch) return fail(SAT_EINVAL, "lstm_ln_param_grads: null pointer");
+    if (slots < 1 || slots > sat_lstm_ln_slots(slots) || n < 1) return fail(SAT_EINVAL, "lstm_ln_param_grads: bad shape (slots=%d n=%d)", slots, n);
+    return ln_param_grads(part, slots, n, d_gate_w, d_gate_b, d_cell_w, d_cell_b, scratch, (hipStream_t)stream);
 }
 
 int sat_decoder_pack_weights(const sat_decoder_dims* d, const sat_decoder_params* w, float* wcat, void* wcat_bf16, float* bcat, void* stream) {

@@ -6,7 +6,7 @@
 namespace sat {
 struct Ws;
 int check_dims(const sat_decoder_dims* d);
-size_t decoder_workspace_bytes(const sat_decoder_dims& d);
+size_t decoder_workspace_bytes(const sat_decoder_dims& d, bool ln = false);      // ln: with what the layer-normalised cell saves
 int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, float* logits, float* alphas,
                 char* ws, size_t ws_bytes, hipStream_t st);
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,

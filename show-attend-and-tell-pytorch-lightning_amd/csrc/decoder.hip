@@ -30,11 +30,15 @@ struct Ws {
     float *dmean_rows;                                           // dropout > 0: d(mean rows) of the InitLSTM backward
     float *colpart2, *slab2;                                     // scratch of decoder_bwd's leaf part when it runs on a side stream
     float *Wup;                                                  // weight_drop > 0, layers > 1: masked W_hh of the stacked layers, [layers - 1][4n][n]
+    // layer-normalised cell only, carved last (every other pointer is where the plain cell has it): what the forward saves for the backward,
+    // [layers][T1][N][5n] normalised values and [layers][T1][N][5] reciprocal standard deviations; the parameter-gradient partials [layers][slots][10n]
+    float *ln_xhat, *ln_rstd, *ln_part;
+    int ln_nslots;
     char *zero_begin, *zero_end;                                 // [dHout .. dwf_part]: what decoder_bwd zeroes in one memset
     long slab_elems;
 };
 
-Ws layout(const sat_decoder_dims& d, char* base) {
+Ws layout(const sat_decoder_dims& d, char* base, bool ln = false) {
     Ws w; size_t off = 0;
     const long N = (long)d.B * d.R, T1 = d.T - 1, HCW = d.A + d.D + 4L * d.n;
     auto take = [&](size_t elems, size_t esz = 4) { size_t o = off; off += (elems * esz + 255) & ~(size_t)255; return base ? base + o : (char*)nullptr; };
@@ -107,6 +111,12 @@ Ws layout(const sat_decoder_dims& d, char* base) {
     w.colpart2 = (float*)take((size_t)cdiv(maxrows, 256) * maxcols);
     w.slab2 = (float*)take((size_t)w.slab_elems);
     w.Wup = (d.weight_drop > 0.f && NL > 1) ? (float*)take((size_t)(NL - 1) * 4 * d.n * d.n) : nullptr;
+    w.ln_xhat = w.ln_rstd = w.ln_part = nullptr; w.ln_nslots = 0;
+    if (ln) {
+        w.ln_nslots = ln_slots((int)N);
+        w.ln_xhat = (float*)take((size_t)NL * T1 * N * 5 * d.n); w.ln_rstd = (float*)take((size_t)NL * T1 * N * 5);
+        w.ln_part = (float*)take((size_t)NL * w.ln_nslots * 10 * d.n);
+    }
     w.total = off;
     return w;
 }
@@ -200,10 +210,51 @@ int image_begin(const sat_decoder_dims& d, const sat_decoder_params& p, const fl
     return gemm(st, A_ROW, B_ROW, f, d.m, p.init_i_w, d.m, init_img, n2, images, n2, d.m, 0, EPI_BIAS, p.init_i_b);
 }
 int lstm_cell_pointwise(float* gates, int g_ld, const float* c_prev, const float* h_prev, float* c_new, float* h_new, const int* live, int rows, int n,
-                        hipStream_t st) {
+                        hipStream_t st, const LnCell* ln) {
+    if (ln) return lstm_ln_cell_fwd(gates, g_ld, nullptr, c_prev, h_prev, c_new, h_new, live, 0, rows, n, nullptr, *ln, nullptr, nullptr, st);
     hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)rows * n, 256)), dim3(256), 0, st, gates, g_ld, (const float*)nullptr, c_prev, h_prev, c_new, h_new, live,
                        0, rows, n, (__bf16*)nullptr);
     return launch_ok("lstm_cell_fwd");
+}
+
+// the plain pair on caller-supplied gates (sat_lstm_cell_pointwise_fwd / _bwd): the launches of the time loops, for tools that time them
+int lstm_cell_plain_fwd(float* gates, int g_ld, const float* gy, const float* c_prev, const float* h_prev, float* c_new, float* h_new, const int* lengths, int step,
+                        int rows, int n, void* hb_new, hipStream_t st) {
+    hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)rows * n, 256)), dim3(256), 0, st, gates, g_ld, gy, c_prev, h_prev, c_new, h_new, lengths, step, rows, n,
+                       reinterpret_cast<__bf16*>(hb_new));
+    return launch_ok("lstm_cell_fwd");
+}
+int lstm_cell_plain_bwd(const float* gates, int g_ld, const float* c_prev, const float* c_new, const float* dh_out, float* dh_carry, float* dc_carry, float* dgates,
+                        int dg_ld, const int* lengths, int step, int rows, int n, void* dgb, hipStream_t st) {
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(cdiv((long)rows * n, 256)), dim3(256), 0, st, gates, g_ld, c_prev, c_new, dh_out, dh_carry, dc_carry, dgates, dg_ld,
+                       lengths, step, rows, n, reinterpret_cast<__bf16*>(dgb));
+    return launch_ok("lstm_cell_bwd");
+}
+
+static int ensure_dynamic_lds(const void* kernel, size_t bytes);
+// ------------------------------------------------------------------ layer-normalised cell: launch forms
+// One block per row up to LN_MAX_SLOTS blocks (the backward's partial-sum slots), rows beyond that strided over the blocks; 64, 128 or 256
+// threads by the width of a gate; the row (5n floats) and the cross-wave partials in dynamic LDS.
+int ln_slots(int rows) { return rows < LN_MAX_SLOTS ? (rows < 1 ? 1 : rows) : LN_MAX_SLOTS; }
+static int ln_threads(int n) { return n <= 64 ? 64 : n <= 128 ? 128 : 256; }
+static size_t ln_lds(int n) { return (size_t)(LN_RED + 5L * n) * 4; }
+int lstm_ln_cell_fwd(float* gates, int g_ld, const float* gy, const float* c_prev, const float* h_prev, float* c_new, float* h_new, const int* lengths, int step,
+                     int rows, int n, void* hb_new, const LnCell& ln, float* xhat, float* rstd, hipStream_t st) {
+    const size_t lds = ln_lds(n);
+    SAT_REQUIRE(lds <= 160 * 1024, "lstm_ln_cell_fwd: n=%d needs %zu B of LDS (> 160 KiB)", n, lds);
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_ln_cell_fwd_kernel), lds));
+    hipLaunchKernelGGL(lstm_ln_cell_fwd_kernel, dim3(ln_slots(rows)), dim3(ln_threads(n)), lds, st, gates, g_ld, gy, c_prev, h_prev, c_new, h_new, lengths, step, rows, n,
+                       reinterpret_cast<__bf16*>(hb_new), ln.gate_w, ln.gate_b, ln.cell_w, ln.cell_b, xhat, rstd);
+    return launch_ok("lstm_ln_cell_fwd");
+}
+int lstm_ln_cell_bwd(const float* gates, int g_ld, const float* c_prev, const float* xhat, const float* rstd, const float* dh_out, float* dh_carry, float* dc_carry,
+                     float* dgates, int dg_ld, const int* lengths, int step, int rows, int n, void* dgb, const LnCell& ln, float* part, hipStream_t st) {
+    const size_t lds = ln_lds(n);
+    SAT_REQUIRE(lds <= 160 * 1024, "lstm_ln_cell_bwd: n=%d needs %zu B of LDS (> 160 KiB)", n, lds);
+    SAT_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_ln_cell_bwd_kernel), lds));
+    hipLaunchKernelGGL(lstm_ln_cell_bwd_kernel, dim3(ln_slots(rows)), dim3(ln_threads(n)), lds, st, gates, g_ld, c_prev, xhat, rstd, dh_out, dh_carry, dc_carry, dgates,
+                       dg_ld, lengths, step, rows, n, reinterpret_cast<__bf16*>(dgb), ln.gate_w, ln.cell_w, ln.cell_b, part);
+    return launch_ok("lstm_ln_cell_bwd");
 }
 
 static int live_steps(const sat_decoder_dims& d, const sat_decoder_batch& b) {
@@ -451,7 +502,8 @@ static int flush_outputs(hipStream_t st, const sat_decoder_dims& d, const sat_de
 
 int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, float* logits, float* alphas,
                        char* ws, size_t ws_bytes, hipStream_t st) {
-    Ws w = layout(d, ws);
+    const bool ln = ln_on(p);
+    Ws w = layout(d, ws, ln);
     t_bf16_mfma = d.precision ? 1 : 0;
     SAT_REQUIRE(ws_bytes >= w.total, "decoder_fwd: workspace %zu < %zu bytes", ws_bytes, w.total);
     SAT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "decoder: workspace must be 256-byte aligned");
@@ -461,6 +513,8 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     auto Hs = [&](int t, int l) { return w.H_all + l * LS + (long)t * N * n; };
     auto Cs = [&](int t, int l) { return w.C_all + l * LS + (long)t * N * n; };
     auto GUs = [&](int t, int l) { return w.GU + ((long)(l - 1) * T1 + t) * N * 4 * n; };
+    auto LnX = [&](int t, int l) { return w.ln_xhat + ((long)l * T1 + t) * N * 5 * n; };       // layer-normalised cell: saved for the backward
+    auto LnR = [&](int t, int l) { return w.ln_rstd + ((long)l * T1 + t) * N * 5; };
     const int ts = live_steps(d, b);
     SAT_REQUIRE(b.step_offsets_host[T1] == d.P, "decoder: step_offsets[T-1]=%d != P=%d", b.step_offsets_host[T1], d.P);
     for (int t = 0; t < ts; ++t) SAT_REQUIRE(b.teacher_host[t] || t > 0, "decoder: step 0 must be teacher forced");
@@ -570,13 +624,23 @@ int decoder_fwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         // gates += (beta*z) * W_ih[:, m:]^T
         if (use_b) SAT_TRY(gemm_bb_nt(st, w.XZb, D, w.Wz_b, D, hc + A + D, HCW, N, 4 * n, D, EPI_NONE, nullptr, 1));
         else SAT_TRY(gemm(st, A_ROW, B_ROW, w.XZ + (long)t * N * D, D, p.w_ih + m, m + D, hc + A + D, HCW, N, 4 * n, D, 1));
-        hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, hc + A + D, HCW, w.GY + (long)t * N * 4 * n,
-                           Cs(t, 0), Hs(t, 0), Cs(t + 1, 0), Hs(t + 1, 0), b.lengths, t, N, n, use_b ? w.Hb + (long)(t + 1) * N * n : (__bf16*)nullptr);
-        SAT_TRY(launch_ok("lstm_cell_fwd"));
+        if (ln) {       // the layer-normalised cell: the same single launch in the step
+            SAT_TRY(lstm_ln_cell_fwd(hc + A + D, HCW, w.GY + (long)t * N * 4 * n, Cs(t, 0), Hs(t, 0), Cs(t + 1, 0), Hs(t + 1, 0), b.lengths, t, N, n,
+                                     use_b ? w.Hb + (long)(t + 1) * N * n : (__bf16*)nullptr, ln_layer(p, 0), LnX(t, 0), LnR(t, 0), st));
+        } else {
+            hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, hc + A + D, HCW, w.GY + (long)t * N * 4 * n,
+                               Cs(t, 0), Hs(t, 0), Cs(t + 1, 0), Hs(t + 1, 0), b.lengths, t, N, n, use_b ? w.Hb + (long)(t + 1) * N * n : (__bf16*)nullptr);
+            SAT_TRY(launch_ok("lstm_cell_fwd"));
+        }
         for (int l = 1; l < NL; ++l) {          // stacked layers: input = the layer below's new h (nn.LSTM, no inter-layer dropout: model.py:175-180)
             float* gu = GUs(t, l);
             SAT_TRY(gemm(st, A_ROW, B_ROW, Hs(t + 1, l - 1), n, p.up_w_ih[l - 1], n, gu, 4 * n, N, 4 * n, n, 0, EPI_BIAS, w.bup + (long)(l - 1) * 4 * n));
             SAT_TRY(gemm(st, A_ROW, B_ROW, Hs(t, l), n, up_w_hh[l - 1], n, gu, 4 * n, N, 4 * n, n, 1));
+            if (ln) {
+                SAT_TRY(lstm_ln_cell_fwd(gu, 4 * n, nullptr, Cs(t, l), Hs(t, l), Cs(t + 1, l), Hs(t + 1, l), b.lengths, t, N, n, nullptr, ln_layer(p, l), LnX(t, l),
+                                         LnR(t, l), st));
+                continue;
+            }
             hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, gu, 4 * n, (const float*)nullptr,
                                Cs(t, l), Hs(t, l), Cs(t + 1, l), Hs(t + 1, l), b.lengths, t, N, n);
             SAT_TRY(launch_ok("lstm_cell_fwd (stacked layer)"));
@@ -600,7 +664,9 @@ int decoder_reg_fwd(const sat_decoder_dims& d, const sat_decoder_batch& b, char*
 int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sat_decoder_batch& b, const float* dlogits,
                        const float* alphas, const float* dalphas, const sat_decoder_params& g, float* dann, char* ws, size_t ws_bytes, hipStream_t st,
                        hipStream_t side, hipEvent_t fork_event, const float* reg_gscale) {
-    Ws w = layout(d, ws);
+    const bool ln = ln_on(p);
+    SAT_REQUIRE(ln == ln_on(g), "decoder_bwd: the layer-norm tensors are %s in the parameters and %s in the gradients", ln ? "set" : "NULL", ln ? "NULL" : "set");
+    Ws w = layout(d, ws, ln);
     t_bf16_mfma = d.precision ? 1 : 0;
     SAT_REQUIRE(ws_bytes >= w.total, "decoder_bwd: workspace %zu < %zu bytes", ws_bytes, w.total);
     SAT_REQUIRE(!side || fork_event, "decoder_bwd: side stream without event");
@@ -620,6 +686,7 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     //   mean_rows  the critical chain used to put d(mean rows) back into it while g.init_f_w still wants the forward's values: it has a
     //              buffer of its own now (dmean_rows)
     //   emb_count / emb_offset / emb_cursor / emb_list, colpart2, slab2   leaf scratch; st keeps colpart and slab
+    //   ln_part   (layer-normalised cell) zeroed before and accumulated by the time loop; read by the leaf sums over its slots only
     // The critical launches after the event write dmean, dmean_rows and dann only.
     const bool fork = side != nullptr;
     const hipStream_t ls = fork ? side : st;                    // where the leaf part goes
@@ -636,6 +703,9 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
     auto DGUs = [&](int t, int l) { return w.DGU + ((long)(l - 1) * T1 + t) * N * 4 * n; };
     auto dHcs = [&](int l) { return w.dHc + (long)l * N * n; };
     auto dCcs = [&](int l) { return w.dCc + (long)l * N * n; };
+    auto LnX = [&](int t, int l) { return w.ln_xhat + ((long)l * T1 + t) * N * 5 * n; };
+    auto LnR = [&](int t, int l) { return w.ln_rstd + ((long)l * T1 + t) * N * 5; };
+    auto LnP = [&](int l) { return w.ln_part + (long)l * w.ln_nslots * 10 * n; };
     float* const slab = w.slab; const long se = w.slab_elems;
     // weight-drop: the state gradients flow through the masked matrices the forward left in the workspace (Wcat, Wup)
     const float* up_w_hh[SAT_MAX_LSTM_LAYERS] = {};
@@ -643,6 +713,7 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
 
     SAT_TRY(dev_fill_bytes(st, w.zero_begin, 0, (size_t)(w.zero_end - w.zero_begin)));       // dHout, dZout, dHc, dCc, dU, dwf_part
     if (NL > 1 && KR < T1 * N) SAT_TRY(dev_fill_bytes(st, w.DGU, 0, (size_t)(NL - 1) * T1 * N * 4 * n * 4));
+    if (ln) SAT_TRY(dev_fill_bytes(st, w.ln_part, 0, (size_t)NL * w.ln_nslots * 10 * n * 4));
 
     // ---- output layer, all packed rows at once (DeepOutput backward)
     float* const lslab = wl.slab;
@@ -698,16 +769,26 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
         float* dhc = w.DHC + (long)t * N * HCW;
         for (int l = top; l >= 1; --l) {        // stacked layers, top down: gate grads, then into the layer below and the own past
             float* dgu = DGUs(t, l);
-            hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, GUs(t, l), 4 * n, Cs(t, l), Cs(t + 1, l),
-                               l == top ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(l), dCcs(l), dgu, 4 * n, b.lengths, t, N, n);
-            SAT_TRY(launch_ok("lstm_cell_bwd (stacked layer)"));
+            if (ln) {
+                SAT_TRY(lstm_ln_cell_bwd(GUs(t, l), 4 * n, Cs(t, l), LnX(t, l), LnR(t, l), l == top ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(l),
+                                         dCcs(l), dgu, 4 * n, b.lengths, t, N, n, nullptr, ln_layer(p, l), LnP(l), st));
+            } else {
+                hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, GUs(t, l), 4 * n, Cs(t, l), Cs(t + 1, l),
+                                   l == top ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(l), dCcs(l), dgu, 4 * n, b.lengths, t, N, n);
+                SAT_TRY(launch_ok("lstm_cell_bwd (stacked layer)"));
+            }
             SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dgu, 4 * n, p.up_w_ih[l - 1], n, dHcs(l - 1), n, N, n, 4 * n, 1, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
             SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dgu, 4 * n, up_w_hh[l - 1], n, dHcs(l), n, N, n, 4 * n, 1, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
         }
-        hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, hc + A + D, HCW, Cs(t, 0),
-                           Cs(t + 1, 0), top == 0 ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(0), dCcs(0), dhc + A + D, HCW, b.lengths, t, N, n,
-                           use_b ? w.DHCb + A + D : (__bf16*)nullptr);
-        SAT_TRY(launch_ok("lstm_cell_bwd"));
+        if (ln) {
+            SAT_TRY(lstm_ln_cell_bwd(hc + A + D, HCW, Cs(t, 0), LnX(t, 0), LnR(t, 0), top == 0 ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(0), dCcs(0),
+                                     dhc + A + D, HCW, b.lengths, t, N, n, use_b ? w.DHCb + A + D : (__bf16*)nullptr, ln_layer(p, 0), LnP(0), st));
+        } else {
+            hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(cdiv((long)N * n, 256)), dim3(256), 0, st, hc + A + D, HCW, Cs(t, 0),
+                               Cs(t + 1, 0), top == 0 ? w.dHout + (long)t * N * n : (const float*)nullptr, dHcs(0), dCcs(0), dhc + A + D, HCW, b.lengths, t, N, n,
+                               use_b ? w.DHCb + A + D : (__bf16*)nullptr);
+            SAT_TRY(launch_ok("lstm_cell_bwd"));
+        }
         // d(beta*z) = dG * W_ih[:, m:]
         if (use_b) SAT_TRY(gemm_bb_nn(st, w.DHCb + A + D, HCW, w.Wz_b, D, w.dXZ, D, N, D, 4 * n, 0, slab, se));
         else SAT_TRY(gemm(st, A_ROW, B_KMAJOR, dhc + A + D, HCW, p.w_ih + m, m + D, w.dXZ, D, N, D, 4 * n, 0, EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, slab, se));
@@ -749,6 +830,9 @@ int decoder_bwd(const sat_decoder_dims& d, const sat_decoder_params& p, const sa
             for (int l = 1; l < NL; ++l) gw[l] = g.up_w_hh[l - 1];
             SAT_TRY(weight_drop(gw, gw, nullptr, NL, 4L * n * n, 0, d.weight_drop, (unsigned long long)d.dropout_seed, ls));
         }
+        // layer-normalised cell: the sum over the slots of the time loop's partials, per layer (leaf work)
+        for (int l = 0; ln && l < NL; ++l)
+            SAT_TRY(ln_param_grads(LnP(l), w.ln_nslots, n, g.ln_gate_w[l], g.ln_gate_b[l], g.ln_cell_w[l], g.ln_cell_b[l], wl.colpart, ls));
         SAT_TRY(colsum(ls, wl, w.DHC + A, HCW, KR, D, g.beta_b));
         SAT_TRY(colsum(ls, wl, dG, HCW, KR, 4 * n, g.b_ih));
         SAT_TRY(dev_copy_bytes(ls, g.b_hh, g.b_ih, (size_t)4 * n * 4));
@@ -841,7 +925,14 @@ int colsum_public(const float* x, long ld, long rows, int cols, float* out, floa
     return colsum(st, w, x, ld, (int)rows, cols, out);
 }
 
-size_t decoder_workspace_bytes(const sat_decoder_dims& d) { return layout(d, nullptr).total; }
+size_t decoder_workspace_bytes(const sat_decoder_dims& d, bool ln) { return layout(d, nullptr, ln).total; }
+int ln_param_grads(const float* part, int slots, int n, float* dgate_w, float* dgate_b, float* dcell_w, float* dcell_b, float* scratch, hipStream_t st) {
+    Ws w; w.colpart = scratch;
+    SAT_TRY(colsum(st, w, part, 10L * n, slots, 4 * n, dgate_w));
+    SAT_TRY(colsum(st, w, part + 4L * n, 10L * n, slots, 4 * n, dgate_b));
+    SAT_TRY(colsum(st, w, part + 8L * n, 10L * n, slots, n, dcell_w));
+    return colsum(st, w, part + 9L * n, 10L * n, slots, n, dcell_b);
+}
 
 
 // ------------------------------------------------------------------ sub-module step entry points (SURVEY 8b minimum set)

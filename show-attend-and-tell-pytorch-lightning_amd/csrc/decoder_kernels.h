@@ -582,6 +582,187 @@ __global__ void lstm_cell_bwd_kernel(const float* __restrict__ gates, int g_ld, 
     dh_carry[idx] = 0.f;
 }
 
+// ------------------------------------------------------------------ layer-normalised LSTM cell (Ba et al. 2016)
+//   x^_k = (a_k - mean_k) * rstd_k, k in {i,f,g,o} over the n units of each gate;  i,f,o = sigmoid, g = tanh of gamma_k x^_k + beta_k
+//   c_t = f c_{t-1} + i g (carried un-normalised);  c^ = (c_t - mean_c) * rstd_c;  h_t = o tanh(gamma_c c^ + beta_c)
+// biased variance, eps = LN_EPS; mean first, then the squared deviations (two passes over the row in LDS).
+// One block walks rows blockIdx.x, blockIdx.x + gridDim.x, ...; a thread owns the units tid, tid + blockDim.x, ... of its row in every
+// pass, so everything it reads back from LDS or from an in-place buffer (c_new == c_prev, h_new == h_prev) it wrote or read itself.
+// dyn LDS: [LN_RED floats: cross-wave partials][5n floats: the row]
+constexpr float LN_EPS = 1e-5f;
+constexpr int LN_RED = 32;                     // 8 sums x 4 waves
+constexpr int LN_MAX_SLOTS = 1024;             // blocks (= partial-sum slots of the backward kernel): one row a block up to here (C2: 640 rows)
+
+// the K sums of a block, the same bits in every thread: lanes by shuffle, waves in index order through LDS
+template <int K>
+__device__ __forceinline__ void ln_block_sum(float (&v)[K], float* s_red) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+    const int nw = blockDim.x >> 6;
+    if (nw == 1) return;
+    __syncthreads();                           // the previous sums have been read
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) s_red[(threadIdx.x >> 6) * K + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) { float s = 0.f; for (int w = 0; w < nw; ++w) s += s_red[w * K + k]; v[k] = s; }
+}
+
+// Same contract as lstm_cell_fwd_kernel (gates in place, gy addend, lengths / step mask, bf16 copy of h).  xhat (N, 5n) = [x^_i x^_f x^_g
+// x^_o c^] and rstd (N, 5) are saved for the backward pass when xhat is not NULL (dead rows: not written).
+__global__ void lstm_ln_cell_fwd_kernel(float* gates, int g_ld, const float* __restrict__ gy, const float* c_prev, const float* h_prev,
+                                        float* c_new, float* h_new, const int* __restrict__ lengths, int step, int N, int n, __bf16* hb_new,
+                                        const float* __restrict__ gam_g, const float* __restrict__ bet_g, const float* __restrict__ gam_c,
+                                        const float* __restrict__ bet_c, float* __restrict__ xhat, float* __restrict__ rstd) {
+    extern __shared__ __attribute__((aligned(16))) float ln_sm[];
+    float* s_red = ln_sm; float* s_row = ln_sm + LN_RED;
+    const int tid = threadIdx.x, bd = blockDim.x;
+    const float inv_n = 1.f / (float)n;
+    for (int row = blockIdx.x; row < N; row += gridDim.x) {
+        float* g = gates + (long)row * g_ld;
+        const long r0 = (long)row * n;
+        if (lengths && lengths[row] <= step) {           // finished caption: state carried, zero gates (block-uniform branch)
+            for (int j = tid; j < n; j += bd) {
+                const float hp = h_prev[r0 + j];
+                c_new[r0 + j] = c_prev[r0 + j]; h_new[r0 + j] = hp;
+                if (hb_new) hb_new[r0 + j] = (__bf16)hp;
+                g[j] = 0.f; g[n + j] = 0.f; g[2 * n + j] = 0.f; g[3 * n + j] = 0.f;
+            }
+            continue;
+        }
+        const float* y = gy ? gy + (long)row * 4 * n : nullptr;
+        float mu[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int j = tid; j < n; j += bd) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const float a = g[k * n + j] + (y ? y[k * n + j] : 0.f); s_row[k * n + j] = a; mu[k] += a; }
+        }
+        ln_block_sum<4>(mu, s_red);
+        float rs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mu[k] *= inv_n;
+        for (int j = tid; j < n; j += bd) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const float dlt = s_row[k * n + j] - mu[k]; rs[k] = fmaf(dlt, dlt, rs[k]); }
+        }
+        ln_block_sum<4>(rs, s_red);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rs[k] = 1.f / sqrtf(rs[k] * inv_n + LN_EPS);
+        float* xh = xhat ? xhat + (long)row * 5 * n : nullptr;
+        float mc[1] = {0.f};
+        for (int j = tid; j < n; j += bd) {
+            float act[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float x = (s_row[k * n + j] - mu[k]) * rs[k];
+                if (xh) xh[k * n + j] = x;
+                act[k] = fmaf(x, gam_g[k * n + j], bet_g[k * n + j]);
+            }
+            const float gi = fast_sigmoid(act[0]), gf = fast_sigmoid(act[1]), gg = fast_tanh(act[2]), go = fast_sigmoid(act[3]);
+            const float c = gf * c_prev[r0 + j] + gi * gg;
+            c_new[r0 + j] = c;
+            g[j] = gi; g[n + j] = gf; g[2 * n + j] = gg; g[3 * n + j] = go;
+            s_row[3 * n + j] = go; s_row[4 * n + j] = c;
+            mc[0] += c;
+        }
+        ln_block_sum<1>(mc, s_red);
+        const float mean_c = mc[0] * inv_n;
+        float qc[1] = {0.f};
+        for (int j = tid; j < n; j += bd) { const float dlt = s_row[4 * n + j] - mean_c; qc[0] = fmaf(dlt, dlt, qc[0]); }
+        ln_block_sum<1>(qc, s_red);
+        const float rs_c = 1.f / sqrtf(qc[0] * inv_n + LN_EPS);
+        for (int j = tid; j < n; j += bd) {
+            const float ch = (s_row[4 * n + j] - mean_c) * rs_c;
+            if (xh) xh[4 * n + j] = ch;
+            const float hn = s_row[3 * n + j] * fast_tanh(fmaf(ch, gam_c[j], bet_c[j]));
+            h_new[r0 + j] = hn;
+            if (hb_new) hb_new[r0 + j] = (__bf16)hn;
+        }
+        if (rstd && tid == 0) { float* r = rstd + (long)row * 5; r[0] = rs[0]; r[1] = rs[1]; r[2] = rs[2]; r[3] = rs[3]; r[4] = rs_c; }
+    }
+}
+
+// Same contract as lstm_cell_bwd_kernel (dh_carry / dc_carry, dead rows: zero dgates, bf16 copy of dgates); dgates is the gradient of the
+// PRE-NORM sum a.  Per live row:
+//   dh = dh_carry + dh_out;  tc = tanh(gamma_c c^ + beta_c);  du = dh o (1 - tc^2);  d a^_o = dh tc o (1 - o)
+//   d c^ = du gamma_c;  dc = dc_carry + rstd_c (d c^ - mean(d c^) - c^ mean(d c^ c^))                            two row sums
+//   d a^_i = dc g i (1 - i), d a^_f = dc c_{t-1} f (1 - f), d a^_g = dc i (1 - g^2);  d x^_k = d a^_k gamma_k
+//   d a_k = rstd_k (d x^_k - mean(d x^_k) - x^_k mean(d x^_k x^_k))                                              eight row sums
+// Parameter gradients: block b ADDS its rows' d a^_k x^_k, d a^_k, du c^, du into slot b of part (gridDim.x, 10n) =
+// [dgamma_g 4n | dbeta_g 4n | dgamma_c n | dbeta_c n] with a plain read-modify-write; a slot has one writer per launch, the launches of a
+// backward pass follow each other on one stream, and the sum over slots comes after the loop: fixed order, no atomics.  part NULL: skipped.
+__global__ void lstm_ln_cell_bwd_kernel(const float* __restrict__ gates, int g_ld, const float* __restrict__ c_prev, const float* __restrict__ xhat,
+                                        const float* __restrict__ rstd, const float* __restrict__ dh_out, float* __restrict__ dh_carry,
+                                        float* __restrict__ dc_carry, float* __restrict__ dgates, int dg_ld, const int* __restrict__ lengths, int step,
+                                        int N, int n, __bf16* __restrict__ dgb, const float* __restrict__ gam_g, const float* __restrict__ gam_c,
+                                        const float* __restrict__ bet_c, float* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) float ln_sm[];
+    float* s_red = ln_sm; float* s_row = ln_sm + LN_RED;
+    const int tid = threadIdx.x, bd = blockDim.x;
+    const float inv_n = 1.f / (float)n;
+    float* slot = part ? part + (long)blockIdx.x * 10 * n : nullptr;
+    for (int row = blockIdx.x; row < N; row += gridDim.x) {
+        float* dg = dgates + (long)row * dg_ld;
+        __bf16* db = dgb ? dgb + (long)row * dg_ld : nullptr;
+        if (lengths && lengths[row] <= step) {
+            for (int j = tid; j < n; j += bd) {
+                dg[j] = 0.f; dg[n + j] = 0.f; dg[2 * n + j] = 0.f; dg[3 * n + j] = 0.f;
+                if (db) { db[j] = (__bf16)0.f; db[n + j] = (__bf16)0.f; db[2 * n + j] = (__bf16)0.f; db[3 * n + j] = (__bf16)0.f; }
+            }
+            continue;
+        }
+        const float* g = gates + (long)row * g_ld;
+        const float* xh = xhat + (long)row * 5 * n;
+        const float* rr = rstd + (long)row * 5;
+        const float rs[4] = {rr[0], rr[1], rr[2], rr[3]};
+        const float rs_c = rr[4];
+        const long r0 = (long)row * n;
+        float sc[2] = {0.f, 0.f};
+        for (int j = tid; j < n; j += bd) {
+            const float go = g[3 * n + j], ch = xh[4 * n + j], gc = gam_c[j];
+            const float tc = fast_tanh(fmaf(ch, gc, bet_c[j]));
+            const float dh = dh_carry[r0 + j] + (dh_out ? dh_out[r0 + j] : 0.f);
+            const float du = dh * go * (1.f - tc * tc);
+            if (slot) { slot[8 * n + j] += du * ch; slot[9 * n + j] += du; }
+            const float dch = du * gc;
+            s_row[3 * n + j] = dh * tc * go * (1.f - go);
+            s_row[4 * n + j] = dch;
+            sc[0] += dch; sc[1] = fmaf(dch, ch, sc[1]);
+        }
+        ln_block_sum<2>(sc, s_red);
+        const float m1 = sc[0] * inv_n, m2 = sc[1] * inv_n;
+        float sg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int j = tid; j < n; j += bd) {
+            const float ch = xh[4 * n + j];
+            const float dc = dc_carry[r0 + j] + rs_c * (s_row[4 * n + j] - m1 - ch * m2);
+            const float gi = g[j], gf = g[n + j], gg = g[2 * n + j];
+            const float da[4] = {dc * gg * gi * (1.f - gi), dc * c_prev[r0 + j] * gf * (1.f - gf), dc * gi * (1.f - gg * gg), s_row[3 * n + j]};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float x = xh[k * n + j];
+                if (slot) { slot[k * n + j] += da[k] * x; slot[4 * n + k * n + j] += da[k]; }
+                const float dx = da[k] * gam_g[k * n + j];
+                s_row[k * n + j] = dx;
+                sg[k] += dx; sg[4 + k] = fmaf(dx, x, sg[4 + k]);
+            }
+            dc_carry[r0 + j] = dc * gf;
+            dh_carry[r0 + j] = 0.f;
+        }
+        ln_block_sum<8>(sg, s_red);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) sg[k] *= inv_n;
+        for (int j = tid; j < n; j += bd) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = rs[k] * (s_row[k * n + j] - sg[k] - xh[k * n + j] * sg[4 + k]);
+                dg[k * n + j] = d;
+                if (db) db[k * n + j] = (__bf16)d;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ attention backward (one decode step)
 // grid = B; block = 256.  Per live caption row i of image b:
 //   dz = dZ_out + dXZ*beta ; dbeta_pre = dXZ * z * beta(1-beta)

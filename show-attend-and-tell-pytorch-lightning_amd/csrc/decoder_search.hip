@@ -68,13 +68,16 @@ static int step_run(const sat_decoder_dims& d, const sat_decoder_params& p, cons
     if (noise) SAT_TRY(gemm(st, A_ROW, B_ROW, noise, n, w_hh, n, gates, HCW, N, 4 * n, n, 1));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.Y, m, p.w_ih, m + D, gates, HCW, N, 4 * n, m, 1));
     SAT_TRY(gemm(st, A_ROW, B_ROW, w.XZ, D, p.w_ih + m, m + D, gates, HCW, N, 4 * n, D, 1));
-    SAT_TRY(lstm_cell_pointwise(gates, HCW, c, h, c, h, live, N, n, st));
+    const bool ln = ln_on(p);                   // the layer-normalised cell: the same launch count, nothing saved
+    LnCell lc = ln ? ln_layer(p, 0) : LnCell();
+    SAT_TRY(lstm_cell_pointwise(gates, HCW, c, h, c, h, live, N, n, st, ln ? &lc : nullptr));
     for (int l = 1; l < NL; ++l) {              // stacked layers: input = the layer below's new h (nn.LSTM, no inter-layer dropout)
         float* hl = h + l * KS; float* cl = c + l * KS;
         SAT_TRY(gemm(st, A_ROW, B_ROW, hl - KS, n, p.up_w_ih[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 0, EPI_BIAS, w.bup + (long)(l - 1) * 4 * n));
         SAT_TRY(gemm(st, A_ROW, B_ROW, hl, n, p.up_w_hh[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 1));
         if (noise) SAT_TRY(gemm(st, A_ROW, B_ROW, noise + l * KS, n, p.up_w_hh[l - 1], n, w.gu, 4 * n, N, 4 * n, n, 1));
-        SAT_TRY(lstm_cell_pointwise(w.gu, 4 * n, cl, hl, cl, hl, live, N, n, st));
+        if (ln) lc = ln_layer(p, l);
+        SAT_TRY(lstm_cell_pointwise(w.gu, 4 * n, cl, hl, cl, hl, live, N, n, st, ln ? &lc : nullptr));
     }
     SAT_TRY(gemm(st, A_ROW, B_ROW, htop, n, p.out_hidden, n, w.u, m, N, m, n));
     if (d.deep_output) SAT_TRY(gemm(st, A_ROW, B_ROW, w.Z, D, p.out_context, D, w.u, m, N, m, D, 1, EPI_ADD_TANH, nullptr, nullptr, nullptr, w.Y, m));

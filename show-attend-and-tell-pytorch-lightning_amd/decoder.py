@@ -117,7 +117,8 @@ def check_weight_drop(p):
     return float(p)
 
 
-def _params_struct(tensors, layers=1):
+def _params_struct(tensors, layers=1, ln=None):
+    """``ln``: the layer-norm group of the normalised cell by name (``_lib.ln_param_names``), or None: those fields stay NULL = the plain cell"""
     s = L.DecoderParams()
     for k in L.PARAM_FIELDS:
         t = tensors.get(k)
@@ -126,7 +127,22 @@ def _params_struct(tensors, layers=1):
         arr = getattr(s, k)
         for l in range(1, layers):
             arr[l - 1] = tensors["%s_l%d" % (k[3:], l)].data_ptr()
+    if ln:
+        for k in L.LN_FIELDS:
+            arr = getattr(s, k)
+            for l in range(layers):
+                arr[l] = ln["%s_l%d" % (k, l)].data_ptr()
     return s
+
+
+def split_ln(params, n_ln):
+    """(decoder parameter list, layer-norm group) of the trailing-group form ``*params, *ln`` with ``n_ln`` layer-norm tensors (0: none)"""
+    n_ln = int(n_ln)
+    if n_ln == 0:
+        return list(params), []
+    if n_ln < 0 or n_ln % len(L.LN_FIELDS) or n_ln // len(L.LN_FIELDS) != layers_of(len(params) - n_ln):
+        raise ValueError("layer-norm group of %d tensors after %d decoder parameters; expected 4 per LSTM layer" % (n_ln, len(params) - n_ln))
+    return list(params[:-n_ln]), list(params[-n_ln:])
 
 
 def layers_of(n_params):
@@ -225,13 +241,16 @@ class DecoderTrainFn(torch.autograd.Function):
         return DecoderTrainFn._backward(ctx, dlogits, dalphas, None)
 
     @staticmethod
-    def _forward(ctx, with_reg, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params):
-        """the body of both Functions; ``with_reg``: a third output, the (ar, tar) pair of the top-layer states (``DecoderTrainRegFn``)"""
+    def _forward(ctx, with_reg, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params, n_ln=0):
+        """the body of all four Functions; ``with_reg``: a third output, the (ar, tar) pair of the top-layer states (``DecoderTrainRegFn``);
+        ``n_ln``: the last ``n_ln`` tensors of ``params`` are the layer-norm group (``_lib.ln_param_names``) of the normalised cell"""
         lib = L.lib()
-        L.require_gpu(ann, caps_i32, *[p for p in params if p is not None])
+        params, ln_params = split_ln(params, n_ln)
+        L.require_gpu(ann, caps_i32, *[p for p in params if p is not None], *ln_params)
         layers = layers_of(len(params))
         names = L.param_names(layers)
         tens = dict(zip(names, params))
+        ln_tens = dict(zip(L.ln_param_names(layers), ln_params))
         ann = ann.contiguous()
         B, Lc, D = ann.shape
         V, m = tens["embedding"].shape
@@ -249,12 +268,17 @@ class DecoderTrainFn(torch.autograd.Function):
             _check_param(k, tens[k], shapes[k])
             if tens[k] is None and k not in ("out_context", "out_b"):
                 raise ValueError("decoder parameter %s is missing" % k)
+        for k, t in ln_tens.items():
+            if t is None:
+                raise ValueError("layer-norm parameter %s is missing" % k)
+            _check_param(k, t, (4 * n,) if k.startswith("ln_gate") else (n,))
         # dropout: (p, p_embedding, seed), or with weight-drop / variational dropout (p, p_embedding, seed, weight_drop, variational_dropout)
         p_out, p_emb, seed, *more = dropout
         weight_drop, variational = more if more else (0.0, False)
         dims = decoder_dims(B, R, T, Lc, D, A, m, n, V, plan.P, deep, padding_idx, precision, embed_max_norm, p_out, p_emb, seed, layers=layers,
                             weight_drop=weight_drop, variational_dropout=variational)
-        ws_bytes = lib.sat_decoder_workspace_bytes(C.byref(dims))
+        w = _params_struct(tens, layers, ln_tens)
+        ws_bytes = lib.sat_decoder_workspace_bytes_ln(C.byref(dims), C.byref(w)) if ln_tens else lib.sat_decoder_workspace_bytes(C.byref(dims))
         if ws_bytes == 0:
             raise L.SatHipError("sat_decoder_workspace_bytes: %s" % lib.sat_last_error().decode())
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=ann.device)
@@ -264,13 +288,13 @@ class DecoderTrainFn(torch.autograd.Function):
         batch = L.DecoderBatch(ann=ann.data_ptr(), caps=caps_i32.data_ptr(), lengths=plan.lengths.data_ptr(), prow=plan.prow.data_ptr(),
                                src_row=plan.src_row.data_ptr(), step_offsets_host=plan.offsets_host.ctypes.data,
                                teacher_host=teacher.ctypes.data)
-        w = _params_struct(tens, layers)
         L.check(lib.sat_decoder_train_fwd(C.byref(dims), C.byref(w), C.byref(batch), L.ptr(logits), L.ptr(alphas), L.ptr(ws), ws_bytes,
                                           L.stream_ptr()), "sat_decoder_train_fwd")
         ctx.dims, ctx.plan, ctx.teacher, ctx.ws, ctx.ws_bytes = dims, plan, teacher, ws, ws_bytes
         ctx.caps, ctx.layers, ctx.leaf_side = caps_i32, layers, bool(leaf_side)
-        ctx.save_for_backward(ann, alphas, *[p for p in params if p is not None])
+        ctx.save_for_backward(ann, alphas, *[p for p in params if p is not None], *ln_params)
         ctx.present = [p is not None for p in params]
+        ctx.n_ln = len(ln_params)
         if not with_reg:
             return logits, alphas
         scratch = torch.empty(lib.sat_activation_reg_scratch_bytes(N, T - 1, n), dtype=torch.uint8, device=ann.device)
@@ -289,6 +313,8 @@ class DecoderTrainFn(torch.autograd.Function):
         params = [next(it) if present else None for present in ctx.present]
         names = L.param_names(ctx.layers)
         tens = dict(zip(names, params))
+        n_ln = getattr(ctx, "n_ln", 0)
+        ln_tens = dict(zip(L.ln_param_names(ctx.layers), list(it))) if n_ln else {}
         plan, dims = ctx.plan, ctx.dims
         taken = set()
 
@@ -299,6 +325,7 @@ class DecoderTrainFn(torch.autograd.Function):
             return L.grad_buffer(t)
 
         grads = {k: (None if t is None else gbuf(t)) for k, t in tens.items()}
+        ln_grads = {k: gbuf(t) for k, t in ln_tens.items()}
         dann = torch.empty_like(ann)
         if dlogits is None:
             dlogits = torch.zeros(plan.P, dims.V, dtype=torch.float32, device=ann.device)
@@ -307,9 +334,9 @@ class DecoderTrainFn(torch.autograd.Function):
         batch = L.DecoderBatch(ann=ann.data_ptr(), caps=ctx.caps.data_ptr(), lengths=plan.lengths.data_ptr(), prow=plan.prow.data_ptr(),
                                src_row=plan.src_row.data_ptr(), step_offsets_host=plan.offsets_host.ctypes.data,
                                teacher_host=ctx.teacher.ctypes.data)
-        w, g = _params_struct(tens, ctx.layers), _params_struct(grads, ctx.layers)
+        w, g = _params_struct(tens, ctx.layers, ln_tens), _params_struct(grads, ctx.layers, ln_grads)
         side_ptr = ev_ptr = None
-        if ctx.leaf_side and ctx.needs_input_grad[0] and _leaf_side_allowed(tens, len(taken)):
+        if ctx.leaf_side and ctx.needs_input_grad[0] and _leaf_side_allowed({**tens, **ln_tens}, len(taken)):
             # dann is all the encoder backward waits for: the parameter gradients go to the encoder's side stream, ahead of its weight
             # gradients, and the main stream waits for them when the backward pass ends (nothing may read a .grad before that)
             dev = ann.device
@@ -327,7 +354,7 @@ class DecoderTrainFn(torch.autograd.Function):
         if side_ptr is not None:
             # what the side stream reads, and what it writes (autograd drops the gradient of a frozen parameter at once): the allocator must
             # not hand these blocks out again before the side stream is done
-            for t in (ctx.ws, dlogits, ann, *grads.values()):
+            for t in (ctx.ws, dlogits, ann, *grads.values(), *ln_grads.values()):
                 if t is not None:
                     t.record_stream(side)
             done_ev.record(side)
@@ -343,6 +370,8 @@ class DecoderTrainFn(torch.autograd.Function):
                 torch.autograd.Variable._execution_engine.queue_callback(join)          # runs when this backward pass has finished
             except RuntimeError:                      # not called by the autograd engine
                 join()
+        if n_ln:          # DecoderTrainLNFn / DecoderTrainLNRegFn: one more leading argument (n_ln), the layer-norm group behind the parameters
+            return (dann, None, None, None, None, None, None, None, None, None, None, None, *[grads[k] for k in names], *ln_grads.values())
         return (dann, None, None, None, None, None, None, None, None, None, None, *[grads[k] for k in names])
 
 
@@ -354,6 +383,36 @@ class DecoderTrainRegFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params):
         return DecoderTrainFn._forward(ctx, True, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params)
+
+    @staticmethod
+    def backward(ctx, dlogits, dalphas, dreg):
+        return DecoderTrainFn._backward(ctx, dlogits, dalphas, dreg)
+
+
+class DecoderTrainLNFn(torch.autograd.Function):
+    """``DecoderTrainFn`` with the layer-normalised LSTM cell ("Layer-normalised LSTM"): ``n_ln`` = 4 * layers, and the
+    last ``n_ln`` tensors behind the decoder parameter list are the layer-norm group in ``_lib.ln_param_names`` order.  The parameter
+    list itself keeps its meaning (18 + 4 per stacked layer)."""
+
+    @staticmethod
+    def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, n_ln, *params):
+        if not n_ln:
+            raise ValueError("DecoderTrainLNFn: n_ln = 4 * layers layer-norm tensors (the plain cell: DecoderTrainFn)")
+        return DecoderTrainFn._forward(ctx, False, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params, n_ln=n_ln)
+
+    @staticmethod
+    def backward(ctx, dlogits, dalphas):
+        return DecoderTrainFn._backward(ctx, dlogits, dalphas, None)
+
+
+class DecoderTrainLNRegFn(torch.autograd.Function):
+    """``DecoderTrainLNFn`` with ``DecoderTrainRegFn``'s third output"""
+
+    @staticmethod
+    def forward(ctx, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, n_ln, *params):
+        if not n_ln:
+            raise ValueError("DecoderTrainLNRegFn: n_ln = 4 * layers layer-norm tensors (the plain cell: DecoderTrainRegFn)")
+        return DecoderTrainFn._forward(ctx, True, ann, caps_i32, plan, teacher, deep, padding_idx, R, precision, embed_max_norm, dropout, leaf_side, *params, n_ln=n_ln)
 
     @staticmethod
     def backward(ctx, dlogits, dalphas, dreg):

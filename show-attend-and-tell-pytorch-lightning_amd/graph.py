@@ -147,12 +147,13 @@ class GraphedTrainStep:
             caps2 = caps.reshape(Bn * R, T)
             caps_i32 = caps2.to(dtype=torch.int32).contiguous()
             dec_params = model.param_list()
+            ln_params = model.ln_param_list()                   # the layer-normalised cell: its group behind the parameter list, as train_decode
             dctx = _Ctx()
             ar_alpha, tar_beta = model.reg_coefficients()
             with_reg = bool(ar_alpha or tar_beta)               # the activation regularisers: DecoderTrainRegFn's third output, as SAT._step_losses
             logits, alphas, *reg = Dk.DecoderTrainFn._forward(dctx, with_reg, ann_bld, caps_i32, plan, teacher, bool(hp.deep_output), model.pad_idx, R,
                                                               int(model.sat_precision == "bf16"), getattr(hp, "embed_norm", None) or 0.0,
-                                                              model._dropout_args(None), False, *dec_params)      # no side-stream fork of the parameter gradients: no engine ends this backward
+                                                              model._dropout_args(None), False, *dec_params, *ln_params, n_ln=len(ln_params))      # no side-stream fork of the parameter gradients: no engine ends this backward
             targets = plan.pack(caps2[:, 1:].unsqueeze(-1)).squeeze(-1)
             cctx, sctx = _Ctx(), _Ctx()
             token_loss = model.token_loss_on()                  # TokenLoss in the criterion's place, as SAT._step_losses
@@ -188,7 +189,7 @@ class GraphedTrainStep:
                 else:
                     grads[id(p)] = (p, g)
 
-            for p, g in zip(dec_params, douts[11:]):
+            for p, g in zip(dec_params + ln_params, douts[12 if ln_params else 11:]):
                 give(p, g)
             if any(p.requires_grad for p in enc_params):
                 eouts = enc.Fn.backward(ectx, dann.reshape(Bn, h, w, D).permute(0, 3, 1, 2))
@@ -242,7 +243,7 @@ class GraphedTrainStep:
             self.stats["eager: " + why] += 1
             return self._eager(batch, epsilon, gstep, teacher)
         key = (tuple(img.shape), tuple(caps.shape), lengths.numpy().tobytes(), np.asarray(teacher, np.int32).tobytes(), float(epsilon),
-               model.sat_precision, model.training, self._params_sig(), model.reg_coefficients(), model.token_loss_key())
+               model.sat_precision, model.training, self._params_sig(), model.reg_coefficients(), model.token_loss_key(), model.lstm_layer_norm_on())
         stale = self._stale_copies()
         if stale:
             self._graphs.clear()                          # filter copies are about to be remade: every graph points at the old ones

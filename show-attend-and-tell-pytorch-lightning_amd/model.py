@@ -20,7 +20,7 @@ from . import _lib as L
 from . import constraints
 from . import decoder as Dk
 from . import encoder as E
-from .modules import DeepOutput, Embedding, Gate, InitLSTM, LSTM, SoftAttention  # noqa: F401  (the reference's module names, model.py:66-131)
+from .modules import DeepOutput, Embedding, Gate, InitLSTM, LSTM, LSTMLayerNorm, SoftAttention  # noqa: F401  (the reference's module names, model.py:66-131)
 from .encoder import get_encoder  # noqa: F401  (module-level name, as in the reference)
 
 try:                                     # Lightning is optional plumbing (absent in the build image)
@@ -173,6 +173,8 @@ class SATDecoder(nn.Module):
         Dk.check_weight_drop(getattr(hp, "weight_drop", 0.0))      # weight-drop and variational dropout: train_decode in training mode
         if not isinstance(getattr(hp, "variational_dropout", False), (bool, int)):
             raise ValueError("variational_dropout=%r: True or False" % (getattr(hp, "variational_dropout"),))
+        if not isinstance(getattr(hp, "lstm_layer_norm", False), (bool, int)) or getattr(hp, "lstm_layer_norm", False) not in (0, 1):
+            raise ValueError("lstm_layer_norm=%r: True or False" % (getattr(hp, "lstm_layer_norm"),))
         self.pad_idx = int(hp.vocab_stoi["<PAD>"])
         # token losses: the defaults keep the label-smoothed cross entropy and its launches
         token_loss, focal_gamma, ul_alpha = getattr(hp, "token_loss", "ce"), getattr(hp, "focal_gamma", 2.0), getattr(hp, "ul_alpha", 0.0)
@@ -184,6 +186,8 @@ class SATDecoder(nn.Module):
         self.embedding_dropout = nn.Dropout(p=hp.embedding_dropout)
         self.init_lstm = InitLSTM(hp, bias=True)
         self.lstm = LSTM(input_size=hp.embed_dim + hp.encoder_dim, hidden_size=hp.decoder_dim, num_layers=hp.decoder_layers, bias=True)
+        if getattr(hp, "lstm_layer_norm", False):           # layer-normalised cell: off, the module does not exist and the state dict is the reference's
+            self.lstm_ln = LSTMLayerNorm(hp.decoder_dim, hp.decoder_layers)
         self.attention = SoftAttention(hp)
         self.beta = Gate(nn.Linear(hp.decoder_dim, hp.encoder_dim, bias=True), nn.Sigmoid())
         fan_in = self.beta[0].weight.shape[1]
@@ -202,6 +206,18 @@ class SATDecoder(nn.Module):
                 self.beta[0].weight, self.beta[0].bias, o.hidden.weight, (o.context.weight if o.deep else None),
                 o.output.weight, o.output.bias] + up
 
+    def lstm_layer_norm_on(self):
+        return getattr(self, "lstm_ln", None) is not None
+
+    def ln_param_list(self):
+        """the layer-norm group of the normalised cell in ``_lib.ln_param_names`` order ([] with the plain cell): it travels next to
+        ``param_list()``, never inside it"""
+        if not self.lstm_layer_norm_on():
+            return []
+        ln = self.lstm_ln
+        return [getattr(getattr(ln, "%s_l%d" % (mod, l)), par) for l in range(self.hp.decoder_layers)
+                for mod, par in (("gates", "weight"), ("gates", "bias"), ("cell", "weight"), ("cell", "bias"))]
+
     def load_decoder_state(self, sd):
         own = self.state_dict()
         for k, v in sd.items():
@@ -212,7 +228,8 @@ class SATDecoder(nn.Module):
     def _params_struct(self):
         layers = self.hp.decoder_layers
         tens = dict(zip(L.param_names(layers), self.param_list()))
-        return Dk._params_struct(tens, layers), tens
+        ln = dict(zip(L.ln_param_names(layers), self.ln_param_list()))
+        return Dk._params_struct(tens, layers, ln), {**tens, **ln}
 
     @torch.no_grad()
     def beam_decode(self, ann_bld, hw, beamk=3, max_gen_length=32, temperature=1.0, sample_method="beam", sample_topk=3,
@@ -659,10 +676,14 @@ class SATDecoder(nn.Module):
             teacher = plan.teacher_flags(float(epsilon), draw)
         caps2 = caps.reshape(B * R, T)
         caps_i32 = caps2.to(device=ann_bld.device, dtype=torch.int32).contiguous()
-        fn = Dk.DecoderTrainRegFn if with_reg else Dk.DecoderTrainFn
+        ln = self.ln_param_list()
+        if ln:              # the normalised cell: the same call with the layer-norm group behind the parameter list
+            fn = Dk.DecoderTrainLNRegFn if with_reg else Dk.DecoderTrainLNFn
+        else:
+            fn = Dk.DecoderTrainRegFn if with_reg else Dk.DecoderTrainFn
         logits_packed, alphas, *reg = fn.apply(ann_bld, caps_i32, plan, teacher, bool(self.hp.deep_output), self.pad_idx, R,
                                                int(getattr(self, "sat_precision", "fp32") == "bf16"), getattr(self.hp, "embed_norm", None) or 0.0,
-                                               self._dropout_args(dropout_seed), bool(leaf_side), *self.param_list())
+                                               self._dropout_args(dropout_seed), bool(leaf_side), *([len(ln)] if ln else []), *self.param_list(), *ln)
         targets_packed = plan.pack(caps2[:, 1:].to(ann_bld.device).unsqueeze(-1)).squeeze(-1)
         extra = dict(reg=reg[0]) if with_reg else {}
         if not with_loss:
@@ -694,7 +715,7 @@ class SAT(SATDecoder, _Base):
                          decoder_tf_min=0.5, epochs=10, encoder_finetune_after=-1, att_gamma=1.0, label_smoothing=0.0,
                          dropout=0.0, embedding_dropout=0.0, weight_tying=False, deep_output=False, decoder_layers=1,
                          lr_warmup_steps=0, ar_alpha=0.0, tar_beta=0.0, token_loss="ce", focal_gamma=2.0, ul_alpha=0.0,
-                         weight_drop=0.0, variational_dropout=False).items():
+                         weight_drop=0.0, variational_dropout=False, lstm_layer_norm=False).items():
             hp.setdefault(k, v)
         self.scheduler = None
         self.opt_init_lr = None
@@ -1079,7 +1100,10 @@ class SAT(SATDecoder, _Base):
                         (no_decay if p.dim() == 1 else decay).append(p)
             return [{"params": no_decay, "lr": lr, "weight_decay": 0.0}, {"params": decay, "lr": lr, "weight_decay": weight_decay}]
 
-        params = groups([self.init_lstm, self.lstm, self.attention, self.beta, self.output], hp.weight_decay, hp.decoder_lr)
+        dec = [self.init_lstm, self.lstm, self.attention, self.beta, self.output]
+        if self.lstm_layer_norm_on():                       # gains and shifts are 1-D: the decoder's no-decay group
+            dec.insert(2, self.lstm_ln)
+        params = groups(dec, hp.weight_decay, hp.decoder_lr)
         if hp.embedding_lr > 0 and not hp.weight_tying:
             params += [{"params": self.embedding.parameters(), "lr": hp.embedding_lr, "weight_decay": 0.0}]
         if hp.encoder_finetune_after > 0 and hp.encoder_lr > 0:          # F10: mirrored as written

@@ -337,3 +337,25 @@ class LSTM(nn.LSTM):
                 inp = hs[l]
             outs.append(inp)
         return torch.stack(outs, 0), (torch.stack(hs, 0), torch.stack(cs, 0))
+
+
+class _LayerNormParams(nn.Module):
+    """gain (ones) and shift (zeros) of one layer norm over ``width`` units, under nn.LayerNorm's parameter names"""
+
+    def __init__(self, width):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(width, dtype=torch.float32))
+        self.bias = nn.Parameter(torch.zeros(width, dtype=torch.float32))
+
+
+class LSTMLayerNorm(nn.Module):
+    """The parameters of the layer-normalised LSTM cell (``lstm_layer_norm``; Ba et al. 2016): per layer ``l``
+    ``gates_l{l}.weight`` / ``.bias`` (4n: the four gate norms side by side, i f g o) and ``cell_l{l}.weight`` / ``.bias`` (n).
+    It holds parameters only: the cell itself runs inside the decoder's step (``SATDecoder.train_decode`` and the searches)."""
+
+    def __init__(self, hidden_size, num_layers):
+        super().__init__()
+        self.hidden_size, self.num_layers = int(hidden_size), int(num_layers)
+        for l in range(self.num_layers):
+            setattr(self, "gates_l%d" % l, _LayerNormParams(4 * self.hidden_size))
+            setattr(self, "cell_l%d" % l, _LayerNormParams(self.hidden_size))
