@@ -1210,10 +1210,12 @@ typedef struct sat_opt_hyper {
     float bias_correction1;         /* 1 - beta1^step                                  */
     float bias_correction2_sqrt;    /* sqrt(1 - beta2^step)                            */
     float momentum;
-    float clip_value;               /* > 0: clamp every gradient element to [-v, v] (clip_grad_value_) */
+    float clip_value;               /* > 0: clamp every gradient element to [-v, v] (clip_grad_value_: +-inf become +-v, a NaN stays NaN) */
 } sat_opt_hyper;
 int32_t sat_optimizer_chunk_elems(void);
-/* coef[0] = min(1, max_norm / (||g||_2 + 1e-6)) over ALL tensors (clip_grad_norm_), coef[1] = the norm; fixed-order reduction */
+/* coef[0] = min(1, max_norm / (||g||_2 + 1e-6)) over ALL tensors (clip_grad_norm_), coef[1] = the norm; fixed-order reduction.
+ * Non-finite gradients as in torch: a NaN anywhere makes the norm AND the coefficient NaN, so the step that reads coef[0] writes NaN
+ * into every element of every tensor (a diverged run shows, it does not train on); an infinite norm gives coefficient 0.           */
 int sat_grad_clip_coef(const sat_opt_tensor* tensors, const sat_opt_chunk* chunks, int32_t n_chunks, float max_norm, double* scratch,
                        float* coef, void* stream);
 /* p, m, v updated in place from g * clip_coef[0] (clip_coef NULL = 1) */

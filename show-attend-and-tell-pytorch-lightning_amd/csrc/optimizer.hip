@@ -35,13 +35,20 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
     if (threadIdx.x == 0) {
         const float norm = (float)sqrt(sh[0]);
         const float c = max_norm / (norm + 1e-6f);
-        coef[0] = c < 1.f ? c : 1.f; coef[1] = norm;
+        coef[0] = c > 1.f ? 1.f : c; coef[1] = norm;          // a NaN norm hands on a NaN coefficient (clip_grad_norm_ does): the step then writes NaN
     }
 }
 
-__device__ __forceinline__ void opt_update(const sat_opt_hyper& h, float lr, float wd, float coef, float& p, float g, float& m, float& v) {
+// the gradient element both updates start from: scaled by the norm coefficient, then clipped by value as clip_grad_value_ clips it -
+// +-inf clamp to +-clip_value and NaN stays NaN (fminf / fmaxf return the other operand for a NaN, hence the select)
+__device__ __forceinline__ float clipped_grad(float g, float coef, float clip_value) {
     g *= coef;
-    if (h.clip_value > 0.f) g = fminf(fmaxf(g, -h.clip_value), h.clip_value);        // clip_grad_value_
+    if (clip_value > 0.f) g = (g != g) ? g : fminf(fmaxf(g, -clip_value), clip_value);
+    return g;
+}
+
+__device__ __forceinline__ void opt_update(const sat_opt_hyper& h, float lr, float wd, float coef, float& p, float g, float& m, float& v) {
+    g = clipped_grad(g, coef, h.clip_value);
     if (h.kind == SAT_OPT_SGD) {
         if (wd != 0.f) g = fmaf(wd, p, g);
         if (h.momentum != 0.f) {
@@ -69,9 +76,9 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(const sat_opt_tenso
     const float lr = t.lr, wd = t.weight_decay;
     const bool has_m = t.m != nullptr, has_v = t.v != nullptr;
     // 16 bytes per lane where the tensor allows it (chunk starts are multiples of 64 Ki elements; bases come 16-byte aligned
-    // from the allocator, checked here), scalar tail
+    // from the allocator, checked here; the bf16 copy is stored 8 bytes at a time), scalar tail
     const bool vec = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
-                       reinterpret_cast<uintptr_t>(t.v)) & 15) == 0;
+                       reinterpret_cast<uintptr_t>(t.v)) & 15) == 0 && (reinterpret_cast<uintptr_t>(t.shadow_bf16) & 7) == 0;
     long i = c.start;
     if (vec) {
         const long nv = (end - c.start) / 4;
@@ -108,8 +115,7 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(const sat_opt_tenso
 // pass that updates p.  A kernel of its own, so that a step without averaging launches exactly the kernel above.
 // torch.optim.ASGD (single-tensor form): g += wd * p;  p *= 1 - lambd * eta;  p -= eta * g  (eta travels in the table's lr field)
 __device__ __forceinline__ void asgd_update(const sat_opt_hyper& h, float lambd, float eta, float wd, float coef, float& p, float g) {
-    g *= coef;
-    if (h.clip_value > 0.f) g = fminf(fmaxf(g, -h.clip_value), h.clip_value);
+    g = clipped_grad(g, coef, h.clip_value);
     if (wd != 0.f) g = fmaf(wd, p, g);
     p *= fmaf(-lambd, eta, 1.f);
     p = fmaf(-eta, g, p);
