@@ -398,7 +398,8 @@ static int launch_gemm_bf16_tile(const GemmArgs& g, int tile_mode, hipStream_t s
     k.wide_slab = (k.nsplit > 1 && g.N % 4 == 0 && al16(g.slab)) ? 1 : 0;
     k.tile_stats = nullptr;
     if (g.tile_rows) *g.tile_rows = 0;
-    if (g.tile_stats && g.tile_rows && g.c_bf16 && k.wide_store && !g.accumulate && !g.g.cls && !g.bn_x) { k.tile_stats = g.tile_stats; *g.tile_rows = tbm; }
+    // (no epilogue function: both write-outs take the statistics from the raw accumulator, in front of ep_value - they would be those of the un-biased values)
+    if (g.tile_stats && g.tile_rows && g.c_bf16 && k.wide_store && !g.accumulate && !g.g.cls && !g.bn_x && g.epi == EPI_NONE) { k.tile_stats = g.tile_stats; *g.tile_rows = tbm; }
     // BatchNorm-backward statistics of a data-gradient launch (accumulating launches included: the statistics see the final values)
     if (g.tile_stats && g.tile_rows && g.bn_x && g.bn_mean && g.bn_invstd && g.c_bf16 && k.wide_store && k.nsplit == 1 && !g.g.cls && g.ldc == g.N &&
         g.epi == EPI_NONE && al16(g.bn_x) && BMt != 256) {
