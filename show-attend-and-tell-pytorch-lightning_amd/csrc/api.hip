@@ -42,6 +42,10 @@ int sat_debug_option(const char* name, int32_t value) {
     if (!strcmp(name, "bn_onepass")) { dev_switch(SW_BN_ONEPASS) = value; return SAT_OK; }
     if (!strcmp(name, "wide_tiles")) { dev_switch(SW_WIDE_TILES) = value; return SAT_OK; }
     if (!strcmp(name, "glds_tile")) { glds_force_tile() = value; return SAT_OK; }
+    if (!strcmp(name, "glds_stages")) { glds_force_stages() = value; return SAT_OK; }
+    if (!strcmp(name, "glds_stages_tr_bf16")) { glds_stages_tr_bf16() = value; return SAT_OK; }
+    if (!strcmp(name, "glds_stages_f32")) { glds_stages_f32() = value; return SAT_OK; }
+    if (!strcmp(name, "w3_stages")) { w3_stages() = value; return SAT_OK; }
     if (!strcmp(name, "glds_stages8")) { glds_stages8() = value; return SAT_OK; }
     if (!strcmp(name, "glds_tall_k")) { glds_tall_k() = value; return SAT_OK; }
     if (!strcmp(name, "glds_tall_conv")) { glds_tall_conv() = value; return SAT_OK; }

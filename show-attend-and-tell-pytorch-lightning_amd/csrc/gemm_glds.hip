@@ -33,6 +33,10 @@ static int rung_tiles(const BArgs& k, int tile, hipStream_t st, int* bm_used) {
 
 int& glds_force_tile() { static int v = getenv("SAT_GLDS_TILE") ? atoi(getenv("SAT_GLDS_TILE")) : -1; return v; }
 int& glds_ablate() { static int v = 0; return v; }
+// ring depth by result type of the forms that transpose an operand out of LDS (the rule below; tools/ab_step.py varies them at run time)
+int& glds_stages_tr_bf16() { static int v = getenv("SAT_GLDS_STAGES_TR_BF16") ? atoi(getenv("SAT_GLDS_STAGES_TR_BF16")) : 1; return v; }
+int& glds_stages_f32() { static int v = getenv("SAT_GLDS_STAGES_F32") ? atoi(getenv("SAT_GLDS_STAGES_F32")) : 2; return v; }
+int& glds_force_stages() { static int v = getenv("SAT_GLDS_STAGES") ? atoi(getenv("SAT_GLDS_STAGES")) : 0; return v; }
 int& glds_tall_k() { static int v = getenv("SAT_GLDS_TALL_K") ? atoi(getenv("SAT_GLDS_TALL_K")) : 1 << 30; return v; }
 int& glds_tall_conv() { static int v = getenv("SAT_GLDS_TALL_CONV") ? atoi(getenv("SAT_GLDS_TALL_CONV")) : 1152; return v; }
 int& glds_stages8() { static int v = getenv("SAT_GLDS_STAGES8") ? atoi(getenv("SAT_GLDS_STAGES8")) : 0; return v; }
@@ -41,22 +45,21 @@ int& glds_stages8() { static int v = getenv("SAT_GLDS_STAGES8") ? atoi(getenv("S
 int launch_gemm_glds(const BArgs& k0, int amode, int bmode, int c_bf16, int BMt, hipStream_t st, int* bm_used) {
     const int force_tile = glds_force_tile();      // dev: force a tile form (enum above); SAT_GLDS_TILE or sat_debug_option("glds_tile", n)
     static const int off = getenv("SAT_NO_GLDS") ? atoi(getenv("SAT_NO_GLDS")) : 0;
-    static const int force_stages = getenv("SAT_GLDS_STAGES") ? atoi(getenv("SAT_GLDS_STAGES")) : 0;
+    const int force_stages = glds_force_stages();  // dev / tests: force the ring depth (1 .. 4, 0 = automatic); SAT_GLDS_STAGES or sat_debug_option("glds_stages", n)
     static const int deep_from = getenv("SAT_GLDS_DEEP_FROM") ? atoi(getenv("SAT_GLDS_DEEP_FROM")) : 1 << 30;
     static const int rotate = getenv("SAT_GLDS_ROT") ? atoi(getenv("SAT_GLDS_ROT")) : 1 << 20;     // 0: off; n: rotation window in k-tiles
     if (off) return -1;
     BArgs k = k0;
-    // ring depth: short reductions keep two stages (two workgroups per CU overlap each other); from `deep_from` k-tiles
-    // on, one workgroup per CU with three tiles in flight hides the HBM / L2 latency that a cold operand costs
     const int ktiles = cdiv(k.kchunk < k.K ? k.kchunk : k.K, 64);
-    // a single k-tile needs one stage: less LDS, a third workgroup per CU for the streaming 1x1 layers with 64 input channels
-    // short reductions into a bf16 result (<= 168 VGPRs): one stage leaves room for a third workgroup per CU, which hides more of
-    // the launch / load / store phases of these latency-bound tiles than the second stage does
-    // (round 3, with the 128 x 64 tiles: EVERY bf16-result launch keeps one stage - the resident workgroups hide each other's latencies better than
-    // a second stage of the same workgroup does: C2 21.26 -> 21.00 ms, C3 shard 14.19 -> 13.87, C4 shard 33.97 -> 33.79; fp32 results keep two
-    // stages: one stage everywhere is 0.2 ms slower at C2)
-    static const int s1_upto = getenv("SAT_GLDS_S1_UPTO") ? atoi(getenv("SAT_GLDS_S1_UPTO")) : 1 << 30;
-    k.nstage = force_stages ? force_stages : (ktiles >= deep_from ? 4 : ((ktiles == 1 || (c_bf16 && ktiles <= s1_upto)) ? 1 : 2));
+    // Ring depth.  A single k-tile needs one stage.  Beyond that: one stage for every bf16 result (the resident workgroups - four to six per
+    // CU - hide each other's load / MFMA / store phases better than a second stage of the same workgroup does), two for the fp32 results
+    // (weight gradients, on the second stream).  Re-measured once the ring of the transposing forms existed in the binary (fragment reads
+    // as inline asm, lds_frag.h; profiles/lds_ring_depth_sweep.txt): launch by launch the fp32-result forms are fastest with FOUR stages
+    // (tn 128x128 2.96 -> 2.39 ms per C2 step, tn 64x64 0.45 -> 0.27) and the bf16-result forms with one or two, but inside the step
+    // (tools/ab_step.py, base 19.25 ms) every deeper ring loses: bf16 results 2 / 3 stages 19.53 / 20.18, fp32 results 3 / 4 stages 19.32 /
+    // 19.56, one stage 19.33 - a deeper ring takes the LDS of the workgroups of the OTHER stream that share the CU.  The depths stay.
+    const int by_form = c_bf16 ? (bmode != B_ROW ? glds_stages_tr_bf16() : 1) : glds_stages_f32();
+    k.nstage = force_stages ? force_stages : (ktiles >= deep_from ? 4 : (ktiles == 1 ? 1 : by_form));
     k.rotate = rotate;
     if (k.nstage < 1) k.nstage = 1;
     if (k.nstage > 4) k.nstage = 4;

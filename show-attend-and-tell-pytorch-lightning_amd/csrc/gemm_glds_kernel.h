@@ -26,9 +26,11 @@
 #include <stdlib.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #pragma once
 #include "gemm_bf16_common.h"
+#include "lds_frag.h"
 #include "profile.h"
 
 #ifndef SAT_GLDS_ABLATE
@@ -341,50 +343,92 @@ __global__ __launch_bounds__(64 * WR * WC, (BM == 128 && BN == 64 && sizeof(TC) 
             const bool more = S > 1 && it + S - 1 < T;
             const __bf16* as = smem + cur * STAGE;
             const __bf16* bs = as + A_EL;
-            // fragments are double buffered in registers: the reads of k-step s+1 are in flight under the MFMAs of step s
-            bf16x8 af[2][TM], bf[2][TN];
-            auto load_frags = [&](int kk, bf16x8 (&fa)[TM], bf16x8 (&fb)[TN]) {
+            if constexpr (AK || BKM) {
+                // a transposing form: fragment reads as inline asm with hand-counted waits (lds_frag.h), double buffered in registers -
+                // the RD reads of k-step s+1 are in flight under the MFMAs of step s, so step s waits until only those are outstanding
+                constexpr int RD = (AK ? 2 : 1) * TM + (BKM ? 2 : 1) * TN;
+                constexpr int A_B = A_EL * 2;      // byte offset of the B tile in a stage
+                static_assert(A_B + (48 + 4) * BN * 2 < 65536 && (48 + 4) * BM * 2 < 65536, "fragment offsets must fit the ds offset field");
+                const unsigned sbase = lds_addr(smem) + (unsigned)(cur * (STAGE * 2));
+                unsigned a_ad[TM], b_ad[TN];
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    if (!AK) fa[i] = *reinterpret_cast<const bf16x8*>(as + a_off[i] + ((((kk >> 3) + lh) ^ a_sw[i]) << 3));
-                    else {
-                        const __bf16* p = as + a_off[i] + kk * BM;
-                        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p);
-                        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(p + 4 * BM));
-                        fa[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                for (int i = 0; i < TM; ++i) a_ad[i] = sbase + a_off[i] * 2;
+#pragma unroll
+                for (int j = 0; j < TN; ++j) b_ad[j] = sbase + b_off[j] * 2;
+                Frag fa[2][TM], fb[2][TN];
+                auto read_frags = [&](auto kc, Frag (&xa)[TM], Frag (&xb)[TN]) {
+                    constexpr int kk = decltype(kc)::value;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+                        if constexpr (AK) { xa[i].lo = lds_read_tr16<kk * BM * 2>(a_ad[i]); xa[i].hi = lds_read_tr16<(kk + 4) * BM * 2>(a_ad[i]); }
+                        else xa[i].q = lds_read_b128<0>(a_ad[i] + (((((kk >> 3) + lh) ^ a_sw[i]) << 3) * 2));
                     }
-                }
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (!BKM) fb[j] = *reinterpret_cast<const bf16x8*>(bs + b_off[j] + ((((kk >> 3) + lh) ^ b_sw[j]) << 3));
-                    else {
-                        const __bf16* p = bs + b_off[j] + kk * BN;
-                        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p);
-                        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(p + 4 * BN));
-                        fb[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    for (int j = 0; j < TN; ++j) {
+                        if constexpr (BKM) { xb[j].lo = lds_read_tr16<A_B + kk * BN * 2>(b_ad[j]); xb[j].hi = lds_read_tr16<A_B + (kk + 4) * BN * 2>(b_ad[j]); }
+                        else xb[j].q = lds_read_b128<A_B>(b_ad[j] + (((((kk >> 3) + lh) ^ b_sw[j]) << 3) * 2));
                     }
-                }
-            };
-            if (!(abl & 4) || it == 0) load_frags(0, af[0], bf[0]);
+                };
+                auto k_step = [&](auto kc) {
+                    constexpr int ks = decltype(kc)::value;
+                    constexpr bool ahead = ks + 1 < KB / 16;
+                    if constexpr (ahead) {
+                        if (!(abl & 4) || it == 0) read_frags(std::integral_constant<int, (ks + 1) * 16>{}, fa[(ks + 1) & 1], fb[(ks + 1) & 1]);
+                    }
+                    // this k-step's share of the next tile's LDS-DMA pieces, issued under the MFMAs
+                    if (more) {
 #pragma unroll
-            for (int ks = 0; ks < KB / 16; ++ks) {
-                if (ks + 1 < KB / 16 && (!(abl & 4) || it == 0)) load_frags((ks + 1) * 16, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
-                // this k-step's share of the next tile's LDS-DMA pieces, issued under the MFMAs
-                if (more) {
+                        for (int jj = (ks * G) / 4; jj < ((ks + 1) * G) / 4; ++jj) issue_piece(nxt, nxt, jj);          // G pieces spread over the four k-steps
+                    }
+                    lds_wait<ahead ? (RD < 15 ? RD : 15) : 0>();
+                    bf16x8 va[TM], vb[TN];
 #pragma unroll
-                    for (int jj = (ks * G) / 4; jj < ((ks + 1) * G) / 4; ++jj) issue_piece(nxt, nxt, jj);          // G pieces spread over the four k-steps
-                }
-                if constexpr (!(abl & 2)) {
+                    for (int i = 0; i < TM; ++i) { frag_landed<AK>(fa[ks & 1][i]); va[i] = frag_value<AK>(fa[ks & 1][i]); }
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) { frag_landed<BKM>(fb[ks & 1][j]); vb[j] = frag_value<BKM>(fb[ks & 1][j]); }
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
-                } else {
+                        for (int j = 0; j < TN; ++j) {
+                            if constexpr (!(abl & 2)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[i], vb[j], acc[i][j], 0, 0, 0);
+                            else keep_alive(va[i], vb[j]);
+                        }
+                };
+                if (!(abl & 4) || it == 0) read_frags(std::integral_constant<int, 0>{}, fa[0], fb[0]);
+                static_assert(KB / 16 == 4, "four k-steps per tile");
+                k_step(std::integral_constant<int, 0>{}); k_step(std::integral_constant<int, 1>{});
+                k_step(std::integral_constant<int, 2>{}); k_step(std::integral_constant<int, 3>{});
+            } else {
+                // both operands row-major: plain ds_read_b128 reads, which the compiler counts itself (it does not drain the ring for them);
+                // fragments are double buffered in registers: the reads of k-step s+1 are in flight under the MFMAs of step s
+                bf16x8 af[2][TM], bf[2][TN];
+                auto load_frags = [&](int kk, bf16x8 (&fa)[TM], bf16x8 (&fb)[TN]) {
 #pragma unroll
-                    for (int i = 0; i < TM; ++i)
+                    for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(as + a_off[i] + ((((kk >> 3) + lh) ^ a_sw[i]) << 3));
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) keep_alive(af[ks & 1][i], bf[ks & 1][j]);      // keep the fragment reads alive
+                    for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(bs + b_off[j] + ((((kk >> 3) + lh) ^ b_sw[j]) << 3));
+                };
+                if (!(abl & 4) || it == 0) load_frags(0, af[0], bf[0]);
+#pragma unroll
+                for (int ks = 0; ks < KB / 16; ++ks) {
+                    if (ks + 1 < KB / 16 && (!(abl & 4) || it == 0)) load_frags((ks + 1) * 16, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
+                    // this k-step's share of the next tile's LDS-DMA pieces, issued under the MFMAs
+                    if (more) {
+#pragma unroll
+                        for (int jj = (ks * G) / 4; jj < ((ks + 1) * G) / 4; ++jj) issue_piece(nxt, nxt, jj);          // G pieces spread over the four k-steps
+                    }
+                    if constexpr (!(abl & 2)) {
+#pragma unroll
+                        for (int i = 0; i < TM; ++i)
+#pragma unroll
+                            for (int j = 0; j < TN; ++j)
+                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < TM; ++i)
+#pragma unroll
+                            for (int j = 0; j < TN; ++j) keep_alive(af[ks & 1][i], bf[ks & 1][j]);      // keep the fragment reads alive
+                    }
                 }
             }
             if (more) advance_tile();

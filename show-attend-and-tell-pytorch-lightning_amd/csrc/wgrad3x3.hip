@@ -15,7 +15,10 @@
 // Split over pixel ranges (grid z) with fp32 partials in the caller's slab, combined by the fixed-order reduce kernel the other forms use.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "gemm_bf16_common.h"
+#include "lds_frag.h"
 #include "profile.h"
 
 namespace sat {
@@ -28,7 +31,8 @@ namespace {
 constexpr int W3_OOB = (int)0x80000000;
 constexpr int W3_WAVES = 9, W3_THREADS = 64 * W3_WAVES;
 constexpr int W3_MAXP = 4;          // LDS-DMA instructions per wave and k-tile, at most (33 pieces / 9 waves)
-constexpr int W3_STAGES = 3;        // LDS ring: two k-tiles in flight under the one being multiplied (128 VGPRs: one 9-wave workgroup per CU)
+constexpr int W3_STAGES = 3;        // LDS ring: two k-tiles in flight under the one being multiplied (132 VGPRs: one 9-wave workgroup per CU)
+constexpr int W3_MIN_STAGES = 2, W3_MAX_STAGES = 4;      // what sat_debug_option("glds_stages", n) may ask for (a stage is 21 - 33 KB)
 
 __device__ __forceinline__ i32x4 w3_rsrc(const void* base) {
     const unsigned long long b = reinterpret_cast<unsigned long long>(base);
@@ -46,10 +50,11 @@ struct W3Args {
     int per;                 // k-tiles per workgroup (grid.z = ceil(units / per))
     int HP;                  // halo pixels (nr + 2) * (W + 2), rounded up to a multiple of 8
     int Z;
+    int S;                   // stages of the LDS ring
 };
 
 __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(W3Args a) {
-    extern __shared__ __attribute__((aligned(1024))) __bf16 smem[];      // W3_STAGES x (dy tile 64 x 64 | halo HP x 64)
+    extern __shared__ __attribute__((aligned(1024))) __bf16 smem[];      // a.S x (dy tile 64 x 64 | halo HP x 64)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ci0 = blockIdx.x * 64, co0 = blockIdx.y * 64, bz = blockIdx.z;
     const int W = a.W, H = a.H, C = a.C, K = a.K, nr = a.nr, HW2 = W + 2;
@@ -135,46 +140,61 @@ __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(W3Args a) {
 #pragma unroll
     for (int j = 0; j < W3_MAXP; ++j) mine += p_on[j] ? 1 : 0;
     mine = __builtin_amdgcn_readfirstlane(mine);
+    const int S = a.S;
     if (u0 < u1) {
-        issue(0, u0);
-        if (u0 + 1 < u1) issue(1, u0 + 1);
-        int cur = 0, nxt = 2;
+        for (int t = 0; t < S - 1 && u0 + t < u1; ++t) issue(t, u0 + t);
+        int cur = 0, nxt = S - 1;
         for (int u = u0; u < u1; ++u) {
-            // tile u has landed when at most the pieces of tile u + 1 are still outstanding (counted wait: the newer tile stays in flight)
-            if (u + 1 < u1) {
-                if (mine == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else if (mine == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else if (mine == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // tile u has landed when at most the pieces of the `ahead` newer tiles are still outstanding (counted wait: they stay in flight)
+            const int ahead = min(u1 - 1 - u, S - 2);
+            switch (mine * ahead) {
+                case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+                case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+                case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+                case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+                case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+                default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (u + 2 < u1) issue(nxt, u + 2);        // the stage of tile u - 1: every wave has finished reading it (it passed the barrier)
-            const __bf16* st = smem + cur * STAGE;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                bf16x8 af[2], bf[2];
+            if (u + S - 1 < u1) issue(nxt, u + S - 1);        // the stage of tile u - 1: every wave has finished reading it (it passed the barrier)
+            // fragment reads as inline asm with hand-counted waits (lds_frag.h: the transpose-read builtin would drain the tile in flight),
+            // double buffered in registers: the eight reads of k-step s+1 are in flight under the MFMAs of step s
+            const unsigned sbase = lds_addr(smem) + (unsigned)(cur * STAGE * 2);
+            Frag fa[2][2], fb[2][2];
+            auto read_frags = [&](auto kc, Frag (&xa)[2], Frag (&xb)[2]) {
+                constexpr int ks = decltype(kc)::value;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const __bf16* p = st + a_off[i] + ks * 16 * 64;
-                    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p);
-                    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(p + 4 * 64));
-                    af[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    xa[i].lo = lds_read_tr16<ks * 16 * 64 * 2>(sbase + a_off[i] * 2);
+                    xa[i].hi = lds_read_tr16<(ks * 16 + 4) * 64 * 2>(sbase + a_off[i] * 2);
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(st + b_off[ks][0][j]));
-                    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(st + b_off[ks][1][j]));
-                    bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    xb[j].lo = lds_read_tr16<0>(sbase + b_off[ks][0][j] * 2);
+                    xb[j].hi = lds_read_tr16<0>(sbase + b_off[ks][1][j] * 2);
                 }
+            };
+            auto k_step = [&](auto kc) {
+                constexpr int ks = decltype(kc)::value;
+                if constexpr (ks + 1 < 4) read_frags(std::integral_constant<int, ks + 1>{}, fa[(ks + 1) & 1], fb[(ks + 1) & 1]);
+                lds_wait<(ks + 1 < 4) ? 8 : 0>();
+                bf16x8 af[2], bf[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) { frag_landed<true>(fa[ks & 1][i]); af[i] = frag_value<true>(fa[ks & 1][i]); }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) { frag_landed<true>(fb[ks & 1][j]); bf[j] = frag_value<true>(fb[ks & 1][j]); }
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-            }
-            cur = (cur + 1 == W3_STAGES) ? 0 : cur + 1;
-            nxt = (nxt + 1 == W3_STAGES) ? 0 : nxt + 1;
+            };
+            read_frags(std::integral_constant<int, 0>{}, fa[0], fb[0]);
+            k_step(std::integral_constant<int, 0>{}); k_step(std::integral_constant<int, 1>{});
+            k_step(std::integral_constant<int, 2>{}); k_step(std::integral_constant<int, 3>{});
+            cur = (cur + 1 == S) ? 0 : cur + 1;
+            nxt = (nxt + 1 == S) ? 0 : nxt + 1;
         }
     }
     // ---- write-out: dW[filter][tap][channel] (KRSC) or this split's slab; C/D layout: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -193,6 +213,8 @@ __global__ __launch_bounds__(W3_THREADS) void wgrad3x3_kernel(W3Args a) {
             }
 }
 }  // namespace
+
+int& w3_stages() { static int v = getenv("SAT_W3_STAGES") ? atoi(getenv("SAT_W3_STAGES")) : W3_STAGES; return v; }
 
 // 0 when the geometry is not this kernel's (the caller keeps the implicit-GEMM form)
 int wgrad3x3_eligible(const ConvGeom& g) {
@@ -221,10 +243,13 @@ int launch_wgrad3x3(const void* dy, const void* x, float* dw, const ConvGeom& g,
     while (z > 1 && (!slab || z * out_elems > slab_elems)) --z;
     a.per = (int)cdiv(a.units, z); a.Z = (int)cdiv(a.units, a.per);
     a.out = a.Z > 1 ? slab : dw;
-    const size_t lds = W3_STAGES * (size_t)(64 * 64 + a.HP * 64) * sizeof(__bf16);
+    const int forced = glds_force_stages();          // dev / tests: sat_debug_option("glds_stages", n)
+    const int want = forced ? forced : w3_stages();
+    a.S = want < W3_MIN_STAGES ? W3_MIN_STAGES : (want > W3_MAX_STAGES ? W3_MAX_STAGES : want);
+    const size_t lds = a.S * (size_t)(64 * 64 + a.HP * 64) * sizeof(__bf16);
     static bool attr_set = false;
     if (!attr_set) {
-        SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        SAT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
         attr_set = true;
     }
     {
